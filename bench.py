@@ -2,7 +2,7 @@
 """bench.py -- template/search pairs per second (forward + backward + Adam) of the BAT tracker
 at KITTI-Car shapes (template 512 / search 1024 points), BASELINE.json's metric.
 
-    python bench.py --gpus 1 --steps K --warmup W          (one MI355X)
+    python bench.py --gpus 1 --steps K --warmup W          (one MI355X; add --full for everything below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...        (no torchrun environment: spawns the N ranks itself, like the
                                          reference's `pl.Trainer(gpus=-1, accelerator='ddp')`, main.py:53-64,82)
@@ -11,12 +11,30 @@ One "step" = one full training step of the hot path on one synthetic batch of `-
 pairs PER GPU (weak scaling; default 48 = BASELINE config 2): FPS, ball queries, the fused
 grouped-MLP stack, BoxCloud xcorr, vote heads, losses, backward, the one-message RCCL
 gradient all-reduce and the Adam update.  Inputs are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line (contract in the task statement) that also carries
+region.  Rank 0 prints ONE JSON line: `metric`, `value` (pairs/s), `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (one timed step) and the configuration.  A plain run does only that: set
+up, warm up, time `--steps` steps, write the outputs (`--dump-outputs`), print the line.
+
+--dump-outputs DIR  after the timed steps, the model is put back to its seeded starting state
+                    (weights, BatchNorm buffers, optimizer) and one more step of the timed path
+                    (the same captured graph) runs on the first resident batch; what it computed
+                    is written as float32 .npy files: loss.npy (the loss step() returned),
+                    grads.npy (every parameter's gradient, flat, in named_parameters order),
+                    exp_avg.npy / exp_avg_sq.npy (Adam's moments after the update, same order),
+                    buffers.npy (the floating-point buffers: BatchNorm running statistics); with
+                    --infer out0.npy, out1.npy, ... (what the last replayed forward returned).
+                    Inputs are the same every run, so two runs or two builds can be compared
+                    file by file.  (The state the timed steps leave behind is not written: the
+                    step's reductions use floating-point atomics, and training amplifies their
+                    rounding from step to step.)
+--full              also measures:
   "roofline"     -- the dominant kernel family (fp32-MFMA grouped-MLP GEMMs) measured live
                     with HIP events on the launch stream: algorithmic FLOPs / time vs the
-                    157.3 TFLOP/s dense fp32 matrix peak of gfx950;
+                    157.3 TFLOP/s dense fp32 matrix peak of gfx950 (`--per-launch FILE`: the
+                    per-launch table);
   "cpu_baseline" -- the oracle's PyTorch restatement of the same step timed on this host's
-                    cores on a bounded sample (kind "port": the reference has no CPU path).
+                    cores on a bounded sample (kind "port": the reference has no CPU path);
+  "secondary"    -- short lines of the other BASELINE configs (default configuration only).
 """
 import argparse
 import json
@@ -41,6 +59,10 @@ PEAK_HBM_GBS = 8000.0
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, the CPU baseline and the secondary "
+                    "lines (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timing, run one step of the timed "
+                    "path from the seeded starting state and write what it computed to DIR/<name>.npy (float32)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=48, help="pairs per GPU (BASELINE config 2: 48)")
@@ -65,7 +87,61 @@ def parse():
                     "(DataParallelStep(exchange=True)); prices the exchange path's per-step overhead on a one-GPU box")
     ap.add_argument("--composed", action="store_true", help="disable the fused kernels (debug A/B only)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying one HIP graph")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.per_launch and not args.full:
+        ap.error("--per-launch is part of the roofline measurement: add --full")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(path, arrays):
+    """arrays {name: tensor} -> path/<name>.npy in float32; when they exceed DUMP_LIMIT_BYTES together, a fixed seeded
+    sample of each (the same share of every array, sorted flat indices)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * DUMP_LIMIT_BYTES / total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def snapshot(model, optimizer):
+    """copies of the parameters, buffers and optimizer state, for restore()"""
+    import copy
+    return ([t.detach().clone() for t in list(model.parameters()) + list(model.buffers())],
+            copy.deepcopy(optimizer.state_dict()))
+
+
+def restore(model, optimizer, snap):
+    """back to a snapshot() in place: a captured graph keeps reading the same parameter and buffer storage"""
+    import copy
+    tensors, opt_state = snap
+    with torch.no_grad():
+        for t, v in zip(list(model.parameters()) + list(model.buffers()), tensors):
+            t.copy_(v)
+    optimizer.load_state_dict(copy.deepcopy(opt_state))
+
+
+def step_outputs(model, optimizer, loss):
+    """what one training step leaves its caller: the loss, the parameters' gradients, Adam's two moments after the update
+    and the BatchNorm running statistics.  (Not the updated parameters: Adam's first step moves each by lr * g / (|g| +
+    eps), which turns the rounding of near-zero gradients -- biases in front of a BatchNorm, whose exact gradient is 0 --
+    into differences of up to lr; the moments carry the same update kernel's results without that division.)"""
+    params = list(model.parameters())
+    flat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts])
+    out = {"loss": loss.reshape(-1),
+           "grads": flat(p.grad if p.grad is not None else torch.zeros_like(p) for p in params),
+           "buffers": flat(b for b in model.buffers() if b.is_floating_point())}
+    for k in ("exp_avg", "exp_avg_sq"):
+        out[k] = flat(optimizer.state[p][k] if k in optimizer.state.get(p, {}) else torch.zeros_like(p) for p in params)
+    return out
 
 
 def mlp_flops_per_pair(model_name):
@@ -155,12 +231,16 @@ def cpu_baseline(model_name, sd, batch_size, budget_s=150.0):
     has no CPU path).  More threads than the problem has parallel work THRASH (round 1's 128-thread figure was 4x slower
     than 8 threads), so the thread count is swept on a batch-8 probe first; the best count then runs the bench batch
     itself -- SURVEY.md section 8d: 3 warm-up (2 when the budget is short) + >= 10 timed iterations, median -- and batch 1
-    (3 + 10); last, the process-parallel figure over all physical cores (cpu_process_parallel)."""
+    (3 + 10); last, the process-parallel figure over all cores it may use (cpu_process_parallel)."""
     try:
         import psutil
-        cores = psutil.cpu_count(logical=False) or os.cpu_count() or 1
+        physical = psutil.cpu_count(logical=False) or os.cpu_count() or 1
     except ImportError:
-        cores = os.cpu_count() or 1
+        physical = os.cpu_count() or 1
+    # the cores this process may use: the affinity mask, and OMP_NUM_THREADS where the host sets a share of its cores
+    cores = min(physical, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else physical)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        cores = min(cores, int(os.environ["OMP_NUM_THREADS"]))
     t_begin = time.perf_counter()
     step = _cpu_step_fn(model_name, sd)
     probe = [synth.to_torch(synth.make_batch(5000 + 8 * i, 8)) for i in range(2)]
@@ -187,10 +267,10 @@ def cpu_baseline(model_name, sd, batch_size, budget_s=150.0):
     vfull, nfull = sample(batch_size, 2, 10, t_begin + 0.7 * budget_s)
     v1, n1 = sample(1, 3, 10, t_begin + 0.75 * budget_s)
     par = None
-    if cores >= 16:      # every physical core: 8 processes x cores/8 threads (its own time limit: 1 warm-up + 2 steps each, all
+    if cores >= 16:      # every available core: 8 processes x cores/8 threads (its own time limit: 1 warm-up + 2 steps each, all
         par = cpu_process_parallel(model_name, sd, batch_size, cores // 8, cores, timeout_s=180.0)      # processes at once)
     res = {"value": round(vfull, 3), "unit": "pairs/s", "cores": best, "kind": "port",
-           "batch1_value": round(v1, 3), "host_physical_cores": cores, "thread_sweep_batch8_pairs_per_s": sweep,
+           "batch1_value": round(v1, 3), "host_physical_cores": physical, "cores_available": cores, "thread_sweep_batch8_pairs_per_s": sweep,
            "timed_iterations": nfull,
            "sample": "%s fwd+bwd+Adam on oracle/torch_ref.py (C index ops + PyTorch fp32 CPU convs); threads swept on a "
                      "batch-8 probe, the best (%d threads) timed on batch %d: median of %d iterations after 2 warm-up; "
@@ -307,6 +387,8 @@ def run_infer(args):
         g.replay()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"out%d" % i: t for i, t in enumerate(out)})
     return {
         "metric": "tracked frames/sec (eval forward, %s KITTI-Car %s, batch %d)" % (model.__class__.__name__, shapes, B),
         "value": round(B / ms * 1e3, 1), "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -334,8 +416,8 @@ def run(args):
                          (args.gpus, world, args.gpus))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP library is the only compute path (no CPU fallback)")
-    line = measure(args, rank, local_rank, world, full=True)
-    if rank == 0:
+    line = measure(args, rank, local_rank, world, full=args.full)
+    if rank == 0 and args.full:
         default_cfg = (args.model == "BAT" and not args.dense and args.search_size == 1024 and world == 1 and
                        not args.composed and not args.no_graph)
         if default_cfg and not args.no_secondary:
@@ -366,7 +448,7 @@ def secondary_lines(args):
 
     def one(tag, **over):
         a = copy.copy(args)
-        a.steps, a.warmup, a.no_cpu_baseline, a.per_launch = args.secondary_steps, 5, True, None
+        a.steps, a.warmup, a.no_cpu_baseline, a.per_launch, a.dump_outputs = args.secondary_steps, 5, True, None, None
         over = dict(over)
         a.full = over.pop("full", False)
         for k, v in over.items():
@@ -411,7 +493,7 @@ def secondary_lines(args):
 
 def measure(args, rank, local_rank, world, full=True):
     """one timed run of the training step described by `args`; -> the JSON line as a dict (rank 0; {} elsewhere).
-    full=False: no roofline instrumentation and no CPU baseline (the `secondary` lines)."""
+    full=False: no roofline instrumentation and no CPU baseline (a plain run, and the `secondary` lines)."""
     dev = torch.device("cuda", local_rank)
     from open3dsot_amd import capi, sa_modules
     capi.load()
@@ -439,6 +521,9 @@ def measure(args, rank, local_rank, world, full=True):
         D.init_distributed(force=True)          # a one-rank RCCL communicator
     trainer = D.DataParallelStep(model, world=world, graph=not args.no_graph, graph_warmup=2,
                                  exchange=True if exchange else None)
+    # --dump-outputs: the seeded state the model starts from (weights, BatchNorm buffers, optimizer), put back before
+    # the step whose results are written
+    start = snapshot(model, trainer.optimizer) if args.dump_outputs else None
 
     # resident synthetic batches (distinct per rank and per pool slot)
     pool = []
@@ -473,11 +558,20 @@ def measure(args, rank, local_rank, world, full=True):
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        trainer.step(pool[i % len(pool)], next_batch=pool[(i + 1) % len(pool)])
+        loss = trainer.step(pool[i % len(pool)], next_batch=pool[(i + 1) % len(pool)])
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
     log("timed %d steps: %.3f s" % (args.steps, elapsed))
+    if args.dump_outputs:      # (every rank: the step holds the gradient all-reduce)
+        # the reductions of the step use floating-point atomics, so the state the timed steps leave behind differs from
+        # run to run by more than rounding (a few steps of training amplify it).  The written step therefore starts from
+        # the seeded state: one more step of the timed path (the same captured graph) on the first resident batch
+        restore(model, trainer.optimizer, start)
+        loss = trainer.step(pool[0])
+        torch.cuda.synchronize()
+        if rank == 0:
+            write_outputs(args.dump_outputs, step_outputs(model, trainer.optimizer, loss))
     multi = None
     if world > 1:
         # self-checks of the multi-GPU run (the driver computes the scaling efficiency itself; these only say whether the
@@ -590,8 +684,9 @@ def measure(args, rank, local_rank, world, full=True):
                        "global_batch": world * args.batch, "parallelism": "dp%d" % world,
                        "fused_kernels": bool(sa_modules.fused_enabled()),
                        "hip_graph": trainer.graph is not None},      # (false = the capture failed and the step ran eagerly: see graph_error)
-            "roofline": roofline,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if full and not args.no_cpu_baseline and world == 1 and args.search_size == 1024:
             line["cpu_baseline"] = cpu_baseline(args.model, sd_cpu, args.batch, args.cpu_budget)
         if trainer.graph is None and not args.no_graph:

@@ -6,6 +6,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import fixture_io  # noqa: E402
 
 
 def pytest_configure(config):
@@ -14,8 +16,7 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_python_layers.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_python_layers.npz"))
 
 
 @pytest.fixture(scope="session")

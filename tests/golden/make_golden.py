@@ -20,6 +20,8 @@ import sys
 import numpy as np
 import torch
 
+import fixture_io
+
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 REF = "/root/reference"
 sys.path.insert(0, ROOT)
@@ -145,8 +147,8 @@ def main():
             fix["rpn.%s.%s" % (mode, nm)] = t.detach().numpy()
 
     path = os.path.join(OUT, "ref_python_layers.npz")
-    np.savez_compressed(path, **{k: (v.astype(np.float32) if v.dtype == np.float64 else v) for k, v in fix.items()})
-    print("wrote", path, "%.1f MB" % (os.path.getsize(path) / 1e6), len(fix), "arrays")
+    written = fixture_io.save(path, **{k: (v.astype(np.float32) if v.dtype == np.float64 else v) for k, v in fix.items()})
+    print("wrote", path, "%.1f MB" % (sum(os.path.getsize(p) for p in written) / 1e6), len(fix), "arrays")
 
 
 if __name__ == "__main__":

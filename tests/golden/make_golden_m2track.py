@@ -16,6 +16,8 @@ import types
 import numpy as np
 import torch
 
+import fixture_io
+
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 REF = "/root/reference"
 sys.path.insert(0, ROOT)
@@ -116,8 +118,8 @@ def main():
     fix["box.offset_box"] = points_utils.get_offset_box_tensor(ref_box, off_box).numpy()
     fix["box.remove_transform"] = points_utils.remove_transform_points_tensor(pts.clone(), ref_box).numpy()
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_m2track.npz")
-    np.savez_compressed(path, **fix)
-    print("wrote", path, "%.1f MB" % (os.path.getsize(path) / 1e6), len(fix), "arrays")
+    written = fixture_io.save(path, **fix)
+    print("wrote", path, "%.1f MB" % (sum(os.path.getsize(p) for p in written) / 1e6), len(fix), "arrays")
     # ---- round 4: the same reference model (the state dict above) at the BENCHMARKED batch of 48 frame pairs.  The twelve
     # Linear -> BatchNorm1d -> ReLU rows of the heads normalise over the batch: over 8 samples a 1e-7 difference of a pooled
     # feature moves a normalised value by 1e-4 (the bounds of the batch-8 fixture reflect that, not the kernels); over 48 the
@@ -141,8 +143,8 @@ def main():
                 if "running" in k:
                     fix2["train.sd_after." + k] = v.detach().numpy().copy()
     path2 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_m2track_b48.npz")
-    np.savez_compressed(path2, **fix2)
-    print("wrote", path2, "%.1f MB" % (os.path.getsize(path2) / 1e6), len(fix2), "arrays")
+    written = fixture_io.save(path2, **fix2)
+    print("wrote", path2, "%.1f MB" % (sum(os.path.getsize(p) for p in written) / 1e6), len(fix2), "arrays")
     # ---- round 5: the fp64 YARDSTICK of both fixtures (third file; the two above stay byte-identical).  The same reference
     # model evaluated in double precision on the same inputs, with its two hard-mask decisions (`torch.argmax` of the
     # segmentation logits per point and of the motion-state logits per cloud, models/m2track.py:95,113) REPLAYED from the
@@ -196,8 +198,8 @@ def main():
                     if "running" in k:
                         fix3["%s.train.sd_after.%s" % (tag, k)] = v.detach().numpy().copy()
     path3 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_m2track_f64.npz")
-    np.savez_compressed(path3, **fix3)
-    print("wrote", path3, "%.1f MB" % (os.path.getsize(path3) / 1e6), len(fix3), "arrays")
+    written = fixture_io.save(path3, **fix3)
+    print("wrote", path3, "%.1f MB" % (sum(os.path.getsize(p) for p in written) / 1e6), len(fix3), "arrays")
 
 
 if __name__ == "__main__":

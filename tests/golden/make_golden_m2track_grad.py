@@ -47,6 +47,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import fixture_io  # noqa: E402
 import make_golden_m2track as base  # noqa: E402  (installs the stubs, loads the reference modules; does not run main())
 
 from open3dsot_amd import m2track as ours, synth  # noqa: E402
@@ -56,7 +57,7 @@ FULL_LIMIT, SAMPLE = 40000, 32768
 
 def reference_model():
     from types import SimpleNamespace
-    gold = np.load(os.path.join(HERE, "ref_m2track.npz"))
+    gold = fixture_io.load(os.path.join(HERE, "ref_m2track.npz"))
     torch.manual_seed(77)
     net = base.ref_m2.M2TRACK(SimpleNamespace(**ours.M2_KITTI))
     net.load_state_dict({k[3:]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith("sd.")}, strict=True)
@@ -151,8 +152,8 @@ def main():
               "max %.2e (keys above 1e-6 of the whole norm: %d of %d)" % (tag, loss32, loss64, gn, whole, float(np.median(live)),
                                                                         max(live), len(live), len(yard)))
     path = os.path.join(HERE, "ref_m2track_grad.npz")
-    np.savez_compressed(path, **fix)
-    print("wrote", path, "%.2f MB" % (os.path.getsize(path) / 1e6), len(fix), "arrays")
+    written = fixture_io.save(path, **fix)
+    print("wrote", path, "%.2f MB" % (sum(os.path.getsize(p) for p in written) / 1e6), len(fix), "arrays")
 
 
 if __name__ == "__main__":

@@ -35,6 +35,7 @@ from oracle import ext_shim  # noqa: E402
 shim = ext_shim.install()
 sys.path.insert(0, REF)
 import det_init  # noqa: E402
+import fixture_io  # noqa: E402
 from open3dsot_amd import synth, trackers  # noqa: E402
 
 B, M, N, SEED0 = 8, 512, 1024, 4100
@@ -152,5 +153,5 @@ for name in ("BAT", "P2B"):
     print(name, "loss32 %.6f loss64 %.6f | reference fp32 gradient vs its fp64 truth: whole %.2e, per-key median %.2e max %.2e"
           % (r32["loss"], r64["loss"], whole, float(np.median(list(yard.values()))), max(yard.values())))
 path = os.path.join(ROOT, "tests", "golden", "ref_trackers_b8.npz")
-np.savez_compressed(path, **out)
-print("wrote", path, "%.2f MB" % (os.path.getsize(path) / 1e6), len(out), "arrays")
+written = fixture_io.save(path, **out)
+print("wrote", path, "%.2f MB" % (sum(os.path.getsize(p) for p in written) / 1e6), len(out), "arrays")

@@ -41,9 +41,17 @@ def _data(first, n):
     return {"x": x, "y": x.sum(1) * 0.3}
 
 
+def _cpu_rank():
+    """the gloo ranks compute on the CPU: on a host with one GPU, rank 1 must not select a second device.  The devices are
+    hidden before anything in the rank starts the GPU runtime (which reads these variables once, at start-up)"""
+    os.environ["HIP_VISIBLE_DEVICES"] = os.environ["CUDA_VISIBLE_DEVICES"] = "-1"
+    assert not torch.cuda.is_available()
+
+
 def _worker(rank, world, port, out):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    _cpu_rank()
     from open3dsot_amd import dist as D
     r, _, w = D.init_distributed("gloo")
     torch.manual_seed(100 + rank)         # different init per rank: broadcast must fix it
@@ -172,6 +180,7 @@ def _bat_model(seed):
 def _bat_worker(rank, world, port, out):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    _cpu_rank()
     torch.set_num_threads(2)
     _patch_ext_with_oracle()
     from open3dsot_amd import dist as D
@@ -233,6 +242,7 @@ def test_two_rank_gloo_real_tracker(tmp_path):
 def _m2_worker(rank, world, port, out):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    _cpu_rank()
     torch.set_num_threads(2)
     from open3dsot_amd import dist as D, m2track, synth
     r, _, w = D.init_distributed("gloo")

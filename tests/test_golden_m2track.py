@@ -5,18 +5,21 @@ product's mirror (open3dsot_amd/m2track.py, backbone.py, box_utils.py) loads the
 with strict=True and must reproduce outputs, losses and BatchNorm running statistics, on the module-by-
 module path and on the flat-GEMM path of the per-point stacks."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import fixture_io  # noqa: E402
 TOL = dict(rtol=2e-4, atol=2e-5)
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track.npz"))
 
 
 def build(gold, train):
@@ -120,7 +123,7 @@ def test_rotz_as_one_gemm_is_the_stacked_matrix_bit_for_bit():
 
 @pytest.fixture(scope="module")
 def gold64():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_f64.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_f64.npz"))
 
 
 def scale_err(a, b):
@@ -212,7 +215,7 @@ def assert_grads_within_fp64_yardstick(named_grads, goldg, tag, report=None):
 
 @pytest.fixture(scope="module")
 def goldg():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_grad.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_grad.npz"))
 
 
 class replay_hard_masks:
@@ -340,7 +343,7 @@ def test_m2track_flat_path_gradients_within_the_references_fp64_yardstick(gold, 
 
 @pytest.fixture(scope="module")
 def gold48():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_b48.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_b48.npz"))
 
 
 @pytest.mark.parametrize("mode", ["train", "eval"])

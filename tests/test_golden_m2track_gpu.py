@@ -2,28 +2,31 @@
 own model: tests/golden/ref_m2track.npz holds what /root/reference/models/m2track.py produced (forward, compute_loss,
 BatchNorm running statistics; tests/golden/make_golden_m2track.py).  GPU twin of tests/test_golden_m2track.py."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import fixture_io  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track.npz"))
 
 
 @pytest.fixture(scope="module")
 def gold48():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_b48.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_b48.npz"))
 
 
 @pytest.fixture(scope="module")
 def gold64():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_f64.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_f64.npz"))
 
 
 @pytest.mark.parametrize("mode", ["train", "eval"])
@@ -70,7 +73,7 @@ def test_gpu_m2track_within_the_references_fp64_yardstick(gold, gold48, gold64, 
 
 @pytest.fixture(scope="module")
 def goldg():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_grad.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_m2track_grad.npz"))
 
 
 @pytest.mark.parametrize("tag", ["b8", "b48", "b48x2048"])

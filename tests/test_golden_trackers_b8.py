@@ -22,11 +22,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import det_init  # noqa: E402
+import fixture_io  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(ROOT, "tests", "golden", "ref_trackers_b8.npz"))
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_trackers_b8.npz"))
 
 
 def rel(a, b):

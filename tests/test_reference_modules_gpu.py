@@ -107,9 +107,10 @@ def test_reference_tracker_class_trains_over_hip_ext(ref_layers, name):
     unchanged", executed."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
     import det_init
+    import fixture_io
     import ref_stubs
     from open3dsot_amd import synth, trackers
-    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_trackers_b8.npz"))
+    gold = fixture_io.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_trackers_b8.npz"))
     B, M, N, seed0, wseed = [int(v) for v in gold["meta.shape"]]
     sys.path.insert(0, REF)
     try:

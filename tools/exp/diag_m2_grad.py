@@ -14,9 +14,9 @@ import torch
 import test_golden_m2track as T
 from open3dsot_amd import backbone, box_utils, fused_loss, fused_pointwise, fused_rows, m2track, nn_blocks
 
-gold = np.load(os.path.join(ROOT, "tests/golden/ref_m2track.npz"))
-gold48 = np.load(os.path.join(ROOT, "tests/golden/ref_m2track_b48.npz"))
-goldg = np.load(os.path.join(ROOT, "tests/golden/ref_m2track_grad.npz"))
+gold = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track.npz"))
+gold48 = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track_b48.npz"))
+goldg = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track_grad.npz"))
 
 
 def run(tag, label, dev="cuda"):

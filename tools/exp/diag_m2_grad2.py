@@ -13,9 +13,9 @@ import torch
 import test_golden_m2track as T
 from open3dsot_amd import backbone, m2track
 
-gold = np.load(os.path.join(ROOT, "tests/golden/ref_m2track.npz"))
-gold48 = np.load(os.path.join(ROOT, "tests/golden/ref_m2track_b48.npz"))
-goldg = np.load(os.path.join(ROOT, "tests/golden/ref_m2track_grad.npz"))
+gold = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track.npz"))
+gold48 = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track_b48.npz"))
+goldg = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track_grad.npz"))
 tag = "b48x2048"
 keys = ["box_mlp.6.weight", "box_mlp.6.bias", "box_mlp.4.weight", "box_mlp.3.weight", "box_mlp.1.weight", "box_mlp.0.weight",
         "mini_pointnet2.features.17.weight", "mini_pointnet2.features.14.weight", "mini_pointnet2.features.9.weight",

@@ -12,9 +12,9 @@ import torch
 import test_golden_m2track as T
 from open3dsot_amd import backbone, fused_rows, m2track
 
-gold = np.load(os.path.join(ROOT, "tests/golden/ref_m2track.npz"))
-gold48 = np.load(os.path.join(ROOT, "tests/golden/ref_m2track_b48.npz"))
-goldg = np.load(os.path.join(ROOT, "tests/golden/ref_m2track_grad.npz"))
+gold = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track.npz"))
+gold48 = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track_b48.npz"))
+goldg = T.fixture_io.load(os.path.join(ROOT, "tests/golden/ref_m2track_grad.npz"))
 tag = "b48x2048"
 fused_rows.set_fused_rows(False)
 cap = {}

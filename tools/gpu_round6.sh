@@ -45,11 +45,11 @@ if has pmc; then
   [ -f $OUT/hbm_traffic.json ] && cp $OUT/hbm_traffic.json $REPO/profiles/hbm_traffic.json
 fi
 if has bench; then
-  timeout 1200 python bench.py --per-launch $OUT/per_launch_roofline_bat.txt > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
+  timeout 1200 python bench.py --full --per-launch $OUT/per_launch_roofline_bat.txt > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
   tail -3 $OUT/bench.err | cut -c1-300
 fi
 if has qbench; then
-  timeout 600 python bench.py --no-cpu-baseline --no-secondary --per-launch $OUT/per_launch_roofline_bat.txt > $OUT/bench.json 2> $OUT/bench.err; echo "qbench exit $?"
+  timeout 600 python bench.py --full --no-cpu-baseline --no-secondary --per-launch $OUT/per_launch_roofline_bat.txt > $OUT/bench.json 2> $OUT/bench.err; echo "qbench exit $?"
   tail -2 $OUT/bench.err | cut -c1-300
 fi
 for p in $PARTS; do case "$p" in hook:*)     # hook:<module>.<dict>.<key>[:MODEL] -> same-box A/B of a test hook (tools/ab_hook.py)
@@ -84,7 +84,7 @@ for p in $PARTS; do case "$p" in m:*)
   [ -n "$G" ] && python tools/trace_families.py $OUT/steady_state_per_step_$ML.txt > $OUT/steady_state_families_$ML.txt 2>/dev/null
   rm -rf $OUT/trace_$ML
   head -3 $OUT/steady_state_per_step_$ML.txt | cut -c1-200
-  timeout 300 python bench.py --model $M --no-cpu-baseline --no-secondary --per-launch $OUT/per_launch_roofline_$ML.txt > $OUT/bench_$ML.json 2> $OUT/bench_$ML.err; echo "bench $M exit $?" ;;
+  timeout 300 python bench.py --model $M --full --no-cpu-baseline --no-secondary --per-launch $OUT/per_launch_roofline_$ML.txt > $OUT/bench_$ML.json 2> $OUT/bench_$ML.err; echo "bench $M exit $?" ;;
 esac; done
 if has sq; then
   cd /tmp

@@ -7,4 +7,4 @@ cd $REPO
 S1=$(find $OUT/pmc_sq1 -name "*counter_collection.csv" | head -1); S2=$(find $OUT/pmc_sq2 -name "*counter_collection.csv" | head -1)
 python tools/sq_summary.py "$S1" "$S2" $OUT/sq_counters_dense.csv
 rm -rf $OUT/pmc_sq1 $OUT/pmc_sq2
-timeout 300 python bench.py --dense --no-cpu-baseline --no-secondary --per-launch $OUT/per_launch_roofline_dense.txt > $OUT/bench_dense.json 2>/dev/null
+timeout 300 python bench.py --dense --full --no-cpu-baseline --no-secondary --per-launch $OUT/per_launch_roofline_dense.txt > $OUT/bench_dense.json 2>/dev/null
