@@ -676,6 +676,41 @@ int o3d_m2track_loss(const float* seg_logits, const int64_t* seg_label, const fl
 int o3d_boxcloud(const float* points, const float* center, const float* wlh, const float* rot, float wlh_factor,
                  int B, int N, float* out, void* stream);
 
+/* ---- the tracking front end (csrc/track.hip): crop, resample and box update of a tracked sequence on the device --------
+ * A box is 15 floats: centre (3), wlh = width, length, height (3), row-major rotation matrix (9).
+ *
+ * o3d_track_crop: up to O3D_CROP_MAX_JOBS box crops with order-preserving compaction in two launches.  Job: the n points
+ * (n,3) kept by `box` (scale, offset) are written, expressed in the frame of the box and in their original order, to out
+ * (capacity,3); count[0] = the number kept (survivors beyond `capacity` are counted, not written).  mode O3D_CROP_SUBWINDOW:
+ * generate_subwindow(oriented=True) (datasets/points_utils.py:218-250); O3D_CROP_MODEL: cropAndCenterPC (:103-124).  The
+ * fp32 operation order is fixed and written down at the head of csrc/track.hip.  `jobs` is a HOST table; scratch: at least
+ * o3d_track_crop_scratch(jobs, n_jobs) int32 on the device (one per workgroup of 256 points; -1: bad table). */
+#define O3D_CROP_MAX_JOBS 4
+#define O3D_CROP_SUBWINDOW 0
+#define O3D_CROP_MODEL 1
+typedef struct {
+    const float* points; int n; const float* box; float scale, offset; int mode; float* out; int capacity; int32_t* count;
+} o3d_crop_job;
+long o3d_track_crop_scratch(const o3d_crop_job* jobs, int n_jobs);
+int o3d_track_crop(const o3d_crop_job* jobs, int n_jobs, int32_t* scratch, int scratch_len, void* stream);
+
+/* dst (n,3)[i] = src (n_src,3)[idx[i]] for 1 or 2 HOST jobs in one launch (the gather of regularize_pc,
+ * datasets/points_utils.py:24-40, straight into the network's input buffers); zero != 0: dst = 0 (its `num_points <= 2`
+ * case; src / idx unused).  A row whose index lies outside [0, n_src) is written as zeros. */
+typedef struct {
+    const float* src; int n_src; const int32_t* idx; float* dst; int n; int zero;
+} o3d_resample_job;
+int o3d_track_resample(const o3d_resample_job* jobs, int n_jobs, void* stream);
+
+/* getOffsetBB (datasets/points_utils.py:43-85): the box `ref` (15) moved by offset (4) = x, y, z, theta given in ref's frame
+ * (a row of o3d_best_proposal's output): centre' = c + R (x, y, use_z ? z : 0), R' = R Rz(theta).  The new box goes to out
+ * (15) | NULL and, with results (T,15) and frame (1) int32, to results[frame[0]] (when frame[0] < T); frame[0] += 1.
+ * yaw_state (10) | NULL = {R0 (9), yaw}: the orientation is kept as R0 Rz(yaw) and only yaw accumulates (rebase != 0:
+ * restart from ref's rotation).  limit_box: :70-76 literally; its random replacement is a counter-based hash of
+ * (seed, frame[0], component) in [-1, 1). */
+int o3d_track_offset_box(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees, int use_z,
+                         int limit_box, int seed, float* out, float* results, int T, int32_t* frame, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,267 @@
+// The tracking front end: what the reference does on the host between "a LiDAR frame arrives" and "the network runs", and
+// between "the network answers" and "the next frame's search region is known" (models/base_model.py:59-86,166-247).
+//
+//   o3d_track_crop        generate_subwindow(oriented=True) / cropAndCenterPC  (datasets/points_utils.py:103-124,146-250)
+//   o3d_track_resample    the row gather of regularize_pc (:24-40) straight into the network's input buffers
+//   o3d_track_offset_box  getOffsetBB (:43-85) with the box sequence kept on the device
+//
+// A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
+//
+// ---- the crop's fp32 operation order (compiled with -ffp-contract=off: the crop kernels hold no fused multiply-add) ---------------
+// Every operation below is one IEEE fp32 operation, in the order of the parentheses; tests/tracking_oracle.py restates it in
+// numpy and the two agree bit for bit.
+//   d  = p - c                                    dx = px - cx, dy = py - cy, dz = pz - cz
+//   q  = R^T d                                    qx = ((R00*dx + R10*dy) + R20*dz)
+//                                                 qy = ((R01*dx + R11*dy) + R21*dz)
+//                                                 qz = ((R02*dx + R12*dy) + R22*dz)
+//   box-frame half extents (x pairs with l,       hx = ((l*scale)*0.5 + offset),  hy = ((w*scale)*0.5 + offset),
+//   y with w: Box.corners)                        hz = ((h*scale)*0.5 + offset)
+//   box-frame test                                |qx| < hx  and  |qy| < hy  and  |qz| < hz          (six strict inequalities)
+//   mode MODEL only, first (crop_pc_axis_aligned on the world-frame cloud, box scaled by 4*scale, padded by 2*offset):
+//     s4 = 4*scale,  L = (l*s4)*0.5,  W = (w*s4)*0.5,  H = (h*s4)*0.5,  o2 = 2*offset
+//     e_i = (((|Ri0|*L + |Ri1|*W) + |Ri2|*H) + o2)       the extent of the scaled box's corners along world axis i
+//     world test                                  |dx| < e_0  and  |dy| < e_1  and  |dz| < e_2
+// A point is kept iff it passes the box-frame test (and, in mode MODEL, the world test); the output row is q.
+//
+// ---- compaction: two launches, no workgroup ever waits for another ------------------------------------------------------------
+// Launch 1: every workgroup of 256 points counts its survivors (wave64 ballot + popcount, four waves summed through LDS) into
+// scratch[workgroup].  Launch 2: every workgroup sums the counts of the workgroups before it in its job (<= 469 integers for a
+// 120 000-point frame, out of L2), evaluates the predicate again and scatters its survivors behind that base, in their original
+// order.  Survivors beyond `capacity` are counted, not written.  Up to O3D_CROP_MAX_JOBS jobs share the two launches.
+#include "o3d_common.hpp"
+
+namespace {
+
+constexpr int CROP_WG = 256;
+
+struct CropTable {
+    o3d_crop_job job[O3D_CROP_MAX_JOBS];
+    int wg_start[O3D_CROP_MAX_JOBS + 1];       // first workgroup of job j; [n_jobs] = the grid
+    int n_jobs;
+};
+
+// keep? and q for one point, in the operation order of the header comment
+__device__ __forceinline__ bool crop_point(const o3d_crop_job& J, const float* __restrict__ box, int i, float& qx, float& qy, float& qz) {
+    const float* p = J.points + 3 * (long)i;
+    const float dx = p[0] - box[0], dy = p[1] - box[1], dz = p[2] - box[2];
+    const float w = box[3], l = box[4], h = box[5];
+    const float* R = box + 6;
+    bool keep = true;
+    if (J.mode == O3D_CROP_MODEL) {
+        const float s4 = 4.f * J.scale, o2 = 2.f * J.offset;
+        const float L = (l * s4) * 0.5f, W = (w * s4) * 0.5f, H = (h * s4) * 0.5f;
+        const float e0 = ((fabsf(R[0]) * L + fabsf(R[1]) * W) + fabsf(R[2]) * H) + o2;
+        const float e1 = ((fabsf(R[3]) * L + fabsf(R[4]) * W) + fabsf(R[5]) * H) + o2;
+        const float e2 = ((fabsf(R[6]) * L + fabsf(R[7]) * W) + fabsf(R[8]) * H) + o2;
+        keep = fabsf(dx) < e0 && fabsf(dy) < e1 && fabsf(dz) < e2;
+    }
+    qx = (R[0] * dx + R[3] * dy) + R[6] * dz;
+    qy = (R[1] * dx + R[4] * dy) + R[7] * dz;
+    qz = (R[2] * dx + R[5] * dy) + R[8] * dz;
+    const float hx = (l * J.scale) * 0.5f + J.offset, hy = (w * J.scale) * 0.5f + J.offset, hz = (h * J.scale) * 0.5f + J.offset;
+    return keep && fabsf(qx) < hx && fabsf(qy) < hy && fabsf(qz) < hz;
+}
+
+__device__ __forceinline__ int crop_job_of(const CropTable& t, int wg) {
+    int j = 0;
+#pragma unroll
+    for (int k = 1; k < O3D_CROP_MAX_JOBS; ++k)
+        if (k < t.n_jobs && wg >= t.wg_start[k]) j = k;
+    return j;
+}
+
+template <bool SCATTER>
+__global__ __launch_bounds__(CROP_WG) void crop_kernel(CropTable t, int32_t* __restrict__ scratch) {
+    __shared__ int wave_cnt[CROP_WG / 64];
+    __shared__ int red[CROP_WG / 64];
+    const int wg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = crop_job_of(t, wg);
+    const o3d_crop_job& J = t.job[j];
+    const int first = t.wg_start[j];
+    const int i = (wg - first) * CROP_WG + tid;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    const bool keep = i < J.n && crop_point(J, J.box, i, qx, qy, qz);
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = __popcll(mask);
+    if (!SCATTER) {
+        __syncthreads();
+        if (tid == 0) scratch[wg] = (wave_cnt[0] + wave_cnt[1]) + (wave_cnt[2] + wave_cnt[3]);
+        return;
+    }
+    // the survivors of the workgroups before this one in the job
+    int part = 0;
+    for (int k = first + tid; k < wg; k += CROP_WG) part += scratch[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
+    if (lane == 0) red[wave] = part;
+    __syncthreads();
+    int base = (red[0] + red[1]) + (red[2] + red[3]);
+    int total = base;
+#pragma unroll
+    for (int k = 0; k < CROP_WG / 64; ++k) {
+        if (k < wave) base += wave_cnt[k];
+        total += wave_cnt[k];
+    }
+    if (keep) {
+        const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pos < J.capacity) {
+            float* o = J.out + 3 * (long)pos;
+            o[0] = qx; o[1] = qy; o[2] = qz;
+        }
+    }
+    if (tid == 0 && wg == t.wg_start[j + 1] - 1) J.count[0] = total;     // the job's last workgroup knows the count
+}
+
+__global__ __launch_bounds__(256) void resample_kernel(o3d_resample_job a, o3d_resample_job b) {
+    const o3d_resample_job& J = blockIdx.y == 0 ? a : b;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= J.n) return;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (!J.zero) {
+        const int s = J.idx[i];
+        if ((unsigned)s < (unsigned)J.n_src) {        // an index outside the source is a caller's bug: the row stays zero
+            const float* p = J.src + 3 * (long)s;
+            x = p[0]; y = p[1]; z = p[2];
+        }
+    }
+    float* o = J.dst + 3 * (long)i;
+    o[0] = x; o[1] = y; o[2] = z;
+}
+
+// counter-based draw from U[-1, 1): a 32-bit mix of (seed, frame, component) (the finaliser of MurmurHash3), its top 24 bits
+__device__ __forceinline__ float limit_draw(unsigned seed, unsigned frame, unsigned comp) {
+    unsigned x = seed * 0x9E3779B1u ^ (frame * 0x85EBCA77u + comp * 0xC2B2AE3Du + 0x27D4EB2Fu);
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return (float)(x >> 8) * (2.f / 16777216.f) - 1.f;
+}
+
+struct OffsetArgs {
+    const float* ref; const float* offset; float* yaw_state; float* out; float* results; int32_t* frame;
+    int T, degrees, use_z, limit_box, rebase, seed;
+};
+
+// one thread: the arithmetic is a 3x3 product; carried in double so that the stored fp32 box is the rounded exact result
+__global__ void offset_box_kernel(OffsetArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int k = a.frame ? a.frame[0] : 0;
+    float off[4] = {a.offset[0], a.offset[1], a.offset[2], a.offset[3]};
+    const float w = a.ref[3], l = a.ref[4], h = a.ref[5];
+    if (a.limit_box) {                                // datasets/points_utils.py:70-76, literally (no abs)
+        if (off[0] > w) off[0] = limit_draw((unsigned)a.seed, (unsigned)k, 0u);
+        if (off[1] > fminf(l, 2.f)) off[1] = limit_draw((unsigned)a.seed, (unsigned)k, 1u);
+        if (a.use_z && off[2] > h) off[2] = 0.f;
+    }
+    const double theta = a.degrees ? (double)off[3] * (3.14159265358979323846 / 180.0) : (double)off[3];
+    double R0[9], yaw = theta;
+    if (a.yaw_state && !a.rebase) {
+        for (int i = 0; i < 9; ++i) R0[i] = a.yaw_state[i];
+        yaw = (double)a.yaw_state[9] + theta;
+    } else {
+        for (int i = 0; i < 9; ++i) R0[i] = a.ref[6 + i];
+    }
+    // the reference box's own rotation carries the offset into the world: R = R0 Rz(yaw before the update)
+    double Rr[9];
+    if (a.yaw_state && !a.rebase) {
+        double s, c;
+        sincos((double)a.yaw_state[9], &s, &c);
+        for (int r = 0; r < 3; ++r) {
+            Rr[3 * r] = R0[3 * r] * c + R0[3 * r + 1] * s;
+            Rr[3 * r + 1] = R0[3 * r + 1] * c - R0[3 * r] * s;
+            Rr[3 * r + 2] = R0[3 * r + 2];
+        }
+    } else {
+        for (int i = 0; i < 9; ++i) Rr[i] = R0[i];
+    }
+    const double ox = off[0], oy = off[1], oz = a.use_z ? (double)off[2] : 0.0;
+    float box[15];
+    for (int r = 0; r < 3; ++r) box[r] = (float)((double)a.ref[r] + ((Rr[3 * r] * ox + Rr[3 * r + 1] * oy) + Rr[3 * r + 2] * oz));
+    box[3] = w; box[4] = l; box[5] = h;
+    const float yaw_f = (float)yaw;                   // the stored state: the next update starts from exactly this value
+    double s, c;
+    sincos(a.yaw_state ? (double)yaw_f : yaw, &s, &c);
+    for (int r = 0; r < 3; ++r) {
+        box[6 + 3 * r] = (float)(R0[3 * r] * c + R0[3 * r + 1] * s);
+        box[6 + 3 * r + 1] = (float)(R0[3 * r + 1] * c - R0[3 * r] * s);
+        box[6 + 3 * r + 2] = (float)R0[3 * r + 2];
+    }
+    if (a.yaw_state) {
+        if (a.rebase)
+            for (int i = 0; i < 9; ++i) a.yaw_state[i] = (float)R0[i];
+        a.yaw_state[9] = yaw_f;
+    }
+    for (int i = 0; i < 15; ++i) {
+        if (a.out) a.out[i] = box[i];
+        if (a.results && k >= 0 && k < a.T) a.results[15 * (long)k + i] = box[i];
+    }
+    if (a.frame) a.frame[0] = k + 1;
+}
+
+}  // namespace
+
+extern "C" long o3d_track_crop_scratch(const o3d_crop_job* jobs, int n_jobs) {
+    if (!jobs || n_jobs < 1 || n_jobs > O3D_CROP_MAX_JOBS) return -1;
+    long wgs = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (jobs[j].n < 0) return -1;
+        wgs += jobs[j].n > 0 ? o3d_cdiv(jobs[j].n, CROP_WG) : 1;
+    }
+    return wgs;
+}
+
+// jobs: a HOST table of n_jobs (1..O3D_CROP_MAX_JOBS) jobs; scratch: scratch_len >= o3d_track_crop_scratch(jobs, n_jobs) int32
+// on the device.  A job with n == 0 writes count = 0.
+extern "C" int o3d_track_crop(const o3d_crop_job* jobs, int n_jobs, int32_t* scratch, int scratch_len, void* stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > O3D_CROP_MAX_JOBS || !scratch) return O3D_EINVAL;
+    CropTable t;
+    t.n_jobs = n_jobs;
+    long wgs = 0;
+    for (int j = 0; j < O3D_CROP_MAX_JOBS; ++j) {
+        t.wg_start[j] = (int)wgs;
+        if (j >= n_jobs) { t.job[j] = o3d_crop_job{}; continue; }
+        const o3d_crop_job& J = jobs[j];
+        if (J.n < 0 || J.n > (1 << 30) || J.capacity < 0 || !J.box || !J.count || (J.n > 0 && !J.points) || (J.capacity > 0 && !J.out) ||
+            (J.mode != O3D_CROP_SUBWINDOW && J.mode != O3D_CROP_MODEL) || !(J.scale >= 0.f) || !(J.offset >= 0.f))
+            return O3D_EINVAL;
+        t.job[j] = J;
+        wgs += J.n > 0 ? o3d_cdiv(J.n, CROP_WG) : 1;
+    }
+    t.wg_start[O3D_CROP_MAX_JOBS] = (int)wgs;
+    for (int j = n_jobs; j < O3D_CROP_MAX_JOBS; ++j) t.wg_start[j] = (int)wgs;
+    if (wgs > scratch_len) return O3D_EINVAL;
+    hipLaunchKernelGGL(crop_kernel<false>, dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), t, scratch);
+    hipLaunchKernelGGL(crop_kernel<true>, dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), t, scratch);
+    return o3d_launch_status();
+}
+
+// dst[i] = src[idx[i]] (rows of 3 floats) for n_jobs (1 or 2) HOST jobs in one launch; a job with `zero` set fills dst with
+// zeros instead (regularize_pc's `num_points <= 2` case) and needs neither src nor idx
+extern "C" int o3d_track_resample(const o3d_resample_job* jobs, int n_jobs, void* stream) {
+    if (!jobs || n_jobs < 1 || n_jobs > 2) return O3D_EINVAL;
+    int nmax = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const o3d_resample_job& J = jobs[j];
+        if (J.n < 0 || J.n_src < 0 || (J.n > 0 && !J.dst) || (J.n > 0 && !J.zero && (!J.src || !J.idx || J.n_src < 1))) return O3D_EINVAL;
+        nmax = J.n > nmax ? J.n : nmax;
+    }
+    if (nmax == 0) return O3D_OK;
+    hipLaunchKernelGGL(resample_kernel, dim3(o3d_cdiv(nmax, 256), n_jobs), dim3(256), 0, o3d_stream(stream), jobs[0], jobs[n_jobs - 1]);
+    return o3d_launch_status();
+}
+
+// getOffsetBB on the device.  ref (15): the reference box; offset (4) = x, y, z, theta in ref's frame (o3d_best_proposal's
+// output row); out (15) | NULL: the new box; results (T,15) | NULL with frame (1) int32 | NULL: the new box is also written to
+// row frame[0] (when < T) and frame[0] is incremented -- the host never reads the box.
+//   centre' = c + R (ox, oy, use_z ? oz : 0),   R' = R Rz(theta),   wlh unchanged
+// yaw_state (10) | NULL = R0 (9) and the yaw accumulated since: with it (and rebase == 0) the orientation of `ref` is taken as
+// R0 Rz(yaw) and the new one is R0 Rz(yaw + theta), one product from an orthonormal R0 however long the chain; rebase != 0
+// restarts the state from ref (R0 = ref's rotation, yaw = theta).  limit_box mirrors datasets/points_utils.py:70-76 literally:
+// `offset[0] > w`, `offset[1] > min(l, 2)` replace the component by a draw from U[-1, 1), `use_z and offset[2] > h` sets it
+// to 0 (no abs).  The reference's draw is the unseeded global numpy generator, so there is nothing to reproduce: the draw here
+// is a counter-based hash of (seed, frame[0], component), the same for the same three numbers.
+extern "C" int o3d_track_offset_box(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees, int use_z,
+                                    int limit_box, int seed, float* out, float* results, int T, int32_t* frame, void* stream) {
+    if (!ref || !offset || (!out && !results) || T < 0 || (results && (!frame || T < 1))) return O3D_EINVAL;
+    OffsetArgs a{ref, offset, yaw_state, out, results, frame, T, degrees, use_z, limit_box, rebase, seed};
+    hipLaunchKernelGGL(offset_box_kernel, dim3(1), dim3(64), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}

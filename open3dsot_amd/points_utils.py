@@ -65,3 +65,157 @@ def regularize_pc(points, sample_size, seed=None):
     if idx is None:
         return torch.zeros((sample_size, 3), dtype=torch.float32, device=points.device), None
     return points.index_select(0, torch.as_tensor(idx, dtype=torch.long, device=points.device)), idx
+
+
+# ---- the tracking front end (csrc/track.hip): crops, resampling and the box update on the device ---------------------------
+# A box travels as the triple (center, wlh, rot) above or, between kernels, as ONE (15,) float32 GPU tensor
+# [center (3) | wlh (3) | rot (9) row-major] -- `pack_box` / `unpack_box`.
+CROP_SUBWINDOW, CROP_MODEL = 0, 1
+CROP_MAX_JOBS = 4
+
+
+class _CropJob(ctypes.Structure):            # o3d_crop_job (include/o3dsot.h)
+    _fields_ = [("points", _vp), ("n", _i), ("box", _vp), ("scale", _f), ("offset", _f), ("mode", _i), ("out", _vp),
+                ("capacity", _i), ("count", _vp)]
+
+
+class _ResampleJob(ctypes.Structure):        # o3d_resample_job
+    _fields_ = [("src", _vp), ("n_src", _i), ("idx", _vp), ("dst", _vp), ("n", _i), ("zero", _i)]
+
+
+capi.register("o3d_track_crop_scratch", [_vp, _i])
+capi.register("o3d_track_crop", [_vp, _i, _vp, _i, _vp])
+capi.register("o3d_track_resample", [_vp, _i, _vp])
+capi.register("o3d_track_offset_box", [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
+
+
+def _need_gpu(t, what):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError("%s: CPU not supported (tensor must be a GPU tensor)" % what)
+
+
+def pack_box(box, device):
+    """(center, wlh, rot) or a (15,) vector -> (15,) float32 tensor on `device`"""
+    if torch.is_tensor(box) and box.numel() == 15:
+        return box.to(device=device, dtype=torch.float32).reshape(15).contiguous()
+    if not torch.is_tensor(box) and len(box) == 15:
+        return _dev32(box, device).reshape(15)
+    c, s, r = box
+    return torch.cat([_dev32(c, device).reshape(3), _dev32(s, device).reshape(3), _dev32(r, device).reshape(9)])
+
+
+def unpack_box(box15):
+    """(15,) -> (center (3), wlh (3), rot (3,3)) views"""
+    return box15[0:3], box15[3:6], box15[6:15].reshape(3, 3)
+
+
+def crop_jobs(jobs, scratch=None, stream=None):
+    """One o3d_track_crop call.  jobs: up to 4 tuples (points (n,3) f32 GPU contiguous, box15 GPU, scale, offset, mode,
+    out (capacity,3) f32 GPU, count (1,) int32 GPU).  Nothing is read back here."""
+    assert 1 <= len(jobs) <= CROP_MAX_JOBS
+    dev = jobs[0][0].device
+    table = (_CropJob * len(jobs))()
+    for j, (pts, box, scale, offset, mode, out, count) in enumerate(jobs):
+        assert pts.is_cuda and pts.dtype == torch.float32 and pts.is_contiguous() and pts.dim() == 2 and pts.shape[1] == 3
+        assert box.is_cuda and box.dtype == torch.float32 and box.is_contiguous() and box.numel() == 15
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and count.dtype == torch.int32
+        table[j] = _CropJob(pts.data_ptr(), pts.shape[0], box.data_ptr(), float(scale), float(offset), int(mode),
+                            out.data_ptr(), out.shape[0], count.data_ptr())
+    lib = capi.load()
+    need = lib.o3d_track_crop_scratch(ctypes.addressof(table), len(jobs))
+    if scratch is None or scratch.numel() < need:
+        scratch = torch.empty((max(need, 1),), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        capi.check(lib.o3d_track_crop(ctypes.addressof(table), len(jobs), scratch.data_ptr(), scratch.numel(), s), "o3d_track_crop")
+    return scratch
+
+
+def resample_jobs(jobs):
+    """One o3d_track_resample call.  jobs: 1 or 2 tuples (src (n_src,3) | None, idx (n,) int32 | None, dst (n,3)); src None:
+    dst is zero-filled (regularize_pc with <= 2 points)."""
+    table = (_ResampleJob * len(jobs))()
+    for j, (src, idx, dst) in enumerate(jobs):
+        assert dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
+        n = dst.numel() // 3
+        if src is None:
+            table[j] = _ResampleJob(None, 0, None, dst.data_ptr(), n, 1)
+        else:
+            assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() >= n
+            table[j] = _ResampleJob(src.data_ptr(), src.shape[0], idx.data_ptr(), dst.data_ptr(), n, 0)
+    dev = jobs[0][2].device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_resample(ctypes.addressof(table), len(jobs), torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_track_resample")
+
+
+def _crop(points, box, scale, offset, mode, what):
+    _need_gpu(points, what)
+    pts = points.contiguous().float()
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be (N, 3)")
+    dev = pts.device
+    b = pack_box(box, dev)
+    out = torch.empty((max(pts.shape[0], 1), 3), dtype=torch.float32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    crop_jobs([(pts, b, scale, offset, mode, out, count)])
+    return out[:int(count.item())], b
+
+
+def generate_subwindow(points, sample_bb, scale, offset=2):
+    """datasets/points_utils.py:218-250 (oriented=True): the points of `points` (N,3, GPU) inside `sample_bb` scaled by
+    `scale` and padded by `offset`, in the frame of the box, in their original order -> (n,3).  One sync (the count)."""
+    return _crop(points, sample_bb, scale, offset, CROP_SUBWINDOW, "generate_subwindow")[0]
+
+
+def cropAndCenterPC(points, box, offset=0, scale=1.0):
+    """datasets/points_utils.py:103-124 (normalize=False) -> (cropped (n,3) in the box frame, canonical box = (zero centre,
+    wlh, identity) on the device)"""
+    out, b = _crop(points, box, scale, offset, CROP_MODEL, "cropAndCenterPC")
+    return out, (torch.zeros(3, device=out.device), b[3:6].clone(), torch.eye(3, device=out.device))
+
+
+def getModel(PCs, boxes, offset=0, scale=1.0):
+    """datasets/points_utils.py:88-100: the crops of the clouds `PCs` by their `boxes`, concatenated -> (points, canonical
+    box of the last one)"""
+    if len(PCs) == 0:
+        raise ValueError("getModel needs at least one cloud")
+    parts, canon = [], None
+    for pc, box in zip(PCs, boxes):
+        p, canon = cropAndCenterPC(pc, box, offset=offset, scale=scale)
+        parts.append(p)
+    return torch.cat(parts, 0), canon
+
+
+def offset_box(ref15, offset4, out=None, yaw_state=None, rebase=False, degrees=True, use_z=False, limit_box=True, seed=0,
+               results=None, frame=None):
+    """One o3d_track_offset_box launch on device operands (no sync); returns `out` (allocated when None and no results)."""
+    _need_gpu(ref15, "getOffsetBB")
+    _need_gpu(offset4, "getOffsetBB")
+    dev = ref15.device
+    assert ref15.dtype == torch.float32 and ref15.is_contiguous() and ref15.numel() == 15
+    assert offset4.dtype == torch.float32 and offset4.is_contiguous() and offset4.numel() >= 4
+    if out is None and results is None:
+        out = torch.empty((15,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_offset_box(
+            ref15.data_ptr(), offset4.data_ptr(), yaw_state.data_ptr() if yaw_state is not None else None, int(bool(rebase)),
+            int(bool(degrees)), int(bool(use_z)), int(bool(limit_box)), int(seed) & 0x7fffffff,
+            out.data_ptr() if out is not None else None, results.data_ptr() if results is not None else None,
+            results.shape[0] if results is not None else 0, frame.data_ptr() if frame is not None else None,
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_offset_box")
+    return out
+
+
+def getOffsetBB(box, offset, degrees=True, use_z=False, limit_box=True, seed=0, frame=0, yaw_state=None):
+    """datasets/points_utils.py:43-85 on the device: `box` (center, wlh, rot) moved by `offset` (4,) GPU tensor = (x, y, z,
+    theta) in the box frame -> (center, wlh, rot) GPU tensors.  `limit_box`'s random replacement (the reference draws from the
+    unseeded global numpy generator, so nothing can be pinned) is a counter-based hash of (seed, frame, component).
+    yaw_state: a (10,) GPU tensor {R0, yaw} that carries the orientation of a chain of updates (see o3d_track_offset_box)."""
+    _need_gpu(offset, "getOffsetBB")
+    dev = offset.device
+    fr = torch.full((1,), int(frame), dtype=torch.int32, device=dev)
+    res = torch.empty((int(frame) + 1, 15), dtype=torch.float32, device=dev)
+    out = offset_box(pack_box(box, dev), offset.contiguous().float().reshape(-1), torch.empty(15, device=dev), yaw_state, False,
+                     degrees, use_z, limit_box, seed, res, fr)
+    return unpack_box(out)

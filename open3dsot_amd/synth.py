@@ -159,6 +159,36 @@ def make_motion_batch(first_index, batch_size, point_sample_size=1024, seed0=432
     return {k: np.stack([o[k] for o in out], 0) for k in out[0]}
 
 
+def make_sequence(seed, n_frames, n_points):
+    """A seeded LiDAR-like sequence for the tracking loop (open3dsot_amd/tracking.py): `n_frames` frames of about `n_points`
+    points shaped like a KITTI sweep -- a ground plane (60 % of the points, 3 cm noise) and uniform clutter, both out to
+    +-60 m around the sensor, and one car-sized box (1/16 of the points, at least 64, sampled like `_surface`: a close
+    target, so that its search window holds more points than the network's input and is resampled without duplicates) on a
+    smooth yawing path that starts 15-25 m from the sensor, standing on the ground.
+    -> (frames: list of (n,3) float32, gt_boxes (n_frames,15) float32 = [centre | wlh | rotation matrix row-major])."""
+    rng = np.random.default_rng([int(seed), 0x5E9])
+    wlh = np.array([1.6, 3.9, 1.5]) * rng.uniform(0.9, 1.1, 3)
+    ground = -1.73
+    pos = np.array([rng.uniform(15, 25), rng.uniform(-8, 8)])
+    yaw, speed, rate = rng.uniform(-np.pi, np.pi), rng.uniform(0.4, 1.2), np.deg2rad(rng.uniform(-3, 3))
+    n_obj = max(64, n_points // 16)
+    n_gnd = int(0.6 * (n_points - n_obj))
+    n_clu = n_points - n_obj - n_gnd
+    frames, boxes = [], []
+    for t in range(n_frames):
+        rot = _rotz(yaw)
+        center = np.array([pos[0], pos[1], ground + wlh[2] / 2])
+        obj = _surface(rng, wlh, n_obj) @ rot.T + center
+        gnd = np.stack([rng.uniform(-60, 60, n_gnd), rng.uniform(-60, 60, n_gnd), ground + rng.normal(0, 0.03, n_gnd)], 1)
+        clu = np.stack([rng.uniform(-60, 60, n_clu), rng.uniform(-60, 60, n_clu), rng.uniform(ground, ground + 6, n_clu)], 1)
+        pts = np.concatenate([obj, gnd, clu], 0)
+        frames.append(pts[rng.permutation(pts.shape[0])].astype(np.float32))
+        boxes.append(np.concatenate([center, wlh, rot.reshape(-1)]).astype(np.float32))
+        pos = pos + speed * np.array([np.cos(yaw), np.sin(yaw)])
+        yaw = yaw + rate
+    return frames, np.stack(boxes, 0)
+
+
 def to_torch(batch, device=None):
     import torch
     return {k: torch.from_numpy(v).to(device) if device is not None else torch.from_numpy(v)

@@ -1,0 +1,260 @@
+"""Track a sequence on the device: the frame loop of MatchingBaseModel.evaluate_one_sequence (models/base_model.py:59-86)
+with everything between "a frame arrives" and "the next search region is known" on the GPU.
+
+Per frame t >= 1 (the reference's build_input_dict :240-247 + evaluate_one_sample :44-57):
+
+  o3d_track_crop, one call, two jobs    the search window of frame t by the reference box (generate_subwindow) and the model
+                                        crop of frame t-1 by ITS OWN result box (cropAndCenterPC), appended to the bank
+  8-byte pinned read-back               the two point counts -- THE ONE HOST SYNC of a frame, see below
+  np.random.default_rng(1).choice       the reference's own index draw (regularize_pc, seed=1), twice
+  one index upload                      (template_size + search_size) int32 = 6 KB
+  o3d_track_resample                    both gathers, straight into the network's static input buffers
+  o3d_boxcloud                          the template's BoxCloud against the canonical box (BAT only)
+  forward + o3d_best_proposal           replayed as one HIP graph captured once per tracker (eager when the capture fails,
+                                        unless O3D_REQUIRE_GRAPH=1)
+  o3d_track_offset_box                  getOffsetBB: the new box into the (T,15) results buffer; the host never reads it
+
+Why one sync remains: the reference resamples a crop of n points with `default_rng(1).choice(n, size, replace=size > n)`.
+Which indices that call returns depends on n, so index parity with the reference needs n on the host before the draw.  A
+device-side sampler would remove the sync and change every index; it is out of scope here.
+
+The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
+(`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import capi, points_utils as PU
+
+_DEFAULTS = dict(search_bb_scale=1.25, search_bb_offset=2, model_bb_scale=1.25, model_bb_offset=0, template_size=512,
+                 search_size=1024, degrees=True, use_z=True, limit_box=False, shape_aggregation="firstandprevious",
+                 reference_BB="previous_result")      # cfgs/BAT_Car.yaml :5-10,14,53-57
+
+
+def _aggregation(name):
+    """the branch models/base_model.py:177-194 takes, in its order of tests (substring matches on the upper-cased name)"""
+    u = str(name).upper()
+    for key in ("FIRSTANDPREVIOUS", "FIRST", "PREVIOUS", "ALL"):
+        if key in u:
+            return key.lower()
+    raise ValueError("shape_aggregation %r: expected first, previous, firstandprevious or all" % (name,))
+
+
+def draw_indices(num_points, sample_size):
+    """regularize_pc's draw (datasets/points_utils.py:24-40 with seed=1) -> int indices, or None for its zero-fill case"""
+    if num_points <= 2:
+        return None
+    if num_points == sample_size:
+        return np.arange(num_points)
+    return np.random.default_rng(1).choice(num_points, size=sample_size, replace=sample_size > num_points)
+
+
+class SequenceTracker:
+    """Device-resident tracking loop for the matching trackers (trackers.BAT, trackers.P2B).
+
+        trk = SequenceTracker(model)            # model on the GPU, eval mode
+        trk.init(points0, box0)                 # (N,3) float32 GPU tensor; box0 = (center, wlh, rot) or a 15-vector
+        box = trk.update(points)                # a (15,) device VIEW of the new box (no sync for it)
+        boxes = trk.results()                   # (T,15) on the host, one sync
+
+    `update(points, ref_box=...)` searches around (and offsets from) the given box instead of the previous result: the
+    reference's `reference_BB: previous_gt / current_gt`.  `seed` feeds limit_box's replacement draw only.
+    use_graph: None = capture, fall back to eager when the capture fails (O3D_REQUIRE_GRAPH=1: raise instead); False = eager.
+    """
+
+    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
+        p = next(model.parameters())
+        if not p.is_cuda:
+            raise RuntimeError("SequenceTracker: CPU not supported (the model must live on a GPU)")
+        capi.load()
+        self.model, self.dev, self.seed = model, p.device, int(seed)
+        c = model.config
+        for k, v in _DEFAULTS.items():
+            setattr(self, k, getattr(c, k, v))
+        self.aggregation = _aggregation(self.shape_aggregation)
+        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
+            raise ValueError("reference_BB %r" % (self.reference_BB,))
+        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
+        self.with_boxcloud = hasattr(model, "mlp_bc")
+        self.use_graph = use_graph
+        self.require_graph = os.environ.get("O3D_REQUIRE_GRAPH", "0") == "1"
+        dev, M, N = self.dev, int(self.template_size), int(self.search_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.inputs = {"template_points": torch.zeros((1, M, 3), **f32), "search_points": torch.zeros((1, N, 3), **f32)}
+        if self.with_boxcloud:
+            self.inputs["points2cc_dist_t"] = torch.zeros((1, M, 9), **f32)
+        self.search_buf = torch.empty((search_capacity, 3), **f32)
+        self.model_capacity = int(model_capacity)
+        self.bank = torch.empty((2 * self.model_capacity, 3), **f32)
+        self.counts = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self.counts_host = torch.zeros((2,), dtype=torch.int32).pin_memory()
+        self.idx = torch.zeros((M + N,), dtype=torch.int32, device=dev)
+        self.idx_host = torch.zeros((M + N,), dtype=torch.int32).pin_memory()
+        self.cur = torch.zeros((15,), **f32)               # the last result box: next frame's search and model crop read it
+        self.yaw_state = torch.zeros((10,), **f32)
+        self.canon = torch.zeros((15,), **f32)             # the template's canonical box: zero centre, wlh, identity
+        self.boxes = torch.zeros((int(max_frames), 15), **f32)
+        self.frame = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.scratch = None
+        self.graph, self.out, self.graph_failed = None, None, None
+        self.t = 0
+        self.log = []          # per frame: (search count, model count of the crop made this frame | None, template points)
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    def init(self, points0, box0):
+        PU._need_gpu(points0, "SequenceTracker.init")
+        b = PU.pack_box(box0, self.dev)
+        self.cur.copy_(b)
+        self.yaw_state[:9].copy_(b[6:15])
+        self.yaw_state[9] = 0.0
+        self.canon.zero_()
+        self.canon[3:6].copy_(b[3:6])
+        self.canon[6], self.canon[10], self.canon[14] = 1.0, 1.0, 1.0
+        self.boxes[0].copy_(b)
+        self.frame.fill_(1)
+        self.prev_points = points0.contiguous().float()
+        self.t, self.bank_fixed, self.bank_total, self.log = 1, 0, 0, []
+        return self.boxes[0]
+
+    def set_box(self, box):
+        """Overwrite the last result box (re-initialisation from a detector, teacher forcing in the tests): the next update
+        searches around it and crops the last frame's model points by it."""
+        b = PU.pack_box(box, self.dev)
+        self.cur.copy_(b)
+        self.yaw_state[:9].copy_(b[6:15])
+        self.yaw_state[9] = 0.0
+        self.boxes[self.t - 1].copy_(b)
+
+    def _grow_boxes(self):
+        if self.t >= self.boxes.shape[0]:
+            bigger = torch.zeros((2 * self.boxes.shape[0], 15), dtype=torch.float32, device=self.dev)
+            bigger[:self.boxes.shape[0]].copy_(self.boxes)
+            self.boxes = bigger
+
+    def _model_slot(self):
+        """where this frame's model crop goes in the bank, or None when the template does not change"""
+        if self.aggregation == "first":
+            return 0 if self.t == 1 else None
+        if self.aggregation == "previous":
+            return 0
+        if self.aggregation == "firstandprevious":
+            return 0 if self.t == 1 else self.bank_fixed
+        return self.bank_total                                  # all: appended
+
+    def _ensure_bank(self, need):
+        if need > self.bank.shape[0]:
+            bigger = torch.empty((max(need, 2 * self.bank.shape[0]), 3), dtype=torch.float32, device=self.dev)
+            bigger[:self.bank_total].copy_(self.bank[:self.bank_total])
+            self.bank = bigger
+
+    def _crops(self, pts, ref, slot):
+        """the frame's one crop call + the count read-back -> (search count, model count | None)"""
+        c = self
+        while True:
+            jobs = [(pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts[0:1])]
+            if slot is not None:
+                c._ensure_bank(slot + c.model_capacity)
+                jobs.append((c.prev_points, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL,
+                             c.bank[slot:slot + c.model_capacity], c.counts[1:2]))
+            c.scratch = PU.crop_jobs(jobs, c.scratch)
+            c.counts_host.copy_(c.counts, non_blocking=True)
+            torch.cuda.current_stream(c.dev).synchronize()                       # the one sync of the frame
+            ns, nm = int(c.counts_host[0]), (int(c.counts_host[1]) if slot is not None else None)
+            if ns <= c.search_buf.shape[0] and (nm is None or nm <= c.model_capacity):
+                return ns, nm
+            if ns > c.search_buf.shape[0]:                                       # a crop larger than its buffer: grow, crop again
+                c.search_buf = torch.empty((2 * ns, 3), dtype=torch.float32, device=c.dev)
+            if nm is not None and nm > c.model_capacity:
+                c.model_capacity = 2 * nm
+
+    def _forward(self):
+        with torch.no_grad():
+            return self.model.evaluate_one_sample(self.inputs)
+
+    def _network(self):
+        """forward + best proposal on the static inputs -> (best (1,4), index (1,)) device tensors"""
+        if self.use_graph is False or self.graph_failed:
+            self.out = self._forward()
+            return self.out
+        if self.graph is None:
+            try:
+                side = torch.cuda.Stream(self.dev)
+                side.wait_stream(torch.cuda.current_stream(self.dev))
+                with torch.cuda.stream(side):
+                    self._forward()
+                torch.cuda.current_stream(self.dev).wait_stream(side)
+                torch.cuda.synchronize(self.dev)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    out = self._forward()
+                self.graph, self.out = g, out
+            except Exception as e:      # noqa: BLE001  (whatever the capture raised: eager unless a graph is required)
+                if self.require_graph or self.use_graph is True:
+                    raise
+                self.graph_failed = repr(e)
+                torch.cuda.synchronize(self.dev)
+                self.out = self._forward()
+                return self.out
+        self.graph.replay()
+        return self.out
+
+    # ---- one frame ---------------------------------------------------------------------------------------------------------
+    def update(self, points, ref_box=None):
+        PU._need_gpu(points, "SequenceTracker.update")
+        if self.t < 1:
+            raise RuntimeError("SequenceTracker.update before init")
+        if self.needs_ref_box and ref_box is None:
+            raise ValueError("reference_BB %r needs update(points, ref_box=...)" % (self.reference_BB,))
+        with torch.cuda.device(self.dev):
+            return self._update(points.contiguous().float(), ref_box)
+
+    def _update(self, pts, ref_box):
+        c, M, N = self, int(self.template_size), int(self.search_size)
+        c._grow_boxes()
+        ref = c.cur if ref_box is None else PU.pack_box(ref_box, c.dev)
+        slot = c._model_slot()
+        ns, nm = c._crops(pts, ref, slot)
+        if slot is not None:
+            c.bank_total = slot + nm
+            if c.t == 1:
+                c.bank_fixed = nm                      # the first frame's crop stays at the head of the bank
+                if c.aggregation == "firstandprevious":            # getModel([first, previous]) at t = 1: the same crop twice
+                    c._ensure_bank(2 * nm + c.model_capacity)
+                    c.bank[nm:2 * nm].copy_(c.bank[:nm])
+                    c.bank_total = 2 * nm
+        nt = c.bank_total
+        it, isr = draw_indices(nt, M), draw_indices(ns, N)
+        if it is not None:
+            c.idx_host[:M] = torch.from_numpy(it.astype(np.int32))
+        if isr is not None:
+            c.idx_host[M:] = torch.from_numpy(isr.astype(np.int32))
+        c.idx.copy_(c.idx_host, non_blocking=True)
+        PU.resample_jobs([(c.bank if it is not None else None, c.idx[:M], c.inputs["template_points"]),
+                          (c.search_buf if isr is not None else None, c.idx[M:], c.inputs["search_points"])])
+        if c.with_boxcloud:
+            capi.check(capi.load().o3d_boxcloud(c.inputs["template_points"].data_ptr(), c.canon.data_ptr(), c.canon[3:6].data_ptr(),
+                                                c.canon[6:15].data_ptr(), 1.0, 1, M, c.inputs["points2cc_dist_t"].data_ptr(),
+                                                torch.cuda.current_stream(c.dev).cuda_stream), "o3d_boxcloud")
+        best, _ = c._network()
+        PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
+                      use_z=c.use_z, limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        c.prev_points = pts
+        c.log.append((ns, nm, nt))
+        c.t += 1
+        return c.boxes[c.t - 1]
+
+    def results(self):
+        """(T,15) float32 on the host: row 0 the initial box, row t the result of frame t (one sync)"""
+        return self.boxes[:self.t].cpu().numpy()
+
+
+def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
+    """The convenience loop: frames = a sequence of (N_t,3) GPU tensors, box0 the target's box in frames[0]; ref_boxes[t]
+    (optional) is handed to update() of frame t.  -> (T,15) result boxes on the host."""
+    trk = SequenceTracker(model, seed=seed, use_graph=use_graph)
+    trk.init(frames[0], box0)
+    for t in range(1, len(frames)):
+        trk.update(frames[t], None if ref_boxes is None else ref_boxes[t])
+    return trk.results()
