@@ -711,6 +711,19 @@ int o3d_track_resample(const o3d_resample_job* jobs, int n_jobs, void* stream);
 int o3d_track_offset_box(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees, int use_z,
                          int limit_box, int seed, float* out, float* results, int T, int32_t* frame, void* stream);
 
+/* The network input of the motion tracker (M2-Track) in one launch: MotionBaseModel.build_input_dict (models/base_model.py:
+ * 263-302) behind its two generate_subwindow crops.  prev (n_prev,3) / cur (n_this,3): the crops of the previous and the
+ * current frame (two O3D_CROP_SUBWINDOW jobs by the same box); idx (2N): row i < N of the output gathers prev[idx[i]], row
+ * i >= N gathers cur[idx[i]] (an index outside its source leaves a zero row); zero_prev / zero_this != 0: that half is
+ * zero-filled (regularize_pc's `num_points <= 2` case) and needs neither its crop nor idx.  wlh (3, on the device): the
+ * canonical box = centre 0, identity rotation.  points (2N,5) = xyz, time stamp (0 | 0.1), prior targetness (previous half:
+ * points_in_box of the row against the box scaled by 1.25, inclusive, written 1 / 0 when first_frame else 0.8 / 0.2; current
+ * half 0.5); candidate_bc (2N,9) | NULL: the previous half's distances to the box centre and its eight corners
+ * (get_point_to_box_distance), the current half zeros.  The fp32 operation order is written at the head of csrc/track.hip. */
+int o3d_track_motion_input(const float* prev, int n_prev, const float* cur, int n_this, const int32_t* idx, int N,
+                           int zero_prev, int zero_this, const float* wlh, int first_frame, float* points,
+                           float* candidate_bc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

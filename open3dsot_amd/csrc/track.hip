@@ -4,6 +4,8 @@
 //   o3d_track_crop        generate_subwindow(oriented=True) / cropAndCenterPC  (datasets/points_utils.py:103-124,146-250)
 //   o3d_track_resample    the row gather of regularize_pc (:24-40) straight into the network's input buffers
 //   o3d_track_offset_box  getOffsetBB (:43-85) with the box sequence kept on the device
+//   o3d_track_motion_input  the network input of the motion tracker: MotionBaseModel.build_input_dict behind its two crops
+//                         (models/base_model.py:263-302)
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -22,6 +24,18 @@
 //     e_i = (((|Ri0|*L + |Ri1|*W) + |Ri2|*H) + o2)       the extent of the scaled box's corners along world axis i
 //     world test                                  |dx| < e_0  and  |dy| < e_1  and  |dz| < e_2
 // A point is kept iff it passes the box-frame test (and, in mode MODEL, the world test); the output row is q.
+//
+// ---- the motion input's fp32 operation order (o3d_track_motion_input; tests/motion_oracle.py restates it) ---------------------
+// Row i of `points` (2N,5) is (x, y, z, time stamp, prior targetness); (x, y, z) is the gathered row (zeros when the half is
+// zero-filled or the index lies outside the source), copied, not computed.  Previous half (i < N), box = centre 0, identity
+// rotation, the given wlh (x pairs with l, y with w):
+//   half extents of the box scaled by 1.25        hx = ((l*1.25)*0.5),  hy = ((w*1.25)*0.5),  hz = ((h*1.25)*0.5)
+//   inside (inclusive: points_in_box)             |x| <= hx  and  |y| <= hy  and  |z| <= hz
+//   channel 3 = 0,  channel 4 = inside ? 1 : 0 when first_frame, else inside ? float32(0.8) : float32(0.2)
+//   BoxCloud, landmark 0 the centre, 1..8 the corners of Box.corners (wlh_factor 1):
+//     a = l*0.5, b = w*0.5, c = h*0.5;  corner k = (sx_k*a, sy_k*b, sz_k*c),  sx = +,+,+,+,-,-,-,-  sy = +,-,-,+,+,-,-,+
+//     sz = +,+,-,-,+,+,-,-;   dx = x - X, dy = y - Y, dz = z - Z;   distance = sqrt(((dx*dx + dy*dy) + dz*dz))
+// Current half (i >= N): channel 3 = float32(0.1), channel 4 = 0.5, BoxCloud row = 0.
 //
 // ---- compaction: two launches, no workgroup ever waits for another ------------------------------------------------------------
 // Launch 1: every workgroup of 256 points counts its survivors (wave64 ballot + popcount, four waves summed through LDS) into
@@ -126,6 +140,53 @@ __global__ __launch_bounds__(256) void resample_kernel(o3d_resample_job a, o3d_r
     }
     float* o = J.dst + 3 * (long)i;
     o[0] = x; o[1] = y; o[2] = z;
+}
+
+struct MotionInputArgs {
+    const float* src[2]; int n_src[2]; int zero[2];      // [0] the previous crop, [1] the current crop
+    const int32_t* idx; const float* wlh; int N, first_frame;
+    float* points; float* bc;
+};
+
+__global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * a.N) return;
+    const int half = i >= a.N ? 1 : 0;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (!a.zero[half]) {
+        const int s = a.idx[i];
+        if ((unsigned)s < (unsigned)a.n_src[half]) {  // an index outside the source is a caller's bug: the row stays zero
+            const float* p = a.src[half] + 3 * (long)s;
+            x = p[0]; y = p[1]; z = p[2];
+        }
+    }
+    float* o = a.points + 5 * (long)i;
+    float* bc = a.bc ? a.bc + 9 * (long)i : nullptr;
+    o[0] = x; o[1] = y; o[2] = z;
+    if (half) {
+        o[3] = 0.1f; o[4] = 0.5f;
+        if (bc) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) bc[k] = 0.f;
+        }
+        return;
+    }
+    const float w = a.wlh[0], l = a.wlh[1], h = a.wlh[2];
+    const float hx = (l * 1.25f) * 0.5f, hy = (w * 1.25f) * 0.5f, hz = (h * 1.25f) * 0.5f;
+    const bool inside = fabsf(x) <= hx && fabsf(y) <= hy && fabsf(z) <= hz;
+    o[3] = 0.f;
+    o[4] = a.first_frame ? (inside ? 1.f : 0.f) : (inside ? 0.8f : 0.2f);
+    if (!bc) return;
+    const float ca = l * 0.5f, cb = w * 0.5f, cc = h * 0.5f;
+    bc[0] = sqrtf((x * x + y * y) + z * z);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float X = k < 4 ? ca : -ca;
+        const float Y = ((k & 3) == 0 || (k & 3) == 3) ? cb : -cb;
+        const float Z = (k & 2) ? -cc : cc;
+        const float dx = x - X, dy = y - Y, dz = z - Z;
+        bc[1 + k] = sqrtf((dx * dx + dy * dy) + dz * dz);
+    }
 }
 
 // counter-based draw from U[-1, 1): a 32-bit mix of (seed, frame, component) (the finaliser of MurmurHash3), its top 24 bits
@@ -263,5 +324,22 @@ extern "C" int o3d_track_offset_box(const float* ref, const float* offset, float
     if (!ref || !offset || (!out && !results) || T < 0 || (results && (!frame || T < 1))) return O3D_EINVAL;
     OffsetArgs a{ref, offset, yaw_state, out, results, frame, T, degrees, use_z, limit_box, rebase, seed};
     hipLaunchKernelGGL(offset_box_kernel, dim3(1), dim3(64), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+// The network input of the motion tracker in one launch (MotionBaseModel.build_input_dict behind its two crops).  prev
+// (n_prev,3) / cur (n_this,3): the crops of the previous and the current frame in the frame of the reference box; idx (2N):
+// row i < N gathers prev[idx[i]], row i >= N gathers cur[idx[i]]; zero_prev / zero_this: that half is zero-filled instead
+// (regularize_pc with <= 2 points) and needs neither its crop nor idx; wlh (3, device): the canonical box.  points (2N,5) and
+// candidate_bc (2N,9) | NULL (box_aware=False) are written as the header of this file states.
+extern "C" int o3d_track_motion_input(const float* prev, int n_prev, const float* cur, int n_this, const int32_t* idx, int N,
+                                      int zero_prev, int zero_this, const float* wlh, int first_frame, float* points,
+                                      float* candidate_bc, void* stream) {
+    if (N < 0 || N > (1 << 29) || n_prev < 0 || n_this < 0 || !wlh || !points) return O3D_EINVAL;
+    if (!zero_prev && (!prev || n_prev < 1 || !idx)) return O3D_EINVAL;
+    if (!zero_this && (!cur || n_this < 1 || !idx)) return O3D_EINVAL;
+    if (N == 0) return O3D_OK;
+    MotionInputArgs a{{prev, cur}, {n_prev, n_this}, {zero_prev != 0, zero_this != 0}, idx, wlh, N, first_frame != 0, points, candidate_bc};
+    hipLaunchKernelGGL(motion_input_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
     return o3d_launch_status();
 }

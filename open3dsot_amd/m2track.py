@@ -163,6 +163,13 @@ class M2TRACK(nn.Module):
         out.update({"seg_logits": seg_logits, "motion_pred": motion_pred, "aux_estimation_boxes": aux_box})
         return out
 
+    def evaluate_one_sample(self, data):
+        """the network half of BaseModel.evaluate_one_sample (models/base_model.py:44-57) for the motion tracker: points
+        (1,2N,5) [+ candidate_bc (1,2N,9)] -> estimation_boxes (1,4) = (x, y, z, theta) in the frame of the reference box, on
+        the device (tracking.MotionSequenceTracker hands it to o3d_track_offset_box without a read-back)"""
+        with torch.no_grad():
+            return self(data)["estimation_boxes"]
+
     def compute_loss(self, data, output):
         """models/m2track.py:153-231.  Same terms, same weights, same dict; the four (centre, angle) pairs -- first-stage
         box, refined box, previous-frame box, motion -- are evaluated as ONE stacked smooth-L1 each and the weighted total

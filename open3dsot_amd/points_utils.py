@@ -87,6 +87,7 @@ capi.register("o3d_track_crop_scratch", [_vp, _i])
 capi.register("o3d_track_crop", [_vp, _i, _vp, _i, _vp])
 capi.register("o3d_track_resample", [_vp, _i, _vp])
 capi.register("o3d_track_offset_box", [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
+capi.register("o3d_track_motion_input", [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp])
 
 
 def _need_gpu(t, what):
@@ -219,3 +220,75 @@ def getOffsetBB(box, offset, degrees=True, use_z=False, limit_box=True, seed=0, 
     out = offset_box(pack_box(box, dev), offset.contiguous().float().reshape(-1), torch.empty(15, device=dev), yaw_state, False,
                      degrees, use_z, limit_box, seed, res, fr)
     return unpack_box(out)
+
+
+# ---- the motion tracker's input (MotionBaseModel.build_input_dict, models/base_model.py:255-304) ---------------------------
+def motion_input(prev_crop, this_crop, idx, wlh, first_frame, zero=(False, False), out_points=None, out_bc=None):
+    """One o3d_track_motion_input launch (no sync): the two crops (n,3) of the previous and the current frame in the frame of
+    the reference box, gathered by idx (2N,) int32 [rows < N from prev_crop, rows >= N from this_crop] -> (points (2N,5),
+    candidate_bc (2N,9)).  wlh (3,) GPU: the canonical box; zero[h]: half h is zero-filled (its crop and its indices are not
+    read; the crop may be None).  out_bc=False skips the BoxCloud (box_aware=False) and returns None for it; the outputs are
+    allocated when None."""
+    _need_gpu(wlh, "motion_input")
+    dev = wlh.device
+    zp, zt = bool(zero[0]), bool(zero[1])
+    for src, z in ((prev_crop, zp), (this_crop, zt)):
+        if not (z and src is None):
+            _need_gpu(src, "motion_input")
+            assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == 3
+    if idx is not None:
+        _need_gpu(idx, "motion_input")
+        assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() % 2 == 0
+        n2 = idx.numel()
+    elif out_points is not None:
+        n2 = out_points.numel() // 5
+    else:
+        raise ValueError("motion_input needs idx or out_points to know the sample size")
+    assert wlh.dtype == torch.float32 and wlh.is_contiguous() and wlh.numel() == 3
+    if out_points is None:
+        out_points = torch.empty((n2, 5), dtype=torch.float32, device=dev)
+    if out_bc is None:
+        out_bc = torch.empty((n2, 9), dtype=torch.float32, device=dev)
+    elif out_bc is False:
+        out_bc = None
+    assert out_points.is_cuda and out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.numel() == 5 * n2
+    assert out_bc is None or (out_bc.is_cuda and out_bc.dtype == torch.float32 and out_bc.is_contiguous() and out_bc.numel() == 9 * n2)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_motion_input(
+            prev_crop.data_ptr() if prev_crop is not None else None, prev_crop.shape[0] if prev_crop is not None else 0,
+            this_crop.data_ptr() if this_crop is not None else None, this_crop.shape[0] if this_crop is not None else 0,
+            idx.data_ptr() if idx is not None else None, n2 // 2, int(zp), int(zt), wlh.data_ptr(), int(bool(first_frame)),
+            out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_motion_input")
+    return out_points, out_bc
+
+
+def _box_device(box, what):
+    """the GPU a box lives on (a (15,) tensor or a (center, wlh, rot) triple of tensors); anything else is refused"""
+    parts = (box,) if torch.is_tensor(box) else tuple(box)
+    for x in parts:
+        _need_gpu(x, what)
+    return parts[0].device
+
+
+def transform_box(box, ref_box):
+    """datasets/points_utils.py:253-258 on the device: `box` expressed in the frame of `ref_box` -> (center, wlh, rot) GPU
+    tensors (transform_box(b, b) is the canonical box of b).  Not on the per-frame path: a 3x3 product in torch."""
+    dev = _box_device(box, "transform_box")
+    _box_device(ref_box, "transform_box")
+    c, s, r = unpack_box(pack_box(box, dev))
+    rc, _, rr = unpack_box(pack_box(ref_box, dev))
+    return rr.t() @ (c - rc), s.clone(), rr.t() @ r
+
+
+def points_in_box(box, points, wlh_factor=1.0):
+    """nuscenes.utils.geometry_utils.points_in_box on the device: points (3,N) GPU tensor -> (N,) bool, the points inside `box`
+    scaled by wlh_factor, faces included (the projections onto the three edges from corner 0 of Box.corners).  A mirror for
+    callers of the reference's name; the tracker's own mask comes from o3d_track_motion_input."""
+    _need_gpu(points, "points_in_box")
+    if points.dim() != 2 or points.shape[0] != 3:
+        raise ValueError("points must be (3, N)")
+    c, s, r = unpack_box(pack_box(box, points.device))
+    q = r.t() @ (points.float() - c[:, None])                      # the box frame: x pairs with l, y with w
+    half = (torch.stack([s[1], s[0], s[2]]) * float(wlh_factor) * 0.5)[:, None]
+    return (q.abs() <= half).all(0)

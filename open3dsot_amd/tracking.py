@@ -51,60 +51,39 @@ def draw_indices(num_points, sample_size):
     return np.random.default_rng(1).choice(num_points, size=sample_size, replace=sample_size > num_points)
 
 
-class SequenceTracker:
-    """Device-resident tracking loop for the matching trackers (trackers.BAT, trackers.P2B).
+class _DeviceTracker:
+    """What the two tracking loops share: the box state on the device (the last result box, R0 + accumulated yaw, the
+    canonical box), the (T,15) results buffer with its device-side frame counter, the crop call with the frame's one count
+    read-back (and buffer growth when a crop exceeds its capacity) and the network as a HIP graph captured once per tracker
+    (eager when the capture fails, unless O3D_REQUIRE_GRAPH=1).  Subclasses provide `_forward()` on their static inputs."""
+    _NAME = "tracker"
 
-        trk = SequenceTracker(model)            # model on the GPU, eval mode
-        trk.init(points0, box0)                 # (N,3) float32 GPU tensor; box0 = (center, wlh, rot) or a 15-vector
-        box = trk.update(points)                # a (15,) device VIEW of the new box (no sync for it)
-        boxes = trk.results()                   # (T,15) on the host, one sync
-
-    `update(points, ref_box=...)` searches around (and offsets from) the given box instead of the previous result: the
-    reference's `reference_BB: previous_gt / current_gt`.  `seed` feeds limit_box's replacement draw only.
-    use_graph: None = capture, fall back to eager when the capture fails (O3D_REQUIRE_GRAPH=1: raise instead); False = eager.
-    """
-
-    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
+    def __init__(self, model, seed, use_graph, max_frames, defaults):
         p = next(model.parameters())
         if not p.is_cuda:
-            raise RuntimeError("SequenceTracker: CPU not supported (the model must live on a GPU)")
+            raise RuntimeError("%s: CPU not supported (the model must live on a GPU)" % self._NAME)
         capi.load()
         self.model, self.dev, self.seed = model, p.device, int(seed)
-        c = model.config
-        for k, v in _DEFAULTS.items():
-            setattr(self, k, getattr(c, k, v))
-        self.aggregation = _aggregation(self.shape_aggregation)
-        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
-            raise ValueError("reference_BB %r" % (self.reference_BB,))
-        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
-        self.with_boxcloud = hasattr(model, "mlp_bc")
+        for k, v in defaults.items():
+            setattr(self, k, getattr(model.config, k, v))
         self.use_graph = use_graph
         self.require_graph = os.environ.get("O3D_REQUIRE_GRAPH", "0") == "1"
-        dev, M, N = self.dev, int(self.template_size), int(self.search_size)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.inputs = {"template_points": torch.zeros((1, M, 3), **f32), "search_points": torch.zeros((1, N, 3), **f32)}
-        if self.with_boxcloud:
-            self.inputs["points2cc_dist_t"] = torch.zeros((1, M, 9), **f32)
-        self.search_buf = torch.empty((search_capacity, 3), **f32)
-        self.model_capacity = int(model_capacity)
-        self.bank = torch.empty((2 * self.model_capacity, 3), **f32)
-        self.counts = torch.zeros((2,), dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.counts = torch.zeros((2,), dtype=torch.int32, device=self.dev)
         self.counts_host = torch.zeros((2,), dtype=torch.int32).pin_memory()
-        self.idx = torch.zeros((M + N,), dtype=torch.int32, device=dev)
-        self.idx_host = torch.zeros((M + N,), dtype=torch.int32).pin_memory()
-        self.cur = torch.zeros((15,), **f32)               # the last result box: next frame's search and model crop read it
+        self.cur = torch.zeros((15,), **f32)               # the last result box: the next frame's crops read it
         self.yaw_state = torch.zeros((10,), **f32)
-        self.canon = torch.zeros((15,), **f32)             # the template's canonical box: zero centre, wlh, identity
+        self.canon = torch.zeros((15,), **f32)             # the canonical box: zero centre, wlh, identity
         self.boxes = torch.zeros((int(max_frames), 15), **f32)
-        self.frame = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.frame = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.scratch = None
         self.graph, self.out, self.graph_failed = None, None, None
         self.t = 0
-        self.log = []          # per frame: (search count, model count of the crop made this frame | None, template points)
+        self.log = []
 
     # ---- state -------------------------------------------------------------------------------------------------------------
     def init(self, points0, box0):
-        PU._need_gpu(points0, "SequenceTracker.init")
+        PU._need_gpu(points0, self._NAME + ".init")
         b = PU.pack_box(box0, self.dev)
         self.cur.copy_(b)
         self.yaw_state[:9].copy_(b[6:15])
@@ -115,12 +94,12 @@ class SequenceTracker:
         self.boxes[0].copy_(b)
         self.frame.fill_(1)
         self.prev_points = points0.contiguous().float()
-        self.t, self.bank_fixed, self.bank_total, self.log = 1, 0, 0, []
+        self.t, self.log = 1, []
         return self.boxes[0]
 
     def set_box(self, box):
         """Overwrite the last result box (re-initialisation from a detector, teacher forcing in the tests): the next update
-        searches around it and crops the last frame's model points by it."""
+        crops around it and offsets from it."""
         b = PU.pack_box(box, self.dev)
         self.cur.copy_(b)
         self.yaw_state[:9].copy_(b[6:15])
@@ -133,48 +112,26 @@ class SequenceTracker:
             bigger[:self.boxes.shape[0]].copy_(self.boxes)
             self.boxes = bigger
 
-    def _model_slot(self):
-        """where this frame's model crop goes in the bank, or None when the template does not change"""
-        if self.aggregation == "first":
-            return 0 if self.t == 1 else None
-        if self.aggregation == "previous":
-            return 0
-        if self.aggregation == "firstandprevious":
-            return 0 if self.t == 1 else self.bank_fixed
-        return self.bank_total                                  # all: appended
-
-    def _ensure_bank(self, need):
-        if need > self.bank.shape[0]:
-            bigger = torch.empty((max(need, 2 * self.bank.shape[0]), 3), dtype=torch.float32, device=self.dev)
-            bigger[:self.bank_total].copy_(self.bank[:self.bank_total])
-            self.bank = bigger
-
-    def _crops(self, pts, ref, slot):
-        """the frame's one crop call + the count read-back -> (search count, model count | None)"""
-        c = self
+    def _crop_counts(self, make_jobs):
+        """The frame's one crop call + the count read-back.  make_jobs() -> [(crop job, grow)]: the job's count lands in
+        counts[j]; grow(n) is called when its n survivors exceed the job's buffer, and the call is made again.  -> counts"""
         while True:
-            jobs = [(pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts[0:1])]
-            if slot is not None:
-                c._ensure_bank(slot + c.model_capacity)
-                jobs.append((c.prev_points, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL,
-                             c.bank[slot:slot + c.model_capacity], c.counts[1:2]))
-            c.scratch = PU.crop_jobs(jobs, c.scratch)
-            c.counts_host.copy_(c.counts, non_blocking=True)
-            torch.cuda.current_stream(c.dev).synchronize()                       # the one sync of the frame
-            ns, nm = int(c.counts_host[0]), (int(c.counts_host[1]) if slot is not None else None)
-            if ns <= c.search_buf.shape[0] and (nm is None or nm <= c.model_capacity):
-                return ns, nm
-            if ns > c.search_buf.shape[0]:                                       # a crop larger than its buffer: grow, crop again
-                c.search_buf = torch.empty((2 * ns, 3), dtype=torch.float32, device=c.dev)
-            if nm is not None and nm > c.model_capacity:
-                c.model_capacity = 2 * nm
-
-    def _forward(self):
-        with torch.no_grad():
-            return self.model.evaluate_one_sample(self.inputs)
+            jobs = make_jobs()
+            self.scratch = PU.crop_jobs([j for j, _ in jobs], self.scratch)
+            self.counts_host.copy_(self.counts, non_blocking=True)
+            torch.cuda.current_stream(self.dev).synchronize()                    # the one sync of the frame
+            ns = [int(self.counts_host[j]) for j in range(len(jobs))]
+            over = {}                                                            # grow -> its largest overflowing count
+            for n, (job, grow) in zip(ns, jobs):
+                if n > job[5].shape[0]:
+                    over[grow] = max(n, over.get(grow, 0))
+            if not over:
+                return ns
+            for grow, n in over.items():                                         # a crop larger than its buffer: grow, crop again
+                grow(n)
 
     def _network(self):
-        """forward + best proposal on the static inputs -> (best (1,4), index (1,)) device tensors"""
+        """the forward on the static inputs -> its device tensors (the same objects at every replay)"""
         if self.use_graph is False or self.graph_failed:
             self.out = self._forward()
             return self.out
@@ -199,6 +156,89 @@ class SequenceTracker:
                 return self.out
         self.graph.replay()
         return self.out
+
+    def _forward(self):
+        with torch.no_grad():
+            return self.model.evaluate_one_sample(self.inputs)
+
+    def results(self):
+        """(T,15) float32 on the host: row 0 the initial box, row t the result of frame t (one sync)"""
+        return self.boxes[:self.t].cpu().numpy()
+
+
+class SequenceTracker(_DeviceTracker):
+    """Device-resident tracking loop for the matching trackers (trackers.BAT, trackers.P2B).
+
+        trk = SequenceTracker(model)            # model on the GPU, eval mode
+        trk.init(points0, box0)                 # (N,3) float32 GPU tensor; box0 = (center, wlh, rot) or a 15-vector
+        box = trk.update(points)                # a (15,) device VIEW of the new box (no sync for it)
+        boxes = trk.results()                   # (T,15) on the host, one sync
+
+    `update(points, ref_box=...)` searches around (and offsets from) the given box instead of the previous result: the
+    reference's `reference_BB: previous_gt / current_gt`.  `seed` feeds limit_box's replacement draw only.
+    use_graph: None = capture, fall back to eager when the capture fails (O3D_REQUIRE_GRAPH=1: raise instead); False = eager.
+    """
+    _NAME = "SequenceTracker"
+
+    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
+        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS)
+        self.aggregation = _aggregation(self.shape_aggregation)
+        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
+            raise ValueError("reference_BB %r" % (self.reference_BB,))
+        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
+        self.with_boxcloud = hasattr(model, "mlp_bc")
+        dev, M, N = self.dev, int(self.template_size), int(self.search_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.inputs = {"template_points": torch.zeros((1, M, 3), **f32), "search_points": torch.zeros((1, N, 3), **f32)}
+        if self.with_boxcloud:
+            self.inputs["points2cc_dist_t"] = torch.zeros((1, M, 9), **f32)
+        self.search_buf = torch.empty((search_capacity, 3), **f32)
+        self.model_capacity = int(model_capacity)
+        self.bank = torch.empty((2 * self.model_capacity, 3), **f32)
+        self.idx = torch.zeros((M + N,), dtype=torch.int32, device=dev)
+        self.idx_host = torch.zeros((M + N,), dtype=torch.int32).pin_memory()
+        # log, per frame: (search count, model count of the crop made this frame | None, template points)
+
+    def init(self, points0, box0):
+        box = super().init(points0, box0)
+        self.bank_fixed, self.bank_total = 0, 0
+        return box
+
+    def _model_slot(self):
+        """where this frame's model crop goes in the bank, or None when the template does not change"""
+        if self.aggregation == "first":
+            return 0 if self.t == 1 else None
+        if self.aggregation == "previous":
+            return 0
+        if self.aggregation == "firstandprevious":
+            return 0 if self.t == 1 else self.bank_fixed
+        return self.bank_total                                  # all: appended
+
+    def _ensure_bank(self, need):
+        if need > self.bank.shape[0]:
+            bigger = torch.empty((max(need, 2 * self.bank.shape[0]), 3), dtype=torch.float32, device=self.dev)
+            bigger[:self.bank_total].copy_(self.bank[:self.bank_total])
+            self.bank = bigger
+
+    def _crops(self, pts, ref, slot):
+        """the frame's one crop call + the count read-back -> (search count, model count | None)"""
+        c = self
+
+        def grow_search(n):
+            c.search_buf = torch.empty((2 * n, 3), dtype=torch.float32, device=c.dev)
+
+        def grow_model(n):
+            c.model_capacity = 2 * n
+
+        def make_jobs():
+            jobs = [((pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts[0:1]), grow_search)]
+            if slot is not None:
+                c._ensure_bank(slot + c.model_capacity)
+                jobs.append(((c.prev_points, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL,
+                              c.bank[slot:slot + c.model_capacity], c.counts[1:2]), grow_model))
+            return jobs
+        ns = c._crop_counts(make_jobs)
+        return ns[0], (ns[1] if slot is not None else None)
 
     # ---- one frame ---------------------------------------------------------------------------------------------------------
     def update(self, points, ref_box=None):
@@ -245,16 +285,95 @@ class SequenceTracker:
         c.t += 1
         return c.boxes[c.t - 1]
 
-    def results(self):
-        """(T,15) float32 on the host: row 0 the initial box, row t the result of frame t (one sync)"""
-        return self.boxes[:self.t].cpu().numpy()
+
+# cfgs/M2_track_kitti.yaml :5-8,32-33
+_MOTION_DEFAULTS = dict(bb_scale=1.25, bb_offset=2, point_sample_size=1024, degrees=False, use_z=True, limit_box=False)
+
+
+class MotionSequenceTracker(_DeviceTracker):
+    """Device-resident tracking loop for the motion tracker (m2track.M2TRACK): the frame loop of evaluate_one_sequence over
+    MotionBaseModel.build_input_dict (models/base_model.py:255-304).  Same surface as SequenceTracker (init, update, set_box,
+    results, log, out).  Per frame t >= 1:
+
+      o3d_track_crop, one call, two jobs    frame t-1 and frame t, both by the last result box (generate_subwindow twice)
+      8-byte pinned read-back               the two point counts -- the one host sync of the frame (see the module docstring)
+      draw_indices twice, one index upload  2 x point_sample_size int32 = 8 KB
+      o3d_track_motion_input                gather + time stamp + prior-targetness mask + candidate BoxCloud, one launch, into
+                                            the network's static inputs; first_frame = (t == 1)
+      forward                               replayed as one HIP graph captured once per tracker
+      o3d_track_offset_box                  reads estimation_boxes where the forward left it; the new box goes to results
+
+    log, per frame: (previous-frame count, current-frame count)."""
+    _NAME = "MotionSequenceTracker"
+
+    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, capacity=32768):
+        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS)
+        dev, N = self.dev, int(self.point_sample_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.box_aware = bool(getattr(model, "box_aware", False))
+        self.inputs = {"points": torch.zeros((1, 2 * N, 5), **f32)}
+        if self.box_aware:
+            self.inputs["candidate_bc"] = torch.zeros((1, 2 * N, 9), **f32)
+        self.crop_buf = torch.empty((2, int(capacity), 3), **f32)          # [0] the previous frame's crop, [1] the current one's
+        self.idx = torch.zeros((2 * N,), dtype=torch.int32, device=dev)
+        self.idx_host = torch.zeros((2 * N,), dtype=torch.int32).pin_memory()
+
+    def _crops(self, pts):
+        c = self
+
+        def grow(n):                                   # both jobs share it: called once, with the larger of the two counts
+            c.crop_buf = torch.empty((2, 2 * n, 3), dtype=torch.float32, device=c.dev)
+
+        def make_jobs():
+            return [((src, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], c.counts[h:h + 1]), grow)
+                    for h, src in enumerate((c.prev_points, pts))]
+        return c._crop_counts(make_jobs)
+
+    def update(self, points):
+        PU._need_gpu(points, "MotionSequenceTracker.update")
+        if self.t < 1:
+            raise RuntimeError("MotionSequenceTracker.update before init")
+        with torch.cuda.device(self.dev):
+            return self._update(points.contiguous().float())
+
+    def _update(self, pts):
+        c, N = self, int(self.point_sample_size)
+        c._grow_boxes()
+        n_prev, n_this = c._crops(pts)
+        ip, it = draw_indices(n_prev, N), draw_indices(n_this, N)
+        if ip is not None:
+            c.idx_host[:N] = torch.from_numpy(ip.astype(np.int32))
+        if it is not None:
+            c.idx_host[N:] = torch.from_numpy(it.astype(np.int32))
+        c.idx.copy_(c.idx_host, non_blocking=True)
+        PU.motion_input(c.crop_buf[0, :n_prev], c.crop_buf[1, :n_this], c.idx, c.canon[3:6], c.t == 1, zero=(ip is None, it is None),
+                        out_points=c.inputs["points"], out_bc=c.inputs["candidate_bc"] if c.box_aware else False)
+        est = c._network()
+        PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
+                      limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        c.prev_points = pts
+        c.log.append((n_prev, n_this))
+        c.t += 1
+        return c.boxes[c.t - 1]
+
+
+def tracker_for(model, **kw):
+    """the tracker class of a model: MotionSequenceTracker for m2track.M2TRACK, SequenceTracker for the matching trackers"""
+    from .m2track import M2TRACK
+    return (MotionSequenceTracker if isinstance(model, M2TRACK) else SequenceTracker)(model, **kw)
 
 
 def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
     """The convenience loop: frames = a sequence of (N_t,3) GPU tensors, box0 the target's box in frames[0]; ref_boxes[t]
-    (optional) is handed to update() of frame t.  -> (T,15) result boxes on the host."""
-    trk = SequenceTracker(model, seed=seed, use_graph=use_graph)
+    (optional, matching trackers only) is handed to update() of frame t.  The tracker class follows the model's type.
+    -> (T,15) result boxes on the host."""
+    trk = tracker_for(model, seed=seed, use_graph=use_graph)
+    if isinstance(trk, MotionSequenceTracker) and ref_boxes is not None:
+        raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
     trk.init(frames[0], box0)
     for t in range(1, len(frames)):
-        trk.update(frames[t], None if ref_boxes is None else ref_boxes[t])
+        if ref_boxes is None:
+            trk.update(frames[t])
+        else:
+            trk.update(frames[t], ref_boxes[t])
     return trk.results()

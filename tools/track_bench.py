@@ -1,7 +1,7 @@
 """ms per tracked frame of a whole sequence: the device-resident loop (open3dsot_amd/tracking.py) against the loop a user
 had to write before it existed, on the same box in the same run.  Not bench.py: that measures the network alone.
 
-  python tools/track_bench.py [--frames 200] [--points 120000] [--model BAT]
+  python tools/track_bench.py [--frames 200] [--points 120000] [--model BAT | P2B | M2TRACK]
 
 Both loops track the same synth.make_sequence with a random-init model in eval mode and start from the frames resident in
 HBM (device loop) / in host memory (host loop: where a dataset reader leaves them).
@@ -9,6 +9,9 @@ HBM (device loop) / in host memory (host loop: where a dataset reader leaves the
   host loop     the numpy crops (tests/tracking_oracle.py, the fp32 restatement of the reference's generate_subwindow /
                 cropAndCenterPC) -> upload -> model.prepare_input (BAT; P2B: regularize_pc) -> model.evaluate_one_sample
                 -> read back the (4,) offset -> getOffsetBB's algebra in numpy
+  --model M2TRACK: the device loop is MotionSequenceTracker.update; the host loop is MotionBaseModel.build_input_dict
+                restated in numpy (tests/motion_oracle.py::host_input: two crops, two index draws, time stamp, prior-targetness
+                mask, candidate BoxCloud) -> upload -> model.evaluate_one_sample -> read back -> getOffsetBB in numpy
 Prints one JSON line with both figures and their ratio.
 """
 import argparse
@@ -23,8 +26,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))      # det_init, for motion_oracle.init_weights
+import motion_oracle as MO  # noqa: E402
 import tracking_oracle as TO  # noqa: E402
-from open3dsot_amd import points_utils as PU, synth, trackers, tracking  # noqa: E402
+from open3dsot_amd import m2track, points_utils as PU, synth, trackers, tracking  # noqa: E402
 
 
 def host_loop(model, cfg, frames, box0, dev):
@@ -49,6 +54,19 @@ def host_loop(model, cfg, frames, box0, dev):
     return np.stack(boxes)
 
 
+def motion_host_loop(model, cfg, frames, box0, dev):
+    """frames: host arrays.  The motion tracker's loop with build_input_dict on the host."""
+    boxes = [np.asarray(box0, np.float32)]
+    for t in range(1, len(frames)):
+        pts, bc, _ = MO.host_input(frames[t - 1], frames[t], boxes[-1], cfg, t == 1, with_bc=cfg["box_aware"])
+        data = {"points": torch.from_numpy(pts).to(dev)[None]}
+        if bc is not None:
+            data["candidate_bc"] = torch.from_numpy(bc).to(dev)[None]
+        off = model.evaluate_one_sample(data)[0].cpu().numpy()           # the read-back (a sync)
+        boxes.append(TO.offset_box(boxes[-1], off, cfg["degrees"], cfg["use_z"], cfg["limit_box"])[0])
+    return np.stack(boxes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
@@ -60,14 +78,29 @@ def main():
         raise SystemExit("track_bench.py needs a GPU: the HIP library is the only compute path (no CPU fallback)")
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
-    cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
-    cfg.update(TO.TEST_KEYS)
-    model = trackers.get_model(args.model)(trackers.make_config(cfg)).to(dev).eval()
+    motion = args.model.upper() == "M2TRACK"
+    if motion:
+        # the fixture's weights (tests/motion_oracle.py::init_weights) with the three box-moving heads scaled by a further 0.02:
+        # a He-initialised head answers with metres per frame, and even the fixture's decimetre per frame lifts the box off the
+        # ground within 25 frames, after which both loops would crop empty space and zero-fill their inputs
+        cfg = MO.case_config("kitti")
+        model = MO.init_weights(m2track.M2TRACK(**cfg))
+        with torch.no_grad():
+            for name in ("motion_mlp", "final_mlp", "box_mlp"):
+                getattr(model, name)[-1].weight *= 0.02
+                getattr(model, name)[-1].bias *= 0.02
+        model = model.to(dev).eval()
+        loop = motion_host_loop
+    else:
+        cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+        cfg.update(TO.TEST_KEYS)
+        model = trackers.get_model(args.model)(trackers.make_config(cfg)).to(dev).eval()
+        loop = host_loop
     frames, gt = synth.make_sequence(args.seed, args.frames, args.points)
     dframes = [torch.from_numpy(f).to(dev) for f in frames]
     warm = min(20, args.frames)
 
-    trk = tracking.SequenceTracker(model)
+    trk = tracking.tracker_for(model)
     trk.init(dframes[0], gt[0])
     for t in range(1, warm):                                            # capture + warm-up
         trk.update(dframes[t])
@@ -79,10 +112,10 @@ def main():
     dev_boxes = trk.results()                                           # the one read-back of the boxes (a sync)
     dev_ms = (time.perf_counter() - t0) / (args.frames - 1) * 1e3
 
-    host_loop(model, cfg, frames[:warm], gt[0], dev)
+    loop(model, cfg, frames[:warm], gt[0], dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    host_boxes = host_loop(model, cfg, frames, gt[0], dev)
+    host_boxes = loop(model, cfg, frames, gt[0], dev)
     torch.cuda.synchronize()
     host_ms = (time.perf_counter() - t0) / (args.frames - 1) * 1e3
 
@@ -93,12 +126,19 @@ def main():
         trk._network()
     torch.cuda.synchronize()
     fwd_ms = (time.perf_counter() - t0) / 200 * 1e3
+    extra = {}
+    if motion:      # what the untrained segmentation head made of the last frame: the stages behind it run on the masked points
+        with torch.no_grad():
+            seg = model(trk.inputs)["seg_logits"][0]
+        extra = {"foreground_points_last_frame": int((seg[1] > seg[0]).sum()), "points_per_frame": int(seg.shape[1]),
+                 "crop_counts_last_frame": list(trk.log[-1])}
     print(json.dumps({
-        "workload": "%s tracking a %d-frame, %d-point synthetic sequence (random-init weights, eval, fp32)" % (args.model.upper(), args.frames, args.points),
+        "workload": "%s tracking a %d-frame, %d-point synthetic sequence (%s weights, eval, fp32)" % (
+            args.model.upper(), args.frames, args.points, "random-init, box-moving heads scaled" if motion else "random-init"),
         "device_loop_ms_per_frame": round(dev_ms, 4), "host_loop_ms_per_frame": round(host_ms, 4),
         "host_over_device": round(host_ms / dev_ms, 2), "forward_replay_ms": round(fwd_ms, 4),
         "front_end_ms_per_frame": round(dev_ms - fwd_ms, 4), "hip_graph": trk.graph is not None,
-        "largest_box_difference_between_the_loops": float(np.abs(dev_boxes - host_boxes).max())}))
+        "largest_box_difference_between_the_loops": float(np.abs(dev_boxes - host_boxes).max()), **extra}))
 
 
 if __name__ == "__main__":
