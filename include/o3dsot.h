@@ -724,6 +724,34 @@ int o3d_track_motion_input(const float* prev, int n_prev, const float* cur, int 
                            int zero_prev, int zero_this, const float* wlh, int first_frame, float* points,
                            float* candidate_bc, void* stream);
 
+/* ---- the same three steps for K targets of one scene per launch (tracking.MultiTargetTracker) ------------------------------
+ * o3d_track_crop_multi: ONE cloud against K boxes.  `groups` is a HOST table of 1 or 2 groups (a frame of the tracker: frame t
+ * against the K reference boxes, frame t-1 against the K result boxes); a group's `targets` is a DEVICE table of n_targets
+ * (1..O3D_CROP_MULTI_MAX_TARGETS) targets.  Every point is loaded once and tested against all targets of its group
+ * (O3D_CROP_MULTI_CHUNK of them staged in LDS at a time); per target, the rows written to out (capacity,3) and count[0] are
+ * bit-identical to an o3d_track_crop job with the same box, scale, offset, mode and capacity.  Three launches (count, scan,
+ * scatter), no waiting: csrc/track.hip.  scratch: at least o3d_track_crop_multi_scratch(groups, n_groups) int32 on the device
+ * (n_targets per workgroup of 256 points; -1: bad table). */
+#define O3D_CROP_MULTI_MAX_TARGETS 1024
+#define O3D_CROP_MULTI_CHUNK 32
+typedef struct { const float* box; float scale, offset; int mode; float* out; int capacity; int32_t* count; } o3d_crop_target;
+typedef struct { const float* points; int n; const o3d_crop_target* targets; int n_targets; } o3d_crop_group;
+long o3d_track_crop_multi_scratch(const o3d_crop_group* groups, int n_groups);
+int o3d_track_crop_multi(const o3d_crop_group* groups, int n_groups, int32_t* scratch, long scratch_len, void* stream);
+
+/* o3d_track_resample for a DEVICE table of n_jobs jobs in one launch (2K per frame: straight into rows of the batched static
+ * inputs (K,M,3) and (K,N,3)); per job the semantics of o3d_track_resample (zero-fill job; an index outside the source
+ * writes a zero row). */
+int o3d_track_resample_multi(const o3d_resample_job* jobs, int n_jobs, void* stream);
+
+/* o3d_track_offset_box for K targets in one launch, one thread per target: ref (K,15), offset (K,4) = o3d_best_proposal's
+ * output, yaw_state (K,10) | NULL, rebase (K) int32 | NULL, active (K) int32 | NULL, out (K,15) | NULL, results (T,K,15) | NULL
+ * with ONE shared frame counter.  Target k's box is bit-identical to o3d_track_offset_box called with seed + k; an inactive
+ * target writes its ref unchanged to out and to its results row and leaves its yaw_state alone. */
+int o3d_track_offset_box_multi(const float* ref, const float* offset, float* yaw_state, const int32_t* rebase,
+                               const int32_t* active, int K, int degrees, int use_z, int limit_box, int seed, float* out,
+                               float* results, int T, int32_t* frame, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@
 //   o3d_track_offset_box  getOffsetBB (:43-85) with the box sequence kept on the device
 //   o3d_track_motion_input  the network input of the motion tracker: MotionBaseModel.build_input_dict behind its two crops
 //                         (models/base_model.py:263-302)
+//   o3d_track_crop_multi / o3d_track_resample_multi / o3d_track_offset_box_multi
+//                         the same three steps for K targets of one scene per launch (tracking.MultiTargetTracker); every
+//                         target's result is bit-identical to the single-target entry point's
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -42,6 +45,21 @@
 // scratch[workgroup].  Launch 2: every workgroup sums the counts of the workgroups before it in its job (<= 469 integers for a
 // 120 000-point frame, out of L2), evaluates the predicate again and scatters its survivors behind that base, in their original
 // order.  Survivors beyond `capacity` are counted, not written.  Up to O3D_CROP_MAX_JOBS jobs share the two launches.
+//
+// ---- o3d_track_crop_multi: one cloud against K boxes, three launches, no workgroup ever waits for another --------------------
+// A group is one cloud of n points and a DEVICE table of K targets (box, scale, offset, mode, out, capacity, count); a call
+// takes 1 or 2 groups.  scratch holds, per group, K rows of W = ceil(n / 256) int32 (target-major).
+//   launch 1 (count)    workgroup w of a group loads its 256 points ONCE and tests them against all K targets, whose
+//                       parameters are staged in LDS CROP_MULTI_CHUNK at a time; per target a wave64 ballot + popcount, the
+//                       four waves summed through LDS -> scratch[k][w].  Reads: points, the table, the boxes.
+//   launch 2 (scan)     one workgroup per (group, target) replaces its OWN row scratch[k][0..W) by its exclusive prefix sums
+//                       and writes count[0] = the row's total.  It reads what launch 1 wrote, nothing of its own launch.
+//   launch 3 (scatter)  as launch 1, then every survivor goes to row scratch[k][w] + (survivors before it in the workgroup)
+//                       of the target's `out`, when that row is below `capacity`.  It reads what launch 2 wrote and writes
+//                       `out` only.
+// Within a launch no workgroup reads a word that another workgroup of that launch writes; the order between the launches is
+// the stream's.  There is no flag, no atomic and no loop that waits.  Every (point, target) decision is made by crop_xyz, the
+// arithmetic of crop_point above operation for operation, with no early rejection: rows and counts equal o3d_track_crop's.
 #include "o3d_common.hpp"
 
 namespace {
@@ -257,6 +275,224 @@ __global__ void offset_box_kernel(OffsetArgs a) {
     if (a.frame) a.frame[0] = k + 1;
 }
 
+// ---- K targets per launch ------------------------------------------------------------------------------------------------------
+constexpr int CROP_MULTI_CHUNK = O3D_CROP_MULTI_CHUNK;      // targets staged in LDS at a time (<= 32: one keep bit each)
+constexpr int CROP_MULTI_WORDS = 18;                        // box (15), scale, offset, mode
+
+struct CropMultiTable {
+    const float* points[2]; const o3d_crop_target* targets[2];
+    int n[2], K[2], wgs[2];                    // wgs: workgroups of 256 points of the group (1 for an empty cloud)
+    long sbase[2];                             // the group's first word in scratch
+    int n_groups;
+};
+
+// crop_point for a point held in registers and a target staged in LDS (P = box (15), scale, offset, mode as bits): the
+// same operations in the same order
+__device__ __forceinline__ bool crop_xyz(float px, float py, float pz, const float* P, float& qx, float& qy, float& qz) {
+    const float dx = px - P[0], dy = py - P[1], dz = pz - P[2];
+    const float w = P[3], l = P[4], h = P[5];
+    const float* R = P + 6;
+    const float scale = P[15], offset = P[16];
+    bool keep = true;
+    if (__float_as_int(P[17]) == O3D_CROP_MODEL) {
+        const float s4 = 4.f * scale, o2 = 2.f * offset;
+        const float L = (l * s4) * 0.5f, W = (w * s4) * 0.5f, H = (h * s4) * 0.5f;
+        const float e0 = ((fabsf(R[0]) * L + fabsf(R[1]) * W) + fabsf(R[2]) * H) + o2;
+        const float e1 = ((fabsf(R[3]) * L + fabsf(R[4]) * W) + fabsf(R[5]) * H) + o2;
+        const float e2 = ((fabsf(R[6]) * L + fabsf(R[7]) * W) + fabsf(R[8]) * H) + o2;
+        keep = fabsf(dx) < e0 && fabsf(dy) < e1 && fabsf(dz) < e2;
+    }
+    qx = (R[0] * dx + R[3] * dy) + R[6] * dz;
+    qy = (R[1] * dx + R[4] * dy) + R[7] * dz;
+    qz = (R[2] * dx + R[5] * dy) + R[8] * dz;
+    const float hx = (l * scale) * 0.5f + offset, hy = (w * scale) * 0.5f + offset, hz = (h * scale) * 0.5f + offset;
+    return keep && fabsf(qx) < hx && fabsf(qy) < hy && fabsf(qz) < hz;
+}
+
+template <bool SCATTER>
+__global__ __launch_bounds__(CROP_WG) void crop_multi_kernel(CropMultiTable t, int32_t* __restrict__ scratch) {
+    __shared__ float par[CROP_MULTI_CHUNK][CROP_MULTI_WORDS];
+    __shared__ int wave_cnt[CROP_MULTI_CHUNK][CROP_WG / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = (t.n_groups > 1 && (int)blockIdx.x >= t.wgs[0]) ? 1 : 0;
+    const int w = (int)blockIdx.x - (g ? t.wgs[0] : 0);
+    const int K = t.K[g], W = t.wgs[g];
+    const o3d_crop_target* __restrict__ T = t.targets[g];
+    int32_t* __restrict__ S = scratch + t.sbase[g];
+    const int i = w * CROP_WG + tid;
+    const bool in = i < t.n[g];
+    float px = 0.f, py = 0.f, pz = 0.f;
+    if (in) {
+        const float* p = t.points[g] + 3 * (long)i;
+        px = p[0]; py = p[1]; pz = p[2];
+    }
+    for (int k0 = 0; k0 < K; k0 += CROP_MULTI_CHUNK) {
+        const int nc = K - k0 < CROP_MULTI_CHUNK ? K - k0 : CROP_MULTI_CHUNK;
+        __syncthreads();                                   // the previous chunk's readers are done with par / wave_cnt
+        for (int e = tid; e < nc * CROP_MULTI_WORDS; e += CROP_WG) {
+            const int k = e / CROP_MULTI_WORDS, f = e - k * CROP_MULTI_WORDS;
+            const o3d_crop_target& J = T[k0 + k];
+            par[k][f] = f < 15 ? J.box[f] : f == 15 ? J.scale : f == 16 ? J.offset : __int_as_float(J.mode);
+        }
+        __syncthreads();
+        unsigned bits = 0u;                                // bit k: this thread's point survives target k0 + k
+        for (int k = 0; k < nc; ++k) {
+            float qx, qy, qz;
+            const bool keep = in && crop_xyz(px, py, pz, par[k], qx, qy, qz);
+            const unsigned long long mask = __ballot(keep);
+            if (lane == 0) wave_cnt[k][wave] = __popcll(mask);
+            if (keep) bits |= 1u << k;
+        }
+        __syncthreads();
+        if (!SCATTER) {
+            if (tid < nc) S[(long)(k0 + tid) * W + w] = (wave_cnt[tid][0] + wave_cnt[tid][1]) + (wave_cnt[tid][2] + wave_cnt[tid][3]);
+            continue;
+        }
+        for (int k = 0; k < nc; ++k) {
+            const bool keep = (bits >> k) & 1u;
+            const unsigned long long mask = __ballot(keep);
+            if (!keep) continue;
+            int pos = S[(long)(k0 + k) * W + w];           // the survivors of the workgroups before this one (launch 2)
+            for (int v = 0; v < wave; ++v) pos += wave_cnt[k][v];
+            pos += __popcll(mask & ((1ull << lane) - 1ull));
+            const o3d_crop_target& J = T[k0 + k];
+            if (pos < J.capacity) {
+                float qx, qy, qz;
+                crop_xyz(px, py, pz, par[k], qx, qy, qz);
+                float* o = J.out + 3 * (long)pos;
+                o[0] = qx; o[1] = qy; o[2] = qz;
+            }
+        }
+    }
+}
+
+// one workgroup per (group, target): its row of W counts -> exclusive prefix sums in place, count[0] = the total
+__global__ __launch_bounds__(CROP_WG) void crop_multi_scan_kernel(CropMultiTable t, int32_t* __restrict__ scratch) {
+    __shared__ int wave_sum[CROP_WG / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = (t.n_groups > 1 && (int)blockIdx.x >= t.K[0]) ? 1 : 0;
+    const int k = (int)blockIdx.x - (g ? t.K[0] : 0);
+    const int W = t.wgs[g];
+    int32_t* __restrict__ row = scratch + t.sbase[g] + (long)k * W;
+    int carry = 0;
+    for (int w0 = 0; w0 < W; w0 += CROP_WG) {
+        const int w = w0 + tid;
+        const int v = w < W ? row[w] : 0;
+        int incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int u = 0; u < CROP_WG / 64; ++u) {
+            if (u < wave) before += wave_sum[u];
+            total += wave_sum[u];
+        }
+        if (w < W) row[w] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();                                   // wave_sum is rewritten by the next pass
+    }
+    if (tid == 0) t.targets[g][k].count[0] = carry;
+}
+
+// resample_kernel's rows for a DEVICE table of jobs: blockIdx.x = the job, its rows strided over blockIdx.y and the threads
+__global__ __launch_bounds__(256) void resample_multi_kernel(const o3d_resample_job* __restrict__ jobs) {
+    const o3d_resample_job J = jobs[blockIdx.x];
+    for (int i = blockIdx.y * 256 + threadIdx.x; i < J.n; i += gridDim.y * 256) {
+        float x = 0.f, y = 0.f, z = 0.f;
+        if (!J.zero && J.src && J.idx) {
+            const int s = J.idx[i];
+            if ((unsigned)s < (unsigned)J.n_src) {    // an index outside the source is a caller's bug: the row stays zero
+                const float* p = J.src + 3 * (long)s;
+                x = p[0]; y = p[1]; z = p[2];
+            }
+        }
+        float* o = J.dst + 3 * (long)i;
+        o[0] = x; o[1] = y; o[2] = z;
+    }
+}
+
+struct OffsetMultiArgs {
+    const float* ref; const float* offset; float* yaw_state; const int32_t* rebase; const int32_t* active;
+    float* out; float* results; int32_t* frame;
+    int K, T, degrees, use_z, limit_box, seed;
+};
+
+// offset_box_kernel for target j of K: the same double arithmetic, expression for expression (ref, offset, yaw_state: the
+// target's rows; rebase, seed: the target's), -> box (15) and the updated yaw_state
+__device__ __forceinline__ void offset_box_one(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees,
+                                               int use_z, int limit_box, unsigned seed, unsigned k, float* box) {
+    float off[4] = {offset[0], offset[1], offset[2], offset[3]};
+    const float w = ref[3], l = ref[4], h = ref[5];
+    if (limit_box) {
+        if (off[0] > w) off[0] = limit_draw(seed, k, 0u);
+        if (off[1] > fminf(l, 2.f)) off[1] = limit_draw(seed, k, 1u);
+        if (use_z && off[2] > h) off[2] = 0.f;
+    }
+    const double theta = degrees ? (double)off[3] * (3.14159265358979323846 / 180.0) : (double)off[3];
+    double R0[9], yaw = theta;
+    if (yaw_state && !rebase) {
+        for (int i = 0; i < 9; ++i) R0[i] = yaw_state[i];
+        yaw = (double)yaw_state[9] + theta;
+    } else {
+        for (int i = 0; i < 9; ++i) R0[i] = ref[6 + i];
+    }
+    double Rr[9];
+    if (yaw_state && !rebase) {
+        double s, c;
+        sincos((double)yaw_state[9], &s, &c);
+        for (int r = 0; r < 3; ++r) {
+            Rr[3 * r] = R0[3 * r] * c + R0[3 * r + 1] * s;
+            Rr[3 * r + 1] = R0[3 * r + 1] * c - R0[3 * r] * s;
+            Rr[3 * r + 2] = R0[3 * r + 2];
+        }
+    } else {
+        for (int i = 0; i < 9; ++i) Rr[i] = R0[i];
+    }
+    const double ox = off[0], oy = off[1], oz = use_z ? (double)off[2] : 0.0;
+    for (int r = 0; r < 3; ++r) box[r] = (float)((double)ref[r] + ((Rr[3 * r] * ox + Rr[3 * r + 1] * oy) + Rr[3 * r + 2] * oz));
+    box[3] = w; box[4] = l; box[5] = h;
+    const float yaw_f = (float)yaw;
+    double s, c;
+    sincos(yaw_state ? (double)yaw_f : yaw, &s, &c);
+    for (int r = 0; r < 3; ++r) {
+        box[6 + 3 * r] = (float)(R0[3 * r] * c + R0[3 * r + 1] * s);
+        box[6 + 3 * r + 1] = (float)(R0[3 * r + 1] * c - R0[3 * r] * s);
+        box[6 + 3 * r + 2] = (float)R0[3 * r + 2];
+    }
+    if (yaw_state) {
+        if (rebase)
+            for (int i = 0; i < 9; ++i) yaw_state[i] = (float)R0[i];
+        yaw_state[9] = yaw_f;
+    }
+}
+
+// ONE workgroup: every thread reads the shared frame counter before thread 0 advances it
+__global__ __launch_bounds__(256) void offset_box_multi_kernel(OffsetMultiArgs a) {
+    const int k = a.frame ? a.frame[0] : 0;
+    __syncthreads();
+    for (int j = threadIdx.x; j < a.K; j += 256) {
+        const float* ref = a.ref + 15 * (long)j;
+        float box[15];
+        if (a.active && !a.active[j]) {
+            for (int i = 0; i < 15; ++i) box[i] = ref[i];
+        } else {
+            offset_box_one(ref, a.offset + 4 * (long)j, a.yaw_state ? a.yaw_state + 10 * (long)j : nullptr,
+                           a.rebase ? a.rebase[j] != 0 : 0, a.degrees, a.use_z, a.limit_box, (unsigned)a.seed + (unsigned)j,
+                           (unsigned)k, box);
+        }
+        for (int i = 0; i < 15; ++i) {
+            if (a.out) a.out[15 * (long)j + i] = box[i];
+            if (a.results && k >= 0 && k < a.T) a.results[15 * ((long)k * a.K + j) + i] = box[i];
+        }
+    }
+    if (a.frame && threadIdx.x == 0) a.frame[0] = k + 1;
+}
+
 }  // namespace
 
 extern "C" long o3d_track_crop_scratch(const o3d_crop_job* jobs, int n_jobs) {
@@ -341,5 +577,70 @@ extern "C" int o3d_track_motion_input(const float* prev, int n_prev, const float
     if (N == 0) return O3D_OK;
     MotionInputArgs a{{prev, cur}, {n_prev, n_this}, {zero_prev != 0, zero_this != 0}, idx, wlh, N, first_frame != 0, points, candidate_bc};
     hipLaunchKernelGGL(motion_input_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+// ---- K targets per launch ------------------------------------------------------------------------------------------------------
+static bool crop_multi_table(const o3d_crop_group* groups, int n_groups, CropMultiTable& t, long& need) {
+    if (!groups || n_groups < 1 || n_groups > 2) return false;
+    t = CropMultiTable{};
+    t.n_groups = n_groups;
+    need = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const o3d_crop_group& G = groups[g];
+        if (G.n < 0 || G.n > (1 << 30) || (G.n > 0 && !G.points) || !G.targets || G.n_targets < 1 ||
+            G.n_targets > O3D_CROP_MULTI_MAX_TARGETS)
+            return false;
+        t.points[g] = G.points; t.targets[g] = G.targets; t.n[g] = G.n; t.K[g] = G.n_targets;
+        t.wgs[g] = G.n > 0 ? o3d_cdiv(G.n, CROP_WG) : 1;
+        t.sbase[g] = need;
+        need += (long)t.wgs[g] * G.n_targets;
+    }
+    return true;
+}
+
+extern "C" long o3d_track_crop_multi_scratch(const o3d_crop_group* groups, int n_groups) {
+    CropMultiTable t;
+    long need;
+    return crop_multi_table(groups, n_groups, t, need) ? need : -1;
+}
+
+// groups: a HOST table of 1 or 2 groups; a group's `targets` is a DEVICE table of n_targets (1..O3D_CROP_MULTI_MAX_TARGETS)
+// targets whose boxes, out buffers and counts live on the device.  The host cannot read that table: a target whose capacity
+// is <= 0 is counted only; a mode other than O3D_CROP_MODEL crops as O3D_CROP_SUBWINDOW.  scratch: scratch_len >=
+// o3d_track_crop_multi_scratch(groups, n_groups) int32 on the device.  An empty cloud writes count = 0 for its targets.
+extern "C" int o3d_track_crop_multi(const o3d_crop_group* groups, int n_groups, int32_t* scratch, long scratch_len, void* stream) {
+    CropMultiTable t;
+    long need;
+    if (!crop_multi_table(groups, n_groups, t, need) || !scratch || scratch_len < need) return O3D_EINVAL;
+    const int wgs = t.wgs[0] + t.wgs[1], rows = t.K[0] + t.K[1];
+    hipLaunchKernelGGL(crop_multi_kernel<false>, dim3(wgs), dim3(CROP_WG), 0, o3d_stream(stream), t, scratch);
+    hipLaunchKernelGGL(crop_multi_scan_kernel, dim3(rows), dim3(CROP_WG), 0, o3d_stream(stream), t, scratch);
+    hipLaunchKernelGGL(crop_multi_kernel<true>, dim3(wgs), dim3(CROP_WG), 0, o3d_stream(stream), t, scratch);
+    return o3d_launch_status();
+}
+
+// o3d_track_resample for a DEVICE table of n_jobs jobs in one launch (the 2K gathers of a frame of K targets); the host
+// cannot read the table: a job with n <= 0 writes nothing, a job without src or idx is zero-filled
+extern "C" int o3d_track_resample_multi(const o3d_resample_job* jobs, int n_jobs, void* stream) {
+    if (n_jobs < 0 || n_jobs > (1 << 20) || (n_jobs > 0 && !jobs)) return O3D_EINVAL;
+    if (n_jobs == 0) return O3D_OK;
+    hipLaunchKernelGGL(resample_multi_kernel, dim3(n_jobs, 4), dim3(256), 0, o3d_stream(stream), jobs);
+    return o3d_launch_status();
+}
+
+// o3d_track_offset_box for K targets in one launch: ref (K,15), offset (K,4), yaw_state (K,10) | NULL, rebase (K) int32 | NULL
+// (per target; NULL = none), active (K) int32 | NULL (NULL = all), out (K,15) | NULL (may be ref), results (T,K,15) | NULL with
+// the ONE frame counter: every target's box goes to results[frame[0]][k], then frame[0] += 1.  Target k is updated as
+// o3d_track_offset_box updates it with seed + k (seed + K < 2^31); an inactive target's ref goes to out and results unchanged
+// and its yaw_state is not touched.
+extern "C" int o3d_track_offset_box_multi(const float* ref, const float* offset, float* yaw_state, const int32_t* rebase,
+                                          const int32_t* active, int K, int degrees, int use_z, int limit_box, int seed, float* out,
+                                          float* results, int T, int32_t* frame, void* stream) {
+    if (!ref || !offset || K < 1 || K > (1 << 20) || (!out && !results) || T < 0 || (results && (!frame || T < 1)) || seed < 0 ||
+        seed > 0x7fffffff - K)
+        return O3D_EINVAL;
+    OffsetMultiArgs a{ref, offset, yaw_state, rebase, active, out, results, frame, K, T, degrees, use_z, limit_box, seed};
+    hipLaunchKernelGGL(offset_box_multi_kernel, dim3(1), dim3(256), 0, o3d_stream(stream), a);
     return o3d_launch_status();
 }

@@ -88,6 +88,10 @@ capi.register("o3d_track_crop", [_vp, _i, _vp, _i, _vp])
 capi.register("o3d_track_resample", [_vp, _i, _vp])
 capi.register("o3d_track_offset_box", [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
 capi.register("o3d_track_motion_input", [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp])
+capi.register("o3d_track_crop_multi_scratch", [_vp, _i])
+capi.register("o3d_track_crop_multi", [_vp, _i, _vp, ctypes.c_long, _vp])
+capi.register("o3d_track_resample_multi", [_vp, _i, _vp])
+capi.register("o3d_track_offset_box_multi", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
 
 
 def _need_gpu(t, what):
@@ -148,6 +152,114 @@ def resample_jobs(jobs):
     with torch.cuda.device(dev):
         capi.check(capi.load().o3d_track_resample(ctypes.addressof(table), len(jobs), torch.cuda.current_stream(dev).cuda_stream),
                    "o3d_track_resample")
+
+
+# ---- K targets per launch (o3d_track_*_multi): the job tables live on the DEVICE ------------------------------------------------
+# The tables are arrays of C structs holding device pointers.  They are described here as numpy record types with the C
+# layout, so that a caller (tracking.MultiTargetTracker) fills a whole table in a pinned buffer with a few array assignments
+# and uploads it with one asynchronous copy.
+CROP_MULTI_MAX_TARGETS = 1024
+CROP_MULTI_CHUNK = 32                        # targets the crop stages in LDS at a time (O3D_CROP_MULTI_CHUNK)
+CROP_TARGET = np.dtype([("box", "u8"), ("scale", "f4"), ("offset", "f4"), ("mode", "i4"), ("out", "u8"), ("capacity", "i4"),
+                        ("count", "u8")], align=True)                                         # o3d_crop_target, 48 bytes
+RESAMPLE_JOB = np.dtype([("src", "u8"), ("n_src", "i4"), ("idx", "u8"), ("dst", "u8"), ("n", "i4"), ("zero", "i4")],
+                        align=True)                                                           # o3d_resample_job, 40 bytes
+assert CROP_TARGET.itemsize == 48 and RESAMPLE_JOB.itemsize == ctypes.sizeof(_ResampleJob) == 40
+
+
+class _CropGroup(ctypes.Structure):          # o3d_crop_group
+    _fields_ = [("points", _vp), ("n", _i), ("targets", _vp), ("n_targets", _i)]
+
+
+def crop_target_table(targets, device):
+    """targets: tuples (box15 GPU, scale, offset, mode, out (capacity,3) f32 GPU, count (1,) int32 GPU) -> the o3d_crop_target
+    table as a uint8 tensor on `device` (a blocking upload: for tests and tools; the tracker fills a pinned buffer).  The
+    caller keeps the tensors alive."""
+    tab = np.zeros((len(targets),), CROP_TARGET)
+    for k, (box, scale, offset, mode, out, count) in enumerate(targets):
+        assert box.is_cuda and box.dtype == torch.float32 and box.is_contiguous() and box.numel() == 15
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and count.is_cuda and count.dtype == torch.int32
+        tab[k] = (box.data_ptr(), scale, offset, mode, out.data_ptr(), out.shape[0], count.data_ptr())
+    return torch.from_numpy(tab.view(np.uint8)).to(device)
+
+
+def resample_job_table(jobs, device):
+    """jobs: tuples (src (n_src,3) | None, idx (n,) int32 | None, dst (n,3)) as resample_jobs takes -> the o3d_resample_job
+    table as a uint8 tensor on `device` (a blocking upload)"""
+    tab = np.zeros((len(jobs),), RESAMPLE_JOB)
+    for j, (src, idx, dst) in enumerate(jobs):
+        assert dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
+        n = dst.numel() // 3
+        if src is None:
+            tab[j] = (0, 0, 0, dst.data_ptr(), n, 1)
+        else:
+            assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() >= n
+            tab[j] = (src.data_ptr(), src.shape[0], idx.data_ptr(), dst.data_ptr(), n, 0)
+    return torch.from_numpy(tab.view(np.uint8)).to(device)
+
+
+def crop_multi(groups, scratch=None):
+    """One o3d_track_crop_multi call.  groups: 1 or 2 tuples (points (n,3) f32 GPU contiguous, table) with table a uint8 GPU
+    tensor of o3d_crop_target records (crop_target_table, or a CROP_TARGET array uploaded by the caller): every point of a
+    group is tested against all of its targets.  Nothing is read back here.  -> the scratch buffer (reuse it)."""
+    assert 1 <= len(groups) <= 2
+    dev = groups[0][0].device
+    table = (_CropGroup * len(groups))()
+    for g, (pts, tab) in enumerate(groups):
+        assert pts.is_cuda and pts.dtype == torch.float32 and pts.is_contiguous() and pts.dim() == 2 and pts.shape[1] == 3
+        assert tab.is_cuda and tab.dtype == torch.uint8 and tab.is_contiguous() and tab.numel() % CROP_TARGET.itemsize == 0
+        table[g] = _CropGroup(pts.data_ptr(), pts.shape[0], tab.data_ptr(), tab.numel() // CROP_TARGET.itemsize)
+    lib = capi.load()
+    need = lib.o3d_track_crop_multi_scratch(ctypes.addressof(table), len(groups))
+    if need < 0:
+        raise capi.O3DError("o3d_track_crop_multi: bad table (1..%d targets per group)" % CROP_MULTI_MAX_TARGETS)
+    if scratch is None or scratch.numel() < need:
+        scratch = torch.empty((max(need, 1),), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(lib.o3d_track_crop_multi(ctypes.addressof(table), len(groups), scratch.data_ptr(), scratch.numel(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_crop_multi")
+    return scratch
+
+
+def resample_multi(table, n_jobs=None):
+    """One o3d_track_resample_multi launch over a uint8 GPU tensor of o3d_resample_job records (resample_job_table, or a
+    RESAMPLE_JOB array uploaded by the caller); n_jobs: the first n_jobs records (default: all)."""
+    assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous()
+    n = table.numel() // RESAMPLE_JOB.itemsize if n_jobs is None else int(n_jobs)
+    assert n * RESAMPLE_JOB.itemsize <= table.numel()
+    dev = table.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_resample_multi(table.data_ptr(), n, torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_track_resample_multi")
+
+
+def offset_box_multi(ref, offset, yaw_state=None, out=None, results=None, frame=None, rebase=None, active=None, degrees=True,
+                     use_z=False, limit_box=True, seed=0):
+    """One o3d_track_offset_box_multi launch on device operands (no sync): ref (K,15), offset (K,4), yaw_state (K,10) | None,
+    out (K,15) | None, results (T,K,15) with frame (1,) int32 | None, rebase / active (K,) int32 | None.  Target k is updated
+    as offset_box updates it with seed + k.  -> out (allocated when None and no results)."""
+    _need_gpu(ref, "offset_box_multi")
+    _need_gpu(offset, "offset_box_multi")
+    dev, K = ref.device, ref.numel() // 15
+    assert ref.dtype == torch.float32 and ref.is_contiguous() and ref.numel() == 15 * K and K >= 1
+    assert offset.dtype == torch.float32 and offset.is_contiguous() and offset.numel() == 4 * K
+    if out is None and results is None:
+        out = torch.empty((K, 15), dtype=torch.float32, device=dev)
+    for t, width, dt in ((yaw_state, 10, torch.float32), (out, 15, torch.float32), (rebase, 1, torch.int32), (active, 1, torch.int32)):
+        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == width * K)
+    if results is not None:
+        assert results.is_cuda and results.dtype == torch.float32 and results.is_contiguous() and results.numel() % (15 * K) == 0
+        assert frame is not None and frame.dtype == torch.int32
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_offset_box_multi(
+            ref.data_ptr(), offset.data_ptr(), ptr(yaw_state), ptr(rebase), ptr(active), K, int(bool(degrees)), int(bool(use_z)),
+            int(bool(limit_box)), int(seed) & 0x3fffffff, ptr(out), ptr(results),
+            results.numel() // (15 * K) if results is not None else 0, ptr(frame), torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_offset_box_multi")
+    return out
 
 
 def _crop(points, box, scale, offset, mode, what):

@@ -159,13 +159,8 @@ def make_motion_batch(first_index, batch_size, point_sample_size=1024, seed0=432
     return {k: np.stack([o[k] for o in out], 0) for k in out[0]}
 
 
-def make_sequence(seed, n_frames, n_points):
-    """A seeded LiDAR-like sequence for the tracking loop (open3dsot_amd/tracking.py): `n_frames` frames of about `n_points`
-    points shaped like a KITTI sweep -- a ground plane (60 % of the points, 3 cm noise) and uniform clutter, both out to
-    +-60 m around the sensor, and one car-sized box (1/16 of the points, at least 64, sampled like `_surface`: a close
-    target, so that its search window holds more points than the network's input and is resampled without duplicates) on a
-    smooth yawing path that starts 15-25 m from the sensor, standing on the ground.
-    -> (frames: list of (n,3) float32, gt_boxes (n_frames,15) float32 = [centre | wlh | rotation matrix row-major])."""
+def _sequence64(seed, n_frames, n_points):
+    """make_sequence before its float32 cast -> (frames: list of (n,3) float64, boxes: list of (centre, wlh, rot (3,3)))"""
     rng = np.random.default_rng([int(seed), 0x5E9])
     wlh = np.array([1.6, 3.9, 1.5]) * rng.uniform(0.9, 1.1, 3)
     ground = -1.73
@@ -182,11 +177,46 @@ def make_sequence(seed, n_frames, n_points):
         gnd = np.stack([rng.uniform(-60, 60, n_gnd), rng.uniform(-60, 60, n_gnd), ground + rng.normal(0, 0.03, n_gnd)], 1)
         clu = np.stack([rng.uniform(-60, 60, n_clu), rng.uniform(-60, 60, n_clu), rng.uniform(ground, ground + 6, n_clu)], 1)
         pts = np.concatenate([obj, gnd, clu], 0)
-        frames.append(pts[rng.permutation(pts.shape[0])].astype(np.float32))
-        boxes.append(np.concatenate([center, wlh, rot.reshape(-1)]).astype(np.float32))
+        frames.append(pts[rng.permutation(pts.shape[0])])
+        boxes.append((center, wlh, rot))
         pos = pos + speed * np.array([np.cos(yaw), np.sin(yaw)])
         yaw = yaw + rate
-    return frames, np.stack(boxes, 0)
+    return frames, boxes
+
+
+def make_sequence(seed, n_frames, n_points):
+    """A seeded LiDAR-like sequence for the tracking loop (open3dsot_amd/tracking.py): `n_frames` frames of about `n_points`
+    points shaped like a KITTI sweep -- a ground plane (60 % of the points, 3 cm noise) and uniform clutter, both out to
+    +-60 m around the sensor, and one car-sized box (1/16 of the points, at least 64, sampled like `_surface`: a close
+    target, so that its search window holds more points than the network's input and is resampled without duplicates) on a
+    smooth yawing path that starts 15-25 m from the sensor, standing on the ground.
+    -> (frames: list of (n,3) float32, gt_boxes (n_frames,15) float32 = [centre | wlh | rotation matrix row-major])."""
+    frames, boxes = _sequence64(seed, n_frames, n_points)
+    return ([f.astype(np.float32) for f in frames],
+            np.stack([np.concatenate([c, wlh, rot.reshape(-1)]).astype(np.float32) for c, wlh, rot in boxes], 0))
+
+
+def scene_subseed(seed, j):
+    """the make_sequence seed of sub-scene j of make_scene(seed, ...)"""
+    return 1024 * int(seed) + int(j)
+
+
+def make_scene(seed, n_frames, n_points, n_targets):
+    """A scene with several targets in the same sweeps (open3dsot_amd/tracking.py::MultiTargetTracker): the `n_targets`
+    sequences make_sequence(scene_subseed(seed, j), n_frames, n_points), j = 0 .. n_targets-1 (n_points each), sequence j
+    rotated about z by 2 pi j / n_targets (in fp64, before the float32 cast) so that the targets start in different
+    sectors, merged frame by frame in the order of j.  Sub-scene 0 is not rotated: its points are the first rows of every
+    frame and its boxes are make_sequence's.
+    -> (frames: list of (n_targets * n,3) float32, gt_boxes (n_frames, n_targets, 15) float32)."""
+    assert 1 <= n_targets <= 1024
+    parts, boxes = [], np.zeros((n_frames, n_targets, 15), np.float32)
+    for j in range(n_targets):
+        fr, bx = _sequence64(scene_subseed(seed, j), n_frames, n_points)
+        rz = _rotz(2.0 * np.pi * j / n_targets) if j else np.eye(3)
+        parts.append([f @ rz.T for f in fr])
+        for t, (c, wlh, rot) in enumerate(bx):
+            boxes[t, j] = np.concatenate([rz @ c, wlh, (rz @ rot).reshape(-1)]).astype(np.float32)
+    return [np.concatenate([p[t] for p in parts], 0).astype(np.float32) for t in range(n_frames)], boxes
 
 
 def to_torch(batch, device=None):

@@ -21,6 +21,7 @@ device-side sampler would remove the sync and change every index; it is out of s
 The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
 (`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
 """
+import collections
 import os
 
 import numpy as np
@@ -49,6 +50,35 @@ def draw_indices(num_points, sample_size):
     if num_points == sample_size:
         return np.arange(num_points)
     return np.random.default_rng(1).choice(num_points, size=sample_size, replace=sample_size > num_points)
+
+
+class DrawCache:
+    """draw_indices memoised: its result depends on (num_points, sample_size) alone, and a frame of K targets asks for 2K
+    draws.  get() -> the int32 indices (read-only, shared between callers) or None for the zero-fill case.  Bounded: the
+    least recently used pair goes when `maxsize` pairs are held."""
+
+    def __init__(self, maxsize=2048):
+        self.maxsize, self.hits, self.misses = int(maxsize), 0, 0
+        self._held = collections.OrderedDict()
+
+    def get(self, num_points, sample_size):
+        key = (int(num_points), int(sample_size))
+        if key in self._held:
+            self.hits += 1
+            self._held.move_to_end(key)
+            return self._held[key]
+        self.misses += 1
+        idx = draw_indices(*key)
+        if idx is not None:
+            idx = idx.astype(np.int32)
+            idx.setflags(write=False)
+        self._held[key] = idx
+        if len(self._held) > self.maxsize:
+            self._held.popitem(last=False)
+        return idx
+
+    def __len__(self):
+        return len(self._held)
 
 
 class _DeviceTracker:
@@ -115,15 +145,24 @@ class _DeviceTracker:
     def _crop_counts(self, make_jobs):
         """The frame's one crop call + the count read-back.  make_jobs() -> [(crop job, grow)]: the job's count lands in
         counts[j]; grow(n) is called when its n survivors exceed the job's buffer, and the call is made again.  -> counts"""
-        while True:
+        def launch():
             jobs = make_jobs()
             self.scratch = PU.crop_jobs([j for j, _ in jobs], self.scratch)
+            return [(job[5].shape[0], grow) for job, grow in jobs]
+        return self._counts_loop(launch)
+
+    def _counts_loop(self, launch):
+        """launch() makes the crop call and -> [(capacity, grow)], one per count in `counts`; the counts are read back (the
+        one sync of the frame); where one exceeds its capacity, grow(n) is called once with the largest such n and the call
+        is made again.  -> counts"""
+        while True:
+            caps = launch()
             self.counts_host.copy_(self.counts, non_blocking=True)
             torch.cuda.current_stream(self.dev).synchronize()                    # the one sync of the frame
-            ns = [int(self.counts_host[j]) for j in range(len(jobs))]
+            ns = self.counts_host[:len(caps)].tolist()
             over = {}                                                            # grow -> its largest overflowing count
-            for n, (job, grow) in zip(ns, jobs):
-                if n > job[5].shape[0]:
+            for n, (cap, grow) in zip(ns, caps):
+                if n > cap:
                     over[grow] = max(n, over.get(grow, 0))
             if not over:
                 return ns
@@ -286,6 +325,254 @@ class SequenceTracker(_DeviceTracker):
         return c.boxes[c.t - 1]
 
 
+class MultiTargetTracker(_DeviceTracker):
+    """Device-resident tracking loop for K targets in the same frames (the matching trackers: trackers.BAT, trackers.P2B).
+    What SequenceTracker does per target happens here once per frame for all of them:
+
+        trk = MultiTargetTracker(model, K)      # model on the GPU, eval mode
+        trk.init(points0, boxes0)               # (N,3) float32 GPU tensor; boxes0 (K,15) or K boxes as pack_box takes them
+        boxes = trk.update(points)              # a (K,15) device VIEW of the new boxes (no sync for it)
+        all_boxes = trk.results()               # (T,K,15) on the host, one sync
+
+    Per frame t >= 1, whatever K:
+
+      o3d_track_crop_multi, one call    group 0: frame t against the K reference boxes (search windows); group 1: frame t-1
+                                        against the K result boxes (model crops, appended to each target's bank).  Every
+                                        point is read once per group.  (Its 96 K-byte target table is uploaded in front.)
+      pinned read-back of 2K counts     the one host sync of the frame, shared by the K targets
+      2K index draws                    default_rng(1).choice, memoised by (count, size): DrawCache
+      one upload                        the 2K resample jobs and the K (template_size + search_size) indices, one pinned buffer
+      o3d_track_resample_multi          all 2K gathers straight into rows of the batched static inputs (K,M,3), (K,N,3)
+      o3d_boxcloud, B = K               the templates' BoxClouds against the canonical boxes (BAT only)
+      forward + o3d_best_proposal       batch K, replayed as one HIP graph captured once per tracker (eager when the capture
+                                        fails, unless O3D_REQUIRE_GRAPH=1)
+      o3d_track_offset_box_multi        the K new boxes into row t of the (T,K,15) results buffer
+
+    The template bank is per target: bank[k] holds target k's crops with SequenceTracker's slot rules for the four
+    shape_aggregation modes.  `update(points, ref_boxes=...)` (K,15): the reference's `reference_BB: previous_gt / current_gt`.
+    `seed`: target k's limit_box draws use seed + k.  log, per frame: (search counts (K), model counts (K) | None, template
+    counts (K)); crop_calls: the crop calls since init (one per frame, one more whenever a crop outgrew its buffer)."""
+    _NAME = "MultiTargetTracker"
+
+    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
+        from .m2track import M2TRACK
+        if isinstance(model, M2TRACK):
+            raise TypeError("MultiTargetTracker serves the matching trackers (BAT, P2B); the motion tracker follows one "
+                            "target per MotionSequenceTracker")
+        K = int(n_targets)
+        if not 1 <= K <= PU.CROP_MULTI_MAX_TARGETS:
+            raise ValueError("n_targets must be 1..%d" % PU.CROP_MULTI_MAX_TARGETS)
+        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS)
+        self.K = K
+        self.aggregation = _aggregation(self.shape_aggregation)
+        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
+            raise ValueError("reference_BB %r" % (self.reference_BB,))
+        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
+        self.with_boxcloud = hasattr(model, "mlp_bc")
+        dev, M, N = self.dev, int(self.template_size), int(self.search_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        # the state of _DeviceTracker, one row per target
+        self.counts = torch.zeros((2 * K,), **i32)                 # [0:K] search, [K:2K] model
+        self.counts_host = torch.zeros((2 * K,), dtype=torch.int32).pin_memory()
+        self.cur = torch.zeros((K, 15), **f32)
+        self.yaw_state = torch.zeros((K, 10), **f32)
+        self.canon_wlh = torch.zeros((K, 3), **f32)                # the canonical boxes: zero centre, wlh, identity
+        self.canon_centre = torch.zeros((K, 3), **f32)
+        self.canon_rot = torch.eye(3, **f32).reshape(1, 9).repeat(K, 1).contiguous()
+        self.boxes = torch.zeros((int(max_frames), K, 15), **f32)
+        self.active = torch.ones((K,), **i32)
+        self.rebase_all = torch.ones((K,), **i32)
+        self.retired = set()                                       # the host's copy of `active == 0`
+        self.inputs = {"template_points": torch.zeros((K, M, 3), **f32), "search_points": torch.zeros((K, N, 3), **f32)}
+        if self.with_boxcloud:
+            self.inputs["points2cc_dist_t"] = torch.zeros((K, M, 9), **f32)
+        self.search_buf = torch.empty((K, int(search_capacity), 3), **f32)
+        self.model_capacity = int(model_capacity)
+        self.bank = torch.empty((K, 2 * self.model_capacity, 3), **f32)
+        # the crop's target table, [0:K] search, [K:2K] model
+        self.crop_tab_host = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8).pin_memory()
+        self.crop_tab = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8, device=dev)
+        self.crop_rec = self.crop_tab_host.numpy().view(PU.CROP_TARGET)
+        # the frame's one upload: 2K resample jobs [template 0..K-1, search 0..K-1], then the K * (M + N) indices
+        jb = 2 * K * PU.RESAMPLE_JOB.itemsize
+        self.stage_host = torch.zeros((jb + 4 * K * (M + N),), dtype=torch.uint8).pin_memory()
+        self.stage = torch.zeros((jb + 4 * K * (M + N),), dtype=torch.uint8, device=dev)
+        self.job_rec = self.stage_host.numpy()[:jb].view(PU.RESAMPLE_JOB)
+        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, M + N)
+        self.idx_ptr = self.stage.data_ptr() + jb
+        self.draws = DrawCache()
+        self.bank_fixed = np.zeros((K,), np.int64)
+        self.bank_total = np.zeros((K,), np.int64)
+        self.crop_calls = 0
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    def _pack_boxes(self, boxes):
+        if torch.is_tensor(boxes) or isinstance(boxes, np.ndarray):
+            b = PU._dev32(boxes, self.dev).reshape(-1, 15)
+        else:
+            b = torch.stack([PU.pack_box(x, self.dev) for x in boxes])
+        if b.shape[0] != self.K:
+            raise ValueError("%d boxes for %d targets" % (b.shape[0], self.K))
+        return b.contiguous()
+
+    def init(self, points0, boxes0):
+        PU._need_gpu(points0, "MultiTargetTracker.init")
+        b = self._pack_boxes(boxes0)
+        self.cur.copy_(b)
+        self.yaw_state[:, :9].copy_(b[:, 6:15])
+        self.yaw_state[:, 9] = 0.0
+        self.canon_wlh.copy_(b[:, 3:6])
+        self.boxes[0].copy_(b)
+        self.frame.fill_(1)
+        self.active.fill_(1)
+        self.retired.clear()
+        self.prev_points = points0.contiguous().float()
+        self.bank_fixed[:], self.bank_total[:] = 0, 0
+        self.t, self.log, self.crop_calls = 1, [], 0
+        return self.boxes[0]
+
+    def set_box(self, k, box):
+        """Overwrite target k's last result box (SequenceTracker.set_box for one target)."""
+        b = PU.pack_box(box, self.dev)
+        self.cur[k].copy_(b)
+        self.yaw_state[k, :9].copy_(b[6:15])
+        self.yaw_state[k, 9] = 0.0
+        self.boxes[self.t - 1, k].copy_(b)
+
+    def retire(self, k):
+        """Stop following target k: from the next update on its rows repeat its last box and its yaw state stays as it is.
+        Its slot is NOT compacted away -- it still runs through the crops, the resampling and the network (the batch keeps
+        its shape, so the captured graph stays valid); only its box update is switched off.  Under a reference_BB rule that takes the caller's boxes, its row of `ref_boxes` is
+        ignored: its reference stays its own last box."""
+        self.active[k] = 0
+        self.retired.add(int(k) % self.K)
+
+    def _grow_boxes(self):
+        if self.t >= self.boxes.shape[0]:
+            bigger = torch.zeros((2 * self.boxes.shape[0], self.K, 15), dtype=torch.float32, device=self.dev)
+            bigger[:self.boxes.shape[0]].copy_(self.boxes)
+            self.boxes = bigger
+
+    def _model_slots(self):
+        """where this frame's model crops go in each target's bank (K,), or None when the templates do not change"""
+        if self.aggregation == "first":
+            return np.zeros((self.K,), np.int64) if self.t == 1 else None
+        if self.aggregation == "previous":
+            return np.zeros((self.K,), np.int64)
+        if self.aggregation == "firstandprevious":
+            return np.zeros((self.K,), np.int64) if self.t == 1 else self.bank_fixed.copy()
+        return self.bank_total.copy()                             # all: appended
+
+    def _ensure_bank(self, need):
+        if need > self.bank.shape[1]:
+            old = self.bank
+            self.bank = torch.empty((self.K, max(need, 2 * old.shape[1]), 3), dtype=torch.float32, device=self.dev)
+            self.bank[:, :old.shape[1]].copy_(old)
+
+    def _crops(self, pts, ref, slots):
+        """the frame's one crop call + the count read-back -> (search counts (K), model counts (K) | None)"""
+        c, K = self, self.K
+        k15 = 60 * np.arange(K, dtype=np.uint64)
+
+        def grow_search(n):
+            c.search_buf = torch.empty((K, 2 * n, 3), dtype=torch.float32, device=c.dev)
+
+        def grow_model(n):
+            c.model_capacity = 2 * n
+
+        def launch():
+            rec, kk = c.crop_rec, np.arange(K, dtype=np.uint64)
+            s = rec[:K]
+            s["box"], s["scale"], s["offset"], s["mode"] = ref.data_ptr() + k15, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW
+            s["out"], s["capacity"] = c.search_buf.data_ptr() + 12 * c.search_buf.shape[1] * kk, c.search_buf.shape[1]
+            s["count"] = c.counts.data_ptr() + 4 * kk
+            groups, caps = [(pts, c.crop_tab[:K * PU.CROP_TARGET.itemsize])], [(c.search_buf.shape[1], grow_search)] * K
+            if slots is not None:
+                c._ensure_bank(int(slots.max()) + c.model_capacity)
+                m = rec[K:]
+                m["box"], m["scale"], m["offset"], m["mode"] = c.cur.data_ptr() + k15, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL
+                m["out"] = c.bank.data_ptr() + 12 * (c.bank.shape[1] * kk + slots.astype(np.uint64))
+                m["capacity"], m["count"] = c.model_capacity, c.counts.data_ptr() + 4 * (kk + np.uint64(K))
+                groups.append((c.prev_points, c.crop_tab[K * PU.CROP_TARGET.itemsize:]))
+                caps += [(c.model_capacity, grow_model)] * K
+            c.crop_tab.copy_(c.crop_tab_host, non_blocking=True)
+            c.scratch = PU.crop_multi(groups, c.scratch)
+            c.crop_calls += 1                  # one per frame, one more whenever a crop outgrew its buffer
+            return caps
+        ns = c._counts_loop(launch)
+        return np.array(ns[:K], np.int64), (np.array(ns[K:], np.int64) if slots is not None else None)
+
+    # ---- one frame ---------------------------------------------------------------------------------------------------------
+    def update(self, points, ref_boxes=None):
+        PU._need_gpu(points, "MultiTargetTracker.update")
+        if self.t < 1:
+            raise RuntimeError("MultiTargetTracker.update before init")
+        if self.needs_ref_box and ref_boxes is None:
+            raise ValueError("reference_BB %r needs update(points, ref_boxes=...)" % (self.reference_BB,))
+        with torch.cuda.device(self.dev):
+            return self._update(points.contiguous().float(), ref_boxes)
+
+    def _update(self, pts, ref_boxes):
+        c, K, M, N = self, self.K, int(self.template_size), int(self.search_size)
+        c._grow_boxes()
+        ref = c.cur if ref_boxes is None else c._pack_boxes(ref_boxes)
+        if ref_boxes is not None and c.retired:        # a retired target's reference is its own last box, not the caller's
+            rows = sorted(c.retired)
+            ref = ref.clone()
+            ref[rows] = c.cur[rows]
+        slots = c._model_slots()
+        ns, nm = c._crops(pts, ref, slots)
+        if slots is not None:
+            c.bank_total = slots + nm
+            if c.t == 1:
+                c.bank_fixed = nm.copy()               # the first frame's crops stay at the head of the banks
+                if c.aggregation == "firstandprevious":            # getModel([first, previous]) at t = 1: the same crop twice
+                    c._ensure_bank(2 * int(nm.max()) + c.model_capacity)
+                    for k in range(K):
+                        c.bank[k, nm[k]:2 * nm[k]].copy_(c.bank[k, :nm[k]])
+                    c.bank_total = 2 * nm
+        nt = c.bank_total.copy()
+        # the frame's one upload: the indices and the 2K resample jobs
+        zero = np.zeros((2 * K,), np.int32)
+        for k in range(K):
+            it, isr = c.draws.get(nt[k], M), c.draws.get(ns[k], N)
+            if it is None:
+                zero[k] = 1
+            else:
+                c.idx_rec[k, :M] = it
+            if isr is None:
+                zero[K + k] = 1
+            else:
+                c.idx_rec[k, M:] = isr
+        kk = np.arange(K, dtype=np.uint64)
+        j = c.job_rec
+        j["src"][:K], j["src"][K:] = c.bank.data_ptr() + 12 * c.bank.shape[1] * kk, c.search_buf.data_ptr() + 12 * c.search_buf.shape[1] * kk
+        j["n_src"][:K], j["n_src"][K:] = nt, ns
+        j["idx"][:K], j["idx"][K:] = c.idx_ptr + 4 * (M + N) * kk, c.idx_ptr + 4 * ((M + N) * kk + np.uint64(M))
+        j["dst"][:K], j["dst"][K:] = c.inputs["template_points"].data_ptr() + 12 * M * kk, c.inputs["search_points"].data_ptr() + 12 * N * kk
+        j["n"][:K], j["n"][K:] = M, N
+        j["zero"] = zero
+        c.stage.copy_(c.stage_host, non_blocking=True)
+        PU.resample_multi(c.stage, 2 * K)
+        if c.with_boxcloud:
+            capi.check(capi.load().o3d_boxcloud(c.inputs["template_points"].data_ptr(), c.canon_centre.data_ptr(), c.canon_wlh.data_ptr(),
+                                                c.canon_rot.data_ptr(), 1.0, K, M, c.inputs["points2cc_dist_t"].data_ptr(),
+                                                torch.cuda.current_stream(c.dev).cuda_stream), "o3d_boxcloud")
+        best, _ = c._network()
+        PU.offset_box_multi(ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame,
+                            rebase=c.rebase_all if ref_boxes is not None else None, active=c.active, degrees=c.degrees,
+                            use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        c.prev_points = pts
+        c.log.append((ns, nm, nt))
+        c.t += 1
+        return c.boxes[c.t - 1]
+
+    def results(self):
+        """(T,K,15) float32 on the host: row 0 the initial boxes, row t the results of frame t (one sync)"""
+        return self.boxes[:self.t].cpu().numpy()
+
+
 # cfgs/M2_track_kitti.yaml :5-8,32-33
 _MOTION_DEFAULTS = dict(bb_scale=1.25, bb_offset=2, point_sample_size=1024, degrees=False, use_z=True, limit_box=False)
 
@@ -376,4 +663,15 @@ def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
             trk.update(frames[t])
         else:
             trk.update(frames[t], ref_boxes[t])
+    return trk.results()
+
+
+def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None):
+    """track_sequence for K targets in the same frames: boxes0 (K,15) the targets' boxes in frames[0]; ref_boxes[t] (K,15)
+    (optional) is handed to update() of frame t.  -> (T,K,15) result boxes on the host."""
+    b0 = boxes0 if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray) else list(boxes0)
+    trk = MultiTargetTracker(model, len(b0), seed=seed, use_graph=use_graph)
+    trk.init(frames[0], b0)
+    for t in range(1, len(frames)):
+        trk.update(frames[t], None if ref_boxes is None else ref_boxes[t])
     return trk.results()

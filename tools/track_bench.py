@@ -2,6 +2,7 @@
 had to write before it existed, on the same box in the same run.  Not bench.py: that measures the network alone.
 
   python tools/track_bench.py [--frames 200] [--points 120000] [--model BAT | P2B | M2TRACK]
+  python tools/track_bench.py --targets K [--frames 200] [--points 120000] [--model BAT | P2B]
 
 Both loops track the same synth.make_sequence with a random-init model in eval mode and start from the frames resident in
 HBM (device loop) / in host memory (host loop: where a dataset reader leaves them).
@@ -13,6 +14,11 @@ HBM (device loop) / in host memory (host loop: where a dataset reader leaves the
                 restated in numpy (tests/motion_oracle.py::host_input: two crops, two index draws, time stamp, prior-targetness
                 mask, candidate BoxCloud) -> upload -> model.evaluate_one_sample -> read back -> getOffsetBB in numpy
 Prints one JSON line with both figures and their ratio.
+
+--targets K: K targets in the same frames (synth.make_scene, --points after merging): tracking.MultiTargetTracker, one batched
+loop, against K SequenceTrackers run one after another over the same frames in the same process.  Both start from the
+frames resident in HBM.  Prints one JSON line: ms per frame of both, targets x frames per second, their ratio and the
+largest difference between the boxes of the two (batch-K against batch-1 forward, compounding over the sequence).
 """
 import argparse
 import json
@@ -67,17 +73,80 @@ def motion_host_loop(model, cfg, frames, box0, dev):
     return np.stack(boxes)
 
 
+def multi_target_main(args, dev):
+    K = args.targets
+    cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+    cfg.update(TO.TEST_KEYS)
+    # the tracking fixture's weights: a He-initialised head moves every box by metres per frame, off its target
+    model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+    frames, gt = synth.make_scene(args.seed, args.frames, max(args.points // K, 1024), K)
+    dframes = [torch.from_numpy(f).to(dev) for f in frames]
+    warm = min(20, args.frames)
+
+    def run_multi(n):
+        for t in range(1, n):
+            multi.update(dframes[t])
+        return multi.results()                                          # the one read-back of the boxes (a sync)
+
+    def run_singles(n):
+        out = []
+        for k, s in enumerate(singles):                                 # one target after another
+            s.init(dframes[0], gt[0, k])
+            for t in range(1, n):
+                s.update(dframes[t])
+            out.append(s.results())
+        return np.stack(out, 1)
+
+    multi = tracking.MultiTargetTracker(model, K)
+    multi.init(dframes[0], gt[0])
+    run_multi(warm)                                                     # capture + warm-up
+    torch.cuda.synchronize()
+    multi.init(dframes[0], gt[0])
+    t0 = time.perf_counter()
+    multi_boxes = run_multi(args.frames)
+    multi_ms = (time.perf_counter() - t0) / (args.frames - 1) * 1e3
+
+    singles = [tracking.SequenceTracker(model) for _ in range(K)]
+    run_singles(warm)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    single_boxes = run_singles(args.frames)
+    single_ms = (time.perf_counter() - t0) / (args.frames - 1) * 1e3
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        multi._network()
+    torch.cuda.synchronize()
+    fwd_ms = (time.perf_counter() - t0) / 200 * 1e3
+    diff = np.abs(multi_boxes - single_boxes).reshape(args.frames, -1).max(1)
+    print(json.dumps({
+        "workload": "%s tracking %d targets through a %d-frame, %d-point synthetic scene (fixture weights, eval, fp32)" % (
+            args.model.upper(), K, args.frames, int(frames[0].shape[0])),
+        "targets": K, "batched_loop_ms_per_frame": round(multi_ms, 4), "sequential_loops_ms_per_frame": round(single_ms, 4),
+        "one_sequential_loop_ms_per_frame": round(single_ms / K, 4), "sequential_over_batched": round(single_ms / multi_ms, 2),
+        "batched_target_frames_per_s": round(K * 1e3 / multi_ms, 1), "sequential_target_frames_per_s": round(K * 1e3 / single_ms, 1),
+        "batched_forward_replay_ms": round(fwd_ms, 4), "batched_front_end_ms_per_frame": round(multi_ms - fwd_ms, 4),
+        "hip_graph": multi.graph is not None, "crop_calls": multi.crop_calls,
+        "largest_box_difference_frame_1": float(diff[1]), "largest_box_difference": float(diff.max())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--points", type=int, default=120000)
     ap.add_argument("--model", default="BAT")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--targets", type=int, default=0, help="K > 0: MultiTargetTracker against K SequenceTrackers in turn")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("track_bench.py needs a GPU: the HIP library is the only compute path (no CPU fallback)")
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
+    if args.targets > 0:
+        if args.model.upper() == "M2TRACK":
+            raise SystemExit("--targets serves the matching trackers (BAT, P2B): the motion tracker stays single-target")
+        return multi_target_main(args, dev)
     motion = args.model.upper() == "M2TRACK"
     if motion:
         # the fixture's weights (tests/motion_oracle.py::init_weights) with the three box-moving heads scaled by a further 0.02:
