@@ -58,13 +58,16 @@
 //                       of the target's `out`, when that row is below `capacity`.  It reads what launch 2 wrote and writes
 //                       `out` only.
 // Within a launch no workgroup reads a word that another workgroup of that launch writes; the order between the launches is
-// the stream's.  There is no flag, no atomic and no loop that waits.  Every (point, target) decision is made by crop_xyz, the
-// arithmetic of crop_point above operation for operation, with no early rejection: rows and counts equal o3d_track_crop's.
+// the stream's.  There is no flag, no atomic and no loop that waits.  Every (point, target) decision is made by crop_test, the
+// one function that o3d_track_crop calls too, with no early rejection: rows and counts equal o3d_track_crop's.
 #include "o3d_common.hpp"
 
 namespace {
 
 constexpr int CROP_WG = 256;
+
+// workgroups of a cloud of n points: an empty cloud keeps one, which writes count = 0
+inline int crop_wgs(int n) { return n > 0 ? o3d_cdiv(n, CROP_WG) : 1; }
 
 struct CropTable {
     o3d_crop_job job[O3D_CROP_MAX_JOBS];
@@ -72,15 +75,16 @@ struct CropTable {
     int n_jobs;
 };
 
-// keep? and q for one point, in the operation order of the header comment
-__device__ __forceinline__ bool crop_point(const o3d_crop_job& J, const float* __restrict__ box, int i, float& qx, float& qy, float& qz) {
-    const float* p = J.points + 3 * (long)i;
-    const float dx = p[0] - box[0], dy = p[1] - box[1], dz = p[2] - box[2];
+// keep? and q for the point p against `box` (15), in the operation order of the header comment: THE crop test, of both
+// o3d_track_crop (box in global memory) and o3d_track_crop_multi (box staged in LDS)
+__device__ __forceinline__ bool crop_test(float px, float py, float pz, const float* box, float scale, float offset, int mode,
+                                          float& qx, float& qy, float& qz) {
+    const float dx = px - box[0], dy = py - box[1], dz = pz - box[2];
     const float w = box[3], l = box[4], h = box[5];
     const float* R = box + 6;
     bool keep = true;
-    if (J.mode == O3D_CROP_MODEL) {
-        const float s4 = 4.f * J.scale, o2 = 2.f * J.offset;
+    if (mode == O3D_CROP_MODEL) {
+        const float s4 = 4.f * scale, o2 = 2.f * offset;
         const float L = (l * s4) * 0.5f, W = (w * s4) * 0.5f, H = (h * s4) * 0.5f;
         const float e0 = ((fabsf(R[0]) * L + fabsf(R[1]) * W) + fabsf(R[2]) * H) + o2;
         const float e1 = ((fabsf(R[3]) * L + fabsf(R[4]) * W) + fabsf(R[5]) * H) + o2;
@@ -90,8 +94,26 @@ __device__ __forceinline__ bool crop_point(const o3d_crop_job& J, const float* _
     qx = (R[0] * dx + R[3] * dy) + R[6] * dz;
     qy = (R[1] * dx + R[4] * dy) + R[7] * dz;
     qz = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    const float hx = (l * J.scale) * 0.5f + J.offset, hy = (w * J.scale) * 0.5f + J.offset, hz = (h * J.scale) * 0.5f + J.offset;
+    const float hx = (l * scale) * 0.5f + offset, hy = (w * scale) * 0.5f + offset, hz = (h * scale) * 0.5f + offset;
     return keep && fabsf(qx) < hx && fabsf(qy) < hy && fabsf(qz) < hz;
+}
+
+// crop_test for point i of a job; `box` is J.box, which nothing writes during the launch
+__device__ __forceinline__ bool crop_point(const o3d_crop_job& J, const float* __restrict__ box, int i, float& qx, float& qy, float& qz) {
+    const float* p = J.points + 3 * (long)i;
+    return crop_test(p[0], p[1], p[2], box, J.scale, J.offset, J.mode, qx, qy, qz);
+}
+
+// (x, y, z) = row idx[i] of src (n_src,3); zeros when `zero` is set (src and idx are then not read) or the index lies
+// outside the source (a caller's bug: the row stays zero)
+__device__ __forceinline__ void gather_row(const float* src, int n_src, const int32_t* idx, int i, int zero, float& x, float& y, float& z) {
+    x = y = z = 0.f;
+    if (zero) return;
+    const int s = idx[i];
+    if ((unsigned)s < (unsigned)n_src) {
+        const float* p = src + 3 * (long)s;
+        x = p[0]; y = p[1]; z = p[2];
+    }
 }
 
 __device__ __forceinline__ int crop_job_of(const CropTable& t, int wg) {
@@ -148,14 +170,8 @@ __global__ __launch_bounds__(256) void resample_kernel(o3d_resample_job a, o3d_r
     const o3d_resample_job& J = blockIdx.y == 0 ? a : b;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= J.n) return;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (!J.zero) {
-        const int s = J.idx[i];
-        if ((unsigned)s < (unsigned)J.n_src) {        // an index outside the source is a caller's bug: the row stays zero
-            const float* p = J.src + 3 * (long)s;
-            x = p[0]; y = p[1]; z = p[2];
-        }
-    }
+    float x, y, z;
+    gather_row(J.src, J.n_src, J.idx, i, J.zero, x, y, z);
     float* o = J.dst + 3 * (long)i;
     o[0] = x; o[1] = y; o[2] = z;
 }
@@ -170,14 +186,8 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 2 * a.N) return;
     const int half = i >= a.N ? 1 : 0;
-    float x = 0.f, y = 0.f, z = 0.f;
-    if (!a.zero[half]) {
-        const int s = a.idx[i];
-        if ((unsigned)s < (unsigned)a.n_src[half]) {  // an index outside the source is a caller's bug: the row stays zero
-            const float* p = a.src[half] + 3 * (long)s;
-            x = p[0]; y = p[1]; z = p[2];
-        }
-    }
+    float x, y, z;
+    gather_row(a.src[half], a.n_src[half], a.idx, i, a.zero[half], x, y, z);
     float* o = a.points + 5 * (long)i;
     float* bc = a.bc ? a.bc + 9 * (long)i : nullptr;
     o[0] = x; o[1] = y; o[2] = z;
@@ -219,30 +229,31 @@ struct OffsetArgs {
     int T, degrees, use_z, limit_box, rebase, seed;
 };
 
-// one thread: the arithmetic is a 3x3 product; carried in double so that the stored fp32 box is the rounded exact result
-__global__ void offset_box_kernel(OffsetArgs a) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int k = a.frame ? a.frame[0] : 0;
-    float off[4] = {a.offset[0], a.offset[1], a.offset[2], a.offset[3]};
-    const float w = a.ref[3], l = a.ref[4], h = a.ref[5];
-    if (a.limit_box) {                                // datasets/points_utils.py:70-76, literally (no abs)
-        if (off[0] > w) off[0] = limit_draw((unsigned)a.seed, (unsigned)k, 0u);
-        if (off[1] > fminf(l, 2.f)) off[1] = limit_draw((unsigned)a.seed, (unsigned)k, 1u);
-        if (a.use_z && off[2] > h) off[2] = 0.f;
+// getOffsetBB for one target, THE box update of both o3d_track_offset_box and o3d_track_offset_box_multi (ref, offset,
+// yaw_state: the target's rows; rebase, seed: the target's; k: the frame) -> box (15) and the updated yaw_state.  The
+// arithmetic is a 3x3 product; carried in double so that the stored fp32 box is the rounded exact result
+__device__ __forceinline__ void offset_box_one(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees,
+                                               int use_z, int limit_box, unsigned seed, unsigned k, float* box) {
+    float off[4] = {offset[0], offset[1], offset[2], offset[3]};
+    const float w = ref[3], l = ref[4], h = ref[5];
+    if (limit_box) {                                  // datasets/points_utils.py:70-76, literally (no abs)
+        if (off[0] > w) off[0] = limit_draw(seed, k, 0u);
+        if (off[1] > fminf(l, 2.f)) off[1] = limit_draw(seed, k, 1u);
+        if (use_z && off[2] > h) off[2] = 0.f;
     }
-    const double theta = a.degrees ? (double)off[3] * (3.14159265358979323846 / 180.0) : (double)off[3];
+    const double theta = degrees ? (double)off[3] * (3.14159265358979323846 / 180.0) : (double)off[3];
     double R0[9], yaw = theta;
-    if (a.yaw_state && !a.rebase) {
-        for (int i = 0; i < 9; ++i) R0[i] = a.yaw_state[i];
-        yaw = (double)a.yaw_state[9] + theta;
+    if (yaw_state && !rebase) {
+        for (int i = 0; i < 9; ++i) R0[i] = yaw_state[i];
+        yaw = (double)yaw_state[9] + theta;
     } else {
-        for (int i = 0; i < 9; ++i) R0[i] = a.ref[6 + i];
+        for (int i = 0; i < 9; ++i) R0[i] = ref[6 + i];
     }
     // the reference box's own rotation carries the offset into the world: R = R0 Rz(yaw before the update)
     double Rr[9];
-    if (a.yaw_state && !a.rebase) {
+    if (yaw_state && !rebase) {
         double s, c;
-        sincos((double)a.yaw_state[9], &s, &c);
+        sincos((double)yaw_state[9], &s, &c);
         for (int r = 0; r < 3; ++r) {
             Rr[3 * r] = R0[3 * r] * c + R0[3 * r + 1] * s;
             Rr[3 * r + 1] = R0[3 * r + 1] * c - R0[3 * r] * s;
@@ -251,23 +262,30 @@ __global__ void offset_box_kernel(OffsetArgs a) {
     } else {
         for (int i = 0; i < 9; ++i) Rr[i] = R0[i];
     }
-    const double ox = off[0], oy = off[1], oz = a.use_z ? (double)off[2] : 0.0;
-    float box[15];
-    for (int r = 0; r < 3; ++r) box[r] = (float)((double)a.ref[r] + ((Rr[3 * r] * ox + Rr[3 * r + 1] * oy) + Rr[3 * r + 2] * oz));
+    const double ox = off[0], oy = off[1], oz = use_z ? (double)off[2] : 0.0;
+    for (int r = 0; r < 3; ++r) box[r] = (float)((double)ref[r] + ((Rr[3 * r] * ox + Rr[3 * r + 1] * oy) + Rr[3 * r + 2] * oz));
     box[3] = w; box[4] = l; box[5] = h;
     const float yaw_f = (float)yaw;                   // the stored state: the next update starts from exactly this value
     double s, c;
-    sincos(a.yaw_state ? (double)yaw_f : yaw, &s, &c);
+    sincos(yaw_state ? (double)yaw_f : yaw, &s, &c);
     for (int r = 0; r < 3; ++r) {
         box[6 + 3 * r] = (float)(R0[3 * r] * c + R0[3 * r + 1] * s);
         box[6 + 3 * r + 1] = (float)(R0[3 * r + 1] * c - R0[3 * r] * s);
         box[6 + 3 * r + 2] = (float)R0[3 * r + 2];
     }
-    if (a.yaw_state) {
-        if (a.rebase)
-            for (int i = 0; i < 9; ++i) a.yaw_state[i] = (float)R0[i];
-        a.yaw_state[9] = yaw_f;
+    if (yaw_state) {
+        if (rebase)
+            for (int i = 0; i < 9; ++i) yaw_state[i] = (float)R0[i];
+        yaw_state[9] = yaw_f;
     }
+}
+
+// one thread of the launch's 64 works
+__global__ void offset_box_kernel(OffsetArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int k = a.frame ? a.frame[0] : 0;
+    float box[15];
+    offset_box_one(a.ref, a.offset, a.yaw_state, a.rebase, a.degrees, a.use_z, a.limit_box, (unsigned)a.seed, (unsigned)k, box);
     for (int i = 0; i < 15; ++i) {
         if (a.out) a.out[i] = box[i];
         if (a.results && k >= 0 && k < a.T) a.results[15 * (long)k + i] = box[i];
@@ -285,29 +303,6 @@ struct CropMultiTable {
     long sbase[2];                             // the group's first word in scratch
     int n_groups;
 };
-
-// crop_point for a point held in registers and a target staged in LDS (P = box (15), scale, offset, mode as bits): the
-// same operations in the same order
-__device__ __forceinline__ bool crop_xyz(float px, float py, float pz, const float* P, float& qx, float& qy, float& qz) {
-    const float dx = px - P[0], dy = py - P[1], dz = pz - P[2];
-    const float w = P[3], l = P[4], h = P[5];
-    const float* R = P + 6;
-    const float scale = P[15], offset = P[16];
-    bool keep = true;
-    if (__float_as_int(P[17]) == O3D_CROP_MODEL) {
-        const float s4 = 4.f * scale, o2 = 2.f * offset;
-        const float L = (l * s4) * 0.5f, W = (w * s4) * 0.5f, H = (h * s4) * 0.5f;
-        const float e0 = ((fabsf(R[0]) * L + fabsf(R[1]) * W) + fabsf(R[2]) * H) + o2;
-        const float e1 = ((fabsf(R[3]) * L + fabsf(R[4]) * W) + fabsf(R[5]) * H) + o2;
-        const float e2 = ((fabsf(R[6]) * L + fabsf(R[7]) * W) + fabsf(R[8]) * H) + o2;
-        keep = fabsf(dx) < e0 && fabsf(dy) < e1 && fabsf(dz) < e2;
-    }
-    qx = (R[0] * dx + R[3] * dy) + R[6] * dz;
-    qy = (R[1] * dx + R[4] * dy) + R[7] * dz;
-    qz = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    const float hx = (l * scale) * 0.5f + offset, hy = (w * scale) * 0.5f + offset, hz = (h * scale) * 0.5f + offset;
-    return keep && fabsf(qx) < hx && fabsf(qy) < hy && fabsf(qz) < hz;
-}
 
 template <bool SCATTER>
 __global__ __launch_bounds__(CROP_WG) void crop_multi_kernel(CropMultiTable t, int32_t* __restrict__ scratch) {
@@ -338,7 +333,7 @@ __global__ __launch_bounds__(CROP_WG) void crop_multi_kernel(CropMultiTable t, i
         unsigned bits = 0u;                                // bit k: this thread's point survives target k0 + k
         for (int k = 0; k < nc; ++k) {
             float qx, qy, qz;
-            const bool keep = in && crop_xyz(px, py, pz, par[k], qx, qy, qz);
+            const bool keep = in && crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
             const unsigned long long mask = __ballot(keep);
             if (lane == 0) wave_cnt[k][wave] = __popcll(mask);
             if (keep) bits |= 1u << k;
@@ -358,7 +353,7 @@ __global__ __launch_bounds__(CROP_WG) void crop_multi_kernel(CropMultiTable t, i
             const o3d_crop_target& J = T[k0 + k];
             if (pos < J.capacity) {
                 float qx, qy, qz;
-                crop_xyz(px, py, pz, par[k], qx, qy, qz);
+                crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
                 float* o = J.out + 3 * (long)pos;
                 o[0] = qx; o[1] = qy; o[2] = qz;
             }
@@ -403,14 +398,8 @@ __global__ __launch_bounds__(CROP_WG) void crop_multi_scan_kernel(CropMultiTable
 __global__ __launch_bounds__(256) void resample_multi_kernel(const o3d_resample_job* __restrict__ jobs) {
     const o3d_resample_job J = jobs[blockIdx.x];
     for (int i = blockIdx.y * 256 + threadIdx.x; i < J.n; i += gridDim.y * 256) {
-        float x = 0.f, y = 0.f, z = 0.f;
-        if (!J.zero && J.src && J.idx) {
-            const int s = J.idx[i];
-            if ((unsigned)s < (unsigned)J.n_src) {    // an index outside the source is a caller's bug: the row stays zero
-                const float* p = J.src + 3 * (long)s;
-                x = p[0]; y = p[1]; z = p[2];
-            }
-        }
+        float x, y, z;
+        gather_row(J.src, J.n_src, J.idx, i, J.zero || !J.src || !J.idx, x, y, z);      // the host cannot check a device table
         float* o = J.dst + 3 * (long)i;
         o[0] = x; o[1] = y; o[2] = z;
     }
@@ -421,55 +410,6 @@ struct OffsetMultiArgs {
     float* out; float* results; int32_t* frame;
     int K, T, degrees, use_z, limit_box, seed;
 };
-
-// offset_box_kernel for target j of K: the same double arithmetic, expression for expression (ref, offset, yaw_state: the
-// target's rows; rebase, seed: the target's), -> box (15) and the updated yaw_state
-__device__ __forceinline__ void offset_box_one(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees,
-                                               int use_z, int limit_box, unsigned seed, unsigned k, float* box) {
-    float off[4] = {offset[0], offset[1], offset[2], offset[3]};
-    const float w = ref[3], l = ref[4], h = ref[5];
-    if (limit_box) {
-        if (off[0] > w) off[0] = limit_draw(seed, k, 0u);
-        if (off[1] > fminf(l, 2.f)) off[1] = limit_draw(seed, k, 1u);
-        if (use_z && off[2] > h) off[2] = 0.f;
-    }
-    const double theta = degrees ? (double)off[3] * (3.14159265358979323846 / 180.0) : (double)off[3];
-    double R0[9], yaw = theta;
-    if (yaw_state && !rebase) {
-        for (int i = 0; i < 9; ++i) R0[i] = yaw_state[i];
-        yaw = (double)yaw_state[9] + theta;
-    } else {
-        for (int i = 0; i < 9; ++i) R0[i] = ref[6 + i];
-    }
-    double Rr[9];
-    if (yaw_state && !rebase) {
-        double s, c;
-        sincos((double)yaw_state[9], &s, &c);
-        for (int r = 0; r < 3; ++r) {
-            Rr[3 * r] = R0[3 * r] * c + R0[3 * r + 1] * s;
-            Rr[3 * r + 1] = R0[3 * r + 1] * c - R0[3 * r] * s;
-            Rr[3 * r + 2] = R0[3 * r + 2];
-        }
-    } else {
-        for (int i = 0; i < 9; ++i) Rr[i] = R0[i];
-    }
-    const double ox = off[0], oy = off[1], oz = use_z ? (double)off[2] : 0.0;
-    for (int r = 0; r < 3; ++r) box[r] = (float)((double)ref[r] + ((Rr[3 * r] * ox + Rr[3 * r + 1] * oy) + Rr[3 * r + 2] * oz));
-    box[3] = w; box[4] = l; box[5] = h;
-    const float yaw_f = (float)yaw;
-    double s, c;
-    sincos(yaw_state ? (double)yaw_f : yaw, &s, &c);
-    for (int r = 0; r < 3; ++r) {
-        box[6 + 3 * r] = (float)(R0[3 * r] * c + R0[3 * r + 1] * s);
-        box[6 + 3 * r + 1] = (float)(R0[3 * r + 1] * c - R0[3 * r] * s);
-        box[6 + 3 * r + 2] = (float)R0[3 * r + 2];
-    }
-    if (yaw_state) {
-        if (rebase)
-            for (int i = 0; i < 9; ++i) yaw_state[i] = (float)R0[i];
-        yaw_state[9] = yaw_f;
-    }
-}
 
 // ONE workgroup: every thread reads the shared frame counter before thread 0 advances it
 __global__ __launch_bounds__(256) void offset_box_multi_kernel(OffsetMultiArgs a) {
@@ -500,7 +440,7 @@ extern "C" long o3d_track_crop_scratch(const o3d_crop_job* jobs, int n_jobs) {
     long wgs = 0;
     for (int j = 0; j < n_jobs; ++j) {
         if (jobs[j].n < 0) return -1;
-        wgs += jobs[j].n > 0 ? o3d_cdiv(jobs[j].n, CROP_WG) : 1;
+        wgs += crop_wgs(jobs[j].n);
     }
     return wgs;
 }
@@ -520,7 +460,7 @@ extern "C" int o3d_track_crop(const o3d_crop_job* jobs, int n_jobs, int32_t* scr
             (J.mode != O3D_CROP_SUBWINDOW && J.mode != O3D_CROP_MODEL) || !(J.scale >= 0.f) || !(J.offset >= 0.f))
             return O3D_EINVAL;
         t.job[j] = J;
-        wgs += J.n > 0 ? o3d_cdiv(J.n, CROP_WG) : 1;
+        wgs += crop_wgs(J.n);
     }
     t.wg_start[O3D_CROP_MAX_JOBS] = (int)wgs;
     for (int j = n_jobs; j < O3D_CROP_MAX_JOBS; ++j) t.wg_start[j] = (int)wgs;
@@ -592,7 +532,7 @@ static bool crop_multi_table(const o3d_crop_group* groups, int n_groups, CropMul
             G.n_targets > O3D_CROP_MULTI_MAX_TARGETS)
             return false;
         t.points[g] = G.points; t.targets[g] = G.targets; t.n[g] = G.n; t.K[g] = G.n_targets;
-        t.wgs[g] = G.n > 0 ? o3d_cdiv(G.n, CROP_WG) : 1;
+        t.wgs[g] = crop_wgs(G.n);
         t.sbase[g] = need;
         need += (long)t.wgs[g] * G.n_targets;
     }

@@ -27,6 +27,17 @@ def _dev32(x, dev):
                            device=dev).contiguous()
 
 
+def boxcloud_into(out, points, center, wlh, rot, wlh_factor=1.0):
+    """One o3d_boxcloud launch (no sync, nothing allocated): contiguous float32 GPU tensors points (B,N,3), center / wlh (B,3),
+    rot (B,9) -> written into out (B,N,9)"""
+    dev = points.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_boxcloud(points.data_ptr(), center.data_ptr(), wlh.data_ptr(), rot.data_ptr(), float(wlh_factor),
+                                            points.shape[0], points.shape[1], out.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "o3d_boxcloud")
+    return out
+
+
 def get_point_to_box_distance(points, center, wlh, rot, wlh_factor=1.0):
     """points (N,3) or (B,N,3) on the GPU; center/wlh (3) or (B,3); rot (3,3) or (B,3,3) -> (N,9) / (B,N,9)"""
     if not points.is_cuda:
@@ -42,12 +53,7 @@ def get_point_to_box_distance(points, center, wlh, rot, wlh_factor=1.0):
     r = _dev32(rot, dev).reshape(-1, 9)
     if not (c.shape[0] == s.shape[0] == r.shape[0] == B):
         raise ValueError("one box per cloud expected")
-    out = torch.empty((B, N, 9), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        rc = capi.load().o3d_boxcloud(pts.data_ptr(), c.data_ptr(), s.data_ptr(), r.data_ptr(), float(wlh_factor), B, N,
-                                      out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise RuntimeError("o3d_boxcloud failed: %d" % rc)
+    out = boxcloud_into(torch.empty((B, N, 9), device=dev, dtype=torch.float32), pts, c, s, r, wlh_factor)
     return out[0] if single else out
 
 
@@ -114,6 +120,24 @@ def unpack_box(box15):
     return box15[0:3], box15[3:6], box15[6:15].reshape(3, 3)
 
 
+def _crop_operands(box, out, count):
+    """what every crop target needs: box15, out (capacity,3) and count (1,) on the GPU"""
+    assert box.is_cuda and box.dtype == torch.float32 and box.is_contiguous() and box.numel() == 15
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and count.is_cuda and count.dtype == torch.int32
+
+
+def _resample_fields(job):
+    """(src (n_src,3) | None, idx (n,) int32 | None, dst (n,3)) -> the six fields of its o3d_resample_job; src None: dst is
+    zero-filled (regularize_pc with <= 2 points)"""
+    src, idx, dst = job
+    assert dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
+    n = dst.numel() // 3
+    if src is None:
+        return 0, 0, 0, dst.data_ptr(), n, 1
+    assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() >= n
+    return src.data_ptr(), src.shape[0], idx.data_ptr(), dst.data_ptr(), n, 0
+
+
 def crop_jobs(jobs, scratch=None, stream=None):
     """One o3d_track_crop call.  jobs: up to 4 tuples (points (n,3) f32 GPU contiguous, box15 GPU, scale, offset, mode,
     out (capacity,3) f32 GPU, count (1,) int32 GPU).  Nothing is read back here."""
@@ -122,8 +146,7 @@ def crop_jobs(jobs, scratch=None, stream=None):
     table = (_CropJob * len(jobs))()
     for j, (pts, box, scale, offset, mode, out, count) in enumerate(jobs):
         assert pts.is_cuda and pts.dtype == torch.float32 and pts.is_contiguous() and pts.dim() == 2 and pts.shape[1] == 3
-        assert box.is_cuda and box.dtype == torch.float32 and box.is_contiguous() and box.numel() == 15
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and count.dtype == torch.int32
+        _crop_operands(box, out, count)
         table[j] = _CropJob(pts.data_ptr(), pts.shape[0], box.data_ptr(), float(scale), float(offset), int(mode),
                             out.data_ptr(), out.shape[0], count.data_ptr())
     lib = capi.load()
@@ -139,15 +162,7 @@ def crop_jobs(jobs, scratch=None, stream=None):
 def resample_jobs(jobs):
     """One o3d_track_resample call.  jobs: 1 or 2 tuples (src (n_src,3) | None, idx (n,) int32 | None, dst (n,3)); src None:
     dst is zero-filled (regularize_pc with <= 2 points)."""
-    table = (_ResampleJob * len(jobs))()
-    for j, (src, idx, dst) in enumerate(jobs):
-        assert dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
-        n = dst.numel() // 3
-        if src is None:
-            table[j] = _ResampleJob(None, 0, None, dst.data_ptr(), n, 1)
-        else:
-            assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() >= n
-            table[j] = _ResampleJob(src.data_ptr(), src.shape[0], idx.data_ptr(), dst.data_ptr(), n, 0)
+    table = (_ResampleJob * len(jobs))(*[_ResampleJob(*_resample_fields(job)) for job in jobs])
     dev = jobs[0][2].device
     with torch.cuda.device(dev):
         capi.check(capi.load().o3d_track_resample(ctypes.addressof(table), len(jobs), torch.cuda.current_stream(dev).cuda_stream),
@@ -177,8 +192,7 @@ def crop_target_table(targets, device):
     caller keeps the tensors alive."""
     tab = np.zeros((len(targets),), CROP_TARGET)
     for k, (box, scale, offset, mode, out, count) in enumerate(targets):
-        assert box.is_cuda and box.dtype == torch.float32 and box.is_contiguous() and box.numel() == 15
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and count.is_cuda and count.dtype == torch.int32
+        _crop_operands(box, out, count)
         tab[k] = (box.data_ptr(), scale, offset, mode, out.data_ptr(), out.shape[0], count.data_ptr())
     return torch.from_numpy(tab.view(np.uint8)).to(device)
 
@@ -187,14 +201,7 @@ def resample_job_table(jobs, device):
     """jobs: tuples (src (n_src,3) | None, idx (n,) int32 | None, dst (n,3)) as resample_jobs takes -> the o3d_resample_job
     table as a uint8 tensor on `device` (a blocking upload)"""
     tab = np.zeros((len(jobs),), RESAMPLE_JOB)
-    for j, (src, idx, dst) in enumerate(jobs):
-        assert dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()
-        n = dst.numel() // 3
-        if src is None:
-            tab[j] = (0, 0, 0, dst.data_ptr(), n, 1)
-        else:
-            assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() >= n
-            tab[j] = (src.data_ptr(), src.shape[0], idx.data_ptr(), dst.data_ptr(), n, 0)
+    tab[:] = [_resample_fields(job) for job in jobs]
     return torch.from_numpy(tab.view(np.uint8)).to(device)
 
 

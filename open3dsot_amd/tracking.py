@@ -82,13 +82,15 @@ class DrawCache:
 
 
 class _DeviceTracker:
-    """What the two tracking loops share: the box state on the device (the last result box, R0 + accumulated yaw, the
-    canonical box), the (T,15) results buffer with its device-side frame counter, the crop call with the frame's one count
-    read-back (and buffer growth when a crop exceeds its capacity) and the network as a HIP graph captured once per tracker
-    (eager when the capture fails, unless O3D_REQUIRE_GRAPH=1).  Subclasses provide `_forward()` on their static inputs."""
+    """What the tracking loops share: the box state on the device (the last result box, R0 + accumulated yaw, the canonical
+    box's wlh), the (T,15) results buffer with its device-side frame counter, the crop call with the frame's one count
+    read-back (and buffer growth when a crop exceeds its capacity), the index staging and the network as a HIP graph captured
+    once per tracker (eager when the capture fails, unless O3D_REQUIRE_GRAPH=1).  With n_targets = K the per-target state has
+    a leading K axis (`lead`): cur (K,15), yaw_state (K,10), boxes (T,K,15), counts (2K,).  Subclasses provide `_update()`
+    and `_forward()` on their static inputs."""
     _NAME = "tracker"
 
-    def __init__(self, model, seed, use_graph, max_frames, defaults):
+    def __init__(self, model, seed, use_graph, max_frames, defaults, n_targets=None):
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("%s: CPU not supported (the model must live on a GPU)" % self._NAME)
@@ -99,12 +101,13 @@ class _DeviceTracker:
         self.use_graph = use_graph
         self.require_graph = os.environ.get("O3D_REQUIRE_GRAPH", "0") == "1"
         f32 = dict(dtype=torch.float32, device=self.dev)
-        self.counts = torch.zeros((2,), dtype=torch.int32, device=self.dev)
-        self.counts_host = torch.zeros((2,), dtype=torch.int32).pin_memory()
-        self.cur = torch.zeros((15,), **f32)               # the last result box: the next frame's crops read it
-        self.yaw_state = torch.zeros((10,), **f32)
-        self.canon = torch.zeros((15,), **f32)             # the canonical box: zero centre, wlh, identity
-        self.boxes = torch.zeros((int(max_frames), 15), **f32)
+        self.lead = lead = () if n_targets is None else (int(n_targets),)
+        self.counts = torch.zeros((2 * (n_targets or 1),), dtype=torch.int32, device=self.dev)
+        self.counts_host = torch.zeros(self.counts.shape, dtype=torch.int32).pin_memory()
+        self.cur = torch.zeros(lead + (15,), **f32)        # the last result box: the next frame's crops read it
+        self.yaw_state = torch.zeros(lead + (10,), **f32)
+        self.canon_wlh = torch.zeros(lead + (3,), **f32)   # the canonical box: zero centre, this wlh, identity
+        self.boxes = torch.zeros((int(max_frames),) + lead + (15,), **f32)
         self.frame = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.scratch = None
         self.graph, self.out, self.graph_failed = None, None, None
@@ -112,34 +115,36 @@ class _DeviceTracker:
         self.log = []
 
     # ---- state -------------------------------------------------------------------------------------------------------------
+    def _pack(self, box0):
+        return PU.pack_box(box0, self.dev)
+
+    def _restart(self, b, k=Ellipsis):
+        """the last result box (of target k) := b, its yaw state restarted from b's rotation"""
+        self.cur[k].copy_(b)
+        self.yaw_state[k][..., :9].copy_(b[..., 6:15])
+        self.yaw_state[k][..., 9] = 0.0
+        self.boxes[self.t - 1][k].copy_(b)
+
     def init(self, points0, box0):
         PU._need_gpu(points0, self._NAME + ".init")
-        b = PU.pack_box(box0, self.dev)
-        self.cur.copy_(b)
-        self.yaw_state[:9].copy_(b[6:15])
-        self.yaw_state[9] = 0.0
-        self.canon.zero_()
-        self.canon[3:6].copy_(b[3:6])
-        self.canon[6], self.canon[10], self.canon[14] = 1.0, 1.0, 1.0
-        self.boxes[0].copy_(b)
+        b = self._pack(box0)
+        self.t, self.log = 1, []
+        self._restart(b)
+        self.canon_wlh.copy_(b[..., 3:6])
         self.frame.fill_(1)
         self.prev_points = points0.contiguous().float()
-        self.t, self.log = 1, []
         return self.boxes[0]
 
     def set_box(self, box):
         """Overwrite the last result box (re-initialisation from a detector, teacher forcing in the tests): the next update
         crops around it and offsets from it."""
-        b = PU.pack_box(box, self.dev)
-        self.cur.copy_(b)
-        self.yaw_state[:9].copy_(b[6:15])
-        self.yaw_state[9] = 0.0
-        self.boxes[self.t - 1].copy_(b)
+        self._restart(PU.pack_box(box, self.dev))
 
     def _grow_boxes(self):
-        if self.t >= self.boxes.shape[0]:
-            bigger = torch.zeros((2 * self.boxes.shape[0], 15), dtype=torch.float32, device=self.dev)
-            bigger[:self.boxes.shape[0]].copy_(self.boxes)
+        T = self.boxes.shape[0]
+        if self.t >= T:
+            bigger = torch.zeros((2 * T,) + self.boxes.shape[1:], dtype=torch.float32, device=self.dev)
+            bigger[:T].copy_(self.boxes)
             self.boxes = bigger
 
     def _crop_counts(self, make_jobs):
@@ -168,6 +173,23 @@ class _DeviceTracker:
                 return ns
             for grow, n in over.items():                                         # a crop larger than its buffer: grow, crop again
                 grow(n)
+
+    def _index_buffers(self, n):
+        """idx (n,) int32 on the device and its pinned host copy, which _stage_indices fills and uploads"""
+        self.idx = torch.zeros((n,), dtype=torch.int32, device=self.dev)
+        self.idx_host = torch.zeros((n,), dtype=torch.int32).pin_memory()
+
+    def _stage_indices(self, *draws):
+        """draws: (point count, sample size) pairs.  The reference's own index draw for each (draw_indices), laid end to end
+        in idx_host, then ONE upload into idx.  -> per draw, whether it is the zero-fill case (its part of idx is not read)"""
+        drawn = [draw_indices(n, size) for n, size in draws]
+        at = 0
+        for i, (_, size) in zip(drawn, draws):
+            if i is not None:
+                self.idx_host[at:at + size] = torch.from_numpy(i.astype(np.int32))
+            at += size
+        self.idx.copy_(self.idx_host, non_blocking=True)
+        return [i is None for i in drawn]
 
     def _network(self):
         """the forward on the static inputs -> its device tensors (the same objects at every replay)"""
@@ -200,12 +222,110 @@ class _DeviceTracker:
         with torch.no_grad():
             return self.model.evaluate_one_sample(self.inputs)
 
+    # ---- one frame ---------------------------------------------------------------------------------------------------------
+    def _run(self, points, *args):
+        """update(): the checks, then the subclass's _update on the tracker's device"""
+        PU._need_gpu(points, self._NAME + ".update")
+        if self.t < 1:
+            raise RuntimeError(self._NAME + ".update before init")
+        self._check(*args)
+        with torch.cuda.device(self.dev):
+            return self._update(points.contiguous().float(), *args)
+
+    def _check(self, *args):
+        pass
+
+    def _done(self, pts, entry):
+        """the end of _update: the frame becomes the previous one, `entry` its line of the log -> a device VIEW of its row"""
+        self.prev_points = pts
+        self.log.append(entry)
+        self.t += 1
+        return self.boxes[self.t - 1]
+
     def results(self):
-        """(T,15) float32 on the host: row 0 the initial box, row t the result of frame t (one sync)"""
+        """(T,15) float32 on the host, (T,K,15) with n_targets = K: row 0 the initial box, row t the result of frame t (one sync)"""
         return self.boxes[:self.t].cpu().numpy()
 
 
-class SequenceTracker(_DeviceTracker):
+class _MatchingTracker(_DeviceTracker):
+    """What SequenceTracker (one target, K = 1, no leading axis) and MultiTargetTracker (K targets) share: the config rules
+    (reference_BB, shape_aggregation), the batch-K static inputs of the network, the canonical boxes of the BoxCloud, the
+    search buffer and the template bank (one per target) with its slot rules.  bank_fixed / bank_total / slots / counts are
+    ints for the single tracker and (K,) int64 arrays for K targets; the same expressions serve both."""
+    _REF_KW = "ref_box"
+
+    def __init__(self, model, seed, use_graph, max_frames, search_capacity, model_capacity, n_targets=None):
+        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS, n_targets)
+        self.K = K = n_targets or 1
+        self.aggregation = _aggregation(self.shape_aggregation)
+        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
+            raise ValueError("reference_BB %r" % (self.reference_BB,))
+        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
+        self.with_boxcloud = hasattr(model, "mlp_bc")
+        M, N = int(self.template_size), int(self.search_size)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.inputs = {"template_points": torch.zeros((K, M, 3), **f32), "search_points": torch.zeros((K, N, 3), **f32)}
+        if self.with_boxcloud:
+            self.inputs["points2cc_dist_t"] = torch.zeros((K, M, 9), **f32)
+        self.canon_centre = torch.zeros((K, 3), **f32)
+        self.canon_rot = torch.eye(3, **f32).reshape(1, 9).repeat(K, 1).contiguous()
+        self.search_buf = torch.empty(self.lead + (int(search_capacity), 3), **f32)
+        self.model_capacity = int(model_capacity)
+        self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
+        # log, per frame: (search count, model count of the crop made this frame | None, template points)
+
+    def init(self, points0, box0):
+        box = super().init(points0, box0)
+        self.bank_fixed, self.bank_total = (np.zeros(self.lead, np.int64), np.zeros(self.lead, np.int64)) if self.lead else (0, 0)
+        return box
+
+    def _check(self, ref):
+        if self.needs_ref_box and ref is None:
+            raise ValueError("reference_BB %r needs update(points, %s=...)" % (self.reference_BB, self._REF_KW))
+
+    def _model_slot(self):
+        """where this frame's model crop goes in the bank (of every target), or None when the template does not change"""
+        first = self.t == 1
+        if self.aggregation == "first":
+            return 0 * self.bank_fixed if first else None
+        if self.aggregation == "previous":
+            return 0 * self.bank_fixed
+        if self.aggregation == "firstandprevious":
+            return 0 * self.bank_fixed if first else self.bank_fixed + 0
+        return self.bank_total + 0                              # all: appended
+
+    def _ensure_bank(self, need):
+        old = self.bank
+        if need > old.shape[-2]:
+            self.bank = torch.empty(self.lead + (max(need, 2 * old.shape[-2]), 3), dtype=torch.float32, device=self.dev)
+            self.bank[..., :old.shape[-2], :].copy_(old)
+
+    def _grow_search(self, n):
+        self.search_buf = torch.empty(self.lead + (2 * n, 3), dtype=torch.float32, device=self.dev)
+
+    def _grow_model(self, n):
+        self.model_capacity = 2 * n
+
+    def _banked(self, slot, nm):
+        """the bank's book-keeping after a model crop of nm points at `slot`"""
+        c = self
+        c.bank_total = slot + nm
+        if c.t == 1:
+            c.bank_fixed = nm + 0                  # the first frame's crop stays at the head of the bank
+            if c.aggregation == "firstandprevious":            # getModel([first, previous]) at t = 1: the same crop twice
+                c._ensure_bank(2 * int(np.max(nm)) + c.model_capacity)
+                for bank, n in zip(c.bank.reshape(-1, c.bank.shape[-2], 3), np.atleast_1d(nm)):
+                    bank[n:2 * n].copy_(bank[:n])
+                c.bank_total = 2 * nm
+
+    def _boxcloud(self):
+        """the templates' BoxClouds against the canonical boxes (BAT only)"""
+        if self.with_boxcloud:
+            PU.boxcloud_into(self.inputs["points2cc_dist_t"], self.inputs["template_points"], self.canon_centre, self.canon_wlh,
+                             self.canon_rot)
+
+
+class SequenceTracker(_MatchingTracker):
     """Device-resident tracking loop for the matching trackers (trackers.BAT, trackers.P2B).
 
         trk = SequenceTracker(model)            # model on the GPU, eval mode
@@ -220,112 +340,46 @@ class SequenceTracker(_DeviceTracker):
     _NAME = "SequenceTracker"
 
     def __init__(self, model, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
-        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS)
-        self.aggregation = _aggregation(self.shape_aggregation)
-        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
-            raise ValueError("reference_BB %r" % (self.reference_BB,))
-        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
-        self.with_boxcloud = hasattr(model, "mlp_bc")
-        dev, M, N = self.dev, int(self.template_size), int(self.search_size)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.inputs = {"template_points": torch.zeros((1, M, 3), **f32), "search_points": torch.zeros((1, N, 3), **f32)}
-        if self.with_boxcloud:
-            self.inputs["points2cc_dist_t"] = torch.zeros((1, M, 9), **f32)
-        self.search_buf = torch.empty((search_capacity, 3), **f32)
-        self.model_capacity = int(model_capacity)
-        self.bank = torch.empty((2 * self.model_capacity, 3), **f32)
-        self.idx = torch.zeros((M + N,), dtype=torch.int32, device=dev)
-        self.idx_host = torch.zeros((M + N,), dtype=torch.int32).pin_memory()
-        # log, per frame: (search count, model count of the crop made this frame | None, template points)
-
-    def init(self, points0, box0):
-        box = super().init(points0, box0)
-        self.bank_fixed, self.bank_total = 0, 0
-        return box
-
-    def _model_slot(self):
-        """where this frame's model crop goes in the bank, or None when the template does not change"""
-        if self.aggregation == "first":
-            return 0 if self.t == 1 else None
-        if self.aggregation == "previous":
-            return 0
-        if self.aggregation == "firstandprevious":
-            return 0 if self.t == 1 else self.bank_fixed
-        return self.bank_total                                  # all: appended
-
-    def _ensure_bank(self, need):
-        if need > self.bank.shape[0]:
-            bigger = torch.empty((max(need, 2 * self.bank.shape[0]), 3), dtype=torch.float32, device=self.dev)
-            bigger[:self.bank_total].copy_(self.bank[:self.bank_total])
-            self.bank = bigger
+        super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity)
+        self._index_buffers(int(self.template_size) + int(self.search_size))
 
     def _crops(self, pts, ref, slot):
         """the frame's one crop call + the count read-back -> (search count, model count | None)"""
         c = self
 
-        def grow_search(n):
-            c.search_buf = torch.empty((2 * n, 3), dtype=torch.float32, device=c.dev)
-
-        def grow_model(n):
-            c.model_capacity = 2 * n
-
         def make_jobs():
-            jobs = [((pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts[0:1]), grow_search)]
+            jobs = [((pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts[0:1]), c._grow_search)]
             if slot is not None:
                 c._ensure_bank(slot + c.model_capacity)
                 jobs.append(((c.prev_points, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL,
-                              c.bank[slot:slot + c.model_capacity], c.counts[1:2]), grow_model))
+                              c.bank[slot:slot + c.model_capacity], c.counts[1:2]), c._grow_model))
             return jobs
         ns = c._crop_counts(make_jobs)
         return ns[0], (ns[1] if slot is not None else None)
 
-    # ---- one frame ---------------------------------------------------------------------------------------------------------
     def update(self, points, ref_box=None):
-        PU._need_gpu(points, "SequenceTracker.update")
-        if self.t < 1:
-            raise RuntimeError("SequenceTracker.update before init")
-        if self.needs_ref_box and ref_box is None:
-            raise ValueError("reference_BB %r needs update(points, ref_box=...)" % (self.reference_BB,))
-        with torch.cuda.device(self.dev):
-            return self._update(points.contiguous().float(), ref_box)
+        return self._run(points, ref_box)
 
     def _update(self, pts, ref_box):
-        c, M, N = self, int(self.template_size), int(self.search_size)
+        c, M = self, int(self.template_size)
         c._grow_boxes()
         ref = c.cur if ref_box is None else PU.pack_box(ref_box, c.dev)
         slot = c._model_slot()
         ns, nm = c._crops(pts, ref, slot)
         if slot is not None:
-            c.bank_total = slot + nm
-            if c.t == 1:
-                c.bank_fixed = nm                      # the first frame's crop stays at the head of the bank
-                if c.aggregation == "firstandprevious":            # getModel([first, previous]) at t = 1: the same crop twice
-                    c._ensure_bank(2 * nm + c.model_capacity)
-                    c.bank[nm:2 * nm].copy_(c.bank[:nm])
-                    c.bank_total = 2 * nm
+            c._banked(slot, nm)
         nt = c.bank_total
-        it, isr = draw_indices(nt, M), draw_indices(ns, N)
-        if it is not None:
-            c.idx_host[:M] = torch.from_numpy(it.astype(np.int32))
-        if isr is not None:
-            c.idx_host[M:] = torch.from_numpy(isr.astype(np.int32))
-        c.idx.copy_(c.idx_host, non_blocking=True)
-        PU.resample_jobs([(c.bank if it is not None else None, c.idx[:M], c.inputs["template_points"]),
-                          (c.search_buf if isr is not None else None, c.idx[M:], c.inputs["search_points"])])
-        if c.with_boxcloud:
-            capi.check(capi.load().o3d_boxcloud(c.inputs["template_points"].data_ptr(), c.canon.data_ptr(), c.canon[3:6].data_ptr(),
-                                                c.canon[6:15].data_ptr(), 1.0, 1, M, c.inputs["points2cc_dist_t"].data_ptr(),
-                                                torch.cuda.current_stream(c.dev).cuda_stream), "o3d_boxcloud")
+        zero_t, zero_s = c._stage_indices((nt, M), (ns, int(c.search_size)))
+        PU.resample_jobs([(None if zero_t else c.bank, c.idx[:M], c.inputs["template_points"]),
+                          (None if zero_s else c.search_buf, c.idx[M:], c.inputs["search_points"])])
+        c._boxcloud()
         best, _ = c._network()
         PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
                       use_z=c.use_z, limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
-        c.prev_points = pts
-        c.log.append((ns, nm, nt))
-        c.t += 1
-        return c.boxes[c.t - 1]
+        return c._done(pts, (ns, nm, nt))
 
 
-class MultiTargetTracker(_DeviceTracker):
+class MultiTargetTracker(_MatchingTracker):
     """Device-resident tracking loop for K targets in the same frames (the matching trackers: trackers.BAT, trackers.P2B).
     What SequenceTracker does per target happens here once per frame for all of them:
 
@@ -352,7 +406,7 @@ class MultiTargetTracker(_DeviceTracker):
     shape_aggregation modes.  `update(points, ref_boxes=...)` (K,15): the reference's `reference_BB: previous_gt / current_gt`.
     `seed`: target k's limit_box draws use seed + k.  log, per frame: (search counts (K), model counts (K) | None, template
     counts (K)); crop_calls: the crop calls since init (one per frame, one more whenever a crop outgrew its buffer)."""
-    _NAME = "MultiTargetTracker"
+    _NAME, _REF_KW = "MultiTargetTracker", "ref_boxes"
 
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
         from .m2track import M2TRACK
@@ -362,52 +416,27 @@ class MultiTargetTracker(_DeviceTracker):
         K = int(n_targets)
         if not 1 <= K <= PU.CROP_MULTI_MAX_TARGETS:
             raise ValueError("n_targets must be 1..%d" % PU.CROP_MULTI_MAX_TARGETS)
-        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS)
-        self.K = K
-        self.aggregation = _aggregation(self.shape_aggregation)
-        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
-            raise ValueError("reference_BB %r" % (self.reference_BB,))
-        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
-        self.with_boxcloud = hasattr(model, "mlp_bc")
-        dev, M, N = self.dev, int(self.template_size), int(self.search_size)
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        # the state of _DeviceTracker, one row per target
-        self.counts = torch.zeros((2 * K,), **i32)                 # [0:K] search, [K:2K] model
-        self.counts_host = torch.zeros((2 * K,), dtype=torch.int32).pin_memory()
-        self.cur = torch.zeros((K, 15), **f32)
-        self.yaw_state = torch.zeros((K, 10), **f32)
-        self.canon_wlh = torch.zeros((K, 3), **f32)                # the canonical boxes: zero centre, wlh, identity
-        self.canon_centre = torch.zeros((K, 3), **f32)
-        self.canon_rot = torch.eye(3, **f32).reshape(1, 9).repeat(K, 1).contiguous()
-        self.boxes = torch.zeros((int(max_frames), K, 15), **f32)
-        self.active = torch.ones((K,), **i32)
-        self.rebase_all = torch.ones((K,), **i32)
+        super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity, K)
+        dev, MN = self.dev, int(self.template_size) + int(self.search_size)
+        self.active = torch.ones((K,), dtype=torch.int32, device=dev)
+        self.rebase_all = torch.ones((K,), dtype=torch.int32, device=dev)
         self.retired = set()                                       # the host's copy of `active == 0`
-        self.inputs = {"template_points": torch.zeros((K, M, 3), **f32), "search_points": torch.zeros((K, N, 3), **f32)}
-        if self.with_boxcloud:
-            self.inputs["points2cc_dist_t"] = torch.zeros((K, M, 9), **f32)
-        self.search_buf = torch.empty((K, int(search_capacity), 3), **f32)
-        self.model_capacity = int(model_capacity)
-        self.bank = torch.empty((K, 2 * self.model_capacity, 3), **f32)
         # the crop's target table, [0:K] search, [K:2K] model
         self.crop_tab_host = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8).pin_memory()
         self.crop_tab = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8, device=dev)
         self.crop_rec = self.crop_tab_host.numpy().view(PU.CROP_TARGET)
         # the frame's one upload: 2K resample jobs [template 0..K-1, search 0..K-1], then the K * (M + N) indices
         jb = 2 * K * PU.RESAMPLE_JOB.itemsize
-        self.stage_host = torch.zeros((jb + 4 * K * (M + N),), dtype=torch.uint8).pin_memory()
-        self.stage = torch.zeros((jb + 4 * K * (M + N),), dtype=torch.uint8, device=dev)
+        self.stage_host = torch.zeros((jb + 4 * K * MN,), dtype=torch.uint8).pin_memory()
+        self.stage = torch.zeros((jb + 4 * K * MN,), dtype=torch.uint8, device=dev)
         self.job_rec = self.stage_host.numpy()[:jb].view(PU.RESAMPLE_JOB)
-        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, M + N)
+        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, MN)
         self.idx_ptr = self.stage.data_ptr() + jb
         self.draws = DrawCache()
-        self.bank_fixed = np.zeros((K,), np.int64)
-        self.bank_total = np.zeros((K,), np.int64)
         self.crop_calls = 0
 
     # ---- state -------------------------------------------------------------------------------------------------------------
-    def _pack_boxes(self, boxes):
+    def _pack(self, boxes):
         if torch.is_tensor(boxes) or isinstance(boxes, np.ndarray):
             b = PU._dev32(boxes, self.dev).reshape(-1, 15)
         else:
@@ -417,28 +446,15 @@ class MultiTargetTracker(_DeviceTracker):
         return b.contiguous()
 
     def init(self, points0, boxes0):
-        PU._need_gpu(points0, "MultiTargetTracker.init")
-        b = self._pack_boxes(boxes0)
-        self.cur.copy_(b)
-        self.yaw_state[:, :9].copy_(b[:, 6:15])
-        self.yaw_state[:, 9] = 0.0
-        self.canon_wlh.copy_(b[:, 3:6])
-        self.boxes[0].copy_(b)
-        self.frame.fill_(1)
+        boxes = super().init(points0, boxes0)
         self.active.fill_(1)
         self.retired.clear()
-        self.prev_points = points0.contiguous().float()
-        self.bank_fixed[:], self.bank_total[:] = 0, 0
-        self.t, self.log, self.crop_calls = 1, [], 0
-        return self.boxes[0]
+        self.crop_calls = 0
+        return boxes
 
     def set_box(self, k, box):
         """Overwrite target k's last result box (SequenceTracker.set_box for one target)."""
-        b = PU.pack_box(box, self.dev)
-        self.cur[k].copy_(b)
-        self.yaw_state[k, :9].copy_(b[6:15])
-        self.yaw_state[k, 9] = 0.0
-        self.boxes[self.t - 1, k].copy_(b)
+        self._restart(PU.pack_box(box, self.dev), k)
 
     def retire(self, k):
         """Stop following target k: from the next update on its rows repeat its last box and its yaw state stays as it is.
@@ -448,38 +464,10 @@ class MultiTargetTracker(_DeviceTracker):
         self.active[k] = 0
         self.retired.add(int(k) % self.K)
 
-    def _grow_boxes(self):
-        if self.t >= self.boxes.shape[0]:
-            bigger = torch.zeros((2 * self.boxes.shape[0], self.K, 15), dtype=torch.float32, device=self.dev)
-            bigger[:self.boxes.shape[0]].copy_(self.boxes)
-            self.boxes = bigger
-
-    def _model_slots(self):
-        """where this frame's model crops go in each target's bank (K,), or None when the templates do not change"""
-        if self.aggregation == "first":
-            return np.zeros((self.K,), np.int64) if self.t == 1 else None
-        if self.aggregation == "previous":
-            return np.zeros((self.K,), np.int64)
-        if self.aggregation == "firstandprevious":
-            return np.zeros((self.K,), np.int64) if self.t == 1 else self.bank_fixed.copy()
-        return self.bank_total.copy()                             # all: appended
-
-    def _ensure_bank(self, need):
-        if need > self.bank.shape[1]:
-            old = self.bank
-            self.bank = torch.empty((self.K, max(need, 2 * old.shape[1]), 3), dtype=torch.float32, device=self.dev)
-            self.bank[:, :old.shape[1]].copy_(old)
-
     def _crops(self, pts, ref, slots):
         """the frame's one crop call + the count read-back -> (search counts (K), model counts (K) | None)"""
         c, K = self, self.K
         k15 = 60 * np.arange(K, dtype=np.uint64)
-
-        def grow_search(n):
-            c.search_buf = torch.empty((K, 2 * n, 3), dtype=torch.float32, device=c.dev)
-
-        def grow_model(n):
-            c.model_capacity = 2 * n
 
         def launch():
             rec, kk = c.crop_rec, np.arange(K, dtype=np.uint64)
@@ -487,7 +475,7 @@ class MultiTargetTracker(_DeviceTracker):
             s["box"], s["scale"], s["offset"], s["mode"] = ref.data_ptr() + k15, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW
             s["out"], s["capacity"] = c.search_buf.data_ptr() + 12 * c.search_buf.shape[1] * kk, c.search_buf.shape[1]
             s["count"] = c.counts.data_ptr() + 4 * kk
-            groups, caps = [(pts, c.crop_tab[:K * PU.CROP_TARGET.itemsize])], [(c.search_buf.shape[1], grow_search)] * K
+            groups, caps = [(pts, c.crop_tab[:K * PU.CROP_TARGET.itemsize])], [(c.search_buf.shape[1], c._grow_search)] * K
             if slots is not None:
                 c._ensure_bank(int(slots.max()) + c.model_capacity)
                 m = rec[K:]
@@ -495,7 +483,7 @@ class MultiTargetTracker(_DeviceTracker):
                 m["out"] = c.bank.data_ptr() + 12 * (c.bank.shape[1] * kk + slots.astype(np.uint64))
                 m["capacity"], m["count"] = c.model_capacity, c.counts.data_ptr() + 4 * (kk + np.uint64(K))
                 groups.append((c.prev_points, c.crop_tab[K * PU.CROP_TARGET.itemsize:]))
-                caps += [(c.model_capacity, grow_model)] * K
+                caps += [(c.model_capacity, c._grow_model)] * K
             c.crop_tab.copy_(c.crop_tab_host, non_blocking=True)
             c.scratch = PU.crop_multi(groups, c.scratch)
             c.crop_calls += 1                  # one per frame, one more whenever a crop outgrew its buffer
@@ -505,33 +493,20 @@ class MultiTargetTracker(_DeviceTracker):
 
     # ---- one frame ---------------------------------------------------------------------------------------------------------
     def update(self, points, ref_boxes=None):
-        PU._need_gpu(points, "MultiTargetTracker.update")
-        if self.t < 1:
-            raise RuntimeError("MultiTargetTracker.update before init")
-        if self.needs_ref_box and ref_boxes is None:
-            raise ValueError("reference_BB %r needs update(points, ref_boxes=...)" % (self.reference_BB,))
-        with torch.cuda.device(self.dev):
-            return self._update(points.contiguous().float(), ref_boxes)
+        return self._run(points, ref_boxes)
 
     def _update(self, pts, ref_boxes):
         c, K, M, N = self, self.K, int(self.template_size), int(self.search_size)
         c._grow_boxes()
-        ref = c.cur if ref_boxes is None else c._pack_boxes(ref_boxes)
+        ref = c.cur if ref_boxes is None else c._pack(ref_boxes)
         if ref_boxes is not None and c.retired:        # a retired target's reference is its own last box, not the caller's
             rows = sorted(c.retired)
             ref = ref.clone()
             ref[rows] = c.cur[rows]
-        slots = c._model_slots()
+        slots = c._model_slot()
         ns, nm = c._crops(pts, ref, slots)
         if slots is not None:
-            c.bank_total = slots + nm
-            if c.t == 1:
-                c.bank_fixed = nm.copy()               # the first frame's crops stay at the head of the banks
-                if c.aggregation == "firstandprevious":            # getModel([first, previous]) at t = 1: the same crop twice
-                    c._ensure_bank(2 * int(nm.max()) + c.model_capacity)
-                    for k in range(K):
-                        c.bank[k, nm[k]:2 * nm[k]].copy_(c.bank[k, :nm[k]])
-                    c.bank_total = 2 * nm
+            c._banked(slots, nm)
         nt = c.bank_total.copy()
         # the frame's one upload: the indices and the 2K resample jobs
         zero = np.zeros((2 * K,), np.int32)
@@ -555,22 +530,12 @@ class MultiTargetTracker(_DeviceTracker):
         j["zero"] = zero
         c.stage.copy_(c.stage_host, non_blocking=True)
         PU.resample_multi(c.stage, 2 * K)
-        if c.with_boxcloud:
-            capi.check(capi.load().o3d_boxcloud(c.inputs["template_points"].data_ptr(), c.canon_centre.data_ptr(), c.canon_wlh.data_ptr(),
-                                                c.canon_rot.data_ptr(), 1.0, K, M, c.inputs["points2cc_dist_t"].data_ptr(),
-                                                torch.cuda.current_stream(c.dev).cuda_stream), "o3d_boxcloud")
+        c._boxcloud()
         best, _ = c._network()
         PU.offset_box_multi(ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame,
                             rebase=c.rebase_all if ref_boxes is not None else None, active=c.active, degrees=c.degrees,
                             use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
-        c.prev_points = pts
-        c.log.append((ns, nm, nt))
-        c.t += 1
-        return c.boxes[c.t - 1]
-
-    def results(self):
-        """(T,K,15) float32 on the host: row 0 the initial boxes, row t the results of frame t (one sync)"""
-        return self.boxes[:self.t].cpu().numpy()
+        return c._done(pts, (ns, nm, nt))
 
 
 # cfgs/M2_track_kitti.yaml :5-8,32-33
@@ -602,8 +567,7 @@ class MotionSequenceTracker(_DeviceTracker):
         if self.box_aware:
             self.inputs["candidate_bc"] = torch.zeros((1, 2 * N, 9), **f32)
         self.crop_buf = torch.empty((2, int(capacity), 3), **f32)          # [0] the previous frame's crop, [1] the current one's
-        self.idx = torch.zeros((2 * N,), dtype=torch.int32, device=dev)
-        self.idx_host = torch.zeros((2 * N,), dtype=torch.int32).pin_memory()
+        self._index_buffers(2 * N)
 
     def _crops(self, pts):
         c = self
@@ -617,31 +581,19 @@ class MotionSequenceTracker(_DeviceTracker):
         return c._crop_counts(make_jobs)
 
     def update(self, points):
-        PU._need_gpu(points, "MotionSequenceTracker.update")
-        if self.t < 1:
-            raise RuntimeError("MotionSequenceTracker.update before init")
-        with torch.cuda.device(self.dev):
-            return self._update(points.contiguous().float())
+        return self._run(points)
 
     def _update(self, pts):
         c, N = self, int(self.point_sample_size)
         c._grow_boxes()
         n_prev, n_this = c._crops(pts)
-        ip, it = draw_indices(n_prev, N), draw_indices(n_this, N)
-        if ip is not None:
-            c.idx_host[:N] = torch.from_numpy(ip.astype(np.int32))
-        if it is not None:
-            c.idx_host[N:] = torch.from_numpy(it.astype(np.int32))
-        c.idx.copy_(c.idx_host, non_blocking=True)
-        PU.motion_input(c.crop_buf[0, :n_prev], c.crop_buf[1, :n_this], c.idx, c.canon[3:6], c.t == 1, zero=(ip is None, it is None),
+        zero = c._stage_indices((n_prev, N), (n_this, N))
+        PU.motion_input(c.crop_buf[0, :n_prev], c.crop_buf[1, :n_this], c.idx, c.canon_wlh, c.t == 1, zero=zero,
                         out_points=c.inputs["points"], out_bc=c.inputs["candidate_bc"] if c.box_aware else False)
         est = c._network()
         PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
                       limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
-        c.prev_points = pts
-        c.log.append((n_prev, n_this))
-        c.t += 1
-        return c.boxes[c.t - 1]
+        return c._done(pts, (n_prev, n_this))
 
 
 def tracker_for(model, **kw):
