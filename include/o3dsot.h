@@ -140,15 +140,26 @@ int o3d_mlp_conv_fwd(const float* X, const float* W, const float* in_scale, cons
                      int B, int Cin, int Cout, int P, float* Y, float* part, const float* stat_c,
                      void* stream);
 
-/* (fold: optional scratch of 64*C floats; long partial lists are first folded into 32 parts by a
- * wide kernel so the finalize does not walk thousands of rows from a handful of workgroups.)
- * Training-mode BatchNorm statistics from the partials: mean, invstd = 1/sqrt(var_biased+eps),
- * scale = gamma*invstd, shift = beta - mean*scale (C each); when running_mean != NULL and
- * momentum >= 0 the running statistics are updated like torch.nn.BatchNorm (unbiased var). */
-int o3d_bn_finalize(const float* part, int nparts, int C, double count, const float* stat_c,
-                    const float* gamma, const float* beta, float* running_mean, float* running_var,
-                    float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
-                    float* fold, void* stream);
+/* BatchNorm statistics from the partials, forward and backward.  One job per BatchNorm layer; njobs = 1 or 2 (two
+ * independent layers, e.g. of two conv stacks advancing side by side, share ONE launch).  jobs: HOST array.
+ * The partial list of a job: part [nparts (+ nparts1)][2][C] rows of per-tile sums.
+ *   meta == NULL: every row is live and tile is ignored.  Otherwise (compact layout) only the first
+ *     ceil(meta[0] / tile) rows are live; tile = columns per partial row (> 0).
+ *   nparts1 == 0: one segment.  Otherwise two segments in one launch (template + search cloud through a shared module,
+ *     models/bat.py:89-90): segment 1's rows follow segment 0's nparts, its count is count1, its live columns meta[4],
+ *     and stat_c / mean / invstd / scale / shift / A1..A3 are laid out (2,C).  Same numbers as one job per segment,
+ *     segment 0 first; the running statistics see segment 0's update first.
+ *   meta != NULL and tile == 128: the rows of a direct GEMM launch -- the extra rows of its remainder tiles (see
+ *     o3d_direct_tail_slots below, with C = the launch's output rows) follow the nparts + nparts1 regular ones.
+ * Forward, training mode: mean, invstd = 1/sqrt(var_biased+eps), scale = gamma*invstd, shift = beta - mean*scale (C
+ * each) from partials {sum y, sum (y - stat_c)^2} over `count` positions (stat_c == NULL means 0); when running_mean !=
+ * NULL and momentum >= 0 the running statistics are updated like torch.nn.BatchNorm (unbiased var). */
+typedef struct {
+    const float* part; int nparts, C; double count; const float* stat_c; const float* gamma; const float* beta;
+    float* running_mean; float* running_var; float momentum, eps; float* mean; float* invstd; float* scale; float* shift;
+    const int32_t* meta; int tile, nparts1; double count1;
+} o3d_bn_fin_args;
+int o3d_bn_finalize(const o3d_bn_fin_args* jobs, int njobs, void* stream);
 
 /* out[b,c,j] = max_k relu(Y[b,c,j*ns+k]*scale[c] + shift[c]); optional arg (k of the max) and
  * yarg (raw Y at that k) for the backward pass. */
@@ -160,11 +171,14 @@ int o3d_bn_relu_maxpool_fwd(const float* Y, const float* scale, const float* shi
 int o3d_pool_bwd_partials_split(const float* dOut, const float* out, const float* yarg, const float* mean, int C,
                                 int npoint, int nsplit, float* part, const int32_t* arg, float* pk, void* stream);
 
-/* BatchNorm backward from partials {sum dN, sum dN*(Y-mean)}: dgamma, dbeta and the per-channel
- * coefficients of dY = A1*dN + A2*Y + A3. */
-int o3d_bn_bwd_finalize(const float* part, int nparts, int C, double count, const float* gamma,
-                        const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                        float* A1, float* A2, float* A3, float* fold, void* stream);
+/* Backward, from partials {sum dN, sum dN*(Y-mean)}: dgamma, dbeta (C each, summed over the segments) and the
+ * per-channel coefficients of dY = A1*dN + A2*Y + A3. */
+typedef struct {
+    const float* part; int nparts, C; double count; const float* gamma; const float* mean; const float* invstd;
+    float* dgamma; float* dbeta; float* A1; float* A2; float* A3;
+    const int32_t* meta; int tile, nparts1; double count1;
+} o3d_bn_bwd_fin_args;
+int o3d_bn_bwd_finalize(const o3d_bn_bwd_fin_args* jobs, int njobs, void* stream);
 
 /* Data gradient of an inner layer.  dY comes from dN (dense, (B,Cout,P)) or, when dN == NULL,
  * from the pooled triple (dOut, out, arg) of o3d_bn_relu_maxpool_fwd.  Writes
@@ -193,14 +207,11 @@ int o3d_mlp_conv_dgrad_plain(const float* dN, const float* Y, const float* A1, c
 
 /* Weight gradient dW (Cout,Cin) = sum_{b,p} dY[b,co,p] * X[b,ci,p]; X = f(X raw) as in
  * o3d_mlp_conv_fwd.  part: scratch of (nslices+16)*Cout*Cin floats (split over positions, reduced in a fixed
- * order).  xyz .. inv_radius: arguments of the slot-wise layer-0 gather retired in round 4 (layer 0 runs on the
- * points, csrc/compact.hip); pass NULL / 0, X must not be NULL. */
+ * order).  X must not be NULL. */
 int o3d_mlp_conv_wgrad(const float* dN, const float* dOut, const float* out, const int32_t* arg, int ns,
                        const float* Y, const float* A1, const float* A2, const float* A3,
-                       const float* X, const float* in_scale, const float* in_shift, const float* xyz,
-                       const float* new_xyz, const float* feats, const int32_t* idx, int N, int C,
-                       int nxyz, float inv_radius, int B, int Cin, int Cout, int P, int nslices,
-                       float* part, float* dW, void* stream);
+                       const float* X, const float* in_scale, const float* in_shift, int B, int Cin, int Cout,
+                       int P, int nslices, float* part, float* dW, void* stream);
 
 /* ---- compact (distinct-neighbour) layout, csrc/compact.hip ------------------------------------------
  * ball_query pads a ball with copies of its first hit (pointnet2_utils.py:268); copies have identical
@@ -258,7 +269,7 @@ int o3d_direct_tile(long P, int M, int compact);
  * cuts the remainder tiles of its last resident round (T mod S live tiles, S = o3d_direct_tail_slots(output rows) resident
  * column-tile slots) into 2 or 4 column blocks that run as workgroups of the same launch, decided on the device from the live
  * count.  Their statistics go to EXTRA rows behind the regular ones: `part` must hold ldp/128 + nseg * S rows; the
- * o3d_bn_finalize_c[2] / o3d_bn_bwd_finalize_c[2] calls with tile = 128 follow the same plan (C = the launch's output rows). */
+ * o3d_bn_finalize / o3d_bn_bwd_finalize jobs with meta and tile = 128 follow the same plan (C = the launch's output rows). */
 int o3d_direct_tail_slots(int M);
 /* test hook: -1 automatic (default), 0 no remainder split, S > 0 pretend S slots for every shape */
 int o3d_direct_tail_override(int slots);
@@ -280,16 +291,6 @@ int o3d_mlp_conv_wgrad2_c_dy(const float* dN, const float* Y, const float* A1, c
                              const float* X, const float* in_scale, const float* in_shift, int Cin, int Cout,
                              long ldp, const float* w, const int32_t* meta, long start1, float* scratch, float* dW,
                              float* dY, void* stream);
-
-/* BatchNorm finalize kernels reading only the live partial rows (meta[0] / tile); per segment: pass the
- * segment's first partial row and its meta block. */
-int o3d_bn_finalize_c(const float* part, int nparts, int C, double count, const float* stat_c,
-                      const float* gamma, const float* beta, float* running_mean, float* running_var,
-                      float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
-                      const int32_t* meta, int tile, void* stream);
-int o3d_bn_bwd_finalize_c(const float* part, int nparts, int C, double count, const float* gamma,
-                          const float* mean, const float* invstd, float* dgamma, float* dbeta, float* A1,
-                          float* A2, float* A3, const int32_t* meta, int tile, void* stream);
 
 /* out[b,c,j] = max over the ball's columns of relu(Y*scale+shift) (max_pool2d over nsample,
  * pointnet2_modules.py:69-73); argq = column of the maximum, yarg = raw Y there.  Pooled tensors hold
@@ -384,19 +385,6 @@ int o3d_mlp_conv_wgrad2(const float* dN, const float* pk, int ns, const float* Y
                         const float* in_shift, int B, int Cin, int Cout, int P, float* scratch, float* dW,
                         void* stream);
 
-/* BatchNorm finalize / backward finalize of TWO segments in one launch (template + search cloud through a
- * shared module, models/bat.py:89-90): partial rows [nparts0 | nparts1], stat_c / mean / invstd / scale /
- * shift / A1..A3 laid out (2,C), meta (2,4) (NULL in the backward variant: every row live).  Same numbers as
- * the one-segment entry points called for segment 0, then 1; dgamma / dbeta (C) are summed over the segments. */
-int o3d_bn_finalize_c2(const float* part, int nparts0, int nparts1, int C, double count0, double count1,
-                       const float* stat_c, const float* gamma, const float* beta, float* running_mean,
-                       float* running_var, float momentum, float eps, float* mean, float* invstd, float* scale,
-                       float* shift, const int32_t* meta, int tile, void* stream);
-int o3d_bn_bwd_finalize_c2(const float* part, int nparts0, int nparts1, int C, double count0, double count1,
-                           const float* gamma, const float* mean, const float* invstd, float* dgamma,
-                           float* dbeta, float* A1, float* A2, float* A3, const int32_t* meta, int tile,
-                           void* stream);
-
 /* ---- 1-D conv stacks of the heads on the flat (C, P = B*N) layout -------------------------------------
  * Replaces pt_utils.Seq / Conv1d (+BatchNorm1d +ReLU) stacks, pointnet2/utils/pytorch_utils.py:124-155,300-457, as
  * used by models/head/rpn.py:16-39 (FC_layer_cla, vote_layer, FC_proposal), models/head/xcorr.py:14-17 (fea_layer)
@@ -444,8 +432,8 @@ int o3d_pw_tile(long P, int M);
  * (nseg,Cin): BatchNorm of the producer layer; Wt (Cin,Cout) = W^T; w / meta / start1: compact layout (or NULL, NULL, 0).
  * scratch: o3d_mlp_conv_bwd_fused_scratch(...) floats.  part_s [2][rows][2][Cin], rows = o3d_mlp_conv_bwd_fused_rows(...)
  * (-1: shape not supported): BatchNorm-backward partials {sum g, sum g*(yprev-mean)} of dNprev, segment 1's block after
- * segment 0's -- finalize with o3d_bn_bwd_finalize (one segment) / o3d_bn_bwd_finalize_c2(part_s, rows, rows, ..., meta
- * = NULL, tile = 1). */
+ * segment 0's -- finalize with an o3d_bn_bwd_finalize job over part_s: nparts = rows, nparts1 = rows for two segments,
+ * meta = NULL. */
 int o3d_mlp_conv_bwd_fused_rows(int Cin, int Cout, long P);
 long o3d_mlp_conv_bwd_fused_scratch(int Cin, int Cout, long P);
 int o3d_mlp_conv_bwd_fused_c(const float* dN, const float* Y, const float* A1, const float* A2, const float* A3,
@@ -457,16 +445,6 @@ int o3d_mlp_conv_bwd_fused_c(const float* dN, const float* Y, const float* A1, c
  * the RPN that read the same seeds -- FC_layer_cla and vote_layer, models/head/rpn.py:16-28,44-54 -- advance layer by layer
  * side by side.  Fields = the arguments of o3d_pw_fwd / o3d_pw_dgrad.  When the two problems do not take the same kernel
  * instantiation the entry issues the two single launches instead; the numbers are the same either way. */
-typedef struct {      /* the arguments of o3d_bn_finalize (no fold scratch: partial lists of <= a few hundred rows) */
-    const float* part; int nparts, C; double count; const float* stat_c; const float* gamma; const float* beta;
-    float* running_mean; float* running_var; float momentum, eps; float* mean; float* invstd; float* scale; float* shift;
-} o3d_bn_fin_args;
-typedef struct {      /* the arguments of o3d_bn_bwd_finalize */
-    const float* part; int nparts, C; double count; const float* gamma; const float* mean; const float* invstd;
-    float* dgamma; float* dbeta; float* A1; float* A2; float* A3;
-} o3d_bn_bwd_fin_args;
-int o3d_bn_finalize_pair(const o3d_bn_fin_args* a, const o3d_bn_fin_args* b, void* stream);
-int o3d_bn_bwd_finalize_pair(const o3d_bn_bwd_fin_args* a, const o3d_bn_bwd_fin_args* b, void* stream);
 typedef struct {
     const float* X; const float* W; const float* in_scale; const float* in_shift; const float* bias; const float* resid;
     int Cin, Cout; long P;

@@ -241,75 +241,91 @@ __global__ __launch_bounds__(BM * 2) void conv_fwd_kernel(FwdArgs a) {
 // BatchNorm statistics finalize: partials -> mean / invstd / scale / shift (+ running stats)
 // ======================================================================================
 // finalize kernels: FIN_CH channels x FIN_SL partial-list slices per 256-thread workgroup
-// (round 3 also tried folding the FIN_SL slices with fp64 butterflies instead of the serial LDS walk and fetching the
-// per-channel constants up front: +0.08 ms per step on the same box -- 16 ds_bpermute round trips per lane cost more than
-// 128 pipelined LDS reads by four lanes.  Not kept.  Likewise requesting the per-channel constants first and the first
-// partial rows beside the live count instead of behind it (the kernel looks like a chain of dependent global accesses):
-// 6.04 vs 6.04 / 6.06 vs 5.97 ms per step, 8.6 us per launch in the trace -- no gain, removed.)
-#ifndef O3D_FIN_FASTMATH
-#define O3D_FIN_FASTMATH 1
-#endif
+// Measured and not kept:
+//  - folding the FIN_SL slices with fp64 butterflies instead of the serial LDS walk, and fetching the per-channel
+//    constants up front (round 3): +0.08 ms per step on the same box -- 16 ds_bpermute round trips per lane cost more
+//    than 128 pipelined LDS reads by four lanes.  Requesting the first partial rows beside the live count instead of
+//    behind it: 6.04 vs 6.04 / 6.06 vs 5.97 ms per step, 8.6 us per launch in the trace -- no gain.
+//  - a wide fp32 pre-fold launch in front of the finalize of a long list (rounds 1-4: above 128 rows): 64 lanes per
+//    channel group walk the compact layout's 6 000-row lists in ~8 us without it, and the fold in front of a 768-row
+//    (M2-Track) or 3 072-row (P2B's xcorr) list was a 4.6 us launch each, 31 per M2-Track step
+//    (profiles/r05_ab_partials_fold.txt).  Round 5 kept it above 16 384 rows only, which no list it applied to reaches
+//    (profiles/bn_finalize_refactor.txt): removed.
 constexpr int FIN_CH = 4, FIN_SL = 64;      // measured: 2x128 and 8x32 are both slower (0.24 / 0.36 vs 0.17 ms per step)
 
-struct BnFinArgs {
-    const float* part;  // [nparts][2][C]
+// the list of partial rows both finalize directions reduce
+struct PartList {
+    const float* part;  // [nparts (+ nparts1)][2][C]
     int nparts, C;
     const int32_t* meta; int tile;   // compact layout: only the first meta[0]/tile parts are live (or NULL)
-    double count;       // positions reduced (B*P)
-    const float* stat_c; // shift used by the producer for the second moment, or NULL
-    const float* gamma; const float* beta;
-    float* running_mean; float* running_var;  // updated in place when momentum >= 0 (may be NULL)
-    float momentum, eps;
-    float* mean; float* invstd; float* scale; float* shift;  // outputs (C each)
-    // second segment (nparts1 > 0): its partial rows follow segment 0's `nparts`, its outputs / stat_c sit at
-    // +C, its live count at meta[4]; the running statistics see segment 0's update first
-    int nparts1; double count1;
+    // second segment (nparts1 > 0): its partial rows follow segment 0's `nparts`, its live count is meta[4]
+    int nparts1;
     // statistics rows of a direct GEMM launch whose remainder tiles were cut into column blocks (mlp_common.hpp::tail_plan):
     // the same plan, from the same live count, tells how many extra rows follow the regular ones
     int tail_slots; long extra_row0;
 };
 
-__device__ __forceinline__ void bn_finalize_body(const BnFinArgs& a, const int bx) {
-    // FIN_CH channels x FIN_SL tile-slices per workgroup: the partial list (up to 13 824 tiles) is a
-    // latency-bound strided read, so it is spread over many lanes with 8 loads in flight each
-    __shared__ double sh[2][FIN_SL][FIN_CH + 1];
+// fp64 sums of segment `seg`'s live partial rows for channel c = {sum part[.][0][c], sum part[.][1][c]}, valid on the
+// sl == 0 lanes: the list (up to a few thousand rows) is a latency-bound strided read, so it is spread over FIN_SL
+// lanes with 8 loads in flight each, then folded serially through LDS
+__device__ __forceinline__ void part_list_sums(const PartList& a, const int seg, const int c,
+                                               double (&sh)[2][FIN_SL][FIN_CH + 1], double& s, double& q) {
     const int cl = threadIdx.x % FIN_CH, sl = threadIdx.x / FIN_CH;
-    const int c = bx * FIN_CH + cl;
-    const int nseg = a.nparts1 > 0 ? 2 : 1;
-    for (int seg = 0; seg < nseg; ++seg) {
-        const float* part = a.part + (seg ? (long)a.nparts * 2 * a.C : 0);
-        const double count = seg ? a.count1 : a.count;
-        const int off = seg * a.C;
-        double s = 0.0, q = 0.0;
-        int nparts = seg ? a.nparts1 : a.nparts;
-        int nextra = 0;
-        if (a.meta) {
-            const int cap = nparts;
-            const int live = (a.meta[4 * seg] + a.tile - 1) / a.tile;    // (ceil: a 512-column row of o3d_pool_bwd_dense may be half live)
-            nparts = live < nparts ? live : nparts;
-            if (a.tail_slots > 0) { const TailPlan pl = tail_plan(nparts, a.tail_slots, cap); nextra = pl.R * (pl.f - 1); }
-        }
-        if (c < a.C) {
+    const float* part = a.part + (seg ? (long)a.nparts * 2 * a.C : 0);
+    s = 0.0; q = 0.0;
+    int nparts = seg ? a.nparts1 : a.nparts;
+    int nextra = 0;
+    if (a.meta) {
+        const int cap = nparts;
+        const int live = (a.meta[4 * seg] + a.tile - 1) / a.tile;    // (ceil: a 512-column row of o3d_pool_bwd_dense may be half live)
+        nparts = live < nparts ? live : nparts;
+        if (a.tail_slots > 0) { const TailPlan pl = tail_plan(nparts, a.tail_slots, cap); nextra = pl.R * (pl.f - 1); }
+    }
+    if (c < a.C) {
 #pragma unroll 8
-            for (int t = sl; t < nparts; t += FIN_SL) {
-                s += (double)part[((long)t * 2 + 0) * a.C + c];
-                q += (double)part[((long)t * 2 + 1) * a.C + c];
-            }
-            const float* extra = a.part + (a.extra_row0 + (long)seg * a.tail_slots) * 2 * a.C;
-            for (int t = sl; t < nextra; t += FIN_SL) {
-                s += (double)extra[((long)t * 2 + 0) * a.C + c];
-                q += (double)extra[((long)t * 2 + 1) * a.C + c];
-            }
+        for (int t = sl; t < nparts; t += FIN_SL) {
+            s += (double)part[((long)t * 2 + 0) * a.C + c];
+            q += (double)part[((long)t * 2 + 1) * a.C + c];
         }
-        if (seg) __syncthreads();
-        sh[0][sl][cl] = s;
-        sh[1][sl][cl] = q;
-        __syncthreads();
-        if (sl == 0 && c < a.C) {
-            s = 0.0; q = 0.0;
-            for (int i = 0; i < FIN_SL; ++i) { s += sh[0][i][cl]; q += sh[1][i][cl]; }
+        const float* extra = a.part + (a.extra_row0 + (long)seg * a.tail_slots) * 2 * a.C;
+        for (int t = sl; t < nextra; t += FIN_SL) {
+            s += (double)extra[((long)t * 2 + 0) * a.C + c];
+            q += (double)extra[((long)t * 2 + 1) * a.C + c];
+        }
+    }
+    if (seg) __syncthreads();
+    sh[0][sl][cl] = s;
+    sh[1][sl][cl] = q;
+    __syncthreads();
+    if (sl == 0 && c < a.C) {
+        s = 0.0; q = 0.0;
+        for (int i = 0; i < FIN_SL; ++i) { s += sh[0][i][cl]; q += sh[1][i][cl]; }
+    }
+}
+
+struct BnFinArgs {
+    PartList list;
+    double count, count1;   // positions reduced (B*P) per segment
+    const float* stat_c; // shift used by the producer for the second moment, or NULL
+    const float* gamma; const float* beta;
+    float* running_mean; float* running_var;  // updated in place when momentum >= 0 (may be NULL)
+    float momentum, eps;
+    // outputs (C each); a second segment's outputs / stat_c sit at +C, the running statistics see segment 0's update first
+    float* mean; float* invstd; float* scale; float* shift;
+};
+
+__device__ __forceinline__ void bn_finalize_body(const BnFinArgs& a, const int bx) {
+    __shared__ double sh[2][FIN_SL][FIN_CH + 1];
+    const int sl = threadIdx.x / FIN_CH;
+    const int c = bx * FIN_CH + threadIdx.x % FIN_CH, C = a.list.C;
+    const int nseg = a.list.nparts1 > 0 ? 2 : 1;
+    for (int seg = 0; seg < nseg; ++seg) {
+        const double count = seg ? a.count1 : a.count;
+        const int off = seg * C;
+        double s, q;
+        part_list_sums(a.list, seg, c, sh, s, q);
+        if (sl == 0 && c < C) {
             const double cs = a.stat_c ? (double)a.stat_c[off + c] : 0.0;
-#if O3D_FIN_FASTMATH
             // no fp64 division / square root (software sequences of ~40 instructions each, on one lane per channel: measured
             // -0.05 ms per BAT step over the 24 forward finalizes, same-box A/B): v_rsq_f32 + one fp64 Newton step
             // (relative error ~1e-14), the reciprocal of the count taken once
@@ -321,12 +337,6 @@ __device__ __forceinline__ void bn_finalize_body(const BnFinArgs& a, const int b
             double rd = (double)rsqrtf((float)v);
             rd = rd * (1.5 - 0.5 * v * rd * rd);
             const float invstd = (float)rd;
-#else
-            const double mean = s / count;
-            double var = q / count - (mean - cs) * (mean - cs);
-            if (var < 0.0) var = 0.0;
-            const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
-#endif
             const float g = a.gamma ? a.gamma[c] : 1.f, bt = a.beta ? a.beta[c] : 0.f;
             a.mean[off + c] = (float)mean;
             a.invstd[off + c] = invstd;
@@ -346,45 +356,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinArgs a) { bn_fina
 
 // two independent finalizes (two BatchNorm layers of two conv stacks advancing side by side) in one launch
 __global__ __launch_bounds__(256) void bn_finalize_pair_kernel(BnFinArgs a0, BnFinArgs a1) {
-    if (blockIdx.y == 0) { if ((int)blockIdx.x * FIN_CH < a0.C) bn_finalize_body(a0, blockIdx.x); }
-    else if ((int)blockIdx.x * FIN_CH < a1.C) bn_finalize_body(a1, blockIdx.x);
-}
-
-// Stage 1 of a long partial list: out[g][i] = sum over parts t = g, g+G, g+2G, ... of part[t][i],
-// i over the 2*C (statistic, channel) columns; coalesced rows, G x ceil(2C/256) workgroups.  The
-// finalize kernels then walk G parts instead of thousands from 1-4 workgroups.
-__global__ __launch_bounds__(256) void partials_fold_kernel(const float* __restrict__ part, int nparts, int n2c,
-                                                            int G, float* __restrict__ out) {
-    const int i = blockIdx.y * 256 + threadIdx.x, g = blockIdx.x;
-    if (i >= n2c) return;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int t = g;
-    for (; t + 3 * G < nparts; t += 4 * G) {
-        s0 += part[(long)t * n2c + i];
-        s1 += part[(long)(t + G) * n2c + i];
-        s2 += part[(long)(t + 2 * G) * n2c + i];
-        s3 += part[(long)(t + 3 * G) * n2c + i];
-    }
-    for (; t < nparts; t += G) s0 += part[(long)t * n2c + i];
-    out[(long)g * n2c + i] = (s0 + s1) + (s2 + s3);
-}
-
-constexpr int FOLD_G = 32;
-
-// folds a long partial list into FOLD_G parts in caller scratch (FOLD_G*2*C floats); no-op when short
-static const float* fold_partials(const float* part, int& nparts, int C, float* fold, hipStream_t s) {
-    // Round 5: only lists beyond O3D_FOLD_ABOVE rows are folded first.  The finalize kernels walk a list with 64 lanes per
-    // channel group and handle the compact layout's 6 000-row lists in ~8 us without a fold; the fold launch in front of every
-    // finalize of a 768-row (M2-Track, 98 304 columns) or 3 072-row (P2B's xcorr) list was a 4.6 us launch each, 31 per M2-Track
-    // step (threshold was 128 rows; same-box A/B in profiles/r05_ab_partials_fold.txt)
-#ifndef O3D_FOLD_ABOVE
-#define O3D_FOLD_ABOVE 16384
-#endif
-    if (!fold || nparts <= O3D_FOLD_ABOVE) return part;
-    hipLaunchKernelGGL(partials_fold_kernel, dim3(FOLD_G, o3d_cdiv(2 * C, 256)), dim3(256), 0, s, part, nparts, 2 * C,
-                       FOLD_G, fold);
-    nparts = FOLD_G;
-    return fold;
+    if (blockIdx.y == 0) { if ((int)blockIdx.x * FIN_CH < a0.list.C) bn_finalize_body(a0, blockIdx.x); }
+    else if ((int)blockIdx.x * FIN_CH < a1.list.C) bn_finalize_body(a1, blockIdx.x);
 }
 
 // ======================================================================================
@@ -465,71 +438,38 @@ __global__ __launch_bounds__(256) void pool_bwd_partials_split_kernel(const floa
 // BatchNorm backward finalize: partials {sum dN, sum dN*(Y-mean)} -> dgamma, dbeta and the
 // coefficients of dY = A1*dN + A2*Y + A3 (per channel).
 struct BnBwdFinArgs {
-    const float* part; int nparts, C; double count;
-    const int32_t* meta; int tile;
+    PartList list;
+    double count, count1;
     const float* gamma; const float* mean; const float* invstd;
+    // a second segment's mean / invstd / A1..A3 sit at +C; dgamma / dbeta (C each) are the SUM over the segments (the
+    // affine parameters are shared)
     float* dgamma; float* dbeta; float* A1; float* A2; float* A3;
-    // second segment (nparts1 > 0): partial rows after segment 0's, mean / invstd / A1..A3 at +C, live count at
-    // meta[4]; dgamma / dbeta (C each) are the SUM over the segments (the affine parameters are shared)
-    int nparts1; double count1;
-    int tail_slots; long extra_row0;      // as BnFinArgs
 };
 
 __device__ __forceinline__ void bn_bwd_finalize_body(const BnBwdFinArgs& a, const int bx) {
     __shared__ double sh[2][FIN_SL][FIN_CH + 1];
-    const int cl = threadIdx.x % FIN_CH, sl = threadIdx.x / FIN_CH;
-    const int c = bx * FIN_CH + cl;
-    const int nseg = a.nparts1 > 0 ? 2 : 1;
+    const int sl = threadIdx.x / FIN_CH;
+    const int c = bx * FIN_CH + threadIdx.x % FIN_CH, C = a.list.C;
+    const int nseg = a.list.nparts1 > 0 ? 2 : 1;
     double dg = 0.0, db = 0.0;
     for (int seg = 0; seg < nseg; ++seg) {
-        const float* part = a.part + (seg ? (long)a.nparts * 2 * a.C : 0);
         const double count = seg ? a.count1 : a.count;
-        const int off = seg * a.C;
-        double s = 0.0, q = 0.0;
-        int nparts = seg ? a.nparts1 : a.nparts;
-        int nextra = 0;
-        if (a.meta) {
-            const int cap = nparts;
-            const int live = (a.meta[4 * seg] + a.tile - 1) / a.tile;    // (ceil: a 512-column row of o3d_pool_bwd_dense may be half live)
-            nparts = live < nparts ? live : nparts;
-            if (a.tail_slots > 0) { const TailPlan pl = tail_plan(nparts, a.tail_slots, cap); nextra = pl.R * (pl.f - 1); }
-        }
-        if (c < a.C) {
-#pragma unroll 8
-            for (int t = sl; t < nparts; t += FIN_SL) {
-                s += (double)part[((long)t * 2 + 0) * a.C + c];
-                q += (double)part[((long)t * 2 + 1) * a.C + c];
-            }
-            const float* extra = a.part + (a.extra_row0 + (long)seg * a.tail_slots) * 2 * a.C;
-            for (int t = sl; t < nextra; t += FIN_SL) {
-                s += (double)extra[((long)t * 2 + 0) * a.C + c];
-                q += (double)extra[((long)t * 2 + 1) * a.C + c];
-            }
-        }
-        if (seg) __syncthreads();
-        sh[0][sl][cl] = s;
-        sh[1][sl][cl] = q;
-        __syncthreads();
-        if (sl == 0 && c < a.C) {
-            s = 0.0; q = 0.0;
-            for (int i = 0; i < FIN_SL; ++i) { s += sh[0][i][cl]; q += sh[1][i][cl]; }
+        const int off = seg * C;
+        double s, q;
+        part_list_sums(a.list, seg, c, sh, s, q);
+        if (sl == 0 && c < C) {
             const double g = a.gamma ? (double)a.gamma[c] : 1.0;
             const double is = (double)a.invstd[off + c], mu = (double)a.mean[off + c];
             db += s;
             dg += q * is;
             const double a1 = g * is;
-#if O3D_FIN_FASTMATH
             const double ic = 1.0 / count;
             const double a2 = -a1 * is * is * q * ic;
             const double a3 = -a1 * s * ic - a2 * mu;
-#else
-            const double a2 = -a1 * is * is * q / count;
-            const double a3 = -a1 * s / count - a2 * mu;
-#endif
             a.A1[off + c] = (float)a1; a.A2[off + c] = (float)a2; a.A3[off + c] = (float)a3;
         }
     }
-    if (sl == 0 && c < a.C) {
+    if (sl == 0 && c < C) {
         a.dbeta[c] = (float)db;
         a.dgamma[c] = (float)dg;
     }
@@ -538,8 +478,8 @@ __device__ __forceinline__ void bn_bwd_finalize_body(const BnBwdFinArgs& a, cons
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(BnBwdFinArgs a) { bn_bwd_finalize_body(a, blockIdx.x); }
 
 __global__ __launch_bounds__(256) void bn_bwd_finalize_pair_kernel(BnBwdFinArgs a0, BnBwdFinArgs a1) {
-    if (blockIdx.y == 0) { if ((int)blockIdx.x * FIN_CH < a0.C) bn_bwd_finalize_body(a0, blockIdx.x); }
-    else if ((int)blockIdx.x * FIN_CH < a1.C) bn_bwd_finalize_body(a1, blockIdx.x);
+    if (blockIdx.y == 0) { if ((int)blockIdx.x * FIN_CH < a0.list.C) bn_bwd_finalize_body(a0, blockIdx.x); }
+    else if ((int)blockIdx.x * FIN_CH < a1.list.C) bn_bwd_finalize_body(a1, blockIdx.x);
 }
 
 // ======================================================================================
@@ -992,48 +932,53 @@ extern "C" int o3d_mlp_conv_fwd(const float* X, const float* W, const float* in_
     return in_scale ? launch_fwd<true>(a, o3d_stream(stream)) : launch_fwd<false>(a, o3d_stream(stream));
 }
 
-extern "C" int o3d_bn_finalize(const float* part, int nparts, int C, double count, const float* stat_c,
-                               const float* gamma, const float* beta, float* running_mean,
-                               float* running_var, float momentum, float eps, float* mean,
-                               float* invstd, float* scale, float* shift, float* fold, void* stream) {
-    if (!part || nparts <= 0 || C <= 0 || !mean || !invstd || !scale || !shift) return O3D_EINVAL;
-    part = fold_partials(part, nparts, C, fold, o3d_stream(stream));
-    BnFinArgs a = {part, nparts, C, nullptr, 1, count, stat_c, gamma, beta, running_mean, running_var, momentum, eps,
-                   mean, invstd, scale, shift};
-    return launch(bn_finalize_kernel, dim3(o3d_cdiv(C, FIN_CH)), dim3(256), 0, o3d_stream(stream), a);
+// ---- BatchNorm finalize, both directions: one or two independent jobs per launch (o3dsot.h) ----
+static_assert(sizeof(o3d_bn_fin_args) == 128 && sizeof(o3d_bn_bwd_fin_args) == 112,
+              "the ctypes mirrors in open3dsot_amd/fused.py (and tests/test_capi_symbols.py) assume this layout");
+
+// the partial-list fields of a job (common to both directions) -> l; false when they are invalid
+template <typename Job>
+static bool fin_part_list(const Job& x, PartList& l) {
+    if (!x.part || x.nparts <= 0 || x.C <= 0 || x.nparts1 < 0 || (x.meta && x.tile <= 0)) return false;
+    l = PartList{x.part, x.nparts, x.C, x.meta, x.tile, x.nparts1, 0, 0};
+    if (x.meta && x.tile == 128) {      // rows of a direct GEMM launch: its remainder-tile rows follow the regular ones
+        l.tail_slots = o3d_direct_tail_slots(x.C);
+        l.extra_row0 = (long)x.nparts + x.nparts1;
+    }
+    return true;
 }
 
-// o3d_bn_finalize for two independent layers in one launch (short partial lists: no fold stage)
-extern "C" int o3d_bn_finalize_pair(const o3d_bn_fin_args* pa, const o3d_bn_fin_args* pb, void* stream) {
-    if (!pa || !pb) return O3D_EINVAL;
+template <typename Args, typename K1, typename K2>
+static int launch_fin(const Args* v, int njobs, K1 single, K2 pair, void* stream) {
+    if (njobs == 1) return launch(single, dim3(o3d_cdiv(v[0].list.C, FIN_CH)), dim3(256), 0, o3d_stream(stream), v[0]);
+    const int cmax = v[0].list.C > v[1].list.C ? v[0].list.C : v[1].list.C;
+    return launch(pair, dim3(o3d_cdiv(cmax, FIN_CH), 2), dim3(256), 0, o3d_stream(stream), v[0], v[1]);
+}
+
+extern "C" int o3d_bn_finalize(const o3d_bn_fin_args* jobs, int njobs, void* stream) {
+    if (!jobs || njobs < 1 || njobs > 2) return O3D_EINVAL;
     BnFinArgs v[2];
-    const o3d_bn_fin_args* q[2] = {pa, pb};
-    for (int i = 0; i < 2; ++i) {
-        const o3d_bn_fin_args& x = *q[i];
-        if (!x.part || x.nparts <= 0 || x.C <= 0 || !x.mean || !x.invstd || !x.scale || !x.shift) return O3D_EINVAL;
-        v[i] = BnFinArgs{x.part, x.nparts, x.C, nullptr, 1, x.count, x.stat_c, x.gamma, x.beta, x.running_mean, x.running_var,
-                         x.momentum, x.eps, x.mean, x.invstd, x.scale, x.shift};
+    for (int i = 0; i < njobs; ++i) {
+        const o3d_bn_fin_args& x = jobs[i];
+        PartList l;
+        if (!fin_part_list(x, l) || !x.mean || !x.invstd || !x.scale || !x.shift) return O3D_EINVAL;
+        v[i] = BnFinArgs{l, x.count, x.count1, x.stat_c, x.gamma, x.beta, x.running_mean, x.running_var, x.momentum,
+                         x.eps, x.mean, x.invstd, x.scale, x.shift};
     }
-    const int cmax = pa->C > pb->C ? pa->C : pb->C;
-    hipLaunchKernelGGL(bn_finalize_pair_kernel, dim3(o3d_cdiv(cmax, FIN_CH), 2), dim3(256), 0, o3d_stream(stream), v[0], v[1]);
-    return o3d_launch_status();
+    return launch_fin(v, njobs, bn_finalize_kernel, bn_finalize_pair_kernel, stream);
 }
 
-extern "C" int o3d_bn_bwd_finalize_pair(const o3d_bn_bwd_fin_args* pa, const o3d_bn_bwd_fin_args* pb, void* stream) {
-    if (!pa || !pb) return O3D_EINVAL;
+extern "C" int o3d_bn_bwd_finalize(const o3d_bn_bwd_fin_args* jobs, int njobs, void* stream) {
+    if (!jobs || njobs < 1 || njobs > 2) return O3D_EINVAL;
     BnBwdFinArgs v[2];
-    const o3d_bn_bwd_fin_args* q[2] = {pa, pb};
-    for (int i = 0; i < 2; ++i) {
-        const o3d_bn_bwd_fin_args& x = *q[i];
-        if (!x.part || x.nparts <= 0 || x.C <= 0 || !x.mean || !x.invstd || !x.dgamma || !x.dbeta || !x.A1 || !x.A2 || !x.A3)
+    for (int i = 0; i < njobs; ++i) {
+        const o3d_bn_bwd_fin_args& x = jobs[i];
+        PartList l;
+        if (!fin_part_list(x, l) || !x.mean || !x.invstd || !x.dgamma || !x.dbeta || !x.A1 || !x.A2 || !x.A3)
             return O3D_EINVAL;
-        v[i] = BnBwdFinArgs{x.part, x.nparts, x.C, x.count, nullptr, 1, x.gamma, x.mean, x.invstd, x.dgamma, x.dbeta, x.A1, x.A2,
-                            x.A3};
+        v[i] = BnBwdFinArgs{l, x.count, x.count1, x.gamma, x.mean, x.invstd, x.dgamma, x.dbeta, x.A1, x.A2, x.A3};
     }
-    const int cmax = pa->C > pb->C ? pa->C : pb->C;
-    hipLaunchKernelGGL(bn_bwd_finalize_pair_kernel, dim3(o3d_cdiv(cmax, FIN_CH), 2), dim3(256), 0, o3d_stream(stream), v[0],
-                       v[1]);
-    return o3d_launch_status();
+    return launch_fin(v, njobs, bn_bwd_finalize_kernel, bn_bwd_finalize_pair_kernel, stream);
 }
 
 extern "C" int o3d_bn_relu_maxpool_fwd(const float* Y, const float* scale, const float* shift, int B,
@@ -1057,67 +1002,6 @@ extern "C" int o3d_pool_bwd_partials_split(const float* dOut, const float* out, 
     hipLaunchKernelGGL(pool_bwd_partials_split_kernel, dim3(C, nsplit), dim3(256), 0, o3d_stream(stream), dOut, out, yarg,
                        mean, C, npoint, part, arg, reinterpret_cast<float2*>(pk));
     return o3d_launch_status();
-}
-
-extern "C" int o3d_bn_bwd_finalize(const float* part, int nparts, int C, double count, const float* gamma,
-                                   const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                                   float* A1, float* A2, float* A3, float* fold, void* stream) {
-    if (!part || nparts <= 0 || C <= 0 || !mean || !invstd || !dgamma || !dbeta || !A1 || !A2 || !A3)
-        return O3D_EINVAL;
-    part = fold_partials(part, nparts, C, fold, o3d_stream(stream));
-    BnBwdFinArgs a = {part, nparts, C, count, nullptr, 1, gamma, mean, invstd, dgamma, dbeta, A1, A2, A3};
-    return launch(bn_bwd_finalize_kernel, dim3(o3d_cdiv(C, FIN_CH)), dim3(256), 0, o3d_stream(stream), a);
-}
-
-// compact layout: only the first meta[0]/tile partial rows are live (tile = positions per partial row)
-extern "C" int o3d_bn_finalize_c(const float* part, int nparts, int C, double count, const float* stat_c,
-                                 const float* gamma, const float* beta, float* running_mean, float* running_var,
-                                 float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
-                                 const int32_t* meta, int tile, void* stream) {
-    if (!part || nparts <= 0 || C <= 0 || !mean || !invstd || !scale || !shift || !meta || tile <= 0) return O3D_EINVAL;
-    BnFinArgs a = {part, nparts, C, meta, tile, count, stat_c, gamma, beta, running_mean, running_var, momentum, eps,
-                   mean, invstd, scale, shift};
-    if (tile == 128) { a.tail_slots = o3d_direct_tail_slots(C); a.extra_row0 = nparts; }     // rows of a direct GEMM launch
-    return launch(bn_finalize_kernel, dim3(o3d_cdiv(C, FIN_CH)), dim3(256), 0, o3d_stream(stream), a);
-}
-
-extern "C" int o3d_bn_bwd_finalize_c(const float* part, int nparts, int C, double count, const float* gamma,
-                                     const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                                     float* A1, float* A2, float* A3, const int32_t* meta, int tile, void* stream) {
-    if (!part || nparts <= 0 || C <= 0 || !mean || !invstd || !dgamma || !dbeta || !A1 || !A2 || !A3 || !meta ||
-        tile <= 0)
-        return O3D_EINVAL;
-    BnBwdFinArgs a = {part, nparts, C, count, meta, tile, gamma, mean, invstd, dgamma, dbeta, A1, A2, A3};
-    if (tile == 128) { a.tail_slots = o3d_direct_tail_slots(C); a.extra_row0 = nparts; }
-    return launch(bn_bwd_finalize_kernel, dim3(o3d_cdiv(C, FIN_CH)), dim3(256), 0, o3d_stream(stream), a);
-}
-
-// Two segments in one launch (see BnFinArgs): partial rows [nparts0 | nparts1], stat_c / outputs (2, C),
-// meta (2, 4).  Equivalent to o3d_bn_finalize_c for segment 0 followed by segment 1.
-extern "C" int o3d_bn_finalize_c2(const float* part, int nparts0, int nparts1, int C, double count0, double count1,
-                                  const float* stat_c, const float* gamma, const float* beta, float* running_mean,
-                                  float* running_var, float momentum, float eps, float* mean, float* invstd,
-                                  float* scale, float* shift, const int32_t* meta, int tile, void* stream) {
-    if (!part || nparts0 <= 0 || nparts1 <= 0 || C <= 0 || !mean || !invstd || !scale || !shift || !meta || tile <= 0)
-        return O3D_EINVAL;
-    BnFinArgs a = {part, nparts0, C, meta, tile, count0, stat_c, gamma, beta, running_mean, running_var, momentum, eps,
-                   mean, invstd, scale, shift, nparts1, count1};
-    if (tile == 128) { a.tail_slots = o3d_direct_tail_slots(C); a.extra_row0 = (long)nparts0 + nparts1; }
-    return launch(bn_finalize_kernel, dim3(o3d_cdiv(C, FIN_CH)), dim3(256), 0, o3d_stream(stream), a);
-}
-
-// Two segments in one launch; meta may be NULL (every partial row live).  dgamma / dbeta (C) = sum over segments.
-extern "C" int o3d_bn_bwd_finalize_c2(const float* part, int nparts0, int nparts1, int C, double count0, double count1,
-                                      const float* gamma, const float* mean, const float* invstd, float* dgamma,
-                                      float* dbeta, float* A1, float* A2, float* A3, const int32_t* meta, int tile,
-                                      void* stream) {
-    if (!part || nparts0 <= 0 || nparts1 <= 0 || C <= 0 || !mean || !invstd || !dgamma || !dbeta || !A1 || !A2 || !A3 ||
-        tile <= 0)
-        return O3D_EINVAL;
-    BnBwdFinArgs a = {part, nparts0, C, count0, meta, tile, gamma, mean, invstd, dgamma, dbeta, A1, A2, A3, nparts1,
-                      count1};
-    if (tile == 128 && meta) { a.tail_slots = o3d_direct_tail_slots(C); a.extra_row0 = (long)nparts0 + nparts1; }
-    return launch(bn_bwd_finalize_kernel, dim3(o3d_cdiv(C, FIN_CH)), dim3(256), 0, o3d_stream(stream), a);
 }
 
 static int fill_dy(DyArgs& d, const float* dN, const float* dOut, const float* out, const int32_t* arg,
@@ -1208,19 +1092,14 @@ void o3d_wgrad_reduce(const float* part, int nslices, long n, float* scratch2, f
 }
 
 // weight gradient.  `part` is scratch of (nslices+16)*Cout*Cin floats; dW (Cout,Cin) is overwritten.
-// X source: (X, in_scale, in_shift) (in_scale NULL = identity).  The gather arguments (xyz ... inv_radius) belonged to
-// the slot-wise layer-0 path retired in round 4 (layer 0 runs on the points, csrc/compact.hip): pass NULL / 0.
+// X source: (X, in_scale, in_shift) (in_scale NULL = identity).
 extern "C" int o3d_mlp_conv_wgrad(const float* dN, const float* dOut, const float* out, const int32_t* arg,
                                   int ns, const float* Y, const float* A1, const float* A2, const float* A3,
                                   const float* X, const float* in_scale, const float* in_shift,
-                                  const float* xyz, const float* new_xyz, const float* feats,
-                                  const int32_t* idx, int N, int C, int nxyz, float inv_radius,
                                   int B, int Cin, int Cout, int P, int nslices, float* part, float* dW,
                                   void* stream) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0 || P % WBK != 0 || nslices <= 0 || !part || !dW)
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0 || P % WBK != 0 || nslices <= 0 || !X || !part || !dW)
         return O3D_EINVAL;
-    (void)xyz; (void)new_xyz; (void)feats; (void)idx; (void)N; (void)C; (void)nxyz; (void)inv_radius;
-    if (!X) return O3D_EINVAL;
     WgradArgs a = {};
     if (fill_dy(a.dy, dN, dOut, out, arg, Y, A1, A2, A3, ns) != O3D_OK) return O3D_EINVAL;
     a.X = X; a.in_scale = in_scale; a.in_shift = in_shift;

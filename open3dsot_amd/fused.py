@@ -36,11 +36,8 @@ capi.register("o3d_mlp_conv_wgrad2_scratch", [_i, _i, _i, _i])
 capi.register("o3d_mlp_conv_bwd_fused_rows", [_i, _i, ctypes.c_long])
 capi.register("o3d_mlp_conv_bwd_fused_scratch", [_i, _i, ctypes.c_long])
 capi.register("o3d_mlp_conv_bwd_fused_c", [_vp] * 10 + [_i, _i, ctypes.c_long, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_bn_finalize", [_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp])
 capi.register("o3d_bn_relu_maxpool_fwd", [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_bn_bwd_finalize", [_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                     _i, _i, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp])
+capi.register("o3d_mlp_conv_wgrad", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp])
 
 _l = ctypes.c_long
 capi.register("o3d_compact_build", [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
@@ -49,8 +46,6 @@ capi.register("o3d_group_dw0_xyz", [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, 
 capi.register("o3d_compact_build2", [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 capi.register("o3d_group_expand_c", [_vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _l, _vp, _vp, _vp, _vp])
 POOL_BWD_SPLIT = 8      # O3D_POOL_BWD_SPLIT of include/o3dsot.h
-capi.register("o3d_bn_finalize_c2", [_vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp])
-capi.register("o3d_bn_bwd_finalize_c2", [_vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp])
 capi.register("o3d_group_reduce_gather_scratch", [_i, _i, _i, _i, _i, _i, _i])
 capi.register("o3d_group_reduce_gather", [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
                                           _vp, _vp, _vp, _vp])
@@ -72,8 +67,22 @@ capi.register("o3d_mlp_conv_dgrad_c", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l,
                                        _vp, _vp])
 capi.register("o3d_mlp_conv_wgrad2_c", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp])
 capi.register("o3d_mlp_conv_wgrad2_c_dy", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp])
-capi.register("o3d_bn_finalize_c", [_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp])
-capi.register("o3d_bn_bwd_finalize_c", [_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp])
+
+
+class _BnFinArgs(ctypes.Structure):       # o3d_bn_fin_args
+    _fields_ = [("part", _vp), ("nparts", _i), ("C", _i), ("count", _d), ("stat_c", _vp), ("gamma", _vp), ("beta", _vp),
+                ("running_mean", _vp), ("running_var", _vp), ("momentum", _f), ("eps", _f), ("mean", _vp), ("invstd", _vp),
+                ("scale", _vp), ("shift", _vp), ("meta", _vp), ("tile", _i), ("nparts1", _i), ("count1", _d)]
+
+
+class _BnBwdFinArgs(ctypes.Structure):    # o3d_bn_bwd_fin_args
+    _fields_ = [("part", _vp), ("nparts", _i), ("C", _i), ("count", _d), ("gamma", _vp), ("mean", _vp), ("invstd", _vp),
+                ("dgamma", _vp), ("dbeta", _vp), ("A1", _vp), ("A2", _vp), ("A3", _vp), ("meta", _vp), ("tile", _i),
+                ("nparts1", _i), ("count1", _d)]
+
+
+capi.register("o3d_bn_finalize", [_vp, _i, _vp])
+capi.register("o3d_bn_bwd_finalize", [_vp, _i, _vp])
 
 TILE = 128   # point columns are padded to this (the widest wave tile of the GEMM kernels, csrc/mlp_direct.hip)
 ETILE = 256  # columns per workgroup tile of the layer-0 expand kernel (csrc/compact.hip expand_c_kernel)
@@ -108,6 +117,46 @@ def _eval_consts(lib, bn, gamma, beta, vec, nrep, st, conv_bias=None):
     """eval-mode BatchNorm -> vec (4, nrep, C) = mean, invstd, scale, shift (one launch, csrc/heads.hip)"""
     _call("bn_eval_consts", 0.0, lib.o3d_bn_eval_consts, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
           gamma.data_ptr(), beta.data_ptr(), _ptr(conv_bias), float(bn.eps), bn.running_mean.numel(), nrep, vec.data_ptr(), st)
+
+
+def bn_fin_job(part, rows, counts, bn, gamma, beta, vec, statc, meta=None, tile=0):
+    """o3d_bn_fin_args of one training-mode BatchNorm layer: statistics partials part (sum(rows), 2, C) over `counts` positions ->
+    vec (4, [nseg,] C) = mean, invstd, scale, shift, and the running statistics of `bn`.  rows / counts: a list, one entry per
+    segment; meta / tile: compact layout (only ceil(meta[0] / tile) rows are live)"""
+    (r0, r1), (n0, n1) = (list(rows) + [0])[:2], (list(counts) + [0.0])[:2]
+    return _BnFinArgs(part.data_ptr(), r0, vec.shape[-1], n0, _ptr(statc), gamma.data_ptr(), beta.data_ptr(),
+                      bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
+                      vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), _ptr(meta), tile, r1, n1)
+
+
+def bn_finalize(lib, st, *job, **kw):
+    """build the forward job (arguments of `bn_fin_job`) and launch it"""
+    job = bn_fin_job(*job, **kw)
+    _call("bn_finalize", 0.0, lib.o3d_bn_finalize, ctypes.addressof(job), 1, st)
+
+
+def bn_bwd_fin_job(part, rows, counts, gamma, mean, invstd, meta=None, tile=0):
+    """o3d_bn_bwd_fin_args of one BatchNorm layer and the tensor it fills: coef (5, [nseg,] C) = dgamma, dbeta (row 0: summed
+    over the segments), A1, A2, A3.  mean / invstd ([nseg,] C) from the forward; the rest as in `bn_fin_job`"""
+    (r0, r1), (n0, n1) = (list(rows) + [0])[:2], (list(counts) + [0.0])[:2]
+    coef = torch.empty((5,) + tuple(mean.shape), device=mean.device, dtype=torch.float32)
+    return _BnBwdFinArgs(part.data_ptr(), r0, mean.shape[-1], n0, gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                         *[coef[k].data_ptr() for k in range(5)], _ptr(meta), tile, r1, n1), coef
+
+
+def bn_bwd_coef(coef, training):
+    """after the launch: (coef, (A1, A2, A3) pointers).  An eval-mode BatchNorm is a fixed affine map: dY = A1 * dN"""
+    if not training:
+        coef[3].zero_()
+        coef[4].zero_()
+    return coef, (coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr())
+
+
+def bn_bwd_finalize(lib, st, training, *job, **kw):
+    """build the backward job (arguments of `bn_bwd_fin_job`), launch it -> coef, (A1, A2, A3) pointers"""
+    job, coef = bn_bwd_fin_job(*job, **kw)
+    _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize, ctypes.addressof(job), 1, st)
+    return bn_bwd_coef(coef, training)
 
 
 # BatchNorm `num_batches_tracked` increments: inside a tracker forward (fused_heads.prep_scope) they are collected and
@@ -611,16 +660,8 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                       scales[-1].data_ptr(), shifts[-1].data_ptr(), Cin, Cout, ldp, cw.data_ptr(), meta.data_ptr(), start1,
                       tile, Y.data_ptr(), _ptr(part), _ptr(statc), st, dims=(Cin, Cout))
             vec = torch.empty((4, nseg, Cout), device=dev, dtype=f32)      # mean, invstd, scale, shift per segment
-            if cfg.training and nseg == 1:
-                _call("bn_finalize", 0.0, lib.o3d_bn_finalize_c, part.data_ptr(), Pmaxs[0] // tile, Cout, counts[0],
-                      statc.data_ptr(), gammas[l].data_ptr(), betas[l].data_ptr(), bn.running_mean.data_ptr(),
-                      bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps), vec[0].data_ptr(), vec[1].data_ptr(),
-                      vec[2].data_ptr(), vec[3].data_ptr(), meta.data_ptr(), tile, st)
-            elif cfg.training:       # both segments in one launch; the running statistics see segment 0's update first
-                _call("bn_finalize", 0.0, lib.o3d_bn_finalize_c2, part.data_ptr(), Pmaxs[0] // tile, Pmaxs[1] // tile, Cout,
-                      counts[0], counts[1], statc.data_ptr(), gammas[l].data_ptr(), betas[l].data_ptr(),
-                      bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
-                      vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), meta.data_ptr(), tile, st)
+            if cfg.training:         # both segments in one launch; the running statistics see segment 0's update first
+                bn_finalize(lib, st, part, [pm // tile for pm in Pmaxs], counts, bn, gammas[l], betas[l], vec, statc, meta, tile)
             else:
                 _eval_consts(lib, bn, gammas[l], betas[l], vec, nseg, st)
             Ys.append(Y)
@@ -717,36 +758,14 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         seg_grads = [[None, None, None] for _ in range(nseg)]
         for l in range(L - 1, -1, -1):
             Cout, Cin = Ws[l].shape
-            coef = torch.empty((5, nseg, Cout), device=dev, dtype=f32)  # dgamma dbeta (row 0: all segments) A1 A2 A3
-            cp = [coef[k].data_ptr() for k in range(5)]
             if l == L - 1 and not pool_dense:       # partials of the pool backward: POOL_BWD_SPLIT rows per segment, all live
-                if nseg == 1:
-                    _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize, part.data_ptr(), POOL_BWD_SPLIT, Cout, counts[0],
-                          gammas[l].data_ptr(), means[l].data_ptr(), invstds[l].data_ptr(), *cp, None, st)
-                else:
-                    _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize_c2, part.data_ptr(), POOL_BWD_SPLIT, POOL_BWD_SPLIT,
-                          Cout, counts[0], counts[1], gammas[l].data_ptr(), means[l].data_ptr(), invstds[l].data_ptr(), *cp,
-                          None, 1, st)
+                rows, live = [POOL_BWD_SPLIT] * nseg, ()
             elif part_rows:      # partials of the fused data + weight gradient kernel: part_rows rows per segment block, all live
-                if nseg == 1:
-                    _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize, part.data_ptr(), part_rows, Cout, counts[0],
-                          gammas[l].data_ptr(), means[l].data_ptr(), invstds[l].data_ptr(), *cp, None, st)
-                else:
-                    _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize_c2, part.data_ptr(), part_rows, part_rows,
-                          Cout, counts[0], counts[1], gammas[l].data_ptr(), means[l].data_ptr(), invstds[l].data_ptr(), *cp,
-                          None, 1, st)
-            elif nseg == 1:
-                _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize_c, part.data_ptr(), Pmaxs[0] // dtile, Cout, counts[0],
-                      gammas[l].data_ptr(), means[l].data_ptr(), invstds[l].data_ptr(), *cp, meta.data_ptr(), dtile, st)
-            else:
-                _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize_c2, part.data_ptr(), Pmaxs[0] // dtile,
-                      Pmaxs[1] // dtile, Cout, counts[0], counts[1], gammas[l].data_ptr(), means[l].data_ptr(),
-                      invstds[l].data_ptr(), *cp, meta.data_ptr(), dtile, st)
-            if not cfg.training:
-                coef[3].zero_()
-                coef[4].zero_()
+                rows, live = [part_rows] * nseg, ()
+            else:                # one row per dtile columns, the live ones
+                rows, live = [pm // dtile for pm in Pmaxs], (meta, dtile)
+            coef, A = bn_bwd_finalize(lib, st, cfg.training, part, rows, counts, gammas[l], means[l], invstds[l], *live)
             grads[3 * l + 1], grads[3 * l + 2] = coef[0, 0], coef[1, 0]      # summed over the segments by the kernel
-            A = (coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr())
             if l == 0 and C == 0 and nxyz == 3 and not (want_xyz or want_feats):
                 # xyz-only layer 0, nobody wants the input gradient (SA level 0): dW0 straight from the columns, no list
                 # sums, no K = 3 GEMM, no centre term (csrc/compact.hip::dw0_xyz_kernel)
@@ -800,8 +819,7 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                     else:
                         _call("conv_wgrad_points", 2.0 * Cin * Cout * ldz, lib.o3d_mlp_conv_wgrad, S.data_ptr(), None, None,
                               None, 4, S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None,
-                              None, None, None, None, None, 0, 0, 0, 1.0, 1, Cin, Cout, ldz, nsl, wpart.data_ptr(),
-                              dWm.data_ptr(), st0)
+                              None, 1, Cin, Cout, ldz, nsl, wpart.data_ptr(), dWm.data_ptr(), st0)
                     if fold:
                         # the centre term of grouped_xyz = xyz[idx] - new_xyz and the compaction of the padded rows in one
                         # launch (was: the term in place, then a strided torch copy of dWm[:, :Cin])

@@ -23,9 +23,10 @@ import weakref
 import torch
 
 from . import capi
-from .fused import _call, _const_vec, _eval_consts, _ptr, _stream, count_batches, counters_begin, counters_end
+from .fused import _call, _const_vec, _eval_consts, _ptr, _stream, bn_bwd_coef, bn_bwd_fin_job, bn_fin_job, count_batches, \
+    counters_begin, counters_end
 
-_vp, _i, _l, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+_vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
 capi.register("o3d_pack_rows", [_vp, _i, _i, _i, _i, _vp, _vp])
 capi.register("o3d_pack_rows_ld", [_vp, _i, _i, _i, _i, _vp, _l, _vp])
 capi.register("o3d_prep_weights", [_vp, _i, _vp])
@@ -380,10 +381,11 @@ def chain_supported(sources, units):
 
 
 # ---- launch plumbing: a stack's forward / backward is a GENERATOR of launches --------------------------------------------
-# (name, flops, C entry, argument list, dims).  Driven alone, every launch is issued as it comes; two stacks driven side
-# by side (`run_chain_pair`: FC_layer_cla and vote_layer read the same seeds, models/head/rpn.py:44-54) advance in
-# lockstep and a pair of launches of the same kind goes out as ONE launch (csrc/mlp_direct.hip::direct_gemm_pair_kernel,
-# csrc/mlp.hip::bn_*finalize_pair_kernel) -- the serial chain of ~15 us sub-round launches is then half as long.
+# (name, flops, C entry, argument list -- for a BatchNorm finalize: the built job struct --, dims).  Driven alone, every
+# launch is issued as it comes; two stacks driven side by side (`run_chain_pair`: FC_layer_cla and vote_layer read the same
+# seeds, models/head/rpn.py:44-54) advance in lockstep and a pair of launches of the same kind goes out as ONE launch
+# (csrc/mlp_direct.hip::direct_gemm_pair_kernel, csrc/mlp.hip::bn_*finalize_pair_kernel) -- the serial chain of ~15 us
+# sub-round launches is then half as long.
 class _PwFwdArgs(ctypes.Structure):       # o3d_pw_fwd_args
     _fields_ = [("X", _vp), ("W", _vp), ("in_scale", _vp), ("in_shift", _vp), ("bias", _vp), ("resid", _vp), ("Cin", _i),
                 ("Cout", _i), ("P", _l), ("Y", _vp), ("part", _vp), ("stat_c", _vp)]
@@ -395,23 +397,12 @@ class _PwDgradArgs(ctypes.Structure):     # o3d_pw_dgrad_args
                 ("dNprev", _vp), ("part", _vp)]
 
 
-class _BnFinArgs(ctypes.Structure):       # o3d_bn_fin_args
-    _fields_ = [("part", _vp), ("nparts", _i), ("C", _i), ("count", _d), ("stat_c", _vp), ("gamma", _vp), ("beta", _vp),
-                ("running_mean", _vp), ("running_var", _vp), ("momentum", _f), ("eps", _f), ("mean", _vp), ("invstd", _vp),
-                ("scale", _vp), ("shift", _vp)]
-
-
-class _BnBwdFinArgs(ctypes.Structure):    # o3d_bn_bwd_fin_args
-    _fields_ = [("part", _vp), ("nparts", _i), ("C", _i), ("count", _d), ("gamma", _vp), ("mean", _vp), ("invstd", _vp),
-                ("dgamma", _vp), ("dbeta", _vp), ("A1", _vp), ("A2", _vp), ("A3", _vp)]
-
-
-for _n in ("o3d_pw_fwd_pair", "o3d_pw_dgrad_pair", "o3d_bn_finalize_pair", "o3d_bn_bwd_finalize_pair"):
+for _n in ("o3d_pw_fwd_pair", "o3d_pw_dgrad_pair"):
     capi.register(_n, [_vp, _vp, _vp])
-# single entry -> (pair entry, argument struct, trailing arguments of the single call that the struct does not carry)
-_PAIRABLE = {"o3d_pw_fwd": ("o3d_pw_fwd_pair", _PwFwdArgs, 1), "o3d_pw_dgrad": ("o3d_pw_dgrad_pair", _PwDgradArgs, 1),
-             "o3d_bn_finalize": ("o3d_bn_finalize_pair", _BnFinArgs, 2),
-             "o3d_bn_bwd_finalize": ("o3d_bn_bwd_finalize_pair", _BnBwdFinArgs, 2)}
+# single entry -> (pair entry, argument struct): every argument of the single call but the last, the stream
+_PAIRABLE = {"o3d_pw_fwd": ("o3d_pw_fwd_pair", _PwFwdArgs), "o3d_pw_dgrad": ("o3d_pw_dgrad_pair", _PwDgradArgs)}
+# entries that take an array of 1 or 2 job structs (fused._BnFinArgs / _BnBwdFinArgs): the generators yield the built job
+_JOB_ENTRIES = ("o3d_bn_finalize", "o3d_bn_bwd_finalize")
 
 
 def _drive(gens):
@@ -427,27 +418,33 @@ def _drive(gens):
         except StopIteration as e:
             pend[k], done[k], res[k] = None, True, e.value
 
-    def single(k):
-        name, flops, entry, args, dims = pend[k]
+    def issue(ks):       # the pending launch of generator ks[0]; a finalize: the jobs of all of `ks` in ONE launch
+        name, flops, entry, args, dims = pend[ks[0]]
+        if entry in _JOB_ENTRIES:
+            arr = (type(args) * len(ks))(*[pend[k][3] for k in ks])
+            args = [ctypes.addressof(arr), len(ks), _stream()]
         _call(name, flops, getattr(lib, entry), *args, dims=dims)
-        advance(k)
+        for k in ks:
+            advance(k)
     for k in range(n):
         advance(k)
     while not all(done):
         live = [k for k in range(n) if not done[k]]
-        if len(live) == 2 and pend[0][2] == pend[1][2] and pend[0][2] in _PAIRABLE and pend[0][3][-1] == pend[1][3][-1]:
-            pair_entry, struct, tail = _PAIRABLE[pend[0][2]]
-            sa, sb = struct(*pend[0][3][:-tail]), struct(*pend[1][3][:-tail])
+        same = len(live) == 2 and pend[0][2] == pend[1][2]
+        if same and pend[0][2] in _JOB_ENTRIES:
+            issue(live)
+        elif same and pend[0][2] in _PAIRABLE and pend[0][3][-1] == pend[1][3][-1]:
+            pair_entry, struct = _PAIRABLE[pend[0][2]]
+            sa, sb = struct(*pend[0][3][:-1]), struct(*pend[1][3][:-1])
             _call(pend[0][0], pend[0][1] + pend[1][1], getattr(lib, pair_entry), ctypes.addressof(sa), ctypes.addressof(sb),
                   pend[0][3][-1])
             advance(0)
             advance(1)
         elif len(live) == 2:
             # not aligned: issue the launch that has no partner (a pack, a row sum ...) or, failing that, the first one
-            k = next((k for k in live if pend[k][2] not in _PAIRABLE), live[0])
-            single(k)
+            issue([next((k for k in live if pend[k][2] not in _PAIRABLE and pend[k][2] not in _JOB_ENTRIES), live[0])])
         else:
-            single(live[0])
+            issue(live)
     return res
 
 
@@ -492,12 +489,8 @@ def _chain_forward(cfg, tensors, need_bwd):
                 yield ("pw_conv_fwd", 2.0 * Kp * Mp * P, "o3d_pw_fwd", [src.data_ptr(), Wp.data_ptr(), sc, sh, None, None, Kp, Mp,
                                                                        P, Y.data_ptr(), part.data_ptr(),
                                                                        bn.running_mean.data_ptr(), st], (Kp, Mp))
-                fold = torch.empty((64, Mp), device=dev, dtype=f32)
-                yield ("bn_finalize", 0.0, "o3d_bn_finalize", [part.data_ptr(), nparts, Mp, float(P), bn.running_mean.data_ptr(),
-                                                               gamma.data_ptr(), beta.data_ptr(), bn.running_mean.data_ptr(),
-                                                               bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
-                                                               vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
-                                                               vec[3].data_ptr(), fold.data_ptr(), st], None)
+                yield ("bn_finalize", 0.0, "o3d_bn_finalize",
+                       bn_fin_job(part, [nparts], [float(P)], bn, gamma, beta, vec, bn.running_mean), None)
             else:
                 yield ("pw_conv_fwd", 2.0 * Kp * Mp * P, "o3d_pw_fwd", [src.data_ptr(), Wp.data_ptr(), sc, sh, None, None, Kp, Mp,
                                                                        P, Y.data_ptr(), None, None, st], (Kp, Mp))
@@ -603,17 +596,10 @@ def _chain_backward(state, dOut, needs):
     for l in range(L - 2, -1, -1):
         Cp = Ys[l].shape[0]
         v = vecs[l]
-        coef = torch.empty((5, Cp), device=dev, dtype=f32)          # dgamma dbeta A1 A2 A3
-        fold = torch.empty((64, Cp), device=dev, dtype=f32)
-        yield ("bn_bwd_finalize", 0.0, "o3d_bn_bwd_finalize", [part.data_ptr(), nparts, Cp, float(P), gammas[l].data_ptr(),
-                                                               v[0].data_ptr(), v[1].data_ptr(), coef[0].data_ptr(),
-                                                               coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(),
-                                                               coef[4].data_ptr(), fold.data_ptr(), st], None)
-        if not cfg.training:
-            coef[3].zero_()
-            coef[4].zero_()
+        job, coef = bn_bwd_fin_job(part, [nparts], [float(P)], gammas[l], v[0], v[1])
+        yield ("bn_bwd_finalize", 0.0, "o3d_bn_bwd_finalize", job, None)
+        coef, A = bn_bwd_coef(coef, cfg.training)
         grads[4 * l + 2], grads[4 * l + 3] = coef[0], coef[1]
-        A = (coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr())
         grads[4 * l] = wgrad(l, dN, Ys[l], A, Cp, coef)
         if l > 0:
             Cq = Ys[l - 1].shape[0]

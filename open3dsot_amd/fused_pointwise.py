@@ -14,7 +14,8 @@ import ctypes
 import torch
 
 from . import capi
-from .fused import _call, _check_versions, _const_vec, _eval_consts, _ptr, _stream, _versions, count_batches, POOL_BWD_SPLIT, TILE
+from .fused import _call, _check_versions, _const_vec, _eval_consts, _ptr, _stream, _versions, bn_bwd_finalize, bn_finalize, \
+    count_batches, POOL_BWD_SPLIT, TILE
 from .fused import bias_fix as _fused_bias_fix
 
 _vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
@@ -98,11 +99,7 @@ class FusedPointwiseChain(torch.autograd.Function):
             vec = torch.empty((4, Cout), device=dev, dtype=f32)
             b = biases[l].detach() if biases[l] is not None else None
             if cfg.training:
-                fold = torch.empty((64, Cout), device=dev, dtype=f32)
-                _call("bn_finalize", 0.0, lib.o3d_bn_finalize, part.data_ptr(), nrows, Cout, float(P), stat_c.data_ptr(),
-                      gammas[l].data_ptr(), betas[l].data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                      float(bn.momentum), float(bn.eps), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
-                      vec[3].data_ptr(), fold.data_ptr(), st)
+                bn_finalize(lib, st, part, [nrows], [float(P)], bn, gammas[l], betas[l], vec, stat_c)
                 if b is not None:       # statistics were taken without the bias: mean(Y + b) = mean(Y) + b
                     bias_fix.setdefault(float(bn.momentum), ([], []))
                     bias_fix[float(bn.momentum)][0].append(bn.running_mean)
@@ -203,21 +200,13 @@ class FusedPointwiseChain(torch.autograd.Function):
                 o += w
         for l in range(L - 1, -1, -1):
             Cout, Cin = Ws[l].shape
-            coef = torch.empty((5, Cout), device=dev, dtype=f32)
-            fold = torch.empty((64, Cout), device=dev, dtype=f32)
-            _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize, part.data_ptr(), nparts, Cout, float(P),
-                  gammas[l].data_ptr(), means[l].data_ptr(), invstds[l].data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                  coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr(), fold.data_ptr(), st)
-            if not cfg.training:
-                coef[3].zero_()
-                coef[4].zero_()
+            coef, A = bn_bwd_finalize(lib, st, cfg.training, part, [nparts], [float(P)], gammas[l], means[l], invstds[l])
             grads[4 * l + 2], grads[4 * l + 3] = coef[0], coef[1]
             if ctx.has_bias[l]:      # dL/db = sum dY: zero behind a training-mode BatchNorm, A1 * sum dN in eval mode
                 if cfg.training:
                     grads[4 * l + 1] = zero_bias[l] if zero_bias is not None else torch.zeros_like(coef[0])
                 else:
                     grads[4 * l + 1] = coef[2] * coef[1]
-            A = (coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr())
             dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
             flops = 2.0 * Cin * Cout * P
             if l == 0 and ctx.has_cbias and ctx.needs_input_grad[1]:
@@ -252,8 +241,8 @@ class FusedPointwiseChain(torch.autograd.Function):
                 xs = (X0.data_ptr(), None, None) if l == 0 else \
                      (Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr())
                 _call("pw_conv_wgrad", flops, lib.o3d_mlp_conv_wgrad, dN.data_ptr(), None, None, None, 4, Ys[l].data_ptr(),
-                      A[0], A[1], A[2], xs[0], xs[1], xs[2], None, None, None, None, 0, 0, 0, 1.0, 1, Cin, Cout, P, nsl,
-                      wpart.data_ptr(), dW.data_ptr(), st, dims=(Cin, Cout))
+                      A[0], A[1], A[2], xs[0], xs[1], xs[2], 1, Cin, Cout, P, nsl, wpart.data_ptr(), dW.data_ptr(), st,
+                      dims=(Cin, Cout))
             grads[4 * l] = dW.unsqueeze(-1)
             if l >= 1:
                 Wt = ctx.Wts[l] if ctx.Wts is not None else Ws[l].t().contiguous()

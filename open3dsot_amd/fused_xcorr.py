@@ -15,7 +15,7 @@ import ctypes
 import torch
 
 from . import capi
-from .fused import _call, _const_vec, _eval_consts, _layers, _ptr, _stream, count_batches
+from .fused import _call, _const_vec, _eval_consts, _layers, _ptr, _stream, bn_bwd_finalize, bn_finalize, count_batches
 from .fused_heads import _up, pack_rows, prep_for
 
 _vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
@@ -101,11 +101,7 @@ class FusedP2BXCorr(torch.autograd.Function):
                     Wts.append(prep.get(params[3 * l], Cin, Cout, transpose=True))
             vec = torch.empty((4, Cout), device=dev, dtype=f32)
             if cfg.training:
-                fold = torch.empty((64, Cout), device=dev, dtype=f32)
-                _call("bn_finalize", 0.0, lib.o3d_bn_finalize, part.data_ptr(), nparts, Cout, float(P), statc.data_ptr(),
-                      gammas[l].data_ptr(), betas[l].data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                      float(bn.momentum), float(bn.eps), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
-                      vec[3].data_ptr(), fold.data_ptr(), st)
+                bn_finalize(lib, st, part, [nparts], [float(P)], bn, gammas[l], betas[l], vec, statc)
             else:
                 _eval_consts(lib, bn, gammas[l], betas[l], vec, 1, st)
             Ys.append(Y)
@@ -158,16 +154,8 @@ class FusedP2BXCorr(torch.autograd.Function):
         dsim = dxyz = dfeat = None
         for l in range(L - 1, -1, -1):
             Cout, Cin = Ws[l].shape
-            coef = torch.empty((5, Cout), device=dev, dtype=f32)
-            fold = torch.empty((64, Cout), device=dev, dtype=f32)
-            _call("bn_bwd_finalize", 0.0, lib.o3d_bn_bwd_finalize, part.data_ptr(), nparts, Cout, float(P), gammas[l].data_ptr(),
-                  vecs[l][0].data_ptr(), vecs[l][1].data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
-                  coef[3].data_ptr(), coef[4].data_ptr(), fold.data_ptr(), st)
-            if not cfg.training:
-                coef[3].zero_()
-                coef[4].zero_()
+            coef, A = bn_bwd_finalize(lib, st, cfg.training, part, [nparts], [float(P)], gammas[l], vecs[l][0], vecs[l][1])
             grads[3 * l + 1], grads[3 * l + 2] = coef[0], coef[1]
-            A = (coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr())
             if l == 0:
                 S = torch.empty((Cout, Pm), device=dev, dtype=f32)
                 ng = lib.o3d_xcorr_reduce_groups(Cout)

@@ -108,7 +108,46 @@ def test_entry_points_reject_bad_arguments_before_touching_the_device():
     assert lib.o3d_compact_build(p, 1, 8, 3, 8, 0, 0, 0, 8, p, p, p, p, p, p, None) == EINVAL       # nsample not a power of two
     assert lib.o3d_pool_fwd_c(None, 256, None, None, None, None, 1, 8, 8, 0, None, None, None, None) == EINVAL
     assert lib.o3d_center_term(None, None, 8, 8, 3, None, None) == EINVAL
-    assert lib.o3d_bn_finalize_c2(None, 1, 1, 8, 1.0, 1.0, *([None] * 5), 0.1, 1e-5, *([None] * 5), 128, None) == EINVAL
+    for entry, mirror in ((lib.o3d_bn_finalize, fused._BnFinArgs), (lib.o3d_bn_bwd_finalize, fused._BnBwdFinArgs)):
+        jobs = (mirror * 2)()                               # zeroed jobs: `part` is NULL
+        assert entry(None, 1, None) == EINVAL
+        assert entry(ctypes.addressof(jobs), 0, None) == EINVAL and entry(ctypes.addressof(jobs), 3, None) == EINVAL
+        assert entry(ctypes.addressof(jobs), 1, None) == EINVAL
+
+
+def _valid_fin_jobs():
+    """a forward and a backward finalize job that pass validation (host buffers for pointers: never dereferenced, because the
+    tests below break one field each and the entry returns before any launch)"""
+    from open3dsot_amd import fused
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p).value
+    fwd = fused._BnFinArgs(p, 1, 8, 1.0, p, p, p, p, p, 0.1, 1e-5, p, p, p, p, p, 128, 0, 0.0)
+    bwd = fused._BnBwdFinArgs(p, 1, 8, 1.0, p, p, p, p, p, p, p, p, p, 128, 0, 0.0)
+    return buf, fwd, bwd
+
+
+def test_finalize_job_structs_have_the_library_layout():
+    """the ctypes mirrors of o3d_bn_fin_args / o3d_bn_bwd_fin_args have the sizes that csrc/mlp.hip static_asserts (a mismatched
+    mirror would hand the kernels wild pointers)"""
+    from open3dsot_amd import fused
+    assert ctypes.sizeof(fused._BnFinArgs) == 128 and ctypes.sizeof(fused._BnBwdFinArgs) == 112
+    src = open(os.path.join(ROOT, "open3dsot_amd", "csrc", "mlp.hip")).read()
+    assert "static_assert(sizeof(o3d_bn_fin_args) == 128 && sizeof(o3d_bn_bwd_fin_args) == 112" in src
+
+
+def test_finalize_entries_read_the_last_fields_where_python_puts_them():
+    """a job that is valid except for tile = 0 beside a non-NULL meta, or except for nparts1 = -1, is refused with O3D_EINVAL
+    before any launch: the fields behind the pointers sit where the mirror writes them"""
+    from open3dsot_amd import capi, fused  # noqa: F401  (registers argtypes)
+    lib = capi.load()
+    for k, entry in ((1, lib.o3d_bn_finalize), (2, lib.o3d_bn_bwd_finalize)):
+        for field, bad in (("tile", 0), ("nparts1", -1), ("nparts", 0), ("C", 0)):
+            job = _valid_fin_jobs()[k]
+            setattr(job, field, bad)
+            assert entry(ctypes.addressof(job), 1, None) == -1, (k, field)
+        job = _valid_fin_jobs()[k]
+        setattr(job, "shift" if k == 1 else "A3", None)                # the last output pointer
+        assert entry(ctypes.addressof(job), 1, None) == -1
 
 
 def test_fused_backward_entry_validates_shapes_without_a_device():

@@ -7,6 +7,7 @@ values differ by 1e-6 can route a gradient differently at a near-tie; an fp32-vs
 comparison is therefore noisy (measured on the GPU box: torch's own CPU fp32 backward is 2e-2
 away from its fp64 run on some RPN weights, tools/diag_grad2.py).  Criterion: relative L2 error
 <= 5e-4 and max error <= 1e-2 of the tensor scale, against fp64."""
+import ctypes
 import os
 
 import numpy as np
@@ -108,8 +109,9 @@ def test_conv_fwd_and_stats(lib, B, Cin, Cout, P, xform):
     assert rel(q, ((ref - c.double()[None, :, None]) ** 2).sum((0, 2))) < 1e-5
 
 
-@pytest.mark.parametrize("B,C,P", [(4, 96, 256), (40, 96, 512)])     # 8 parts / 160 parts (folded first)
+@pytest.mark.parametrize("B,C,P", [(4, 96, 256), (40, 96, 512)])     # 8 parts / 160 parts (more than FIN_SL lanes of rows)
 def test_bn_finalize_matches_torch(lib, B, C, P):
+    from open3dsot_amd import fused
     torch.manual_seed(0)
     Y = torch.randn(B, C, P, device="cuda") * 2 + 3
     bn = torch.nn.BatchNorm2d(C).cuda().train()
@@ -122,15 +124,149 @@ def test_bn_finalize_matches_torch(lib, B, C, P):
     part = torch.stack([Yt.sum(3), ((Yt - rm[None, :, None, None]) ** 2).sum(3)], 0)  # (2,B,C,T)
     part = part.permute(1, 3, 0, 2).reshape(ntiles, 2, C).contiguous()
     vec = torch.empty(4, C, device="cuda")
-    fold = torch.empty(64, C, device="cuda")
-    rc = lib.o3d_bn_finalize(part.data_ptr(), ntiles, C, float(B * P), rm.data_ptr(), bn.weight.data_ptr(),
-                             bn.bias.data_ptr(), rm.data_ptr(), rv.data_ptr(), 0.1, 1e-5, vec[0].data_ptr(),
-                             vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), fold.data_ptr(), st())
+    job = fused._BnFinArgs(part.data_ptr(), ntiles, C, float(B * P), rm.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(),
+                           rm.data_ptr(), rv.data_ptr(), 0.1, 1e-5, vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(),
+                           vec[3].data_ptr(), None, 0, 0, 0.0)
+    rc = lib.o3d_bn_finalize(ctypes.addressof(job), 1, st())
     assert rc == 0
     ref = bn(Y.view(B, C, P, 1))
     got = Y * vec[2][None, :, None] + vec[3][None, :, None]
     assert rel(got, ref.squeeze(-1)) < 1e-5
     assert rel(rm, bn.running_mean) < 1e-5 and rel(rv, bn.running_var) < 1e-5
+
+
+# ---- the finalize entry points on partial lists made directly (no GEMM): every form of a job against the plain one-segment,
+# one-job call.  C = 70 leaves a workgroup with 2 live channels of FIN_CH = 4; the row counts straddle FIN_SL = 64
+class _Fin:
+    """one BatchNorm layer's random partials and constants, [nseg] segments of rows[s] partial rows; `fwd` / `bwd` build the
+    job over fresh outputs (and fresh copies of the running statistics) -> (job, outputs)"""
+
+    def __init__(self, C, rows, seed):
+        g = torch.Generator(device="cuda").manual_seed(seed)
+        self.C, self.rows, nseg = C, list(rows), len(rows)
+        self.part = torch.empty(sum(rows), 2, C, device="cuda")
+        self.part[:, 0] = torch.randn(sum(rows), C, device="cuda", generator=g) * 16
+        self.part[:, 1] = (torch.rand(sum(rows), C, device="cuda", generator=g) + 0.5) * 128
+        self.counts = [128.0 * r for r in rows]
+        self.statc = torch.randn(nseg, C, device="cuda", generator=g) * 0.05
+        self.gamma = torch.rand(C, device="cuda", generator=g) + 0.5
+        self.beta = torch.randn(C, device="cuda", generator=g)
+        self.rm = torch.randn(C, device="cuda", generator=g)
+        self.rv = torch.rand(C, device="cuda", generator=g) + 0.5
+        self.mean = torch.randn(nseg, C, device="cuda", generator=g)
+        self.invstd = torch.rand(nseg, C, device="cuda", generator=g) + 0.5
+
+    def segment(self, s):
+        """segment s as a one-segment layer of its own (views of the same partials and constants)"""
+        import copy
+        one = copy.copy(self)
+        r0 = sum(self.rows[:s])
+        one.rows, one.counts, one.part = [self.rows[s]], [self.counts[s]], self.part[r0:r0 + self.rows[s]]
+        one.statc, one.mean, one.invstd = self.statc[s:s + 1], self.mean[s:s + 1], self.invstd[s:s + 1]
+        return one
+
+    def fwd(self, rm=None, rv=None, meta=None, tile=0):
+        from types import SimpleNamespace
+        from open3dsot_amd import fused
+        vec = torch.full((4, len(self.rows), self.C), float("nan"), device="cuda")
+        bn = SimpleNamespace(running_mean=self.rm.clone() if rm is None else rm, running_var=self.rv.clone() if rv is None else rv,
+                             momentum=0.1, eps=1e-5)
+        job = fused.bn_fin_job(self.part, self.rows, self.counts, bn, self.gamma, self.beta, vec, self.statc, meta, tile)
+        return job, (vec, bn.running_mean, bn.running_var)
+
+    def bwd(self, meta=None, tile=0):
+        from open3dsot_amd import fused
+        job, coef = fused.bn_bwd_fin_job(self.part, self.rows, self.counts, self.gamma, self.mean, self.invstd, meta, tile)
+        coef.fill_(float("nan"))
+        return job, (coef,)
+
+
+def _launch(lib, bwd, *jobs):
+    arr = (type(jobs[0]) * len(jobs))(*jobs)
+    rc = (lib.o3d_bn_bwd_finalize if bwd else lib.o3d_bn_finalize)(ctypes.addressof(arr), len(jobs), st())
+    assert rc == 0
+    torch.cuda.synchronize()
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _no_nan(outs):
+    return not any(bool(torch.isnan(t).any()) for t in outs)
+
+
+@pytest.mark.parametrize("bwd", [False, True])
+@pytest.mark.parametrize("a,b", [((70, 1), (96, 200)), ((96, 63), (70, 64)), ((70, 65), (96, 63)), ((96, 200), (70, 65))])
+def test_bn_finalize_two_jobs_equal_each_alone(lib, a, b, bwd):
+    """two jobs of different C and list length in one call (the pair kernel) = each job in a call of its own, bit for bit on
+    every output, the running statistics included"""
+    layers = [_Fin(a[0], [a[1]], 1), _Fin(b[0], [b[1]], 2)]
+    build = (lambda f: f.bwd()) if bwd else (lambda f: f.fwd())
+    alone = []
+    for f in layers:
+        job, outs = build(f)
+        _launch(lib, bwd, job)
+        alone.append(outs)
+    (ja, oa), (jb, ob) = build(layers[0]), build(layers[1])
+    _launch(lib, bwd, ja, jb)
+    for got, exp in zip((oa, ob), alone):
+        assert _no_nan(got)
+        assert all(_same_bits(x, y) for x, y in zip(got, exp))
+
+
+@pytest.mark.parametrize("C", [70, 96])
+@pytest.mark.parametrize("r0,r1", [(1, 200), (63, 65), (64, 64), (200, 63)])
+def test_bn_finalize_two_segments_equal_two_jobs(lib, C, r0, r1):
+    """a two-segment job (meta = NULL) = the one-segment job on segment 0, then on segment 1 with the running statistics carried
+    over: per-segment outputs and running statistics bit for bit; dgamma / dbeta are sums over the segments rounded ONCE --
+    against the fp64 sums of the same partials formed in torch they may differ by fp64 summation order only, orders of
+    magnitude below half an fp32 ulp, so the rounding differs by at most one step"""
+    f = _Fin(C, [r0, r1], 3)
+    s0, s1 = f.segment(0), f.segment(1)
+    job, (vec, rm, rv) = f.fwd()
+    _launch(lib, False, job)
+    j0, (v0, rm_, rv_) = s0.fwd()
+    _launch(lib, False, j0)
+    j1, (v1, rm_, rv_) = s1.fwd(rm_, rv_)
+    _launch(lib, False, j1)
+    assert _no_nan((vec, rm, rv))
+    assert _same_bits(vec[:, 0], v0[:, 0]) and _same_bits(vec[:, 1], v1[:, 0])
+    assert _same_bits(rm, rm_) and _same_bits(rv, rv_)
+    job, (coef,) = f.bwd()
+    _launch(lib, True, job)
+    j0, (c0,) = s0.bwd()
+    j1, (c1,) = s1.bwd()
+    _launch(lib, True, j0)
+    _launch(lib, True, j1)
+    assert _no_nan((coef[:2, 0], coef[2:]))
+    assert _same_bits(coef[2:, 0], c0[2:, 0]) and _same_bits(coef[2:, 1], c1[2:, 0])
+    p64 = f.part.double()
+    sums = [p64[:r0].sum(0), p64[r0:].sum(0)]                     # per segment (2, C): sum dN, sum dN * (Y - mean)
+    dbeta = (sums[0][0] + sums[1][0]).float()
+    dgamma = (sums[0][1] * f.invstd[0].double() + sums[1][1] * f.invstd[1].double()).float()
+    inf = torch.full_like(dbeta, float("inf"))
+    for got, ref in ((coef[0, 0], dgamma), (coef[1, 0], dbeta)):
+        assert bool(((got >= torch.nextafter(ref, -inf)) & (got <= torch.nextafter(ref, inf))).all())
+
+
+@pytest.mark.parametrize("bwd", [False, True])
+@pytest.mark.parametrize("C", [70, 96])
+@pytest.mark.parametrize("r", [1, 65, 200])
+def test_bn_finalize_meta_limits_the_rows_read(lib, C, r, bwd):
+    """capacity 200 rows of 512 columns (no tail rows at that tile), meta[0] such that ceil(meta[0] / 512) = r, the rows beyond
+    r NaN = the plain job over the first r rows, bit for bit; a NaN in any output means a dead row was read"""
+    f = _Fin(C, [200], 4)
+    f.part[r:] = float("nan")
+    meta = torch.tensor([(r - 1) * 512 + 1, 0, 0, 0], dtype=torch.int32, device="cuda")
+    job, got = f.bwd(meta, 512) if bwd else f.fwd(meta=meta, tile=512)
+    _launch(lib, bwd, job)
+    head = f.segment(0)
+    head.rows = [r]
+    job, exp = head.bwd() if bwd else head.fwd()
+    _launch(lib, bwd, job)
+    assert _no_nan(got)
+    assert all(_same_bits(x, y) for x, y in zip(got, exp))
 
 
 def make_case(kind, B=3, train=True, seed=0, full=False):

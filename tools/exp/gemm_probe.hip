@@ -24,9 +24,8 @@ extern "C" int o3d_mlp_conv_dgrad_wt(const float* dN, const float* dOut, const f
                                      float* part, void* stream);
 extern "C" int o3d_mlp_conv_wgrad(const float* dN, const float* dOut, const float* out, const int32_t* arg, int ns,
                                   const float* Y, const float* A1, const float* A2, const float* A3, const float* X,
-                                  const float* in_scale, const float* in_shift, const float* xyz, const float* new_xyz,
-                                  const float* feats, const int32_t* idx, int N, int C, int nxyz, float inv_radius,
-                                  int B, int Cin, int Cout, int P, int nslices, float* part, float* dW, void* stream);
+                                  const float* in_scale, const float* in_shift, int B, int Cin, int Cout, int P,
+                                  int nslices, float* part, float* dW, void* stream);
 
 extern "C" long o3d_mlp_conv_wgrad2_scratch(int B, int Cin, int Cout, int P);
 extern "C" int o3d_mlp_conv_wgrad2(const float* dN, const float* pk, int ns, const float* Y, const float* A1,
@@ -152,7 +151,7 @@ int main(int argc, char** argv) {
         float t_f = time_ms([&] { o3d_mlp_conv_fwd(X, W, sc, sh, s.B, s.Cin, s.Cout, s.P, Y, part, c, 0); }, reps);
         float t_f0 = time_ms([&] { o3d_mlp_conv_fwd(X, W, sc, sh, s.B, s.Cin, s.Cout, s.P, Y, nullptr, nullptr, 0); }, reps);
         float t_d = time_ms([&] { o3d_mlp_conv_dgrad_wt(dN, 0, 0, 0, 32, Y, A1, A2, A3, W, W, 0, s.B, s.Cin, s.Cout, s.P, X, sc, sh, mu, dNp, part, 0); }, reps);
-        float t_w = time_ms([&] { o3d_mlp_conv_wgrad(dN, 0, 0, 0, 32, Y, A1, A2, A3, X, sc, sh, 0, 0, 0, 0, 0, 0, 0, 1.f, s.B, s.Cin, s.Cout, s.P, nsl, wpart, dW, 0); }, reps);
+        float t_w = time_ms([&] { o3d_mlp_conv_wgrad(dN, 0, 0, 0, 32, Y, A1, A2, A3, X, sc, sh, s.B, s.Cin, s.Cout, s.P, nsl, wpart, dW, 0); }, reps);
         float* w2s; CK(hipMalloc(&w2s, sizeof(float) * o3d_mlp_conv_wgrad2_scratch(s.B, s.Cin, s.Cout, s.P)));
         float* dW2; CK(hipMalloc(&dW2, sizeof(float) * s.Cin * s.Cout));
         float t_w2 = time_ms([&] { o3d_mlp_conv_wgrad2(dN, 0, 32, Y, A1, A2, A3, X, sc, sh, s.B, s.Cin, s.Cout, s.P, w2s, dW2, 0); }, reps);
