@@ -730,6 +730,16 @@ int o3d_track_offset_box_multi(const float* ref, const float* offset, float* yaw
                                const int32_t* active, int K, int degrees, int use_z, int limit_box, int seed, float* out,
                                float* results, int T, int32_t* frame, void* stream);
 
+/* o3d_track_motion_input for K targets of one scene in one launch (tracking.MultiMotionTracker), grid (ceil(2N / 256), K).
+ * `jobs` is a DEVICE table of K (1..O3D_CROP_MULTI_MAX_TARGETS) records holding what changes per frame: the target's two
+ * crops (prev (n_prev,3), cur (n_this,3)), its 2N indices (rows < N gather from prev, rows >= N from cur) and the zero-fill
+ * flags of the two halves.  wlh (K,3): the canonical boxes; points (K,2N,5) and candidate_bc (K,2N,9) | NULL: row k is what
+ * o3d_track_motion_input writes for job k with wlh + 3 k, bit for bit (one definition of the row arithmetic serves both).
+ * N is 1..2^20.  The host cannot read the table: a half whose crop or whose idx is NULL is zero-filled. */
+typedef struct { const float* prev; int n_prev; const float* cur; int n_this; const int32_t* idx; int zero_prev, zero_this; } o3d_motion_job;
+int o3d_track_motion_input_multi(const o3d_motion_job* jobs, int K, int N, const float* wlh, int first_frame, float* points,
+                                 float* candidate_bc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,9 +6,10 @@
 //   o3d_track_offset_box  getOffsetBB (:43-85) with the box sequence kept on the device
 //   o3d_track_motion_input  the network input of the motion tracker: MotionBaseModel.build_input_dict behind its two crops
 //                         (models/base_model.py:263-302)
-//   o3d_track_crop_multi / o3d_track_resample_multi / o3d_track_offset_box_multi
-//                         the same three steps for K targets of one scene per launch (tracking.MultiTargetTracker); every
-//                         target's result is bit-identical to the single-target entry point's
+//   o3d_track_crop_multi / o3d_track_resample_multi / o3d_track_offset_box_multi / o3d_track_motion_input_multi
+//                         the same steps for K targets of one scene per launch (tracking.MultiTargetTracker,
+//                         tracking.MultiMotionTracker); every target's result is bit-identical to the single-target entry
+//                         point's
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -28,7 +29,7 @@
 //     world test                                  |dx| < e_0  and  |dy| < e_1  and  |dz| < e_2
 // A point is kept iff it passes the box-frame test (and, in mode MODEL, the world test); the output row is q.
 //
-// ---- the motion input's fp32 operation order (o3d_track_motion_input; tests/motion_oracle.py restates it) ---------------------
+// ---- the motion input's fp32 operation order (motion_row, of o3d_track_motion_input[_multi]; tests/motion_oracle.py restates it) ---------------------
 // Row i of `points` (2N,5) is (x, y, z, time stamp, prior targetness); (x, y, z) is the gathered row (zeros when the half is
 // zero-filled or the index lies outside the source), copied, not computed.  Previous half (i < N), box = centre 0, identity
 // rotation, the given wlh (x pairs with l, y with w):
@@ -182,14 +183,9 @@ struct MotionInputArgs {
     float* points; float* bc;
 };
 
-__global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * a.N) return;
-    const int half = i >= a.N ? 1 : 0;
-    float x, y, z;
-    gather_row(a.src[half], a.n_src[half], a.idx, i, a.zero[half], x, y, z);
-    float* o = a.points + 5 * (long)i;
-    float* bc = a.bc ? a.bc + 9 * (long)i : nullptr;
+// Row i of the motion input behind its gather, in the operation order of the header comment: (x, y, z) -> o (5) and bc (9) |
+// NULL.  THE row arithmetic of both o3d_track_motion_input and o3d_track_motion_input_multi; wlh (3): the target's canonical box
+__device__ __forceinline__ void motion_row(float x, float y, float z, int half, const float* wlh, int first_frame, float* o, float* bc) {
     o[0] = x; o[1] = y; o[2] = z;
     if (half) {
         o[3] = 0.1f; o[4] = 0.5f;
@@ -199,11 +195,11 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
         }
         return;
     }
-    const float w = a.wlh[0], l = a.wlh[1], h = a.wlh[2];
+    const float w = wlh[0], l = wlh[1], h = wlh[2];
     const float hx = (l * 1.25f) * 0.5f, hy = (w * 1.25f) * 0.5f, hz = (h * 1.25f) * 0.5f;
     const bool inside = fabsf(x) <= hx && fabsf(y) <= hy && fabsf(z) <= hz;
     o[3] = 0.f;
-    o[4] = a.first_frame ? (inside ? 1.f : 0.f) : (inside ? 0.8f : 0.2f);
+    o[4] = first_frame ? (inside ? 1.f : 0.f) : (inside ? 0.8f : 0.2f);
     if (!bc) return;
     const float ca = l * 0.5f, cb = w * 0.5f, cc = h * 0.5f;
     bc[0] = sqrtf((x * x + y * y) + z * z);
@@ -215,6 +211,15 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
         const float dx = x - X, dy = y - Y, dz = z - Z;
         bc[1 + k] = sqrtf((dx * dx + dy * dy) + dz * dz);
     }
+}
+
+__global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * a.N) return;
+    const int half = i >= a.N ? 1 : 0;
+    float x, y, z;
+    gather_row(a.src[half], a.n_src[half], a.idx, i, a.zero[half], x, y, z);
+    motion_row(x, y, z, half, a.wlh, a.first_frame, a.points + 5 * (long)i, a.bc ? a.bc + 9 * (long)i : nullptr);
 }
 
 // counter-based draw from U[-1, 1): a 32-bit mix of (seed, frame, component) (the finaliser of MurmurHash3), its top 24 bits
@@ -433,6 +438,23 @@ __global__ __launch_bounds__(256) void offset_box_multi_kernel(OffsetMultiArgs a
     if (a.frame && threadIdx.x == 0) a.frame[0] = k + 1;
 }
 
+// motion_input_kernel for a DEVICE table of K jobs: blockIdx.y = the target, whose rows are rows [k * 2N, (k + 1) * 2N) of
+// points / bc and whose canonical box is wlh + 3 k
+static_assert(sizeof(o3d_motion_job) == 48, "o3d_motion_job: points_utils.MOTION_JOB mirrors this layout");
+__global__ __launch_bounds__(256) void motion_input_multi_kernel(const o3d_motion_job* __restrict__ jobs, int N, const float* __restrict__ wlh,
+                                                                 int first_frame, float* __restrict__ points, float* __restrict__ bc) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * N) return;
+    const int k = blockIdx.y;
+    const o3d_motion_job J = jobs[k];
+    const int half = i >= N ? 1 : 0;
+    const float* src = half ? J.cur : J.prev;
+    float x, y, z;
+    gather_row(src, half ? J.n_this : J.n_prev, J.idx, i, (half ? J.zero_this : J.zero_prev) || !src || !J.idx, x, y, z);      // the host cannot check a device table
+    const long row = (long)k * (2 * (long)N) + i;
+    motion_row(x, y, z, half, wlh + 3 * (long)k, first_frame, points + 5 * row, bc ? bc + 9 * row : nullptr);
+}
+
 }  // namespace
 
 extern "C" long o3d_track_crop_scratch(const o3d_crop_job* jobs, int n_jobs) {
@@ -582,5 +604,17 @@ extern "C" int o3d_track_offset_box_multi(const float* ref, const float* offset,
         return O3D_EINVAL;
     OffsetMultiArgs a{ref, offset, yaw_state, rebase, active, out, results, frame, K, T, degrees, use_z, limit_box, seed};
     hipLaunchKernelGGL(offset_box_multi_kernel, dim3(1), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+// o3d_track_motion_input for K targets in one launch (tracking.MultiMotionTracker): jobs is a DEVICE table of K records that
+// hold what changes per frame (the two crops, their counts, the 2N indices, the zero-fill flags); wlh (K,3), points (K,2N,5),
+// candidate_bc (K,2N,9) | NULL.  Row k is what o3d_track_motion_input writes for job k and wlh + 3 k, bit for bit.  The host
+// cannot read the table: a half without its crop or without idx is zero-filled.
+extern "C" int o3d_track_motion_input_multi(const o3d_motion_job* jobs, int K, int N, const float* wlh, int first_frame, float* points,
+                                            float* candidate_bc, void* stream) {
+    if (!jobs || !wlh || !points || K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || N < 1 || N > (1 << 20)) return O3D_EINVAL;
+    hipLaunchKernelGGL(motion_input_multi_kernel, dim3(o3d_cdiv(2 * N, 256), K), dim3(256), 0, o3d_stream(stream), jobs, N, wlh,
+                       first_frame != 0, points, candidate_bc);
     return o3d_launch_status();
 }

@@ -98,6 +98,7 @@ capi.register("o3d_track_crop_multi_scratch", [_vp, _i])
 capi.register("o3d_track_crop_multi", [_vp, _i, _vp, ctypes.c_long, _vp])
 capi.register("o3d_track_resample_multi", [_vp, _i, _vp])
 capi.register("o3d_track_offset_box_multi", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
+capi.register("o3d_track_motion_input_multi", [_vp, _i, _i, _vp, _i, _vp, _vp, _vp])
 
 
 def _need_gpu(t, what):
@@ -171,7 +172,7 @@ def resample_jobs(jobs):
 
 # ---- K targets per launch (o3d_track_*_multi): the job tables live on the DEVICE ------------------------------------------------
 # The tables are arrays of C structs holding device pointers.  They are described here as numpy record types with the C
-# layout, so that a caller (tracking.MultiTargetTracker) fills a whole table in a pinned buffer with a few array assignments
+# layout, so that a caller (tracking.MultiTargetTracker, tracking.MultiMotionTracker) fills a whole table in a pinned buffer with a few array assignments
 # and uploads it with one asynchronous copy.
 CROP_MULTI_MAX_TARGETS = 1024
 CROP_MULTI_CHUNK = 32                        # targets the crop stages in LDS at a time (O3D_CROP_MULTI_CHUNK)
@@ -179,7 +180,9 @@ CROP_TARGET = np.dtype([("box", "u8"), ("scale", "f4"), ("offset", "f4"), ("mode
                         ("count", "u8")], align=True)                                         # o3d_crop_target, 48 bytes
 RESAMPLE_JOB = np.dtype([("src", "u8"), ("n_src", "i4"), ("idx", "u8"), ("dst", "u8"), ("n", "i4"), ("zero", "i4")],
                         align=True)                                                           # o3d_resample_job, 40 bytes
-assert CROP_TARGET.itemsize == 48 and RESAMPLE_JOB.itemsize == ctypes.sizeof(_ResampleJob) == 40
+MOTION_JOB = np.dtype([("prev", "u8"), ("n_prev", "i4"), ("cur", "u8"), ("n_this", "i4"), ("idx", "u8"), ("zero_prev", "i4"),
+                       ("zero_this", "i4")], align=True)                                      # o3d_motion_job, 48 bytes
+assert CROP_TARGET.itemsize == 48 and RESAMPLE_JOB.itemsize == ctypes.sizeof(_ResampleJob) == 40 and MOTION_JOB.itemsize == 48
 
 
 class _CropGroup(ctypes.Structure):          # o3d_crop_group
@@ -379,6 +382,53 @@ def motion_input(prev_crop, this_crop, idx, wlh, first_frame, zero=(False, False
             idx.data_ptr() if idx is not None else None, n2 // 2, int(zp), int(zt), wlh.data_ptr(), int(bool(first_frame)),
             out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
             torch.cuda.current_stream(dev).cuda_stream), "o3d_track_motion_input")
+    return out_points, out_bc
+
+
+def _motion_fields(job):
+    """(prev_crop (n,3) | None, this_crop (n,3) | None, idx (2N,) int32 | None, (zero_prev, zero_this)) as motion_input takes
+    them -> the seven fields of its o3d_motion_job"""
+    prev, this, idx, zero = job
+    for src in (prev, this):
+        assert src is None or (src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == 3)
+    assert idx is None or (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous())
+    return (prev.data_ptr() if prev is not None else 0, prev.shape[0] if prev is not None else 0,
+            this.data_ptr() if this is not None else 0, this.shape[0] if this is not None else 0,
+            idx.data_ptr() if idx is not None else 0, int(bool(zero[0])), int(bool(zero[1])))
+
+
+def motion_job_table(jobs, device):
+    """jobs: K tuples (prev_crop | None, this_crop | None, idx (2N,) int32 | None, (zero_prev, zero_this)) -> the
+    o3d_motion_job table as a uint8 tensor on `device` (a blocking upload: for tests and tools; the tracker fills a pinned
+    buffer).  The caller keeps the tensors alive."""
+    tab = np.zeros((len(jobs),), MOTION_JOB)
+    tab[:] = [_motion_fields(job) for job in jobs]
+    return torch.from_numpy(tab.view(np.uint8)).to(device)
+
+
+def motion_input_multi(table, K, N, wlh, first_frame, out_points, out_bc):
+    """One o3d_track_motion_input_multi launch (no sync) over a uint8 GPU tensor that starts with K o3d_motion_job records
+    (motion_job_table, or a MOTION_JOB array uploaded by the caller): wlh (K,3) GPU, the canonical boxes -> out_points
+    (K,2N,5) and out_bc (K,2N,9), or None / False to skip the BoxCloud (box_aware=False).  Row k is motion_input's for job k."""
+    _need_gpu(wlh, "motion_input_multi")
+    _need_gpu(table, "motion_input_multi")
+    _need_gpu(out_points, "motion_input_multi")
+    K, N = int(K), int(N)
+    if out_bc is None or out_bc is False:
+        out_bc = None
+    else:
+        _need_gpu(out_bc, "motion_input_multi")
+    assert 1 <= K <= CROP_MULTI_MAX_TARGETS and N >= 1
+    assert table.dtype == torch.uint8 and table.is_contiguous() and K * MOTION_JOB.itemsize <= table.numel()
+    assert wlh.dtype == torch.float32 and wlh.is_contiguous() and wlh.numel() == 3 * K
+    assert out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.numel() == 10 * K * N
+    assert out_bc is None or (out_bc.dtype == torch.float32 and out_bc.is_contiguous() and out_bc.numel() == 18 * K * N)
+    dev = wlh.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_motion_input_multi(
+            table.data_ptr(), K, N, wlh.data_ptr(), int(bool(first_frame)), out_points.data_ptr(),
+            out_bc.data_ptr() if out_bc is not None else None, torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_motion_input_multi")
     return out_points, out_bc
 
 

@@ -247,6 +247,74 @@ class _DeviceTracker:
         return self.boxes[:self.t].cpu().numpy()
 
 
+class _KTargets:
+    """What the two K-target loops (MultiTargetTracker, MultiMotionTracker) share on top of _DeviceTracker's leading K axis:
+    the pack of K boxes, set_box / retire per target, and the target table of o3d_track_crop_multi: 2K o3d_crop_target
+    records in a pinned buffer, group 0 in [0:K], group 1 in [K:2K], target k of group g counting into counts[g K + k]."""
+
+    @staticmethod
+    def _n_targets(n_targets):
+        K = int(n_targets)
+        if not 1 <= K <= PU.CROP_MULTI_MAX_TARGETS:
+            raise ValueError("n_targets must be 1..%d" % PU.CROP_MULTI_MAX_TARGETS)
+        return K
+
+    def _k_state(self, K):
+        self.K = K
+        self.active = torch.ones((K,), dtype=torch.int32, device=self.dev)
+        self.retired = set()                                       # the host's copy of `active == 0`
+        self.crop_tab_host = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8).pin_memory()
+        self.crop_tab = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8, device=self.dev)
+        self.crop_rec = self.crop_tab_host.numpy().view(PU.CROP_TARGET)
+        self.draws = DrawCache()
+        self.crop_calls = 0
+
+    def _pack(self, boxes):
+        if torch.is_tensor(boxes) or isinstance(boxes, np.ndarray):
+            b = PU._dev32(boxes, self.dev).reshape(-1, 15)
+        else:
+            b = torch.stack([PU.pack_box(x, self.dev) for x in boxes])
+        if b.shape[0] != self.K:
+            raise ValueError("%d boxes for %d targets" % (b.shape[0], self.K))
+        return b.contiguous()
+
+    def init(self, points0, boxes0):
+        boxes = super().init(points0, boxes0)
+        self.active.fill_(1)
+        self.retired.clear()
+        self.crop_calls = 0
+        return boxes
+
+    def set_box(self, k, box):
+        """Overwrite target k's last result box (the single tracker's set_box for one target)."""
+        self._restart(PU.pack_box(box, self.dev), k)
+
+    def retire(self, k):
+        """Stop following target k: from the next update on its rows repeat its last box and its yaw state stays as it is.
+        Its slot is NOT compacted away -- it still runs through the crops, the resampling and the network (the batch keeps
+        its shape, so the captured graph stays valid); only its box update is switched off.  Where update() takes the caller's
+        reference boxes (MultiTargetTracker under such a reference_BB rule), its row of `ref_boxes` is ignored: its reference
+        stays its own last box."""
+        self.active[k] = 0
+        self.retired.add(int(k) % self.K)
+
+    def _crop_group(self, g, boxes, scale, offset, mode, out, capacity):
+        """Group g (0 or 1) of the target table: target k crops by boxes[k] ((K,15) on the device) into the `capacity` rows at
+        the device address out[k] ((K,) uint64).  -> the group's part of the device table, for PU.crop_multi"""
+        K, size = self.K, PU.CROP_TARGET.itemsize
+        kk = np.arange(K, dtype=np.uint64)
+        r = self.crop_rec[g * K:(g + 1) * K]
+        r["box"], r["scale"], r["offset"], r["mode"] = boxes.data_ptr() + 60 * kk, scale, offset, mode
+        r["out"], r["capacity"], r["count"] = out, capacity, self.counts.data_ptr() + 4 * (kk + np.uint64(g * K))
+        return self.crop_tab[g * K * size:(g + 1) * K * size]
+
+    def _crop_multi(self, groups):
+        """the table's upload and the one o3d_track_crop_multi call of groups = [(points, its part of the table)]"""
+        self.crop_tab.copy_(self.crop_tab_host, non_blocking=True)
+        self.scratch = PU.crop_multi(groups, self.scratch)
+        self.crop_calls += 1                   # one per frame, one more whenever a crop outgrew its buffer
+
+
 class _MatchingTracker(_DeviceTracker):
     """What SequenceTracker (one target, K = 1, no leading axis) and MultiTargetTracker (K targets) share: the config rules
     (reference_BB, shape_aggregation), the batch-K static inputs of the network, the canonical boxes of the BoxCloud, the
@@ -379,7 +447,7 @@ class SequenceTracker(_MatchingTracker):
         return c._done(pts, (ns, nm, nt))
 
 
-class MultiTargetTracker(_MatchingTracker):
+class MultiTargetTracker(_KTargets, _MatchingTracker):
     """Device-resident tracking loop for K targets in the same frames (the matching trackers: trackers.BAT, trackers.P2B).
     What SequenceTracker does per target happens here once per frame for all of them:
 
@@ -412,19 +480,12 @@ class MultiTargetTracker(_MatchingTracker):
         from .m2track import M2TRACK
         if isinstance(model, M2TRACK):
             raise TypeError("MultiTargetTracker serves the matching trackers (BAT, P2B); the motion tracker follows one "
-                            "target per MotionSequenceTracker")
-        K = int(n_targets)
-        if not 1 <= K <= PU.CROP_MULTI_MAX_TARGETS:
-            raise ValueError("n_targets must be 1..%d" % PU.CROP_MULTI_MAX_TARGETS)
+                            "target per MotionSequenceTracker, K targets per MultiMotionTracker")
+        K = self._n_targets(n_targets)
         super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity, K)
+        self._k_state(K)
         dev, MN = self.dev, int(self.template_size) + int(self.search_size)
-        self.active = torch.ones((K,), dtype=torch.int32, device=dev)
         self.rebase_all = torch.ones((K,), dtype=torch.int32, device=dev)
-        self.retired = set()                                       # the host's copy of `active == 0`
-        # the crop's target table, [0:K] search, [K:2K] model
-        self.crop_tab_host = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8).pin_memory()
-        self.crop_tab = torch.zeros((2 * K * PU.CROP_TARGET.itemsize,), dtype=torch.uint8, device=dev)
-        self.crop_rec = self.crop_tab_host.numpy().view(PU.CROP_TARGET)
         # the frame's one upload: 2K resample jobs [template 0..K-1, search 0..K-1], then the K * (M + N) indices
         jb = 2 * K * PU.RESAMPLE_JOB.itemsize
         self.stage_host = torch.zeros((jb + 4 * K * MN,), dtype=torch.uint8).pin_memory()
@@ -432,61 +493,24 @@ class MultiTargetTracker(_MatchingTracker):
         self.job_rec = self.stage_host.numpy()[:jb].view(PU.RESAMPLE_JOB)
         self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, MN)
         self.idx_ptr = self.stage.data_ptr() + jb
-        self.draws = DrawCache()
-        self.crop_calls = 0
-
-    # ---- state -------------------------------------------------------------------------------------------------------------
-    def _pack(self, boxes):
-        if torch.is_tensor(boxes) or isinstance(boxes, np.ndarray):
-            b = PU._dev32(boxes, self.dev).reshape(-1, 15)
-        else:
-            b = torch.stack([PU.pack_box(x, self.dev) for x in boxes])
-        if b.shape[0] != self.K:
-            raise ValueError("%d boxes for %d targets" % (b.shape[0], self.K))
-        return b.contiguous()
-
-    def init(self, points0, boxes0):
-        boxes = super().init(points0, boxes0)
-        self.active.fill_(1)
-        self.retired.clear()
-        self.crop_calls = 0
-        return boxes
-
-    def set_box(self, k, box):
-        """Overwrite target k's last result box (SequenceTracker.set_box for one target)."""
-        self._restart(PU.pack_box(box, self.dev), k)
-
-    def retire(self, k):
-        """Stop following target k: from the next update on its rows repeat its last box and its yaw state stays as it is.
-        Its slot is NOT compacted away -- it still runs through the crops, the resampling and the network (the batch keeps
-        its shape, so the captured graph stays valid); only its box update is switched off.  Under a reference_BB rule that takes the caller's boxes, its row of `ref_boxes` is
-        ignored: its reference stays its own last box."""
-        self.active[k] = 0
-        self.retired.add(int(k) % self.K)
 
     def _crops(self, pts, ref, slots):
         """the frame's one crop call + the count read-back -> (search counts (K), model counts (K) | None)"""
         c, K = self, self.K
-        k15 = 60 * np.arange(K, dtype=np.uint64)
+        kk = np.arange(K, dtype=np.uint64)
 
         def launch():
-            rec, kk = c.crop_rec, np.arange(K, dtype=np.uint64)
-            s = rec[:K]
-            s["box"], s["scale"], s["offset"], s["mode"] = ref.data_ptr() + k15, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW
-            s["out"], s["capacity"] = c.search_buf.data_ptr() + 12 * c.search_buf.shape[1] * kk, c.search_buf.shape[1]
-            s["count"] = c.counts.data_ptr() + 4 * kk
-            groups, caps = [(pts, c.crop_tab[:K * PU.CROP_TARGET.itemsize])], [(c.search_buf.shape[1], c._grow_search)] * K
+            cap = c.search_buf.shape[1]
+            groups = [(pts, c._crop_group(0, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW,
+                                          c.search_buf.data_ptr() + 12 * cap * kk, cap))]
+            caps = [(cap, c._grow_search)] * K
             if slots is not None:
                 c._ensure_bank(int(slots.max()) + c.model_capacity)
-                m = rec[K:]
-                m["box"], m["scale"], m["offset"], m["mode"] = c.cur.data_ptr() + k15, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL
-                m["out"] = c.bank.data_ptr() + 12 * (c.bank.shape[1] * kk + slots.astype(np.uint64))
-                m["capacity"], m["count"] = c.model_capacity, c.counts.data_ptr() + 4 * (kk + np.uint64(K))
-                groups.append((c.prev_points, c.crop_tab[K * PU.CROP_TARGET.itemsize:]))
+                out = c.bank.data_ptr() + 12 * (c.bank.shape[1] * kk + slots.astype(np.uint64))
+                groups.append((c.prev_points, c._crop_group(1, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, out,
+                                                            c.model_capacity)))
                 caps += [(c.model_capacity, c._grow_model)] * K
-            c.crop_tab.copy_(c.crop_tab_host, non_blocking=True)
-            c.scratch = PU.crop_multi(groups, c.scratch)
-            c.crop_calls += 1                  # one per frame, one more whenever a crop outgrew its buffer
+            c._crop_multi(groups)
             return caps
         ns = c._counts_loop(launch)
         return np.array(ns[:K], np.int64), (np.array(ns[K:], np.int64) if slots is not None else None)
@@ -596,10 +620,117 @@ class MotionSequenceTracker(_DeviceTracker):
         return c._done(pts, (n_prev, n_this))
 
 
+class MultiMotionTracker(_KTargets, _DeviceTracker):
+    """Device-resident tracking loop of the motion tracker (m2track.M2TRACK) for K targets in the same frames: what
+    MotionSequenceTracker does per target happens here once per frame for all of them.  The surface is MultiTargetTracker's:
+
+        trk = MultiMotionTracker(model, K)      # model on the GPU, eval mode
+        trk.init(points0, boxes0)               # (N,3) float32 GPU tensor; boxes0 (K,15) or K boxes as pack_box takes them
+        boxes = trk.update(points)              # a (K,15) device VIEW of the new boxes (no sync for it)
+        all_boxes = trk.results()               # (T,K,15) on the host, one sync
+
+    Per frame t >= 1, whatever K:
+
+      o3d_track_crop_multi, one call    group 0: frame t-1, group 1: frame t, both against the K last result boxes
+                                        (generate_subwindow) into crop_buf (2,K,capacity,3).  (Its 96 K-byte target table is
+                                        uploaded in front.)
+      pinned read-back of 2K counts     the one host sync of the frame, shared by the K targets
+      2K index draws                    default_rng(1).choice, memoised by (count, point_sample_size): DrawCache
+      one upload                        the K o3d_motion_job records and the K x 2N indices, one pinned buffer
+      o3d_track_motion_input_multi      gather + time stamp + prior-targetness mask + candidate BoxCloud of all K targets,
+                                        one launch, into the batch-K static inputs; first_frame = (t == 1)
+      forward, batch K                  replayed as one HIP graph captured once per tracker (eager when the capture fails,
+                                        unless O3D_REQUIRE_GRAPH=1)
+      o3d_track_offset_box_multi        the K new boxes into row t of the (T,K,15) results buffer
+
+    log, per frame: (previous-frame counts (K), current-frame counts (K)); crop_calls: the crop calls since init (one per
+    frame, one more whenever a crop outgrew the buffer: all 2K rows then grow to twice the largest count)."""
+    _NAME = "MultiMotionTracker"
+
+    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768):
+        from .m2track import M2TRACK
+        if not isinstance(model, M2TRACK):
+            raise TypeError("MultiMotionTracker serves the motion tracker (M2TRACK); the matching trackers (BAT, P2B) follow "
+                            "K targets with MultiTargetTracker")
+        K = self._n_targets(n_targets)
+        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, K)
+        self._k_state(K)
+        dev, N = self.dev, int(self.point_sample_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.box_aware = bool(getattr(model, "box_aware", False))
+        self.inputs = {"points": torch.zeros((K, 2 * N, 5), **f32)}
+        if self.box_aware:
+            self.inputs["candidate_bc"] = torch.zeros((K, 2 * N, 9), **f32)
+        self.crop_buf = torch.empty((2, K, int(capacity), 3), **f32)       # [0] the previous frame's crops, [1] the current one's
+        # the frame's one upload: K motion jobs, then the K * 2N indices
+        jb = K * PU.MOTION_JOB.itemsize
+        self.stage_host = torch.zeros((jb + 8 * K * N,), dtype=torch.uint8).pin_memory()
+        self.stage = torch.zeros((jb + 8 * K * N,), dtype=torch.uint8, device=dev)
+        self.job_rec = self.stage_host.numpy()[:jb].view(PU.MOTION_JOB)
+        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, 2 * N)
+        self.idx_ptr = self.stage.data_ptr() + jb
+
+    def _crops(self, pts):
+        """the frame's one crop call + the count read-back -> (previous-frame counts (K), current-frame counts (K))"""
+        c, K = self, self.K
+        kk = np.arange(K, dtype=np.uint64)
+
+        def grow(n):                                   # all 2K crops share it: called once, with the largest count
+            c.crop_buf = torch.empty((2, K, 2 * n, 3), dtype=torch.float32, device=c.dev)
+
+        def launch():
+            cap = c.crop_buf.shape[2]
+            c._crop_multi([(src, c._crop_group(g, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW,
+                                               c.crop_buf[g].data_ptr() + 12 * cap * kk, cap))
+                           for g, src in enumerate((c.prev_points, pts))])
+            return [(cap, grow)] * (2 * K)
+        ns = c._counts_loop(launch)
+        return np.array(ns[:K], np.int64), np.array(ns[K:], np.int64)
+
+    def update(self, points):
+        return self._run(points)
+
+    def _update(self, pts):
+        c, K, N = self, self.K, int(self.point_sample_size)
+        c._grow_boxes()
+        n_prev, n_this = c._crops(pts)
+        # the frame's one upload: the indices and the K motion jobs
+        zero = np.zeros((2, K), np.int32)
+        for k in range(K):
+            for h, n in enumerate((n_prev[k], n_this[k])):
+                i = c.draws.get(n, N)
+                if i is None:
+                    zero[h, k] = 1
+                else:
+                    c.idx_rec[k, h * N:(h + 1) * N] = i
+        kk = np.arange(K, dtype=np.uint64)
+        j, cap = c.job_rec, c.crop_buf.shape[2]
+        j["prev"], j["cur"] = c.crop_buf[0].data_ptr() + 12 * cap * kk, c.crop_buf[1].data_ptr() + 12 * cap * kk
+        j["n_prev"], j["n_this"] = n_prev, n_this
+        j["idx"] = c.idx_ptr + 8 * N * kk
+        j["zero_prev"], j["zero_this"] = zero[0], zero[1]
+        c.stage.copy_(c.stage_host, non_blocking=True)
+        PU.motion_input_multi(c.stage, K, N, c.canon_wlh, c.t == 1, c.inputs["points"],
+                              c.inputs["candidate_bc"] if c.box_aware else False)
+        est = c._network()
+        PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
+                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        return c._done(pts, (n_prev, n_this))
+
+
+def _is_motion(model):
+    from .m2track import M2TRACK
+    return isinstance(model, M2TRACK)
+
+
 def tracker_for(model, **kw):
     """the tracker class of a model: MotionSequenceTracker for m2track.M2TRACK, SequenceTracker for the matching trackers"""
-    from .m2track import M2TRACK
-    return (MotionSequenceTracker if isinstance(model, M2TRACK) else SequenceTracker)(model, **kw)
+    return (MotionSequenceTracker if _is_motion(model) else SequenceTracker)(model, **kw)
+
+
+def multi_tracker_for(model, n_targets, **kw):
+    """tracker_for for K targets: MultiMotionTracker for m2track.M2TRACK, MultiTargetTracker for the matching trackers"""
+    return (MultiMotionTracker if _is_motion(model) else MultiTargetTracker)(model, n_targets, **kw)
 
 
 def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
@@ -620,10 +751,16 @@ def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
 
 def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None):
     """track_sequence for K targets in the same frames: boxes0 (K,15) the targets' boxes in frames[0]; ref_boxes[t] (K,15)
-    (optional) is handed to update() of frame t.  -> (T,K,15) result boxes on the host."""
+    (optional, matching trackers only) is handed to update() of frame t.  The tracker class follows the model's type.
+    -> (T,K,15) result boxes on the host."""
     b0 = boxes0 if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray) else list(boxes0)
-    trk = MultiTargetTracker(model, len(b0), seed=seed, use_graph=use_graph)
+    trk = multi_tracker_for(model, len(b0), seed=seed, use_graph=use_graph)
+    if isinstance(trk, MultiMotionTracker) and ref_boxes is not None:
+        raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
     trk.init(frames[0], b0)
     for t in range(1, len(frames)):
-        trk.update(frames[t], None if ref_boxes is None else ref_boxes[t])
+        if ref_boxes is None:
+            trk.update(frames[t])
+        else:
+            trk.update(frames[t], ref_boxes[t])
     return trk.results()

@@ -2,7 +2,7 @@
 had to write before it existed, on the same box in the same run.  Not bench.py: that measures the network alone.
 
   python tools/track_bench.py [--frames 200] [--points 120000] [--model BAT | P2B | M2TRACK]
-  python tools/track_bench.py --targets K [--frames 200] [--points 120000] [--model BAT | P2B]
+  python tools/track_bench.py --targets K [--frames 200] [--points 120000] [--model BAT | P2B | M2TRACK]
 
 Both loops track the same synth.make_sequence with a random-init model in eval mode and start from the frames resident in
 HBM (device loop) / in host memory (host loop: where a dataset reader leaves them).
@@ -19,6 +19,8 @@ Prints one JSON line with both figures and their ratio.
 loop, against K SequenceTrackers run one after another over the same frames in the same process.  Both start from the
 frames resident in HBM.  Prints one JSON line: ms per frame of both, targets x frames per second, their ratio and the
 largest difference between the boxes of the two (batch-K against batch-1 forward, compounding over the sequence).
+--targets K --model M2TRACK: tracking.MultiMotionTracker against K MotionSequenceTrackers run in turn, the same way, with the
+same keys.
 """
 import argparse
 import json
@@ -73,12 +75,30 @@ def motion_host_loop(model, cfg, frames, box0, dev):
     return np.stack(boxes)
 
 
+def motion_model(dev):
+    """-> (model, cfg): the fixture's weights (tests/motion_oracle.py::init_weights) with the three box-moving heads scaled by a
+    further 0.02: a He-initialised head answers with metres per frame, and even the fixture's decimetre per frame lifts the box
+    off the ground within 25 frames, after which the loops would crop empty space and zero-fill their inputs"""
+    cfg = MO.case_config("kitti")
+    model = MO.init_weights(m2track.M2TRACK(**cfg))
+    with torch.no_grad():
+        for name in ("motion_mlp", "final_mlp", "box_mlp"):
+            getattr(model, name)[-1].weight *= 0.02
+            getattr(model, name)[-1].bias *= 0.02
+    return model.to(dev).eval(), cfg
+
+
 def multi_target_main(args, dev):
     K = args.targets
-    cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
-    cfg.update(TO.TEST_KEYS)
-    # the tracking fixture's weights: a He-initialised head moves every box by metres per frame, off its target
-    model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+    if args.model.upper() == "M2TRACK":
+        model, cfg = motion_model(dev)
+        Multi, Single = tracking.MultiMotionTracker, tracking.MotionSequenceTracker
+    else:
+        cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+        cfg.update(TO.TEST_KEYS)
+        # the tracking fixture's weights: a He-initialised head moves every box by metres per frame, off its target
+        model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+        Multi, Single = tracking.MultiTargetTracker, tracking.SequenceTracker
     frames, gt = synth.make_scene(args.seed, args.frames, max(args.points // K, 1024), K)
     dframes = [torch.from_numpy(f).to(dev) for f in frames]
     warm = min(20, args.frames)
@@ -97,7 +117,7 @@ def multi_target_main(args, dev):
             out.append(s.results())
         return np.stack(out, 1)
 
-    multi = tracking.MultiTargetTracker(model, K)
+    multi = Multi(model, K)
     multi.init(dframes[0], gt[0])
     run_multi(warm)                                                     # capture + warm-up
     torch.cuda.synchronize()
@@ -106,7 +126,7 @@ def multi_target_main(args, dev):
     multi_boxes = run_multi(args.frames)
     multi_ms = (time.perf_counter() - t0) / (args.frames - 1) * 1e3
 
-    singles = [tracking.SequenceTracker(model) for _ in range(K)]
+    singles = [Single(model) for _ in range(K)]
     run_singles(warm)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -137,28 +157,17 @@ def main():
     ap.add_argument("--points", type=int, default=120000)
     ap.add_argument("--model", default="BAT")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--targets", type=int, default=0, help="K > 0: MultiTargetTracker against K SequenceTrackers in turn")
+    ap.add_argument("--targets", type=int, default=0, help="K > 0: the batched K-target loop against K single-target trackers in turn")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("track_bench.py needs a GPU: the HIP library is the only compute path (no CPU fallback)")
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
     if args.targets > 0:
-        if args.model.upper() == "M2TRACK":
-            raise SystemExit("--targets serves the matching trackers (BAT, P2B): the motion tracker stays single-target")
         return multi_target_main(args, dev)
     motion = args.model.upper() == "M2TRACK"
     if motion:
-        # the fixture's weights (tests/motion_oracle.py::init_weights) with the three box-moving heads scaled by a further 0.02:
-        # a He-initialised head answers with metres per frame, and even the fixture's decimetre per frame lifts the box off the
-        # ground within 25 frames, after which both loops would crop empty space and zero-fill their inputs
-        cfg = MO.case_config("kitti")
-        model = MO.init_weights(m2track.M2TRACK(**cfg))
-        with torch.no_grad():
-            for name in ("motion_mlp", "final_mlp", "box_mlp"):
-                getattr(model, name)[-1].weight *= 0.02
-                getattr(model, name)[-1].bias *= 0.02
-        model = model.to(dev).eval()
+        model, cfg = motion_model(dev)
         loop = motion_host_loop
     else:
         cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
