@@ -1063,8 +1063,7 @@ extern "C" int o3d_mlp_conv_dgrad_c(const float* dN, const float* Y, const float
                                     const float* scale_p,
                                     const float* shift_p, const float* mean_p, float* dNprev, float* part,
                                     void* stream) {
-    // Y == NULL (then A1..A3 are ignored): dN is the finished dY of o3d_mlp_conv_wgrad2_c_dy
-    if (!dN || (Y && (!A1 || !A2 || !A3)) || !Wt || !w || !meta || !Yprev || !scale_p || !shift_p || !mean_p ||
+    if (!dN || !Y || !A1 || !A2 || !A3 || !Wt || !w || !meta || !Yprev || !scale_p || !shift_p || !mean_p ||
         !dNprev || !part || ldp <= 0 || ldp > 0x7fffffff || !o3d_direct_ok(Cin, Cout, (int)ldp) ||
         (tile != 64 && tile != 128))
         return O3D_EINVAL;
@@ -1084,10 +1083,8 @@ extern "C" int o3d_mlp_conv_dgrad_plain(const float* dN, const float* Y, const f
     return launch_dgrad<false, 2>(a, o3d_stream(stream));
 }
 
-// dW[i] = sum over slices of part[z][i], in a fixed order (two stages above 32 slices; scratch2 holds
-// 16 * n floats)
-void o3d_wgrad_reduce(const float* part, int nslices, long n, float* scratch2, float* dW, hipStream_t s) {
-    (void)scratch2;
+// dW[i] = sum over slices of part[z][i], in a fixed order, in one launch (wgrad_reduce1_kernel)
+void o3d_wgrad_reduce(const float* part, int nslices, long n, float* dW, hipStream_t s) {
     hipLaunchKernelGGL(wgrad_reduce1_kernel, dim3(o3d_cdiv(n, 32)), dim3(256), 0, s, part, nslices, n, dW);
 }
 
@@ -1121,6 +1118,6 @@ extern "C" int o3d_mlp_conv_wgrad(const float* dN, const float* dOut, const floa
                     : launch(conv_wgrad_kernel<false, false>, grid, block, lds, s, a);
     }
     if (rc != O3D_OK) return rc;
-    o3d_wgrad_reduce(part, nslices, (long)Cout * Cin, part + (long)nslices * Cout * Cin, dW, s);
+    o3d_wgrad_reduce(part, nslices, (long)Cout * Cin, dW, s);
     return o3d_launch_status();
 }

@@ -11,6 +11,7 @@ exchange is one collective on one contiguous message: over xGMI's 7 point-to-poi
 issued once after backward instead of being chopped into overlap buckets.
 Backend: "nccl" (= RCCL on ROCm) on GPUs, "gloo" on CPU (tests, world_size 2).
 """
+import contextlib
 import os
 
 import torch
@@ -47,22 +48,12 @@ def shard_indices(step, rank, world, per_rank_batch):
 
 
 def _defer_wgrads():
-    """the backward's scope: the heads' weight gradients in grouped launches (fused_heads.defer_wgrads) and the weight-gradient
-    side branch (fused.wgrad_branch: the set-abstraction levels' wgrad launches on a second stream / graph branch, joined when
-    the scope ends, i.e. before anything reads a gradient)"""
-    import contextlib
+    """the backward's scope: the heads' weight gradients in grouped launches, flushed when the scope ends, i.e. before
+    anything reads a gradient (fused_heads.defer_wgrads)"""
     if not torch.cuda.is_available():
         return contextlib.nullcontext()
-    from . import fused, fused_heads
-    stack = contextlib.ExitStack()
-    stack.enter_context(fused.wgrad_branch())          # exits LAST: joins after the heads' final flush
-    stack.enter_context(fused_heads.defer_wgrads())
-    return stack
-
-
-# prefetch variants (round 6; gpurun_out/prefetch_matrix2.txt: in place / by copy and default / high stream priority all within
-# 0.03 ms of each other on the BAT step): extras written straight into the next FlatBatch's own fields; default stream priority
-_PREFETCH = {"inplace": True, "high_priority": False}
+    from . import fused_heads
+    return fused_heads.defer_wgrads()
 
 
 class FlatBatch(dict):
@@ -302,14 +293,14 @@ class DataParallelStep:
 
     def _prefetch(self, next_batch):
         if self._side is None:
-            self._side = torch.cuda.Stream(priority=-1 if _PREFETCH["high_priority"] else 0)
+            self._side = torch.cuda.Stream()
         own = getattr(next_batch, "extra_keys", ()) if next_batch is not self._static else ()
         # behind everything the main stream has been given so far (the input copy of THIS step; not its graph, which is
         # replayed after this call): nothing on the main stream still reads the buffers written here
         self._side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._side), torch.no_grad():
             src = {k: v for k, v in next_batch.items() if k not in own}
-            if own and self._sampling_takes_out and _PREFETCH["inplace"]:      # straight into the FlatBatch's own fields
+            if own and self._sampling_takes_out:      # straight into the FlatBatch's own fields
                 extra = self._sampling(src, out={k: next_batch[k] for k in own})
             else:
                 extra = self._sampling(src)

@@ -16,7 +16,6 @@ statistics exactly like torch.nn.BatchNorm2d (biased variance to normalise, unbi
 running_var, momentum 0.1); the NEXT kernel applies BN+ReLU while loading.  Saved for
 backward: Y_l and four per-channel vectors per layer, plus arg-max of the pool.
 """
-import contextlib
 import ctypes
 
 import torch
@@ -66,7 +65,6 @@ capi.register("o3d_mlp_conv_fwd_c", [_vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _
 capi.register("o3d_mlp_conv_dgrad_c", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp])
 capi.register("o3d_mlp_conv_wgrad2_c", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad2_c_dy", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp])
 
 
 class _BnFinArgs(ctypes.Structure):       # o3d_bn_fin_args
@@ -410,95 +408,6 @@ def _const_vec(dev, n, value):
 _CONST = {}
 
 
-# ---- weight gradients on a second branch of the step (round 6) ---------------------------------------------------------
-# The weight gradient of a layer is a LEAF of the backward: nothing in the step reads dW_l before the optimizer, while the
-# data gradient of the same layer heads the critical chain  dgrad_l -> bn_bwd_finalize_{l-1} -> dgrad_{l-1} -> ...  (a chain of
-# launches with wave-quantised tails and ~7 us dependent finalizes during which most of the chip idles).  Inside
-# `wgrad_branch()` -- DataParallelStep wraps loss.backward() in it -- the wgrad launches (+ their slice reductions, the layer-0
-# per-point weight gradient and its centre term) go to a SIDE stream forked from the launch stream behind the layer's
-# bn_bwd_finalize; the scope's end joins it.  Captured into the step's HIP graph the fork/join are graph edges: the wgrad
-# nodes form a second branch that the hardware schedules into the main chain's idle slots.
-# Soundness = the contract of fused_heads.defer_wgrads (the gradient tensors autograd is handed are FILLED LATER): a parameter
-# that already holds a gradient or carries hooks is never branched (`_deferrable`), a parameter met twice in one scope joins
-# first, and everything a side launch reads is kept alive in the scope until the join (a tensor freed on the launch stream
-# could be handed out again while the side launch still reads it).
-# MEASURED AND NOT KEPT AS THE DEFAULT (profiles/r06_ab_wgrad_branch.txt, same-box alternating A/B on the final kernels): the
-# branch overlaps 1.07 ms of kernel time per BAT step (sum of kernel durations 6.57 ms against a busy union of 5.11; without
-# it 5.50 / 5.20) and the busy time does shrink by 0.09 ms -- the tails are filled -- but every fork / join is a cross-queue
-# dependency of the replayed graph (~7-10 us each, 14 forks per step) and the overlapped kernels stretch (the 14 slice
-# reductions 0.11 -> 0.36 ms): BAT 5.31 -> 5.39 ms, P2B 8.71 -> 8.79, M2-Track 6.30 -> 6.52.  The mechanism stays as a tested
-# switch (tests/test_model_gpu.py::test_wgrad_side_branch_equals_inline_launches), off.
-_WGRAD_BRANCH = {"on": False,      # tools/ab_hook.py fused._WGRAD_BRANCH.on flips it for the same-box A/B; tests run both
-                 "heads_only": False}   # True (with "on"): only the heads' grouped launches branch (ONE fork per full group)
-_BRANCH = {"scope": None, "last_launches": 0}      # last_launches: side-branch forks of the scope that closed last (tests)
-_SIDE_STREAMS = {}
-
-
-def set_wgrad_branch(enabled):
-    _WGRAD_BRANCH["on"] = bool(enabled)
-
-
-def _branch_join(sc):
-    if sc["side"] is not None and sc["forked"]:
-        sc["main"].wait_stream(sc["side"])
-    sc["forked"] = False
-    sc["keep"] = []
-    sc["keys"] = set()
-
-
-@contextlib.contextmanager
-def wgrad_branch():
-    if not _WGRAD_BRANCH["on"] or _BRANCH["scope"] is not None or not torch.cuda.is_available():
-        yield
-        return
-    sc = _BRANCH["scope"] = {"main": None, "side": None, "keep": [], "keys": set(), "forked": False, "launches": 0}
-    try:
-        yield
-    finally:
-        _BRANCH["scope"] = None
-        _BRANCH["last_launches"] = sc["launches"]
-        _branch_join(sc)
-
-
-def branch_join():
-    """the launch stream waits for everything the open scope has put on the side branch (no-op without one)"""
-    if _BRANCH["scope"] is not None:
-        _branch_join(_BRANCH["scope"])
-
-
-def _branch_side(params, keep):
-    """-> the side stream the weight-gradient launches of `params` may go to (forked behind everything the launch stream
-    has been given so far), or None: launch inline.  keep: every tensor those launches read or use as scratch."""
-    sc = _BRANCH["scope"]
-    if sc is None:
-        return None
-    from .fused_heads import _deferrable
-    params = [p for p in params if p is not None]
-    if params and _WGRAD_BRANCH["heads_only"]:      # a set-abstraction level's own weight gradient: inline in this mode
-        return None
-    if not _deferrable(params):
-        return None
-    main = torch.cuda.current_stream()
-    if sc["main"] is None:
-        key = (main.device.index, main.cuda_stream)
-        side = _SIDE_STREAMS.get(key)
-        if side is None:
-            side = _SIDE_STREAMS[key] = torch.cuda.Stream(device=main.device)
-        sc["main"], sc["side"] = main, side
-    elif main != sc["main"]:
-        return None
-    keys = {id(p) for p in params}
-    if sc["keys"] & keys:      # second use of a parameter: autograd ADDS this gradient to the first as soon as the backward
-        _branch_join(sc)       # returns -- the first must be complete, and this one is launched inline
-        return None
-    sc["keys"] |= keys
-    sc["side"].wait_stream(main)
-    sc["keep"].append(keep)
-    sc["forked"] = True
-    sc["launches"] += 1
-    return sc["side"]
-
-
 # ---- the autograd function ---------------------------------------------------------------
 class _Cfg:
     __slots__ = ("nxyz", "inv_radius", "training", "bns", "eps", "momentum", "centers", "geo", "geo_dims")
@@ -685,7 +594,6 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         if need_bwd:
             ctx.cfg = cfg
             ctx.versions = _versions(params)
-            ctx.wparams = [params[3 * l] for l in range(L)]       # (identity only: which parameter a weight gradient belongs to)
             # weights as the backward's GEMMs want them: W_l^T for the data gradients, W0^T padded to 64 rows
             ctx.Wts = [None] + [prep.get(params[3 * l], Ws[l].shape[1], Ws[l].shape[0], transpose=True) for l in range(1, L)]
             want_in = any(ctx.needs_input_grad[2:2 + 4 * nseg])
@@ -807,29 +715,24 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                     dWm = torch.empty((Cout, Cin), device=dev, dtype=f32)
                 fold = bool(nxyz) and dWm.shape[1] != Cin
                 dW = torch.empty((Cout, Cin), device=dev, dtype=f32) if fold else None
-                # dW0 is a leaf: the per-point weight gradient and its centre term on the side branch (the data gradient
-                # W0^T . S below, which the next level's backward waits for, stays on the launch stream)
-                side = _branch_side([ctx.wparams[0]], (S, T, wpart, dWm, dW, one, zero, ctx.saved))
-                st0 = side.cuda_stream if side is not None else st
-                with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                    if aligned:
-                        _call("conv_wgrad_points", 2.0 * Cinm * Cout * ldz, lib.o3d_mlp_conv_wgrad2, S.data_ptr(), None, 4,
-                              S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None, None, 1,
-                              Cinm, Cout, ldz, wpart.data_ptr(), dWm.data_ptr(), st0, dims=(Cinm, Cout, True))
-                    else:
-                        _call("conv_wgrad_points", 2.0 * Cin * Cout * ldz, lib.o3d_mlp_conv_wgrad, S.data_ptr(), None, None,
-                              None, 4, S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None,
-                              None, 1, Cin, Cout, ldz, nsl, wpart.data_ptr(), dWm.data_ptr(), st0)
-                    if fold:
-                        # the centre term of grouped_xyz = xyz[idx] - new_xyz and the compaction of the padded rows in one
-                        # launch (was: the term in place, then a strided torch copy of dWm[:, :Cin])
-                        _call("center_term", 0.0, lib.o3d_center_term_out, T.data_ptr(), centers.data_ptr(), Cout, nballs,
-                              dWm.shape[1], dWm.data_ptr(), Cin, dW.data_ptr(), st0)
-                    else:
-                        if nxyz:      # the centre term of grouped_xyz = xyz[idx] - new_xyz
-                            _call("center_term", 0.0, lib.o3d_center_term, T.data_ptr(), centers.data_ptr(), Cout, nballs,
-                                  dWm.shape[1], dWm.data_ptr(), st0)
-                        dW = dWm if dWm.shape[1] == Cin else dWm[:, :Cin].contiguous()
+                if aligned:
+                    _call("conv_wgrad_points", 2.0 * Cinm * Cout * ldz, lib.o3d_mlp_conv_wgrad2, S.data_ptr(), None, 4,
+                          S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None, None, 1,
+                          Cinm, Cout, ldz, wpart.data_ptr(), dWm.data_ptr(), st, dims=(Cinm, Cout, True))
+                else:
+                    _call("conv_wgrad_points", 2.0 * Cin * Cout * ldz, lib.o3d_mlp_conv_wgrad, S.data_ptr(), None, None,
+                          None, 4, S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None,
+                          None, 1, Cin, Cout, ldz, nsl, wpart.data_ptr(), dWm.data_ptr(), st)
+                if fold:
+                    # the centre term of grouped_xyz = xyz[idx] - new_xyz and the compaction of the padded rows in one
+                    # launch (was: the term in place, then a strided torch copy of dWm[:, :Cin])
+                    _call("center_term", 0.0, lib.o3d_center_term_out, T.data_ptr(), centers.data_ptr(), Cout, nballs,
+                          dWm.shape[1], dWm.data_ptr(), Cin, dW.data_ptr(), st)
+                else:
+                    if nxyz:      # the centre term of grouped_xyz = xyz[idx] - new_xyz
+                        _call("center_term", 0.0, lib.o3d_center_term, T.data_ptr(), centers.data_ptr(), Cout, nballs,
+                              dWm.shape[1], dWm.data_ptr(), st)
+                    dW = dWm if dWm.shape[1] == Cin else dWm[:, :Cin].contiguous()
                 grads[0] = dW
                 if want_xyz or want_feats:
                     # dX = W0^T . S as a plain forward GEMM on the direct MFMA kernel: rows padded to a multiple of 64
@@ -871,30 +774,16 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
             flops = (2.0 * Cin * Cout, meta, ldp)      # executed FLOPs = per live column (count read back when profiling)
             dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
             wpart = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Cin, Cout, ldp),), device=dev, dtype=f32)
-            dYm = None
-            if _DY_ONCE["on"]:
-                # (experiment, review item 2-ii) the weight gradient writes the operand it stages, dY, once; the data gradient
-                # below then loads that ONE tensor instead of rebuilding dY from dN and Y
-                dYm = torch.empty((Cout, ldp), device=dev, dtype=f32)
-                _call("conv_wgrad", flops, lib.o3d_mlp_conv_wgrad2_c_dy, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
-                      Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), Cin, Cout, ldp,
-                      cw.data_ptr(), meta.data_ptr(), start1, wpart.data_ptr(), dW.data_ptr(), dYm.data_ptr(), st,
-                      dims=(Cin, Cout))
-            else:
-                side = _branch_side([ctx.wparams[l]], (dN, coef, wpart, ctx.saved))
-                with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                    _call("conv_wgrad", flops, lib.o3d_mlp_conv_wgrad2_c, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
-                          Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), Cin, Cout, ldp,
-                          cw.data_ptr(), meta.data_ptr(), start1, wpart.data_ptr(), dW.data_ptr(),
-                          side.cuda_stream if side is not None else st, dims=(Cin, Cout))
+            _call("conv_wgrad", flops, lib.o3d_mlp_conv_wgrad2_c, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
+                  Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), Cin, Cout, ldp, cw.data_ptr(),
+                  meta.data_ptr(), start1, wpart.data_ptr(), dW.data_ptr(), st, dims=(Cin, Cout))
             grads[3 * l] = dW
             Wt = ctx.Wts[l]
             dNp = torch.empty((Cin, ldp), device=dev, dtype=f32)
             dtile = _direct_tile(lib, ldp, Cin)
             part = torch.empty((ldp // dtile + _tail_rows(lib, dtile, Cin, nseg, 1), 2, Cin), device=dev, dtype=f32)
-            _call("conv_dgrad", flops, lib.o3d_mlp_conv_dgrad_c, (dYm if dYm is not None else dN).data_ptr(),
-                  None if dYm is not None else Ys[l].data_ptr(), A[0], A[1], A[2],
-                  Wt.data_ptr(), Cin, Cout, ldp, cw.data_ptr(), meta.data_ptr(), start1, dtile, Ys[l - 1].data_ptr(),
+            _call("conv_dgrad", flops, lib.o3d_mlp_conv_dgrad_c, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2], Wt.data_ptr(),
+                  Cin, Cout, ldp, cw.data_ptr(), meta.data_ptr(), start1, dtile, Ys[l - 1].data_ptr(),
                   scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), means[l - 1].data_ptr(), dNp.data_ptr(),
                   part.data_ptr(), st, dims=(Cin, Cout))
             dN = dNp
@@ -917,11 +806,6 @@ _POOL_BWD_DENSE = {"on": True}
 
 def set_pool_bwd_dense(enabled):
     _POOL_BWD_DENSE["on"] = bool(enabled)
-
-
-# (experiment, round 6) dY written once by the weight gradient, the data gradient loads one operand tensor: see
-# profiles/r06_ab_dy_once.txt.  tools/ab_hook.py fused._DY_ONCE.on flips it; tests run both.
-_DY_ONCE = {"on": False}
 
 
 # data + weight gradient of a 64-input-channel inner layer in ONE kernel (csrc/mlp_wgrad.hip::fused_bwd_kernel: SA level 0's

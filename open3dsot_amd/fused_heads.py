@@ -62,36 +62,15 @@ def _flush_jobs(jobs, st):
         _call("pw_conv_wgrad", sum(j[0] for j in chunk), lib.o3d_mlp_conv_wgrad2_group, ctypes.addressof(arr), len(chunk), st)
 
 
-def _flush_queue(early=False):
-    """early: FULL groups of jobs (multiples of _MAXJOBS) while the scope is still open -- launched on the weight-gradient side
-    branch when one is open (open3dsot_amd/fused.py::wgrad_branch), beside the rest of the backward instead of behind it; what
-    does not fill a group stays queued; the parameter keys stay recorded, so that a later second use of one of these
-    parameters still finds it"""
+def _flush_queue():
+    """launch everything queued, grouped per launch stream, and forget the recorded parameter keys"""
     q = _DEFER["queue"]
-    _DEFER["queue"] = []
-    if not early:
-        _DEFER["keys"] = set()
+    _DEFER["queue"], _DEFER["keys"] = [], set()
     by_stream = {}
     for jobs, keep, st in q:
         by_stream.setdefault(st, []).extend(jobs)
     for st, jobs in by_stream.items():
-        side = None
-        if early:
-            n = (len(jobs) // _MAXJOBS) * _MAXJOBS
-            if n < len(jobs):        # the remainder waits for the next full group / the end of the scope (operands: held by
-                _DEFER["queue"].append((jobs[n:], q, st))      # `q`, which the re-queued entry keeps alive)
-                jobs = jobs[:n]
-            if jobs and st == _stream():
-                from . import fused
-                side = fused._branch_side([], q)       # (the scope keeps `q` -- the operands -- alive until the join)
-        if not jobs:
-            continue
-        if side is not None:
-            with torch.cuda.stream(side):
-                _flush_jobs(jobs, side.cuda_stream)
-        else:
-            _flush_jobs(jobs, st)
-    del q
+        _flush_jobs(jobs, st)
 
 
 def _deferrable(params):
@@ -125,15 +104,8 @@ def _submit_jobs(jobs, keep, st, params):
     _DEFER["queue"].append((jobs, keep, st))      # (the queue keeps the operands alive until the flush)
     if (_DEFER["keys"] & keys) or not _deferrable(params):
         _flush_queue()
-        from . import fused
-        fused.branch_join()         # an earlier group with this parameter may be running on the side branch
     else:
         _DEFER["keys"] |= keys
-        from . import fused
-        if fused._BRANCH["scope"] is not None and sum(len(e[0]) for e in _DEFER["queue"]) >= _MAXJOBS:
-            # only with the weight-gradient side branch open (off by default): full groups go out beside the rest of the
-            # backward.  Without it an early flush only splits the step's 23 jobs into more launches than the 3 of the final one
-            _flush_queue(early=True)
 
 
 @contextlib.contextmanager

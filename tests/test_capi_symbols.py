@@ -1,8 +1,10 @@
-"""The C-ABI library builds for gfx950, loads without a GPU and exports every symbol that
+"""The C-ABI library builds for gfx950, loads without a GPU and exports exactly the symbols that
 include/o3dsot.h declares; the Python binding refuses CPU tensors (no CPU fallback)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -27,6 +29,14 @@ def test_library_exports_header():
     assert capi.version().startswith("o3dsot-hip")
     for n in capi.SIGNATURES:  # everything the binding calls is exported as well
         assert hasattr(lib, n), n
+    # and the other way round: every C entry point the library defines is declared (an export that lost its declaration
+    # and its caller would otherwise stay in the library unnoticed)
+    nm = shutil.which("nm")
+    if nm is not None:
+        out = subprocess.run([nm, "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
+        defined = {f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3 and f[1] in "Tt"}
+        exported = sorted(n for n in defined if n.startswith("o3d_"))
+        assert not set(exported) - set(names), "exported but not declared in include/o3dsot.h: %s" % (set(exported) - set(names))
 
 
 def test_code_object_is_gfx950():
@@ -108,6 +118,8 @@ def test_entry_points_reject_bad_arguments_before_touching_the_device():
     assert lib.o3d_compact_build(p, 1, 8, 3, 8, 0, 0, 0, 8, p, p, p, p, p, p, None) == EINVAL       # nsample not a power of two
     assert lib.o3d_pool_fwd_c(None, 256, None, None, None, None, 1, 8, 8, 0, None, None, None, None) == EINVAL
     assert lib.o3d_center_term(None, None, 8, 8, 3, None, None) == EINVAL
+    # the compact data gradient rebuilds dY from dN AND Y: every operand valid but Y
+    assert lib.o3d_mlp_conv_dgrad_c(p, None, p, p, p, p, 64, 128, 2048, p, p, 1024, 64, p, p, p, p, p, p, None) == EINVAL
     for entry, mirror in ((lib.o3d_bn_finalize, fused._BnFinArgs), (lib.o3d_bn_bwd_finalize, fused._BnBwdFinArgs)):
         jobs = (mirror * 2)()                               # zeroed jobs: `part` is NULL
         assert entry(None, 1, None) == EINVAL

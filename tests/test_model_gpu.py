@@ -832,14 +832,15 @@ def test_graph_step_equals_eager_step_bookkeeping():
             assert torch.isfinite(w).all(), k
 
 
-def test_graph_replay_gradients_equal_eager_gradients():
+@pytest.mark.parametrize("model_name", ["BAT", "P2B"])
+def test_graph_replay_gradients_equal_eager_gradients(model_name):
     """the captured training step replayed on a NEW batch computes what an eager forward + backward on that batch
     computes (same weights: lr = 0): loss and every parameter gradient -- the timed region of bench.py is this replay"""
     import copy
     from open3dsot_amd import dist as D, synth, trackers
     dev = torch.device("cuda", 0)
     torch.manual_seed(5)
-    model = trackers.BAT().to(dev).train()
+    model = trackers.get_model(model_name)().to(dev).train()
     twin = copy.deepcopy(model)
     b0, b1 = [synth.to_torch(synth.make_batch(950 + 6 * i, 6, 256, 512), dev) for i in range(2)]
     step = D.DataParallelStep(model, optimizer=torch.optim.SGD(model.parameters(), lr=0.0), world=1, graph=True,
@@ -866,91 +867,7 @@ def test_graph_replay_gradients_equal_eager_gradients():
         err = float((grads_g[k] - p.grad).abs().max()) / scale
         worst = max(worst, err)
         assert err < 5e-3, (k, err)          # LDS-atomic summation order differs run to run; nothing else may
-    print("graph replay vs eager: worst per-parameter max-norm gradient difference %.1e" % worst)
-
-
-@pytest.mark.parametrize("model_name", ["BAT", "P2B"])
-@pytest.mark.parametrize("graph", [False, True])
-def test_wgrad_side_branch_equals_inline_launches(model_name, graph):
-    """fused.wgrad_branch (round 6): inside DataParallelStep's backward the set-abstraction levels' weight-gradient launches
-    (and full groups of the heads' deferred ones) run on a side stream / second branch of the captured graph, joined before
-    anything reads a gradient.  Same step with the branch switched off (every launch inline on the launch stream): loss and
-    every parameter gradient equal to the run-to-run noise of the backward's LDS atomics; the branch really forked."""
-    import copy
-    from open3dsot_amd import dist as D, fused, synth, trackers
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(9)
-    model = trackers.get_model(model_name)().to(dev).train()
-    twin = copy.deepcopy(model)
-    b0, b1 = [synth.to_torch(synth.make_batch(970 + 6 * i, 6, 256, 512), dev) for i in range(2)]
-    res = {}
-    was = fused._WGRAD_BRANCH["on"]
-    for on, m in ((True, model), (False, twin)):
-        fused.set_wgrad_branch(on)
-        fused._BRANCH["last_launches"] = 0
-        try:
-            step = D.DataParallelStep(m, optimizer=torch.optim.SGD(m.parameters(), lr=0.0), world=1, graph=graph,
-                                      graph_warmup=0, require_graph=graph)
-            step.step(b0)
-            forks = fused._BRANCH["last_launches"]
-            loss = float(step.step(b1))
-            torch.cuda.synchronize()
-            assert (step.graph is not None) == graph, step.graph_error
-        finally:
-            fused.set_wgrad_branch(was)
-        assert (forks > 0) == on, (on, forks)
-        res[on] = (loss, {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None})
-    (la, ga), (lb, gb) = res[True], res[False]
-    assert abs(la - lb) <= 1e-5 * (1 + abs(lb)), (la, lb)
-    assert set(ga) == set(gb)
-    top = max(float(v.abs().max()) for v in gb.values())
-    worst = 0.0
-    for k, want in gb.items():
-        scale = float(want.abs().max())
-        if scale < 1e-4 * top:
-            assert float(ga[k].abs().max()) < 1e-3 * top, k
-            continue
-        err = float((ga[k] - want).abs().max()) / scale
-        worst = max(worst, err)
-        assert err < 5e-3, (k, err)
-    print("%s graph=%s: side branch vs inline, worst per-parameter max-norm gradient difference %.1e" % (model_name, graph, worst))
-
-
-def test_dy_written_once_equals_the_two_operand_data_gradient():
-    """fused._DY_ONCE (round-6 experiment, off by default): the weight-gradient launch writes the operand it stages,
-    dY = A1*dN + w*(A2*Y + A3), and the data gradient loads that one tensor (o3d_mlp_conv_wgrad2_c_dy +
-    o3d_mlp_conv_dgrad_c with Y = NULL) instead of rebuilding it from dN and Y: same loss, same gradients (the summation
-    order inside the kernels is unchanged; what differs run to run is the LDS-atomic noise of the list sums)"""
-    import copy
-    from open3dsot_amd import fused, synth, trackers
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(13)
-    model = trackers.BAT().to(dev).train()
-    twin = copy.deepcopy(model)
-    batch = synth.to_torch(synth.make_batch(990, 6, 256, 512), dev)
-    res = {}
-    for on, m in ((True, model), (False, twin)):
-        fused._DY_ONCE["on"] = on
-        try:
-            loss, _ = m.training_loss(batch)
-            loss.backward()
-            torch.cuda.synchronize()
-        finally:
-            fused._DY_ONCE["on"] = False
-        res[on] = (float(loss.detach()), {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None})
-    (la, ga), (lb, gb) = res[True], res[False]
-    assert la == lb, (la, lb)
-    top = max(float(v.abs().max()) for v in gb.values())
-    worst = 0.0
-    for k, want in gb.items():
-        scale = float(want.abs().max())
-        if scale < 1e-4 * top:
-            assert float(ga[k].abs().max()) < 1e-3 * top, k
-            continue
-        err = float((ga[k] - want).abs().max()) / scale
-        worst = max(worst, err)
-        assert err < 5e-3, (k, err)
-    print("dY written once vs two-operand data gradient: worst per-parameter max-norm gradient difference %.1e" % worst)
+    print("%s graph replay vs eager: worst per-parameter max-norm gradient difference %.1e" % (model_name, worst))
 
 
 @pytest.mark.parametrize("train", [True, False])

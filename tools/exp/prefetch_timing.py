@@ -9,7 +9,6 @@ from open3dsot_amd import dist as D, synth, trackers
 
 geo = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 trackers._GEOMETRY_PREFETCH["on"] = bool(geo)
-D._PREFETCH["inplace"] = bool(int(sys.argv[2])) if len(sys.argv) > 2 else False
 dev = torch.device("cuda", 0)
 torch.manual_seed(1234)
 model = trackers.BAT().to(dev).train()
@@ -50,5 +49,5 @@ print("pair_geometry outputs:", fused._GEO_STATS, "| pool[1] is FlatBatch:", isi
 gd = [r["g0"].elapsed_time(r["g1"]) for r in rec]
 pe = [r["g0"].elapsed_time(r["p_end"]) for r in rec]          # prefetch end relative to the graph's start
 gap = [rec[i]["g1"].elapsed_time(rec[i + 1]["g0"]) for i in range(len(rec) - 1)]   # end of graph t -> start of graph t+1
-print("geometry prefetch %d inplace %d | step %.3f ms | graph replay %.3f ms (min %.3f max %.3f) | prefetch ends %.3f ms after the graph starts (max %.3f) | graph-to-graph gap %.3f ms (max %.3f)"
-      % (geo, int(D._PREFETCH["inplace"]), t_all0.elapsed_time(t_all1) / 60, st.median(gd), min(gd), max(gd), st.median(pe), max(pe), st.median(gap), max(gap)))
+print("geometry prefetch %d | step %.3f ms | graph replay %.3f ms (min %.3f max %.3f) | prefetch ends %.3f ms after the graph starts (max %.3f) | graph-to-graph gap %.3f ms (max %.3f)"
+      % (geo, t_all0.elapsed_time(t_all1) / 60, st.median(gd), min(gd), max(gd), st.median(pe), max(pe), st.median(gap), max(gap)))
