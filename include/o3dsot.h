@@ -733,6 +733,66 @@ typedef struct { const float* prev; int n_prev; const float* cur; int n_this; co
 int o3d_track_motion_input_multi(const o3d_motion_job* jobs, int K, int N, const float* wlh, int first_frame, float* points,
                                  float* candidate_bc, void* stream);
 
+/* ---- training batches built on the device (csrc/train_batch.hip): the device form of PointTrackingSampler +
+ * siamese_processing (datasets/sampler.py:16-79) for BAT and P2B.  Frames and ground-truth boxes resident in HBM go in, the
+ * training dict comes out; no host synchronisation.  The formulas are written at the head of csrc/train_batch.hip.
+ *
+ * o3d_track_crop_groups: o3d_track_crop_multi for G (1..O3D_CROP_MAX_GROUPS) groups.  A group is one cloud and a DEVICE table
+ * of n_targets (1..O3D_CROP_MULTI_MAX_TARGETS) o3d_crop_target records, with the semantics of o3d_track_crop_multi; per
+ * (group, target), rows and count[0] are bit-identical to o3d_track_crop_multi on that group alone.  The host knows every n:
+ * o3d_track_crop_groups_scratch (host only, no HIP call) fills wg_start / row_start / sbase of the HOST table `groups`,
+ * writes grid[0] = the workgroups of the count and scatter launches, grid[1] = those of the scan launch, and returns the
+ * scratch length in int32 (-1: bad table).  The caller uploads the planned records; o3d_track_crop_groups takes the planned
+ * host table (validated again, before any HIP call) and its device copy `dev_groups`, which the three launches read. */
+#define O3D_CROP_MAX_GROUPS 4096
+typedef struct {
+    const float* points; int n; const o3d_crop_target* targets; int n_targets;
+    int wg_start;             /* planned: the group's first workgroup in the count / scatter grids */
+    int row_start;            /* planned: its first (group, target) row = its first workgroup in the scan grid */
+    long sbase;               /* planned: its first word in scratch (n_targets rows of ceil(n / 256) int32 follow) */
+} o3d_crop_plan;
+long o3d_track_crop_groups_scratch(o3d_crop_plan* groups, int n_groups, int* grid);
+int o3d_track_crop_groups(const o3d_crop_plan* groups, const o3d_crop_plan* dev_groups, int n_groups, int32_t* scratch,
+                          long scratch_len, void* stream);
+
+/* Which candidates fill the batch (one workgroup).  counts (J,3) int32 = the counts of the first-frame, template-frame and
+ * search crops of candidate j, before any truncation; 1 <= B <= J <= O3D_TRAIN_MAX_CANDIDATES.  Candidate j is valid iff
+ * counts[j][0] + counts[j][1] > 20 and counts[j][2] > 20 (datasets/sampler.py:46,59).  sel (B): sel[r] = the (r mod n_valid)-th
+ * valid candidate, -1 when none is valid; n_valid (1); overflow (1) = the number of crops, over the B chosen rows, whose count
+ * exceeds its capacity cap[c]. */
+#define O3D_TRAIN_MAX_CANDIDATES 1024
+int o3d_train_select(const int32_t* counts, int J, int B, int cap_first, int cap_template, int cap_search, int32_t* sel,
+                     int32_t* n_valid, int32_t* overflow, void* stream);
+
+/* Per candidate, one thread each, double precision inside and rounded once: gt_search, sample_bb, template_bb (J,15) and
+ * offset (J,4) = the search jitter (x, y, 0, theta) -> search_box (J,15) = transform_box(gt_search, sample_bb)
+ * (datasets/points_utils.py:253-258: centre R_sb^T (c - c_sb), rotation R_sb^T R), box_label (J,4) = (its centre,
+ * -theta), bbox_size (J,3) = its wlh, model_box (J,15) = centre 0, the wlh of template_bb, identity. */
+int o3d_train_labels(const float* gt_search, const float* sample_bb, const float* template_bb, const float* offset, int J,
+                     float* search_box, float* box_label, float* bbox_size, float* model_box, void* stream);
+
+/* Sample and gather, grid (rows, B, 2).  Output row r takes candidate j = sel[r].  Template cloud: the virtual concatenation
+ * of crop_first[j] (min(counts[j][0], cap_first) rows) and crop_template[j] (min(counts[j][1], cap_template) rows), resampled
+ * to M rows; search cloud: crop_search[j] (min(counts[j][2], cap_search) rows) resampled to N rows (regularize_pc,
+ * datasets/points_utils.py:24-40).  The crops are pools (J,cap,3).  idx_t (J,M) / idx_s (J,N) int32 | NULL: the indices of
+ * candidate j (both or neither); NULL: the device draw keyed by (seed, counter, j, cloud, row), integers only
+ * (csrc/train_batch.hip).  A cloud of n <= 2 rows, sel[r] < 0 or an index outside [0, n) gives a zero row with seg_label 0.
+ * seg_label (B,N) = crop_test of the row against search_box[j] (scale 1, offset 0: get_in_box_mask).  Row r of box_label (B,4),
+ * bbox_size (B,3) and of the BoxCloud boxes bc_boxes [2][centre (B,3) | wlh (B,3) | rotation (B,9)] ([0] = model_box, [1] =
+ * search_box; | NULL) is candidate j's (zeros when sel[r] < 0).  used_t (B,M) / used_s (B,N) int32 | NULL: the indices used
+ * (-1: zero row). */
+typedef struct {
+    const int32_t* sel; const int32_t* counts;
+    const float* crop_first; const float* crop_template; const float* crop_search;
+    int cap_first, cap_template, cap_search, J, B, M, N;
+    const int32_t* idx_t; const int32_t* idx_s;
+    unsigned seed, counter;
+    const float* search_box; const float* model_box; const float* cand_box_label; const float* cand_bbox_size;
+    float* template_points; float* search_points; float* seg_label; float* box_label; float* bbox_size; float* bc_boxes;
+    int32_t* used_t; int32_t* used_s;
+} o3d_train_sample_args;
+int o3d_train_sample(const o3d_train_sample_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

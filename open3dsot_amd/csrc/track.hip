@@ -61,14 +61,11 @@
 // Within a launch no workgroup reads a word that another workgroup of that launch writes; the order between the launches is
 // the stream's.  There is no flag, no atomic and no loop that waits.  Every (point, target) decision is made by crop_test, the
 // one function that o3d_track_crop calls too, with no early rejection: rows and counts equal o3d_track_crop's.
-#include "o3d_common.hpp"
+// crop_test, gather_row, offset_box_one and the workgroup bodies of the three launches (crop_multi_wg, crop_scan_row) live in
+// track_common.hpp: csrc/train_batch.hip (o3d_track_crop_groups, o3d_train_sample) calls the same definitions.
+#include "track_common.hpp"
 
 namespace {
-
-constexpr int CROP_WG = 256;
-
-// workgroups of a cloud of n points: an empty cloud keeps one, which writes count = 0
-inline int crop_wgs(int n) { return n > 0 ? o3d_cdiv(n, CROP_WG) : 1; }
 
 struct CropTable {
     o3d_crop_job job[O3D_CROP_MAX_JOBS];
@@ -76,45 +73,10 @@ struct CropTable {
     int n_jobs;
 };
 
-// keep? and q for the point p against `box` (15), in the operation order of the header comment: THE crop test, of both
-// o3d_track_crop (box in global memory) and o3d_track_crop_multi (box staged in LDS)
-__device__ __forceinline__ bool crop_test(float px, float py, float pz, const float* box, float scale, float offset, int mode,
-                                          float& qx, float& qy, float& qz) {
-    const float dx = px - box[0], dy = py - box[1], dz = pz - box[2];
-    const float w = box[3], l = box[4], h = box[5];
-    const float* R = box + 6;
-    bool keep = true;
-    if (mode == O3D_CROP_MODEL) {
-        const float s4 = 4.f * scale, o2 = 2.f * offset;
-        const float L = (l * s4) * 0.5f, W = (w * s4) * 0.5f, H = (h * s4) * 0.5f;
-        const float e0 = ((fabsf(R[0]) * L + fabsf(R[1]) * W) + fabsf(R[2]) * H) + o2;
-        const float e1 = ((fabsf(R[3]) * L + fabsf(R[4]) * W) + fabsf(R[5]) * H) + o2;
-        const float e2 = ((fabsf(R[6]) * L + fabsf(R[7]) * W) + fabsf(R[8]) * H) + o2;
-        keep = fabsf(dx) < e0 && fabsf(dy) < e1 && fabsf(dz) < e2;
-    }
-    qx = (R[0] * dx + R[3] * dy) + R[6] * dz;
-    qy = (R[1] * dx + R[4] * dy) + R[7] * dz;
-    qz = (R[2] * dx + R[5] * dy) + R[8] * dz;
-    const float hx = (l * scale) * 0.5f + offset, hy = (w * scale) * 0.5f + offset, hz = (h * scale) * 0.5f + offset;
-    return keep && fabsf(qx) < hx && fabsf(qy) < hy && fabsf(qz) < hz;
-}
-
 // crop_test for point i of a job; `box` is J.box, which nothing writes during the launch
 __device__ __forceinline__ bool crop_point(const o3d_crop_job& J, const float* __restrict__ box, int i, float& qx, float& qy, float& qz) {
     const float* p = J.points + 3 * (long)i;
     return crop_test(p[0], p[1], p[2], box, J.scale, J.offset, J.mode, qx, qy, qz);
-}
-
-// (x, y, z) = row idx[i] of src (n_src,3); zeros when `zero` is set (src and idx are then not read) or the index lies
-// outside the source (a caller's bug: the row stays zero)
-__device__ __forceinline__ void gather_row(const float* src, int n_src, const int32_t* idx, int i, int zero, float& x, float& y, float& z) {
-    x = y = z = 0.f;
-    if (zero) return;
-    const int s = idx[i];
-    if ((unsigned)s < (unsigned)n_src) {
-        const float* p = src + 3 * (long)s;
-        x = p[0]; y = p[1]; z = p[2];
-    }
 }
 
 __device__ __forceinline__ int crop_job_of(const CropTable& t, int wg) {
@@ -222,68 +184,10 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
     motion_row(x, y, z, half, a.wlh, a.first_frame, a.points + 5 * (long)i, a.bc ? a.bc + 9 * (long)i : nullptr);
 }
 
-// counter-based draw from U[-1, 1): a 32-bit mix of (seed, frame, component) (the finaliser of MurmurHash3), its top 24 bits
-__device__ __forceinline__ float limit_draw(unsigned seed, unsigned frame, unsigned comp) {
-    unsigned x = seed * 0x9E3779B1u ^ (frame * 0x85EBCA77u + comp * 0xC2B2AE3Du + 0x27D4EB2Fu);
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return (float)(x >> 8) * (2.f / 16777216.f) - 1.f;
-}
-
 struct OffsetArgs {
     const float* ref; const float* offset; float* yaw_state; float* out; float* results; int32_t* frame;
     int T, degrees, use_z, limit_box, rebase, seed;
 };
-
-// getOffsetBB for one target, THE box update of both o3d_track_offset_box and o3d_track_offset_box_multi (ref, offset,
-// yaw_state: the target's rows; rebase, seed: the target's; k: the frame) -> box (15) and the updated yaw_state.  The
-// arithmetic is a 3x3 product; carried in double so that the stored fp32 box is the rounded exact result
-__device__ __forceinline__ void offset_box_one(const float* ref, const float* offset, float* yaw_state, int rebase, int degrees,
-                                               int use_z, int limit_box, unsigned seed, unsigned k, float* box) {
-    float off[4] = {offset[0], offset[1], offset[2], offset[3]};
-    const float w = ref[3], l = ref[4], h = ref[5];
-    if (limit_box) {                                  // datasets/points_utils.py:70-76, literally (no abs)
-        if (off[0] > w) off[0] = limit_draw(seed, k, 0u);
-        if (off[1] > fminf(l, 2.f)) off[1] = limit_draw(seed, k, 1u);
-        if (use_z && off[2] > h) off[2] = 0.f;
-    }
-    const double theta = degrees ? (double)off[3] * (3.14159265358979323846 / 180.0) : (double)off[3];
-    double R0[9], yaw = theta;
-    if (yaw_state && !rebase) {
-        for (int i = 0; i < 9; ++i) R0[i] = yaw_state[i];
-        yaw = (double)yaw_state[9] + theta;
-    } else {
-        for (int i = 0; i < 9; ++i) R0[i] = ref[6 + i];
-    }
-    // the reference box's own rotation carries the offset into the world: R = R0 Rz(yaw before the update)
-    double Rr[9];
-    if (yaw_state && !rebase) {
-        double s, c;
-        sincos((double)yaw_state[9], &s, &c);
-        for (int r = 0; r < 3; ++r) {
-            Rr[3 * r] = R0[3 * r] * c + R0[3 * r + 1] * s;
-            Rr[3 * r + 1] = R0[3 * r + 1] * c - R0[3 * r] * s;
-            Rr[3 * r + 2] = R0[3 * r + 2];
-        }
-    } else {
-        for (int i = 0; i < 9; ++i) Rr[i] = R0[i];
-    }
-    const double ox = off[0], oy = off[1], oz = use_z ? (double)off[2] : 0.0;
-    for (int r = 0; r < 3; ++r) box[r] = (float)((double)ref[r] + ((Rr[3 * r] * ox + Rr[3 * r + 1] * oy) + Rr[3 * r + 2] * oz));
-    box[3] = w; box[4] = l; box[5] = h;
-    const float yaw_f = (float)yaw;                   // the stored state: the next update starts from exactly this value
-    double s, c;
-    sincos(yaw_state ? (double)yaw_f : yaw, &s, &c);
-    for (int r = 0; r < 3; ++r) {
-        box[6 + 3 * r] = (float)(R0[3 * r] * c + R0[3 * r + 1] * s);
-        box[6 + 3 * r + 1] = (float)(R0[3 * r + 1] * c - R0[3 * r] * s);
-        box[6 + 3 * r + 2] = (float)R0[3 * r + 2];
-    }
-    if (yaw_state) {
-        if (rebase)
-            for (int i = 0; i < 9; ++i) yaw_state[i] = (float)R0[i];
-        yaw_state[9] = yaw_f;
-    }
-}
 
 // one thread of the launch's 64 works
 __global__ void offset_box_kernel(OffsetArgs a) {
@@ -299,8 +203,6 @@ __global__ void offset_box_kernel(OffsetArgs a) {
 }
 
 // ---- K targets per launch ------------------------------------------------------------------------------------------------------
-constexpr int CROP_MULTI_CHUNK = O3D_CROP_MULTI_CHUNK;      // targets staged in LDS at a time (<= 32: one keep bit each)
-constexpr int CROP_MULTI_WORDS = 18;                        // box (15), scale, offset, mode
 
 struct CropMultiTable {
     const float* points[2]; const o3d_crop_target* targets[2];
@@ -311,92 +213,16 @@ struct CropMultiTable {
 
 template <bool SCATTER>
 __global__ __launch_bounds__(CROP_WG) void crop_multi_kernel(CropMultiTable t, int32_t* __restrict__ scratch) {
-    __shared__ float par[CROP_MULTI_CHUNK][CROP_MULTI_WORDS];
-    __shared__ int wave_cnt[CROP_MULTI_CHUNK][CROP_WG / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = (t.n_groups > 1 && (int)blockIdx.x >= t.wgs[0]) ? 1 : 0;
     const int w = (int)blockIdx.x - (g ? t.wgs[0] : 0);
-    const int K = t.K[g], W = t.wgs[g];
-    const o3d_crop_target* __restrict__ T = t.targets[g];
-    int32_t* __restrict__ S = scratch + t.sbase[g];
-    const int i = w * CROP_WG + tid;
-    const bool in = i < t.n[g];
-    float px = 0.f, py = 0.f, pz = 0.f;
-    if (in) {
-        const float* p = t.points[g] + 3 * (long)i;
-        px = p[0]; py = p[1]; pz = p[2];
-    }
-    for (int k0 = 0; k0 < K; k0 += CROP_MULTI_CHUNK) {
-        const int nc = K - k0 < CROP_MULTI_CHUNK ? K - k0 : CROP_MULTI_CHUNK;
-        __syncthreads();                                   // the previous chunk's readers are done with par / wave_cnt
-        for (int e = tid; e < nc * CROP_MULTI_WORDS; e += CROP_WG) {
-            const int k = e / CROP_MULTI_WORDS, f = e - k * CROP_MULTI_WORDS;
-            const o3d_crop_target& J = T[k0 + k];
-            par[k][f] = f < 15 ? J.box[f] : f == 15 ? J.scale : f == 16 ? J.offset : __int_as_float(J.mode);
-        }
-        __syncthreads();
-        unsigned bits = 0u;                                // bit k: this thread's point survives target k0 + k
-        for (int k = 0; k < nc; ++k) {
-            float qx, qy, qz;
-            const bool keep = in && crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
-            const unsigned long long mask = __ballot(keep);
-            if (lane == 0) wave_cnt[k][wave] = __popcll(mask);
-            if (keep) bits |= 1u << k;
-        }
-        __syncthreads();
-        if (!SCATTER) {
-            if (tid < nc) S[(long)(k0 + tid) * W + w] = (wave_cnt[tid][0] + wave_cnt[tid][1]) + (wave_cnt[tid][2] + wave_cnt[tid][3]);
-            continue;
-        }
-        for (int k = 0; k < nc; ++k) {
-            const bool keep = (bits >> k) & 1u;
-            const unsigned long long mask = __ballot(keep);
-            if (!keep) continue;
-            int pos = S[(long)(k0 + k) * W + w];           // the survivors of the workgroups before this one (launch 2)
-            for (int v = 0; v < wave; ++v) pos += wave_cnt[k][v];
-            pos += __popcll(mask & ((1ull << lane) - 1ull));
-            const o3d_crop_target& J = T[k0 + k];
-            if (pos < J.capacity) {
-                float qx, qy, qz;
-                crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
-                float* o = J.out + 3 * (long)pos;
-                o[0] = qx; o[1] = qy; o[2] = qz;
-            }
-        }
-    }
+    crop_multi_wg<SCATTER>(t.points[g], t.n[g], t.targets[g], t.K[g], t.wgs[g], scratch + t.sbase[g], w);
 }
 
 // one workgroup per (group, target): its row of W counts -> exclusive prefix sums in place, count[0] = the total
 __global__ __launch_bounds__(CROP_WG) void crop_multi_scan_kernel(CropMultiTable t, int32_t* __restrict__ scratch) {
-    __shared__ int wave_sum[CROP_WG / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = (t.n_groups > 1 && (int)blockIdx.x >= t.K[0]) ? 1 : 0;
     const int k = (int)blockIdx.x - (g ? t.K[0] : 0);
-    const int W = t.wgs[g];
-    int32_t* __restrict__ row = scratch + t.sbase[g] + (long)k * W;
-    int carry = 0;
-    for (int w0 = 0; w0 < W; w0 += CROP_WG) {
-        const int w = w0 + tid;
-        const int v = w < W ? row[w] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int u = 0; u < CROP_WG / 64; ++u) {
-            if (u < wave) before += wave_sum[u];
-            total += wave_sum[u];
-        }
-        if (w < W) row[w] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();                                   // wave_sum is rewritten by the next pass
-    }
-    if (tid == 0) t.targets[g][k].count[0] = carry;
+    crop_scan_row(scratch + t.sbase[g] + (long)k * t.wgs[g], t.wgs[g], t.targets[g][k].count);
 }
 
 // resample_kernel's rows for a DEVICE table of jobs: blockIdx.x = the job, its rows strided over blockIdx.y and the threads

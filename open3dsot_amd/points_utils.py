@@ -461,3 +461,97 @@ def points_in_box(box, points, wlh_factor=1.0):
     q = r.t() @ (points.float() - c[:, None])                      # the box frame: x pairs with l, y with w
     half = (torch.stack([s[1], s[0], s[2]]) * float(wlh_factor) * 0.5)[:, None]
     return (q.abs() <= half).all(0)
+
+
+# ---- training batches built on the device (csrc/train_batch.hip; open3dsot_amd/sampler.py is the caller) --------------------
+CROP_MAX_GROUPS = 4096
+TRAIN_MAX_CANDIDATES = 1024
+CROP_PLAN = np.dtype([("points", "u8"), ("n", "i4"), ("targets", "u8"), ("n_targets", "i4"), ("wg_start", "i4"),
+                      ("row_start", "i4"), ("sbase", "i8")], align=True)                       # o3d_crop_plan, 48 bytes
+
+
+class _TrainSampleArgs(ctypes.Structure):    # o3d_train_sample_args
+    _fields_ = [("sel", _vp), ("counts", _vp), ("crop_first", _vp), ("crop_template", _vp), ("crop_search", _vp),
+                ("cap_first", _i), ("cap_template", _i), ("cap_search", _i), ("J", _i), ("B", _i), ("M", _i), ("N", _i),
+                ("idx_t", _vp), ("idx_s", _vp), ("seed", ctypes.c_uint), ("counter", ctypes.c_uint),
+                ("search_box", _vp), ("model_box", _vp), ("cand_box_label", _vp), ("cand_bbox_size", _vp),
+                ("template_points", _vp), ("search_points", _vp), ("seg_label", _vp), ("box_label", _vp), ("bbox_size", _vp),
+                ("bc_boxes", _vp), ("used_t", _vp), ("used_s", _vp)]
+
+
+assert CROP_PLAN.itemsize == 48 and ctypes.sizeof(_TrainSampleArgs) == 192
+capi.register("o3d_track_crop_groups_scratch", [_vp, _i, _vp])
+capi.register("o3d_track_crop_groups", [_vp, _vp, _i, _vp, ctypes.c_long, _vp])
+capi.register("o3d_train_select", [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
+capi.register("o3d_train_labels", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp])
+capi.register("o3d_train_sample", [_vp, _vp])
+
+
+def crop_groups_plan(plan):
+    """The host planner of o3d_track_crop_groups (no device call): fills wg_start / row_start / sbase of the CROP_PLAN array
+    `plan` (points, n, targets, n_targets set by the caller) in place -> (scratch length in int32, workgroups of the count /
+    scatter launches, workgroups of the scan launch).  Raises O3DError on a bad table."""
+    assert plan.dtype == CROP_PLAN and plan.ndim == 1 and plan.flags.c_contiguous
+    grid = (ctypes.c_int * 2)()
+    need = capi.load().o3d_track_crop_groups_scratch(plan.ctypes.data, plan.shape[0], ctypes.addressof(grid))
+    if need < 0:
+        raise capi.O3DError("o3d_track_crop_groups: bad table (1..%d groups of 1..%d targets)" % (CROP_MAX_GROUPS, CROP_MULTI_MAX_TARGETS))
+    return need, grid[0], grid[1]
+
+
+def crop_groups(plan, dev_plan, scratch):
+    """One o3d_track_crop_groups call (three launches, no sync): plan = the planned CROP_PLAN array on the host, dev_plan =
+    its copy on the GPU (a uint8 tensor, or an address), scratch = an int32 GPU tensor of at least crop_groups_plan's length."""
+    dev = scratch.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_crop_groups(
+            plan.ctypes.data, dev_plan.data_ptr() if torch.is_tensor(dev_plan) else int(dev_plan), plan.shape[0], scratch.data_ptr(),
+            scratch.numel(), torch.cuda.current_stream(dev).cuda_stream), "o3d_track_crop_groups")
+
+
+def crop_groups_table(groups, device):
+    """groups: tuples (points (n,3) f32 GPU contiguous, table = a uint8 GPU tensor of o3d_crop_target records) -> (plan, its
+    device copy, scratch length): a blocking upload, for tests and tools; the batch builder fills a pinned buffer."""
+    plan = np.zeros((len(groups),), CROP_PLAN)
+    for g, (pts, tab) in enumerate(groups):
+        assert pts.is_cuda and pts.dtype == torch.float32 and pts.is_contiguous() and pts.dim() == 2 and pts.shape[1] == 3
+        assert tab.is_cuda and tab.dtype == torch.uint8 and tab.is_contiguous() and tab.numel() % CROP_TARGET.itemsize == 0
+        plan[g] = (pts.data_ptr(), pts.shape[0], tab.data_ptr(), tab.numel() // CROP_TARGET.itemsize, 0, 0, 0)
+    need = crop_groups_plan(plan)[0]
+    return plan, torch.from_numpy(plan.view(np.uint8).copy()).to(device), need
+
+
+def train_select(counts, B, caps, sel, n_valid, overflow):
+    """One o3d_train_select launch: counts (J,3) int32 GPU, caps = (cap_first, cap_template, cap_search) -> sel (B,), n_valid
+    (1,), overflow (1,) int32 GPU tensors, written in place"""
+    for t in (counts, sel, n_valid, overflow):
+        _need_gpu(t, "train_select")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    J = counts.numel() // 3
+    assert counts.numel() == 3 * J and sel.numel() >= B
+    dev = counts.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_select(counts.data_ptr(), J, int(B), int(caps[0]), int(caps[1]), int(caps[2]), sel.data_ptr(),
+                                                n_valid.data_ptr(), overflow.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_train_select")
+
+
+def train_labels(gt_search, sample_bb, template_bb, offset, search_box, box_label, bbox_size, model_box):
+    """One o3d_train_labels launch on (J,15) / (J,4) float32 GPU tensors; the last four are written in place"""
+    J = gt_search.numel() // 15
+    for t, width in ((gt_search, 15), (sample_bb, 15), (template_bb, 15), (offset, 4), (search_box, 15), (box_label, 4),
+                     (bbox_size, 3), (model_box, 15)):
+        _need_gpu(t, "train_labels")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == width * J
+    dev = gt_search.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_labels(gt_search.data_ptr(), sample_bb.data_ptr(), template_bb.data_ptr(), offset.data_ptr(), J,
+                                                search_box.data_ptr(), box_label.data_ptr(), bbox_size.data_ptr(), model_box.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "o3d_train_labels")
+
+
+def train_sample(args, device):
+    """One o3d_train_sample launch: args = a filled _TrainSampleArgs (the caller keeps its tensors alive)"""
+    with torch.cuda.device(device):
+        capi.check(capi.load().o3d_train_sample(ctypes.addressof(args), torch.cuda.current_stream(device).cuda_stream),
+                   "o3d_train_sample")

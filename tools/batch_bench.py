@@ -1,0 +1,158 @@
+"""What a training batch costs when it is built on the device (open3dsot_amd/sampler.py), and whether it hides beside the
+training step.  Not bench.py: that measures the step on batches that are already resident.
+
+  python tools/batch_bench.py [--tracklets 16] [--frames 8] [--points 120000] [--batch 48] [--candidates 60]
+                              [--builds 200] [--warmup 20] [--steps 40] [--repeats 3] [--host-batches 2]
+
+Setup: `--tracklets` synth.make_sequence tracklets of `--frames` frames of `--points` points resident in HBM, the BAT data
+config (cfgs/BAT_Car.yaml), the frame choice of DeviceBatchSampler(random_sample=True).  Three measurements, one JSON line:
+  build_ms            device events around `--builds` builds after `--warmup` builds, alone on the device -> pairs/s;
+                      build_host_ms = the median host time of the call itself (what the enqueueing thread spends)
+  host_port_pairs_s   the YARDSTICK: tests/sampler_oracle.py::build, the numpy PORT of the reference's siamese_processing (not
+                      the reference itself), on the host of the same machine, the frames in host memory, same candidates
+  step_ms_resident / step_ms_side / step_ms_inline   DataParallelStep (BAT, captured) fed resident synth batches, against the
+                      same trainer fed builder batches that are built on a side stream while a step runs, against the same
+                      trainer with every batch built on the main stream between two steps; blocks of `--steps` steps, the
+                      three alternated `--repeats` times in the same process (the spread is in the lists)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import sampler_oracle as SO  # noqa: E402
+from open3dsot_amd import dist as D, sampler, synth, trackers  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    for name, default in (("tracklets", 16), ("frames", 8), ("points", 120000), ("batch", 48), ("candidates", 60), ("builds", 200),
+                          ("warmup", 20), ("steps", 40), ("repeats", 3), ("host-batches", 2)):
+        ap.add_argument("--" + name, type=int, default=default)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("batch_bench needs a GPU: nothing here can be measured on the host")
+    dev = torch.device("cuda", 0)
+    B, J = args.batch, args.candidates
+    cfg = dict(sampler.DATA_KEYS)
+    host = [synth.make_sequence(500 + i, args.frames, args.points) for i in range(args.tracklets)]
+    tracklets = sampler.DeviceTracklets([h[0] for h in host], [h[1] for h in host], device=dev)
+    # (make_sequence puts 1/16 of a frame on the target -- 7 500 points of 120 000, far more than a KITTI car -- so the model
+    # crops need more room than the default capacity)
+    builder = sampler.SiameseBatchBuilder(cfg, B, candidates=J, capacity=(8192, 8192, 16384), seed=0)
+    it = sampler.DeviceBatchSampler(tracklets, builder, random_sample=True, seed=0, sample_per_epoch=1 << 30)
+    index = [0]
+
+    def next_samples():
+        s = [it.sample(index[0] + i) for i in range(J)]
+        index[0] += J
+        return s
+
+    # ---- 1. the build alone ---------------------------------------------------------------------------------------------------
+    out = None
+    for _ in range(args.warmup):
+        out = builder.build(next_samples(), out=out)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    frame_bytes = 0
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(args.builds):
+        s = next_samples()
+        frame_bytes += sum(t.frames[f].numel() * 4 for t, f in {(id(x[0]), f): (x[0], f) for x in s for f in x[1:4]}.values())
+        out = builder.build(s, out=out)
+    e1.record()
+    torch.cuda.synchronize()
+    wall_ms = (time.perf_counter() - t0) * 1e3 / args.builds
+    build_ms = e0.elapsed_time(e1) / args.builds
+    n_valid, overflow = int(out["n_valid"][0]), int(out["overflow"][0])
+    host_ms = []                                                 # the host's share: the call alone, the device idle before it
+    for _ in range(20):
+        s = next_samples()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = builder.build(s, out=out)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    torch.cuda.synchronize()
+
+    # ---- 2. the numpy port on the host ----------------------------------------------------------------------------------------------
+    host_map = {id(t): h for t, h in zip(tracklets, host)}
+    t0 = time.perf_counter()
+    for _ in range(args.host_batches):
+        s = next_samples()
+        off_t, off_s = builder.draw_offsets([x[4] for x in s])
+        SO.build(host_map, [(id(x[0]),) + tuple(x[1:]) for x in s], cfg, B, off_t, off_s, builder.caps)
+    host_s = (time.perf_counter() - t0) / args.host_batches
+
+    # ---- 3. the step, fed resident batches against builder batches built beside it -------------------------------------------------
+    torch.manual_seed(0)
+    model = trackers.BAT().to(dev).train()
+    trainer = D.DataParallelStep(model, world=1, graph=True, graph_warmup=2, require_graph=True)
+    extra = {"n_valid": torch.full((1,), B, dtype=torch.int32, device=dev), "overflow": torch.zeros(1, dtype=torch.int32, device=dev)}
+    pool = [dict(synth.to_torch(synth.make_batch(100 + i * B, B), dev), **extra) for i in range(3)]
+    for i in range(8):
+        if trainer.graph is not None and not isinstance(pool[0], D.FlatBatch):
+            pool = [trainer.make_batch(b) for b in pool]
+        trainer.step(pool[i % 3], next_batch=pool[(i + 1) % 3])
+    assert trainer.graph is not None and isinstance(pool[0], D.FlatBatch)
+    built = [trainer.make_batch(dict(b)) for b in pool]          # three more buffers in the captured step's layout
+    side, main = torch.cuda.Stream(), torch.cuda.current_stream()
+    ready = [torch.cuda.Event() for _ in range(3)]
+
+    def build_into(k):
+        side.wait_stream(main)                                   # the step that last read built[k] has been enqueued
+        with torch.cuda.stream(side):
+            builder.build(next_samples(), out=built[k])
+            ready[k].record(side)
+
+    def block(mode):
+        if mode == "side":
+            build_into(0)
+            build_into(1)
+        elif mode == "inline":
+            builder.build(next_samples(), out=built[0])
+            builder.build(next_samples(), out=built[1])
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(args.steps):
+            if mode == "side":
+                build_into((i + 2) % 3)                          # beside step i
+                main.wait_event(ready[(i + 1) % 3])
+                main.wait_event(ready[i % 3])
+                trainer.step(built[i % 3], next_batch=built[(i + 1) % 3])
+            elif mode == "inline":
+                builder.build(next_samples(), out=built[(i + 2) % 3])     # on the main stream, before step i
+                trainer.step(built[i % 3], next_batch=built[(i + 1) % 3])
+            else:
+                trainer.step(pool[i % 3], next_batch=pool[(i + 1) % 3])
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / args.steps
+    times = {"resident": [], "side": [], "inline": []}
+    for mode in times:
+        block(mode)                                              # every route warm
+    for _ in range(args.repeats):
+        for mode in times:
+            times[mode].append(round(block(mode), 4))
+    print(json.dumps({
+        "tool": "batch_bench", "device": torch.cuda.get_device_name(0), "config": "BAT_Car data keys", "batch": B, "candidates": J,
+        "tracklets": args.tracklets, "frames": args.frames, "points": args.points, "capacity": list(builder.caps),
+        "builds": args.builds, "build_ms": round(build_ms, 4), "build_wall_ms": round(wall_ms, 4),
+        "build_host_ms": round(float(sorted(host_ms)[len(host_ms) // 2]), 4),
+        "build_pairs_per_s": round(B / build_ms * 1e3, 1), "frame_mb_per_build": round(frame_bytes / args.builds / 1e6, 1),
+        "frame_gb_per_s": round(frame_bytes / args.builds / build_ms / 1e6, 1), "last_n_valid": n_valid, "last_overflow": overflow,
+        "host_port": "tests/sampler_oracle.py::build (numpy port of the reference's sampler, one process)",
+        "host_port_s_per_batch": round(host_s, 3), "host_port_pairs_per_s": round(B / host_s, 1),
+        "step_ms_resident": times["resident"], "step_ms_side": times["side"], "step_ms_inline": times["inline"],
+        "steps_per_block": args.steps}))
+
+
+if __name__ == "__main__":
+    main()
