@@ -294,7 +294,7 @@ int o3d_pool_fwd_c(const float* Y, long ldp, const float* scale, const float* sh
 
 /* o3d_pool_fwd_c with the tile transposed through LDS (lane = channel, a wave walks one ball's columns: no idle lanes for
  * the small balls the distinct-neighbour layout produces).  cball (ldp) = ball of every column, meta = the live counts of
- * o3d_compact_build; C % 64 == 0, nsample <= 32 (else O3D_EINVAL: use o3d_pool_fwd_c).  Same results. */
+ * o3d_compact_build; C % 32 == 0, nsample <= 32 (else O3D_EINVAL: use o3d_pool_fwd_c).  Same results. */
 int o3d_pool_fwd_ct(const float* Y, long ldp, const float* scale, const float* shift, const int32_t* ball_off,
                     const int32_t* ball_cnt, const int32_t* cball, const int32_t* meta, long start1, int B, int C,
                     int npoint0, int npoint1, int nsample, float* out, int32_t* argq, float* yarg, void* stream);
@@ -321,8 +321,10 @@ int o3d_pool_bwd_dense(const float* dOut0, long sb0, long sc0, const float* dOut
 
 /* The same sums as o3d_group_reduce_c without float atomics: the cloud's columns are sorted by (column chunk,
  * point) once per call (perm: ldp ints; poff: o3d_group_reduce_gather_scratch(...) ints, -1 = shape not covered,
- * use o3d_group_reduce_c) and every sum is a gather from an LDS-staged chunk in a fixed order (bitwise
- * reproducible).  spanmax = npoint*nsample of the largest segment. */
+ * use o3d_group_reduce_c) and the sums are gathers from an LDS-staged chunk.  The ball sums T add up in a fixed order;
+ * the point sums S do not: the order inside a point's list comes from the LDS atomics of the sort, and a thread flushes
+ * each run of equal points with one LDS float atomic, so two runs of the same call may differ in the last bits of S.
+ * spanmax = npoint*nsample of the largest segment. */
 long o3d_group_reduce_gather_scratch(int B, int nseg, int npoint0, int ld0, int npoint1, int ld1, int spanmax);
 int o3d_group_reduce_gather(const float* dN, const float* Y0, long ldp, const float* A1, const float* A2,
                             const float* A3, const int32_t* gp, const float* cw, const int32_t* ball_off,

@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void pool_c_kernel(const float* __restrict__ Y
 // fma and a compare / select per element.  A ball belongs to the 256-column chunk its first column lies in (it may run up
 // to 31 columns into the next chunk: the tile is 160 wide).  Strict `>` over ascending columns keeps the first maximum,
 // as pool_c_kernel does.  Results leave through a second LDS staging so that the stores run along the ball index.
-// C % 64 == 0, balls of at most 32 columns.
+// C % PT_CH == 0 (32), balls of at most 32 columns.
 constexpr int PT_CH = 32, PT_COLS = 128, PT_OVER = 32, PT_LD = PT_COLS + PT_OVER + 3;     // odd stride: conflict-free; +3: the 4-wide reads
 constexpr int PT_RB = 32, PT_RLD = PT_CH + 1;         // balls per output batch; padded row of the result staging
 
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(BT) void reduce_c_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------
 // The same reduce WITHOUT float atomics (tools/exp/reduce_gather_probe.hip: 138.6 vs 297.7 us on the SA1 shape).
 //   csr_build_kernel   per cloud, once per SA call: the cloud's columns sorted by (column chunk, point, column) in
-//                      `perm` (counting sort in LDS, lists sorted -> fixed summation order) and the list starts
+//                      `perm` (counting sort in LDS; the order INSIDE a point's list is whatever the LDS atomics hand out) and the list starts
 //                      poff[cloud][chunk*ld + n] (relative to the cloud's first column), total at [nchunk*ld].
 //   reduce_gather_kernel  per (cloud, CS channels): the chunk's dY staged in LDS with plain stores; thread n
 //                      gathers its own list, thread j sums its ball's contiguous range.
@@ -1298,7 +1298,7 @@ extern "C" int o3d_pool_fwd_c(const float* Y, long ldp, const float* scale, cons
 }
 
 // o3d_pool_fwd_c on the LDS-transposed tile (pool_t_kernel): additionally needs the column -> ball map and the live
-// counts; C % 64 == 0 and balls of at most 32 columns (nsample <= 32), else O3D_EINVAL (use o3d_pool_fwd_c)
+// counts; C % 32 == 0 (PT_CH) and balls of at most 32 columns (nsample <= 32), else O3D_EINVAL (use o3d_pool_fwd_c)
 extern "C" int o3d_pool_fwd_ct(const float* Y, long ldp, const float* scale, const float* shift, const int32_t* ball_off,
                                const int32_t* ball_cnt, const int32_t* cball, const int32_t* meta, long start1, int B, int C,
                                int npoint0, int npoint1, int nsample, float* out, int32_t* argq, float* yarg, void* stream) {
