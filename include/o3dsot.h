@@ -795,6 +795,83 @@ typedef struct {
 } o3d_train_sample_args;
 int o3d_train_sample(const o3d_train_sample_args* args, void* stream);
 
+/* ---- M2-Track training batches (csrc/train_batch.hip): the device form of MotionTrackingSampler + motion_processing
+ * (datasets/sampler.py:82-180,262-288) with apply_augmentation (datasets/points_utils.py:299-361).  Boxes are assumed
+ * yaw-only (rotations about z), as every box of the reference's datasets is: the angle of a box is atan2(R[1][0], R[0][0]).
+ *
+ * An augmentation record: a point p with inside_box(p, box, 1.25) -- the inclusive test of points_in_box: d = p - c, q = R^T d,
+ * |qx| <= (l*1.25)*0.5 and |qy| <= (w*1.25)*0.5 and |qz| <= (h*1.25)*0.5 -- is replaced by A d + c; every other point, and
+ * every point when enabled == 0, is unchanged. */
+typedef struct { int enabled; float box[15]; float A[9]; float c[3]; } o3d_crop_aug;
+
+/* apply_transform for the boxes, one thread per record slot.  gt (K,15), draw (K,6) = (tx, ty, tz, rot in degrees, flip_x,
+ * flip_y; a flip is set when its value is not 0).  Box k, double inside and rounded once:  c' = c + R t,  R' = R Rz(rot)
+ * (flip_x ? Rz(180 deg) : I),  wlh unchanged  -> out_box (K,15).  Its record: enabled = 1, box = gt[k],
+ * A = R Rz(rot) diag(flip_x ? -1 : 1, flip_y ? -1 : 1, 1) R^T,  c = c'.  slot_src (n_slots) int32 | NULL: slot i of `aug`
+ * takes record slot_src[i], or a disabled record (all zero) when slot_src[i] < 0, so that the records land in the order of
+ * the crop's target tables; NULL: n_slots == K and slot i takes record i.  out_box[k] is written by the slot that takes
+ * record k.  1 <= K, n_slots <= 3 * O3D_TRAIN_MAX_CANDIDATES. */
+int o3d_train_augment(const float* gt, const float* draw, const int32_t* slot_src, int K, int n_slots, float* out_box,
+                      o3d_crop_aug* aug, void* stream);
+
+/* o3d_track_crop_groups with an optional augmentation record per target.  dev_aug: a DEVICE array of n_groups pointers |
+ * NULL (= every entry NULL); entry g points at the n_targets records of group g, or is NULL.  The point is loaded once; a
+ * target whose record is enabled tests and writes the replaced point.  Same three launches, same planner
+ * (o3d_track_crop_groups_scratch), same validation before any HIP call.  With every record NULL or disabled, rows and counts
+ * are bit-identical to o3d_track_crop_groups. */
+int o3d_track_crop_groups_aug(const o3d_crop_plan* groups, const o3d_crop_plan* dev_groups, const o3d_crop_aug* const* dev_aug,
+                              int n_groups, int32_t* scratch, long scratch_len, void* stream);
+
+/* inside_box for n points against ONE box: mask (n) int32 = 1 | 0.  The device function the augmentation mask and the motion
+ * seg_label use, as an entry of its own (points_utils.points_in_box; tests). */
+int o3d_train_inside_box(const float* points, int n, const float* box, float factor, int32_t* mask, void* stream);
+
+/* The per-candidate labels of motion_processing (datasets/sampler.py:122-158), one thread per candidate, double inside and
+ * rounded once.  prev_gt, this_gt (J,15): the two frames' boxes (augmented or not); ref_box (J,15) = getOffsetBB(prev_gt).
+ * this_box (J,15) = transform_box(this_gt, ref_box), prev_box (J,15) = transform_box(prev_gt, ref_box), canon_box (J,15) =
+ * centre 0, the wlh of prev_gt, identity; with motion_box = transform_box(this_box, prev_box): box_label (J,4) = (centre of
+ * this_box, theta), box_label_prev, motion_label likewise; theta = atan2(R[1][0], R[0][0]), times 180/pi when `degrees` (the
+ * reference's orientation.radians * orientation.axis[-1] for a yaw-only box away from +-pi); motion_state (J) int32 =
+ * |c_this - c_prev| > motion_threshold; bbox_size (J,3) = the wlh of this_gt. */
+int o3d_train_motion_labels(const float* prev_gt, const float* this_gt, const float* ref_box, int J, int degrees,
+                            float motion_threshold, float* this_box, float* prev_box, float* canon_box, float* box_label,
+                            float* box_label_prev, float* motion_label, int32_t* motion_state, float* bbox_size, void* stream);
+
+/* o3d_train_select for motion batches.  counts (J,3) = (points of the un-augmented previous frame inside the un-augmented
+ * previous box, previous crop, current crop), before truncation; candidate j is valid iff counts[j][0] > 10 and counts[j][2] >
+ * 20 (datasets/sampler.py:99,120); overflow = the truncated previous and current crops among the chosen rows.
+ * DEVIATION: the in-box count comes from the crop (a count-only target: scale 1, offset 0), whose test is strict where
+ * points_in_box is inclusive; the two differ only for a point exactly on a face. */
+int o3d_train_select_motion(const int32_t* counts, int J, int B, int cap_prev, int cap_this, int32_t* sel, int32_t* n_valid,
+                            int32_t* overflow, void* stream);
+
+/* Sample, gather and label, grid (ceil(2N / 256), B).  Output row r takes candidate j = sel[r].  Rows i < N gather from
+ * crop_prev[j] (min(counts[j][1], cap_prev) rows), rows i >= N from crop_this[j] (min(counts[j][2], cap_this) rows); idx_prev /
+ * idx_this (J,N) int32 | NULL (both or neither): the indices, NULL: o3d_train_sample's draw keyed by (seed, counter, j, cloud,
+ * row), cloud 0 = previous, 1 = current.  A half of n <= 2 rows, or an index outside [0, n), gives a zero xyz.  points (B,2N,5)
+ * and candidate_bc (B,2N,9) | NULL are o3d_track_motion_input's row for the gathered xyz, the wlh of canon_box[j] and
+ * first_frame = (candidate_id[j] == 0); seg_label (B,2N) int64 = inside_box(xyz, prev_box[j], 1.25) on the previous half,
+ * inside_box(xyz, this_box[j], 1.25) on the current half.  Row r of box_label, box_label_prev, motion_label (B,4),
+ * motion_state_label (B) int64, bbox_size (B,3) is candidate j's.  With bc_boxes ([2][centre (B,3) | wlh (B,3) | rotation
+ * (B,9)], [0] = prev_box, [1] = this_box; | NULL), xyz_halves (2,B,N,3) receives the xyz of the two halves, the operands of
+ * the two o3d_boxcloud calls that follow.  sel[r] < 0: every output of row r is zero.  used_prev / used_this (B,N) int32 |
+ * NULL: the indices used (-1: zero xyz). */
+typedef struct {
+    const int32_t* sel; const int32_t* counts;
+    const float* crop_prev; const float* crop_this;
+    int cap_prev, cap_this, J, B, N;
+    const int32_t* idx_prev; const int32_t* idx_this; const int32_t* candidate_id;
+    unsigned seed, counter;
+    const float* prev_box; const float* this_box; const float* canon_box;
+    const float* cand_box_label; const float* cand_box_label_prev; const float* cand_motion_label;
+    const int32_t* cand_motion_state; const float* cand_bbox_size;
+    float* points; float* candidate_bc; int64_t* seg_label;
+    float* box_label; float* box_label_prev; float* motion_label; int64_t* motion_state_label; float* bbox_size;
+    float* bc_boxes; float* xyz_halves;
+    int32_t* used_prev; int32_t* used_this;
+} o3d_train_motion_sample_args;
+int o3d_train_motion_sample(const o3d_train_motion_sample_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,8 +61,9 @@
 // Within a launch no workgroup reads a word that another workgroup of that launch writes; the order between the launches is
 // the stream's.  There is no flag, no atomic and no loop that waits.  Every (point, target) decision is made by crop_test, the
 // one function that o3d_track_crop calls too, with no early rejection: rows and counts equal o3d_track_crop's.
-// crop_test, gather_row, offset_box_one and the workgroup bodies of the three launches (crop_multi_wg, crop_scan_row) live in
-// track_common.hpp: csrc/train_batch.hip (o3d_track_crop_groups, o3d_train_sample) calls the same definitions.
+// crop_test, gather_row, offset_box_one, inside_box, the keyed index draw and the workgroup bodies of the three launches
+// (crop_multi_wg, crop_scan_row) live in track_common.hpp: csrc/train_batch.hip (o3d_track_crop_groups[_aug], o3d_train_sample)
+// calls the same definitions.  motion_row is defined here, and so is its third caller, o3d_train_motion_sample.
 #include "track_common.hpp"
 
 namespace {
@@ -281,6 +282,70 @@ __global__ __launch_bounds__(256) void motion_input_multi_kernel(const o3d_motio
     motion_row(x, y, z, half, wlh + 3 * (long)k, first_frame, points + 5 * row, bc ? bc + 9 * row : nullptr);
 }
 
+static_assert(sizeof(o3d_train_motion_sample_args) == 248, "o3d_train_motion_sample_args: points_utils._TrainMotionSampleArgs mirrors this layout");
+// ---- o3d_train_motion_sample (the training-batch form of the motion input, sampler.MotionBatchBuilder: it lives here, beside
+// motion_row, so that the row arithmetic keeps its one definition; the draw and inside_box are track_common.hpp's) -----------------
+__global__ __launch_bounds__(256) void train_motion_sample_kernel(o3d_train_motion_sample_args a) {
+    const int r = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int N = a.N, B = a.B;
+    const int j = a.sel[r];
+    const bool live = j >= 0 && j < a.J;
+    if (blockIdx.x == 0) {                                 // the rows of the per-candidate labels that the batch takes
+        for (int e = threadIdx.x; e < 46; e += 256) {
+            if (e < 4) a.box_label[4 * (long)r + e] = live ? a.cand_box_label[4 * (long)j + e] : 0.f;
+            else if (e < 8) a.box_label_prev[4 * (long)r + (e - 4)] = live ? a.cand_box_label_prev[4 * (long)j + (e - 4)] : 0.f;
+            else if (e < 12) a.motion_label[4 * (long)r + (e - 8)] = live ? a.cand_motion_label[4 * (long)j + (e - 8)] : 0.f;
+            else if (e < 15) a.bbox_size[3 * (long)r + (e - 12)] = live ? a.cand_bbox_size[3 * (long)j + (e - 12)] : 0.f;
+            else if (e == 15) a.motion_state_label[r] = live ? (int64_t)a.cand_motion_state[j] : 0;
+            else if (a.bc_boxes) {
+                const int which = e < 31 ? 0 : 1, f = e - (which ? 31 : 16);      // f: the field of the (15) box
+                const float v = live ? (which ? a.this_box : a.prev_box)[15 * (long)j + f] : 0.f;
+                float* o = a.bc_boxes + (long)which * 15 * B;
+                if (f < 3) o[3 * (long)r + f] = v;
+                else if (f < 6) o[3 * (long)B + 3 * (long)r + (f - 3)] = v;
+                else o[6 * (long)B + 9 * (long)r + (f - 6)] = v;
+            }
+        }
+    }
+    if (i >= 2 * N) return;
+    const int half = i >= N ? 1 : 0, ih = i - half * N;
+    const long row = (long)r * (2 * (long)N) + i;
+    float* o = a.points + 5 * row;
+    float* bc = a.candidate_bc ? a.candidate_bc + 9 * row : nullptr;
+    float* xyz = a.xyz_halves ? a.xyz_halves + 3 * (((long)half * B + r) * N + ih) : nullptr;
+    int32_t* used = half ? a.used_this : a.used_prev;
+    if (!live) {
+        for (int e = 0; e < 5; ++e) o[e] = 0.f;
+        if (bc) for (int e = 0; e < 9; ++e) bc[e] = 0.f;
+        if (xyz) { xyz[0] = 0.f; xyz[1] = 0.f; xyz[2] = 0.f; }
+        a.seg_label[row] = 0;
+        if (used) used[(long)r * N + ih] = -1;
+        return;
+    }
+    const int cap = half ? a.cap_this : a.cap_prev;
+    const int n = min(a.counts[3 * (long)j + 1 + half], cap);
+    int s = -1;
+    if (n > 2) {
+        const int32_t* given = half ? a.idx_this : a.idx_prev;
+        if (given) {
+            s = given[(long)j * N + ih];
+        } else {
+            const unsigned key = mix32((a.seed * 0x9E3779B1u) ^
+                                       (a.counter * 0x85EBCA77u + (unsigned)j * 0xC2B2AE3Du + (unsigned)half * 0x27D4EB2Fu + 0x165667B1u));
+            s = sample_index(key, ih, n, N);
+        }
+        if ((unsigned)s >= (unsigned)n) s = -1;
+    }
+    const float* src = (half ? a.crop_this : a.crop_prev) + 3 * (long)j * cap;
+    float px, py, pz;
+    gather_row(src, n, &s, 0, s < 0, px, py, pz);
+    motion_row(px, py, pz, half, a.canon_box + 15 * (long)j + 3, a.candidate_id[j] == 0, o, bc);
+    if (xyz) { xyz[0] = px; xyz[1] = py; xyz[2] = pz; }
+    float dx, dy, dz;
+    a.seg_label[row] = inside_box(px, py, pz, (half ? a.this_box : a.prev_box) + 15 * (long)j, 1.25f, dx, dy, dz) ? 1 : 0;
+    if (used) used[(long)r * N + ih] = s;
+}
+
 }  // namespace
 
 extern "C" long o3d_track_crop_scratch(const o3d_crop_job* jobs, int n_jobs) {
@@ -442,5 +507,21 @@ extern "C" int o3d_track_motion_input_multi(const o3d_motion_job* jobs, int K, i
     if (!jobs || !wlh || !points || K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || N < 1 || N > (1 << 20)) return O3D_EINVAL;
     hipLaunchKernelGGL(motion_input_multi_kernel, dim3(o3d_cdiv(2 * N, 256), K), dim3(256), 0, o3d_stream(stream), jobs, N, wlh,
                        first_frame != 0, points, candidate_bc);
+    return o3d_launch_status();
+}
+
+// Sample, gather and label for M2-Track training batches (include/o3dsot.h states the contract; the other kernels of a batch are
+// csrc/train_batch.hip's)
+extern "C" int o3d_train_motion_sample(const o3d_train_motion_sample_args* args, void* stream) {
+    if (!args) return O3D_EINVAL;
+    const o3d_train_motion_sample_args& a = *args;
+    if (!a.sel || !a.counts || !a.crop_prev || !a.crop_this || a.cap_prev < 0 || a.cap_this < 0 || a.cap_prev > (1 << 29) ||
+        a.cap_this > (1 << 29) || a.J < 1 || a.J > O3D_TRAIN_MAX_CANDIDATES || a.B < 1 || a.B > a.J || a.N < 1 || a.N > (1 << 20) ||
+        (a.idx_prev == nullptr) != (a.idx_this == nullptr) || !a.candidate_id || !a.prev_box || !a.this_box || !a.canon_box ||
+        !a.cand_box_label || !a.cand_box_label_prev || !a.cand_motion_label || !a.cand_motion_state || !a.cand_bbox_size || !a.points ||
+        !a.seg_label || !a.box_label || !a.box_label_prev || !a.motion_label || !a.motion_state_label || !a.bbox_size ||
+        (a.bc_boxes != nullptr) != (a.xyz_halves != nullptr))
+        return O3D_EINVAL;
+    hipLaunchKernelGGL(train_motion_sample_kernel, dim3(o3d_cdiv(2 * a.N, 256), a.B), dim3(256), 0, o3d_stream(stream), a);
     return o3d_launch_status();
 }

@@ -46,6 +46,46 @@ __device__ __forceinline__ void gather_row(const float* src, int n_src, const in
     }
 }
 
+// the inclusive test of points_in_box (nuscenes geometry_utils) for the point p against `box` (15) scaled by `factor`:
+// d = p - c, q = R^T d in crop_test's operation order, then |qx| <= (l*factor)*0.5 and |qy| <= (w*factor)*0.5 and |qz| <=
+// (h*factor)*0.5.  THE test of the augmentation mask (crop_multi_wg<.., true>) and of both seg_label halves of
+// o3d_train_motion_sample; d is returned for the caller that transforms the point
+__device__ __forceinline__ bool inside_box(float px, float py, float pz, const float* box, float factor, float& dx, float& dy, float& dz) {
+    dx = px - box[0]; dy = py - box[1]; dz = pz - box[2];
+    const float w = box[3], l = box[4], h = box[5];
+    const float* R = box + 6;
+    const float qx = (R[0] * dx + R[3] * dy) + R[6] * dz;
+    const float qy = (R[1] * dx + R[4] * dy) + R[7] * dz;
+    const float qz = (R[2] * dx + R[5] * dy) + R[8] * dz;
+    return fabsf(qx) <= (l * factor) * 0.5f && fabsf(qy) <= (w * factor) * 0.5f && fabsf(qz) <= (h * factor) * 0.5f;
+}
+
+// ---- the keyed index draw of o3d_train_sample and o3d_train_motion_sample (train_batch.hip writes it down) ------------------------
+__device__ __forceinline__ unsigned mix32(unsigned x) {
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+
+// the draw of the header comment: row i of a cloud of n > 2 rows resampled to S rows
+__device__ __forceinline__ int sample_index(unsigned key, int i, int n, int S) {
+    if (n == S) return i;
+    if (S > n) return (int)__umulhi(mix32(key ^ ((unsigned)i * 0x9E3779B1u + 0x85EBCA77u)), (unsigned)n);
+    const int b = 32 - __clz(n - 1), h = (b + 1) >> 1;
+    const unsigned mask = (1u << h) - 1u;
+    unsigned x = (unsigned)i;
+    do {
+        unsigned L = x >> h, R = x & mask;
+#pragma unroll
+        for (unsigned round = 0; round < 4u; ++round) {
+            const unsigned f = mix32(key ^ (R * 0x9E3779B1u + round * 0x85EBCA77u + 0xC2B2AE3Du)) & mask;
+            const unsigned t = L ^ f;
+            L = R; R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= (unsigned)n);
+    return (int)x;
+}
+
 // counter-based draw from U[-1, 1): a 32-bit mix of (seed, frame, component) (the finaliser of MurmurHash3), its top 24 bits
 __device__ __forceinline__ float limit_draw(unsigned seed, unsigned frame, unsigned comp) {
     unsigned x = seed * 0x9E3779B1u ^ (frame * 0x85EBCA77u + comp * 0xC2B2AE3Du + 0x27D4EB2Fu);
@@ -107,15 +147,33 @@ __device__ __forceinline__ void offset_box_one(const float* ref, const float* of
 // ---- one cloud against K targets (o3d_track_crop_multi, o3d_track_crop_groups) ---------------------------------------------------
 constexpr int CROP_MULTI_CHUNK = O3D_CROP_MULTI_CHUNK;      // targets staged in LDS at a time (<= 32: one keep bit each)
 constexpr int CROP_MULTI_WORDS = 18;                        // box (15), scale, offset, mode
+constexpr int CROP_AUG_WORDS = 28;                          // o3d_crop_aug: enabled, box (15), A (9), c' (3)
+static_assert(sizeof(o3d_crop_aug) == 4 * CROP_AUG_WORDS, "o3d_crop_aug: points_utils.CROP_AUG mirrors this layout");
+
+// the point a target with the staged augmentation record `a` (CROP_AUG_WORDS words) sees in place of p: a point inside the
+// record's box scaled by 1.25 becomes p'_i = ((A_i0*dx + A_i1*dy) + A_i2*dz) + c'_i with d = p - c, every other point and
+// every point of a disabled record stays p (train_batch.hip writes the order down)
+__device__ __forceinline__ void aug_point(const float* a, float& x, float& y, float& z) {
+    if (__float_as_int(a[0]) == 0) return;
+    float dx, dy, dz;
+    if (!inside_box(x, y, z, a + 1, 1.25f, dx, dy, dz)) return;
+    const float* A = a + 16;
+    const float* c = a + 25;
+    x = ((A[0] * dx + A[1] * dy) + A[2] * dz) + c[0];
+    y = ((A[3] * dx + A[4] * dy) + A[5] * dz) + c[1];
+    z = ((A[6] * dx + A[7] * dy) + A[8] * dz) + c[2];
+}
 
 // Workgroup w of a group (the cloud `points` (n,3), the DEVICE table T of K targets, W = crop_wgs(n), S = the group's K rows
 // of W int32 in scratch): the count pass (SCATTER false: S[k][w] = this workgroup's survivors of target k) or the scatter
 // pass (SCATTER true: S[k][w] holds the survivors of the workgroups before this one).  THE body of both crop_multi_kernel
-// and crop_groups_kernel; every argument is the same for all threads of the workgroup
-template <bool SCATTER>
+// and crop_groups_kernel; every argument is the same for all threads of the workgroup.  AUG (o3d_track_crop_groups_aug): A =
+// the group's K augmentation records | NULL, staged beside par; target k tests and writes aug_point(A[k], p) in place of p
+template <bool SCATTER, bool AUG = false>
 __device__ __forceinline__ void crop_multi_wg(const float* __restrict__ points, int n, const o3d_crop_target* __restrict__ T, int K, int W,
-                                              int32_t* __restrict__ S, int w) {
+                                              int32_t* __restrict__ S, int w, const o3d_crop_aug* __restrict__ A = nullptr) {
     __shared__ float par[CROP_MULTI_CHUNK][CROP_MULTI_WORDS];
+    __shared__ float aug[AUG ? CROP_MULTI_CHUNK : 1][CROP_AUG_WORDS];
     __shared__ int wave_cnt[CROP_MULTI_CHUNK][CROP_WG / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = w * CROP_WG + tid;
@@ -133,11 +191,22 @@ __device__ __forceinline__ void crop_multi_wg(const float* __restrict__ points, 
             const o3d_crop_target& J = T[k0 + k];
             par[k][f] = f < 15 ? J.box[f] : f == 15 ? J.scale : f == 16 ? J.offset : __int_as_float(J.mode);
         }
+        if constexpr (AUG) {
+            const float* src = reinterpret_cast<const float*>(A ? A + k0 : nullptr);      // the records are 28 words each
+            for (int e = tid; e < nc * CROP_AUG_WORDS; e += CROP_WG) (&aug[0][0])[e] = src ? src[e] : 0.f;      // zero: disabled
+        }
         __syncthreads();
         unsigned bits = 0u;                                // bit k: this thread's point survives target k0 + k
         for (int k = 0; k < nc; ++k) {
             float qx, qy, qz;
-            const bool keep = in && crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
+            bool keep;
+            if constexpr (AUG) {
+                float x = px, y = py, z = pz;
+                aug_point(aug[k], x, y, z);
+                keep = in && crop_test(x, y, z, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
+            } else {
+                keep = in && crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
+            }
             const unsigned long long mask = __ballot(keep);
             if (lane == 0) wave_cnt[k][wave] = __popcll(mask);
             if (keep) bits |= 1u << k;
@@ -157,7 +226,13 @@ __device__ __forceinline__ void crop_multi_wg(const float* __restrict__ points, 
             const o3d_crop_target& J = T[k0 + k];
             if (pos < J.capacity) {
                 float qx, qy, qz;
-                crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
+                if constexpr (AUG) {
+                    float x = px, y = py, z = pz;
+                    aug_point(aug[k], x, y, z);
+                    crop_test(x, y, z, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
+                } else {
+                    crop_test(px, py, pz, par[k], par[k][15], par[k][16], __float_as_int(par[k][17]), qx, qy, qz);
+                }
                 float* o = J.out + 3 * (long)pos;
                 o[0] = qx; o[1] = qy; o[2] = qz;
             }

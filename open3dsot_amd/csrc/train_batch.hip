@@ -10,8 +10,29 @@
 //                           (getModel), seg_label, and the rows of the per-candidate labels that the batch takes
 //   o3d_boxcloud (boxcloud.hip)             points2cc_dist_t / _s (BAT)
 //
-// Every keep decision (the crops and seg_label) is crop_test, every row gather gather_row: the definitions of
+// and for M2-Track (datasets/sampler.py:82-180 motion_processing with apply_augmentation, datasets/points_utils.py:299-361):
+//   o3d_train_augment           apply_transform for the boxes of both frames of every candidate, and the records by which the
+//                               crop moves the points (K = 2J)
+//   o3d_track_offset_box_multi  the jittered reference box of every candidate (K = J)
+//   o3d_train_motion_labels     the three transform_box, the three labels, motion_state_label, bbox_size
+//   o3d_track_crop_groups_aug   both crops of every candidate and the in-box count of its previous frame; a target with an
+//                               enabled record sees the augmented point
+//   o3d_train_select_motion     which candidates fill the batch (sampler.py:99,120)
+//   o3d_train_motion_sample     (track.hip, beside motion_row) regularize_pc of both halves, the row's channels, seg_label, the label rows
+//   o3d_boxcloud (2)            prev_bc, this_bc
+//
+// Every keep decision (the crops and seg_label) is crop_test or inside_box, every row gather gather_row: the definitions of
 // track_common.hpp, which track.hip uses.  This file is compiled with -ffp-contract=off like track.hip.
+//
+// ---- the augmented point's fp32 operation order (aug_point, track_common.hpp; tests/motion_sampler_oracle.py restates it) -----------
+// A record holds enabled, the un-augmented box (c, wlh, R), A (3x3 row-major) and c'.  For the point p and an enabled record:
+//   d  = p - c                                    dx = px - cx, dy = py - cy, dz = pz - cz
+//   q  = R^T d                                    qx = ((R00*dx + R10*dy) + R20*dz), qy, qz as in the crop (track.hip)
+//   inside (inclusive: points_in_box, 1.25)       |qx| <= ((l*1.25)*0.5)  and  |qy| <= ((w*1.25)*0.5)  and  |qz| <= ((h*1.25)*0.5)
+//   inside:  p'_i = (((A_i0*dx + A_i1*dy) + A_i2*dz) + c'_i)          otherwise p' = p
+// The crop of that target is crop_test(p') with the operation order of track.hip.  A and c' are computed once per record in
+// double and rounded once (o3d_train_augment): A = R Rz(rot) diag(fx, fy, 1) R^T, c' = c + R t.
+// seg_label of a motion batch is inside_box(row, box, 1.25) in the same order, with the row's xyz as p.
 //
 // ---- o3d_track_crop_groups: G clouds, three launches, no workgroup ever waits for another -------------------------------------------
 // The host knows every n and plans the table (o3d_track_crop_groups_scratch): group g owns workgroups [wg_start, wg_start +
@@ -53,6 +74,7 @@
 static_assert(sizeof(o3d_crop_target) == 48, "o3d_crop_target: points_utils.CROP_TARGET mirrors this layout");
 static_assert(sizeof(o3d_crop_plan) == 48, "o3d_crop_plan: points_utils.CROP_PLAN mirrors this layout");
 static_assert(sizeof(o3d_train_sample_args) == 192, "o3d_train_sample_args: points_utils._TrainSampleArgs mirrors this layout");
+static_assert(sizeof(o3d_crop_aug) == 112, "o3d_crop_aug: points_utils.CROP_AUG mirrors this layout");
 
 namespace {
 
@@ -67,12 +89,16 @@ __device__ __forceinline__ int crop_group_of(const o3d_crop_plan* __restrict__ G
     return lo;
 }
 
-template <bool SCATTER>
-__global__ __launch_bounds__(CROP_WG) void crop_groups_kernel(const o3d_crop_plan* __restrict__ G, int n_groups, int32_t* __restrict__ scratch) {
-    const o3d_crop_plan g = G[crop_group_of<false>(G, n_groups, (int)blockIdx.x)];
+// AUG (o3d_track_crop_groups_aug): aug[group] = the group's augmentation records | NULL; aug itself may be NULL
+template <bool SCATTER, bool AUG = false>
+__global__ __launch_bounds__(CROP_WG) void crop_groups_kernel(const o3d_crop_plan* __restrict__ G, int n_groups, int32_t* __restrict__ scratch,
+                                                              const o3d_crop_aug* const* __restrict__ aug = nullptr) {
+    const int gi = crop_group_of<false>(G, n_groups, (int)blockIdx.x);
+    const o3d_crop_plan g = G[gi];
     const int W = g.n > 0 ? (g.n + CROP_WG - 1) / CROP_WG : 1, w = (int)blockIdx.x - g.wg_start;
     if (w < 0 || w >= W) return;                           // a device table that disagrees with the planned grid: nothing is touched
-    crop_multi_wg<SCATTER>(g.points, g.n, g.targets, g.n_targets, W, scratch + g.sbase, w);
+    if (AUG) crop_multi_wg<SCATTER, true>(g.points, g.n, g.targets, g.n_targets, W, scratch + g.sbase, w, aug ? aug[gi] : nullptr);
+    else crop_multi_wg<SCATTER>(g.points, g.n, g.targets, g.n_targets, W, scratch + g.sbase, w);
 }
 
 __global__ __launch_bounds__(CROP_WG) void crop_groups_scan_kernel(const o3d_crop_plan* __restrict__ G, int n_groups, int32_t* __restrict__ scratch) {
@@ -85,6 +111,8 @@ __global__ __launch_bounds__(CROP_WG) void crop_groups_scan_kernel(const o3d_cro
 // ---- o3d_train_select -----------------------------------------------------------------------------------------------------------------
 constexpr int SELECT_WG = O3D_TRAIN_MAX_CANDIDATES;        // one thread per candidate
 
+// MOTION (o3d_train_select_motion): counts = (in-box, previous crop, current crop); cap0 is not used
+template <bool MOTION>
 __global__ __launch_bounds__(SELECT_WG) void train_select_kernel(const int32_t* __restrict__ counts, int J, int B, int cap0, int cap1, int cap2,
                                                                  int32_t* __restrict__ sel, int32_t* __restrict__ n_valid,
                                                                  int32_t* __restrict__ overflow) {
@@ -93,7 +121,7 @@ __global__ __launch_bounds__(SELECT_WG) void train_select_kernel(const int32_t* 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int c0 = 0, c1 = 0, c2 = 0;
     if (tid < J) { c0 = counts[3 * tid]; c1 = counts[3 * tid + 1]; c2 = counts[3 * tid + 2]; }
-    const bool valid = tid < J && c0 + c1 > 20 && c2 > 20;
+    const bool valid = tid < J && (MOTION ? c0 > 10 : c0 + c1 > 20) && c2 > 20;
     const unsigned long long mask = __ballot(valid);
     if (lane == 0) wave_tot[wave] = __popcll(mask);
     __syncthreads();
@@ -108,7 +136,7 @@ __global__ __launch_bounds__(SELECT_WG) void train_select_kernel(const int32_t* 
     if (tid < B) {
         const int j = nv > 0 ? list[tid % nv] : -1;
         sel[tid] = j;
-        if (j >= 0) over = (counts[3 * j] > cap0) + (counts[3 * j + 1] > cap1) + (counts[3 * j + 2] > cap2);
+        if (j >= 0) over = (MOTION ? 0 : counts[3 * j] > cap0) + (counts[3 * j + 1] > cap1) + (counts[3 * j + 2] > cap2);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) over += __shfl_xor(over, off, 64);
@@ -154,31 +182,6 @@ __global__ __launch_bounds__(256) void train_labels_kernel(LabelArgs a) {
 }
 
 // ---- o3d_train_sample -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned mix32(unsigned x) {
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
-
-// the draw of the header comment: row i of a cloud of n > 2 rows resampled to S rows
-__device__ __forceinline__ int sample_index(unsigned key, int i, int n, int S) {
-    if (n == S) return i;
-    if (S > n) return (int)__umulhi(mix32(key ^ ((unsigned)i * 0x9E3779B1u + 0x85EBCA77u)), (unsigned)n);
-    const int b = 32 - __clz(n - 1), h = (b + 1) >> 1;
-    const unsigned mask = (1u << h) - 1u;
-    unsigned x = (unsigned)i;
-    do {
-        unsigned L = x >> h, R = x & mask;
-#pragma unroll
-        for (unsigned round = 0; round < 4u; ++round) {
-            const unsigned f = mix32(key ^ (R * 0x9E3779B1u + round * 0x85EBCA77u + 0xC2B2AE3Du)) & mask;
-            const unsigned t = L ^ f;
-            L = R; R = t;
-        }
-        x = (L << h) | R;
-    } while (x >= (unsigned)n);
-    return (int)x;
-}
-
 __global__ __launch_bounds__(256) void train_sample_kernel(o3d_train_sample_args a) {
     const int r = blockIdx.y, cloud = blockIdx.z, i = blockIdx.x * 256 + threadIdx.x;
     const int S = cloud ? a.N : a.M;
@@ -245,6 +248,118 @@ __global__ __launch_bounds__(256) void train_sample_kernel(o3d_train_sample_args
     if (used) used[row] = s;
 }
 
+// ---- o3d_train_augment ----------------------------------------------------------------------------------------------------------------
+struct AugmentArgs { const float* gt; const float* draw; const int32_t* slot_src; int K, n_slots; float* out_box; o3d_crop_aug* aug; };
+
+__global__ __launch_bounds__(256) void train_augment_kernel(AugmentArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_slots) return;
+    const int k = a.slot_src ? a.slot_src[i] : i;
+    o3d_crop_aug rec;
+    if (k < 0 || k >= a.K) {                               // a disabled record: all zero
+        rec.enabled = 0;
+        for (int e = 0; e < 15; ++e) rec.box[e] = 0.f;
+        for (int e = 0; e < 9; ++e) rec.A[e] = 0.f;
+        for (int e = 0; e < 3; ++e) rec.c[e] = 0.f;
+        a.aug[i] = rec;
+        return;
+    }
+    const float* gt = a.gt + 15 * (long)k;
+    const float* dr = a.draw + 6 * (long)k;
+    double R[9], t[3] = {dr[0], dr[1], dr[2]};
+    for (int e = 0; e < 9; ++e) R[e] = gt[6 + e];
+    double s, c;
+    sincos((double)dr[3] * (3.14159265358979323846 / 180.0), &s, &c);
+    const double fx = dr[4] != 0.f ? -1.0 : 1.0, fy = dr[5] != 0.f ? -1.0 : 1.0;
+    // M = R Rz(rot): column 0 = c R0 + s R1, column 1 = -s R0 + c R1, column 2 = R2 (R0, R1, R2: the columns of R)
+    double M[9];
+    for (int r = 0; r < 3; ++r) {
+        M[3 * r] = R[3 * r] * c + R[3 * r + 1] * s;
+        M[3 * r + 1] = R[3 * r + 1] * c - R[3 * r] * s;
+        M[3 * r + 2] = R[3 * r + 2];
+    }
+    float* o = a.out_box + 15 * (long)k;
+    rec.enabled = 1;
+    for (int r = 0; r < 3; ++r) {
+        const float cr = (float)((double)gt[r] + ((R[3 * r] * t[0] + R[3 * r + 1] * t[1]) + R[3 * r + 2] * t[2]));
+        o[r] = cr;
+        rec.c[r] = cr;
+        o[3 + r] = gt[3 + r];
+        // the box: M Rz(180 deg) for flip_x = M diag(-1, -1, 1), exactly
+        o[6 + 3 * r] = (float)(fx * M[3 * r]);
+        o[6 + 3 * r + 1] = (float)(fx * M[3 * r + 1]);
+        o[6 + 3 * r + 2] = (float)M[3 * r + 2];
+        // the points: A = M diag(fx, fy, 1) R^T
+        for (int q = 0; q < 3; ++q)
+            rec.A[3 * r + q] = (float)(((fx * M[3 * r]) * R[3 * q] + (fy * M[3 * r + 1]) * R[3 * q + 1]) + M[3 * r + 2] * R[3 * q + 2]);
+    }
+    for (int e = 0; e < 15; ++e) rec.box[e] = gt[e];
+    a.aug[i] = rec;
+}
+
+// ---- o3d_train_inside_box -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void train_inside_box_kernel(const float* __restrict__ points, int n, const float* __restrict__ box,
+                                                               float factor, int32_t* __restrict__ mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float dx, dy, dz;
+    mask[i] = inside_box(points[3 * (long)i], points[3 * (long)i + 1], points[3 * (long)i + 2], box, factor, dx, dy, dz) ? 1 : 0;
+}
+
+// ---- o3d_train_motion_labels ----------------------------------------------------------------------------------------------------------
+struct MotionLabelArgs {
+    const float* prev_gt; const float* this_gt; const float* ref_box; int J, degrees; float motion_threshold;
+    float* this_box; float* prev_box; float* canon_box; float* box_label; float* box_label_prev; float* motion_label;
+    int32_t* motion_state; float* bbox_size;
+};
+
+// transform_box in double: (c, R) of a box in the frame of (cr, Rr) -> centre Rr^T (c - cr), rotation Rr^T R
+__device__ __forceinline__ void transform_box64(const double* c, const double* R, const double* cr, const double* Rr, double* oc, double* oR) {
+    const double d[3] = {c[0] - cr[0], c[1] - cr[1], c[2] - cr[2]};
+    for (int r = 0; r < 3; ++r) {                          // row r of Rr^T = column r of Rr
+        oc[r] = (Rr[r] * d[0] + Rr[3 + r] * d[1]) + Rr[6 + r] * d[2];
+        for (int q = 0; q < 3; ++q) oR[3 * r + q] = (Rr[r] * R[q] + Rr[3 + r] * R[3 + q]) + Rr[6 + r] * R[6 + q];
+    }
+}
+
+__device__ __forceinline__ void label_row(const double* c, const double* R, int degrees, float* o) {
+    const double theta = atan2(R[3], R[0]);
+    o[0] = (float)c[0]; o[1] = (float)c[1]; o[2] = (float)c[2];
+    o[3] = (float)(degrees ? theta * (180.0 / 3.14159265358979323846) : theta);
+}
+
+__global__ __launch_bounds__(256) void train_motion_labels_kernel(MotionLabelArgs a) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.J) return;
+    const float* pg = a.prev_gt + 15 * (long)j;
+    const float* tg = a.this_gt + 15 * (long)j;
+    const float* rb = a.ref_box + 15 * (long)j;
+    double cp[3], Rp[9], ct[3], Rt[9], cr[3], Rr[9];
+    for (int e = 0; e < 3; ++e) { cp[e] = pg[e]; ct[e] = tg[e]; cr[e] = rb[e]; }
+    for (int e = 0; e < 9; ++e) { Rp[e] = pg[6 + e]; Rt[e] = tg[6 + e]; Rr[e] = rb[6 + e]; }
+    double c_this[3], R_this[9], c_prev[3], R_prev[9], c_mot[3], R_mot[9];
+    transform_box64(ct, Rt, cr, Rr, c_this, R_this);
+    transform_box64(cp, Rp, cr, Rr, c_prev, R_prev);
+    transform_box64(c_this, R_this, c_prev, R_prev, c_mot, R_mot);
+    float* ob = a.this_box + 15 * (long)j;
+    float* pb = a.prev_box + 15 * (long)j;
+    float* cb = a.canon_box + 15 * (long)j;
+    for (int e = 0; e < 3; ++e) {
+        ob[e] = (float)c_this[e]; pb[e] = (float)c_prev[e]; cb[e] = 0.f;
+        ob[3 + e] = tg[3 + e]; pb[3 + e] = pg[3 + e]; cb[3 + e] = pg[3 + e];
+        a.bbox_size[3 * (long)j + e] = tg[3 + e];
+    }
+    for (int e = 0; e < 9; ++e) {
+        ob[6 + e] = (float)R_this[e]; pb[6 + e] = (float)R_prev[e];
+        cb[6 + e] = (e == 0 || e == 4 || e == 8) ? 1.f : 0.f;
+    }
+    label_row(c_this, R_this, a.degrees, a.box_label + 4 * (long)j);
+    label_row(c_prev, R_prev, a.degrees, a.box_label_prev + 4 * (long)j);
+    label_row(c_mot, R_mot, a.degrees, a.motion_label + 4 * (long)j);
+    const double dx = c_this[0] - c_prev[0], dy = c_this[1] - c_prev[1], dz = c_this[2] - c_prev[2];
+    a.motion_state[j] = sqrt((dx * dx + dy * dy) + dz * dz) > (double)a.motion_threshold ? 1 : 0;
+}
+
 static bool crop_groups_plan(const o3d_crop_plan* groups, int n_groups, bool check_plan, o3d_crop_plan* fill, long& wgs, long& rows,
                              long& need) {
     if (!groups || n_groups < 1 || n_groups > O3D_CROP_MAX_GROUPS) return false;
@@ -297,7 +412,7 @@ extern "C" int o3d_train_select(const int32_t* counts, int J, int B, int cap_fir
     if (!counts || !sel || !n_valid || !overflow || J < 1 || J > O3D_TRAIN_MAX_CANDIDATES || B < 1 || B > J || cap_first < 0 ||
         cap_template < 0 || cap_search < 0)
         return O3D_EINVAL;
-    hipLaunchKernelGGL(train_select_kernel, dim3(1), dim3(SELECT_WG), 0, o3d_stream(stream), counts, J, B, cap_first, cap_template,
+    hipLaunchKernelGGL(train_select_kernel<false>, dim3(1), dim3(SELECT_WG), 0, o3d_stream(stream), counts, J, B, cap_first, cap_template,
                        cap_search, sel, n_valid, overflow);
     return o3d_launch_status();
 }
@@ -323,5 +438,56 @@ extern "C" int o3d_train_sample(const o3d_train_sample_args* args, void* stream)
         return O3D_EINVAL;
     const int rows = a.M > a.N ? a.M : a.N;
     hipLaunchKernelGGL(train_sample_kernel, dim3(o3d_cdiv(rows, 256), a.B, 2), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_crop_groups_aug(const o3d_crop_plan* groups, const o3d_crop_plan* dev_groups, const o3d_crop_aug* const* dev_aug,
+                                         int n_groups, int32_t* scratch, long scratch_len, void* stream) {
+    long wgs, rows, need;
+    if (!crop_groups_plan(groups, n_groups, true, nullptr, wgs, rows, need) || !dev_groups || !scratch || scratch_len < need)
+        return O3D_EINVAL;
+    hipLaunchKernelGGL((crop_groups_kernel<false, true>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), dev_groups, n_groups, scratch,
+                       dev_aug);
+    hipLaunchKernelGGL(crop_groups_scan_kernel, dim3((int)rows), dim3(CROP_WG), 0, o3d_stream(stream), dev_groups, n_groups, scratch);
+    hipLaunchKernelGGL((crop_groups_kernel<true, true>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), dev_groups, n_groups, scratch,
+                       dev_aug);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_train_augment(const float* gt, const float* draw, const int32_t* slot_src, int K, int n_slots, float* out_box,
+                                 o3d_crop_aug* aug, void* stream) {
+    if (!gt || !draw || !out_box || !aug || K < 1 || K > 3 * O3D_TRAIN_MAX_CANDIDATES || n_slots < 1 ||
+        n_slots > 3 * O3D_TRAIN_MAX_CANDIDATES || (!slot_src && n_slots != K))
+        return O3D_EINVAL;
+    AugmentArgs a{gt, draw, slot_src, K, n_slots, out_box, aug};
+    hipLaunchKernelGGL(train_augment_kernel, dim3(o3d_cdiv(n_slots, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_train_inside_box(const float* points, int n, const float* box, float factor, int32_t* mask, void* stream) {
+    if (n < 0 || n > (1 << 30) || !box || !(factor >= 0.f) || (n > 0 && (!points || !mask))) return O3D_EINVAL;
+    if (n == 0) return O3D_OK;
+    hipLaunchKernelGGL(train_inside_box_kernel, dim3(o3d_cdiv(n, 256)), dim3(256), 0, o3d_stream(stream), points, n, box, factor, mask);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_train_motion_labels(const float* prev_gt, const float* this_gt, const float* ref_box, int J, int degrees,
+                                       float motion_threshold, float* this_box, float* prev_box, float* canon_box, float* box_label,
+                                       float* box_label_prev, float* motion_label, int32_t* motion_state, float* bbox_size, void* stream) {
+    if (!prev_gt || !this_gt || !ref_box || !this_box || !prev_box || !canon_box || !box_label || !box_label_prev || !motion_label ||
+        !motion_state || !bbox_size || J < 1 || J > O3D_TRAIN_MAX_CANDIDATES || !(motion_threshold >= 0.f))
+        return O3D_EINVAL;
+    MotionLabelArgs a{prev_gt, this_gt, ref_box, J, degrees != 0, motion_threshold, this_box, prev_box, canon_box, box_label,
+                      box_label_prev, motion_label, motion_state, bbox_size};
+    hipLaunchKernelGGL(train_motion_labels_kernel, dim3(o3d_cdiv(J, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_train_select_motion(const int32_t* counts, int J, int B, int cap_prev, int cap_this, int32_t* sel, int32_t* n_valid,
+                                       int32_t* overflow, void* stream) {
+    if (!counts || !sel || !n_valid || !overflow || J < 1 || J > O3D_TRAIN_MAX_CANDIDATES || B < 1 || B > J || cap_prev < 0 || cap_this < 0)
+        return O3D_EINVAL;
+    hipLaunchKernelGGL(train_select_kernel<true>, dim3(1), dim3(SELECT_WG), 0, o3d_stream(stream), counts, J, B, 0, cap_prev, cap_this, sel,
+                       n_valid, overflow);
     return o3d_launch_status();
 }

@@ -453,7 +453,8 @@ def transform_box(box, ref_box):
 def points_in_box(box, points, wlh_factor=1.0):
     """nuscenes.utils.geometry_utils.points_in_box on the device: points (3,N) GPU tensor -> (N,) bool, the points inside `box`
     scaled by wlh_factor, faces included (the projections onto the three edges from corner 0 of Box.corners).  A mirror for
-    callers of the reference's name; the tracker's own mask comes from o3d_track_motion_input."""
+    callers of the reference's name; the tracker's own mask comes from o3d_track_motion_input, the batch builder's from
+    `inside_box` below (one kernel, a fixed fp32 operation order)."""
     _need_gpu(points, "points_in_box")
     if points.dim() != 2 or points.shape[0] != 3:
         raise ValueError("points must be (3, N)")
@@ -555,3 +556,117 @@ def train_sample(args, device):
     with torch.cuda.device(device):
         capi.check(capi.load().o3d_train_sample(ctypes.addressof(args), torch.cuda.current_stream(device).cuda_stream),
                    "o3d_train_sample")
+
+
+# ---- M2-Track training batches (csrc/train_batch.hip; sampler.MotionBatchBuilder is the caller) -----------------------------
+CROP_AUG = np.dtype([("enabled", "i4"), ("box", "f4", (15,)), ("A", "f4", (9,)), ("c", "f4", (3,))], align=True)      # o3d_crop_aug
+
+
+class _TrainMotionSampleArgs(ctypes.Structure):    # o3d_train_motion_sample_args
+    _fields_ = [("sel", _vp), ("counts", _vp), ("crop_prev", _vp), ("crop_this", _vp),
+                ("cap_prev", _i), ("cap_this", _i), ("J", _i), ("B", _i), ("N", _i),
+                ("idx_prev", _vp), ("idx_this", _vp), ("candidate_id", _vp), ("seed", ctypes.c_uint), ("counter", ctypes.c_uint),
+                ("prev_box", _vp), ("this_box", _vp), ("canon_box", _vp),
+                ("cand_box_label", _vp), ("cand_box_label_prev", _vp), ("cand_motion_label", _vp), ("cand_motion_state", _vp),
+                ("cand_bbox_size", _vp),
+                ("points", _vp), ("candidate_bc", _vp), ("seg_label", _vp),
+                ("box_label", _vp), ("box_label_prev", _vp), ("motion_label", _vp), ("motion_state_label", _vp), ("bbox_size", _vp),
+                ("bc_boxes", _vp), ("xyz_halves", _vp), ("used_prev", _vp), ("used_this", _vp)]
+
+
+assert CROP_AUG.itemsize == 112 and ctypes.sizeof(_TrainMotionSampleArgs) == 248
+capi.register("o3d_train_augment", [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp])
+capi.register("o3d_track_crop_groups_aug", [_vp, _vp, _vp, _i, _vp, ctypes.c_long, _vp])
+capi.register("o3d_train_inside_box", [_vp, _i, _vp, _f, _vp, _vp])
+capi.register("o3d_train_motion_labels", [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+capi.register("o3d_train_select_motion", [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
+capi.register("o3d_train_motion_sample", [_vp, _vp])
+
+
+def _addr(t):
+    return None if t is None else (t.data_ptr() if torch.is_tensor(t) else int(t))
+
+
+def train_augment(gt, draw, out_box, aug, slot_src=None):
+    """One o3d_train_augment launch: gt (K,15), draw (K,6) float32 GPU -> out_box (K,15) and the records `aug` (a uint8 GPU
+    tensor of n_slots CROP_AUG records, or an address with slot_src given); slot_src (n_slots,) int32 GPU | None"""
+    for t, width in ((gt, 15), (draw, 6), (out_box, 15)):
+        _need_gpu(t, "train_augment")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() % width == 0
+    K = gt.numel() // 15
+    assert draw.numel() == 6 * K and out_box.numel() == 15 * K
+    n_slots = K if slot_src is None else slot_src.numel()
+    assert slot_src is None or (slot_src.is_cuda and slot_src.dtype == torch.int32 and slot_src.is_contiguous())
+    assert not torch.is_tensor(aug) or (aug.is_cuda and aug.is_contiguous() and aug.numel() * aug.element_size() >= n_slots * CROP_AUG.itemsize)
+    dev = gt.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_augment(gt.data_ptr(), draw.data_ptr(), _addr(slot_src), K, n_slots, out_box.data_ptr(), _addr(aug),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "o3d_train_augment")
+
+
+def crop_groups_aug(plan, dev_plan, dev_aug, scratch):
+    """One o3d_track_crop_groups_aug call (three launches, no sync): crop_groups with dev_aug = the DEVICE array of
+    plan.shape[0] pointers to CROP_AUG records (an int64 GPU tensor, an address, or None = no record anywhere)"""
+    dev = scratch.device
+    assert not torch.is_tensor(dev_aug) or (dev_aug.is_cuda and dev_aug.dtype == torch.int64 and dev_aug.is_contiguous()
+                                            and dev_aug.numel() >= plan.shape[0])
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_crop_groups_aug(
+            plan.ctypes.data, _addr(dev_plan), _addr(dev_aug), plan.shape[0], scratch.data_ptr(), scratch.numel(),
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_crop_groups_aug")
+
+
+def inside_box(points, box15, factor=1.0):
+    """One o3d_train_inside_box launch: points (n,3) float32 GPU contiguous, box15 (15,) GPU -> (n,) int32 mask, the inclusive
+    test of points_in_box in the kernels' fp32 operation order"""
+    _need_gpu(points, "inside_box")
+    _need_gpu(box15, "inside_box")
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3
+    assert box15.dtype == torch.float32 and box15.is_contiguous() and box15.numel() == 15
+    dev = points.device
+    mask = torch.empty((points.shape[0],), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_inside_box(points.data_ptr(), points.shape[0], box15.data_ptr(), float(factor), mask.data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream), "o3d_train_inside_box")
+    return mask
+
+
+def train_motion_labels(prev_gt, this_gt, ref_box, degrees, motion_threshold, this_box, prev_box, canon_box, box_label,
+                        box_label_prev, motion_label, motion_state, bbox_size):
+    """One o3d_train_motion_labels launch on (J,15) float32 GPU tensors; the last eight are written in place ((J,15) x 3,
+    (J,4) x 3, motion_state (J,) int32, bbox_size (J,3))"""
+    J = prev_gt.numel() // 15
+    for t, width, dt in ((prev_gt, 15, torch.float32), (this_gt, 15, torch.float32), (ref_box, 15, torch.float32),
+                         (this_box, 15, torch.float32), (prev_box, 15, torch.float32), (canon_box, 15, torch.float32),
+                         (box_label, 4, torch.float32), (box_label_prev, 4, torch.float32), (motion_label, 4, torch.float32),
+                         (motion_state, 1, torch.int32), (bbox_size, 3, torch.float32)):
+        _need_gpu(t, "train_motion_labels")
+        assert t.dtype == dt and t.is_contiguous() and t.numel() == width * J
+    dev = prev_gt.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_motion_labels(
+            prev_gt.data_ptr(), this_gt.data_ptr(), ref_box.data_ptr(), J, int(bool(degrees)), float(motion_threshold), this_box.data_ptr(),
+            prev_box.data_ptr(), canon_box.data_ptr(), box_label.data_ptr(), box_label_prev.data_ptr(), motion_label.data_ptr(),
+            motion_state.data_ptr(), bbox_size.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "o3d_train_motion_labels")
+
+
+def train_select_motion(counts, B, caps, sel, n_valid, overflow):
+    """One o3d_train_select_motion launch: counts (J,3) int32 GPU = (in-box, previous crop, current crop), caps = (cap_prev,
+    cap_this) -> sel (B,), n_valid (1,), overflow (1,) int32 GPU tensors, written in place"""
+    for t in (counts, sel, n_valid, overflow):
+        _need_gpu(t, "train_select_motion")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    J = counts.numel() // 3
+    assert counts.numel() == 3 * J and sel.numel() >= B
+    dev = counts.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_select_motion(counts.data_ptr(), J, int(B), int(caps[0]), int(caps[1]), sel.data_ptr(),
+                                                       n_valid.data_ptr(), overflow.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_train_select_motion")
+
+
+def train_motion_sample(args, device):
+    """One o3d_train_motion_sample launch: args = a filled _TrainMotionSampleArgs (the caller keeps its tensors alive)"""
+    with torch.cuda.device(device):
+        capi.check(capi.load().o3d_train_motion_sample(ctypes.addressof(args), torch.cuda.current_stream(device).cuda_stream),
+                   "o3d_train_motion_sample")

@@ -10,7 +10,19 @@ a fixed number of launches on the current stream (csrc/train_batch.hip):
     o3d_train_sample             regularize_pc of both clouds, seg_label, the batch's label rows
     o3d_boxcloud (2, box_aware)  points2cc_dist_t / points2cc_dist_s
 
-Not covered: M2-Track's motion_processing, use_augmentation, dataset readers.
+M2-Track's batches (MotionTrackingSampler + motion_processing, sampler.py:82-180,262-288, with apply_augmentation,
+points_utils.py:299-361) come from MotionBatchBuilder: one pinned upload and ten launches with augmentation and BoxCloud
+
+    o3d_train_augment            apply_transform for both frames' boxes, and the records that move the points (K = 2J)
+    o3d_track_offset_box_multi   the jittered reference box of every candidate
+    o3d_train_motion_labels      the three transform_box, the three labels, motion_state_label, bbox_size
+    o3d_track_crop_groups_aug (3)  both crops and the in-box count of every candidate, every frame read once
+    o3d_train_select_motion      which candidates fill the batch
+    o3d_train_motion_sample      regularize_pc of both halves, the five point channels, candidate_bc, seg_label, the label rows
+    o3d_boxcloud (2, box_aware)  prev_bc / this_bc
+
+Not covered (DESIGN.md sections 13, 13b): use_augmentation for the siamese builder (a small follow-up now: one more fixture and
+the search frame's record only), dataset readers.
 """
 import math
 
@@ -23,12 +35,16 @@ from . import points_utils as PU
 DATA_KEYS = dict(search_bb_scale=1.25, search_bb_offset=2, model_bb_scale=1.25, model_bb_offset=0, template_size=512,
                  search_size=1024, degrees=True, box_aware=True, num_candidates=4, data_limit_box=False, use_augmentation=False)
 DEFAULT_CAPACITY = (4096, 4096, 16384)       # rows of the first-frame, template-frame and search crop buffers
+# the data keys of cfgs/M2_track_kitti.yaml:5-8,10,17-20,24
+MOTION_DATA_KEYS = dict(bb_scale=1.25, bb_offset=2, point_sample_size=1024, degrees=False, data_limit_box=True, num_candidates=4,
+                        motion_threshold=0.15, use_augmentation=True, box_aware=True)
+DEFAULT_MOTION_CAPACITY = (16384, 16384)     # rows of the previous-frame and current-frame crop buffers
 
 
-def _cfg(config, key):
+def _cfg(config, key, defaults=DATA_KEYS):
     if isinstance(config, dict):
-        return config.get(key, DATA_KEYS[key])
-    return getattr(config, key, DATA_KEYS[key])
+        return config.get(key, defaults[key])
+    return getattr(config, key, defaults[key])
 
 
 class DeviceTracklet:
@@ -69,7 +85,102 @@ def _section(layout, name, nbytes):
     layout["_end"] = off + -(-nbytes // 64) * 64
 
 
-class SiameseBatchBuilder:
+class _DeviceBatchBuilder:
+    """What SiameseBatchBuilder and MotionBatchBuilder share: the over-provisioned sizes, the two-slot pinned staging buffer
+    and its sections, the crop tables of a batch (every distinct frame one group) and the output dict"""
+
+    def _init_sizes(self, batch_size, candidates, seed, record_indices):
+        self.B = int(batch_size)
+        self.J = int(candidates) if candidates is not None else int(math.ceil(1.25 * self.B))
+        if not 1 <= self.B <= self.J <= PU.TRAIN_MAX_CANDIDATES:
+            raise ValueError("1 <= batch_size <= candidates <= %d" % PU.TRAIN_MAX_CANDIDATES)
+        self.seed = int(seed)
+        self.rng = np.random.default_rng(self.seed)
+        self.counter = 0
+        self.record_indices = bool(record_indices)
+        self.device = None
+
+    def _allocate_staging(self, lay, dev):
+        self.device = dev
+        self._layout = lay
+        self._up = torch.empty(lay["_end"], dtype=torch.uint8, device=dev)
+        self._pinned = [torch.empty(lay["_end"], dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._events = [torch.cuda.Event() for _ in range(2)]
+        self._used = [False, False]
+
+    def _view(self, slot, name, dtype, shape):
+        off, nbytes = self._layout[name]
+        return self._pinned[slot].numpy()[off:off + nbytes].view(dtype).reshape(shape)
+
+    def _dev(self, name):
+        return self._up.data_ptr() + self._layout[name][0]
+
+    def _dev32(self, name, count):
+        """the first `count` float32 of section `name` of the uploaded buffer, as a tensor"""
+        o = self._layout[name][0] // 4
+        return self._up.view(torch.float32)[o:o + count]
+
+    def _begin(self, samples):
+        """-> (device, stream, slot) of this build; allocates on the first one, waits for the slot's upload of two builds ago"""
+        if len(samples) != self.J:
+            raise ValueError("build() takes %d candidates, got %d" % (self.J, len(samples)))
+        dev = samples[0][0].frames[0].device
+        if self.device is None:
+            with torch.cuda.device(dev):
+                self._allocate(dev)
+        assert dev == self.device
+        slot = self.counter & 1
+        if self._used[slot]:
+            self._events[slot].synchronize()          # the upload of two builds ago: long done in a running loop
+        return dev, torch.cuda.current_stream(dev), slot
+
+    def _crop_tables(self, slot, wanted):
+        """wanted: (tracklet, frame, c, j) for every crop, in the order of the candidates -> (the planned CROP_PLAN rows of
+        this batch in the pinned slot, the scratch length, [(first target, c list, j list)] per group): every distinct frame
+        is one group whose targets are self._rec[c, j] of the crops that read it"""
+        groups, order = {}, []
+        for trk, f, c, j in wanted:
+            key = (id(trk), f)
+            if key not in groups:
+                groups[key] = (trk.frames[f], [], [])
+                order.append(key)
+            groups[key][1].append(c)
+            groups[key][2].append(j)
+        n_rec = self._rec.shape[0] * self.J
+        targets = self._view(slot, "targets", PU.CROP_TARGET, (n_rec,))
+        plan = self._view(slot, "plan", PU.CROP_PLAN, (n_rec,))[:len(order)]
+        pos, where = 0, []
+        tab = self._dev("targets")
+        for g, key in enumerate(order):
+            pts, cs, js = groups[key]
+            k = len(cs)
+            targets[pos:pos + k] = self._rec[cs, js]
+            plan[g] = (pts.data_ptr(), pts.shape[0], tab + PU.CROP_TARGET.itemsize * pos, k, 0, 0, 0)
+            where.append((pos, cs, js))
+            pos += k
+        need = PU.crop_groups_plan(plan)[0]
+        if self._scratch.numel() < need:
+            with torch.cuda.device(self.device):
+                self._scratch = torch.empty(need, dtype=torch.int32, device=self.device)
+        return plan, need, where
+
+    def _upload(self, slot, nbytes, stream):
+        self._up[:nbytes].copy_(self._pinned[slot][:nbytes], non_blocking=True)       # THE upload of this batch
+        self._events[slot].record(stream)
+        self._used[slot] = True
+
+    def _outputs(self, out, dev):
+        res = {}
+        for k, (shape, dtype) in self._shapes().items():
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, k
+            res[k] = t
+        return res
+
+
+class SiameseBatchBuilder(_DeviceBatchBuilder):
     """build(samples) -> the training dict: template_points (B,M,3), search_points (B,N,3), box_label (B,4), bbox_size (B,3),
     seg_label (B,N) and, with box_aware, points2cc_dist_t (B,M,9) / points2cc_dist_s (B,N,9) -- the keys and shapes of
     synth.make_batch -- plus n_valid (1,) and overflow (1,) int32, all device tensors.
@@ -98,10 +209,7 @@ class SiameseBatchBuilder:
     def __init__(self, config, batch_size, candidates=None, capacity=DEFAULT_CAPACITY, seed=0, record_indices=False):
         if _cfg(config, "use_augmentation"):
             raise NotImplementedError("SiameseBatchBuilder: use_augmentation (points_utils.apply_augmentation) is not built")
-        self.B = int(batch_size)
-        self.J = int(candidates) if candidates is not None else int(math.ceil(1.25 * self.B))
-        if not 1 <= self.B <= self.J <= PU.TRAIN_MAX_CANDIDATES:
-            raise ValueError("1 <= batch_size <= candidates <= %d" % PU.TRAIN_MAX_CANDIDATES)
+        self._init_sizes(batch_size, candidates, seed, record_indices)
         self.caps = tuple(int(c) for c in ((capacity,) * 3 if isinstance(capacity, int) else capacity))
         assert len(self.caps) == 3 and min(self.caps) >= 1
         self.M, self.N = int(_cfg(config, "template_size")), int(_cfg(config, "search_size"))
@@ -110,16 +218,10 @@ class SiameseBatchBuilder:
         self.num_candidates = int(_cfg(config, "num_candidates"))
         self.scales = (float(_cfg(config, "model_bb_scale")), float(_cfg(config, "model_bb_offset")),
                        float(_cfg(config, "search_bb_scale")), float(_cfg(config, "search_bb_offset")))
-        self.seed = int(seed)
-        self.rng = np.random.default_rng(self.seed)
-        self.counter = 0
-        self.record_indices = bool(record_indices)
-        self.device = None
 
     # ---- buffers (allocated once, on the first build) ---------------------------------------------------------------------------------
     def _allocate(self, dev):
         J, B, M, N = self.J, self.B, self.M, self.N
-        self.device = dev
         lay = {"_end": 0}
         _section(lay, "refs", 2 * J * 60)             # rows [0, J): the template frame's box, [J, 2J): the search frame's
         _section(lay, "offs", 2 * J * 16)             # (x, y, 0, theta) of the two jitters
@@ -129,11 +231,7 @@ class SiameseBatchBuilder:
         self._base_bytes = lay["_end"]
         _section(lay, "idx_t", J * M * 4)             # teacher-forced builds only
         _section(lay, "idx_s", J * N * 4)
-        self._layout = lay
-        self._up = torch.empty(lay["_end"], dtype=torch.uint8, device=dev)
-        self._pinned = [torch.empty(lay["_end"], dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._events = [torch.cuda.Event() for _ in range(2)]
-        self._used = [False, False]
+        self._allocate_staging(lay, dev)
 
         def f32(*shape):
             return torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -164,13 +262,6 @@ class SiameseBatchBuilder:
             rec["count"][c] = self.counts.data_ptr() + 12 * j + 4 * c
         self._rec = rec
 
-    def _view(self, slot, name, dtype, shape):
-        off, nbytes = self._layout[name]
-        return self._pinned[slot].numpy()[off:off + nbytes].view(dtype).reshape(shape)
-
-    def _dev(self, name):
-        return self._up.data_ptr() + self._layout[name][0]
-
     def draw_offsets(self, candidate_ids):
         """the host draw of the two box jitters of J candidates -> (offset_t (J,3), offset_s (J,3)) float64"""
         J = len(candidate_ids)
@@ -186,21 +277,10 @@ class SiameseBatchBuilder:
 
     def build(self, samples, draws=None, out=None):
         J, B, M, N = self.J, self.B, self.M, self.N
-        if len(samples) != J:
-            raise ValueError("build() takes %d candidates, got %d" % (J, len(samples)))
-        dev = samples[0][0].frames[0].device
-        if self.device is None:
-            with torch.cuda.device(dev):
-                self._allocate(dev)
-        assert dev == self.device
-        stream = torch.cuda.current_stream(dev)
-        slot = self.counter & 1
-        if self._used[slot]:
-            self._events[slot].synchronize()          # the upload of two builds ago: long done in a running loop
+        dev, stream, slot = self._begin(samples)
         refs = self._view(slot, "refs", np.float32, (2 * J, 15))
         offs = self._view(slot, "offs", np.float32, (2 * J, 4))
         first = self._view(slot, "first", np.float32, (J, 15))
-        targets = self._view(slot, "targets", PU.CROP_TARGET, (3 * J,))
         if draws is None:
             off_t, off_s = self.draw_offsets([s[4] for s in samples])
         else:
@@ -210,27 +290,11 @@ class SiameseBatchBuilder:
         offs[:J, :2], offs[:J, 3] = off_t[:, :2], off_t[:, 2]
         offs[J:, :2], offs[J:, 3] = off_s[:, :2], off_s[:, 2]
         # the groups: every distinct frame once, with the crops that read it
-        groups, order = {}, []
+        wanted = []
         for j, (trk, f0, f1, f2, _) in enumerate(samples):
             first[j], refs[j], refs[J + j] = trk.boxes[f0], trk.boxes[f1], trk.boxes[f2]
-            for c, f in enumerate((f0, f1, f2)):
-                key = (id(trk), f)
-                if key not in groups:
-                    groups[key] = (trk.frames[f], [], [])
-                    order.append(key)
-                groups[key][1].append(c)
-                groups[key][2].append(j)
-        G = len(order)
-        plan = self._view(slot, "plan", PU.CROP_PLAN, (3 * J,))[:G]
-        pos = 0
-        tab = self._dev("targets")
-        for g, key in enumerate(order):
-            pts, cs, js = groups[key]
-            k = len(cs)
-            targets[pos:pos + k] = self._rec[cs, js]
-            plan[g] = (pts.data_ptr(), pts.shape[0], tab + PU.CROP_TARGET.itemsize * pos, k, 0, 0, 0)
-            pos += k
-        need = PU.crop_groups_plan(plan)[0]
+            wanted += [(trk, f, c, j) for c, f in enumerate((f0, f1, f2))]
+        plan = self._crop_tables(slot, wanted)[0]
         nbytes = self._base_bytes
         idx_t = idx_s = None
         if draws is not None and draws.get("idx_t") is not None:
@@ -239,14 +303,8 @@ class SiameseBatchBuilder:
             nbytes = self._layout["_end"]
             idx_t, idx_s = self._dev("idx_t"), self._dev("idx_s")
         with torch.cuda.device(dev):
-            if self._scratch.numel() < need:
-                self._scratch = torch.empty(need, dtype=torch.int32, device=dev)
-            self._up[:nbytes].copy_(self._pinned[slot][:nbytes], non_blocking=True)       # THE upload of this batch
-            self._events[slot].record(stream)
-            self._used[slot] = True
-            up32 = self._up.view(torch.float32)
-            r0, o0 = self._layout["refs"][0] // 4, self._layout["offs"][0] // 4
-            refs_d, offs_d = up32[r0:r0 + 2 * J * 15], up32[o0:o0 + 2 * J * 4]
+            self._upload(slot, nbytes, stream)
+            refs_d, offs_d = self._dev32("refs", 2 * J * 15), self._dev32("offs", 2 * J * 4)
             PU.offset_box_multi(refs_d, offs_d, out=self._jit, degrees=self.degrees, use_z=False, limit_box=self.limit_box,
                                 seed=(self.seed + 7919 * self.counter) & 0x3fffffff)
             PU.train_labels(refs_d[J * 15:], self._jit[J:], self._jit[:J], offs_d[J * 4:], self._search_box, self._cand_label,
@@ -269,30 +327,209 @@ class SiameseBatchBuilder:
         self.counter += 1
         return res
 
-    def _outputs(self, out, dev):
+    def _shapes(self):
         B, M, N = self.B, self.M, self.N
         shapes = {"template_points": ((B, M, 3), torch.float32), "search_points": ((B, N, 3), torch.float32),
                   "box_label": ((B, 4), torch.float32), "bbox_size": ((B, 3), torch.float32), "seg_label": ((B, N), torch.float32)}
         if self.box_aware:
             shapes.update(points2cc_dist_t=((B, M, 9), torch.float32), points2cc_dist_s=((B, N, 9), torch.float32))
         shapes.update(n_valid=((1,), torch.int32), overflow=((1,), torch.int32))
-        res = {}
-        for k, (shape, dtype) in shapes.items():
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=dev)
-            assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape, k
-            res[k] = t
+        return shapes
+
+
+class MotionBatchBuilder(_DeviceBatchBuilder):
+    """build(samples) -> the M2-Track training dict: points (B,2N,5), seg_label (B,2N) int64, box_label / box_label_prev /
+    motion_label (B,4), motion_state_label (B,) int64 and, with box_aware, candidate_bc (B,2N,9), prev_bc / this_bc (B,N,9) --
+    the keys, shapes and dtypes of synth.make_motion_batch -- plus bbox_size (B,3), n_valid (1,) and overflow (1,) int32, all
+    device tensors.  The contract is SiameseBatchBuilder's: J = `candidates` (default ceil(1.25 B)) samples (tracklet, prev,
+    this: frame indices, candidate_id) per batch, of which the first B valid ones fill it (valid iff the reference's two
+    assertions hold: more than 10 points of the un-augmented previous frame inside its box, more than 20 points in the current
+    crop, sampler.py:99,120); fixed crop buffers capacity = (prev, this) with `overflow`; two-slot pinned staging; out=.
+
+    draws: {offset (J,3), aug_prev (J,6), aug_this (J,6), idx_prev (J,N), idx_this (J,N)} teacher-forces the box jitter, the
+    augmentation (tx, ty, tz, rotation in degrees, flip_x, flip_y per frame) and the resampling indices.  Without it the
+    offsets and the augmentation come from a numpy Generator seeded with `seed` (offset: uniform +-0.3 with the angle x5
+    degrees or x deg2rad(5), zero for candidate_id 0, sampler.py:106-110; per (candidate, frame): translation uniform +-0.3,
+    rotation uniform +-10 degrees, two fair booleans, points_utils.py:353-355 -- the two frames are drawn independently even
+    when they are the same frame, as the reference draws them) and the indices are drawn on the device.
+
+    The attributes sel (B,), counts (J,3) = (in-box, previous crop, current crop), crops and, with record_indices, used_prev /
+    used_this (B,N) show the last build's intermediate results."""
+    motion = True
+
+    def __init__(self, config, batch_size, candidates=None, capacity=DEFAULT_MOTION_CAPACITY, seed=0, record_indices=False):
+        self._init_sizes(batch_size, candidates, seed, record_indices)
+        self.caps = tuple(int(c) for c in ((capacity,) * 2 if isinstance(capacity, int) else capacity))
+        assert len(self.caps) == 2 and min(self.caps) >= 1
+
+        def cfg(key):
+            return _cfg(config, key, MOTION_DATA_KEYS)
+        self.N = int(cfg("point_sample_size"))
+        self.degrees, self.box_aware = bool(cfg("degrees")), bool(cfg("box_aware"))
+        self.limit_box, self.augment = bool(cfg("data_limit_box")), bool(cfg("use_augmentation"))
+        self.num_candidates = int(cfg("num_candidates"))
+        self.scale, self.offset = float(cfg("bb_scale")), float(cfg("bb_offset"))
+        self.motion_threshold = float(cfg("motion_threshold"))
+
+    def _allocate(self, dev):
+        J, B, N = self.J, self.B, self.N
+        lay = {"_end": 0}
+        _section(lay, "refs", 2 * J * 60)             # rows [0, J): the previous frame's box, [J, 2J): the current frame's
+        _section(lay, "offs", J * 16)                 # (x, y, 0, theta) of the jitter
+        _section(lay, "aug", 2 * J * 24)              # the augmentation draws, rows as refs
+        _section(lay, "cand", J * 4)                  # candidate_id
+        _section(lay, "slots", 3 * J * 4)             # record slot -> row of refs / aug, -1: disabled (the in-box count)
+        _section(lay, "augptr", 3 * J * 8)            # per group: its first record
+        _section(lay, "targets", 3 * J * PU.CROP_TARGET.itemsize)
+        _section(lay, "plan", 3 * J * PU.CROP_PLAN.itemsize)
+        self._base_bytes = lay["_end"]
+        _section(lay, "idx_prev", J * N * 4)          # teacher-forced builds only
+        _section(lay, "idx_this", J * N * 4)
+        self._allocate_staging(lay, dev)
+
+        def f32(*shape):
+            return torch.zeros(shape, dtype=torch.float32, device=dev)
+
+        def i32(*shape):
+            return torch.zeros(shape, dtype=torch.int32, device=dev)
+        self._gt_aug, self._ref_box = f32(2 * J, 15), f32(J, 15)
+        self._aug = torch.zeros(3 * J * PU.CROP_AUG.itemsize, dtype=torch.uint8, device=dev)
+        self._this_box, self._prev_box, self._canon_box = f32(J, 15), f32(J, 15), f32(J, 15)
+        self._cand_label, self._cand_label_prev, self._cand_motion = f32(J, 4), f32(J, 4), f32(J, 4)
+        self._cand_state, self._cand_size = i32(J), f32(J, 3)
+        self.counts = i32(J, 3)
+        self.crops = tuple(f32(J, c, 3) for c in self.caps)
+        self.sel = i32(B)
+        self._bc_boxes, self._xyz = f32(2, 15 * B), f32(2, B, N, 3)
+        self.used_prev = i32(B, N) if self.record_indices else None
+        self.used_this = i32(B, N) if self.record_indices else None
+        self._scratch = i32(1 << 16)
+        # the target record c of candidate j: 0 = the in-box count of the previous frame (count only), 1 / 2 = the crops
+        rec = np.zeros((3, J), PU.CROP_TARGET)
+        j = np.arange(J, dtype=np.uint64)
+        rec["box"][0] = self._dev("refs") + 60 * j
+        rec["scale"][0], rec["offset"][0], rec["capacity"][0] = 1.0, 0.0, 0
+        for c in (1, 2):
+            rec["box"][c] = self._ref_box.data_ptr() + 60 * j
+            rec["scale"][c], rec["offset"][c] = self.scale, self.offset
+            rec["out"][c] = self.crops[c - 1].data_ptr() + 12 * self.caps[c - 1] * j
+            rec["capacity"][c] = self.caps[c - 1]
+        for c in range(3):
+            rec["mode"][c] = PU.CROP_SUBWINDOW
+            rec["count"][c] = self.counts.data_ptr() + 12 * j + 4 * c
+        self._rec = rec
+
+    def draw_offsets(self, candidate_ids):
+        """the host draw of the box jitter of J candidates -> offset (J,3) float64"""
+        J = len(candidate_ids)
+        off = self.rng.uniform(-0.3, 0.3, (J, 3))
+        off[:, 2] *= 5.0 if self.degrees else float(np.deg2rad(5))
+        off[np.asarray(candidate_ids) == 0] = 0.0
+        return off
+
+    def draw_augmentation(self, J):
+        """the host draw of apply_augmentation for both frames of J candidates -> (aug_prev, aug_this) (J,6) float64 = (tx,
+        ty, tz, rotation in degrees, flip_x, flip_y)"""
+        a = np.concatenate([self.rng.uniform(-0.3, 0.3, (2, J, 3)), self.rng.uniform(-10.0, 10.0, (2, J, 1)),
+                            self.rng.integers(0, 2, (2, J, 2)).astype(np.float64)], 2)
+        return a[0], a[1]
+
+    def build(self, samples, draws=None, out=None):
+        J, B, N = self.J, self.B, self.N
+        dev, stream, slot = self._begin(samples)
+        refs = self._view(slot, "refs", np.float32, (2 * J, 15))
+        offs = self._view(slot, "offs", np.float32, (J, 4))
+        cand = self._view(slot, "cand", np.int32, (J,))
+        ids = [s[3] for s in samples]
+        off = self.draw_offsets(ids) if draws is None else np.asarray(draws["offset"], np.float64)
+        assert off.shape == (J, 3)
+        offs[:] = 0
+        offs[:, :2], offs[:, 3] = off[:, :2], off[:, 2]
+        cand[:] = ids
+        if self.augment:
+            aug = self._view(slot, "aug", np.float32, (2 * J, 6))
+            aug[:J], aug[J:] = self.draw_augmentation(J) if draws is None else (draws["aug_prev"], draws["aug_this"])
+        wanted = []
+        for j, (trk, f1, f2, _) in enumerate(samples):
+            refs[j], refs[J + j] = trk.boxes[f1], trk.boxes[f2]
+            wanted += [(trk, f1, 0, j), (trk, f1, 1, j), (trk, f2, 2, j)]
+        plan, _, where = self._crop_tables(slot, wanted)
+        if self.augment:
+            slots = self._view(slot, "slots", np.int32, (3 * J,))
+            augptr = self._view(slot, "augptr", np.uint64, (3 * J,))
+            for g, (pos, cs, js) in enumerate(where):
+                slots[pos:pos + len(cs)] = [-1 if c == 0 else (c - 1) * J + j for c, j in zip(cs, js)]
+                augptr[g] = self._aug.data_ptr() + PU.CROP_AUG.itemsize * pos
+        nbytes = self._base_bytes
+        idx_prev = idx_this = None
+        if draws is not None and draws.get("idx_prev") is not None:
+            self._view(slot, "idx_prev", np.int32, (J, N))[:] = draws["idx_prev"]
+            self._view(slot, "idx_this", np.int32, (J, N))[:] = draws["idx_this"]
+            nbytes = self._layout["_end"]
+            idx_prev, idx_this = self._dev("idx_prev"), self._dev("idx_this")
+        with torch.cuda.device(dev):
+            self._upload(slot, nbytes, stream)
+            gt = self._dev32("refs", 2 * J * 15)
+            if self.augment:
+                s0 = self._layout["slots"][0] // 4
+                PU.train_augment(gt, self._dev32("aug", 2 * J * 6), self._gt_aug, self._aug,
+                                 self._up.view(torch.int32)[s0:s0 + 3 * J])
+                gt = self._gt_aug.view(-1)
+            PU.offset_box_multi(gt[:J * 15], self._dev32("offs", J * 4), out=self._ref_box, degrees=self.degrees, use_z=False,
+                                limit_box=self.limit_box, seed=(self.seed + 7919 * self.counter) & 0x3fffffff)
+            PU.train_motion_labels(gt[:J * 15], gt[J * 15:], self._ref_box, self.degrees, self.motion_threshold, self._this_box,
+                                   self._prev_box, self._canon_box, self._cand_label, self._cand_label_prev, self._cand_motion,
+                                   self._cand_state, self._cand_size)
+            if self.augment:
+                PU.crop_groups_aug(plan, self._dev("plan"), self._dev("augptr"), self._scratch)
+            else:
+                PU.crop_groups(plan, self._dev("plan"), self._scratch)
+            res = self._outputs(out, dev)
+            PU.train_select_motion(self.counts, B, self.caps, self.sel, res["n_valid"], res["overflow"])
+            bc = self.box_aware
+            a = PU._TrainMotionSampleArgs(
+                self.sel.data_ptr(), self.counts.data_ptr(), self.crops[0].data_ptr(), self.crops[1].data_ptr(), self.caps[0],
+                self.caps[1], J, B, N, idx_prev, idx_this, self._dev("cand"), self.seed & 0xffffffff, self.counter & 0xffffffff,
+                self._prev_box.data_ptr(), self._this_box.data_ptr(), self._canon_box.data_ptr(), self._cand_label.data_ptr(),
+                self._cand_label_prev.data_ptr(), self._cand_motion.data_ptr(), self._cand_state.data_ptr(), self._cand_size.data_ptr(),
+                res["points"].data_ptr(), res["candidate_bc"].data_ptr() if bc else None, res["seg_label"].data_ptr(),
+                res["box_label"].data_ptr(), res["box_label_prev"].data_ptr(), res["motion_label"].data_ptr(),
+                res["motion_state_label"].data_ptr(), res["bbox_size"].data_ptr(), self._bc_boxes.data_ptr() if bc else None,
+                self._xyz.data_ptr() if bc else None, self.used_prev.data_ptr() if self.record_indices else None,
+                self.used_this.data_ptr() if self.record_indices else None)
+            PU.train_motion_sample(a, dev)
+            if bc:
+                for w, key in enumerate(("prev_bc", "this_bc")):
+                    b = self._bc_boxes[w]
+                    PU.boxcloud_into(res[key], self._xyz[w], b[:3 * B], b[3 * B:6 * B], b[6 * B:])
+        self.counter += 1
         return res
+
+    def _shapes(self):
+        B, N = self.B, self.N
+        shapes = {"points": ((B, 2 * N, 5), torch.float32), "seg_label": ((B, 2 * N), torch.int64),
+                  "box_label": ((B, 4), torch.float32), "box_label_prev": ((B, 4), torch.float32),
+                  "motion_label": ((B, 4), torch.float32), "motion_state_label": ((B,), torch.int64),
+                  "bbox_size": ((B, 3), torch.float32)}
+        if self.box_aware:
+            shapes.update(candidate_bc=((B, 2 * N, 9), torch.float32), prev_bc=((B, N, 9), torch.float32),
+                          this_bc=((B, N, 9), torch.float32))
+        shapes.update(n_valid=((1,), torch.int32), overflow=((1,), torch.int32))
+        return shapes
 
 
 class DeviceBatchSampler:
     """An iterator of training dicts with the frame choice of PointTrackingSampler.__getitem__ (sampler.py:218-237): with
     random_sample, a random tracklet and frames (0, two distinct random frames); otherwise the annotations in order, frames
     (0, max(this - 1, 0), this).  The candidate id is index % num_candidates.  Every batch is over-provisioned to the
-    builder's J candidates, so that invalid ones (too few points) are skipped on the device."""
+    builder's J candidates, so that invalid ones (too few points) are skipped on the device.  With a MotionBatchBuilder the
+    frame choice is MotionTrackingSampler's (sampler.py:262-288): the annotations in order, frames (max(this - 1, 0), this);
+    random_sample is refused, because the reference forces it off (sampler.py:264)."""
 
     def __init__(self, tracklets, builder, random_sample=False, seed=0, sample_per_epoch=10000):
+        self.motion = bool(getattr(builder, "motion", False))
+        if self.motion and random_sample:
+            raise ValueError("DeviceBatchSampler: MotionTrackingSampler has no random_sample (datasets/sampler.py:264)")
         self.tracklets, self.builder, self.random_sample = tracklets, builder, bool(random_sample)
         self.rng = np.random.default_rng(int(seed))
         self.num_candidates = builder.num_candidates
@@ -304,7 +541,8 @@ class DeviceBatchSampler:
         return self.length // self.builder.J
 
     def sample(self, index):
-        """-> (tracklet, first, template, search, candidate_id) of sample `index`"""
+        """-> (tracklet, first, template, search, candidate_id) of sample `index`; (tracklet, prev, this, candidate_id) with
+        a MotionBatchBuilder"""
         anno, cand = index // self.num_candidates, index % self.num_candidates
         if self.random_sample:
             trk = self.tracklets[int(self.rng.integers(0, len(self.tracklets)))]
@@ -312,6 +550,8 @@ class DeviceBatchSampler:
             return trk, 0, int(a), int(b), cand
         t = int(np.searchsorted(self.starts, anno, side="right")) - 1
         this = anno - int(self.starts[t])
+        if self.motion:
+            return self.tracklets[t], max(this - 1, 0), this, cand
         return self.tracklets[t], 0, max(this - 1, 0), this, cand
 
     def __iter__(self):

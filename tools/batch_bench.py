@@ -3,6 +3,7 @@ training step.  Not bench.py: that measures the step on batches that are already
 
   python tools/batch_bench.py [--tracklets 16] [--frames 8] [--points 120000] [--batch 48] [--candidates 60]
                               [--builds 200] [--warmup 20] [--steps 40] [--repeats 3] [--host-batches 2]
+                              [--model BAT|M2TRACK]
 
 Setup: `--tracklets` synth.make_sequence tracklets of `--frames` frames of `--points` points resident in HBM, the BAT data
 config (cfgs/BAT_Car.yaml), the frame choice of DeviceBatchSampler(random_sample=True).  Three measurements, one JSON line:
@@ -14,6 +15,9 @@ config (cfgs/BAT_Car.yaml), the frame choice of DeviceBatchSampler(random_sample
                       same trainer fed builder batches that are built on a side stream while a step runs, against the same
                       trainer with every batch built on the main stream between two steps; blocks of `--steps` steps, the
                       three alternated `--repeats` times in the same process (the spread is in the lists)
+--model M2TRACK: the same three measurements for sampler.MotionBatchBuilder with the M2-Track data config
+(cfgs/M2_track_kitti.yaml: augmentation and BoxCloud on), the annotations in order as MotionTrackingSampler walks them (wrapping
+at the end of the data), tests/motion_sampler_oracle.py::build as the host port, and m2track.M2TRACK as the step.
 """
 import argparse
 import json
@@ -26,8 +30,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import motion_sampler_oracle as MSO  # noqa: E402
 import sampler_oracle as SO  # noqa: E402
-from open3dsot_amd import dist as D, sampler, synth, trackers  # noqa: E402
+from open3dsot_amd import dist as D, m2track, sampler, synth, trackers  # noqa: E402
 
 
 def main():
@@ -35,22 +40,28 @@ def main():
     for name, default in (("tracklets", 16), ("frames", 8), ("points", 120000), ("batch", 48), ("candidates", 60), ("builds", 200),
                           ("warmup", 20), ("steps", 40), ("repeats", 3), ("host-batches", 2)):
         ap.add_argument("--" + name, type=int, default=default)
+    ap.add_argument("--model", choices=("BAT", "M2TRACK"), default="BAT")
     args = ap.parse_args()
+    motion = args.model == "M2TRACK"
     if not torch.cuda.is_available():
         raise SystemExit("batch_bench needs a GPU: nothing here can be measured on the host")
     dev = torch.device("cuda", 0)
     B, J = args.batch, args.candidates
-    cfg = dict(sampler.DATA_KEYS)
+    cfg = dict(sampler.MOTION_DATA_KEYS if motion else sampler.DATA_KEYS)
     host = [synth.make_sequence(500 + i, args.frames, args.points) for i in range(args.tracklets)]
     tracklets = sampler.DeviceTracklets([h[0] for h in host], [h[1] for h in host], device=dev)
     # (make_sequence puts 1/16 of a frame on the target -- 7 500 points of 120 000, far more than a KITTI car -- so the model
     # crops need more room than the default capacity)
-    builder = sampler.SiameseBatchBuilder(cfg, B, candidates=J, capacity=(8192, 8192, 16384), seed=0)
-    it = sampler.DeviceBatchSampler(tracklets, builder, random_sample=True, seed=0, sample_per_epoch=1 << 30)
+    if motion:
+        builder = sampler.MotionBatchBuilder(cfg, B, candidates=J, capacity=(16384, 16384), seed=0)
+        it = sampler.DeviceBatchSampler(tracklets, builder)
+    else:
+        builder = sampler.SiameseBatchBuilder(cfg, B, candidates=J, capacity=(8192, 8192, 16384), seed=0)
+        it = sampler.DeviceBatchSampler(tracklets, builder, random_sample=True, seed=0, sample_per_epoch=1 << 30)
     index = [0]
 
     def next_samples():
-        s = [it.sample(index[0] + i) for i in range(J)]
+        s = [it.sample((index[0] + i) % it.length) for i in range(J)]
         index[0] += J
         return s
 
@@ -65,7 +76,7 @@ def main():
     e0.record()
     for _ in range(args.builds):
         s = next_samples()
-        frame_bytes += sum(t.frames[f].numel() * 4 for t, f in {(id(x[0]), f): (x[0], f) for x in s for f in x[1:4]}.values())
+        frame_bytes += sum(t.frames[f].numel() * 4 for t, f in {(id(x[0]), f): (x[0], f) for x in s for f in x[1:-1]}.values())
         out = builder.build(s, out=out)
     e1.record()
     torch.cuda.synchronize()
@@ -86,16 +97,24 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.host_batches):
         s = next_samples()
-        off_t, off_s = builder.draw_offsets([x[4] for x in s])
-        SO.build(host_map, [(id(x[0]),) + tuple(x[1:]) for x in s], cfg, B, off_t, off_s, builder.caps)
+        keyed = [(id(x[0]),) + tuple(x[1:]) for x in s]
+        if motion:
+            a_prev, a_this = builder.draw_augmentation(J)
+            MSO.build(host_map, keyed, cfg, B, builder.draw_offsets([x[3] for x in s]), a_prev, a_this, builder.caps)
+        else:
+            off_t, off_s = builder.draw_offsets([x[4] for x in s])
+            SO.build(host_map, keyed, cfg, B, off_t, off_s, builder.caps)
     host_s = (time.perf_counter() - t0) / args.host_batches
 
     # ---- 3. the step, fed resident batches against builder batches built beside it -------------------------------------------------
     torch.manual_seed(0)
-    model = trackers.BAT().to(dev).train()
+    model = (m2track.M2TRACK() if motion else trackers.BAT()).to(dev).train()
     trainer = D.DataParallelStep(model, world=1, graph=True, graph_warmup=2, require_graph=True)
     extra = {"n_valid": torch.full((1,), B, dtype=torch.int32, device=dev), "overflow": torch.zeros(1, dtype=torch.int32, device=dev)}
-    pool = [dict(synth.to_torch(synth.make_batch(100 + i * B, B), dev), **extra) for i in range(3)]
+    if motion:
+        extra["bbox_size"] = torch.ones((B, 3), dtype=torch.float32, device=dev)
+    make = synth.make_motion_batch if motion else synth.make_batch
+    pool = [dict(synth.to_torch(make(100 + i * B, B), dev), **extra) for i in range(3)]
     for i in range(8):
         if trainer.graph is not None and not isinstance(pool[0], D.FlatBatch):
             pool = [trainer.make_batch(b) for b in pool]
@@ -142,13 +161,14 @@ def main():
         for mode in times:
             times[mode].append(round(block(mode), 4))
     print(json.dumps({
-        "tool": "batch_bench", "device": torch.cuda.get_device_name(0), "config": "BAT_Car data keys", "batch": B, "candidates": J,
+        "tool": "batch_bench", "device": torch.cuda.get_device_name(0), "model": args.model,
+        "config": "M2_track_kitti data keys" if motion else "BAT_Car data keys", "batch": B, "candidates": J,
         "tracklets": args.tracklets, "frames": args.frames, "points": args.points, "capacity": list(builder.caps),
         "builds": args.builds, "build_ms": round(build_ms, 4), "build_wall_ms": round(wall_ms, 4),
         "build_host_ms": round(float(sorted(host_ms)[len(host_ms) // 2]), 4),
         "build_pairs_per_s": round(B / build_ms * 1e3, 1), "frame_mb_per_build": round(frame_bytes / args.builds / 1e6, 1),
         "frame_gb_per_s": round(frame_bytes / args.builds / build_ms / 1e6, 1), "last_n_valid": n_valid, "last_overflow": overflow,
-        "host_port": "tests/sampler_oracle.py::build (numpy port of the reference's sampler, one process)",
+        "host_port": "tests/%s.py::build (numpy port of the reference's sampler, one process)" % ("motion_sampler_oracle" if motion else "sampler_oracle"),
         "host_port_s_per_batch": round(host_s, 3), "host_port_pairs_per_s": round(B / host_s, 1),
         "step_ms_resident": times["resident"], "step_ms_side": times["side"], "step_ms_inline": times["inline"],
         "steps_per_block": args.steps}))
