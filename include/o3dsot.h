@@ -872,6 +872,24 @@ typedef struct {
 } o3d_train_motion_sample_args;
 int o3d_train_motion_sample(const o3d_train_motion_sample_args* args, void* stream);
 
+/* estimateOverlap / estimateAccuracy (utils/metrics.py:27-72) for n box pairs in one launch: a (n,15) the annotation boxes,
+ * b (n,15) the result boxes, e.g. the flattened (T,K) rows of a tracker's results buffer.  valid (n) int32 | NULL: a row with
+ * valid == 0 is skipped entirely (its outputs are not written, nothing is counted).  dim = 2 (BEV) | 3; up = 1 | 2, the index
+ * of the non-zero component of up_axis ((0,-1,0) and (0,0,1), the two the reference supports).  overlaps, distances (n) | NULL.
+ * The arithmetic runs in double in the order stated at the head of csrc/metrics.hip and is rounded once to fp32: the
+ * footprint is the projection of four box corners under the FULL rotation matrix, the intersection a Sutherland-Hodgman clip,
+ * the dim-3 height rule the reference's own (from the centre down by h); the dim-2 distance is |difference of the up
+ * component|, as the reference's mask selects.
+ * DEGENERATE INPUT: a non-finite box or a union that is not > 0 gives overlap 0 (the reference raises or returns NaN).
+ * Counters (each | NULL): cnt_s (ns) int64 += #{overlap >= thr_s[i]}, cnt_p (np) int64 += #{distance <= thr_p[i]}, total (1)
+ * int64 += #valid rows; the fp32-rounded results are compared with the fp32 thresholds thr_s (ns), thr_p (np), 1..64 each.
+ * Integer atomics: the counts do not depend on the order of execution.
+ * O3D_EINVAL (before any HIP call): a or b NULL, n < 0, dim not 2 | 3, up not 1 | 2, a counter without its thresholds, more
+ * than 64 thresholds.  n == 0: returns 0 without a launch. */
+int o3d_track_score(const float* a, const float* b, const int32_t* valid, int n, int dim, int up, float* overlaps,
+                    float* distances, const float* thr_s, int ns, const float* thr_p, int np, int64_t* cnt_s, int64_t* cnt_p,
+                    int64_t* total, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

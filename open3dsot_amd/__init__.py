@@ -9,6 +9,8 @@ BAT / P2B feature-extraction hot path.
     open3dsot_amd.backbone / xcorr / rpn / trackers
                                  host-side mirror of models/backbone, models/head, BAT / P2B
     open3dsot_amd.dist           one-process-per-GPU data-parallel step (RCCL all-reduce)
+    open3dsot_amd.tracking       the frame loops on the device, and their evaluation (evaluate_sequence, evaluate)
+    open3dsot_amd.metrics        IoU / centre distance of box pairs and Success / Precision as device counters
     open3dsot_amd.sampler        training batches built on the device (PointTrackingSampler + siamese_processing)
 """
 __version__ = "0.1.0"

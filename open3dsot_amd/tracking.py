@@ -246,6 +246,22 @@ class _DeviceTracker:
         """(T,15) float32 on the host, (T,K,15) with n_targets = K: row 0 the initial box, row t the result of frame t (one sync)"""
         return self.boxes[:self.t].cpu().numpy()
 
+    def score(self, gt_boxes, valid=None, metrics=None):
+        """Score rows [0:t] of the results buffer against gt_boxes (t,15) ((t,K,15) with n_targets = K; host or device), where
+        they are, in ONE launch of o3d_track_score: estimateOverlap / estimateAccuracy with the model config's IoU_space and
+        up_axis (3 and (0,0,1) when absent, as in cfgs/BAT_Car.yaml).  valid (t[,K]) | None: rows with 0 are not scored.
+        metrics: a metrics.SuccessPrecision that the same launch adds to.  -> (overlaps, distances) (t[,K]) device tensors;
+        no sync."""
+        from . import metrics as MT
+        gt = PU._dev32(gt_boxes, self.dev)
+        if tuple(gt.shape) != (self.t,) + self.lead + (15,):
+            raise ValueError("%s.score: gt_boxes %s for results %s" % (self._NAME, tuple(gt.shape), (self.t,) + self.lead + (15,)))
+        if valid is not None:
+            valid = torch.as_tensor(valid).to(self.dev)
+        cfg = self.model.config
+        return MT.score_boxes(gt, self.boxes[:self.t], int(getattr(cfg, "IoU_space", 3)), tuple(getattr(cfg, "up_axis", (0, 0, 1))),
+                              valid=valid, accumulate=metrics)
+
 
 class _KTargets:
     """What the two K-target loops (MultiTargetTracker, MultiMotionTracker) share on top of _DeviceTracker's leading K axis:
@@ -764,3 +780,80 @@ def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None)
         else:
             trk.update(frames[t], ref_boxes[t])
     return trk.results()
+
+
+def _track_with_gt(trk, frames, gt):
+    """the frame loop of evaluate_one_sequence on `trk`: it starts from gt[0]; under reference_BB previous_gt / current_gt the
+    matching ground-truth box goes to update() (generate_search_area, models/base_model.py:208-214).  gt: (T[,K],15) on the
+    tracker's device."""
+    if len(frames) != gt.shape[0]:
+        raise ValueError("%d frames, %d ground-truth boxes" % (len(frames), gt.shape[0]))
+    trk.init(frames[0], gt[0])
+    by_gt = getattr(trk, "needs_ref_box", False)
+    back = 1 if by_gt and "PREVIOUS_GT" in str(trk.reference_BB).upper() else 0
+    for t in range(1, len(frames)):
+        if by_gt:
+            trk.update(frames[t], gt[t - back])
+        else:
+            trk.update(frames[t])
+
+
+def evaluate_sequence(model, frames, gt_boxes, seed=0, use_graph=None, tracker=None, metrics=None):
+    """The device form of evaluate_one_sequence (models/base_model.py:59-86): frames = a sequence of (N_t,3) GPU tensors,
+    gt_boxes (T,15) host or device.  The tracker starts from gt_boxes[0], follows the config's reference_BB rule, and the
+    whole sequence is scored ONCE at its end, on the device (frame 0 scores the first box against itself, as the reference
+    does).  tracker: one to reuse (its captured graph with it) | None: tracker_for(model).  metrics: a SuccessPrecision to add to.
+    -> (ious (T), distances (T), results (T,15)) device tensors; no sync beyond the tracker's own."""
+    trk = tracker if tracker is not None else tracker_for(model, seed=seed, use_graph=use_graph)
+    gt = PU._dev32(gt_boxes, trk.dev).reshape(-1, 15)
+    _track_with_gt(trk, frames, gt)
+    ious, distances = trk.score(gt, metrics=metrics)
+    return ious, distances, trk.boxes[:trk.t]
+
+
+def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None, tracker=None, metrics=None):
+    """evaluate_sequence over track_targets: gt_boxes (T,K,15), the K targets' boxes in the same frames.  valid (T,K) | None on
+    the host: 0 where a target has no annotation; a target is retired at its first such frame (its later rows repeat its last
+    box and are not scored, whatever `valid` says there).  -> (ious (T,K), distances (T,K), results (T,K,15)) device tensors."""
+    gt_host = gt_boxes.shape
+    trk = tracker if tracker is not None else multi_tracker_for(model, gt_host[1], seed=seed, use_graph=use_graph)
+    gt = PU._dev32(gt_boxes, trk.dev).reshape(gt_host[0], trk.K, 15)
+    if len(frames) != gt.shape[0]:
+        raise ValueError("%d frames, %d ground-truth boxes" % (len(frames), gt.shape[0]))
+    live = None
+    if valid is not None:
+        live = np.asarray(valid.detach().cpu().numpy() if torch.is_tensor(valid) else valid) != 0
+        if live.shape != (gt.shape[0], trk.K) or not live[0].all():
+            raise ValueError("valid must be (T,K) with every target annotated in frame 0")
+        live = np.logical_and.accumulate(live, axis=0)
+    trk.init(frames[0], gt[0])
+    by_gt = getattr(trk, "needs_ref_box", False)
+    back = 1 if by_gt and "PREVIOUS_GT" in str(trk.reference_BB).upper() else 0
+    for t in range(1, len(frames)):
+        if live is not None:
+            for k in np.flatnonzero(live[t - 1] & ~live[t]):
+                trk.retire(int(k))
+        if by_gt:
+            trk.update(frames[t], gt[t - back])
+        else:
+            trk.update(frames[t])
+    ious, distances = trk.score(gt, valid=live, metrics=metrics)
+    return ious, distances, trk.boxes[:trk.t]
+
+
+def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None):
+    """The test epoch (test_step / validation_step of the reference over its tracklets): every tracklet of `tracklets` -- a
+    sampler.DeviceTracklets, or any iterable of (frames, boxes) -- goes through evaluate_sequence on ONE tracker (one captured
+    graph for the epoch) and adds to ONE metrics.SuccessPrecision (`metrics` | None: a new one); the metric is read back once,
+    at the end.  -> {"success", "precision", "frames", "tracklets"}."""
+    from . import metrics as MT
+    trk = tracker_for(model, seed=seed, use_graph=use_graph)
+    m = metrics if metrics is not None else MT.SuccessPrecision(device=trk.dev)
+    count = 0
+    for item in tracklets:
+        frames, boxes = (item.frames, item.boxes) if hasattr(item, "frames") else item
+        evaluate_sequence(model, frames, boxes, tracker=trk, metrics=m)
+        count += 1
+    out = m.compute()
+    out["tracklets"] = count
+    return out
