@@ -369,7 +369,7 @@ int o3d_act_bwd_partials(const float* g, const float* Y, const float* scale, con
 int o3d_gmax_fwd(const float* Y, const float* scale, const float* shift, int B, int C, int N, float* out,
                  int32_t* argq, float* yarg, void* stream);
 
-/* Weight gradient of an aligned inner layer (Cin, Cout multiples of 64; P multiple of 128), workgroup
+/* Weight gradient of an aligned inner layer (Cin, Cout, P multiples of 64), workgroup
  * tile matched to the layer: dW (Cout,Cin) = sum dY * f(X), dY = A1*dN + A2*Y + A3 from dN (dense) or,
  * when dN == NULL, from the packed pooled source pk of o3d_pool_bwd_partials_split; f(x) =
  * max(x*in_scale+in_shift, 0), or x when in_scale == in_shift == NULL.  scratch:
@@ -420,6 +420,10 @@ int o3d_prep_weights(const long* jobs, int njobs, void* stream);
 int o3d_row_sum(const float* G, int C, long P, float* out, void* stream);
 
 int o3d_pw_tile(long P, int M);
+/* The kernel class o3d_pw_fwd (M = Cout, K = Cin) / o3d_pw_dgrad (M = Cin, K = Cout) launch for a shape, computed by the
+ * launcher's own rules (no launch): 2 = 64 x 64 wave tiles, 3 = 64 x 128, 4 = the split-K tile, 5 = the 32-row narrow
+ * tile, -1 = a shape the entries refuse.  tests/test_gemm_kernels_gpu.py asserts it for every case. */
+int o3d_pw_class(long P, int M, int K);
 
 /* Data gradient + weight gradient of one aligned inner layer in ONE launch (csrc/mlp_wgrad.hip::fused_bwd_kernel):
  * replaces the pair o3d_mlp_conv_wgrad2_c + o3d_mlp_conv_dgrad_c for Cin == 64, Cout in {64, 128} and a dense dN --

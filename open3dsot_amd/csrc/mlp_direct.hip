@@ -151,7 +151,8 @@ __device__ __forceinline__ void compute_group(const RawB<NT>& f, const float4& a
 //        pytorch_utils.py:124-155 with bn=False / activation=None, and the input gradient of a stack)
 // NT = 4: 128 columns per wave (one dwordx4 B load per k row); NT = 2: 64 columns (dwordx2) -- twice the waves
 // of half the length for launches that do not fill the chip (everything after compaction at batch 48).
-// MT = 2: 64 output rows per wave (MT = 1, 32 rows, is only used by the split-K tile further down).
+// MT = 2: 64 output rows per wave; MT = 1, 32 rows: the narrow tile of launch_direct_small (narrow_ok) and the split-K tile
+// further down.
 template <int WAVES, int MODE, int EPI, int NT, int MT = 2>
 __device__ __forceinline__ void direct_gemm_body(DirectArgs& a, const int bx, const int by, const long part_row = -1) {
     constexpr int POS = 32 * NT;
@@ -604,6 +605,15 @@ int launch_direct_nt(const DirectArgs& a, hipStream_t st) {
 
 static int pw_tile(long P, int M) { return o3d_direct_tile(P, M, 0); }
 
+// the 32-row narrow tile of launch_direct_small (rule and measurements there); never with a pooled source
+static bool narrow_ok(const DirectArgs& a, int tile) { return tile == 128 && a.M <= 128 && !a.pk; }
+
+// the tile launch_direct_small picks: 2 = 64 x 64 wave tiles, 3 = 64 x 128, 4 = the split-K tile
+static int small_class(const DirectArgs& a, int tile) {
+    if (splitk_ok(a, tile)) return 4;
+    return tile == 64 ? 2 : 3;
+}
+
 template <int MODE, int EPI>
 int launch_direct_small(const DirectArgs& a, int tile, hipStream_t st) {
     if constexpr (MODE <= B_DY && EPI <= 2) {
@@ -614,7 +624,7 @@ int launch_direct_small(const DirectArgs& a, int tile, hipStream_t st) {
     // waves, 64 accumulator registers (four per SIMD fit), the second reader of a B panel hits L1/L2.  Same box, M2-Track step:
     // 6.487 -> 6.439 ms; on the compact launches of BAT (launch_direct below) the same rule measured +0.02 / 0.00 ms: not there.
     if constexpr (MODE != B_DYPOOL) {
-        if (tile == 128 && a.M <= 128) return launch_direct_nt<MODE, EPI, 4, 1>(a, st);
+        if (narrow_ok(a, tile)) return launch_direct_nt<MODE, EPI, 4, 1>(a, st);
     }
     return tile == 64 ? launch_direct_nt<MODE, EPI, 2>(a, st) : launch_direct_nt<MODE, EPI, 4>(a, st);
 }
@@ -708,6 +718,20 @@ int o3d_direct_dgrad(const float* dN, const float* pk, int ns,
 // o3d_pw_tile(P, rows of the output) columns per partial row.
 extern "C" int o3d_pw_tile(long P, int M) { return pw_tile(P, M); }
 
+// Which kernel class o3d_pw_fwd (M = Cout, K = Cin) / o3d_pw_dgrad (M = Cin, K = Cout) launch for a shape, from the functions
+// the launcher itself calls: 2 = 64 x 64 wave tiles, 3 = 64 x 128, 4 = the split-K tile, 5 = the 32-row narrow tile,
+// -1 = a shape the entries refuse.  Read-only (no launch); the per-class tests assert it, so a retuned threshold names the
+// cases it moved.
+extern "C" int o3d_pw_class(long P, int M, int K) {
+    if (P <= 0 || P > 0x7fffffff || P % 64 != 0 || M <= 0 || M % DT_M != 0 || K <= 0 || K % 16 != 0) return -1;
+    const int tile = pw_tile(P, M);
+    if (tile == 128 && P % 128 != 0) return -1;
+    DirectArgs a = {};
+    a.M = M; a.K = K; a.P = (int)P; a.B = 1;
+    const int cls = small_class(a, tile);
+    return cls == 3 && narrow_ok(a, tile) ? 5 : cls;
+}
+
 extern "C" int o3d_pw_fwd(const float* X, const float* W, const float* in_scale, const float* in_shift,
                           const float* bias, const float* resid, int Cin, int Cout, long P, float* Y, float* part,
                           const float* stat_c, void* stream) {
@@ -761,12 +785,6 @@ int launch_pair_nt(const DirectArgs& a, const DirectArgs& b, hipStream_t st) {
     else
         hipLaunchKernelGGL((direct_gemm_pair_kernel<1, MODE, EPI, NT, MT>), dim3(tiles, smax, 2), dim3(64), 0, st, a, b);
     return o3d_launch_status();
-}
-
-// the tile launch_direct_small picks: 2 = 64 x 64 wave tiles, 3 = 64 x 128, 4 = the split-K tile
-static int small_class(const DirectArgs& a, int tile) {
-    if (splitk_ok(a, tile)) return 4;
-    return tile == 64 ? 2 : 3;
 }
 
 template <int MODE, int EPI>

@@ -32,6 +32,7 @@ capi.register("o3d_pack_rows_ld", [_vp, _i, _i, _i, _i, _vp, _l, _vp])
 capi.register("o3d_prep_weights", [_vp, _i, _vp])
 capi.register("o3d_row_sum", [_vp, _i, _l, _vp, _vp])
 capi.register("o3d_pw_tile", [_l, _i])
+capi.register("o3d_pw_class", [_l, _i, _i])
 capi.register("o3d_pw_fwd", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp])
 capi.register("o3d_pw_dgrad", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 capi.register("o3d_mlp_conv_wgrad2_group", [_vp, _i, _vp])
