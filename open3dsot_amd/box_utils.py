@@ -5,16 +5,10 @@ Mirror of the tensor helpers of datasets/points_utils.py: `rotz_batch_tensor` :3
 `remove_transform_points_tensor` :439-452.  Boxes are (B,4) = (x, y, z, yaw).  The reference mutates
 its `points` argument in place (`points -= ...`); these functions do not (same values returned).
 """
-import ctypes
-
 import torch
 
 from . import capi
 
-_vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-capi.register("o3d_motion_merge_fwd", [_vp, _l, _l, _vp, _vp, _i, _i, _vp, _vp, _vp])
-capi.register("o3d_offset_box", [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_motion_merge_bwd", [_vp, _l, _l, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp])
 
 _ROTZ = {}        # device -> (basis (2, 9), constant part (9,)) of the z rotation as a linear map of (cos, sin)
 

@@ -25,62 +25,9 @@ from torch.autograd.graph import increment_version as _increment_version
 from . import capi
 from .ops import QueryAndGroup
 
-_vp, _i, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
-capi.register("o3d_mlp_conv_fwd", [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_dgrad_wt", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
-                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_dgrad_plain", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad2", [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad2_scratch", [_i, _i, _i, _i])
-capi.register("o3d_mlp_conv_bwd_fused_rows", [_i, _i, ctypes.c_long])
-capi.register("o3d_mlp_conv_bwd_fused_scratch", [_i, _i, ctypes.c_long])
-capi.register("o3d_mlp_conv_bwd_fused_c", [_vp] * 10 + [_i, _i, ctypes.c_long, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_bn_relu_maxpool_fwd", [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp])
-
-_l = ctypes.c_long
-capi.register("o3d_compact_build", [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_group_expand_c3", [_vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _l, _vp, _vp, _vp, _vp])
-capi.register("o3d_group_dw0_xyz", [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _l, _i, _vp, _vp, _vp])
-capi.register("o3d_compact_build2", [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_group_expand_c", [_vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _l, _l, _vp, _vp, _vp, _vp])
-POOL_BWD_SPLIT = 8      # O3D_POOL_BWD_SPLIT of include/o3dsot.h
-capi.register("o3d_group_reduce_gather_scratch", [_i, _i, _i, _i, _i, _i, _i])
-capi.register("o3d_group_reduce_gather", [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp,
-                                          _vp, _vp, _vp, _vp])
-capi.register("o3d_pack_points", [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp])
-capi.register("o3d_center_term", [_vp, _vp, _i, _i, _i, _vp, _vp])
-capi.register("o3d_center_grad", [_vp, _vp, _i, _i, _i, _f, _vp, _vp])
-capi.register("o3d_center_term_out", [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp])
-capi.register("o3d_pool_fwd_c", [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_pool_fwd_ct", [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_pool_bwd_c", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _l, _l, _vp, _vp, _vp])
-capi.register("o3d_pool_bwd_dense", [_vp, _l, _l, _vp, _l, _l] + [_vp] * 7 + [_l, _l, _i, _i, _i, _i, _vp, _vp, _vp])
-capi.register("o3d_sa_eval_fused", [_vp, _l, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _l, _vp, _vp])
-capi.register("o3d_group_reduce_c", [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp,
-                                     _vp, _vp])
-capi.register("o3d_direct_tile", [ctypes.c_long, _i, _i])
-capi.register("o3d_bn_eval_consts", [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp])
-capi.register("o3d_mlp_conv_fwd_c", [_vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_dgrad_c", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad2_c", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _l, _vp, _vp, _vp])
-
-
-class _BnFinArgs(ctypes.Structure):       # o3d_bn_fin_args
-    _fields_ = [("part", _vp), ("nparts", _i), ("C", _i), ("count", _d), ("stat_c", _vp), ("gamma", _vp), ("beta", _vp),
-                ("running_mean", _vp), ("running_var", _vp), ("momentum", _f), ("eps", _f), ("mean", _vp), ("invstd", _vp),
-                ("scale", _vp), ("shift", _vp), ("meta", _vp), ("tile", _i), ("nparts1", _i), ("count1", _d)]
-
-
-class _BnBwdFinArgs(ctypes.Structure):    # o3d_bn_bwd_fin_args
-    _fields_ = [("part", _vp), ("nparts", _i), ("C", _i), ("count", _d), ("gamma", _vp), ("mean", _vp), ("invstd", _vp),
-                ("dgamma", _vp), ("dbeta", _vp), ("A1", _vp), ("A2", _vp), ("A3", _vp), ("meta", _vp), ("tile", _i),
-                ("nparts1", _i), ("count1", _d)]
-
-
-capi.register("o3d_bn_finalize", [_vp, _i, _vp])
-capi.register("o3d_bn_bwd_finalize", [_vp, _i, _vp])
+POOL_BWD_SPLIT = capi.CONSTANTS["O3D_POOL_BWD_SPLIT"]
+_BnFinArgs = capi.struct("o3d_bn_fin_args")
+_BnBwdFinArgs = capi.struct("o3d_bn_bwd_fin_args")
 
 TILE = 128   # point columns are padded to this (the widest wave tile of the GEMM kernels, csrc/mlp_direct.hip)
 ETILE = 256  # columns per workgroup tile of the layer-0 expand kernel (csrc/compact.hip expand_c_kernel)
@@ -418,8 +365,6 @@ def _direct_tile(lib, pmax, m):
     return lib.o3d_direct_tile(pmax, m, 1)
 
 
-capi.register("o3d_direct_tail_slots", [_i])
-capi.register("o3d_direct_tail_override", [_i])
 _TAIL = {"on": True, "applied": -1}       # "on": False = no split (tools/ab_hook.py fused._TAIL.on flips it for the same-box A/B)
 
 
@@ -969,9 +914,6 @@ def sa_group_mlp_pool_pair(grouper, mlp, a, b):
     for conv, bn in layers:
         params += [conv.weight, bn.weight, bn.bias]
     return FusedGroupedMLPCompact.apply(cfg, 2, a[0], a[1], a[2], idx_a, b[0], b[1], b[2], idx_b, *params)
-
-
-capi.register("o3d_sample_query", [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _f, _i, _vp, _vp])
 
 
 GEO_KEYS = ("centers", "ball_cnt", "ball_off", "gp", "cball", "cw", "meta")

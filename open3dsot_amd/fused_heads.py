@@ -26,23 +26,7 @@ from . import capi
 from .fused import _call, _const_vec, _eval_consts, _ptr, _stream, bn_bwd_coef, bn_bwd_fin_job, bn_fin_job, count_batches, \
     counters_begin, counters_end
 
-_vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-capi.register("o3d_pack_rows", [_vp, _i, _i, _i, _i, _vp, _vp])
-capi.register("o3d_pack_rows_ld", [_vp, _i, _i, _i, _i, _vp, _l, _vp])
-capi.register("o3d_prep_weights", [_vp, _i, _vp])
-capi.register("o3d_row_sum", [_vp, _i, _l, _vp, _vp])
-capi.register("o3d_pw_tile", [_l, _i])
-capi.register("o3d_pw_class", [_l, _i, _i])
-capi.register("o3d_pw_fwd", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp])
-capi.register("o3d_pw_dgrad", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_mlp_conv_wgrad2_group", [_vp, _i, _vp])
-
-
-class _WgradJob(ctypes.Structure):        # o3d_wgrad_job of include/o3dsot.h
-    _fields_ = [("dN", _vp), ("Y", _vp), ("A1", _vp), ("A2", _vp), ("A3", _vp), ("X", _vp), ("in_scale", _vp),
-                ("in_shift", _vp), ("Cin", _i), ("Cout", _i), ("P", _l), ("scratch", _vp), ("dW", _vp), ("out_rows", _i),
-                ("out_cols", _i)]
-
+_WgradJob = capi.struct("o3d_wgrad_job")
 
 # the weight gradients of a stack are ONE grouped launch (+ one reduction launch) at the end of its backward instead of a
 # launch + reduction per layer (csrc/mlp_wgrad.hip::wgrad2_group_kernel)
@@ -137,9 +121,7 @@ def _up(v, m):
     return -(-v // m) * m
 
 
-class _RowsSrc(ctypes.Structure):
-    _fields_ = [("p", ctypes.c_void_p), ("sb", ctypes.c_long), ("sc", ctypes.c_long), ("sn", ctypes.c_long),
-                ("C", ctypes.c_int)]
+_RowsSrc = capi.struct("o3d_rows_src")
 
 
 def pack_rows(sources, rows):
@@ -359,19 +341,8 @@ def chain_supported(sources, units):
 # seeds, models/head/rpn.py:44-54) advance in lockstep and a pair of launches of the same kind goes out as ONE launch
 # (csrc/mlp_direct.hip::direct_gemm_pair_kernel, csrc/mlp.hip::bn_*finalize_pair_kernel) -- the serial chain of ~15 us
 # sub-round launches is then half as long.
-class _PwFwdArgs(ctypes.Structure):       # o3d_pw_fwd_args
-    _fields_ = [("X", _vp), ("W", _vp), ("in_scale", _vp), ("in_shift", _vp), ("bias", _vp), ("resid", _vp), ("Cin", _i),
-                ("Cout", _i), ("P", _l), ("Y", _vp), ("part", _vp), ("stat_c", _vp)]
-
-
-class _PwDgradArgs(ctypes.Structure):     # o3d_pw_dgrad_args
-    _fields_ = [("dN", _vp), ("Y", _vp), ("A1", _vp), ("A2", _vp), ("A3", _vp), ("Wt", _vp), ("Cin", _i), ("Cout", _i),
-                ("P", _l), ("Yprev", _vp), ("scale_p", _vp), ("shift_p", _vp), ("mean_p", _vp), ("resid", _vp),
-                ("dNprev", _vp), ("part", _vp)]
-
-
-for _n in ("o3d_pw_fwd_pair", "o3d_pw_dgrad_pair"):
-    capi.register(_n, [_vp, _vp, _vp])
+_PwFwdArgs = capi.struct("o3d_pw_fwd_args")
+_PwDgradArgs = capi.struct("o3d_pw_dgrad_args")
 # single entry -> (pair entry, argument struct): every argument of the single call but the last, the stream
 _PAIRABLE = {"o3d_pw_fwd": ("o3d_pw_fwd_pair", _PwFwdArgs), "o3d_pw_dgrad": ("o3d_pw_dgrad_pair", _PwDgradArgs)}
 # entries that take an array of 1 or 2 job structs (fused._BnFinArgs / _BnBwdFinArgs): the generators yield the built job

@@ -3,15 +3,10 @@ as ONE launch of csrc/loss.hip: the five loss terms, the weighted total and the 
 total w.r.t. the network outputs.  `MatchingBaseModel.compute_loss` (torch ops, ~110 launches
 forward+backward) stays as the specification the kernel is tested against (tests/test_model_gpu.py).
 """
-import ctypes
-
 import torch
 
 from . import capi
 
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-capi.register("o3d_track_loss", [_vp] * 8 + [_i] * 4 + [_f] * 5 + [_vp] * 7)
-capi.register("o3d_m2track_loss", [_vp] * 14 + [_i] * 3 + [_f] * 7 + [_vp] * 10)
 
 _ON = {"on": True}
 # (the total is its own 0-d output instead of `losses[0]`, whose backward would be a zero fill + a select copy; and there is no

@@ -8,27 +8,12 @@ each cloud ("gmax", AdaptiveMaxPool1d(1)).  Parameters stay in the caller's nn.C
 modules.  A Conv1d bias in front of a training-mode BatchNorm cancels in the output and has zero
 gradient; it only shifts the running mean, which is updated accordingly.
 """
-import ctypes
-
 import torch
 
 from . import capi
 from .fused import _call, _check_versions, _const_vec, _eval_consts, _ptr, _stream, _versions, bn_bwd_finalize, bn_finalize, \
     count_batches, POOL_BWD_SPLIT, TILE
 from .fused import bias_fix as _fused_bias_fix
-
-_vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-capi.register("o3d_pw_tile", [_l, _i])
-capi.register("o3d_pw_fwd", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp])
-capi.register("o3d_pw_dgrad", [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_gmax_bwd_pk", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp])
-capi.register("o3d_thin_bwd_scratch", [])
-capi.register("o3d_thin_bwd", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp])
-capi.register("o3d_bn_relu_apply", [_vp, _vp, _vp, _i, _l, _vp, _vp])
-capi.register("o3d_act_bwd_partials", [_vp, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _vp])
-capi.register("o3d_gmax_fwd", [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_pw_fwd_cloud", [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_cloud_sum_dy", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp])
 
 
 class _Cfg:

@@ -18,11 +18,6 @@ from torch import nn
 from . import capi
 from .fused import _call, _ptr, _stream, count_batches
 
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-capi.register("o3d_row_mlp_fwd", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_row_mlp_bwd", [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i,
-                                  _vp, _vp, _vp, _vp, _vp, _vp])
-
 RMAX = 64
 _ON = {"on": True}
 
@@ -182,21 +177,8 @@ def seq_rows(seq, x):
 
 
 # ---- several stacks of the same depth on the same rows: one launch per layer for all of them ----------------------------------
-class _RowFwdArgs(ctypes.Structure):      # o3d_row_fwd_args
-    _fields_ = [("X", _vp), ("ldx", _i), ("W", _vp), ("bias", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp),
-                ("running_var", _vp), ("momentum", _f), ("eps", _f), ("training", _i), ("relu", _i), ("R", _i), ("Cin", _i),
-                ("Cout", _i), ("Z", _vp), ("Y", _vp), ("mean", _vp), ("invstd", _vp)]
-
-
-class _RowBwdArgs(ctypes.Structure):      # o3d_row_bwd_args
-    _fields_ = [("dY", _vp), ("lddy", _i), ("dZup", _vp), ("Wup", _vp), ("Cup", _i), ("input_mode", _i), ("dX", _vp),
-                ("lddx", _i), ("Z", _vp), ("gamma", _vp), ("beta", _vp), ("mean", _vp), ("invstd", _vp), ("training", _i),
-                ("relu", _i), ("X", _vp), ("ldx", _i), ("R", _i), ("Cin", _i), ("C", _i), ("dZ", _vp), ("dW", _vp), ("db", _vp),
-                ("dgamma", _vp), ("dbeta", _vp)]
-
-
-for _n in ("o3d_row_mlp_fwd_group", "o3d_row_mlp_bwd_group", "o3d_row_mlp_input_grad"):
-    capi.register(_n, [_vp, _i, _vp])
+_RowFwdArgs = capi.struct("o3d_row_fwd_args")
+_RowBwdArgs = capi.struct("o3d_row_bwd_args")
 GROUP_MAX = 4
 
 

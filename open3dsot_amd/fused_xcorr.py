@@ -10,19 +10,11 @@ csrc/mlp_wgrad.hip, csrc/compact.hip) with every column live.  The cosine simila
 small GEMM-shaped products) is one kernel each way (`CosineSimMap`, round 4; torch.bmm + norms until then); its gradient
 arrives from the layer-0 backward kernel.
 """
-import ctypes
-
 import torch
 
 from . import capi
 from .fused import _call, _const_vec, _eval_consts, _layers, _ptr, _stream, bn_bwd_finalize, bn_finalize, count_batches
 from .fused_heads import _up, pack_rows, prep_for
-
-_vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-capi.register("o3d_xcorr_expand", [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_xcorr_reduce_groups", [_i])
-capi.register("o3d_pool_bwd_partials_split", [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_xcorr_reduce", [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp])
 
 
 def supported(mlp, t_feat, s_feat):
@@ -210,10 +202,6 @@ class FusedP2BXCorr(torch.autograd.Function):
         for l in range(L):
             gw += [grads[3 * l].view(Ws[l].shape[0], Ws[l].shape[1], 1, 1), grads[3 * l + 1], grads[3 * l + 2]]
         return (None, dsim, dxyz, dfeat, *gw)
-
-
-capi.register("o3d_cosine_sim_fwd", [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_cosine_sim_bwd", [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp])
 
 
 class CosineSimMap(torch.autograd.Function):

@@ -8,15 +8,11 @@ launch of o3d_track_score (csrc/metrics.hip) over device-resident boxes, and its
 
 A box is 15 floats: centre (3), wlh (3), row-major rotation (9), as everywhere in this package.  There is no CPU path.
 """
-import ctypes
-
 import torch
 
 from . import capi
 from .points_utils import _need_gpu
 
-_vp, _i = ctypes.c_void_p, ctypes.c_int
-capi.register("o3d_track_score", [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp])
 
 MAX_THRESHOLDS = 64
 

@@ -7,15 +7,10 @@ flat buffers and the gradients read where autograd left them (device job table, 
 one ~10 us launch.  `state_dict()` has torch.optim.Adam's layout (`step`, `exp_avg`, `exp_avg_sq` per parameter), so
 checkpoints are interchangeable with the reference's optimizer.
 """
-import ctypes
-
 import torch
 from torch.autograd.graph import increment_version
 
 from . import capi
-
-_vp, _i, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-capi.register("o3d_adam_step", [_vp, _i, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _d, _vp])
 
 
 class FlatAdam(torch.optim.Optimizer):

@@ -18,9 +18,6 @@ import torch
 
 from . import capi
 
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-capi.register("o3d_boxcloud", [_vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp])
-
 
 def _dev32(x, dev):
     return torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x, dtype=torch.float32,
@@ -76,29 +73,10 @@ def regularize_pc(points, sample_size, seed=None):
 # ---- the tracking front end (csrc/track.hip): crops, resampling and the box update on the device ---------------------------
 # A box travels as the triple (center, wlh, rot) above or, between kernels, as ONE (15,) float32 GPU tensor
 # [center (3) | wlh (3) | rot (9) row-major] -- `pack_box` / `unpack_box`.
-CROP_SUBWINDOW, CROP_MODEL = 0, 1
-CROP_MAX_JOBS = 4
-
-
-class _CropJob(ctypes.Structure):            # o3d_crop_job (include/o3dsot.h)
-    _fields_ = [("points", _vp), ("n", _i), ("box", _vp), ("scale", _f), ("offset", _f), ("mode", _i), ("out", _vp),
-                ("capacity", _i), ("count", _vp)]
-
-
-class _ResampleJob(ctypes.Structure):        # o3d_resample_job
-    _fields_ = [("src", _vp), ("n_src", _i), ("idx", _vp), ("dst", _vp), ("n", _i), ("zero", _i)]
-
-
-capi.register("o3d_track_crop_scratch", [_vp, _i])
-capi.register("o3d_track_crop", [_vp, _i, _vp, _i, _vp])
-capi.register("o3d_track_resample", [_vp, _i, _vp])
-capi.register("o3d_track_offset_box", [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
-capi.register("o3d_track_motion_input", [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp])
-capi.register("o3d_track_crop_multi_scratch", [_vp, _i])
-capi.register("o3d_track_crop_multi", [_vp, _i, _vp, ctypes.c_long, _vp])
-capi.register("o3d_track_resample_multi", [_vp, _i, _vp])
-capi.register("o3d_track_offset_box_multi", [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp])
-capi.register("o3d_track_motion_input_multi", [_vp, _i, _i, _vp, _i, _vp, _vp, _vp])
+CROP_SUBWINDOW, CROP_MODEL = capi.CONSTANTS["O3D_CROP_SUBWINDOW"], capi.CONSTANTS["O3D_CROP_MODEL"]
+CROP_MAX_JOBS = capi.CONSTANTS["O3D_CROP_MAX_JOBS"]
+_CropJob = capi.struct("o3d_crop_job")
+_ResampleJob = capi.struct("o3d_resample_job")
 
 
 def _need_gpu(t, what):
@@ -174,19 +152,12 @@ def resample_jobs(jobs):
 # The tables are arrays of C structs holding device pointers.  They are described here as numpy record types with the C
 # layout, so that a caller (tracking.MultiTargetTracker, tracking.MultiMotionTracker) fills a whole table in a pinned buffer with a few array assignments
 # and uploads it with one asynchronous copy.
-CROP_MULTI_MAX_TARGETS = 1024
-CROP_MULTI_CHUNK = 32                        # targets the crop stages in LDS at a time (O3D_CROP_MULTI_CHUNK)
-CROP_TARGET = np.dtype([("box", "u8"), ("scale", "f4"), ("offset", "f4"), ("mode", "i4"), ("out", "u8"), ("capacity", "i4"),
-                        ("count", "u8")], align=True)                                         # o3d_crop_target, 48 bytes
-RESAMPLE_JOB = np.dtype([("src", "u8"), ("n_src", "i4"), ("idx", "u8"), ("dst", "u8"), ("n", "i4"), ("zero", "i4")],
-                        align=True)                                                           # o3d_resample_job, 40 bytes
-MOTION_JOB = np.dtype([("prev", "u8"), ("n_prev", "i4"), ("cur", "u8"), ("n_this", "i4"), ("idx", "u8"), ("zero_prev", "i4"),
-                       ("zero_this", "i4")], align=True)                                      # o3d_motion_job, 48 bytes
-assert CROP_TARGET.itemsize == 48 and RESAMPLE_JOB.itemsize == ctypes.sizeof(_ResampleJob) == 40 and MOTION_JOB.itemsize == 48
-
-
-class _CropGroup(ctypes.Structure):          # o3d_crop_group
-    _fields_ = [("points", _vp), ("n", _i), ("targets", _vp), ("n_targets", _i)]
+CROP_MULTI_MAX_TARGETS = capi.CONSTANTS["O3D_CROP_MULTI_MAX_TARGETS"]
+CROP_MULTI_CHUNK = capi.CONSTANTS["O3D_CROP_MULTI_CHUNK"]      # targets the crop stages in LDS at a time
+CROP_TARGET = capi.dtype("o3d_crop_target")
+RESAMPLE_JOB = capi.dtype("o3d_resample_job")
+MOTION_JOB = capi.dtype("o3d_motion_job")
+_CropGroup = capi.struct("o3d_crop_group")
 
 
 def crop_target_table(targets, device):
@@ -465,27 +436,10 @@ def points_in_box(box, points, wlh_factor=1.0):
 
 
 # ---- training batches built on the device (csrc/train_batch.hip; open3dsot_amd/sampler.py is the caller) --------------------
-CROP_MAX_GROUPS = 4096
-TRAIN_MAX_CANDIDATES = 1024
-CROP_PLAN = np.dtype([("points", "u8"), ("n", "i4"), ("targets", "u8"), ("n_targets", "i4"), ("wg_start", "i4"),
-                      ("row_start", "i4"), ("sbase", "i8")], align=True)                       # o3d_crop_plan, 48 bytes
-
-
-class _TrainSampleArgs(ctypes.Structure):    # o3d_train_sample_args
-    _fields_ = [("sel", _vp), ("counts", _vp), ("crop_first", _vp), ("crop_template", _vp), ("crop_search", _vp),
-                ("cap_first", _i), ("cap_template", _i), ("cap_search", _i), ("J", _i), ("B", _i), ("M", _i), ("N", _i),
-                ("idx_t", _vp), ("idx_s", _vp), ("seed", ctypes.c_uint), ("counter", ctypes.c_uint),
-                ("search_box", _vp), ("model_box", _vp), ("cand_box_label", _vp), ("cand_bbox_size", _vp),
-                ("template_points", _vp), ("search_points", _vp), ("seg_label", _vp), ("box_label", _vp), ("bbox_size", _vp),
-                ("bc_boxes", _vp), ("used_t", _vp), ("used_s", _vp)]
-
-
-assert CROP_PLAN.itemsize == 48 and ctypes.sizeof(_TrainSampleArgs) == 192
-capi.register("o3d_track_crop_groups_scratch", [_vp, _i, _vp])
-capi.register("o3d_track_crop_groups", [_vp, _vp, _i, _vp, ctypes.c_long, _vp])
-capi.register("o3d_train_select", [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_train_labels", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_train_sample", [_vp, _vp])
+CROP_MAX_GROUPS = capi.CONSTANTS["O3D_CROP_MAX_GROUPS"]
+TRAIN_MAX_CANDIDATES = capi.CONSTANTS["O3D_TRAIN_MAX_CANDIDATES"]
+CROP_PLAN = capi.dtype("o3d_crop_plan")
+_TrainSampleArgs = capi.struct("o3d_train_sample_args")
 
 
 def crop_groups_plan(plan):
@@ -559,28 +513,8 @@ def train_sample(args, device):
 
 
 # ---- M2-Track training batches (csrc/train_batch.hip; sampler.MotionBatchBuilder is the caller) -----------------------------
-CROP_AUG = np.dtype([("enabled", "i4"), ("box", "f4", (15,)), ("A", "f4", (9,)), ("c", "f4", (3,))], align=True)      # o3d_crop_aug
-
-
-class _TrainMotionSampleArgs(ctypes.Structure):    # o3d_train_motion_sample_args
-    _fields_ = [("sel", _vp), ("counts", _vp), ("crop_prev", _vp), ("crop_this", _vp),
-                ("cap_prev", _i), ("cap_this", _i), ("J", _i), ("B", _i), ("N", _i),
-                ("idx_prev", _vp), ("idx_this", _vp), ("candidate_id", _vp), ("seed", ctypes.c_uint), ("counter", ctypes.c_uint),
-                ("prev_box", _vp), ("this_box", _vp), ("canon_box", _vp),
-                ("cand_box_label", _vp), ("cand_box_label_prev", _vp), ("cand_motion_label", _vp), ("cand_motion_state", _vp),
-                ("cand_bbox_size", _vp),
-                ("points", _vp), ("candidate_bc", _vp), ("seg_label", _vp),
-                ("box_label", _vp), ("box_label_prev", _vp), ("motion_label", _vp), ("motion_state_label", _vp), ("bbox_size", _vp),
-                ("bc_boxes", _vp), ("xyz_halves", _vp), ("used_prev", _vp), ("used_this", _vp)]
-
-
-assert CROP_AUG.itemsize == 112 and ctypes.sizeof(_TrainMotionSampleArgs) == 248
-capi.register("o3d_train_augment", [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp])
-capi.register("o3d_track_crop_groups_aug", [_vp, _vp, _vp, _i, _vp, ctypes.c_long, _vp])
-capi.register("o3d_train_inside_box", [_vp, _i, _vp, _f, _vp, _vp])
-capi.register("o3d_train_motion_labels", [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-capi.register("o3d_train_select_motion", [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_train_motion_sample", [_vp, _vp])
+CROP_AUG = capi.dtype("o3d_crop_aug")
+_TrainMotionSampleArgs = capi.struct("o3d_train_motion_sample_args")
 
 
 def _addr(t):

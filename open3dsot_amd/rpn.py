@@ -8,16 +8,10 @@ proposal MLP -> (B, num_proposal, 5) = (x, y, z, theta, objectness).
 import torch
 from torch import nn
 
-import ctypes
-
 from . import capi
 from . import nn_blocks as pt_utils
 from .sa_modules import PointnetSAModule
 
-_vp, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-capi.register("o3d_rpn_votes_fwd", [_vp, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp])
-capi.register("o3d_rpn_votes_bwd", [_vp, _vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _vp])
-capi.register("o3d_box_assemble", [_vp, _l, _l, _l, _vp, _i, _i, _vp, _vp])
 
 _GLUE = {"on": True}     # TEST hook: False = the torch-op form of the reference (what the kernels are tested against)
 

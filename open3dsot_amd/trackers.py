@@ -15,8 +15,6 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-import ctypes
-
 from . import capi, fused, fused_heads, fused_loss, optim
 from . import nn_blocks as pt_utils
 from .backbone import Pointnet_Backbone
@@ -40,10 +38,6 @@ def make_config(base, **overrides):
     cfg = dict(base)
     cfg.update(overrides)
     return SimpleNamespace(**cfg)
-
-
-capi.register("o3d_best_proposal", [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p])
 
 
 def best_proposal(boxes):

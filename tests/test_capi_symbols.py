@@ -87,17 +87,45 @@ def header_prototypes():
     return protos
 
 
+KIND = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_long: "l", ctypes.c_float: "f", ctypes.c_double: "d"}
+
+
 def test_ctypes_signatures_match_the_header():
-    """every argtypes list registered by the Python binding has the arity and the argument kinds of its
-    prototype in include/o3dsot.h (a silent ctypes mismatch corrupts arguments instead of failing)"""
-    from open3dsot_amd import capi, fused, fused_heads, fused_loss, fused_pointwise, fused_rows, fused_xcorr, optim, points_utils  # noqa: F401  (they register)
+    """every prototype of include/o3dsot.h is bound, and every argtypes list the binding derives has the arity and the
+    argument kinds this file's own parser reads from the prototype (a silent ctypes mismatch corrupts arguments instead of
+    failing)"""
+    from open3dsot_amd import capi
     protos = header_prototypes()
-    kind = {ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_long: "l", ctypes.c_float: "f", ctypes.c_double: "d"}
-    assert len(capi.SIGNATURES) >= 40
+    assert len(protos) >= 40
+    assert set(capi.SIGNATURES) == set(protos) == set(declared_symbols())
     for name, argtypes in capi.SIGNATURES.items():
-        assert name in protos, "%s is bound but not declared in include/o3dsot.h" % name
-        got = [kind[a] for a in argtypes]
+        got = [KIND[a] for a in argtypes]
         assert got == protos[name], (name, got, protos[name])
+
+
+def test_signatures_and_return_types_hand_pinned():
+    """one entry of each flavour written out by hand -- two parsers cannot be wrong the same way here -- and the return type
+    of every entry: long for the *_scratch sizes and o3d_xcorr_reduce_groups, a string for o3d_version, int elsewhere"""
+    from open3dsot_amd import capi
+    pins = {"o3d_ball_query": "ppiiifipp",                                     # a float
+            "o3d_mlp_conv_fwd_c": "ppppiilpplipppp",                           # longs between ints
+            "o3d_adam_step": "pipppdddddddp",                                  # doubles
+            "o3d_bn_finalize": "pip",                                          # a struct pointer and a count
+            "o3d_thin_bwd_scratch": "",                                        # (void)
+            "o3d_track_crop_groups_aug": "pppiplp",                            # const T* const*
+            "o3d_version": ""}
+    for name, kinds in pins.items():
+        assert "".join(KIND[a] for a in capi.SIGNATURES[name]) == kinds, name
+    lib = capi.load()
+    assert len(capi.RESTYPES) == len(capi.SIGNATURES)
+    for name in capi.SIGNATURES:
+        want = ctypes.c_char_p if name == "o3d_version" else \
+            ctypes.c_long if name.endswith("_scratch") or name == "o3d_xcorr_reduce_groups" else ctypes.c_int
+        assert capi.RESTYPES[name] is want, name
+        fn = getattr(lib, name)
+        assert fn.restype is want and list(fn.argtypes) == capi.SIGNATURES[name], name
+    assert sum(n.endswith("_scratch") for n in capi.SIGNATURES) >= 7
+    assert not hasattr(capi, "register")
 
 
 def test_entry_points_reject_bad_arguments_before_touching_the_device():
@@ -243,6 +271,143 @@ def test_row_group_structs_match_the_header_layout():
         assert fields == [f[0] for f in cls._fields_], (name, fields, [f[0] for f in cls._fields_])
 
 
+def header_structs():
+    """name -> field names, in order, of every `typedef struct {...} name;` of include/o3dsot.h (the field parser of
+    test_row_group_structs_match_the_header_layout for all of them: comments stripped, `box[15]` is the field `box`)"""
+    src = open(os.path.join(ROOT, "include", "o3dsot.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    structs = {}
+    for body, name in re.findall(r"typedef struct \{([^}]*)\}\s*(\w+);", src):
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if not decl:
+                continue
+            base, names = re.match(r"((?:const\s+)?\w+\s*\**)\s*(.*)", decl).groups()
+            fields += [re.sub(r"\[\d+\]", "", n).strip().lstrip("*").strip() for n in names.split(",")]
+        structs[name] = fields
+    return structs
+
+
+# sizeof of the 17 job / argument structs on the LP64 hosts this library is built for, written out by hand
+STRUCT_SIZES = {"o3d_bn_fin_args": 128, "o3d_bn_bwd_fin_args": 112, "o3d_rows_src": 40, "o3d_pw_fwd_args": 88,
+                "o3d_pw_dgrad_args": 120, "o3d_wgrad_job": 104, "o3d_row_fwd_args": 128, "o3d_row_bwd_args": 168,
+                "o3d_crop_job": 64, "o3d_resample_job": 40, "o3d_crop_target": 48, "o3d_crop_group": 32, "o3d_motion_job": 48,
+                "o3d_crop_plan": 48, "o3d_train_sample_args": 192, "o3d_crop_aug": 112, "o3d_train_motion_sample_args": 248}
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """every struct the binding derives from the header has the size and the field offsets the host C compiler gives the same
+    header, and so have the numpy records of the device tables: all 17, where the kernels' static_asserts cover 8"""
+    from open3dsot_amd import capi, points_utils as PU
+    structs = header_structs()
+    assert set(structs) == set(STRUCT_SIZES)
+    for name, fields in structs.items():
+        cls = capi.struct(name)
+        assert cls is capi.struct(name) and issubclass(cls, ctypes.Structure)                   # cached
+        assert [f[0] for f in cls._fields_] == fields, name
+        assert ctypes.sizeof(cls) == STRUCT_SIZES[name], name
+    records = {"o3d_crop_target": PU.CROP_TARGET, "o3d_motion_job": PU.MOTION_JOB, "o3d_crop_plan": PU.CROP_PLAN,
+               "o3d_crop_aug": PU.CROP_AUG, "o3d_resample_job": PU.RESAMPLE_JOB}
+    for name, rec in records.items():
+        assert rec == capi.dtype(name) and list(rec.names) == structs[name] and rec.itemsize == STRUCT_SIZES[name], name
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if cc is None:
+        pytest.skip("no host C compiler")
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "o3dsot.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        lines.append('    printf("%s  %%zu\\n", sizeof(%s));' % (name, name))
+        lines += ['    printf("%s %s %%zu\\n", offsetof(%s, %s));' % (name, f, name, f) for f in fields]
+    lines += ["    return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", exe, str(tmp_path / "layout.c")], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    compiled = {(ln.split(" ")[0], ln.split(" ")[1]): int(ln.split(" ")[2]) for ln in out.splitlines()}
+    assert len(compiled) == sum(len(f) + 1 for f in structs.values())
+    for name, fields in structs.items():
+        cls, rec = capi.struct(name), capi.dtype(name)
+        assert ctypes.sizeof(cls) == rec.itemsize == compiled[(name, "")], name
+        for f in fields:
+            assert getattr(cls, f).offset == rec.fields[f][1] == compiled[(name, f)], (name, f)
+
+
+GOOD_HEADER = """
+#ifndef X_H_
+#define X_H_
+#include <stdint.h>
+#define O3D_LIMIT 7
+#define O3D_ENEG (-3)
+typedef struct { const float* p; long sb, sc; int C; float box[3]; unsigned seed; } o3d_a;  /* a comment; with ( */
+const char* o3d_name(void);
+long o3d_size(const o3d_a* jobs, int n);
+int o3d_run(const o3d_a* const* tab, int32_t* out, float r, double lr,
+            long ld, void* stream);
+#endif
+"""
+
+
+def test_the_header_parser_refuses_what_it_does_not_understand():
+    """the parser behind the binding never guesses: text outside its grammar raises at import instead of yielding a wrong
+    argtypes list or layout"""
+    from open3dsot_amd import capi
+    sig, res, structs, consts = capi._parse_header(GOOD_HEADER)
+    assert {n: "".join(KIND[a] for a in v) for n, v in sig.items()} == {"o3d_name": "", "o3d_size": "pi", "o3d_run": "ppfdlp"}
+    assert res == {"o3d_name": ctypes.c_char_p, "o3d_size": ctypes.c_long, "o3d_run": ctypes.c_int}
+    assert consts == {"O3D_LIMIT": 7, "O3D_ENEG": -3}
+    assert structs == {"o3d_a": [("p", ctypes.c_void_p), ("sb", ctypes.c_long), ("sc", ctypes.c_long), ("C", ctypes.c_int),
+                                 ("box", ctypes.c_float * 3), ("seed", ctypes.c_uint)]}
+    bad = {"an unknown type": "int o3d_f(size_t n);",
+           "a pointer to an unknown type": "int o3d_f(const o3d_b* jobs);",
+           "a by-value struct field": "typedef struct { o3d_a inner; int n; } o3d_b;",
+           "a by-value struct parameter": "int o3d_f(o3d_a job);",
+           "a function-pointer parameter": "int o3d_f(int (*cb)(int), void* stream);",
+           "a function-pointer field": "typedef struct { int (*cb)(int); } o3d_b;",
+           "a bit-field": "typedef struct { int a : 3; } o3d_b;",
+           "a two-dimensional array": "typedef struct { float rot[3][3]; } o3d_b;",
+           "a nested struct": "typedef struct { struct { int a; } in; } o3d_b;",
+           "a two-word type": "typedef struct { unsigned int a; } o3d_b;",
+           "an array parameter": "int o3d_f(float box[15]);",
+           "an unknown return type": "float o3d_f(int n);",
+           "a prototype that lost its semicolon": "int o3d_f(int n)\nint o3d_g(int n);",
+           "a prototype split by a stray semicolon": "int o3d_f(int n;\n void* stream);",
+           "a second declaration of a name": "int o3d_run(int n);",
+           "a macro with arguments": "#define O3D_MAX(a, b) ((a) > (b) ? (a) : (b))",
+           "a constant that is no integer": "#define O3D_EPS 1e-5f",
+           "a conditional": "#if defined(O3D_LIMIT)\nint o3d_f(int n);\n#endif"}
+    for what, text in bad.items():
+        with pytest.raises(capi.O3DError):
+            capi._parse_header(GOOD_HEADER.replace("#endif", text + "\n#endif"))
+            pytest.fail("the parser accepted %s" % what)
+
+
+def test_a_missing_header_fails_loudly(monkeypatch, tmp_path):
+    from open3dsot_amd import capi
+    monkeypatch.setattr(capi, "HEADER", str(tmp_path / "o3dsot.h"))
+    with pytest.raises(capi.O3DError, match=re.escape(str(tmp_path / "o3dsot.h"))):
+        capi._read_header()
+
+
+def header_constants():
+    src = open(os.path.join(ROOT, "include", "o3dsot.h")).read()
+    return {n: int(v) for n, v in re.findall(r"^#define\s+(O3D_\w+)\s+\(?(-?\d+)\)?", src, flags=re.M)}
+
+
+def test_limits_come_from_the_header():
+    """capi.CONSTANTS holds the header's integer #defines, and the Python names that used to repeat them as literals"""
+    from open3dsot_amd import capi, fused, points_utils as PU
+    assert capi.CONSTANTS == header_constants() and len(capi.CONSTANTS) >= 11
+    assert (capi.CONSTANTS["O3D_OK"], capi.CONSTANTS["O3D_EINVAL"], capi.CONSTANTS["O3D_ELAUNCH"]) == (0, -1, -2)
+    assert fused.POOL_BWD_SPLIT == capi.CONSTANTS["O3D_POOL_BWD_SPLIT"] == 8
+    assert PU.CROP_MAX_JOBS == capi.CONSTANTS["O3D_CROP_MAX_JOBS"] == 4
+    assert PU.CROP_SUBWINDOW == capi.CONSTANTS["O3D_CROP_SUBWINDOW"] == 0
+    assert PU.CROP_MODEL == capi.CONSTANTS["O3D_CROP_MODEL"] == 1
+    assert PU.CROP_MULTI_MAX_TARGETS == capi.CONSTANTS["O3D_CROP_MULTI_MAX_TARGETS"] == 1024
+    assert PU.CROP_MULTI_CHUNK == capi.CONSTANTS["O3D_CROP_MULTI_CHUNK"] == 32
+    assert PU.CROP_MAX_GROUPS == capi.CONSTANTS["O3D_CROP_MAX_GROUPS"] == 4096
+    assert PU.TRAIN_MAX_CANDIDATES == capi.CONSTANTS["O3D_TRAIN_MAX_CANDIDATES"] == 1024
+
+
 def test_no_tuning_switches_in_the_product():
     """one product path: the kernels read no environment variable, and the Python package knows exactly two `O3D_*`
     variables -- O3D_LIB_VARIANT (load an A/B build of the library, tools/build_variant.sh) and O3D_REQUIRE_GRAPH (fail
@@ -256,4 +421,5 @@ def test_no_tuning_switches_in_the_product():
     names = set()
     for f in glob.glob(os.path.join(ROOT, "open3dsot_amd", "*.py")) + glob.glob(os.path.join(ROOT, "pointnet2_ops", "*.py")):
         names |= set(re.findall(r"[\"'](O3D_[A-Z0-9_]+)[\"']", open(f).read()))
+    names -= set(header_constants())      # the limits the modules read from capi.CONSTANTS are the header's #defines, not variables
     assert names <= {"O3D_LIB_VARIANT", "O3D_REQUIRE_GRAPH"}, names
