@@ -273,6 +273,18 @@ int o3d_direct_tile(long P, int M, int compact);
 int o3d_direct_tail_slots(int M);
 /* test hook: -1 automatic (default), 0 no remainder split, S > 0 pretend S slots for every shape */
 int o3d_direct_tail_override(int slots);
+/* The kernel class o3d_mlp_conv_fwd_c (M = Cout, K = Cin) / o3d_mlp_conv_dgrad_c (M = Cin, K = Cout) launch for ldp columns and
+ * the caller's tile, computed by the launcher's own rules (no launch): 2 = 64 x 64 wave tiles, 3 = 64 x 128, 4 = the split-K
+ * tile, -1 = a shape the entries refuse.  A class-3 launch splits its remainder tiles when o3d_direct_tail_slots(M) > 0.
+ * tests/test_compact_gemm_kernels_gpu.py asserts it for every case. */
+int o3d_direct_class(long ldp, int M, int K, int tile);
+/* Columns: every entry below works on the columns [0, meta[0]) of segment 0 and [start1, start1 + meta[4]) of segment 1
+ * (meta[4*s] = the live columns rounded up to 256) and neither reads nor writes any other column of an operand.  The padding
+ * columns [live, live rounded up) carry w = 0 and are computed like live ones: the forward stores Y there and its statistics
+ * weigh them by w = 0 (so X must be finite there).  The backward entries ASSUME dN == 0 AND finite Y, X / Yprev on the padding
+ * columns: dY = A1*dN + w*(A2*Y + A3) is then 0 there, so padding adds nothing to dW, dNprev is written as 0 there, and the
+ * data gradient's statistics -- which carry no w -- see only live columns.  (o3d_pool_bwd_c / o3d_pool_bwd_dense write such a
+ * dN, and each data gradient hands the next one zeros.)  A non-zero dN on a padding column is counted like a live column. */
 int o3d_mlp_conv_fwd_c(const float* X, const float* W, const float* in_scale, const float* in_shift, int Cin,
                        int Cout, long ldp, const float* w, const int32_t* meta, long start1, int tile, float* Y,
                        float* part, const float* stat_c, void* stream);

@@ -682,6 +682,17 @@ extern "C" int o3d_direct_tile(long P, int M, int compact) {
     return P <= 65536L ? 64 : 128;
 }
 
+// Which kernel class o3d_mlp_conv_fwd_c (M = Cout, K = Cin) / o3d_mlp_conv_dgrad_c (M = Cin, K = Cout) launch for a compact
+// operand of ldp columns and the caller's `tile`, from the functions launch_direct itself calls: 2 = 64 x 64 wave tiles,
+// 3 = 64 x 128, 4 = the split-K tile, -1 = a shape the entries refuse.  Read-only (no launch).  Whether a class-3 launch cuts its
+// remainder tiles into column blocks is o3d_direct_tail_slots(M) > 0.
+extern "C" int o3d_direct_class(long ldp, int M, int K, int tile) {
+    if (ldp <= 0 || ldp > 0x7fffffff || M <= 0 || K <= 0 || !o3d_direct_ok(M, K, (int)ldp) || (tile != 64 && tile != 128)) return -1;
+    DirectArgs a = {};
+    a.M = M; a.K = K; a.P = (int)ldp; a.B = 1;
+    return small_class(a, tile);      // launch_direct's rule: split-K when splitk_ok, else the tile's own class (no narrow tile)
+}
+
 // forward: Y = W . f(X), see o3d_mlp_conv_fwd
 int o3d_direct_fwd(const float* X, const float* W, const float* in_scale, const float* in_shift, int B, int Cin,
                    int Cout, int P, float* Y, float* part, const float* stat_c, const float* w, const int32_t* meta,
