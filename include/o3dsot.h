@@ -751,6 +751,41 @@ typedef struct { const float* prev; int n_prev; const float* cur; int n_this; co
 int o3d_track_motion_input_multi(const o3d_motion_job* jobs, int K, int N, const float* wlh, int first_frame, float* points,
                                  float* candidate_bc, void* stream);
 
+/* ---- the free-running tracking loop (tracking.SequenceTracker / MotionSequenceTracker with sampling="device"): the crop counts
+ * stay on the device and the resampling indices are drawn there, so that a frame is enqueued without a host synchronisation.
+ * The draw is the keyed draw of the training batches, sample_index(key, i, n, S) (csrc/train_batch.hip writes it down; n <= 2
+ * zero-fills, n == S is the identity, S > n draws with replacement, S < n without); a key travels as an int carrying the bits
+ * of the uint32.  Indices therefore differ from regularize_pc's numpy draw by construction.
+ *
+ * o3d_track_resample_drawn: n_jobs (1 or 2; job 1's arguments are ignored with 1) gathers in one launch.  Per job: src (cap,3),
+ * n_dev (1) int32 on the device, n = min(n_dev[0], cap); row i of dst (S,3) is zero when n <= 2, else src[sample_index(key, i,
+ * n, S)]; used (S) int32 | NULL receives the index (-1 for a zero row).  cap 1..2^29, S 1..2^20. */
+int o3d_track_resample_drawn(const float* src0, const int32_t* n_dev0, int cap0, int key0, float* dst0, int S0, int32_t* used0,
+                             const float* src1, const int32_t* n_dev1, int cap1, int key1, float* dst1, int S1, int32_t* used1,
+                             int n_jobs, void* stream);
+
+/* o3d_track_bank_update: the template bank's book-keeping as device state.  state = {fixed, total} int32, read from state_in and
+ * written to state_out (two different slots).  crop (crop_cap,3) with count (1) int32: the frame's staged model crop, nm =
+ * min(count[0], crop_cap); bank (bank_cap,3).  rule = the shape_aggregation; first != 0: the first tracked frame.  slot = 0 for
+ * FIRST and PREVIOUS, for FIRSTANDPREVIOUS 0 when first else fixed, for ALL total; rows [slot, slot + nm) of the bank become
+ * the crop, FIRSTANDPREVIOUS at first also writes rows [nm, 2 nm) (getModel of the same crop twice); total' = slot + nm (2 nm
+ * there), fixed' = first ? nm : fixed.  Rows at or beyond bank_cap are dropped and total' is clipped to bank_cap.  has_crop == 0
+ * (FIRST after the first frame): the state is copied through and nothing else is written. */
+#define O3D_BANK_FIRST 0
+#define O3D_BANK_PREVIOUS 1
+#define O3D_BANK_FIRSTANDPREVIOUS 2
+#define O3D_BANK_ALL 3
+int o3d_track_bank_update(const float* crop, const int32_t* count, int crop_cap, float* bank, int bank_cap, int rule, int first,
+                          int has_crop, const int32_t* state_in, int32_t* state_out, void* stream);
+
+/* o3d_track_motion_input with the two counts read from the device and the indices drawn there: prev / cur (capacity,3), counts
+ * (2) int32 on the device = (previous, current); per half n = min(count, capacity), zero-filled when n <= 2, else row i gathers
+ * sample_index(key of the half, i - half N, n, N).  used (2N) int32 | NULL: the indices (-1 for a zero row).  With the same
+ * indices the outputs are bit-identical to o3d_track_motion_input's (one definition of the row arithmetic). */
+int o3d_track_motion_input_drawn(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
+                                 int key_this, int N, const float* wlh, int first_frame, float* points, float* candidate_bc,
+                                 int32_t* used, void* stream);
+
 /* ---- training batches built on the device (csrc/train_batch.hip): the device form of PointTrackingSampler +
  * siamese_processing (datasets/sampler.py:16-79) for BAT and P2B.  Frames and ground-truth boxes resident in HBM go in, the
  * training dict comes out; no host synchronisation.  The formulas are written at the head of csrc/train_batch.hip.

@@ -10,6 +10,10 @@
 //                         the same steps for K targets of one scene per launch (tracking.MultiTargetTracker,
 //                         tracking.MultiMotionTracker); every target's result is bit-identical to the single-target entry
 //                         point's
+//   o3d_track_resample_drawn / o3d_track_bank_update / o3d_track_motion_input_drawn
+//                         the free-running loop (tracking.py, sampling="device"): the counts are read where the crop left
+//                         them, the indices are the keyed draw of track_common.hpp, the template bank's {fixed, total} is
+//                         device state -- nothing of a frame crosses to the host
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -63,7 +67,8 @@
 // one function that o3d_track_crop calls too, with no early rejection: rows and counts equal o3d_track_crop's.
 // crop_test, gather_row, offset_box_one, inside_box, the keyed index draw and the workgroup bodies of the three launches
 // (crop_multi_wg, crop_scan_row) live in track_common.hpp: csrc/train_batch.hip (o3d_track_crop_groups[_aug], o3d_train_sample)
-// calls the same definitions.  motion_row is defined here, and so is its third caller, o3d_train_motion_sample.
+// calls the same definitions.  motion_row is defined here, and so are its other callers, o3d_track_motion_input_drawn and
+// o3d_train_motion_sample.
 #include "track_common.hpp"
 
 namespace {
@@ -183,6 +188,83 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
     float x, y, z;
     gather_row(a.src[half], a.n_src[half], a.idx, i, a.zero[half], x, y, z);
     motion_row(x, y, z, half, a.wlh, a.first_frame, a.points + 5 * (long)i, a.bc ? a.bc + 9 * (long)i : nullptr);
+}
+
+// ---- the free-running loop (tracking.py, sampling="device"): counts stay on the device, the indices are drawn here ---------------
+// One job of o3d_track_resample_drawn: dst (S,3) resampled from the first min(n_dev[0], cap) rows of src with the keyed draw
+struct DrawnJob {
+    const float* src; const int32_t* n_dev; int cap; unsigned key; float* dst; int S; int32_t* used;
+};
+
+// the row a drawn gather reads: -1 (zero-fill) for a cloud of n <= 2 rows, else sample_index -- always inside [0, n)
+__device__ __forceinline__ int drawn_index(unsigned key, int i, int n, int S) { return n > 2 ? sample_index(key, i, n, S) : -1; }
+
+// resample_kernel with the count read from the device and the index drawn in place: reads n_dev and src, writes dst and used
+__global__ __launch_bounds__(256) void resample_drawn_kernel(DrawnJob a, DrawnJob b) {
+    const DrawnJob& J = blockIdx.y == 0 ? a : b;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= J.S) return;
+    const int n = min(J.n_dev[0], J.cap);
+    const int s = drawn_index(J.key, i, n, J.S);
+    float x, y, z;
+    gather_row(J.src, n, &s, 0, s < 0, x, y, z);
+    float* o = J.dst + 3 * (long)i;
+    o[0] = x; o[1] = y; o[2] = z;
+    if (J.used) J.used[i] = s;
+}
+
+struct BankArgs {
+    const float* crop; const int32_t* count; int crop_cap; float* bank; int bank_cap;
+    const int32_t* state_in; int32_t* state_out; int rule, first, has_crop;
+};
+
+// The template bank's book-keeping as device state {fixed, total}: every thread reads state_in and count, thread 0 of
+// workgroup 0 writes state_out (another two words: the tracker alternates two slots), so no workgroup reads a word that
+// another one of the launch writes.  Thread i carries row i of the staged crop to row slot + i of the bank.
+__global__ __launch_bounds__(256) void bank_update_kernel(BankArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int fixed = a.state_in[0], total = a.state_in[1];
+    if (!a.has_crop) {                                     // rule `first` after frame 1: the template does not change
+        if (i == 0) { a.state_out[0] = fixed; a.state_out[1] = total; }
+        return;
+    }
+    const int nm = max(0, min(a.count[0], a.crop_cap));
+    const bool twice = a.rule == O3D_BANK_FIRSTANDPREVIOUS && a.first;      // getModel([first, previous]) at t = 1
+    const int slot = a.rule == O3D_BANK_ALL ? total : (a.rule == O3D_BANK_FIRSTANDPREVIOUS && !a.first) ? fixed : 0;
+    if (i == 0) {
+        a.state_out[0] = a.first ? nm : fixed;
+        a.state_out[1] = min(twice ? 2 * nm : slot + nm, a.bank_cap);
+    }
+    if (i >= nm) return;
+    const float* p = a.crop + 3 * (long)i;
+    const float x = p[0], y = p[1], z = p[2];
+#pragma unroll
+    for (int copy = 0; copy < 2; ++copy) {
+        const long r = (long)slot + i + (copy ? nm : 0);
+        if ((copy == 0 || twice) && r >= 0 && r < a.bank_cap) {
+            float* o = a.bank + 3 * r;
+            o[0] = x; o[1] = y; o[2] = z;
+        }
+    }
+}
+
+struct MotionDrawnArgs {
+    const float* src[2]; const int32_t* counts; int cap; unsigned key[2];      // [0] the previous crop, [1] the current crop
+    const float* wlh; int N, first_frame;
+    float* points; float* bc; int32_t* used;
+};
+
+// motion_input_kernel with the two counts read from the device and the indices drawn in place
+__global__ __launch_bounds__(256) void motion_input_drawn_kernel(MotionDrawnArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * a.N) return;
+    const int half = i >= a.N ? 1 : 0;
+    const int n = min(a.counts[half], a.cap);
+    const int s = drawn_index(a.key[half], i - half * a.N, n, a.N);
+    float px, py, pz;
+    gather_row(a.src[half], n, &s, 0, s < 0, px, py, pz);
+    motion_row(px, py, pz, half, a.wlh, a.first_frame, a.points + 5 * (long)i, a.bc ? a.bc + 9 * (long)i : nullptr);
+    if (a.used) a.used[i] = s;
 }
 
 struct OffsetArgs {
@@ -430,6 +512,43 @@ extern "C" int o3d_track_motion_input(const float* prev, int n_prev, const float
     if (N == 0) return O3D_OK;
     MotionInputArgs a{{prev, cur}, {n_prev, n_this}, {zero_prev != 0, zero_this != 0}, idx, wlh, N, first_frame != 0, points, candidate_bc};
     hipLaunchKernelGGL(motion_input_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+// ---- the free-running loop: no count and no index ever crosses to the host (include/o3dsot.h states the contracts) ---------------
+static bool drawn_job_ok(const float* src, const int32_t* n_dev, int cap, const float* dst, int S) {
+    return src && n_dev && dst && cap >= 1 && cap <= (1 << 29) && S >= 1 && S <= (1 << 20);
+}
+
+extern "C" int o3d_track_resample_drawn(const float* src0, const int32_t* n_dev0, int cap0, int key0, float* dst0, int S0, int32_t* used0,
+                                        const float* src1, const int32_t* n_dev1, int cap1, int key1, float* dst1, int S1, int32_t* used1,
+                                        int n_jobs, void* stream) {
+    if (n_jobs < 1 || n_jobs > 2 || !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) || (n_jobs == 2 && !drawn_job_ok(src1, n_dev1, cap1, dst1, S1)))
+        return O3D_EINVAL;
+    const DrawnJob a{src0, n_dev0, cap0, (unsigned)key0, dst0, S0, used0};
+    const DrawnJob b = n_jobs == 2 ? DrawnJob{src1, n_dev1, cap1, (unsigned)key1, dst1, S1, used1} : a;
+    const int smax = a.S > b.S ? a.S : b.S;
+    hipLaunchKernelGGL(resample_drawn_kernel, dim3(o3d_cdiv(smax, 256), n_jobs), dim3(256), 0, o3d_stream(stream), a, b);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_bank_update(const float* crop, const int32_t* count, int crop_cap, float* bank, int bank_cap, int rule, int first,
+                                     int has_crop, const int32_t* state_in, int32_t* state_out, void* stream) {
+    if (!crop || !count || !bank || !state_in || !state_out || state_in == state_out || crop_cap < 1 || crop_cap > (1 << 29) ||
+        bank_cap < 1 || bank_cap > (1 << 29) || rule < O3D_BANK_FIRST || rule > O3D_BANK_ALL)
+        return O3D_EINVAL;
+    const BankArgs a{crop, count, crop_cap, bank, bank_cap, state_in, state_out, rule, first != 0, has_crop != 0};
+    hipLaunchKernelGGL(bank_update_kernel, dim3(has_crop ? o3d_cdiv(crop_cap, 256) : 1), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_motion_input_drawn(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
+                                            int key_this, int N, const float* wlh, int first_frame, float* points, float* candidate_bc,
+                                            int32_t* used, void* stream) {
+    if (!prev || !cur || !counts || !wlh || !points || capacity < 1 || capacity > (1 << 29) || N < 1 || N > (1 << 20)) return O3D_EINVAL;
+    const MotionDrawnArgs a{{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this}, wlh, N, first_frame != 0, points,
+                            candidate_bc, used};
+    hipLaunchKernelGGL(motion_input_drawn_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
     return o3d_launch_status();
 }
 

@@ -403,6 +403,108 @@ def motion_input_multi(table, K, N, wlh, first_frame, out_points, out_bc):
     return out_points, out_bc
 
 
+# ---- the free-running loop (tracking.py, sampling="device"): counts and indices never leave the device -------------------------
+BANK_RULES = {"first": capi.CONSTANTS["O3D_BANK_FIRST"], "previous": capi.CONSTANTS["O3D_BANK_PREVIOUS"],
+              "firstandprevious": capi.CONSTANTS["O3D_BANK_FIRSTANDPREVIOUS"], "all": capi.CONSTANTS["O3D_BANK_ALL"]}
+
+
+def _mix32(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+    x ^= x >> 13
+    x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def draw_key(seed, counter, j, cloud):
+    """the key of the keyed index draw (the formula at the head of csrc/train_batch.hip) -> a uint32 as a Python int"""
+    a = (int(seed) * 0x9E3779B1) & 0xFFFFFFFF
+    b = (int(counter) * 0x85EBCA77 + int(j) * 0xC2B2AE3D + int(cloud) * 0x27D4EB2F + 0x165667B1) & 0xFFFFFFFF
+    return _mix32(a ^ b)
+
+
+def _key_bits(key):
+    """a uint32 key -> the C int that carries its bits"""
+    key = int(key) & 0xFFFFFFFF
+    return key - (1 << 32) if key >= (1 << 31) else key
+
+
+def _count_operand(t):
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= 1
+
+
+def resample_drawn(jobs):
+    """One o3d_track_resample_drawn launch (no sync).  jobs: 1 or 2 tuples (src (cap,3) f32 GPU, n_dev (1,) int32 GPU, key,
+    dst (S,3), used (S,) int32 GPU | None): dst is resampled from the first min(n_dev[0], cap) rows of src with the keyed draw
+    (zeros when that count is <= 2); used receives the indices (-1 for a zero row)."""
+    assert 1 <= len(jobs) <= 2
+    args = []
+    for src, n_dev, key, dst, used in jobs:
+        _need_gpu(src, "resample_drawn")
+        _need_gpu(dst, "resample_drawn")
+        assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == 3
+        assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() % 3 == 0
+        _count_operand(n_dev)
+        S = dst.numel() // 3
+        assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= S)
+        args += [src.data_ptr(), n_dev.data_ptr(), src.shape[0], _key_bits(key), dst.data_ptr(), S,
+                 used.data_ptr() if used is not None else None]
+    if len(jobs) == 1:
+        args += [None, None, 0, 0, None, 0, None]
+    dev = jobs[0][3].device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_resample_drawn(*args, len(jobs), torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_track_resample_drawn")
+
+
+def bank_update(crop, count, bank, rule, first, has_crop, state_in, state_out):
+    """One o3d_track_bank_update launch (no sync): the staged model crop `crop` (crop_cap,3) with its device count (1,) int32
+    goes into `bank` (bank_cap,3) by the shape_aggregation `rule` (a key of BANK_RULES); state_in / state_out (2,) int32 GPU =
+    {fixed, total} before and after (two different tensors).  has_crop False: the state is copied through."""
+    for t in (crop, bank):
+        _need_gpu(t, "bank_update")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3
+    _count_operand(count)
+    for s in (state_in, state_out):
+        assert s.is_cuda and s.dtype == torch.int32 and s.is_contiguous() and s.numel() == 2
+    dev = bank.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_bank_update(
+            crop.data_ptr(), count.data_ptr(), crop.shape[0], bank.data_ptr(), bank.shape[0], BANK_RULES[rule], int(bool(first)),
+            int(bool(has_crop)), state_in.data_ptr(), state_out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_bank_update")
+
+
+def motion_input_drawn(prev_crop, this_crop, counts, keys, wlh, first_frame, out_points, out_bc=None, used=None):
+    """One o3d_track_motion_input_drawn launch (no sync): motion_input with the two counts read from `counts` (2,) int32 GPU
+    (capped at the crops' common capacity) and the 2N indices drawn on the device with keys = (previous, current).
+    out_points (2N,5); out_bc (2N,9) | None / False (box_aware=False); used (2N,) int32 GPU | None: the indices, -1 for a
+    zero-filled row."""
+    for t in (prev_crop, this_crop):
+        _need_gpu(t, "motion_input_drawn")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3
+    assert prev_crop.shape[0] == this_crop.shape[0]
+    _need_gpu(out_points, "motion_input_drawn")
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 2
+    assert wlh.is_cuda and wlh.dtype == torch.float32 and wlh.is_contiguous() and wlh.numel() == 3
+    assert out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.numel() % 10 == 0
+    n2 = out_points.numel() // 5
+    if out_bc is None or out_bc is False:
+        out_bc = None
+    else:
+        assert out_bc.is_cuda and out_bc.dtype == torch.float32 and out_bc.is_contiguous() and out_bc.numel() == 9 * n2
+    assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= n2)
+    dev = wlh.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_motion_input_drawn(
+            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), prev_crop.shape[0], _key_bits(keys[0]),
+            _key_bits(keys[1]), n2 // 2, wlh.data_ptr(), int(bool(first_frame)), out_points.data_ptr(),
+            out_bc.data_ptr() if out_bc is not None else None, used.data_ptr() if used is not None else None,
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_motion_input_drawn")
+    return out_points, out_bc
+
+
 def _box_device(box, what):
     """the GPU a box lives on (a (15,) tensor or a (center, wlh, rot) triple of tensors); anything else is refused"""
     parts = (box,) if torch.is_tensor(box) else tuple(box)

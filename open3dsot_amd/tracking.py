@@ -16,7 +16,22 @@ Per frame t >= 1 (the reference's build_input_dict :240-247 + evaluate_one_sampl
 
 Why one sync remains: the reference resamples a crop of n points with `default_rng(1).choice(n, size, replace=size > n)`.
 Which indices that call returns depends on n, so index parity with the reference needs n on the host before the draw.  A
-device-side sampler would remove the sync and change every index; it is out of scope here.
+device-side sampler removes the sync and changes every index: that is the second mode, below.
+
+sampling="device" (SequenceTracker, MotionSequenceTracker): the free-running loop.  The counts stay
+where the crop kernel wrote them, the indices are the keyed draw of the training batches (sample_index in
+csrc/track_common.hpp, key = draw_key(seed, 0, 0, cloud), the same key at every frame), and the template bank's {fixed, total}
+is device state.  Per frame t >= 1:
+
+  o3d_track_crop, one call, two jobs    the search window into search_buf, the model crop into a staging buffer
+  a device copy of the counts           row t of counts_log (T,2) int32; read on request only (counts(), overflow())
+  o3d_track_bank_update                 the staged crop into the bank by the shape_aggregation rule; {fixed, total} advances
+  o3d_track_resample_drawn              both draws and both gathers, straight into the static inputs
+  o3d_boxcloud, forward, o3d_track_offset_box   as above
+
+No copy in either direction and no synchronisation after the first update() (whose graph capture may synchronise).  The price:
+every buffer has a fixed capacity (a longer crop keeps its first `capacity` survivors), and the indices are not numpy's -- the
+same rule (n <= 2 zero-fills, n == S is the identity, S > n draws with replacement, S < n without), other numbers.
 
 The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
 (`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
@@ -50,6 +65,26 @@ def draw_indices(num_points, sample_size):
     if num_points == sample_size:
         return np.arange(num_points)
     return np.random.default_rng(1).choice(num_points, size=sample_size, replace=sample_size > num_points)
+
+
+SAMPLING = ("reference", "device")
+
+
+def _sampling(name, multi=None):
+    """the `sampling` keyword checked before anything else; multi: the name of a K-target loop, which has no device mode yet"""
+    if name not in SAMPLING:
+        raise ValueError("sampling %r: expected \"reference\" or \"device\"" % (name,))
+    if multi and name == "device":
+        raise ValueError("%s: sampling=\"device\" serves the single-target trackers (SequenceTracker, MotionSequenceTracker); "
+                         "the K-target loops are a follow-up" % multi)
+    return name
+
+
+def draw_keys(seed):
+    """the two keys of a free-running tracker's index draws: cloud 0 = the template / the previous frame, cloud 1 = the search
+    area / the current frame.  They do not change from frame to frame, as the reference's seed=1 makes its indices a function
+    of the point count alone."""
+    return PU.draw_key(seed, 0, 0, 0), PU.draw_key(seed, 0, 0, 1)
 
 
 class DrawCache:
@@ -86,11 +121,13 @@ class _DeviceTracker:
     box's wlh), the (T,15) results buffer with its device-side frame counter, the crop call with the frame's one count
     read-back (and buffer growth when a crop exceeds its capacity), the index staging and the network as a HIP graph captured
     once per tracker (eager when the capture fails, unless O3D_REQUIRE_GRAPH=1).  With n_targets = K the per-target state has
-    a leading K axis (`lead`): cur (K,15), yaw_state (K,10), boxes (T,K,15), counts (2K,).  Subclasses provide `_update()`
+    a leading K axis (`lead`): cur (K,15), yaw_state (K,10), boxes (T,K,15), counts_dev (2K,).  Subclasses provide `_update()`
     and `_forward()` on their static inputs."""
     _NAME = "tracker"
 
-    def __init__(self, model, seed, use_graph, max_frames, defaults, n_targets=None):
+    def __init__(self, model, seed, use_graph, max_frames, defaults, n_targets=None, sampling="reference", record_indices=False):
+        self.sampling = _sampling(sampling)
+        self.free_running, self.record_indices = sampling == "device", bool(record_indices)
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("%s: CPU not supported (the model must live on a GPU)" % self._NAME)
@@ -102,8 +139,13 @@ class _DeviceTracker:
         self.require_graph = os.environ.get("O3D_REQUIRE_GRAPH", "0") == "1"
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.lead = lead = () if n_targets is None else (int(n_targets),)
-        self.counts = torch.zeros((2 * (n_targets or 1),), dtype=torch.int32, device=self.dev)
-        self.counts_host = torch.zeros(self.counts.shape, dtype=torch.int32).pin_memory()
+        self.counts_dev = torch.zeros((2 * (n_targets or 1),), dtype=torch.int32, device=self.dev)
+        self.counts_host, self.counts_log = None, None
+        if self.free_running:         # the counts stay on the device: row t of counts_log, written by a stream-ordered copy
+            self.counts_log = torch.full((int(max_frames), 2), -1, dtype=torch.int32, device=self.dev)
+            self.keys = draw_keys(self.seed)
+        else:
+            self.counts_host = torch.zeros(self.counts_dev.shape, dtype=torch.int32).pin_memory()
         self.cur = torch.zeros(lead + (15,), **f32)        # the last result box: the next frame's crops read it
         self.yaw_state = torch.zeros(lead + (10,), **f32)
         self.canon_wlh = torch.zeros(lead + (3,), **f32)   # the canonical box: zero centre, this wlh, identity
@@ -132,6 +174,8 @@ class _DeviceTracker:
         self._restart(b)
         self.canon_wlh.copy_(b[..., 3:6])
         self.frame.fill_(1)
+        if self.free_running:
+            self.counts_log.fill_(-1)
         self.prev_points = points0.contiguous().float()
         return self.boxes[0]
 
@@ -146,6 +190,10 @@ class _DeviceTracker:
             bigger = torch.zeros((2 * T,) + self.boxes.shape[1:], dtype=torch.float32, device=self.dev)
             bigger[:T].copy_(self.boxes)
             self.boxes = bigger
+            if self.free_running:                          # counts_log grows with boxes
+                log = torch.full((2 * T, 2), -1, dtype=torch.int32, device=self.dev)
+                log[:T].copy_(self.counts_log)
+                self.counts_log = log
 
     def _crop_counts(self, make_jobs):
         """The frame's one crop call + the count read-back.  make_jobs() -> [(crop job, grow)]: the job's count lands in
@@ -162,7 +210,7 @@ class _DeviceTracker:
         is made again.  -> counts"""
         while True:
             caps = launch()
-            self.counts_host.copy_(self.counts, non_blocking=True)
+            self.counts_host.copy_(self.counts_dev, non_blocking=True)
             torch.cuda.current_stream(self.dev).synchronize()                    # the one sync of the frame
             ns = self.counts_host[:len(caps)].tolist()
             over = {}                                                            # grow -> its largest overflowing count
@@ -238,9 +286,22 @@ class _DeviceTracker:
     def _done(self, pts, entry):
         """the end of _update: the frame becomes the previous one, `entry` its line of the log -> a device VIEW of its row"""
         self.prev_points = pts
-        self.log.append(entry)
+        if entry is not None:                              # the free-running loop keeps no host log: counts()
+            self.log.append(entry)
         self.t += 1
         return self.boxes[self.t - 1]
+
+    def _log_counts(self, k=2):
+        """the free-running loop's record of the frame: counts_dev[:k] -> row t of counts_log, a device copy in stream order"""
+        self.counts_log[self.t, :k].copy_(self.counts_dev[:k])
+
+    def counts(self):
+        """sampling="device" only: (t,2) int32 on the host, row f the two crop counts of frame f as the crop kernel counted
+        them (before the cut to the buffers' capacities), -1 where no crop was made (row 0; the model crop under `first`
+        after frame 1).  One sync."""
+        if not self.free_running:
+            raise RuntimeError("%s.counts: sampling=\"reference\" keeps the counts in `log`" % self._NAME)
+        return self.counts_log[:self.t].cpu().numpy()
 
     def results(self):
         """(T,15) float32 on the host, (T,K,15) with n_targets = K: row 0 the initial box, row t the result of frame t (one sync)"""
@@ -321,7 +382,7 @@ class _KTargets:
         kk = np.arange(K, dtype=np.uint64)
         r = self.crop_rec[g * K:(g + 1) * K]
         r["box"], r["scale"], r["offset"], r["mode"] = boxes.data_ptr() + 60 * kk, scale, offset, mode
-        r["out"], r["capacity"], r["count"] = out, capacity, self.counts.data_ptr() + 4 * (kk + np.uint64(g * K))
+        r["out"], r["capacity"], r["count"] = out, capacity, self.counts_dev.data_ptr() + 4 * (kk + np.uint64(g * K))
         return self.crop_tab[g * K * size:(g + 1) * K * size]
 
     def _crop_multi(self, groups):
@@ -338,8 +399,9 @@ class _MatchingTracker(_DeviceTracker):
     ints for the single tracker and (K,) int64 arrays for K targets; the same expressions serve both."""
     _REF_KW = "ref_box"
 
-    def __init__(self, model, seed, use_graph, max_frames, search_capacity, model_capacity, n_targets=None):
-        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS, n_targets)
+    def __init__(self, model, seed, use_graph, max_frames, search_capacity, model_capacity, n_targets=None, sampling="reference",
+                 record_indices=False, bank_capacity=None):
+        super().__init__(model, seed, use_graph, max_frames, _DEFAULTS, n_targets, sampling, record_indices)
         self.K = K = n_targets or 1
         self.aggregation = _aggregation(self.shape_aggregation)
         if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
@@ -355,12 +417,26 @@ class _MatchingTracker(_DeviceTracker):
         self.canon_rot = torch.eye(3, **f32).reshape(1, 9).repeat(K, 1).contiguous()
         self.search_buf = torch.empty(self.lead + (int(search_capacity), 3), **f32)
         self.model_capacity = int(model_capacity)
-        self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
+        self.bank_capacity = int(bank_capacity) if bank_capacity is not None else 8 * self.model_capacity
+        if self.free_running:         # fixed sizes: nothing can grow a buffer without reading a count
+            if min(int(search_capacity), self.model_capacity, self.bank_capacity) < 1:
+                raise ValueError("search_capacity, model_capacity and bank_capacity must be positive")
+            self.staging = torch.empty((self.model_capacity, 3), **f32)      # the frame's model crop, before it enters the bank
+            self.bank = torch.empty((self.bank_capacity, 3), **f32)
+            self.bank_state = torch.zeros((2, 2), dtype=torch.int32, device=self.dev)      # {fixed, total}, two slots by frame parity
+            i32 = dict(dtype=torch.int32, device=self.dev)
+            self.used_t = torch.full((M,), -1, **i32) if self.record_indices else None
+            self.used_s = torch.full((N,), -1, **i32) if self.record_indices else None
+        else:
+            self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
         # log, per frame: (search count, model count of the crop made this frame | None, template points)
 
     def init(self, points0, box0):
         box = super().init(points0, box0)
-        self.bank_fixed, self.bank_total = (np.zeros(self.lead, np.int64), np.zeros(self.lead, np.int64)) if self.lead else (0, 0)
+        if self.free_running:              # the book-keeping is device state
+            self.bank_state.zero_()
+        else:
+            self.bank_fixed, self.bank_total = (np.zeros(self.lead, np.int64), np.zeros(self.lead, np.int64)) if self.lead else (0, 0)
         return box
 
     def _check(self, ref):
@@ -420,23 +496,36 @@ class SequenceTracker(_MatchingTracker):
     `update(points, ref_box=...)` searches around (and offsets from) the given box instead of the previous result: the
     reference's `reference_BB: previous_gt / current_gt`.  `seed` feeds limit_box's replacement draw only.
     use_graph: None = capture, fall back to eager when the capture fails (O3D_REQUIRE_GRAPH=1: raise instead); False = eager.
+
+    sampling="device": the free-running loop of the module docstring.  When update() returns, the frame is only ENQUEUED:
+    nothing has been read back, and the caller's frame tensor must not be rewritten from another stream before the NEXT frame
+    has been enqueued (its model crop reads it; `prev_points` keeps the reference alive).  `seed` also keys the index draws.
+    search_capacity / model_capacity / bank_capacity (default 8 * model_capacity) are then the fixed sizes of the search
+    buffer, the staging buffer of a frame's model crop and the template bank: a longer crop keeps its first survivors, the
+    draw uses min(count, capacity), and a full bank (aggregation `all`) drops further rows.  `log` stays empty; counts() ->
+    (t,2) (search count, model-crop count | -1) on the host, overflow() -> how often a capacity cut something (one sync each).
+    record_indices=True keeps the last frame's indices in used_t (template_size,) / used_s (search_size,), device int32, -1
+    for a zero-filled cloud.  update(points, ref_box=<device tensor>) stays free of host stops as well.
     """
     _NAME = "SequenceTracker"
 
-    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
-        super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity)
-        self._index_buffers(int(self.template_size) + int(self.search_size))
+    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
+                 sampling="reference", record_indices=False, bank_capacity=None):
+        super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity, None, sampling, record_indices,
+                         bank_capacity)
+        if not self.free_running:
+            self._index_buffers(int(self.template_size) + int(self.search_size))
 
     def _crops(self, pts, ref, slot):
         """the frame's one crop call + the count read-back -> (search count, model count | None)"""
         c = self
 
         def make_jobs():
-            jobs = [((pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts[0:1]), c._grow_search)]
+            jobs = [((pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts_dev[0:1]), c._grow_search)]
             if slot is not None:
                 c._ensure_bank(slot + c.model_capacity)
                 jobs.append(((c.prev_points, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL,
-                              c.bank[slot:slot + c.model_capacity], c.counts[1:2]), c._grow_model))
+                              c.bank[slot:slot + c.model_capacity], c.counts_dev[1:2]), c._grow_model))
             return jobs
         ns = c._crop_counts(make_jobs)
         return ns[0], (ns[1] if slot is not None else None)
@@ -444,7 +533,48 @@ class SequenceTracker(_MatchingTracker):
     def update(self, points, ref_box=None):
         return self._run(points, ref_box)
 
+    def _update_free(self, pts, ref_box):
+        """the frame of sampling="device": enqueued, nothing read back"""
+        c = self
+        c._grow_boxes()
+        ref = c.cur if ref_box is None else PU.pack_box(ref_box, c.dev)
+        first = c.t == 1
+        has_crop = first or c.aggregation != "first"
+        jobs = [(pts, ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.counts_dev[0:1])]
+        if has_crop:
+            jobs.append((c.prev_points, c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, c.staging, c.counts_dev[1:2]))
+        c.scratch = PU.crop_jobs(jobs, c.scratch)
+        c._log_counts(len(jobs))
+        state_in, state_out = c.bank_state[(c.t + 1) & 1], c.bank_state[c.t & 1]
+        PU.bank_update(c.staging, c.counts_dev[1:2], c.bank, c.aggregation, first, has_crop, state_in, state_out)
+        PU.resample_drawn([(c.bank, state_out[1:2], c.keys[0], c.inputs["template_points"], c.used_t),
+                           (c.search_buf, c.counts_dev[0:1], c.keys[1], c.inputs["search_points"], c.used_s)])
+        c._boxcloud()
+        best, _ = c._network()
+        PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
+                      use_z=c.use_z, limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        return c._done(pts, None)
+
+    def overflow(self):
+        """sampling="device" only -> (truncated search crops, truncated model crops, frames on which the bank was full): how
+        often a fixed capacity cut something, worked out on the host from counts() and the capacities (one sync)."""
+        counts = self.counts()
+        over_s = int((counts[1:, 0] > self.search_buf.shape[0]).sum())
+        over_m = int((counts[1:, 1] > self.model_capacity).sum())
+        fixed = total = full = 0
+        for t in range(1, counts.shape[0]):                # the transitions of o3d_track_bank_update, before its clip
+            if counts[t, 1] < 0:
+                continue
+            nm, first = min(int(counts[t, 1]), self.model_capacity), t == 1
+            slot = total if self.aggregation == "all" else fixed if self.aggregation == "firstandprevious" and not first else 0
+            need = 2 * nm if self.aggregation == "firstandprevious" and first else slot + nm
+            full += need > self.bank_capacity
+            fixed, total = (nm if first else fixed), min(need, self.bank_capacity)
+        return over_s, over_m, int(full)
+
     def _update(self, pts, ref_box):
+        if self.free_running:
+            return self._update_free(pts, ref_box)
         c, M = self, int(self.template_size)
         c._grow_boxes()
         ref = c.cur if ref_box is None else PU.pack_box(ref_box, c.dev)
@@ -489,10 +619,13 @@ class MultiTargetTracker(_KTargets, _MatchingTracker):
     The template bank is per target: bank[k] holds target k's crops with SequenceTracker's slot rules for the four
     shape_aggregation modes.  `update(points, ref_boxes=...)` (K,15): the reference's `reference_BB: previous_gt / current_gt`.
     `seed`: target k's limit_box draws use seed + k.  log, per frame: (search counts (K), model counts (K) | None, template
-    counts (K)); crop_calls: the crop calls since init (one per frame, one more whenever a crop outgrew its buffer)."""
+    counts (K)); crop_calls: the crop calls since init (one per frame, one more whenever a crop outgrew its buffer).
+    sampling: "reference" only ("device" raises ValueError: the K-target free-running loop is a follow-up)."""
     _NAME, _REF_KW = "MultiTargetTracker", "ref_boxes"
 
-    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192):
+    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
+                 sampling="reference"):
+        _sampling(sampling, self._NAME)
         from .m2track import M2TRACK
         if isinstance(model, M2TRACK):
             raise TypeError("MultiTargetTracker serves the matching trackers (BAT, P2B); the motion tracker follows one "
@@ -595,11 +728,19 @@ class MotionSequenceTracker(_DeviceTracker):
       forward                               replayed as one HIP graph captured once per tracker
       o3d_track_offset_box                  reads estimation_boxes where the forward left it; the new box goes to results
 
-    log, per frame: (previous-frame count, current-frame count)."""
+    log, per frame: (previous-frame count, current-frame count).
+
+    sampling="device": the free-running loop (module docstring) -- o3d_track_crop, a device copy of the
+    two counts into row t of counts_log, o3d_track_motion_input_drawn (counts read on the device, indices drawn there), the
+    forward, o3d_track_offset_box.  When update() returns, the frame is only ENQUEUED, and the caller's frame tensor must not
+    be rewritten from another stream before the NEXT frame has been enqueued (`prev_points` keeps the reference alive).
+    `capacity` is then the fixed size of both crop buffers (a longer crop keeps its first survivors); `log` stays empty,
+    counts() -> (t,2) (previous-frame count, current-frame count), overflow() -> (truncated previous, truncated current, 0);
+    record_indices=True keeps the last frame's indices in used_prev / used_this (point_sample_size,), -1 for a zero-filled half."""
     _NAME = "MotionSequenceTracker"
 
-    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, capacity=32768):
-        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS)
+    def __init__(self, model, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference", record_indices=False):
+        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, None, sampling, record_indices)
         dev, N = self.dev, int(self.point_sample_size)
         f32 = dict(dtype=torch.float32, device=dev)
         self.box_aware = bool(getattr(model, "box_aware", False))
@@ -607,7 +748,13 @@ class MotionSequenceTracker(_DeviceTracker):
         if self.box_aware:
             self.inputs["candidate_bc"] = torch.zeros((1, 2 * N, 9), **f32)
         self.crop_buf = torch.empty((2, int(capacity), 3), **f32)          # [0] the previous frame's crop, [1] the current one's
-        self._index_buffers(2 * N)
+        if self.free_running:
+            if int(capacity) < 1:
+                raise ValueError("capacity must be positive")
+            self.used = torch.full((2 * N,), -1, dtype=torch.int32, device=dev) if self.record_indices else None
+            self.used_prev, self.used_this = (self.used[:N], self.used[N:]) if self.record_indices else (None, None)
+        else:
+            self._index_buffers(2 * N)
 
     def _crops(self, pts):
         c = self
@@ -616,14 +763,37 @@ class MotionSequenceTracker(_DeviceTracker):
             c.crop_buf = torch.empty((2, 2 * n, 3), dtype=torch.float32, device=c.dev)
 
         def make_jobs():
-            return [((src, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], c.counts[h:h + 1]), grow)
+            return [((src, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], c.counts_dev[h:h + 1]), grow)
                     for h, src in enumerate((c.prev_points, pts))]
         return c._crop_counts(make_jobs)
 
     def update(self, points):
         return self._run(points)
 
+    def _update_free(self, pts):
+        """the frame of sampling="device": enqueued, nothing read back"""
+        c = self
+        c._grow_boxes()
+        c.scratch = PU.crop_jobs([(src, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], c.counts_dev[h:h + 1])
+                                  for h, src in enumerate((c.prev_points, pts))], c.scratch)
+        c._log_counts()
+        PU.motion_input_drawn(c.crop_buf[0], c.crop_buf[1], c.counts_dev, c.keys, c.canon_wlh, c.t == 1, c.inputs["points"],
+                              c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        est = c._network()
+        PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
+                      limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        return c._done(pts, None)
+
+    def overflow(self):
+        """sampling="device" only -> (truncated previous-frame crops, truncated current-frame crops, 0: there is no bank), on the
+        host from counts() and the capacity (one sync)."""
+        counts = self.counts()
+        cap = self.crop_buf.shape[1]
+        return int((counts[1:, 0] > cap).sum()), int((counts[1:, 1] > cap).sum()), 0
+
     def _update(self, pts):
+        if self.free_running:
+            return self._update_free(pts)
         c, N = self, int(self.point_sample_size)
         c._grow_boxes()
         n_prev, n_this = c._crops(pts)
@@ -660,10 +830,12 @@ class MultiMotionTracker(_KTargets, _DeviceTracker):
       o3d_track_offset_box_multi        the K new boxes into row t of the (T,K,15) results buffer
 
     log, per frame: (previous-frame counts (K), current-frame counts (K)); crop_calls: the crop calls since init (one per
-    frame, one more whenever a crop outgrew the buffer: all 2K rows then grow to twice the largest count)."""
+    frame, one more whenever a crop outgrew the buffer: all 2K rows then grow to twice the largest count).
+    sampling: "reference" only ("device" raises ValueError: the K-target free-running loop is a follow-up)."""
     _NAME = "MultiMotionTracker"
 
-    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768):
+    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference"):
+        _sampling(sampling, self._NAME)
         from .m2track import M2TRACK
         if not isinstance(model, M2TRACK):
             raise TypeError("MultiMotionTracker serves the motion tracker (M2TRACK); the matching trackers (BAT, P2B) follow "
@@ -749,11 +921,12 @@ def multi_tracker_for(model, n_targets, **kw):
     return (MultiMotionTracker if _is_motion(model) else MultiTargetTracker)(model, n_targets, **kw)
 
 
-def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
+def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None, sampling="reference"):
     """The convenience loop: frames = a sequence of (N_t,3) GPU tensors, box0 the target's box in frames[0]; ref_boxes[t]
     (optional, matching trackers only) is handed to update() of frame t.  The tracker class follows the model's type.
+    sampling: "reference" (numpy's index draw, one host sync per frame) | "device" (the free-running loop).
     -> (T,15) result boxes on the host."""
-    trk = tracker_for(model, seed=seed, use_graph=use_graph)
+    trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
     if isinstance(trk, MotionSequenceTracker) and ref_boxes is not None:
         raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
     trk.init(frames[0], box0)
@@ -765,12 +938,12 @@ def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None):
     return trk.results()
 
 
-def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None):
+def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None, sampling="reference"):
     """track_sequence for K targets in the same frames: boxes0 (K,15) the targets' boxes in frames[0]; ref_boxes[t] (K,15)
     (optional, matching trackers only) is handed to update() of frame t.  The tracker class follows the model's type.
     -> (T,K,15) result boxes on the host."""
     b0 = boxes0 if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray) else list(boxes0)
-    trk = multi_tracker_for(model, len(b0), seed=seed, use_graph=use_graph)
+    trk = multi_tracker_for(model, len(b0), seed=seed, use_graph=use_graph, sampling=sampling)
     if isinstance(trk, MultiMotionTracker) and ref_boxes is not None:
         raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
     trk.init(frames[0], b0)
@@ -798,23 +971,25 @@ def _track_with_gt(trk, frames, gt):
             trk.update(frames[t])
 
 
-def evaluate_sequence(model, frames, gt_boxes, seed=0, use_graph=None, tracker=None, metrics=None):
+def evaluate_sequence(model, frames, gt_boxes, seed=0, use_graph=None, tracker=None, metrics=None, sampling="reference"):
     """The device form of evaluate_one_sequence (models/base_model.py:59-86): frames = a sequence of (N_t,3) GPU tensors,
     gt_boxes (T,15) host or device.  The tracker starts from gt_boxes[0], follows the config's reference_BB rule, and the
     whole sequence is scored ONCE at its end, on the device (frame 0 scores the first box against itself, as the reference
     does).  tracker: one to reuse (its captured graph with it) | None: tracker_for(model).  metrics: a SuccessPrecision to add to.
     -> (ious (T), distances (T), results (T,15)) device tensors; no sync beyond the tracker's own."""
-    trk = tracker if tracker is not None else tracker_for(model, seed=seed, use_graph=use_graph)
+    _sampling(sampling)
+    trk = tracker if tracker is not None else tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
     gt = PU._dev32(gt_boxes, trk.dev).reshape(-1, 15)
     _track_with_gt(trk, frames, gt)
     ious, distances = trk.score(gt, metrics=metrics)
     return ious, distances, trk.boxes[:trk.t]
 
 
-def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None, tracker=None, metrics=None):
+def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None, tracker=None, metrics=None, sampling="reference"):
     """evaluate_sequence over track_targets: gt_boxes (T,K,15), the K targets' boxes in the same frames.  valid (T,K) | None on
     the host: 0 where a target has no annotation; a target is retired at its first such frame (its later rows repeat its last
     box and are not scored, whatever `valid` says there).  -> (ious (T,K), distances (T,K), results (T,K,15)) device tensors."""
+    _sampling(sampling, "evaluate_targets")
     gt_host = gt_boxes.shape
     trk = tracker if tracker is not None else multi_tracker_for(model, gt_host[1], seed=seed, use_graph=use_graph)
     gt = PU._dev32(gt_boxes, trk.dev).reshape(gt_host[0], trk.K, 15)
@@ -841,13 +1016,13 @@ def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None
     return ious, distances, trk.boxes[:trk.t]
 
 
-def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None):
+def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None, sampling="reference"):
     """The test epoch (test_step / validation_step of the reference over its tracklets): every tracklet of `tracklets` -- a
     sampler.DeviceTracklets, or any iterable of (frames, boxes) -- goes through evaluate_sequence on ONE tracker (one captured
     graph for the epoch) and adds to ONE metrics.SuccessPrecision (`metrics` | None: a new one); the metric is read back once,
     at the end.  -> {"success", "precision", "frames", "tracklets"}."""
     from . import metrics as MT
-    trk = tracker_for(model, seed=seed, use_graph=use_graph)
+    trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
     m = metrics if metrics is not None else MT.SuccessPrecision(device=trk.dev)
     count = 0
     for item in tracklets:

@@ -21,6 +21,13 @@ frames resident in HBM.  Prints one JSON line: ms per frame of both, targets x f
 largest difference between the boxes of the two (batch-K against batch-1 forward, compounding over the sequence).
 --targets K --model M2TRACK: tracking.MultiMotionTracker against K MotionSequenceTrackers run in turn, the same way, with the
 same keys.
+
+--sampling device: the free-running loop (tracking.tracker_for(model, sampling="device"): counts and index draws stay on the
+device, update() only enqueues a frame) against the same tracker class with sampling="reference" (numpy's draw, one host sync
+per frame), on the same frames and the same model (fixture weights, so that the box stays near its target), both from the
+frames resident in HBM, each timed from the first update() to the read-back of its boxes, --repeats times in turn.  Prints one
+JSON line: frames/s of both (median, smallest and largest run), their ratio, the crop counts of the last frame and overflow()
+of the free-running loop.
 """
 import argparse
 import json
@@ -151,6 +158,52 @@ def multi_target_main(args, dev):
         "largest_box_difference_frame_1": float(diff[1]), "largest_box_difference": float(diff.max())}))
 
 
+def sampling_main(args, dev):
+    if args.model.upper() == "M2TRACK":
+        model, cfg = motion_model(dev)
+    else:
+        cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+        cfg.update(TO.TEST_KEYS)
+        model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+    frames, gt = synth.make_sequence(args.seed, args.frames, args.points)
+    dframes = [torch.from_numpy(f).to(dev) for f in frames]
+    warm = min(20, args.frames)
+    modes = ("device", "reference")
+    trks, times, boxes = {}, {m: [] for m in modes}, {}
+    for m in modes:
+        trks[m] = tracking.tracker_for(model, sampling=m)
+        trks[m].init(dframes[0], gt[0])
+        for t in range(1, warm):                                        # capture + warm-up
+            trks[m].update(dframes[t])
+    torch.cuda.synchronize()
+    for _ in range(args.repeats):                                       # the two loops in turn: what disturbs one disturbs the other
+        for m in modes:
+            trk = trks[m]
+            trk.init(dframes[0], gt[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in range(1, args.frames):
+                trk.update(dframes[t])
+            boxes[m] = trk.results()                                    # the one read-back of the boxes (a sync)
+            times[m].append(time.perf_counter() - t0)
+    fps = {m: sorted((args.frames - 1) / dt for dt in times[m]) for m in modes}
+    mid = {m: fps[m][len(fps[m]) // 2] for m in modes}
+    free, ref = trks["device"], trks["reference"]
+    print(json.dumps({
+        "workload": "%s tracking a %d-frame, %d-point synthetic sequence (fixture weights, eval, fp32), median of %d runs, the two "
+                    "loops in turn" % (args.model.upper(), args.frames, args.points, args.repeats),
+        "device_sampling_frames_per_s": round(mid["device"], 1), "reference_sampling_frames_per_s": round(mid["reference"], 1),
+        "device_over_reference": round(mid["device"] / mid["reference"], 3),
+        "device_sampling_frames_per_s_min_max": [round(fps["device"][0], 1), round(fps["device"][-1], 1)],
+        "reference_sampling_frames_per_s_min_max": [round(fps["reference"][0], 1), round(fps["reference"][-1], 1)],
+        "device_sampling_ms_per_frame": round(1e3 / mid["device"], 4), "reference_sampling_ms_per_frame": round(1e3 / mid["reference"], 4),
+        "hip_graph": [free.graph is not None, ref.graph is not None],
+        "device_sampling_counts_last_frame": free.counts()[-1].tolist(), "device_sampling_overflow": list(free.overflow()),
+        "reference_sampling_counts_last_frame": [int(v) if v is not None else -1 for v in ref.log[-1][:2]],
+        "largest_centre_distance_between_the_two_trajectories": float(
+            np.linalg.norm(boxes["device"][:, :3] - boxes["reference"][:, :3], axis=1).max())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
@@ -158,13 +211,20 @@ def main():
     ap.add_argument("--model", default="BAT")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--targets", type=int, default=0, help="K > 0: the batched K-target loop against K single-target trackers in turn")
+    ap.add_argument("--sampling", default="reference", choices=tracking.SAMPLING,
+                    help="device: the free-running loop against the reference-sampling loop, frames/s of both")
+    ap.add_argument("--repeats", type=int, default=15, help="--sampling device: timed runs per loop (the median is reported)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("track_bench.py needs a GPU: the HIP library is the only compute path (no CPU fallback)")
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
     if args.targets > 0:
+        if args.sampling == "device":
+            raise SystemExit("--sampling device times the single-target loops; the K-target loops have no device sampling yet")
         return multi_target_main(args, dev)
+    if args.sampling == "device":
+        return sampling_main(args, dev)
     motion = args.model.upper() == "M2TRACK"
     if motion:
         model, cfg = motion_model(dev)
