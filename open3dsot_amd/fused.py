@@ -22,40 +22,15 @@ import torch
 from torch import nn
 from torch.autograd.graph import increment_version as _increment_version
 
-from . import capi
+from . import capi, gemm
+from .gemm import TILE, _PROF, _TAIL, _call, _const_vec, _ptr, _stream, _up, set_tail_split  # noqa: F401
 from .ops import QueryAndGroup
 
 POOL_BWD_SPLIT = capi.CONSTANTS["O3D_POOL_BWD_SPLIT"]
 _BnFinArgs = capi.struct("o3d_bn_fin_args")
 _BnBwdFinArgs = capi.struct("o3d_bn_bwd_fin_args")
 
-TILE = 128   # point columns are padded to this (the widest wave tile of the GEMM kernels, csrc/mlp_direct.hip)
 ETILE = 256  # columns per workgroup tile of the layer-0 expand kernel (csrc/compact.hip expand_c_kernel)
-
-# ---- optional per-kernel timing (bench.py's roofline leg) ---------------------------------
-_PROF = {"on": False, "events": []}
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _call(name, flops, fn, *args, dims=None):
-    """Launch one C-ABI entry; when profiling, bracket it with HIP events on the launch stream.
-    dims = (Cin, Cout[, pooled]) of a GEMM launch: only used for the per-launch roofline table of `profile_step`."""
-    if _PROF["on"]:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = fn(*args)
-        e1.record()
-        _PROF["events"].append((name, flops, e0, e1, dims))
-    else:
-        rc = fn(*args)
-    capi.check(rc, name)
 
 
 def _eval_consts(lib, bn, gamma, beta, vec, nrep, st, conv_bias=None):
@@ -344,44 +319,21 @@ def _shape_ok(npoint, ns):
     return 4 <= ns <= 256 and (ns & (ns - 1)) == 0 and (npoint * ns) % ETILE == 0
 
 
-def _const_vec(dev, n, value):
-    key = (str(dev), n, value)
-    v = _CONST.get(key)
-    if v is None:
-        v = _CONST[key] = torch.full((n,), float(value), device=dev, dtype=torch.float32)
-    return v
-
-
-_CONST = {}
-
-
 # ---- the autograd function ---------------------------------------------------------------
 class _Cfg:
     __slots__ = ("nxyz", "inv_radius", "training", "bns", "eps", "momentum", "centers", "geo", "geo_dims")
 
 
-def _direct_tile(lib, pmax, m):
-    """columns per wave tile (= per statistics partial row) of the GEMM launches of a level with `pmax` worst-case columns"""
-    return lib.o3d_direct_tile(pmax, m, 1)
-
-
-_TAIL = {"on": True, "applied": -1}       # "on": False = no split (tools/ab_hook.py fused._TAIL.on flips it for the same-box A/B)
-
-
-def set_tail_split(slots):
-    """TEST hook for the remainder-tile split of the large GEMM launches: -1 automatic (default), 0 off, S > 0 pretend S
-    resident slots (small problems then meet every branch of csrc/mlp_common.hpp::tail_plan)"""
-    capi.load().o3d_direct_tail_override(int(slots))
-    _TAIL["on"], _TAIL["applied"] = int(slots) != 0, int(slots)
-
-
-def _tail_rows(lib, tile, rows, nseg, layer):
-    """extra statistics rows behind the regular ones of a 128-column direct GEMM launch over the compact layout with `rows`
-    output rows (layers >= 1; layer 0's rows come from the expand kernel): one block of resident-slot size per segment"""
-    if not _TAIL["on"] and _TAIL["applied"] != 0:          # switched off through the dict (A/B tool): tell the library
-        lib.o3d_direct_tail_override(0)
-        _TAIL["applied"] = 0
-    return nseg * lib.o3d_direct_tail_slots(rows) if (tile == 128 and layer >= 1) else 0
+def _pack_points(lib, segs, nxyz, C, Ns, Npads, B, inv_radius, rows, ldz, st):
+    """the per-point operand X0 (rows, ldz) = [xyz * inv_radius ; feats] of one or two segments, clouds padded to Npads columns"""
+    nseg = len(segs)
+    X0n = torch.empty((rows, ldz), device=segs[0][0].device if nxyz else segs[0][2].device, dtype=torch.float32)
+    xs = [sg[0].detach().contiguous() if nxyz else None for sg in segs]
+    fs = [sg[2].detach().contiguous() if C else None for sg in segs]
+    _call("pack_points", 0.0, lib.o3d_pack_points, _ptr(xs[0]), _ptr(fs[0]), Ns[0], Npads[0],
+          _ptr(xs[-1]) if nseg == 2 else None, _ptr(fs[-1]) if nseg == 2 else None, Ns[-1] if nseg == 2 else 0,
+          Npads[-1] if nseg == 2 else 0, B, nxyz, C, float(inv_radius), rows, X0n.data_ptr(), st)
+    return X0n
 
 
 class FusedGroupedMLPCompact(torch.autograd.Function):
@@ -417,7 +369,7 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         C = segs[0][2].shape[1] if segs[0][2] is not None else 0
         Cin0, C0 = nxyz + C, Ws[0].shape[0]
         Ns = [sg[2].shape[2] if sg[2] is not None else sg[0].shape[1] for sg in segs]
-        Npads = [-(-n // TILE) * TILE for n in Ns]
+        Npads = [_up(n, TILE) for n in Ns]
         Pmaxs = [B * npt * ns for npt in npoints]
         starts = [0, Pmaxs[0]][:nseg]
         start1 = starts[1] if nseg == 2 else 0
@@ -455,14 +407,9 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         # rows padded to a multiple of 16 (zero rows, zero weight columns): the per-point GEMM then runs on the
         # direct MFMA kernel (csrc/mlp_direct.hip needs K % 16 == 0) instead of the generic LDS-staged one
         # (and the buffer itself to a multiple of 64 rows for the weight-gradient kernel of csrc/mlp_wgrad.hip)
-        Cin0p = -(-Cin0 // 16) * 16 if Cin0 > 16 else Cin0
-        Cin0m = -(-Cin0 // 64) * 64 if Cin0 > 16 else Cin0
-        X0n = torch.empty((Cin0m, ldz), device=dev, dtype=f32)
-        xs = [sg[0].detach().contiguous() if nxyz else None for sg in segs]
-        fs = [sg[2].detach().contiguous() if C else None for sg in segs]
-        _call("pack_points", 0.0, lib.o3d_pack_points, _ptr(xs[0]), _ptr(fs[0]), Ns[0], Npads[0],
-              _ptr(xs[-1]) if nseg == 2 else None, _ptr(fs[-1]) if nseg == 2 else None, Ns[-1] if nseg == 2 else 0,
-              Npads[-1] if nseg == 2 else 0, B, nxyz, C, float(cfg.inv_radius), Cin0m, X0n.data_ptr(), st)
+        Cin0p = _up(Cin0, 16) if Cin0 > 16 else Cin0
+        Cin0m = _up(Cin0, 64) if Cin0 > 16 else Cin0
+        X0n = _pack_points(lib, segs, nxyz, C, Ns, Npads, B, cfg.inv_radius, Cin0m, ldz, st)
         centers = None
         if nxyz:       # ball centres of every segment + the dummy ball (origin) of the padding columns
             centers = getattr(cfg, "centers", None)         # laid out like that by o3d_sample_query (sa_pair_sampled)
@@ -479,10 +426,11 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         if not direct3:
             Z = torch.empty((C0, ldz), device=dev, dtype=f32)
             W0p = prep.get(params[0], C0, Cin0p)
-            _call("conv_fwd_points", 2.0 * Cin0p * C0 * ldz, lib.o3d_mlp_conv_fwd, X0n.data_ptr(), W0p.data_ptr(),
-                  None, None, 1, Cin0p, C0, ldz, Z.data_ptr(), None, None, st, dims=(Cin0p, C0))
+            # (through the entry that forces 128-column tiles; the heads' stacks leave the tile to o3d_pw_fwd)
+            gemm.issue(gemm.flat_fwd("points", gemm.Layer(X0n), W0p, Cin0p, C0, ldz, Z, tile128=True))
         counts = [float(pm) for pm in Pmaxs]          # BatchNorm counts every slot (copies included)
-        Ys, means, invstds, scales, shifts = [], [], [], [], []
+        cl = gemm.Compact(ldp, cw, meta, start1, Pmaxs)
+        acts = []              # gemm.Layer per layer: raw output + (mean, invstd, scale, shift) per segment
         if cfg.training:       # shift of the second moment: the running means before this call, one row per segment
             if nseg == 1:
                 statcs = [bn.running_mean.detach().unsqueeze(0) for bn in cfg.bns]
@@ -495,12 +443,11 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         for l in range(L):
             Cout, Cin = Ws[l].shape
             bn = cfg.bns[l]
-            tile = ETILE if l == 0 else _direct_tile(lib, ldp, Cout)
             Y = torch.empty((Cout, ldp), device=dev, dtype=f32)
-            # (+ the rows of a direct GEMM launch's remainder tiles cut into column blocks: csrc/mlp_common.hpp::tail_plan)
-            part = torch.empty((ldp // tile + _tail_rows(lib, tile, Cout, nseg, l), 2, Cout), device=dev, dtype=f32) \
-                if cfg.training else None
             statc = statcs[l] if cfg.training else None
+            if l == 0:       # its statistics partials come from the expand kernel: one row per ETILE columns, the live ones
+                part = torch.empty((ldp // ETILE, 2, Cout), device=dev, dtype=f32) if cfg.training else None
+                stats = gemm.Partials(part, [pm // ETILE for pm in Pmaxs], (meta, ETILE))
             if l == 0 and direct3:
                 _call("group_expand", 0.0, lib.o3d_group_expand_c3, X0n.data_ptr(), ldz, gp.data_ptr(), cball.data_ptr(),
                       cw.data_ptr(), centers.data_ptr(), Ws[0].data_ptr(), Cin0, C0, meta.data_ptr(), start1, ldp,
@@ -510,18 +457,16 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                       cw.data_ptr(), _ptr(centers), Ws[0].data_ptr(), Cin0, C0, meta.data_ptr(), start1, ldp, Y.data_ptr(),
                       _ptr(part), _ptr(statc), st)
             else:
-                _call("conv_fwd", (2.0 * Cin * Cout, meta, ldp), lib.o3d_mlp_conv_fwd_c, Ys[-1].data_ptr(), Ws[l].data_ptr(),
-                      scales[-1].data_ptr(), shifts[-1].data_ptr(), Cin, Cout, ldp, cw.data_ptr(), meta.data_ptr(), start1,
-                      tile, Y.data_ptr(), _ptr(part), _ptr(statc), st, dims=(Cin, Cout))
+                stats = gemm.issue(gemm.compact_fwd(cl, acts[-1], Ws[l], Cin, Cout, Y, statc))
             vec = torch.empty((4, nseg, Cout), device=dev, dtype=f32)      # mean, invstd, scale, shift per segment
             if cfg.training:         # both segments in one launch; the running statistics see segment 0's update first
-                bn_finalize(lib, st, part, [pm // tile for pm in Pmaxs], counts, bn, gammas[l], betas[l], vec, statc, meta, tile)
+                bn_finalize(lib, st, stats.part, stats.rows, counts, bn, gammas[l], betas[l], vec, statc, *stats.live)
             else:
                 _eval_consts(lib, bn, gammas[l], betas[l], vec, nseg, st)
-            Ys.append(Y)
-            means.append(vec[0]); invstds.append(vec[1]); scales.append(vec[2]); shifts.append(vec[3])
+            acts.append(gemm.Layer(Y, vec))
         if cfg.training:
             count_batches(cfg.bns, nseg)
+        last = acts[-1]
         Cl = Ws[-1].shape[0]
         # pooled tensors: one (B, Cl, npoint_s) block per segment in one buffer
         out = torch.empty((nballs * Cl,), device=dev, dtype=f32)
@@ -530,11 +475,11 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         np1 = npoints[1] if nseg == 2 else 0
         if Cl % 64 == 0 and ns <= 32 and ldp >= 288:
             # lane = channel, a wave per ball over an LDS-transposed tile (csrc/compact.hip::pool_t_kernel)
-            _call("pool_fwd", 0.0, lib.o3d_pool_fwd_ct, Ys[-1].data_ptr(), ldp, scales[-1].data_ptr(), shifts[-1].data_ptr(),
+            _call("pool_fwd", 0.0, lib.o3d_pool_fwd_ct, last.Y.data_ptr(), ldp, last.scale.data_ptr(), last.shift.data_ptr(),
                   ball_off.data_ptr(), ball_cnt.data_ptr(), cball.data_ptr(), meta.data_ptr(), start1, B, Cl, npoints[0], np1,
                   ns, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
         else:       # shapes the transposed tile does not take (nsample 64, channels % 64): lanes along the ball's columns
-            _call("pool_fwd", 0.0, lib.o3d_pool_fwd_c, Ys[-1].data_ptr(), ldp, scales[-1].data_ptr(), shifts[-1].data_ptr(),
+            _call("pool_fwd", 0.0, lib.o3d_pool_fwd_c, last.Y.data_ptr(), ldp, last.scale.data_ptr(), last.shift.data_ptr(),
                   ball_off.data_ptr(), ball_cnt.data_ptr(), B, Cl, npoints[0], np1, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
         if need_bwd:
             ctx.cfg = cfg
@@ -542,10 +487,9 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
             # weights as the backward's GEMMs want them: W_l^T for the data gradients, W0^T padded to 64 rows
             ctx.Wts = [None] + [prep.get(params[3 * l], Ws[l].shape[1], Ws[l].shape[0], transpose=True) for l in range(1, L)]
             want_in = any(ctx.needs_input_grad[2:2 + 4 * nseg])
-            ctx.W0t = prep.get(params[0], -(-Cin0 // 64) * 64, C0, transpose=True) if want_in else None
+            ctx.W0t = prep.get(params[0], _up(Cin0, 64), C0, transpose=True) if want_in else None
             ctx.geom = (B, ns, C, nseg, Ns, Npads, npoints, Pmaxs, starts, pt_bases, ball_bases, nballs_s)
-            ctx.saved = (X0n, centers, ball_off, ball_cnt, gp, cball, cw, meta, Ws, gammas, Ys, means, invstds, scales,
-                         shifts, out.detach(), argq, yarg)
+            ctx.saved = (X0n, centers, ball_off, ball_cnt, gp, cball, cw, meta, Ws, gammas, acts, out.detach(), argq, yarg)
         outs = tuple(out[ball_bases[s_] * Cl:(ball_bases[s_] + nballs_s[s_]) * Cl].view(B, Cl, npoints[s_])
                      for s_ in range(nseg))
         return outs if nseg > 1 else outs[0]
@@ -557,8 +501,7 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         cfg = ctx.cfg
         _check_versions(ctx.versions, "FusedGroupedMLPCompact")
         B, ns, C, nseg, Ns, Npads, npoints, Pmaxs, starts, pt_bases, ball_bases, nballs_s = ctx.geom
-        (X0n, centers, ball_off, ball_cnt, gp, cball, cw, meta, Ws, gammas, Ys, means, invstds, scales, shifts, out,
-         argq, yarg) = ctx.saved
+        X0n, centers, ball_off, ball_cnt, gp, cball, cw, meta, Ws, gammas, acts, out, argq, yarg = ctx.saved
         L = len(Ws)
         dev = out.device
         st = _stream()
@@ -567,6 +510,7 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         ldp, ldz, nballs = sum(Pmaxs), X0n.shape[1], sum(nballs_s)
         start1 = starts[1] if nseg == 2 else 0
         counts = [float(pm) for pm in Pmaxs]
+        cl = gemm.Compact(ldp, cw, meta, start1, Pmaxs)
         grads = [None] * (3 * L)
         needs = ctx.needs_input_grad[2:2 + 4 * nseg]
         want_xyz = nxyz > 0 and any(needs[4 * s_] or needs[4 * s_ + 1] for s_ in range(nseg))
@@ -588,8 +532,10 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                 gsrc += [None, 0, 0]
             part = torch.empty((ldp // POOL_DENSE_COLS, 2, Cl), device=dev, dtype=f32)
             _call("pool_bwd", 0.0, lib.o3d_pool_bwd_dense, *gsrc, out.data_ptr(), argq.data_ptr(), yarg.data_ptr(),
-                  means[-1].data_ptr(), cball.data_ptr(), ball_off.data_ptr(), meta.data_ptr(), start1, ldp, B, Cl, npoints[0],
+                  acts[-1].mean.data_ptr(), cball.data_ptr(), ball_off.data_ptr(), meta.data_ptr(), start1, ldp, B, Cl, npoints[0],
                   np1, dN.data_ptr(), part.data_ptr(), st)
+            # one row per POOL_DENSE_COLS columns, the live ones
+            stats = gemm.Partials(part, [pm // POOL_DENSE_COLS for pm in Pmaxs], (meta, POOL_DENSE_COLS))
         else:
             # pooled-layer gradient: the segments' (B, Cl, npoint) blocks back to back, like `out`
             if nseg == 1:
@@ -604,27 +550,23 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                         dst.copy_(dOuts[s_])
             part = torch.empty((nseg, POOL_BWD_SPLIT, 2, Cl), device=dev, dtype=f32)
             _call("pool_bwd", 0.0, lib.o3d_pool_bwd_c, dOut.data_ptr(), out.data_ptr(), argq.data_ptr(), yarg.data_ptr(),
-                  means[-1].data_ptr(), B, Cl, npoints[0], np1, meta.data_ptr(), start1, ldp, dN.data_ptr(),
+                  acts[-1].mean.data_ptr(), B, Cl, npoints[0], np1, meta.data_ptr(), start1, ldp, dN.data_ptr(),
                   part.data_ptr(), st)
-        dtile = POOL_DENSE_COLS if pool_dense else 0
-        part_rows = 0    # > 0: `part` comes from the fused data + weight gradient kernel (rows per segment block)
+            stats = gemm.Partials(part, [POOL_BWD_SPLIT] * nseg, ())      # POOL_BWD_SPLIT rows per segment, all live
         seg_grads = [[None, None, None] for _ in range(nseg)]
         for l in range(L - 1, -1, -1):
             Cout, Cin = Ws[l].shape
-            if l == L - 1 and not pool_dense:       # partials of the pool backward: POOL_BWD_SPLIT rows per segment, all live
-                rows, live = [POOL_BWD_SPLIT] * nseg, ()
-            elif part_rows:      # partials of the fused data + weight gradient kernel: part_rows rows per segment block, all live
-                rows, live = [part_rows] * nseg, ()
-            else:                # one row per dtile columns, the live ones
-                rows, live = [pm // dtile for pm in Pmaxs], (meta, dtile)
-            coef, A = bn_bwd_finalize(lib, st, cfg.training, part, rows, counts, gammas[l], means[l], invstds[l], *live)
+            act = acts[l]
+            coef, A = bn_bwd_finalize(lib, st, cfg.training, stats.part, stats.rows, counts, gammas[l], act.mean, act.invstd,
+                                      *stats.live)
+            g = gemm.Grad(dN, act.Y, A)
             grads[3 * l + 1], grads[3 * l + 2] = coef[0, 0], coef[1, 0]      # summed over the segments by the kernel
             if l == 0 and C == 0 and nxyz == 3 and not (want_xyz or want_feats):
                 # xyz-only layer 0, nobody wants the input gradient (SA level 0): dW0 straight from the columns, no list
                 # sums, no K = 3 GEMM, no centre term (csrc/compact.hip::dw0_xyz_kernel)
                 part0 = torch.empty((ldp // 256, Cout, 3), device=dev, dtype=f32)
                 dW = torch.empty((Cout, 3), device=dev, dtype=f32)
-                _call("group_dw0", 0.0, lib.o3d_group_dw0_xyz, dN.data_ptr(), Ys[0].data_ptr(), ldp, A[0], A[1], A[2],
+                _call("group_dw0", 0.0, lib.o3d_group_dw0_xyz, dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1], A[2],
                       gp.data_ptr(), cball.data_ptr(), cw.data_ptr(), X0n.data_ptr(), ldz, centers.data_ptr(), meta.data_ptr(),
                       start1, Cout, part0.data_ptr(), dW.data_ptr(), st)
                 grads[0] = dW
@@ -638,36 +580,19 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                 if npo >= 0:     # the cloud's columns through a transposed index: one LDS atomic per run of equal points
                     perm = torch.empty((ldp,), device=dev, dtype=torch.int32)
                     poff = torch.empty((npo,), device=dev, dtype=torch.int32)
-                    _call("group_reduce", 0.0, lib.o3d_group_reduce_gather, dN.data_ptr(), Ys[0].data_ptr(), ldp, A[0], A[1],
+                    _call("group_reduce", 0.0, lib.o3d_group_reduce_gather, dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1],
                           A[2], gp.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(), B, nseg, npoints[0],
                           Npads[0], npoints[-1], Npads[-1], Cout, spanmax, perm.data_ptr(), poff.data_ptr(), S.data_ptr(),
                           _ptr(T), st)
                 else:            # the index does not fit the LDS budget (o3d_group_reduce_gather_scratch < 0): one LDS atomic per column
-                    _call("group_reduce", 0.0, lib.o3d_group_reduce_c, dN.data_ptr(), Ys[0].data_ptr(), ldp, A[0], A[1], A[2],
+                    _call("group_reduce", 0.0, lib.o3d_group_reduce_c, dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1], A[2],
                           gp.data_ptr(), cball.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(), B, nseg,
                           npoints[0], Npads[0], npoints[-1], Npads[-1], Cout, S.data_ptr(), _ptr(T), st)
-                one, zero = _const_vec(dev, Cout, 1.0), _const_vec(dev, Cout, 0.0)
-                Cinm = X0n.shape[0]                  # rows of the padded per-point operand
-                aligned = Cinm % 64 == 0
-                if aligned:       # the tile-matched MFMA weight-gradient kernel, X as stored
-                    wpart = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Cinm, Cout, ldz),), device=dev, dtype=f32)
-                    dWm = torch.empty((Cout, Cinm), device=dev, dtype=f32)
-                else:
-                    tiles = ((Cin + 127) // 128) * ((Cout + 127) // 128)
-                    total_chunks = ldz // 32
-                    nsl = max(1, min(total_chunks // 4 if total_chunks >= 4 else 1, 768 // tiles))
-                    wpart = torch.empty((nsl + 16, Cout, Cin), device=dev, dtype=f32)
-                    dWm = torch.empty((Cout, Cin), device=dev, dtype=f32)
-                fold = bool(nxyz) and dWm.shape[1] != Cin
+                Cinm = X0n.shape[0]                  # rows of the padded per-point operand, X as stored
+                dWm = torch.empty((Cout, Cinm), device=dev, dtype=f32)
+                fold = bool(nxyz) and Cinm != Cin
                 dW = torch.empty((Cout, Cin), device=dev, dtype=f32) if fold else None
-                if aligned:
-                    _call("conv_wgrad_points", 2.0 * Cinm * Cout * ldz, lib.o3d_mlp_conv_wgrad2, S.data_ptr(), None, 4,
-                          S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None, None, 1,
-                          Cinm, Cout, ldz, wpart.data_ptr(), dWm.data_ptr(), st, dims=(Cinm, Cout, True))
-                else:
-                    _call("conv_wgrad_points", 2.0 * Cin * Cout * ldz, lib.o3d_mlp_conv_wgrad, S.data_ptr(), None, None,
-                          None, 4, S.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0n.data_ptr(), None,
-                          None, 1, Cin, Cout, ldz, nsl, wpart.data_ptr(), dWm.data_ptr(), st)
+                gemm.issue(gemm.flat_wgrad("points", gemm.Grad.plain(S), gemm.Layer(X0n), Cinm, Cout, ldz, dWm))
                 if fold:
                     # the centre term of grouped_xyz = xyz[idx] - new_xyz and the compaction of the padded rows in one
                     # launch (was: the term in place, then a strided torch copy of dWm[:, :Cin])
@@ -681,11 +606,10 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                 grads[0] = dW
                 if want_xyz or want_feats:
                     # dX = W0^T . S as a plain forward GEMM on the direct MFMA kernel: rows padded to a multiple of 64
-                    Cinm = -(-Cin // 64) * 64
-                    W0t = ctx.W0t                                                          # (Cinm, Cout), rows >= Cin zero
+                    Cinm = _up(Cin, 64)
                     dX = torch.empty((Cinm, ldz), device=dev, dtype=f32)
-                    _call("conv_dgrad_points", 2.0 * Cinm * Cout * ldz, lib.o3d_mlp_conv_fwd, S.data_ptr(), W0t.data_ptr(),
-                          None, None, 1, Cout, Cinm, ldz, dX.data_ptr(), None, None, st, dims=(Cout, Cinm))
+                    # (W0t: (Cinm, Cout), rows >= Cin zero)
+                    gemm.issue(gemm.flat_fwd("points", gemm.Layer(S), ctx.W0t, Cout, Cinm, ldz, dX, tile128=True, kind="dgrad"))
                     dnew_all = None
                     if want_xyz:      # -inv_radius * W0[:, :3]^T . T (3, balls): one small launch (was a torch.addmm on rocBLAS)
                         dnew_all = torch.empty((3, nballs), device=dev, dtype=f32)
@@ -701,36 +625,15 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                             seg_grads[s_][1] = dnew_all[:, ball_bases[s_]:ball_bases[s_] + nballs_s[s_]].reshape(
                                 3, B, npoints[s_]).permute(1, 2, 0)
                 continue
-            rows_fb = lib.o3d_mlp_conv_bwd_fused_rows(Cin, Cout, ldp) if Cout <= FUSED_BWD_MAX_COUT else -1
-            if rows_fb > 0:      # data + weight gradient in one launch (64-channel layers; csrc/mlp_wgrad.hip)
-                dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
-                wpart = torch.empty((lib.o3d_mlp_conv_bwd_fused_scratch(Cin, Cout, ldp),), device=dev, dtype=f32)
-                dNp = torch.empty((Cin, ldp), device=dev, dtype=f32)
-                part = torch.empty((2, rows_fb, 2, Cin), device=dev, dtype=f32)
-                _call("conv_bwd_fused", (4.0 * Cin * Cout, meta, ldp), lib.o3d_mlp_conv_bwd_fused_c, dN.data_ptr(),
-                      Ys[l].data_ptr(), A[0], A[1], A[2], Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(),
-                      shifts[l - 1].data_ptr(), means[l - 1].data_ptr(), ctx.Wts[l].data_ptr(), Cin, Cout, ldp, cw.data_ptr(),
-                      meta.data_ptr(), start1, wpart.data_ptr(), dW.data_ptr(), part.data_ptr(), dNp.data_ptr(), st,
-                      dims=(Cin, Cout))
-                grads[3 * l] = dW
-                dN, part_rows = dNp, rows_fb
-                continue
-            part_rows = 0
-            flops = (2.0 * Cin * Cout, meta, ldp)      # executed FLOPs = per live column (count read back when profiling)
-            dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
-            wpart = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Cin, Cout, ldp),), device=dev, dtype=f32)
-            _call("conv_wgrad", flops, lib.o3d_mlp_conv_wgrad2_c, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
-                  Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), Cin, Cout, ldp, cw.data_ptr(),
-                  meta.data_ptr(), start1, wpart.data_ptr(), dW.data_ptr(), st, dims=(Cin, Cout))
-            grads[3 * l] = dW
-            Wt = ctx.Wts[l]
+            dW = grads[3 * l] = torch.empty((Cout, Cin), device=dev, dtype=f32)
             dNp = torch.empty((Cin, ldp), device=dev, dtype=f32)
-            dtile = _direct_tile(lib, ldp, Cin)
-            part = torch.empty((ldp // dtile + _tail_rows(lib, dtile, Cin, nseg, 1), 2, Cin), device=dev, dtype=f32)
-            _call("conv_dgrad", flops, lib.o3d_mlp_conv_dgrad_c, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2], Wt.data_ptr(),
-                  Cin, Cout, ldp, cw.data_ptr(), meta.data_ptr(), start1, dtile, Ys[l - 1].data_ptr(),
-                  scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), means[l - 1].data_ptr(), dNp.data_ptr(),
-                  part.data_ptr(), st, dims=(Cin, Cout))
+            # data + weight gradient in one launch (64-channel layers; csrc/mlp_wgrad.hip), else the pair
+            both = gemm.compact_bwd_fused(cl, g, ctx.Wts[l], Cin, Cout, acts[l - 1], dW, dNp)
+            if both is not None:
+                stats = gemm.issue(both)[0]
+            else:
+                gemm.issue(gemm.compact_wgrad(cl, g, acts[l - 1], Cin, Cout, dW))
+                stats = gemm.issue(gemm.compact_dgrad(cl, g, ctx.Wts[l], Cin, Cout, acts[l - 1], dNp))
             dN = dNp
         gw = []
         for l in range(L):
@@ -753,9 +656,6 @@ def set_pool_bwd_dense(enabled):
     _POOL_BWD_DENSE["on"] = bool(enabled)
 
 
-# data + weight gradient of a 64-input-channel inner layer in ONE kernel (csrc/mlp_wgrad.hip::fused_bwd_kernel: SA level 0's
-# 64 -> 64 and 64 -> 128 layers); wider outputs take the wgrad2 + direct-dgrad pair
-FUSED_BWD_MAX_COUT = 128
 # layer-0 backward reduce through a transposed index (csrc/compact.hip::reduce_gather_kernel) whenever its index fits the LDS
 # budget; the per-column LDS-atomic kernel (reduce_c_kernel) is the fallback for larger clouds.  `set_reduce_gather(False)`
 # forces the fallback: a TEST hook (tests/test_fused_gpu.py runs both), not a tuning switch.
@@ -817,23 +717,17 @@ def _run_eval(mlp, layers, segs, nxyz, inv_radius):
     Ws = [conv.weight.detach().reshape(conv.out_channels, -1) for conv, _ in layers]
     Cin0, C0 = nxyz + C, Ws[0].shape[0]
     Ns = [sg[2].shape[2] if sg[2] is not None else sg[0].shape[1] for sg in segs]
-    Npads = [-(-n // TILE) * TILE for n in Ns]
+    Npads = [_up(n, TILE) for n in Ns]
     pt_bases = [0, B * Npads[0]][:nseg]
     ldz = sum(B * n for n in Npads)
-    Cin0p = -(-Cin0 // 16) * 16 if Cin0 > 16 else Cin0
+    Cin0p = _up(Cin0, 16) if Cin0 > 16 else Cin0
     with torch.cuda.device(dev):
         st = _stream()
-        X0n = torch.empty((Cin0p, ldz), device=dev, dtype=f32)
-        xs = [sg[0].detach().contiguous() if nxyz else None for sg in segs]
-        fs = [sg[2].detach().contiguous() if C else None for sg in segs]
-        _call("pack_points", 0.0, lib.o3d_pack_points, _ptr(xs[0]), _ptr(fs[0]), Ns[0], Npads[0],
-              _ptr(xs[-1]) if nseg == 2 else None, _ptr(fs[-1]) if nseg == 2 else None, Ns[-1] if nseg == 2 else 0,
-              Npads[-1] if nseg == 2 else 0, B, nxyz, C, float(inv_radius), Cin0p, X0n.data_ptr(), st)
+        X0n = _pack_points(lib, segs, nxyz, C, Ns, Npads, B, inv_radius, Cin0p, ldz, st)
         from .fused_heads import prep_for
         W0p = prep_for(dev).get(layers[0][0].weight, C0, Cin0p)
         Z = torch.empty((C0, ldz), device=dev, dtype=f32)
-        _call("conv_fwd_points", 2.0 * Cin0p * C0 * ldz, lib.o3d_mlp_conv_fwd, X0n.data_ptr(), W0p.data_ptr(), None, None, 1,
-              Cin0p, C0, ldz, Z.data_ptr(), None, None, st)
+        gemm.issue(gemm.flat_fwd("points", gemm.Layer(X0n), W0p, Cin0p, C0, ldz, Z, tile128=True, row=False))
         vecs = [_eval_vec(lib, bn, bn.weight, bn.bias, st) for _, bn in layers]
         outs = []
         for s_, sg in enumerate(segs):
@@ -860,14 +754,16 @@ def _compact_ok(layers, npoint, ns, B):
     return layers[0][0].out_channels % 64 == 0
 
 
+def _cfg_params(mlp, layers, nxyz, inv_radius):
+    """(cfg, [W, gamma, beta per layer]) of FusedGroupedMLPCompact.apply"""
+    cfg = _Cfg()
+    cfg.nxyz, cfg.inv_radius, cfg.training, cfg.bns = nxyz, float(inv_radius), bool(mlp.training), [bn for _, bn in layers]
+    return cfg, [p for conv, bn in layers for p in (conv.weight, bn.weight, bn.bias)]
+
+
 def _run(mlp, xyz, new_xyz, feats, idx, nxyz, inv_radius):
     layers = _layers(mlp)
-    cfg = _Cfg()
-    cfg.nxyz, cfg.inv_radius, cfg.training = nxyz, float(inv_radius), bool(mlp.training)
-    cfg.bns = [bn for _, bn in layers]
-    params = []
-    for conv, bn in layers:
-        params += [conv.weight, bn.weight, bn.bias]
+    cfg, params = _cfg_params(mlp, layers, nxyz, inv_radius)
     B, npoint, ns = idx.shape
     if _eval_fused_ok(mlp, layers, [(xyz, new_xyz, feats, idx)], nxyz):
         return _run_eval(mlp, layers, [(xyz, new_xyz, feats, idx)], nxyz, float(inv_radius))[0]
@@ -900,19 +796,12 @@ def sa_group_mlp_pool_pair(grouper, mlp, a, b):
     B, np_a, ns = idx_a.shape
     np_b = idx_b.shape[1]
     layers = _layers(mlp)
-    if not (_shape_ok(np_a, ns) and _shape_ok(np_b, ns) and _compact_ok(layers, np_a, ns, B) and
-            _compact_ok(layers, np_b, ns, B) and (B * np_a * ns) % 256 == 0):
+    if not _pair_shapes_ok(layers, B, np_a, np_b, ns):
         return None
     inv_r = float(1.0 / grouper.radius if grouper.normalize_xyz else 1.0)
     if _eval_fused_ok(mlp, layers, [(a[0], a[1], a[2], idx_a), (b[0], b[1], b[2], idx_b)], 3):
         return tuple(_run_eval(mlp, layers, [(a[0], a[1], a[2], idx_a), (b[0], b[1], b[2], idx_b)], 3, inv_r))
-    cfg = _Cfg()
-    cfg.nxyz, cfg.training = 3, bool(mlp.training)
-    cfg.inv_radius = inv_r
-    cfg.bns = [bn for _, bn in layers]
-    params = []
-    for conv, bn in layers:
-        params += [conv.weight, bn.weight, bn.bias]
+    cfg, params = _cfg_params(mlp, layers, 3, inv_r)
     return FusedGroupedMLPCompact.apply(cfg, 2, a[0], a[1], a[2], idx_a, b[0], b[1], b[2], idx_b, *params)
 
 
@@ -947,7 +836,7 @@ def pair_geometry(grouper, mlp, xyz_a, np_a, si_a, xyz_b, np_b, si_b, out=None):
     xa, xb = xyz_a.detach().contiguous(), xyz_b.detach().contiguous()
     nb_a, nb_b = B * np_a, B * np_b
     nballs, ldp = nb_a + nb_b, (nb_a + nb_b) * ns
-    Npad_a, Npad_b = -(-xa.shape[1] // TILE) * TILE, -(-xb.shape[1] // TILE) * TILE
+    Npad_a, Npad_b = _up(xa.shape[1], TILE), _up(xb.shape[1], TILE)
     shapes = {"centers": ((nballs + 1, 3), f32), "ball_cnt": ((nballs,), i32), "ball_off": ((nballs + 1,), i32),
               "gp": ((ldp,), i32), "cball": ((ldp,), i32), "cw": ((ldp,), f32), "meta": ((2, 4), i32)}
     if out is not None and all(k in out and tuple(out[k].shape) == sh and out[k].dtype == dt and out[k].device == dev and
@@ -985,8 +874,7 @@ def sa_pair_sampled(grouper, mlp, a, b, geo=None):
         return None
     B, ns = xyz_a.shape[0], grouper.nsample
     layers = _layers(mlp)
-    if not (_shape_ok(np_a, ns) and _shape_ok(np_b, ns) and _compact_ok(layers, np_a, ns, B) and
-            _compact_ok(layers, np_b, ns, B) and (B * np_a * ns) % 256 == 0):
+    if not _pair_shapes_ok(layers, B, np_a, np_b, ns):
         return None
     if (si_a is None and np_a > xyz_a.shape[1]) or (si_b is None and np_b > xyz_b.shape[1]):
         return None
@@ -1017,15 +905,9 @@ def sa_pair_sampled(grouper, mlp, a, b, geo=None):
     if geo is None and _eval_fused_ok(mlp, layers, [(xa, new_a, f_a, idx_a), (xb, new_b, f_b, idx_b)], 3):
         outs = _run_eval(mlp, layers, [(xa, new_a, f_a, idx_a), (xb, new_b, f_b, idx_b)], 3, inv_r)
         return new_a, outs[0], new_b, outs[1]
-    cfg = _Cfg()
-    cfg.nxyz, cfg.training = 3, bool(mlp.training)
-    cfg.inv_radius = inv_r
-    cfg.bns = [bn for _, bn in layers]
+    cfg, params = _cfg_params(mlp, layers, 3, inv_r)
     cfg.centers = centers
     cfg.geo, cfg.geo_dims = geo, (B, ns, (np_a, np_b))
-    params = []
-    for conv, bn in layers:
-        params += [conv.weight, bn.weight, bn.bias]
     outs = FusedGroupedMLPCompact.apply(cfg, 2, xa, new_a, f_a, idx_a, xb, new_b, f_b, idx_b, *params)
     return new_a, outs[0], new_b, outs[1]
 

@@ -22,29 +22,19 @@ import weakref
 
 import torch
 
-from . import capi
-from .fused import _call, _const_vec, _eval_consts, _ptr, _stream, bn_bwd_coef, bn_bwd_fin_job, bn_fin_job, count_batches, \
-    counters_begin, counters_end
-
-_WgradJob = capi.struct("o3d_wgrad_job")
+from . import capi, gemm
+from .fused import _call, _check_versions, _const_vec, _eval_consts, _stream, _versions, bn_bwd_coef, bn_bwd_fin_job, \
+    bn_fin_job, count_batches, counters_begin, counters_end
+from .gemm import _WgradJob, _up  # noqa: F401  (names other modules and the kernel pins reach through this module)
 
 # the weight gradients of a stack are ONE grouped launch (+ one reduction launch) at the end of its backward instead of a
-# launch + reduction per layer (csrc/mlp_wgrad.hip::wgrad2_group_kernel)
-_MAXJOBS = 8                # WG_MAXJOBS of csrc/mlp_wgrad.hip
+# launch + reduction per layer (gemm.flat_wgrad_job / gemm.flush_wgrad_jobs)
 # Deferred weight gradients: inside `defer_wgrads()` (the training step of open3dsot_amd/dist.py wraps loss.backward() in
 # it) the stacks do not launch their grouped weight gradients at the end of their own backward but queue the jobs; the
 # queue is flushed in groups of 8 when the scope ends -- the heads' 23 jobs of a BAT step in 3 launches + 3 reductions
 # instead of 7 + 7.  The gradient tensors autograd was handed are filled by the flush: the scope must end before anything
 # reads them (AccumulateGrad only stores them; `_deferrable` lists what that requires of the parameters).
 _DEFER = {"queue": None, "keys": None}
-
-
-def _flush_jobs(jobs, st):
-    lib = capi.load()
-    for j0 in range(0, len(jobs), _MAXJOBS):
-        chunk = jobs[j0:j0 + _MAXJOBS]
-        arr = (_WgradJob * len(chunk))(*[_WgradJob(*j[1]) for j in chunk])
-        _call("pw_conv_wgrad", sum(j[0] for j in chunk), lib.o3d_mlp_conv_wgrad2_group, ctypes.addressof(arr), len(chunk), st)
 
 
 def _flush_queue():
@@ -55,7 +45,7 @@ def _flush_queue():
     for jobs, keep, st in q:
         by_stream.setdefault(st, []).extend(jobs)
     for st, jobs in by_stream.items():
-        _flush_jobs(jobs, st)
+        gemm.flush_wgrad_jobs(jobs, st)
 
 
 def _deferrable(params):
@@ -83,7 +73,7 @@ def _submit_jobs(jobs, keep, st, params):
     if not jobs:
         return
     if _DEFER["queue"] is None:
-        _flush_jobs(jobs, st)
+        gemm.flush_wgrad_jobs(jobs, st)
         return
     keys = {id(p) for p in params if p is not None}
     _DEFER["queue"].append((jobs, keep, st))      # (the queue keeps the operands alive until the flush)
@@ -115,10 +105,6 @@ def set_fused_heads(enabled):
 
 def enabled():
     return _ON["on"]
-
-
-def _up(v, m):
-    return -(-v // m) * m
 
 
 _RowsSrc = capi.struct("o3d_rows_src")
@@ -363,7 +349,7 @@ def _drive(gens):
             pend[k], done[k], res[k] = None, True, e.value
 
     def issue(ks):       # the pending launch of generator ks[0]; a finalize: the jobs of all of `ks` in ONE launch
-        name, flops, entry, args, dims = pend[ks[0]]
+        name, flops, entry, args, dims = pend[ks[0]][:5]
         if entry in _JOB_ENTRIES:
             arr = (type(args) * len(ks))(*[pend[k][3] for k in ks])
             args = [ctypes.addressof(arr), len(ks), _stream()]
@@ -398,7 +384,6 @@ class _State:
 
 def _chain_forward(cfg, tensors, need_bwd):
     """generator: launches of one stack's forward; returns (output view (B,Cout,N), state for the backward | None)"""
-    lib = capi.load()
     srcs, params = tensors[:cfg.nsrc], tensors[cfg.nsrc:]
     L = len(params) // 4
     B, _, N = srcs[0].shape
@@ -411,7 +396,7 @@ def _chain_forward(cfg, tensors, need_bwd):
     X0 = _as_flat(srcs[0].detach()) if (cfg.nsrc == 1 and K0 == K0p) else None
     if X0 is None:
         X0 = pack_rows([t.detach() for t in srcs], K0p)
-    Ys, vecs, Wts = [], [], []
+    acts, Wts = [], []          # gemm.Layer per layer: raw output (+ mean, invstd, scale, shift of a hidden layer)
     Kp = K0p
     for l in range(L):
         W, bias, gamma, beta = params[4 * l:4 * l + 4]
@@ -420,36 +405,27 @@ def _chain_forward(cfg, tensors, need_bwd):
         Wp = prep.get(W, Mp, Kp)
         if need_bwd:
             Wts.append(prep.get(W, Kp, Mp, transpose=True))
-        src = X0 if l == 0 else Ys[-1]
-        sc = None if l == 0 else vecs[-1][2].data_ptr()
-        sh = None if l == 0 else vecs[-1][3].data_ptr()
+        src = gemm.Layer(X0) if l == 0 else acts[-1]
         Y = torch.empty((Mp, P), device=dev, dtype=f32)
+        vec = None
         if l < L - 1:
             bn = cfg.bns[l]
             vec = torch.empty((4, Mp), device=dev, dtype=f32)            # mean, invstd, scale, shift
+            la = gemm.flat_fwd("pw", src, Wp, Kp, Mp, P, Y, bn.running_mean if cfg.training else None)
+            yield la
             if cfg.training:
-                nparts = P // lib.o3d_pw_tile(P, Mp)
-                part = torch.empty((nparts, 2, Mp), device=dev, dtype=f32)
-                yield ("pw_conv_fwd", 2.0 * Kp * Mp * P, "o3d_pw_fwd", [src.data_ptr(), Wp.data_ptr(), sc, sh, None, None, Kp, Mp,
-                                                                       P, Y.data_ptr(), part.data_ptr(),
-                                                                       bn.running_mean.data_ptr(), st], (Kp, Mp))
                 yield ("bn_finalize", 0.0, "o3d_bn_finalize",
-                       bn_fin_job(part, [nparts], [float(P)], bn, gamma, beta, vec, bn.running_mean), None)
+                       bn_fin_job(la.out.part, la.out.rows, [float(P)], bn, gamma, beta, vec, bn.running_mean), None)
             else:
-                yield ("pw_conv_fwd", 2.0 * Kp * Mp * P, "o3d_pw_fwd", [src.data_ptr(), Wp.data_ptr(), sc, sh, None, None, Kp, Mp,
-                                                                       P, Y.data_ptr(), None, None, st], (Kp, Mp))
-                _eval_consts(lib, bn, gamma, beta, vec, 1, st)
-            vecs.append(vec)
+                _eval_consts(capi.load(), bn, gamma, beta, vec, 1, st)
         else:
             bp = prep.get(bias, 1, Mp) if bias is not None else None
             if cfg.residual and Mp != K0p:
                 raise ValueError("residual stack: padded output rows %d != padded input rows %d" % (Mp, K0p))
             if bp is None and not cfg.residual:       # plain store without statistics
                 bp = _const_vec(dev, Mp, 0.0)
-            yield ("pw_conv_fwd", 2.0 * Kp * Mp * P, "o3d_pw_fwd", [src.data_ptr(), Wp.data_ptr(), sc, sh, _ptr(bp),
-                                                                   X0.data_ptr() if cfg.residual else None, Kp, Mp, P,
-                                                                   Y.data_ptr(), None, None, st], (Kp, Mp))
-        Ys.append(Y)
+            yield gemm.flat_fwd("pw", src, Wp, Kp, Mp, P, Y, bias=bp, resid=X0 if cfg.residual else None)
+        acts.append(gemm.Layer(Y, vec))
         Kp = Mp
     if cfg.training and L > 1:
         count_batches(cfg.bns[:L - 1], 1)
@@ -459,110 +435,83 @@ def _chain_forward(cfg, tensors, need_bwd):
         state = _State()
         state.cfg = cfg
         state.geom = (B, N, L, K0, K0p, [t.shape[1] for t in srcs])
-        state.versions = [(p, p._version) for p in params if p is not None]
-        state.saved = (X0, Ys, vecs, Wts, [params[4 * l + 2] for l in range(L)], [params[4 * l] for l in range(L)])
+        state.versions = _versions(params)
+        state.saved = (X0, acts, Wts, [params[4 * l + 2] for l in range(L)], [params[4 * l] for l in range(L)])
         state.biases = [params[4 * l + 1] for l in range(L)]
-    return Ys[-1][:Cl].view(Cl, B, N).permute(1, 0, 2), state
+    return acts[-1].Y[:Cl].view(Cl, B, N).permute(1, 0, 2), state
 
 
 def _chain_backward(state, dOut, needs):
     """generator: launches of one stack's backward; `needs` = needs_input_grad of (sources..., 4 parameters per layer);
     returns the list of gradients in that order"""
-    lib = capi.load()
     cfg = state.cfg
     B, N, L, K0, K0p, src_C = state.geom
-    for p, v in state.versions:
-        if p._version != v:
-            raise RuntimeError("a parameter of a fused conv stack was modified in place between forward and backward")
-    X0, Ys, vecs, Wts, gammas, Ws = state.saved
+    _check_versions(state.versions, "fused conv stack")
+    X0, acts, Wts, gammas, Ws = state.saved
     P = B * N
     dev, f32 = dOut.device, torch.float32
     st = _stream()
-    nparts = 0
     Cl = Ws[-1].shape[0]
-    Mp = Ys[-1].shape[0]
+    Mp = acts[-1].Y.shape[0]
     G = _as_flat(dOut) if Cl == Mp else None
     if G is None:
         G = pack_rows([dOut], Mp)
     grads = [None] * (4 * L)
     want_x = any(needs[:cfg.nsrc])
-    one, zero = _const_vec(dev, Mp, 1.0), _const_vec(dev, Mp, 0.0)
+    resid = G if cfg.residual else None
     dX0 = None
 
     keep = []            # what the (possibly deferred) grouped launch reads or writes: alive until it has run
     jobs = []            # grouped weight gradients: launched together behind the data-gradient chain
 
-    def wgrad(l, dN, Y, A, Cout_p, coef=None):
-        Xs = X0 if l == 0 else Ys[l - 1]
-        Kp = Xs.shape[0]
-        sc = None if l == 0 else vecs[l - 1][2].data_ptr()
-        sh = None if l == 0 else vecs[l - 1][3].data_ptr()
+    def wgrad(l, g, Cout_p, coef=None):
+        src = gemm.Layer(X0) if l == 0 else acts[l - 1]
         Wl = Ws[l]
-        Cout, Cin = Wl.shape[0], Wl.shape[1]
         # the gradient in the parameter's OWN (Cout, Cin) shape, written compactly by the group's reduction: what
         # autograd receives is contiguous (a slice of the padded buffer is cloned by AccumulateGrad -- one more launch,
         # and with deferred launches a clone of a buffer that is not filled yet)
-        dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
-        scratch = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Kp, Cout_p, P),), device=dev, dtype=f32)
-        jobs.append((2.0 * Kp * Cout_p * P, (dN.data_ptr(), Y.data_ptr(), A[0], A[1], A[2], Xs.data_ptr(), sc, sh, Kp,
-                                             Cout_p, P, scratch.data_ptr(), dW.data_ptr(), Cout, Cin)))
+        dW = torch.empty((Wl.shape[0], Wl.shape[1]), device=dev, dtype=f32)
+        job, scratch = gemm.flat_wgrad_job(g, src, src.Y.shape[0], Cout_p, P, dW, out=(Wl.shape[0], Wl.shape[1]))
+        jobs.append(job)
         # everything the (possibly deferred) launch reads: the layer input and its BatchNorm constants belong to the
         # autograd node, which is released -- and its memory reused -- as soon as this backward returns
-        keep.extend((dN, Y, scratch, dW, coef, Xs, vecs[l - 1] if l > 0 else None))
+        keep.extend((g.dN, g.Y, scratch, dW, coef, src.Y, src.vec))
         return dW.view(Wl.shape)
+
+    def dgrad(l, g, Cout_p):
+        """(destination, launch) that takes layer l's gradient to its producer (l >= 1: the launch's `out` holds the
+        producer's partials) or to the stack's input (l == 0)"""
+        prev = acts[l - 1] if l > 0 else None
+        dst = torch.empty((prev.Y.shape[0] if l > 0 else K0p, P), device=dev, dtype=f32)
+        return dst, gemm.flat_dgrad("pw", g, Wts[l], dst.shape[0], Cout_p, P, dst, prev=prev, resid=None if l > 0 else resid)
 
     # ---- last layer: plain conv (+ bias, + residual)
     l = L - 1
     if needs[cfg.nsrc + 4 * l + 1]:
         db = torch.empty((Mp,), device=dev, dtype=f32)       # the bias gradient rides in the stack's grouped weight-gradient launch
-        jobs.append((0.0, (G.data_ptr(), None, None, None, None, None, None, None, 0, Mp, P, None, db.data_ptr(), 0, 0)))
+        jobs.append(gemm.row_sum_job(G, Mp, P, db))
         keep.extend((G, db))
         grads[4 * l + 1] = db[:Cl]
-    grads[4 * l] = wgrad(l, G, G, (one.data_ptr(), zero.data_ptr(), zero.data_ptr()), Mp)
-    dN, part = None, None
-    if L > 1:
-        Cp = Ys[l - 1].shape[0]
-        dN = torch.empty((Cp, P), device=dev, dtype=f32)
-        nparts = P // lib.o3d_pw_tile(P, Cp)
-        part = torch.empty((nparts, 2, Cp), device=dev, dtype=f32)
-        v = vecs[l - 1]
-        yield ("pw_conv_dgrad", 2.0 * Cp * Mp * P, "o3d_pw_dgrad", [G.data_ptr(), None, None, None, None, Wts[l].data_ptr(), Cp,
-                                                                   Mp, P, Ys[l - 1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(),
-                                                                   v[0].data_ptr(), None, dN.data_ptr(), part.data_ptr(), st],
-               (Cp, Mp, True))
-    elif want_x:
-        dX0 = torch.empty((K0p, P), device=dev, dtype=f32)
-        yield ("pw_conv_dgrad", 2.0 * K0p * Mp * P, "o3d_pw_dgrad", [G.data_ptr(), None, None, None, None, Wts[0].data_ptr(), K0p,
-                                                                    Mp, P, None, None, None, None,
-                                                                    G.data_ptr() if cfg.residual else None, dX0.data_ptr(), None,
-                                                                    st], (K0p, Mp, True))
-    # ---- hidden layers: conv -> BatchNorm -> ReLU
-    for l in range(L - 2, -1, -1):
-        Cp = Ys[l].shape[0]
-        v = vecs[l]
-        job, coef = bn_bwd_fin_job(part, [nparts], [float(P)], gammas[l], v[0], v[1])
-        yield ("bn_bwd_finalize", 0.0, "o3d_bn_bwd_finalize", job, None)
-        coef, A = bn_bwd_coef(coef, cfg.training)
-        grads[4 * l + 2], grads[4 * l + 3] = coef[0], coef[1]
-        grads[4 * l] = wgrad(l, dN, Ys[l], A, Cp, coef)
+    g = gemm.Grad.plain(G)
+    grads[4 * l] = wgrad(l, g, Mp)
+    # ---- then the hidden layers, conv -> BatchNorm -> ReLU, each behind the data gradient of the layer above it
+    for l in range(L - 1, -1, -1):
+        Cp = acts[l].Y.shape[0]
+        if l < L - 1:
+            act = acts[l]
+            job, coef = bn_bwd_fin_job(stats.part, stats.rows, [float(P)], gammas[l], act.mean, act.invstd)
+            yield ("bn_bwd_finalize", 0.0, "o3d_bn_bwd_finalize", job, None)
+            coef, A = bn_bwd_coef(coef, cfg.training)
+            grads[4 * l + 2], grads[4 * l + 3] = coef[0], coef[1]
+            g = gemm.Grad(dN, act.Y, A)
+            grads[4 * l] = wgrad(l, g, Cp, coef)
         if l > 0:
-            Cq = Ys[l - 1].shape[0]
-            dNp = torch.empty((Cq, P), device=dev, dtype=f32)
-            nparts_next = P // lib.o3d_pw_tile(P, Cq)
-            part_next = torch.empty((nparts_next, 2, Cq), device=dev, dtype=f32)
-            vp = vecs[l - 1]
-            yield ("pw_conv_dgrad", 2.0 * Cq * Cp * P, "o3d_pw_dgrad", [dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
-                                                                       Wts[l].data_ptr(), Cq, Cp, P, Ys[l - 1].data_ptr(),
-                                                                       vp[2].data_ptr(), vp[3].data_ptr(), vp[0].data_ptr(), None,
-                                                                       dNp.data_ptr(), part_next.data_ptr(), st], (Cq, Cp))
-            keep.append(dN)
-            dN, part, nparts = dNp, part_next, nparts_next
+            dN, la = dgrad(l, g, Cp)
+            yield la
+            stats = la.out
         elif want_x:
-            dX0 = torch.empty((K0p, P), device=dev, dtype=f32)
-            yield ("pw_conv_dgrad", 2.0 * K0p * Cp * P, "o3d_pw_dgrad", [dN.data_ptr(), Ys[0].data_ptr(), A[0], A[1], A[2],
-                                                                        Wts[0].data_ptr(), K0p, Cp, P, None, None, None, None,
-                                                                        G.data_ptr() if cfg.residual else None, dX0.data_ptr(),
-                                                                        None, st], (K0p, Cp))
+            dX0, la = dgrad(0, g, Cp)
+            yield la
     _submit_jobs(jobs, keep, st, list(Ws) + [b_ for b_ in state.biases if b_ is not None])
     del keep
     gsrc, off = [], 0
@@ -664,14 +613,12 @@ class SharedConvPair(torch.autograd.Function):
     @staticmethod
     @capi.on_tensor_device
     def forward(ctx, W, bias, xa, xb):
-        lib = capi.load()
         B, Cin, Na = xa.shape
         Nb = xb.shape[2]
         Cout = W.shape[0]
         Pa, Pb = B * Na, B * Nb
         P = Pa + Pb
         dev, f32 = xa.device, torch.float32
-        st = _stream()
         prep = prep_for(dev)
         X0 = torch.empty((Cin, P), device=dev, dtype=f32)
         pack_rows_into(xa.detach(), X0, 0)
@@ -679,23 +626,19 @@ class SharedConvPair(torch.autograd.Function):
         Wp = prep.get(W, Cout, Cin)
         bp = prep.get(bias, 1, Cout) if bias is not None else _const_vec(dev, Cout, 0.0)
         Y = torch.empty((Cout, P), device=dev, dtype=f32)
-        _call("pw_conv_fwd", 2.0 * Cin * Cout * P, lib.o3d_pw_fwd, X0.data_ptr(), Wp.data_ptr(), None, None, bp.data_ptr(), None,
-              Cin, Cout, P, Y.data_ptr(), None, None, st, dims=(Cin, Cout))
+        gemm.issue(gemm.flat_fwd("pw", gemm.Layer(X0), Wp, Cin, Cout, P, Y, bias=bp))
         if any(ctx.needs_input_grad):
             ctx.saved = (X0, prep.get(W, Cin, Cout, transpose=True), W, bias)
             ctx.geom = (B, Cin, Cout, Na, Nb)
-            ctx.versions = [(p_, p_._version) for p_ in (W, bias) if p_ is not None]
+            ctx.versions = _versions((W, bias))
         return Y[:, :Pa].view(Cout, B, Na).permute(1, 0, 2), Y[:, Pa:].view(Cout, B, Nb).permute(1, 0, 2)
 
     @staticmethod
     @capi.on_tensor_device
     def backward(ctx, da, db):
-        lib = capi.load()
         X0, Wt, W, bias = ctx.saved
         B, Cin, Cout, Na, Nb = ctx.geom
-        for p_, v in ctx.versions:
-            if p_._version != v:
-                raise RuntimeError("a parameter of a fused conv stack was modified in place between forward and backward")
+        _check_versions(ctx.versions, "fused conv stack")
         Pa, Pb = B * Na, B * Nb
         P = Pa + Pb
         dev, f32 = X0.device, torch.float32
@@ -707,22 +650,20 @@ class SharedConvPair(torch.autograd.Function):
             else:
                 pack_rows_into(d, G, col0)
         dxa = dxb = None
+        g = gemm.Grad.plain(G)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             dX = torch.empty((Cin, P), device=dev, dtype=f32)
-            _call("pw_conv_dgrad", 2.0 * Cin * Cout * P, lib.o3d_pw_dgrad, G.data_ptr(), None, None, None, None, Wt.data_ptr(), Cin,
-                  Cout, P, None, None, None, None, None, dX.data_ptr(), None, st, dims=(Cin, Cout, True))
+            gemm.issue(gemm.flat_dgrad("pw", g, Wt, Cin, Cout, P, dX))
             dxa = dX[:, :Pa].view(Cin, B, Na).permute(1, 0, 2) if ctx.needs_input_grad[2] else None
             dxb = dX[:, Pa:].view(Cin, B, Nb).permute(1, 0, 2) if ctx.needs_input_grad[3] else None
-        one, zero = _const_vec(dev, Cout, 1.0), _const_vec(dev, Cout, 0.0)
         dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
-        scratch = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Cin, Cout, P),), device=dev, dtype=f32)
-        jobs = [(2.0 * Cin * Cout * P, (G.data_ptr(), G.data_ptr(), one.data_ptr(), zero.data_ptr(), zero.data_ptr(),
-                                       X0.data_ptr(), None, None, Cin, Cout, P, scratch.data_ptr(), dW.data_ptr(), 0, 0))]
+        job, scratch = gemm.flat_wgrad_job(g, gemm.Layer(X0), Cin, Cout, P, dW)
+        jobs = [job]
         dbias = None
         if bias is not None and ctx.needs_input_grad[1]:
             dbias = torch.empty((Cout,), device=dev, dtype=f32)
-            jobs.append((0.0, (G.data_ptr(), None, None, None, None, None, None, None, 0, Cout, P, None, dbias.data_ptr(), 0, 0)))
-        _submit_jobs(jobs, [G, X0, scratch, dW, dbias, one, zero], st, [W, bias])
+            jobs.append(gemm.row_sum_job(G, Cout, P, dbias))
+        _submit_jobs(jobs, [G, X0, scratch, dW, dbias], st, [W, bias])
         # fresh views: autograd must hold the ONLY reference to what it is handed, or AccumulateGrad clones it -- with
         # deferred launches a clone of a buffer the flush has not filled yet (round-3 advisor finding on dbias)
         return dW.view(W.shape), dbias.view(Cout) if dbias is not None else None, dxa, dxb

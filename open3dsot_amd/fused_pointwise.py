@@ -10,8 +10,8 @@ gradient; it only shifts the running mean, which is updated accordingly.
 """
 import torch
 
-from . import capi
-from .fused import _call, _check_versions, _const_vec, _eval_consts, _ptr, _stream, _versions, bn_bwd_finalize, bn_finalize, \
+from . import capi, gemm
+from .fused import _call, _check_versions, _eval_consts, _ptr, _stream, _versions, bn_bwd_finalize, bn_finalize, \
     count_batches, POOL_BWD_SPLIT, TILE
 from .fused import bias_fix as _fused_bias_fix
 
@@ -21,12 +21,6 @@ class _Cfg:
 
 
 _POOLED_GMAX = {"on": True}      # test hook: the dense-gradient backward of a "gmax" stack (the path it replaced)
-
-
-def _flat_ok(rows, k, P):
-    """the flat-layout entry points of csrc/mlp_direct.hip (o3d_pw_fwd / o3d_pw_dgrad): they pick the wave tile -- and with it
-    the number of statistics partial rows, P // o3d_pw_tile(P, rows) -- from the size of the launch"""
-    return rows % 64 == 0 and k % 16 == 0 and P % 128 == 0
 
 
 def supported(x, layers):
@@ -56,59 +50,46 @@ class FusedPointwiseChain(torch.autograd.Function):
         # that buffer, no copy -- round 4 made it (B,C,N)-contiguous first and flat again here: two 25 MB copies per hand-over
         xp = x.detach().permute(1, 0, 2)
         X0 = (xp if xp.is_contiguous() else xp.contiguous()).view(Cin0, P)
-        ntiles = P // TILE
-        Ys, means, invstds, scales, shifts = [], [], [], [], []
+        acts = []            # gemm.Layer per layer: raw output + (mean, invstd, scale, shift)
         bias_fix = {}
         for l in range(L):
             Cout, Cin = Ws[l].shape
             bn = cfg.bns[l]
             Y = torch.empty((Cout, P), device=dev, dtype=f32)
-            flat = _flat_ok(Cout, Cin, P) and not (l == 0 and cbias is not None)
-            nrows = P // lib.o3d_pw_tile(P, Cout) if flat else ntiles
-            part = torch.empty((nrows, 2, Cout), device=dev, dtype=f32) if cfg.training else None
             stat_c = bn.running_mean if cfg.training else None
-            src = X0 if l == 0 else Ys[-1]
-            if flat:
-                _call("pw_conv_fwd", 2.0 * Cin * Cout * P, lib.o3d_pw_fwd, src.data_ptr(), Ws[l].data_ptr(),
-                      None if l == 0 else scales[-1].data_ptr(), None if l == 0 else shifts[-1].data_ptr(), None, None, Cin, Cout,
-                      P, Y.data_ptr(), _ptr(part), _ptr(stat_c), st, dims=(Cin, Cout))
-            elif l == 0 and cbias is not None:
-                cb = cbias.detach().contiguous()
-                _call("pw_conv_fwd", 2.0 * Cin * Cout * P, lib.o3d_pw_fwd_cloud, src.data_ptr(), Ws[0].data_ptr(), cb.data_ptr(),
-                      B, N, Cin, Cout, Y.data_ptr(), _ptr(part), _ptr(stat_c), st, dims=(Cin, Cout))
+            if l == 0 and cbias is not None:
+                stats = gemm.issue(gemm.flat_fwd_cloud(X0, Ws[0], cbias.detach().contiguous(), B, N, Cin, Cout, Y, stat_c))
             else:
-                _call("pw_conv_fwd", 2.0 * Cin * Cout * P, lib.o3d_mlp_conv_fwd, src.data_ptr(), Ws[l].data_ptr(),
-                      None if l == 0 else scales[-1].data_ptr(), None if l == 0 else shifts[-1].data_ptr(), 1, Cin, Cout, P,
-                      Y.data_ptr(), _ptr(part), _ptr(stat_c), st, dims=(Cin, Cout))
+                stats = gemm.issue(gemm.flat_fwd("pw", gemm.Layer(X0) if l == 0 else acts[-1], Ws[l], Cin, Cout, P, Y, stat_c))
             vec = torch.empty((4, Cout), device=dev, dtype=f32)
             b = biases[l].detach() if biases[l] is not None else None
             if cfg.training:
-                bn_finalize(lib, st, part, [nrows], [float(P)], bn, gammas[l], betas[l], vec, stat_c)
+                bn_finalize(lib, st, stats.part, stats.rows, [float(P)], bn, gammas[l], betas[l], vec, stat_c)
                 if b is not None:       # statistics were taken without the bias: mean(Y + b) = mean(Y) + b
                     bias_fix.setdefault(float(bn.momentum), ([], []))
                     bias_fix[float(bn.momentum)][0].append(bn.running_mean)
                     bias_fix[float(bn.momentum)][1].append(b)
             else:
                 _eval_consts(lib, bn, gammas[l], betas[l], vec, 1, st, conv_bias=b)
-            Ys.append(Y)
-            means.append(vec[0]); invstds.append(vec[1]); scales.append(vec[2]); shifts.append(vec[3])
+            acts.append(gemm.Layer(Y, vec))
         for mom, (rms, bs) in bias_fix.items():      # one multi-tensor launch per FORWARD inside a tracker scope, else per stack
             _fused_bias_fix(mom, rms, bs)
         if cfg.training:
             count_batches(cfg.bns, 1)
         Cl = Ws[-1].shape[0]
+        last = acts[-1]
         need_bwd = any(ctx.needs_input_grad)
         argq = yarg = None
         if cfg.mode == "act":
             act = torch.empty((Cl, P), device=dev, dtype=f32)
-            _call("pw_apply", 0.0, lib.o3d_bn_relu_apply, Ys[-1].data_ptr(), scales[-1].data_ptr(), shifts[-1].data_ptr(),
+            _call("pw_apply", 0.0, lib.o3d_bn_relu_apply, last.Y.data_ptr(), last.scale.data_ptr(), last.shift.data_ptr(),
                   Cl, P, act.data_ptr(), st)
             out = act.view(Cl, B, N).permute(1, 0, 2)
         else:
             out = torch.empty((B, Cl), device=dev, dtype=f32)
             argq = torch.empty((B, Cl), device=dev, dtype=torch.int32) if need_bwd else None
             yarg = torch.empty((B, Cl), device=dev, dtype=f32) if need_bwd else None
-            _call("pw_gmax", 0.0, lib.o3d_gmax_fwd, Ys[-1].data_ptr(), scales[-1].data_ptr(), shifts[-1].data_ptr(), B, Cl,
+            _call("pw_gmax", 0.0, lib.o3d_gmax_fwd, last.Y.data_ptr(), last.scale.data_ptr(), last.shift.data_ptr(), B, Cl,
                   N, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
         if need_bwd:
             # W^T of the inner layers for the data gradient: from the device's WeightPrep table (inside a tracker forward
@@ -127,8 +108,7 @@ class FusedPointwiseChain(torch.autograd.Function):
             ctx.dims = (B, N, L)
             ctx.has_bias = [b is not None for b in biases]
             ctx.has_cbias = cbias is not None
-            ctx.saved = (X0, Ws, gammas, Ys, means, invstds, scales, shifts, out.detach() if cfg.mode != "act" else None,
-                         argq, yarg)
+            ctx.saved = (X0, Ws, gammas, acts, out.detach() if cfg.mode != "act" else None, argq, yarg)
         return out
 
     @staticmethod
@@ -138,37 +118,35 @@ class FusedPointwiseChain(torch.autograd.Function):
         cfg = ctx.cfg
         _check_versions(ctx.versions, "FusedPointwiseChain")
         B, N, L = ctx.dims
-        X0, Ws, gammas, Ys, means, invstds, scales, shifts, out, argq, yarg = ctx.saved
+        X0, Ws, gammas, acts, out, argq, yarg = ctx.saved
+        last = acts[-1]
         P = B * N
         dev, f32 = dOut.device, torch.float32
         st = _stream()
-        ntiles = P // TILE
         Cl = Ws[-1].shape[0]
-        dN = torch.empty((Cl, P), device=dev, dtype=f32) if not (cfg.mode != "act" and L >= 2 and Cl % 64 == 0 and
-                                                                   Ws[-1].shape[1] % 64 == 0 and N % 128 == 0 and
-                                                                   _POOLED_GMAX["on"]) else None
+        pooled = cfg.mode != "act" and L >= 2 and Cl % 64 == 0 and Ws[-1].shape[1] % 64 == 0 and N % 128 == 0 and \
+            _POOLED_GMAX["on"]
+        dN = torch.empty((Cl, P), device=dev, dtype=f32) if not pooled else None
         pk = None
         if cfg.mode == "act":
             g = dOut.permute(1, 0, 2).reshape(Cl, P).contiguous()
-            part = torch.empty((ntiles, 2, Cl), device=dev, dtype=f32)
-            _call("pw_act_bwd", 0.0, lib.o3d_act_bwd_partials, g.data_ptr(), Ys[-1].data_ptr(), scales[-1].data_ptr(),
-                  shifts[-1].data_ptr(), means[-1].data_ptr(), Cl, P, dN.data_ptr(), part.data_ptr(), st)
-            nparts = ntiles
-        elif L >= 2 and Cl % 64 == 0 and Ws[-1].shape[1] % 64 == 0 and N % 128 == 0 and _POOLED_GMAX["on"]:
+            part = torch.empty((P // TILE, 2, Cl), device=dev, dtype=f32)
+            _call("pw_act_bwd", 0.0, lib.o3d_act_bwd_partials, g.data_ptr(), last.Y.data_ptr(), last.scale.data_ptr(),
+                  last.shift.data_ptr(), last.mean.data_ptr(), Cl, P, dN.data_ptr(), part.data_ptr(), st)
+        elif pooled:
             # the last layer's GEMMs build the one-hot gradient of the max on the fly (csrc/pointwise.hip::gmax_bwd_pk_kernel)
             dOut = dOut.contiguous()
             pk = torch.empty((Cl, B, 2), device=dev, dtype=f32)
             part = torch.empty((1, 2, Cl), device=dev, dtype=f32)
             _call("pool_bwd", 0.0, lib.o3d_gmax_bwd_pk, dOut.data_ptr(), out.data_ptr(), argq.data_ptr(), yarg.data_ptr(),
-                  means[-1].data_ptr(), B, Cl, N, pk.data_ptr(), part.data_ptr(), st)
-            nparts, dN = 1, None
+                  last.mean.data_ptr(), B, Cl, N, pk.data_ptr(), part.data_ptr(), st)
         else:
             dOut = dOut.contiguous()
             part = torch.empty((POOL_BWD_SPLIT, 2, Cl), device=dev, dtype=f32)
             meta = _meta_full(dev, P, B)       # every column is live: one "ball" of N columns per cloud
             _call("pool_bwd", 0.0, lib.o3d_pool_bwd_c, dOut.data_ptr(), out.data_ptr(), argq.data_ptr(), yarg.data_ptr(),
-                  means[-1].data_ptr(), B, Cl, 1, 0, meta.data_ptr(), 0, P, dN.data_ptr(), part.data_ptr(), st)
-            nparts = POOL_BWD_SPLIT
+                  last.mean.data_ptr(), B, Cl, 1, 0, meta.data_ptr(), 0, P, dN.data_ptr(), part.data_ptr(), st)
+        stats = gemm.Partials(part, [part.shape[0]], ())      # of the launch above: every row is live
         grads = [None] * (4 * L)
         dx = dcb = None
         zero_bias = None      # dL/db behind a training-mode BatchNorm is exactly zero: one fill for all layers of the stack
@@ -181,7 +159,10 @@ class FusedPointwiseChain(torch.autograd.Function):
                 o += w
         for l in range(L - 1, -1, -1):
             Cout, Cin = Ws[l].shape
-            coef, A = bn_bwd_finalize(lib, st, cfg.training, part, [nparts], [float(P)], gammas[l], means[l], invstds[l])
+            act = acts[l]
+            src = gemm.Layer(X0) if l == 0 else acts[l - 1]
+            coef, A = bn_bwd_finalize(lib, st, cfg.training, stats.part, stats.rows, [float(P)], gammas[l], act.mean, act.invstd)
+            g = gemm.Grad(dN, act.Y, A) if dN is not None else gemm.Grad.pooled(pk, N, act.Y, A)
             grads[4 * l + 2], grads[4 * l + 3] = coef[0], coef[1]
             if ctx.has_bias[l]:      # dL/db = sum dY: zero behind a training-mode BatchNorm, A1 * sum dN in eval mode
                 if cfg.training:
@@ -192,64 +173,30 @@ class FusedPointwiseChain(torch.autograd.Function):
             flops = 2.0 * Cin * Cout * P
             if l == 0 and ctx.has_cbias and ctx.needs_input_grad[1]:
                 dcb = torch.empty((Cout, B), device=dev, dtype=f32)       # gradient of the per-cloud bias
-                _call("cloud_sum", 0.0, lib.o3d_cloud_sum_dy, dN.data_ptr(), Ys[0].data_ptr(), A[0], A[1], A[2], Cout, B, N,
+                _call("cloud_sum", 0.0, lib.o3d_cloud_sum_dy, dN.data_ptr(), act.Y.data_ptr(), A[0], A[1], A[2], Cout, B, N,
                       dcb.data_ptr(), st)
             thin = l == 0 and Cout == 64 and Cin <= 16       # weight and input gradient in one pass (csrc/pointwise.hip)
             if thin:
                 wpart = torch.empty((lib.o3d_thin_bwd_scratch(),), device=dev, dtype=f32)
                 dX = torch.empty((Cin, B, N), device=dev, dtype=f32) if ctx.needs_input_grad[0] else None
-                _call("pw_conv_wgrad", flops * (2 if dX is not None else 1), lib.o3d_thin_bwd, dN.data_ptr(), Ys[0].data_ptr(), A[0],
+                _call("pw_conv_wgrad", flops * (2 if dX is not None else 1), lib.o3d_thin_bwd, dN.data_ptr(), act.Y.data_ptr(), A[0],
                       A[1], A[2], X0.data_ptr(), Ws[0].data_ptr(), Cin, Cout, P, wpart.data_ptr(), dW.data_ptr(), _ptr(dX), st,
                       dims=(Cin, Cout))
                 if dX is not None:
                     dx = dX.permute(1, 0, 2)
-            elif Cin % 64 == 0 and Cout % 64 == 0:
-                wpart = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Cin, Cout, P),), device=dev, dtype=f32)
-                xs = (X0.data_ptr(), None, None) if l == 0 else \
-                     (Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr())
-                _call("pw_conv_wgrad", flops, lib.o3d_mlp_conv_wgrad2, _ptr(dN), _ptr(pk) if dN is None else None,
-                      N if dN is None else 4, Ys[l].data_ptr(), A[0], A[1], A[2], xs[0], xs[1], xs[2], 1, Cin, Cout, P,
-                      wpart.data_ptr(), dW.data_ptr(), st, dims=(Cin, Cout))
             else:
-                tiles = ((Cin + 127) // 128) * ((Cout + 127) // 128)
-                nsl = max(1, min(P // 32 // 4, 768 // tiles))
-                wpart = torch.empty((nsl + 16, Cout, Cin), device=dev, dtype=f32)
-                xs = (X0.data_ptr(), None, None) if l == 0 else \
-                     (Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr())
-                _call("pw_conv_wgrad", flops, lib.o3d_mlp_conv_wgrad, dN.data_ptr(), None, None, None, 4, Ys[l].data_ptr(),
-                      A[0], A[1], A[2], xs[0], xs[1], xs[2], 1, Cin, Cout, P, nsl, wpart.data_ptr(), dW.data_ptr(), st,
-                      dims=(Cin, Cout))
+                gemm.issue(gemm.flat_wgrad("pw", g, src, Cin, Cout, P, dW))
             grads[4 * l] = dW.unsqueeze(-1)
             if l >= 1:
                 Wt = ctx.Wts[l] if ctx.Wts is not None else Ws[l].t().contiguous()
                 dNp = torch.empty((Cin, P), device=dev, dtype=f32)
-                if dN is None:           # pooled source: 128-column tiles, one ball of N columns per cloud
-                    nrows = ntiles
-                    part = torch.empty((ntiles, 2, Cin), device=dev, dtype=f32)
-                    _call("pw_conv_dgrad", flops, lib.o3d_mlp_conv_dgrad_wt, None, None, None, None, N,
-                          Ys[l].data_ptr(), A[0], A[1], A[2], Ws[l].data_ptr(), Wt.data_ptr(), pk.data_ptr(), 1, Cin, Cout, P,
-                          Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), means[l - 1].data_ptr(),
-                          dNp.data_ptr(), part.data_ptr(), st, dims=(Cin, Cout))
-                elif _flat_ok(Cin, Cout, P):
-                    nrows = P // lib.o3d_pw_tile(P, Cin)
-                    part = torch.empty((nrows, 2, Cin), device=dev, dtype=f32)
-                    _call("pw_conv_dgrad", flops, lib.o3d_pw_dgrad, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
-                          Wt.data_ptr(), Cin, Cout, P, Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(),
-                          means[l - 1].data_ptr(), None, dNp.data_ptr(), part.data_ptr(), st, dims=(Cin, Cout))
-                else:
-                    nrows = ntiles
-                    part = torch.empty((ntiles, 2, Cin), device=dev, dtype=f32)
-                    _call("pw_conv_dgrad", flops, lib.o3d_mlp_conv_dgrad_wt, dN.data_ptr(), None, None, None, 4,
-                          Ys[l].data_ptr(), A[0], A[1], A[2], Ws[l].data_ptr(), Wt.data_ptr(), None, 1, Cin, Cout, P,
-                          Ys[l - 1].data_ptr(), scales[l - 1].data_ptr(), shifts[l - 1].data_ptr(), means[l - 1].data_ptr(),
-                          dNp.data_ptr(), part.data_ptr(), st, dims=(Cin, Cout))
-                dN, nparts = dNp, nrows
+                stats = gemm.issue(gemm.flat_dgrad("pw", g, Wt, Cin, Cout, P, dNp, prev=src, W=Ws[l]))
+                dN = dNp
             elif ctx.needs_input_grad[0] and not thin:
                 dX = torch.empty((Cin, B, N), device=dev, dtype=f32)
                 # (the LDS-staged kernel: on 64 <- 512 x 98 304 columns it takes 0.113 ms, the direct 128-column tile 0.150 ms --
                 # 768 one-wave chains of 512 MFMAs -- and the split-K tile 0.183 ms; profiles/r04_ab_m2track_narrow_tiles.txt)
-                _call("pw_conv_dgrad", flops, lib.o3d_mlp_conv_dgrad_plain, dN.data_ptr(), Ys[0].data_ptr(), A[0], A[1],
-                      A[2], Ws[0].data_ptr(), 1, Cin, Cout, P, dX.data_ptr(), st, dims=(Cin, Cout))
+                gemm.issue(gemm.flat_dgrad("pw", g, None, Cin, Cout, P, dX, W=Ws[0], staged=True))
                 dx = dX.permute(1, 0, 2)
         return (dx, dcb, None, *grads)
 

@@ -12,8 +12,9 @@ arrives from the layer-0 backward kernel.
 """
 import torch
 
-from . import capi
-from .fused import _call, _const_vec, _eval_consts, _layers, _ptr, _stream, bn_bwd_finalize, bn_finalize, count_batches
+from . import capi, gemm
+from .fused import _call, _check_versions, _eval_consts, _layers, _ptr, _stream, _versions, bn_bwd_finalize, bn_finalize, \
+    count_batches
 from .fused_heads import _up, pack_rows, prep_for
 
 
@@ -71,33 +72,28 @@ class FusedP2BXCorr(torch.autograd.Function):
         X0 = pack_rows([zero1, t_xyz.detach().transpose(1, 2), t_feat.detach()], K0p)
         W0p = prep.get(params[0], C0, K0p)
         Z = torch.empty((C0, Pm), device=dev, dtype=f32)
-        _call("conv_fwd_points", 2.0 * K0p * C0 * Pm, lib.o3d_pw_fwd, X0.data_ptr(), W0p.data_ptr(), None, None, None, None,
-              K0p, C0, Pm, Z.data_ptr(), None, None, st)
-        Ys, vecs, Wts = [], [], []
-        tile = lib.o3d_pw_tile(P, 256)          # the xcorr stage has far more than 65536 columns: 128, whatever the rows
+        gemm.issue(gemm.flat_fwd("points", gemm.Layer(X0), W0p, K0p, C0, Pm, Z, row=False))
+        acts, Wts = [], []
         for l in range(L):
             Cout, Cin = Ws[l].shape
             bn = cfg.bns[l]
             Y = torch.empty((Cout, P), device=dev, dtype=f32)
-            nparts = P // 256 if l == 0 else P // tile
-            part = torch.empty((nparts, 2, Cout), device=dev, dtype=f32) if cfg.training else None
             statc = bn.running_mean if cfg.training else None
-            if l == 0:
+            if l == 0:       # its statistics partials come from the expand kernel: one row per 256 columns
+                part = torch.empty((P // 256, 2, Cout), device=dev, dtype=f32) if cfg.training else None
+                stats = gemm.Partials(part, [P // 256], ())
                 _call("xcorr_expand", 0.0, lib.o3d_xcorr_expand, Z.data_ptr(), Pm, simf.data_ptr(), Ws[0].data_ptr(), K0, B, M, N,
                       C0, Y.data_ptr(), _ptr(part), _ptr(statc), st)
             else:
-                _call("conv_fwd", 2.0 * Cin * Cout * P, lib.o3d_pw_fwd, Ys[-1].data_ptr(), Ws[l].data_ptr(),
-                      vecs[-1][2].data_ptr(), vecs[-1][3].data_ptr(), None, None, Cin, Cout, P, Y.data_ptr(), _ptr(part),
-                      _ptr(statc), st, dims=(Cin, Cout))
+                stats = gemm.issue(gemm.flat_fwd("grouped", acts[-1], Ws[l], Cin, Cout, P, Y, statc))
                 if need_bwd:
                     Wts.append(prep.get(params[3 * l], Cin, Cout, transpose=True))
             vec = torch.empty((4, Cout), device=dev, dtype=f32)
             if cfg.training:
-                bn_finalize(lib, st, part, [nparts], [float(P)], bn, gammas[l], betas[l], vec, statc)
+                bn_finalize(lib, st, stats.part, stats.rows, [float(P)], bn, gammas[l], betas[l], vec, statc)
             else:
                 _eval_consts(lib, bn, gammas[l], betas[l], vec, 1, st)
-            Ys.append(Y)
-            vecs.append(vec)
+            acts.append(gemm.Layer(Y, vec))
         if cfg.training:
             count_batches(cfg.bns, 1)
         Cl = Ws[-1].shape[0]
@@ -107,14 +103,14 @@ class FusedP2BXCorr(torch.autograd.Function):
         out = torch.empty((Cl, B * N), device=dev, dtype=f32)
         argq = torch.empty((Cl, B * N), device=dev, dtype=torch.int32) if need_bwd else None
         yarg = torch.empty((Cl, B * N), device=dev, dtype=f32) if need_bwd else None
-        _call("pool_fwd", 0.0, lib.o3d_bn_relu_maxpool_fwd, Ys[-1].data_ptr(), vecs[-1][2].data_ptr(), vecs[-1][3].data_ptr(),
+        _call("pool_fwd", 0.0, lib.o3d_bn_relu_maxpool_fwd, acts[-1].Y.data_ptr(), acts[-1].scale.data_ptr(), acts[-1].shift.data_ptr(),
               1, Cl, B * N, M, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
         if need_bwd:
             ctx.cfg = cfg
-            ctx.geom = (B, N, M, f, K0, K0p, tile)
-            ctx.versions = [(p, p._version) for p in params]
+            ctx.geom = (B, N, M, f, K0, K0p)
+            ctx.versions = _versions(params)
             W0t = prep.get(params[0], K0p, C0, transpose=True)
-            ctx.saved = (X0, simf, Ys, vecs, Ws, Wts, W0t, gammas, out.detach(), argq, yarg)
+            ctx.saved = (X0, simf, acts, Ws, Wts, W0t, gammas, out.detach(), argq, yarg)
         return out.view(Cl, B, N).permute(1, 0, 2)
 
     @staticmethod
@@ -122,11 +118,9 @@ class FusedP2BXCorr(torch.autograd.Function):
     def backward(ctx, dOut):
         lib = capi.load()
         cfg = ctx.cfg
-        B, N, M, f, K0, K0p, tile = ctx.geom
-        for p, v in ctx.versions:
-            if p._version != v:
-                raise RuntimeError("a parameter of the fused xcorr MLP was modified in place between forward and backward")
-        X0, simf, Ys, vecs, Ws, Wts, W0t, gammas, out, argq, yarg = ctx.saved
+        B, N, M, f, K0, K0p = ctx.geom
+        _check_versions(ctx.versions, "FusedP2BXCorr")
+        X0, simf, acts, Ws, Wts, W0t, gammas, out, argq, yarg = ctx.saved
         L = len(Ws)
         P, Pm = B * N * M, B * M
         dev, f32 = dOut.device, torch.float32
@@ -138,29 +132,27 @@ class FusedP2BXCorr(torch.autograd.Function):
         # layer's data / weight gradient kernels read the packed {masked gradient, arg-max slot} pairs
         nparts = 8
         part = torch.empty((nparts, 2, Cl), device=dev, dtype=f32)
+        stats = gemm.Partials(part, [nparts], ())
         pk = torch.empty((Cl, B * N, 2), device=dev, dtype=f32)
         _call("pool_bwd", 0.0, lib.o3d_pool_bwd_partials_split, g.data_ptr(), out.data_ptr(), yarg.data_ptr(),
-              vecs[-1][0].data_ptr(), Cl, B * N, nparts, part.data_ptr(), argq.data_ptr(), pk.data_ptr(), st)
+              acts[-1].mean.data_ptr(), Cl, B * N, nparts, part.data_ptr(), argq.data_ptr(), pk.data_ptr(), st)
         dN = None
         grads = [None] * (3 * L)
         dsim = dxyz = dfeat = None
         for l in range(L - 1, -1, -1):
             Cout, Cin = Ws[l].shape
-            coef, A = bn_bwd_finalize(lib, st, cfg.training, part, [nparts], [float(P)], gammas[l], vecs[l][0], vecs[l][1])
+            act = acts[l]
+            coef, A = bn_bwd_finalize(lib, st, cfg.training, stats.part, stats.rows, [float(P)], gammas[l], act.mean, act.invstd)
             grads[3 * l + 1], grads[3 * l + 2] = coef[0], coef[1]
             if l == 0:
                 S = torch.empty((Cout, Pm), device=dev, dtype=f32)
                 ng = lib.o3d_xcorr_reduce_groups(Cout)
                 dsp = torch.empty((ng, P), device=dev, dtype=f32)
                 dwp = torch.empty((B, Cout), device=dev, dtype=f32)
-                _call("xcorr_reduce", 0.0, lib.o3d_xcorr_reduce, dN.data_ptr(), Ys[0].data_ptr(), A[0], A[1], A[2],
+                _call("xcorr_reduce", 0.0, lib.o3d_xcorr_reduce, dN.data_ptr(), act.Y.data_ptr(), A[0], A[1], A[2],
                       simf.data_ptr(), Ws[0].data_ptr(), K0, B, M, N, Cout, S.data_ptr(), Pm, dsp.data_ptr(), dwp.data_ptr(), st)
-                one, zero = _const_vec(dev, Cout, 1.0), _const_vec(dev, Cout, 0.0)
                 dWm = torch.empty((Cout, K0p), device=dev, dtype=f32)
-                scratch = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, K0p, Cout, Pm),), device=dev, dtype=f32)
-                _call("conv_wgrad_points", 2.0 * K0p * Cout * Pm, lib.o3d_mlp_conv_wgrad2, S.data_ptr(), None, 4, S.data_ptr(),
-                      one.data_ptr(), zero.data_ptr(), zero.data_ptr(), X0.data_ptr(), None, None, 1, K0p, Cout, Pm,
-                      scratch.data_ptr(), dWm.data_ptr(), st)
+                gemm.issue(gemm.flat_wgrad("points", gemm.Grad.plain(S), gemm.Layer(X0), K0p, Cout, Pm, dWm, row=False))
                 dW0 = dWm[:, :K0].clone()
                 dW0[:, 0] = dwp.sum(0)                     # the similarity channel's weight (its X0 row is zero)
                 grads[0] = dW0
@@ -168,35 +160,19 @@ class FusedP2BXCorr(torch.autograd.Function):
                     dsim = dsp.sum(0).view(B, N, M)
                 if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
                     dX0 = torch.empty((K0p, Pm), device=dev, dtype=f32)
-                    _call("conv_dgrad_points", 2.0 * K0p * Cout * Pm, lib.o3d_pw_dgrad, S.data_ptr(), None, None, None, None,
-                          W0t.data_ptr(), K0p, Cout, Pm, None, None, None, None, None, dX0.data_ptr(), None, st)
+                    gemm.issue(gemm.flat_dgrad("points", gemm.Grad.plain(S), W0t, K0p, Cout, Pm, dX0, row=False))
                     if ctx.needs_input_grad[2]:
                         dxyz = dX0[1:4].view(3, B, M).permute(1, 2, 0)
                     if ctx.needs_input_grad[3]:
                         dfeat = dX0[4:4 + f].view(f, B, M).permute(1, 0, 2)
                 continue
-            dW = torch.empty((Cout, Cin), device=dev, dtype=f32)
-            scratch = torch.empty((lib.o3d_mlp_conv_wgrad2_scratch(1, Cin, Cout, P),), device=dev, dtype=f32)
-            _call("conv_wgrad", 2.0 * Cin * Cout * P, lib.o3d_mlp_conv_wgrad2, _ptr(dN), pk.data_ptr() if dN is None else None,
-                  M if dN is None else 4, Ys[l].data_ptr(), A[0], A[1], A[2], Ys[l - 1].data_ptr(), vecs[l - 1][2].data_ptr(),
-                  vecs[l - 1][3].data_ptr(), 1, Cin, Cout, P, scratch.data_ptr(), dW.data_ptr(), st,
-                  dims=(Cin, Cout, dN is None))
-            grads[3 * l] = dW
+            # the pooled layer reads the packed pairs (and, in the entry that still takes them, the pool's own tensors)
+            gs = gemm.Grad(dN, act.Y, A) if dN is not None else \
+                gemm.Grad.pooled(pk, M, act.Y, A, unpacked=(g, out, argq), light=True)
+            dW = grads[3 * l] = torch.empty((Cout, Cin), device=dev, dtype=f32)
+            gemm.issue(gemm.flat_wgrad("grouped", gs, acts[l - 1], Cin, Cout, P, dW))
             dNp = torch.empty((Cin, P), device=dev, dtype=f32)
-            vp = vecs[l - 1]
-            if dN is None:         # pooled source: 128-column tiles (one statistics partial row each)
-                part = torch.empty((P // 128, 2, Cin), device=dev, dtype=f32)
-                _call("conv_dgrad", 2.0 * Cin * Cout * P, lib.o3d_mlp_conv_dgrad_wt, None, g.data_ptr(), out.data_ptr(),
-                      argq.data_ptr(), M, Ys[l].data_ptr(), A[0], A[1], A[2], Ws[l].data_ptr(), Wts[l - 1].data_ptr(),
-                      pk.data_ptr(), 1, Cin, Cout, P, Ys[l - 1].data_ptr(), vp[2].data_ptr(), vp[3].data_ptr(), vp[0].data_ptr(),
-                      dNp.data_ptr(), part.data_ptr(), st, dims=(Cin, Cout, True))
-                nparts = P // 128
-            else:
-                part = torch.empty((P // tile, 2, Cin), device=dev, dtype=f32)
-                _call("conv_dgrad", 2.0 * Cin * Cout * P, lib.o3d_pw_dgrad, dN.data_ptr(), Ys[l].data_ptr(), A[0], A[1], A[2],
-                      Wts[l - 1].data_ptr(), Cin, Cout, P, Ys[l - 1].data_ptr(), vp[2].data_ptr(), vp[3].data_ptr(),
-                      vp[0].data_ptr(), None, dNp.data_ptr(), part.data_ptr(), st, dims=(Cin, Cout))
-                nparts = P // tile
+            stats = gemm.issue(gemm.flat_dgrad("grouped", gs, Wts[l - 1], Cin, Cout, P, dNp, prev=acts[l - 1], W=Ws[l]))
             dN = dNp
         gw = []
         for l in range(L):
