@@ -941,6 +941,39 @@ int o3d_track_score(const float* a, const float* b, const int32_t* valid, int n,
                     float* distances, const float* thr_s, int ns, const float* thr_p, int np, int64_t* cnt_s, int64_t* cnt_p,
                     int64_t* total, void* stream);
 
+/* ---- the preload crop of a dataset reader (csrc/preload.hip; open3dsot_amd/datasets.py is the caller) ----------------------
+ * What kittiDataset._get_frame_from_anno does per annotated object per frame -- PointCloud.transform in camera mode, then
+ * crop_pc_axis_aligned(pc, box, offset=preload_offset) -- for a chunk of raw frames in HBM: three launches and one read-back.
+ * raw (raw_rows,4) float32 on the device, 16-byte aligned: x y z intensity as in the .bin files (the intensity is ignored).
+ * frames (F,6) int32: first raw row, n, first box, number of boxes, workgroup start, scratch base.  The boxes of record f are
+ * [first box, first box + number): the records partition [0, B) in order; two records may name the same raw rows.  `frames` is
+ * the planned HOST table (checked again in every call, its plan included), frames_dev its copy on the device, which the
+ * launches read.  bounds (B,6) float32 on the device: lo x y z, hi x y z, the fp64 bounds of the reference rounded
+ * directionally (lo down, hi up), which makes the fp32 compares lo < p < hi exactly the reference's float32-against-double
+ * compares; -inf / +inf keep every finite point.  transform: 12 doubles on the HOST, the upper 3x4 of velo_to_cam row-major,
+ * passed by value | NULL (velodyne mode): p' = float(((T_i0*x + T_i1*y) + T_i2*z) + T_i3) is tested and written.
+ * o3d_preload_scratch (host only, no HIP call): the caller sets columns 0, 1 and 3 of `frames`; columns 2, 4 and 5 are filled
+ * in place; grid[0] = the workgroups of the count / scatter launches, grid[1] = B (grid may be NULL).  -> the scratch length in
+ * int32, -1 for a bad table.
+ * o3d_preload_count: the count and the scan launch -> counts (B) int32 on the device, the survivors of every box.
+ * o3d_preload_scatter must follow o3d_preload_count on the same scratch with the same tables: survivor number pos of box b, in
+ * the order of the frame, goes to pool (pool_rows,3) row out_row[b] + pos (out_row (B) int64 on the device); a row < 0 or >=
+ * pool_rows is not written.
+ * O3D_EINVAL, before any HIP call: F outside 0..O3D_PRELOAD_MAX_FRAMES, raw_rows outside 0..O3D_PRELOAD_MAX_ROWS, a record with
+ * a negative field, rows past raw_rows, more than O3D_PRELOAD_MAX_BOXES boxes or a plan other than o3d_preload_scratch's, boxes
+ * that do not sum to B, a scratch beyond 2^31 - 1 words or shorter than planned, a NULL or misaligned operand that a launch
+ * would read or write.  F = 0, B = 0, a frame of n = 0 and a record without boxes succeed; the first two launch nothing. */
+#define O3D_PRELOAD_MAX_FRAMES 4096
+#define O3D_PRELOAD_MAX_BOXES 1024
+#define O3D_PRELOAD_MAX_ROWS 536870911
+long o3d_preload_scratch(int32_t* frames, int F, long raw_rows, int* grid);
+int o3d_preload_count(const float* raw, long raw_rows, const int32_t* frames, const int32_t* frames_dev, int F,
+                      const float* bounds, int B, const double* transform, int32_t* scratch, long scratch_len, int32_t* counts,
+                      void* stream);
+int o3d_preload_scatter(const float* raw, long raw_rows, const int32_t* frames, const int32_t* frames_dev, int F,
+                        const float* bounds, int B, const double* transform, int32_t* scratch, long scratch_len,
+                        const long* out_row, float* pool, long pool_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

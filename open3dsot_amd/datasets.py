@@ -1,0 +1,372 @@
+"""Dataset readers that leave the frames in HBM: the KITTI tracking set as a sampler.DeviceTracklets.
+
+KittiTracklets mirrors the reference's kittiDataset (datasets/kitti.py) with coordinate_mode `velodyne` / `camera` and
+preload_offset: the same scene list per split string, the same tracklet list (order of first appearance of track_id in the
+category-filtered label file, frames sorted by frame number, gaps kept), the same boxes (fp64 on the host, cast to float32
+only when packed as [centre | wlh | rotation row-major]) and the same preload crop per annotated object per frame
+(crop_pc_axis_aligned with offset = preload_offset), bit for bit -- but the crop runs on the device (csrc/preload.hip):
+
+    host     parse label_02/<scene>.txt and calib/<scene>.txt, compute boxes and crop bounds in fp64 (plain Python + numpy)
+    host     read each distinct (scene, frame) .bin ONCE into a pinned buffer, up to chunk_frames frames per chunk
+    upload   one copy per chunk (x y z intensity as they lie in the file), one small copy for the tables
+    device   o3d_preload_count (2 launches), the counts read back (the chunk's one synchronisation), o3d_preload_scatter
+    result   every tracklet frame is a contiguous (count,3) view of ONE pool tensor: no per-frame allocation, no copy
+
+Quirks of the reference that are kept: a velodyne file that is missing (or whose length is no multiple of four floats) gives
+the single point (0,0,0), untransformed and uncropped (its bare `except`); an existing empty file gives a (0,3) frame; a box
+that keeps no point gives a (0,3) frame; the strict compares `mini < p < maxi` of the float32 coordinate against the fp64
+bound; in camera mode the transformed coordinate is rounded to float32 before the compare; a calibration line whose values
+do not reshape to 3x4 is skipped.  With preload_offset <= 0 the reference does not crop and all tracklets of a frame share
+one cloud object; here they share one slice of the pool.
+
+save(file) / KittiTracklets.load(file) stand in for the reference's pickle cache: one file with the pool, the row offsets,
+the boxes and the meta; loading is one upload.  There is no CPU fallback: a CPU device raises.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import points_utils as PU
+from .sampler import DeviceTracklet, DeviceTracklets
+
+_NAMED = ("Car", "Van", "Truck", "Pedestrian", "Person_sitting", "Cyclist", "Tram", "Misc")
+_ALL = ("Car", "Van", "Pedestrian", "Cyclist")
+
+
+def kitti_scene_list(split):
+    """kittiDataset._build_scene_list: substring tests on the upper-cased split, in this order"""
+    s = split.upper()
+    if "TRAIN" in s:
+        scenes = [0] if "TINY" in s else range(0, 17)
+    elif "VALID" in s:
+        scenes = [18] if "TINY" in s else range(17, 19)
+    elif "TEST" in s:
+        scenes = [19] if "TINY" in s else range(19, 21)
+    else:
+        scenes = range(21)
+    return ["%04d" % i for i in scenes]
+
+
+def read_kitti_calib(path):
+    """_read_calib_file: name -> (3,4) float64; a line whose values are no floats or do not reshape to 3x4 is skipped"""
+    data = {}
+    with open(path) as f:
+        for line in f:
+            values = line.split()
+            if not values:
+                continue
+            try:
+                data[values[0]] = np.array([float(x) for x in values[1:]], np.float64).reshape(3, 4)
+            except ValueError:
+                pass
+    return data
+
+
+def _keep_type(category_name):
+    if category_name in _NAMED:
+        return lambda t: t == category_name
+    if category_name == "All":
+        return lambda t: t in _ALL
+    return lambda t: t != "DontCare"
+
+
+def _quat(axis, angle):
+    """the unit quaternion (w, x, y, z) of a rotation by `angle` radians about `axis`"""
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    return np.concatenate([[np.cos(angle / 2)], np.sin(angle / 2) * a])
+
+
+def _quat_mul(a, b):
+    """the Hamilton product a b"""
+    return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
+                     a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                     a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1],
+                     a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
+
+
+def _quat_matrix(q):
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def kitti_box(anno, velo_to_cam, coordinate_mode):
+    """The box of _get_frame_from_anno in fp64 -> (15,) [centre | wlh | rotation row-major].  anno: height, width, length, x,
+    y, z, rotation_y; velo_to_cam (4,4).  The rotation is composed as the reference composes it, as a product of two
+    axis-angle quaternions: about (0,0,-1) by rotation_y then by 90 degrees (velodyne), about y by rotation_y then about x by
+    pi/2 (camera)"""
+    h, w, l, x, y, z, ry = anno
+    if coordinate_mode == "velodyne":
+        centre = np.dot(np.linalg.inv(velo_to_cam), np.array([x, y - h / 2, z, 1.0]))[:3]
+        rot = _quat_matrix(_quat_mul(_quat([0, 0, -1], ry), _quat([0, 0, -1], 90 * np.pi / 180.0)))
+    else:
+        centre = np.array([x, y - h / 2, z])
+        rot = _quat_matrix(_quat_mul(_quat([0, 1, 0], ry), _quat([1, 0, 0], np.pi / 2)))
+    return np.concatenate([centre, [w, l, h], rot.reshape(-1)]).astype(np.float64)
+
+
+def kitti_annotations(path, split, category_name="Car", coordinate_mode="velodyne"):
+    """The host half of the reader (no device): -> a list of tracklets, each a dict with scene, track_id, frames (T,) int64,
+    boxes (T,15) float64, in the reference's order; and {scene: velo_to_cam (4,4)}."""
+    if coordinate_mode not in ("velodyne", "camera"):
+        raise ValueError("coordinate_mode must be 'velodyne' or 'camera'")
+    keep = _keep_type(category_name)
+    tracklets, calibs = [], {}
+    for scene in kitti_scene_list(split):
+        rows = {}                                 # track_id -> [(frame, anno)], in order of first appearance (dicts keep it)
+        with open(os.path.join(path, "label_02", scene + ".txt")) as f:
+            for line in f:
+                v = line.split()
+                if not v:
+                    continue
+                if len(v) != 17:
+                    raise ValueError("%s/label_02/%s.txt: a line of %d fields, not 17" % (path, scene, len(v)))
+                if keep(v[2]):
+                    rows.setdefault(int(v[1]), []).append((int(v[0]), tuple(float(x) for x in v[10:17])))
+        if not rows:
+            continue
+        calib = read_kitti_calib(os.path.join(path, "calib", scene + ".txt"))
+        velo_to_cam = calibs[scene] = np.vstack((calib["Tr_velo_cam"], np.array([0.0, 0.0, 0.0, 1.0])))
+        for track_id, annos in rows.items():
+            annos.sort(key=lambda a: a[0])
+            tracklets.append({"scene": scene, "track_id": track_id, "frames": np.array([a[0] for a in annos], np.int64),
+                              "boxes": np.stack([kitti_box(a[1], velo_to_cam, coordinate_mode) for a in annos])})
+    return tracklets, calibs
+
+
+def round_up_f32(m):
+    """the smallest float32 >= m, elementwise, for fp64 m"""
+    m = np.asarray(m, np.float64)
+    with np.errstate(over="ignore"):
+        f = m.astype(np.float32)
+        return np.where(f.astype(np.float64) < m, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+
+
+def round_down_f32(m):
+    """the largest float32 <= m, elementwise, for fp64 m"""
+    m = np.asarray(m, np.float64)
+    with np.errstate(over="ignore"):
+        f = m.astype(np.float32)
+        return np.where(f.astype(np.float64) > m, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+_SIGNS = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
+
+
+def preload_bounds(boxes, offset):
+    """boxes (B,15) fp64 -> (B,6) float32 [lo xyz | hi xyz]: min / max over the corners of Box.corners -+ offset in fp64, lo
+    rounded down and hi rounded up to float32; offset <= 0: -inf / +inf (the reference does not crop)"""
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 15)
+    out = np.empty((boxes.shape[0], 6), np.float32)
+    if offset <= 0:
+        out[:, :3], out[:, 3:] = -np.inf, np.inf
+        return out
+    for b, box in enumerate(boxes):
+        w, l, h = box[3:6]
+        corners = np.dot(box[6:15].reshape(3, 3), _SIGNS * (np.array([l, w, h]) / 2)[:, None]) + box[0:3, None]
+        out[b, :3] = round_down_f32(corners.min(1) - offset)
+        out[b, 3:] = round_up_f32(corners.max(1) + offset)
+    return out
+
+
+def _device(device):
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise RuntimeError("KittiTracklets: CPU not supported (the frames live on a GPU)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def velodyne_rows(path):
+    """rows of a velodyne .bin as the reference reads it (np.fromfile(float32).reshape(-1, 4)); -1: missing or unreadable as
+    (n,4), which the reference turns into the single point (0,0,0)"""
+    try:
+        floats = os.path.getsize(path) // 4
+    except OSError:
+        return -1
+    return floats // 4 if floats % 4 == 0 else -1
+
+
+class PreloadChunk:
+    """The device half for one chunk of raw frames: plan, upload, count, read back, scatter.  files: [(path, n rows)],
+    boxes_per_file: for each file a (k,6) float32 array of bounds (k >= 0).  The steps are separate methods so that
+    tools/preload_bench.py can time them; run() is the sequence the reader uses."""
+
+    def __init__(self, files, bounds_per_file, transform, device, pinned=None):
+        self.device, self.transform = device, transform
+        recs, row = [], 0
+        for (_, n), b in zip(files, bounds_per_file):
+            for k0 in range(0, len(b), PU.PRELOAD_MAX_BOXES):       # a frame with more boxes than a record takes: more records
+                recs.append((row, n, 0, min(PU.PRELOAD_MAX_BOXES, len(b) - k0), 0, 0))
+            row += n
+        self.files, self.raw_rows = files, row
+        self.frames = np.array(recs, np.int32).reshape(-1, PU.PRELOAD_COLS)
+        self.need, self.wgs, self.B = PU.preload_plan(self.frames, row)
+        self.bounds = np.concatenate([np.asarray(b, np.float32).reshape(-1, 6) for b in bounds_per_file] + [np.zeros((0, 6), np.float32)])
+        assert self.bounds.shape[0] == self.B
+        if pinned is None or pinned.shape[0] < row:
+            pinned = torch.empty((max(row, 1), 4), dtype=torch.float32).pin_memory()
+        self.pinned = pinned
+
+    def read(self):
+        host, row = self.pinned.numpy(), 0
+        for path, n in self.files:
+            if n > 0:
+                with open(path, "rb") as f:
+                    got = f.readinto(host[row:row + n])
+                if got != 16 * n:
+                    raise OSError("%s changed while it was read" % path)
+            row += n
+
+    def upload(self):
+        dev = self.device
+        self.raw = self.pinned[:self.raw_rows].to(dev, non_blocking=True)
+        tables = np.concatenate([self.frames.reshape(-1).view(np.uint8), self.bounds.reshape(-1).view(np.uint8)])
+        t = torch.from_numpy(tables).to(dev)
+        nf = self.frames.size * 4
+        self.dev_frames, self.dev_bounds = t[:nf].view(torch.int32), t[nf:].view(torch.float32)
+        self.scratch = torch.empty((self.need,), dtype=torch.int32, device=dev)
+        self.counts = torch.empty((self.B,), dtype=torch.int32, device=dev)
+
+    def count(self):
+        PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.counts)
+
+    def read_back(self):
+        """-> counts (B,) int64 on the host; allocates the chunk's pool segment and uploads every box's first row"""
+        counts = self.counts.cpu().numpy().astype(np.int64)
+        self.first = np.concatenate([[0], np.cumsum(counts)])
+        self.pool = torch.empty((int(self.first[-1]), 3), dtype=torch.float32, device=self.device)
+        self.out_row = torch.from_numpy(self.first[:-1].copy()).to(self.device)
+        return counts
+
+    def scatter(self):
+        PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.out_row, self.pool)
+
+    def run(self):
+        self.read()
+        self.upload()
+        self.count()
+        counts = self.read_back()
+        self.scatter()
+        return counts
+
+
+class KittiTracklets(DeviceTracklets):
+    """KittiTracklets(path, split, ...): the tracklets of the KITTI tracking set under `path` (velodyne/, label_02/, calib/),
+    cropped as the reference preloads them, resident in HBM.  A sampler.DeviceTracklets: goes unchanged into tracking.evaluate
+    and DeviceBatchSampler.  meta[k] = (scene, track_id, frame numbers); pool = the one (rows,3) tensor all frames view;
+    rows[k] = (T,2) int64 [first pool row, count] of tracklet k's frames."""
+
+    def __init__(self, path, split, category_name="Car", coordinate_mode="velodyne", preload_offset=-1, device=None, chunk_frames=64):
+        super().__init__()
+        dev = _device(device)
+        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
+            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        self.path, self.split, self.category_name = path, split, category_name
+        self.coordinate_mode, self.preload_offset = coordinate_mode, preload_offset
+        annos, calibs = kitti_annotations(path, split, category_name, coordinate_mode)
+        self.scene_list = kitti_scene_list(split)
+        # every distinct (scene, frame) once, in order of first use, with the tracklet frames that crop it
+        users, missing = {}, []
+        for k, a in enumerate(annos):
+            for t, frame in enumerate(a["frames"]):
+                users.setdefault((a["scene"], int(frame)), []).append((k, t))
+        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
+        shared = preload_offset <= 0              # no crop: the tracklets of a frame share one slice, as they share one cloud
+        todo = []                                 # (file, n, bounds (k,6), [[(tracklet, frame index)] per box])
+        for (scene, frame), who in users.items():
+            file = os.path.join(path, "velodyne", scene, "%06d.bin" % frame)
+            n = velodyne_rows(file)
+            if n < 0:
+                missing += who
+            elif shared:
+                todo.append((scene, file, n, preload_bounds(np.zeros((1, 15)), preload_offset), [who]))
+            else:
+                todo.append((scene, file, n, preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in who]), preload_offset),
+                             [[u] for u in who]))
+        segments, base, pinned, i = [], 0, None, 0
+        with torch.cuda.device(dev):
+            while i < len(todo):
+                # a chunk: frames of one scene (one transform), at most chunk_frames of them and PRELOAD_MAX_ROWS raw rows
+                j, nrows, nrec = i, 0, 0
+                while j < len(todo) and j - i < chunk_frames and todo[j][0] == todo[i][0]:
+                    rec = max(1, -(-len(todo[j][3]) // PU.PRELOAD_MAX_BOXES))
+                    if j > i and (nrows + todo[j][2] > PU.PRELOAD_MAX_ROWS or nrec + rec > PU.PRELOAD_MAX_FRAMES):
+                        break
+                    nrows, nrec, j = nrows + todo[j][2], nrec + rec, j + 1
+                transform = np.ascontiguousarray(calibs[todo[i][0]][:3]) if coordinate_mode == "camera" else None
+                chunk = PreloadChunk([(t[1], t[2]) for t in todo[i:j]], [t[3] for t in todo[i:j]], transform, dev, pinned)
+                counts = chunk.run()
+                pinned, b = chunk.pinned, 0
+                for t in todo[i:j]:
+                    for who in t[4]:
+                        for k, f in who:
+                            rows[k][f] = (base + chunk.first[b], counts[b])
+                        b += 1
+                segments.append(chunk.pool)
+                base += int(chunk.first[-1])
+                i = j
+            for k, f in missing:                  # the reference's `except`: one point at the origin
+                rows[k][f] = (base, 1)
+                base += 1
+            segments.append(torch.zeros((len(missing), 3), dtype=torch.float32, device=dev))
+            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
+        meta = [(a["scene"], a["track_id"], a["frames"]) for a in annos]
+        self._assemble(pool, rows, [a["boxes"] for a in annos], meta)
+
+    def _assemble(self, pool, rows, boxes64, meta):
+        self.pool, self.rows, self.boxes64, self.meta = pool, rows, boxes64, meta
+        del self[:]
+        for r, b in zip(rows, boxes64):
+            self.append(DeviceTracklet([pool[int(s):int(s) + int(c)] for s, c in r], b.astype(np.float32).reshape(-1, 15)))
+
+    # ---- the reference's accessors ------------------------------------------------------------------------------------------
+    def get_num_scenes(self):
+        return len(self.scene_list)
+
+    def get_num_tracklets(self):
+        return len(self)
+
+    def get_num_frames_total(self):
+        return sum(len(t) for t in self)
+
+    def get_num_frames_tracklet(self, tracklet_id):
+        return len(self[tracklet_id])
+
+    def get_frames(self, seq_id, frame_ids):
+        t = self[seq_id]
+        return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (self.meta[seq_id][0], self.meta[seq_id][1], int(self.meta[seq_id][2][f]))}
+                for f in frame_ids]
+
+    # ---- the cache ----------------------------------------------------------------------------------------------------------
+    def save(self, file):
+        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
+        lengths = np.array([len(t) for t in self], np.int64)
+        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
+        arrays = dict(pool=self.pool.cpu().numpy(), lengths=lengths, rows=cat(self.rows, (0, 2), np.int64),
+                      boxes=cat(self.boxes64, (0, 15), np.float64), frames=cat((m[2] for m in self.meta), (0,), np.int64),
+                      scenes=np.array([m[0] for m in self.meta], dtype="U4"), track_ids=np.array([m[1] for m in self.meta], np.int64),
+                      info=np.array([self.split, self.category_name, self.coordinate_mode, repr(self.preload_offset)]),
+                      scene_list=np.array(self.scene_list, dtype="U4"))
+        with open(file, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, file, device=None):
+        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
+        dev = _device(device)
+        self = cls.__new__(cls)
+        DeviceTracklets.__init__(self)
+        with np.load(file) as z:
+            ends = np.cumsum(z["lengths"])
+            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
+            self.split, self.category_name, self.coordinate_mode = (str(s) for s in z["info"][:3])
+            self.preload_offset = float(z["info"][3])
+            self.path, self.scene_list = None, [str(s) for s in z["scene_list"]]
+            meta = [(str(s), int(t), f) for s, t, f in zip(z["scenes"], z["track_ids"], cut(z["frames"]))]
+            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
+        return self

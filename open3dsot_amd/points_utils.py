@@ -578,6 +578,75 @@ def crop_groups_table(groups, device):
     return plan, torch.from_numpy(plan.view(np.uint8).copy()).to(device), need
 
 
+# ---- the preload crop of a dataset reader (csrc/preload.hip; open3dsot_amd/datasets.py is the caller) -----------------------
+PRELOAD_MAX_FRAMES = capi.CONSTANTS["O3D_PRELOAD_MAX_FRAMES"]
+PRELOAD_MAX_BOXES = capi.CONSTANTS["O3D_PRELOAD_MAX_BOXES"]
+PRELOAD_MAX_ROWS = capi.CONSTANTS["O3D_PRELOAD_MAX_ROWS"]
+PRELOAD_COLS = 6      # a frame record: first raw row, n, first box, number of boxes, workgroup start, scratch base
+
+
+def preload_plan(frames, raw_rows):
+    """The host planner of o3d_preload_count / o3d_preload_scatter (no device call): frames (F,6) int32 with columns 0 (first
+    raw row), 1 (n) and 3 (number of boxes) set; fills columns 2, 4 and 5 in place -> (scratch length in int32, workgroups of
+    the count / scatter launches, B).  Raises O3DError on a bad table."""
+    assert frames.dtype == np.int32 and frames.ndim == 2 and frames.shape[1] == PRELOAD_COLS and frames.flags.c_contiguous
+    grid = (ctypes.c_int * 2)()
+    need = capi.load().o3d_preload_scratch(frames.ctypes.data, frames.shape[0], int(raw_rows), ctypes.addressof(grid))
+    if need < 0:
+        raise capi.O3DError("o3d_preload_scratch: bad table (0..%d frames of 0..%d boxes, %d raw rows at most)"
+                            % (PRELOAD_MAX_FRAMES, PRELOAD_MAX_BOXES, PRELOAD_MAX_ROWS))
+    return need, grid[0], grid[1]
+
+
+def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch):
+    _need_gpu(raw, "preload")
+    assert raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2 and raw.shape[1] == 4
+    assert frames.dtype == np.int32 and frames.ndim == 2 and frames.shape[1] == PRELOAD_COLS and frames.flags.c_contiguous
+    for t, dt in ((dev_frames, torch.int32), (bounds, torch.float32), (scratch, torch.int32)):
+        _need_gpu(t, "preload")
+        assert t.dtype == dt and t.is_contiguous() and t.device == raw.device
+    assert dev_frames.numel() == frames.size and bounds.numel() % 6 == 0
+    if transform is not None:
+        transform = np.ascontiguousarray(transform, np.float64)
+        assert transform.shape == (3, 4)
+    return transform
+
+
+def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts):
+    """One o3d_preload_count call (two launches, no sync): raw (rows,4) float32 GPU, frames = the planned (F,6) int32 table on
+    the host and dev_frames its GPU copy, bounds (B,6) float32 GPU, transform = (3,4) float64 on the host | None, scratch =
+    an int32 GPU tensor of at least preload_plan's length -> counts (B,) int32 GPU, written in place"""
+    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch)
+    _need_gpu(counts, "preload_count")
+    B = bounds.numel() // 6
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= B
+    dev = raw.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_preload_count(
+            raw.data_ptr(), raw.shape[0], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
+            None if transform is None else transform.ctypes.data, scratch.data_ptr(), scratch.numel(), counts.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_preload_count")
+
+
+def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row, pool, pool_rows=None):
+    """One o3d_preload_scatter launch after preload_count on the same operands: out_row (B,) int64 GPU = the first pool row of
+    every box, pool (rows,3) float32 GPU, written in place; no row at or beyond pool_rows (default: all of pool) is written"""
+    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch)
+    _need_gpu(out_row, "preload_scatter")
+    _need_gpu(pool, "preload_scatter")
+    B = bounds.numel() // 6
+    assert out_row.dtype == torch.int64 and out_row.is_contiguous() and out_row.numel() >= B
+    assert pool.dtype == torch.float32 and pool.is_contiguous() and pool.dim() == 2 and pool.shape[1] == 3
+    pool_rows = pool.shape[0] if pool_rows is None else int(pool_rows)
+    assert 0 <= pool_rows <= pool.shape[0]
+    dev = raw.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_preload_scatter(
+            raw.data_ptr(), raw.shape[0], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
+            None if transform is None else transform.ctypes.data, scratch.data_ptr(), scratch.numel(), out_row.data_ptr(),
+            pool.data_ptr(), pool_rows, torch.cuda.current_stream(dev).cuda_stream), "o3d_preload_scatter")
+
+
 def train_select(counts, B, caps, sel, n_valid, overflow):
     """One o3d_train_select launch: counts (J,3) int32 GPU, caps = (cap_first, cap_template, cap_search) -> sel (B,), n_valid
     (1,), overflow (1,) int32 GPU tensors, written in place"""

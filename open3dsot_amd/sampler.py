@@ -22,7 +22,8 @@ points_utils.py:299-361) come from MotionBatchBuilder: one pinned upload and ten
     o3d_boxcloud (2, box_aware)  prev_bc / this_bc
 
 Not covered (DESIGN.md sections 13, 13b): use_augmentation for the siamese builder (a small follow-up now: one more fixture and
-the search frame's record only), dataset readers.
+the search frame's record only).  Real data arrives through datasets.KittiTracklets, which is a
+DeviceTracklets.
 """
 import math
 

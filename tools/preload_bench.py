@@ -1,0 +1,192 @@
+"""What reading a KITTI tree into HBM costs with the device-side preload crop (open3dsot_amd/datasets.py, csrc/preload.hip),
+against the host preload restated in numpy.  Not bench.py: that measures the training step on resident batches.
+
+  python tools/preload_bench.py [--scenes 2] [--frames 50] [--points 120000] [--tracklets 8] [--offset 10] [--runs 7]
+                                [--chunk-frames 64] [--mode velodyne|camera] [--host-only]
+
+Setup: a synthetic tree in a temporary directory -- `--scenes` scenes (0019, 0020: the split `test`) of `--frames`
+velodyne files of `--points` points (uniform in 80 m x 80 m x 4 m), `--tracklets` Car tracklets per scene annotated in every
+frame.  Every file is read once before anything is timed, so all timings are from the page cache.  Each figure is the median
+of `--runs` runs with the smallest and the largest, one JSON line at the end:
+  reader_s            KittiTracklets(...) end to end (host clock, ends in a device synchronise): parse, read, upload, crop
+  read_s              the host's file reads into the pinned buffer (host clock), summed over the chunks
+  upload_ms           the raw frames and the tables, host to device (HIP events)
+  count_ms, scatter_ms  the count + scan launches and the scatter launch (HIP events); launch_GBps = the bytes the three
+                      launches must move (the raw rows twice, the pool rows once) over count_ms + scatter_ms
+  host_numpy_s        the YARDSTICK: this file's numpy restatement of the host preload (every distinct frame read once, one
+                      axis-aligned crop per annotated object per frame, float32 coordinates against fp64 bounds) -- NOT the
+                      reference itself, which also builds a pandas frame and Box / PointCloud objects per annotation
+The clouds of the restatement and of the reader are compared bit for bit before the result is printed.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def write_tree(root, scenes, frames, points, tracklets, seed=0):
+    rng = np.random.default_rng(seed)
+    a = 0.012
+    T = np.hstack([np.array([[0.0, -1.0, 0.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0]]) @
+                   np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]]), [[-0.004], [-0.076], [-0.27]]])
+    for sub in ("label_02", "calib"):
+        os.makedirs(os.path.join(root, sub), exist_ok=True)
+    names = ["%04d" % (19 + s) for s in range(scenes)]
+    for scene in names:
+        os.makedirs(os.path.join(root, "velodyne", scene), exist_ok=True)
+        with open(os.path.join(root, "calib", scene + ".txt"), "w") as f:
+            f.write("Tr_velo_cam " + " ".join("%.12e" % v for v in T.reshape(-1)) + "\n")
+        start = rng.uniform([-25.0, -25.0, -1.0], [25.0, 25.0, -0.6], size=(tracklets, 3))
+        speed = rng.uniform(-0.3, 0.3, size=(tracklets, 3)) * [1.0, 1.0, 0.0]
+        lines = []
+        for frame in range(frames):
+            for k in range(tracklets):
+                cam = T[:, :3] @ (start[k] + frame * speed[k]) + T[:, 3]
+                lines.append("%d %d Car 0 0 -1.500000 100.000000 150.000000 200.000000 250.000000 %.6f %.6f %.6f %.6f %.6f %.6f %.6f"
+                             % (frame, k, 1.5, 1.6, 3.9, cam[0], cam[1] + 0.75, cam[2], 0.2 * k + 0.01 * frame))
+            pts = np.empty((points, 4), np.float32)
+            pts[:, :3] = rng.uniform([-40.0, -40.0, -2.5], [40.0, 40.0, 1.5], size=(points, 3))
+            pts[:, 3] = rng.uniform(size=points)
+            pts.tofile(os.path.join(root, "velodyne", scene, "%06d.bin" % frame))
+        with open(os.path.join(root, "label_02", scene + ".txt"), "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return "test" if scenes == 2 else "testtiny"
+
+
+def host_preload(D, root, split, mode, offset):
+    """the host preload in numpy: -> a list (per tracklet) of lists of (n,3) float32"""
+    annos, calibs = D.kitti_annotations(root, split, "Car", mode)
+    cache, out = {}, []
+    signs = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
+    for a in annos:
+        clouds = []
+        for frame, box in zip(a["frames"], a["boxes"]):
+            key = (a["scene"], int(frame))
+            if key not in cache:
+                pc = np.fromfile(os.path.join(root, "velodyne", key[0], "%06d.bin" % key[1]), np.float32).reshape(-1, 4).T[:3]
+                if mode == "camera":
+                    pc = pc.copy()
+                    pc[:3] = calibs[key[0]].dot(np.vstack((pc, np.ones(pc.shape[1]))))[:3]
+                cache[key] = pc
+            pc = cache[key]
+            if offset > 0:
+                w, l, h = box[3:6]
+                corners = box[6:15].reshape(3, 3) @ (signs * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
+                hi, lo = corners.max(1) + offset, corners.min(1) - offset
+                keep = (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])
+                pc = pc[:, keep]
+            clouds.append(pc)
+        out.append(clouds)
+    return out
+
+
+def stat(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": len(xs)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    for name, default in (("frames", 50), ("points", 120000), ("tracklets", 8), ("runs", 7), ("chunk-frames", 64)):
+        ap.add_argument("--" + name, type=int, default=default)
+    ap.add_argument("--offset", type=float, default=10.0)
+    ap.add_argument("--scenes", type=int, choices=(1, 2), default=2)
+    ap.add_argument("--mode", choices=("velodyne", "camera"), default="velodyne")
+    ap.add_argument("--host-only", action="store_true", help="write the tree and time the numpy restatement only (no device)")
+    args = ap.parse_args()
+    assert args.runs >= 7 or args.host_only, "a median of at least 7 runs"
+    import torch
+    from open3dsot_amd import datasets as D
+    if not args.host_only and not torch.cuda.is_available():
+        raise SystemExit("preload_bench needs a GPU: the reader cannot be measured on the host")
+    with tempfile.TemporaryDirectory() as root:
+        split = write_tree(root, args.scenes, args.frames, args.points, args.tracklets)
+        host = host_preload(D, root, split, args.mode, args.offset)          # reads every file once: the page cache is warm
+        host_s = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            host_preload(D, root, split, args.mode, args.offset)
+            host_s.append(time.perf_counter() - t0)
+        res = {"tool": "preload_bench", "scenes": args.scenes, "frames": args.frames, "points": args.points,
+               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, "mode": args.mode,
+               "crops": sum(len(c) for c in host), "host_numpy_s": stat(host_s)}
+        if args.host_only:
+            print(json.dumps(res))
+            return
+        dev = torch.device("cuda", 0)
+        kw = dict(category_name="Car", coordinate_mode=args.mode, preload_offset=args.offset, device=dev, chunk_frames=args.chunk_frames)
+        trk = D.KittiTracklets(root, split, **kw)                           # warm-up: code objects, the allocator, pinned memory
+        torch.cuda.synchronize(dev)
+        for t, h in zip(trk, host):                                         # faster and different is not faster
+            for g, c in zip(t.frames, h):
+                c = np.ascontiguousarray(c.T, np.float32)
+                assert tuple(g.shape) == c.shape and np.array_equal(g.cpu().numpy().view(np.int32), c.view(np.int32))
+        reader_s = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            trk = D.KittiTracklets(root, split, **kw)
+            torch.cuda.synchronize(dev)
+            reader_s.append(time.perf_counter() - t0)
+        # the split: the same chunks, step by step
+        annos, calibs = D.kitti_annotations(root, split, "Car", args.mode)
+        per_frame = {}
+        for a in annos:
+            for frame, box in zip(a["frames"], a["boxes"]):
+                per_frame.setdefault((a["scene"], int(frame)), []).append(box)
+        keys = list(per_frame)
+        chunks = []
+        i = 0
+        while i < len(keys):
+            j = i
+            while j < len(keys) and j - i < args.chunk_frames and keys[j][0] == keys[i][0]:
+                j += 1
+            chunks.append(keys[i:j])
+            i = j
+        read_s, upload_ms, count_ms, scatter_ms, raw_bytes, pool_bytes = [], [], [], [], 0, 0
+        ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
+        for run in range(args.runs + 1):                                    # run 0 warms up
+            tot = {"read": 0.0, "upload": 0.0, "count": 0.0, "scatter": 0.0}
+            raw_bytes = pool_bytes = 0
+            pinned = None
+            for ck in chunks:
+                files = [(os.path.join(root, "velodyne", s, "%06d.bin" % f), D.velodyne_rows(os.path.join(root, "velodyne", s, "%06d.bin" % f)))
+                         for s, f in ck]
+                bounds = [D.preload_bounds(np.stack(per_frame[k]), args.offset) for k in ck]
+                T = np.ascontiguousarray(calibs[ck[0][0]][:3]) if args.mode == "camera" else None
+                c = D.PreloadChunk(files, bounds, T, dev, pinned)
+                pinned = c.pinned
+                t0 = time.perf_counter()
+                c.read()
+                tot["read"] += time.perf_counter() - t0
+                e = [ev() for _ in range(5)]
+                with torch.cuda.device(dev):
+                    e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
+                    c.read_back()
+                    e[3].record(); c.scatter(); e[4].record()
+                torch.cuda.synchronize(dev)
+                tot["upload"] += e[0].elapsed_time(e[1])
+                tot["count"] += e[1].elapsed_time(e[2])
+                tot["scatter"] += e[3].elapsed_time(e[4])
+                raw_bytes += 16 * c.raw_rows
+                pool_bytes += 12 * c.pool.shape[0]
+            if run:
+                read_s.append(tot["read"]); upload_ms.append(tot["upload"]); count_ms.append(tot["count"]); scatter_ms.append(tot["scatter"])
+        launch_ms = [a + b for a, b in zip(count_ms, scatter_ms)]
+        moved = 2 * raw_bytes + pool_bytes
+        res.update(reader_s=stat(reader_s), read_s=stat(read_s), upload_ms=stat(upload_ms), count_ms=stat(count_ms),
+                   scatter_ms=stat(scatter_ms), raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
+                   launch_GBps=stat([moved / (ms * 1e-3) / 1e9 for ms in launch_ms]),
+                   upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in upload_ms]), chunks=len(chunks),
+                   host_over_reader=statistics.median(host_s) / statistics.median(reader_s))
+        print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
