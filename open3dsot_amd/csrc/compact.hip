@@ -24,12 +24,22 @@
 
 namespace {
 
-// one lane per slot; balls of ns (power of two <= 64) consecutive lanes
-__global__ __launch_bounds__(256) void compact_count_kernel(const int32_t* __restrict__ idx, long nslots, int ns,
-                                                            int32_t* __restrict__ ball_cnt) {
-    const long s = (long)blockIdx.x * 256 + threadIdx.x;
+// One segment of the layout: idx (B,npoint,ns) -> ball_cnt / ball_off (nballs each) / meta (4 ints) of the segment and its
+// columns of the joint gp / cball / cw from col_base on; pt_base / ball_base = its first point column / ball id.  Every build
+// kernel takes two (s0, s1) and covers segment 0's workgroups first, then segment 1's; a one-segment build hands an empty s1
+// (no slots, NULL pointers) and a grid that ends with segment 0, so no workgroup dereferences it.
+struct CompactSeg {
+    const int32_t* idx; long nslots; int npoint, ld, col_base, pt_base, ball_base, nballs;
+    int32_t* ball_cnt; int32_t* ball_off; int32_t* meta;
+};
+
+// one lane per slot; balls of ns (power of two <= 64) consecutive lanes; blocks0 = workgroups of segment 0
+__global__ __launch_bounds__(256) void compact_count_kernel(CompactSeg s0, CompactSeg s1, int ns, int blocks0) {
+    const bool second = (int)blockIdx.x >= blocks0;
+    const CompactSeg& sg = second ? s1 : s0;
+    const long s = (long)(blockIdx.x - (second ? blocks0 : 0)) * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    const int v = s < nslots ? idx[s] : -1;
+    const int v = s < sg.nslots ? sg.idx[s] : -1;
     const int base = lane & ~(ns - 1), k = lane - base;
     const int first = __shfl(v, base, 64);
     // copies = the maximal SUFFIX of slots equal to the first hit (ball_query's padding); an index list
@@ -37,18 +47,19 @@ __global__ __launch_bounds__(256) void compact_count_kernel(const int32_t* __res
     const unsigned long long m = __ballot(v != first);
     const unsigned long long seg = ns == 64 ? ~0ull : (((1ull << ns) - 1) << base);
     const unsigned long long other = m & seg;
-    if (k == 0 && s < nslots) ball_cnt[s / ns] = other ? (63 - __clzll((long long)other)) - base + 1 : 1;
+    if (k == 0 && s < sg.nslots) sg.ball_cnt[s / ns] = other ? (63 - __clzll((long long)other)) - base + 1 : 1;
 }
 
-// exclusive scan of ball_cnt (any n: ceil(n / 1024) balls per thread) by one workgroup; meta = {Ptot rounded up to 256, Ptot, n, 0}
-__global__ __launch_bounds__(1024) void compact_scan_kernel(const int32_t* __restrict__ ball_cnt, int n,
-                                                            int col_base, int32_t* __restrict__ ball_off,
-                                                            int32_t* __restrict__ meta) {
+// exclusive scan of a segment's ball_cnt (any n: ceil(n / 1024) balls per thread) by one workgroup per segment;
+// meta = {Ptot rounded up to 256, Ptot, n, 0}
+__global__ __launch_bounds__(1024) void compact_scan_kernel(CompactSeg s0, CompactSeg s1) {
+    const CompactSeg& sg = blockIdx.x ? s1 : s0;
+    const int n = sg.nballs;
     __shared__ int sh[1024];
     const int per = (n + 1023) / 1024;
     const int i0 = threadIdx.x * per;
     int local = 0;
-    for (int i = i0; i < i0 + per && i < n; ++i) local += ball_cnt[i];
+    for (int i = i0; i < i0 + per && i < n; ++i) local += sg.ball_cnt[i];
     sh[threadIdx.x] = local;
     __syncthreads();
     for (int off = 1; off < 1024; off <<= 1) {
@@ -57,41 +68,41 @@ __global__ __launch_bounds__(1024) void compact_scan_kernel(const int32_t* __res
         sh[threadIdx.x] += v;
         __syncthreads();
     }
-    int run = col_base + sh[threadIdx.x] - local;
+    int run = sg.col_base + sh[threadIdx.x] - local;
     for (int i = i0; i < i0 + per && i < n; ++i) {
-        ball_off[i] = run;
-        run += ball_cnt[i];
+        sg.ball_off[i] = run;
+        run += sg.ball_cnt[i];
     }
     if (threadIdx.x == 1023) {
         const int tot = sh[1023];
-        meta[0] = (tot + 255) & ~255;
-        meta[1] = tot;
-        meta[2] = n;
-        meta[3] = 0;
+        sg.meta[0] = (tot + 255) & ~255;
+        sg.meta[1] = tot;
+        sg.meta[2] = n;
+        sg.meta[3] = 0;
     }
 }
 
-__global__ __launch_bounds__(256) void compact_fill_kernel(const int32_t* __restrict__ idx, long nslots, int ns,
-                                                           int npoint, int ld, int col_base, int pt_base,
-                                                           int ball_base, int dummy_ball,
-                                                           const int32_t* __restrict__ ball_cnt,
-                                                           const int32_t* __restrict__ ball_off,
-                                                           const int32_t* __restrict__ meta,
+// per segment: its nslots / 256 workgroups, then one for its padding columns
+__global__ __launch_bounds__(256) void compact_fill_kernel(CompactSeg s0, CompactSeg s1, int ns, int blocks0, int dummy_ball,
                                                            int32_t* __restrict__ gp, int32_t* __restrict__ cball,
                                                            float* __restrict__ cw) {
-    if (blockIdx.x == gridDim.x - 1) {       // padding columns [Ptot, Ptot_pad)
-        const int q = meta[1] + threadIdx.x;
-        if (q < meta[0]) { gp[col_base + q] = 0; cball[col_base + q] = dummy_ball; cw[col_base + q] = 0.f; }
+    const bool second = (int)blockIdx.x >= blocks0 + 1;
+    const CompactSeg& sg = second ? s1 : s0;
+    const int blk = blockIdx.x - (second ? blocks0 + 1 : 0);
+    const int nblk = (int)(sg.nslots / 256);
+    if (blk == nblk) {       // padding columns [Ptot, Ptot_pad) of this segment
+        const int q = sg.meta[1] + threadIdx.x;
+        if (q < sg.meta[0]) { gp[sg.col_base + q] = 0; cball[sg.col_base + q] = dummy_ball; cw[sg.col_base + q] = 0.f; }
         return;
     }
-    const long s = (long)blockIdx.x * 256 + threadIdx.x;
-    if (s >= nslots) return;
+    const long s = (long)blk * 256 + threadIdx.x;
+    if (s >= sg.nslots) return;
     const int ball = (int)(s / ns), k = (int)(s - (long)ball * ns);
-    const int cnt = ball_cnt[ball];
+    const int cnt = sg.ball_cnt[ball];
     if (k >= cnt) return;
-    const int q = ball_off[ball] + k;                     // ball_off already includes col_base
-    gp[q] = pt_base + (ball / npoint) * ld + idx[s];
-    cball[q] = ball_base + ball;
+    const int q = sg.ball_off[ball] + k;                  // ball_off already includes col_base
+    gp[q] = sg.pt_base + (ball / sg.npoint) * sg.ld + sg.idx[s];
+    cball[q] = sg.ball_base + ball;
     cw[q] = k == 0 ? (float)(1 + ns - cnt) : 1.f;
 }
 
@@ -1019,6 +1030,17 @@ static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // (100 pairs x 1024 balls of the 2048-point search cloud, cfgs/BAT_CAR_NUSCENES.yaml:11,56) has 102 400
 constexpr long O3D_MAX_BALLS = 1L << 20;
 
+// the three build launches for one segment (s1 empty: see CompactSeg) or two
+static int compact_build_launch(const CompactSeg& s0, const CompactSeg& s1, int ns, int dummy_ball, int32_t* gp, int32_t* cball,
+                                float* cw, void* stream) {
+    hipStream_t s = o3d_stream(stream);
+    const int nseg = s1.nslots ? 2 : 1, b0 = (int)(s0.nslots / 256), b1 = (int)(s1.nslots / 256);
+    hipLaunchKernelGGL(compact_count_kernel, dim3(b0 + b1), dim3(256), 0, s, s0, s1, ns, b0);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(nseg), dim3(1024), 0, s, s0, s1);
+    hipLaunchKernelGGL(compact_fill_kernel, dim3(b0 + b1 + nseg), dim3(256), 0, s, s0, s1, ns, b0, dummy_ball, gp, cball, cw);
+    return o3d_launch_status();
+}
+
 // One segment of the compact layout: idx (B,npoint,ns) -> ball_cnt (B*npoint), ball_off (B*npoint+1, absolute
 // columns), and per column gp / cball / cw written at [col_base, col_base + live); meta (4 ints) = {live rounded
 // up to 256, live, B*npoint, 0}.  pt_base / ball_base = first point column / first ball id of the segment,
@@ -1030,13 +1052,24 @@ extern "C" int o3d_compact_build(const int32_t* idx, int B, int npoint, int ns, 
     if (!idx || !ball_cnt || !ball_off || !gp || !cball || !cw || !meta || B <= 0 || npoint <= 0 || ns < 1 ||
         ns > 64 || !pow2(ns) || nballs > O3D_MAX_BALLS || nslots % 256 != 0 || ld <= 0 || col_base < 0 || col_base % 256 != 0)
         return O3D_EINVAL;
-    hipStream_t s = o3d_stream(stream);
-    const int blocks = (int)(nslots / 256);
-    hipLaunchKernelGGL(compact_count_kernel, dim3(blocks), dim3(256), 0, s, idx, nslots, ns, ball_cnt);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, ball_cnt, (int)nballs, col_base, ball_off, meta);
-    hipLaunchKernelGGL(compact_fill_kernel, dim3(blocks + 1), dim3(256), 0, s, idx, nslots, ns, npoint, ld, col_base,
-                       pt_base, ball_base, dummy_ball, ball_cnt, ball_off, meta, gp, cball, cw);
-    return o3d_launch_status();
+    const CompactSeg s0 = {idx, nslots, npoint, ld, col_base, pt_base, ball_base, (int)nballs, ball_cnt, ball_off, meta};
+    return compact_build_launch(s0, CompactSeg{}, ns, dummy_ball, gp, cball, cw, stream);
+}
+
+// Both segments of a paired call (template + search cloud through one shared module) in THREE launches instead of six.
+// Arguments per segment as o3d_compact_build; segment 0 sits at column / point / ball 0.
+extern "C" int o3d_compact_build2(const int32_t* idx0, int npoint0, int ld0, const int32_t* idx1, int npoint1, int ld1,
+                                  int B, int ns, int col_base1, int pt_base1, int dummy_ball, int32_t* ball_cnt,
+                                  int32_t* ball_off, int32_t* gp, int32_t* cball, float* cw, int32_t* meta, void* stream) {
+    const long nb0 = (long)B * npoint0, nb1 = (long)B * npoint1;
+    if (!idx0 || !idx1 || !ball_cnt || !ball_off || !gp || !cball || !cw || !meta || B <= 0 || npoint0 <= 0 ||
+        npoint1 <= 0 || ns < 1 || ns > 64 || !pow2(ns) || nb0 > O3D_MAX_BALLS || nb1 > O3D_MAX_BALLS || (nb0 * ns) % 256 != 0 ||
+        (nb1 * ns) % 256 != 0 || ld0 <= 0 || ld1 <= 0 || col_base1 < 0 || col_base1 % 256 != 0 || pt_base1 < 0)
+        return O3D_EINVAL;
+    const CompactSeg s0 = {idx0, nb0 * ns, npoint0, ld0, 0, 0, 0, (int)nb0, ball_cnt, ball_off, meta};
+    const CompactSeg s1 = {idx1, nb1 * ns, npoint1, ld1, col_base1, pt_base1, (int)nb0, (int)nb1, ball_cnt + nb0, ball_off + nb0,
+                           meta + 4};
+    return compact_build_launch(s0, s1, ns, dummy_ball, gp, cball, cw, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1148,101 +1181,6 @@ extern "C" int o3d_group_dw0_xyz(const float* dN, const float* Y0, long ldp, con
     hipLaunchKernelGGL(dw0_xyz_kernel<8>, dim3(nblk), dim3(256), 0, s, dN, Y0, ldp, A1, A2, A3, gp, cball, cw, X, ldz, centers,
                        meta, start1, C0, part);
     hipLaunchKernelGGL(dw0_reduce_kernel, dim3(C0 * 3), dim3(256), 0, s, part, nblk, C0 * 3, dW);
-    return o3d_launch_status();
-}
-
-// Both segments of a paired call (template + search cloud through one shared module) in THREE launches instead of six:
-// every kernel covers segment 0's workgroups first, then segment 1's.  Arguments per segment as o3d_compact_build.
-namespace {
-struct CompactSeg {
-    const int32_t* idx; long nslots; int npoint, ld, col_base, pt_base, ball_base, nballs;
-    int32_t* ball_cnt; int32_t* ball_off; int32_t* meta;
-};
-
-__global__ __launch_bounds__(256) void compact_count2_kernel(CompactSeg s0, CompactSeg s1, int ns, int blocks0) {
-    const bool second = (int)blockIdx.x >= blocks0;
-    const CompactSeg& sg = second ? s1 : s0;
-    const long s = (long)(blockIdx.x - (second ? blocks0 : 0)) * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const int v = s < sg.nslots ? sg.idx[s] : -1;
-    const int base = lane & ~(ns - 1), k = lane - base;
-    const int first = __shfl(v, base, 64);
-    const unsigned long long m = __ballot(v != first);
-    const unsigned long long seg = ns == 64 ? ~0ull : (((1ull << ns) - 1) << base);
-    const unsigned long long other = m & seg;
-    if (k == 0 && s < sg.nslots) sg.ball_cnt[s / ns] = other ? (63 - __clzll((long long)other)) - base + 1 : 1;
-}
-
-__global__ __launch_bounds__(1024) void compact_scan2_kernel(CompactSeg s0, CompactSeg s1) {
-    const CompactSeg& sg = blockIdx.x ? s1 : s0;
-    const int n = sg.nballs;
-    __shared__ int sh[1024];
-    const int per = (n + 1023) / 1024;
-    const int i0 = threadIdx.x * per;
-    int local = 0;
-    for (int i = i0; i < i0 + per && i < n; ++i) local += sg.ball_cnt[i];
-    sh[threadIdx.x] = local;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = sg.col_base + sh[threadIdx.x] - local;
-    for (int i = i0; i < i0 + per && i < n; ++i) {
-        sg.ball_off[i] = run;
-        run += sg.ball_cnt[i];
-    }
-    if (threadIdx.x == 1023) {
-        const int tot = sh[1023];
-        sg.meta[0] = (tot + 255) & ~255;
-        sg.meta[1] = tot;
-        sg.meta[2] = n;
-        sg.meta[3] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void compact_fill2_kernel(CompactSeg s0, CompactSeg s1, int ns, int blocks0, int dummy_ball,
-                                                            int32_t* __restrict__ gp, int32_t* __restrict__ cball,
-                                                            float* __restrict__ cw) {
-    const bool second = (int)blockIdx.x >= blocks0 + 1;
-    const CompactSeg& sg = second ? s1 : s0;
-    const int blk = blockIdx.x - (second ? blocks0 + 1 : 0);
-    const int nblk = (int)(sg.nslots / 256);
-    if (blk == nblk) {       // padding columns [Ptot, Ptot_pad) of this segment
-        const int q = sg.meta[1] + threadIdx.x;
-        if (q < sg.meta[0]) { gp[sg.col_base + q] = 0; cball[sg.col_base + q] = dummy_ball; cw[sg.col_base + q] = 0.f; }
-        return;
-    }
-    const long s = (long)blk * 256 + threadIdx.x;
-    if (s >= sg.nslots) return;
-    const int ball = (int)(s / ns), k = (int)(s - (long)ball * ns);
-    const int cnt = sg.ball_cnt[ball];
-    if (k >= cnt) return;
-    const int q = sg.ball_off[ball] + k;                  // ball_off already includes col_base
-    gp[q] = sg.pt_base + (ball / sg.npoint) * sg.ld + sg.idx[s];
-    cball[q] = sg.ball_base + ball;
-    cw[q] = k == 0 ? (float)(1 + ns - cnt) : 1.f;
-}
-}  // namespace
-
-extern "C" int o3d_compact_build2(const int32_t* idx0, int npoint0, int ld0, const int32_t* idx1, int npoint1, int ld1,
-                                  int B, int ns, int col_base1, int pt_base1, int dummy_ball, int32_t* ball_cnt,
-                                  int32_t* ball_off, int32_t* gp, int32_t* cball, float* cw, int32_t* meta, void* stream) {
-    const long nb0 = (long)B * npoint0, nb1 = (long)B * npoint1;
-    if (!idx0 || !idx1 || !ball_cnt || !ball_off || !gp || !cball || !cw || !meta || B <= 0 || npoint0 <= 0 ||
-        npoint1 <= 0 || ns < 1 || ns > 64 || !pow2(ns) || nb0 > O3D_MAX_BALLS || nb1 > O3D_MAX_BALLS || (nb0 * ns) % 256 != 0 ||
-        (nb1 * ns) % 256 != 0 || ld0 <= 0 || ld1 <= 0 || col_base1 < 0 || col_base1 % 256 != 0 || pt_base1 < 0)
-        return O3D_EINVAL;
-    CompactSeg s0 = {idx0, nb0 * ns, npoint0, ld0, 0, 0, 0, (int)nb0, ball_cnt, ball_off, meta};
-    CompactSeg s1 = {idx1, nb1 * ns, npoint1, ld1, col_base1, pt_base1, (int)nb0, (int)nb1, ball_cnt + nb0, ball_off + nb0,
-                     meta + 4};
-    hipStream_t s = o3d_stream(stream);
-    const int b0 = (int)(s0.nslots / 256), b1 = (int)(s1.nslots / 256);
-    hipLaunchKernelGGL(compact_count2_kernel, dim3(b0 + b1), dim3(256), 0, s, s0, s1, ns, b0);
-    hipLaunchKernelGGL(compact_scan2_kernel, dim3(2), dim3(1024), 0, s, s0, s1);
-    hipLaunchKernelGGL(compact_fill2_kernel, dim3(b0 + b1 + 2), dim3(256), 0, s, s0, s1, ns, b0, dummy_ball, gp, cball, cw);
     return o3d_launch_status();
 }
 

@@ -321,18 +321,27 @@ def _shape_ok(npoint, ns):
 
 # ---- the autograd function ---------------------------------------------------------------
 class _Cfg:
-    __slots__ = ("nxyz", "inv_radius", "training", "bns", "eps", "momentum", "centers", "geo", "geo_dims")
+    # layout: the call's `gemm.Compact` where the caller has made it (sa_pair_sampled: with the centres, and with the whole
+    # layout when it came with the batch); else forward makes it from the grouping indices
+    __slots__ = ("nxyz", "inv_radius", "training", "bns", "eps", "momentum", "layout")
 
 
-def _pack_points(lib, segs, nxyz, C, Ns, Npads, B, inv_radius, rows, ldz, st):
+def _layout(segs):
+    """the sizes (`gemm.Compact`) of a call's segments (xyz, new_xyz, feats, idx)"""
+    B, _, ns = segs[0][3].shape
+    return gemm.Compact(B, ns, [sg[3].shape[1] for sg in segs],
+                        [sg[2].shape[2] if sg[2] is not None else sg[0].shape[1] for sg in segs])
+
+
+def _pack_points(lib, segs, nxyz, C, cl, inv_radius, rows, st):
     """the per-point operand X0 (rows, ldz) = [xyz * inv_radius ; feats] of one or two segments, clouds padded to Npads columns"""
-    nseg = len(segs)
-    X0n = torch.empty((rows, ldz), device=segs[0][0].device if nxyz else segs[0][2].device, dtype=torch.float32)
+    two = cl.nseg == 2
+    X0n = torch.empty((rows, cl.ldz), device=segs[0][0].device if nxyz else segs[0][2].device, dtype=torch.float32)
     xs = [sg[0].detach().contiguous() if nxyz else None for sg in segs]
     fs = [sg[2].detach().contiguous() if C else None for sg in segs]
-    _call("pack_points", 0.0, lib.o3d_pack_points, _ptr(xs[0]), _ptr(fs[0]), Ns[0], Npads[0],
-          _ptr(xs[-1]) if nseg == 2 else None, _ptr(fs[-1]) if nseg == 2 else None, Ns[-1] if nseg == 2 else 0,
-          Npads[-1] if nseg == 2 else 0, B, nxyz, C, float(inv_radius), rows, X0n.data_ptr(), st)
+    _call("pack_points", 0.0, lib.o3d_pack_points, _ptr(xs[0]), _ptr(fs[0]), cl.Ns[0], cl.Npads[0],
+          _ptr(xs[-1]) if two else None, _ptr(fs[-1]) if two else None, cl.Ns[-1] if two else 0,
+          cl.Npads[-1] if two else 0, cl.B, nxyz, C, float(inv_radius), rows, X0n.data_ptr(), st)
     return X0n
 
 
@@ -357,66 +366,35 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         gammas = [params[3 * l + 1].detach().contiguous() for l in range(L)]
         betas = [params[3 * l + 2].detach().contiguous() for l in range(L)]
         nxyz = cfg.nxyz
-        geo = getattr(cfg, "geo", None)       # the level's coordinate-only part computed ahead of the step (pair_geometry)
-        dev = segs[0][3].device if geo is None else geo["gp"].device
+        # the layout record: its sizes, and -- when the level's coordinate-only part was computed ahead of the step
+        # (pair_geometry) -- its tensors
+        cl = getattr(cfg, "layout", None) or _layout(segs)
+        B, ns, npoints, ldp, ldz, nballs, start1 = cl.B, cl.ns, cl.npoints, cl.ldp, cl.ldz, cl.nballs, cl.start1
+        dev = segs[0][3].device if cl.gp is None else cl.gp.device
         f32, i32 = torch.float32, torch.int32
         st = _stream()
-        if geo is None:
-            B, _, ns = segs[0][3].shape
-            npoints = [sg[3].shape[1] for sg in segs]
-        else:
-            B, ns, npoints = cfg.geo_dims[0], cfg.geo_dims[1], list(cfg.geo_dims[2])
         C = segs[0][2].shape[1] if segs[0][2] is not None else 0
         Cin0, C0 = nxyz + C, Ws[0].shape[0]
-        Ns = [sg[2].shape[2] if sg[2] is not None else sg[0].shape[1] for sg in segs]
-        Npads = [_up(n, TILE) for n in Ns]
-        Pmaxs = [B * npt * ns for npt in npoints]
-        starts = [0, Pmaxs[0]][:nseg]
-        start1 = starts[1] if nseg == 2 else 0
-        ldp = sum(Pmaxs)
-        pt_bases = [0, B * Npads[0]][:nseg]
-        ldz = sum(B * n for n in Npads)
-        nballs_s = [B * npt for npt in npoints]
-        ball_bases = [0, nballs_s[0]][:nseg]
-        nballs = sum(nballs_s)
         need_bwd = any(ctx.needs_input_grad)
         unit = cfg.inv_radius == 1.0          # normalize_xyz False in every tracker config: no scaling launches
-        # ---- compaction of the grouping indices (per segment, into joint arrays)
-        if geo is not None:
-            ball_cnt, ball_off, gp, cball, cw, meta = (geo[k] for k in ("ball_cnt", "ball_off", "gp", "cball", "cw", "meta"))
-            assert nseg == 2 and gp.numel() == ldp and ball_cnt.numel() == nballs and meta.numel() == 8
-        else:
-            ball_cnt = torch.empty((nballs,), device=dev, dtype=i32)
-            ball_off = torch.empty((nballs + 1,), device=dev, dtype=i32)
-            gp = torch.empty((ldp,), device=dev, dtype=i32)
-            cball = torch.empty((ldp,), device=dev, dtype=i32)
-            cw = torch.empty((ldp,), device=dev, dtype=f32)
-            meta = torch.empty((nseg, 4), device=dev, dtype=i32)
-            if nseg == 2:      # both segments: three launches instead of six
-                _call("compact_build", 0.0, lib.o3d_compact_build2, segs[0][3].data_ptr(), npoints[0], Npads[0],
-                      segs[1][3].data_ptr(), npoints[1], Npads[1], B, ns, starts[1], pt_bases[1], nballs, ball_cnt.data_ptr(),
-                      ball_off.data_ptr(), gp.data_ptr(), cball.data_ptr(), cw.data_ptr(), meta.data_ptr(), st)
-            else:
-                for s_, sg in enumerate(segs):
-                    _call("compact_build", 0.0, lib.o3d_compact_build, sg[3].data_ptr(), B, npoints[s_], ns, Npads[s_],
-                          starts[s_], pt_bases[s_], ball_bases[s_], nballs, ball_cnt[ball_bases[s_]:].data_ptr(),
-                          ball_off[ball_bases[s_]:].data_ptr(), gp.data_ptr(), cball.data_ptr(), cw.data_ptr(),
-                          meta[s_].data_ptr(), st)
+        if cl.gp is None:      # compaction of the grouping indices (both segments of a paired call in three launches)
+            cl.alloc(dev, centers=False).build([sg[3] for sg in segs], st)
+        ball_cnt, ball_off, gp, cball, cw, meta = cl.ball_cnt, cl.ball_off, cl.gp, cl.cball, cl.cw, cl.meta
         # ---- layer 0 on the points: Z = W0 . [xyz * inv_radius ; feats], flat (C0, ldz)
-        padded = any(n != npd for n, npd in zip(Ns, Npads))
         # rows padded to a multiple of 16 (zero rows, zero weight columns): the per-point GEMM then runs on the
         # direct MFMA kernel (csrc/mlp_direct.hip needs K % 16 == 0) instead of the generic LDS-staged one
         # (and the buffer itself to a multiple of 64 rows for the weight-gradient kernel of csrc/mlp_wgrad.hip)
         Cin0p = _up(Cin0, 16) if Cin0 > 16 else Cin0
         Cin0m = _up(Cin0, 64) if Cin0 > 16 else Cin0
-        X0n = _pack_points(lib, segs, nxyz, C, Ns, Npads, B, cfg.inv_radius, Cin0m, ldz, st)
+        X0n = _pack_points(lib, segs, nxyz, C, cl, cfg.inv_radius, Cin0m, st)
         centers = None
         if nxyz:       # ball centres of every segment + the dummy ball (origin) of the padding columns
-            centers = getattr(cfg, "centers", None)         # laid out like that by o3d_sample_query (sa_pair_sampled)
+            centers = cl.centers                            # laid out like that by o3d_sample_query (sa_pair_sampled)
             if centers is None:
                 centers = torch.cat([sg[1].detach().reshape(-1, 3) for sg in segs] + [_const_vec(dev, 3, 0.0).view(1, 3)])
             if not unit:
                 centers = centers * cfg.inv_radius
+        cl.centers = centers       # as the kernels read them
         # zero-padded / transposed weight copies come from the device's WeightPrep table (open3dsot_amd/fused_heads.py):
         # inside a tracker forward they were all refreshed by ONE launch, otherwise `get` copies on the spot
         from .fused_heads import prep_for
@@ -428,8 +406,7 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
             W0p = prep.get(params[0], C0, Cin0p)
             # (through the entry that forces 128-column tiles; the heads' stacks leave the tile to o3d_pw_fwd)
             gemm.issue(gemm.flat_fwd("points", gemm.Layer(X0n), W0p, Cin0p, C0, ldz, Z, tile128=True))
-        counts = [float(pm) for pm in Pmaxs]          # BatchNorm counts every slot (copies included)
-        cl = gemm.Compact(ldp, cw, meta, start1, Pmaxs)
+        counts = [float(pm) for pm in cl.Pmaxs]       # BatchNorm counts every slot (copies included)
         acts = []              # gemm.Layer per layer: raw output + (mean, invstd, scale, shift) per segment
         if cfg.training:       # shift of the second moment: the running means before this call, one row per segment
             if nseg == 1:
@@ -447,7 +424,7 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
             statc = statcs[l] if cfg.training else None
             if l == 0:       # its statistics partials come from the expand kernel: one row per ETILE columns, the live ones
                 part = torch.empty((ldp // ETILE, 2, Cout), device=dev, dtype=f32) if cfg.training else None
-                stats = gemm.Partials(part, [pm // ETILE for pm in Pmaxs], (meta, ETILE))
+                stats = gemm.Partials(part, [pm // ETILE for pm in cl.Pmaxs], (meta, ETILE))
             if l == 0 and direct3:
                 _call("group_expand", 0.0, lib.o3d_group_expand_c3, X0n.data_ptr(), ldz, gp.data_ptr(), cball.data_ptr(),
                       cw.data_ptr(), centers.data_ptr(), Ws[0].data_ptr(), Cin0, C0, meta.data_ptr(), start1, ldp,
@@ -472,15 +449,14 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         out = torch.empty((nballs * Cl,), device=dev, dtype=f32)
         argq = torch.empty((nballs * Cl,), device=dev, dtype=i32) if need_bwd else None
         yarg = torch.empty((nballs * Cl,), device=dev, dtype=f32) if need_bwd else None
-        np1 = npoints[1] if nseg == 2 else 0
         if Cl % 64 == 0 and ns <= 32 and ldp >= 288:
             # lane = channel, a wave per ball over an LDS-transposed tile (csrc/compact.hip::pool_t_kernel)
             _call("pool_fwd", 0.0, lib.o3d_pool_fwd_ct, last.Y.data_ptr(), ldp, last.scale.data_ptr(), last.shift.data_ptr(),
-                  ball_off.data_ptr(), ball_cnt.data_ptr(), cball.data_ptr(), meta.data_ptr(), start1, B, Cl, npoints[0], np1,
+                  ball_off.data_ptr(), ball_cnt.data_ptr(), cball.data_ptr(), meta.data_ptr(), start1, B, Cl, npoints[0], cl.np1,
                   ns, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
         else:       # shapes the transposed tile does not take (nsample 64, channels % 64): lanes along the ball's columns
             _call("pool_fwd", 0.0, lib.o3d_pool_fwd_c, last.Y.data_ptr(), ldp, last.scale.data_ptr(), last.shift.data_ptr(),
-                  ball_off.data_ptr(), ball_cnt.data_ptr(), B, Cl, npoints[0], np1, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
+                  ball_off.data_ptr(), ball_cnt.data_ptr(), B, Cl, npoints[0], cl.np1, out.data_ptr(), _ptr(argq), _ptr(yarg), st)
         if need_bwd:
             ctx.cfg = cfg
             ctx.versions = _versions(params)
@@ -488,10 +464,9 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
             ctx.Wts = [None] + [prep.get(params[3 * l], Ws[l].shape[1], Ws[l].shape[0], transpose=True) for l in range(1, L)]
             want_in = any(ctx.needs_input_grad[2:2 + 4 * nseg])
             ctx.W0t = prep.get(params[0], _up(Cin0, 64), C0, transpose=True) if want_in else None
-            ctx.geom = (B, ns, C, nseg, Ns, Npads, npoints, Pmaxs, starts, pt_bases, ball_bases, nballs_s)
-            ctx.saved = (X0n, centers, ball_off, ball_cnt, gp, cball, cw, meta, Ws, gammas, acts, out.detach(), argq, yarg)
-        outs = tuple(out[ball_bases[s_] * Cl:(ball_bases[s_] + nballs_s[s_]) * Cl].view(B, Cl, npoints[s_])
-                     for s_ in range(nseg))
+            ctx.C, ctx.layout = C, cl
+            ctx.saved = (X0n, Ws, gammas, acts, out.detach(), argq, yarg)
+        outs = tuple(cl.pooled(out, Cl))
         return outs if nseg > 1 else outs[0]
 
     @staticmethod
@@ -500,23 +475,21 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
         lib = capi.load()
         cfg = ctx.cfg
         _check_versions(ctx.versions, "FusedGroupedMLPCompact")
-        B, ns, C, nseg, Ns, Npads, npoints, Pmaxs, starts, pt_bases, ball_bases, nballs_s = ctx.geom
-        X0n, centers, ball_off, ball_cnt, gp, cball, cw, meta, Ws, gammas, acts, out, argq, yarg = ctx.saved
+        C, cl = ctx.C, ctx.layout
+        B, ns, nseg, npoints, ldp, ldz, nballs, start1 = cl.B, cl.ns, cl.nseg, cl.npoints, cl.ldp, cl.ldz, cl.nballs, cl.start1
+        centers, ball_off, ball_cnt, gp, cball, cw, meta = cl.centers, cl.ball_off, cl.ball_cnt, cl.gp, cl.cball, cl.cw, cl.meta
+        X0n, Ws, gammas, acts, out, argq, yarg = ctx.saved
         L = len(Ws)
         dev = out.device
         st = _stream()
         f32 = torch.float32
         nxyz = cfg.nxyz
-        ldp, ldz, nballs = sum(Pmaxs), X0n.shape[1], sum(nballs_s)
-        start1 = starts[1] if nseg == 2 else 0
-        counts = [float(pm) for pm in Pmaxs]
-        cl = gemm.Compact(ldp, cw, meta, start1, Pmaxs)
+        counts = [float(pm) for pm in cl.Pmaxs]
         grads = [None] * (3 * L)
         needs = ctx.needs_input_grad[2:2 + 4 * nseg]
         want_xyz = nxyz > 0 and any(needs[4 * s_] or needs[4 * s_ + 1] for s_ in range(nseg))
         want_feats = C > 0 and any(needs[4 * s_ + 2] for s_ in range(nseg))
         Cl = Ws[-1].shape[0]
-        np1 = npoints[1] if nseg == 2 else 0
         dN = torch.empty((Cl, ldp), device=dev, dtype=f32)          # dense class-sum gradient of the pooled layer
         # one pass over the live columns (no zero fill; csrc/compact.hip::pool_bwd_dense_kernel), partial rows per 512 columns;
         # the segments' gradients are read where they lie (any batch / channel strides)
@@ -533,24 +506,23 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
             part = torch.empty((ldp // POOL_DENSE_COLS, 2, Cl), device=dev, dtype=f32)
             _call("pool_bwd", 0.0, lib.o3d_pool_bwd_dense, *gsrc, out.data_ptr(), argq.data_ptr(), yarg.data_ptr(),
                   acts[-1].mean.data_ptr(), cball.data_ptr(), ball_off.data_ptr(), meta.data_ptr(), start1, ldp, B, Cl, npoints[0],
-                  np1, dN.data_ptr(), part.data_ptr(), st)
+                  cl.np1, dN.data_ptr(), part.data_ptr(), st)
             # one row per POOL_DENSE_COLS columns, the live ones
-            stats = gemm.Partials(part, [pm // POOL_DENSE_COLS for pm in Pmaxs], (meta, POOL_DENSE_COLS))
+            stats = gemm.Partials(part, [pm // POOL_DENSE_COLS for pm in cl.Pmaxs], (meta, POOL_DENSE_COLS))
         else:
             # pooled-layer gradient: the segments' (B, Cl, npoint) blocks back to back, like `out`
             if nseg == 1:
                 dOut = dOuts[0].contiguous()
             else:
                 dOut = torch.empty((nballs * Cl,), device=dev, dtype=f32)
-                for s_ in range(nseg):
-                    dst = dOut[ball_bases[s_] * Cl:(ball_bases[s_] + nballs_s[s_]) * Cl].view(B, Cl, npoints[s_])
+                for s_, dst in enumerate(cl.pooled(dOut, Cl)):
                     if dOuts[s_] is None:
                         dst.zero_()
                     else:
                         dst.copy_(dOuts[s_])
             part = torch.empty((nseg, POOL_BWD_SPLIT, 2, Cl), device=dev, dtype=f32)
             _call("pool_bwd", 0.0, lib.o3d_pool_bwd_c, dOut.data_ptr(), out.data_ptr(), argq.data_ptr(), yarg.data_ptr(),
-                  acts[-1].mean.data_ptr(), B, Cl, npoints[0], np1, meta.data_ptr(), start1, ldp, dN.data_ptr(),
+                  acts[-1].mean.data_ptr(), B, Cl, npoints[0], cl.np1, meta.data_ptr(), start1, ldp, dN.data_ptr(),
                   part.data_ptr(), st)
             stats = gemm.Partials(part, [POOL_BWD_SPLIT] * nseg, ())      # POOL_BWD_SPLIT rows per segment, all live
         seg_grads = [[None, None, None] for _ in range(nseg)]
@@ -575,19 +547,17 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                 S = torch.empty((Cout, ldz), device=dev, dtype=f32)
                 T = torch.empty((Cout, nballs), device=dev, dtype=f32) if nxyz else None
                 spanmax = max(npoints) * ns
-                npo = lib.o3d_group_reduce_gather_scratch(B, nseg, npoints[0], Npads[0], npoints[-1], Npads[-1],
-                                                          spanmax) if _REDUCE_GATHER["on"] else -1
+                npo = lib.o3d_group_reduce_gather_scratch(*cl.reduce_dims, spanmax) if _REDUCE_GATHER["on"] else -1
                 if npo >= 0:     # the cloud's columns through a transposed index: one LDS atomic per run of equal points
                     perm = torch.empty((ldp,), device=dev, dtype=torch.int32)
                     poff = torch.empty((npo,), device=dev, dtype=torch.int32)
                     _call("group_reduce", 0.0, lib.o3d_group_reduce_gather, dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1],
-                          A[2], gp.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(), B, nseg, npoints[0],
-                          Npads[0], npoints[-1], Npads[-1], Cout, spanmax, perm.data_ptr(), poff.data_ptr(), S.data_ptr(),
-                          _ptr(T), st)
+                          A[2], gp.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(), *cl.reduce_dims,
+                          Cout, spanmax, perm.data_ptr(), poff.data_ptr(), S.data_ptr(), _ptr(T), st)
                 else:            # the index does not fit the LDS budget (o3d_group_reduce_gather_scratch < 0): one LDS atomic per column
                     _call("group_reduce", 0.0, lib.o3d_group_reduce_c, dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1], A[2],
-                          gp.data_ptr(), cball.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(), B, nseg,
-                          npoints[0], Npads[0], npoints[-1], Npads[-1], Cout, S.data_ptr(), _ptr(T), st)
+                          gp.data_ptr(), cball.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(),
+                          *cl.reduce_dims, Cout, S.data_ptr(), _ptr(T), st)
                 Cinm = X0n.shape[0]                  # rows of the padded per-point operand, X as stored
                 dWm = torch.empty((Cout, Cinm), device=dev, dtype=f32)
                 fold = bool(nxyz) and Cinm != Cin
@@ -616,14 +586,14 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                         _call("center_grad", 0.0, lib.o3d_center_grad, T.data_ptr(), Ws[0].data_ptr(), Ws[0].shape[1], Cout, nballs,
                               -float(cfg.inv_radius), dnew_all.data_ptr(), st)
                     for s_ in range(nseg):
-                        view = dX[:Cin, pt_bases[s_]:pt_bases[s_] + B * Npads[s_]].view(Cin, B, Npads[s_])
+                        pt0, bl0, Npad = cl.pt_bases[s_], cl.ball_bases[s_], cl.Npads[s_]
+                        view = dX[:Cin, pt0:pt0 + B * Npad].view(Cin, B, Npad)
                         if want_feats:
-                            seg_grads[s_][2] = view[nxyz:, :, :Ns[s_]].permute(1, 0, 2)
+                            seg_grads[s_][2] = view[nxyz:, :, :cl.Ns[s_]].permute(1, 0, 2)
                         if want_xyz:
-                            dxyz = view[:3, :, :Ns[s_]].permute(1, 2, 0)
+                            dxyz = view[:3, :, :cl.Ns[s_]].permute(1, 2, 0)
                             seg_grads[s_][0] = dxyz if cfg.inv_radius == 1.0 else dxyz * cfg.inv_radius
-                            seg_grads[s_][1] = dnew_all[:, ball_bases[s_]:ball_bases[s_] + nballs_s[s_]].reshape(
-                                3, B, npoints[s_]).permute(1, 2, 0)
+                            seg_grads[s_][1] = dnew_all[:, bl0:bl0 + cl.nballs_s[s_]].reshape(3, B, npoints[s_]).permute(1, 2, 0)
                 continue
             dW = grads[3 * l] = torch.empty((Cout, Cin), device=dev, dtype=f32)
             dNp = torch.empty((Cin, ldp), device=dev, dtype=f32)
@@ -711,19 +681,15 @@ def _run_eval(mlp, layers, segs, nxyz, inv_radius):
     lib = capi.load()
     dev = segs[0][3].device
     f32 = torch.float32
-    nseg = len(segs)
-    B, _, ns = segs[0][3].shape
+    cl = _layout(segs)       # (its sizes only: this path reads the grouping indices themselves)
+    B, ns, ldz = cl.B, cl.ns, cl.ldz
     C = segs[0][2].shape[1] if segs[0][2] is not None else 0
     Ws = [conv.weight.detach().reshape(conv.out_channels, -1) for conv, _ in layers]
     Cin0, C0 = nxyz + C, Ws[0].shape[0]
-    Ns = [sg[2].shape[2] if sg[2] is not None else sg[0].shape[1] for sg in segs]
-    Npads = [_up(n, TILE) for n in Ns]
-    pt_bases = [0, B * Npads[0]][:nseg]
-    ldz = sum(B * n for n in Npads)
     Cin0p = _up(Cin0, 16) if Cin0 > 16 else Cin0
     with torch.cuda.device(dev):
         st = _stream()
-        X0n = _pack_points(lib, segs, nxyz, C, Ns, Npads, B, inv_radius, Cin0p, ldz, st)
+        X0n = _pack_points(lib, segs, nxyz, C, cl, inv_radius, Cin0p, st)
         from .fused_heads import prep_for
         W0p = prep_for(dev).get(layers[0][0].weight, C0, Cin0p)
         Z = torch.empty((C0, ldz), device=dev, dtype=f32)
@@ -731,7 +697,7 @@ def _run_eval(mlp, layers, segs, nxyz, inv_radius):
         vecs = [_eval_vec(lib, bn, bn.weight, bn.bias, st) for _, bn in layers]
         outs = []
         for s_, sg in enumerate(segs):
-            npoint = sg[3].shape[1]
+            npoint = cl.npoints[s_]
             centers = None
             if nxyz:
                 centers = sg[1].detach().reshape(-1, 3)
@@ -739,7 +705,7 @@ def _run_eval(mlp, layers, segs, nxyz, inv_radius):
             out = torch.empty((B, Ws[2].shape[0], npoint), device=dev, dtype=f32)
             _call("sa_eval_fused", 0.0, lib.o3d_sa_eval_fused, Z.data_ptr(), ldz, sg[3].data_ptr(), _ptr(centers),
                   Ws[0].data_ptr(), Cin0, vecs[0].data_ptr(), Ws[1].data_ptr(), vecs[1].data_ptr(), Ws[2].data_ptr(),
-                  vecs[2].data_ptr(), C0, Ws[1].shape[0], Ws[2].shape[0], B, npoint, ns, Npads[s_], pt_bases[s_],
+                  vecs[2].data_ptr(), C0, Ws[1].shape[0], Ws[2].shape[0], B, npoint, ns, cl.Npads[s_], cl.pt_bases[s_],
                   out.data_ptr(), st)
             outs.append(out)
     return outs
@@ -828,35 +794,32 @@ def pair_geometry(grouper, mlp, xyz_a, np_a, si_a, xyz_b, np_b, si_b, out=None):
         return None
     if (si_a is None and np_a > xyz_a.shape[1]) or (si_b is None and np_b > xyz_b.shape[1]):
         return None
-    dev, f32, i32 = xyz_a.device, torch.float32, torch.int32
+    dev, i32 = xyz_a.device, torch.int32
     for si, npt in ((si_a, np_a), (si_b, np_b)):
         if si is not None and not (si.dtype == i32 and si.is_contiguous() and tuple(si.shape) == (B, npt) and si.device == dev):
             return None
-    lib = capi.load()
     xa, xb = xyz_a.detach().contiguous(), xyz_b.detach().contiguous()
-    nb_a, nb_b = B * np_a, B * np_b
-    nballs, ldp = nb_a + nb_b, (nb_a + nb_b) * ns
-    Npad_a, Npad_b = _up(xa.shape[1], TILE), _up(xb.shape[1], TILE)
-    shapes = {"centers": ((nballs + 1, 3), f32), "ball_cnt": ((nballs,), i32), "ball_off": ((nballs + 1,), i32),
-              "gp": ((ldp,), i32), "cball": ((ldp,), i32), "cw": ((ldp,), f32), "meta": ((2, 4), i32)}
-    if out is not None and all(k in out and tuple(out[k].shape) == sh and out[k].dtype == dt and out[k].device == dev and
-                               out[k].is_contiguous() for k, (sh, dt) in shapes.items()):
-        geo = {k: out[k] for k in shapes}        # written in place: the caller's buffers (a FlatBatch's own fields)
+    cl = gemm.Compact(B, ns, [np_a, np_b], [xa.shape[1], xb.shape[1]])
+    if out is not None and cl.fits(out, dev):
+        cl.take(out)                             # written in place: the caller's buffers (a FlatBatch's own fields)
         _GEO_STATS["in_place"] += 1
     else:
-        geo = {k: torch.empty(sh, device=dev, dtype=dt) for k, (sh, dt) in shapes.items()}
+        cl.alloc(dev)
         _GEO_STATS["allocated"] += 1
     idx_a = torch.empty((B, np_a, ns), device=dev, dtype=i32)
     idx_b = torch.empty((B, np_b, ns), device=dev, dtype=i32)
     with torch.cuda.device(dev):
         st = _stream()
-        _call("sample_query", 0.0, lib.o3d_sample_query, xa.data_ptr(), _ptr(si_a), xa.shape[1], np_a, idx_a.data_ptr(),
-              xb.data_ptr(), _ptr(si_b), xb.shape[1], np_b, idx_b.data_ptr(), B, float(grouper.radius), ns,
-              geo["centers"].data_ptr(), st)
-        _call("compact_build", 0.0, lib.o3d_compact_build2, idx_a.data_ptr(), np_a, Npad_a, idx_b.data_ptr(), np_b, Npad_b, B,
-              ns, nb_a * ns, B * Npad_a, nballs, geo["ball_cnt"].data_ptr(), geo["ball_off"].data_ptr(), geo["gp"].data_ptr(),
-              geo["cball"].data_ptr(), geo["cw"].data_ptr(), geo["meta"].data_ptr(), st)
-    return geo
+        _sample_query(grouper, xa, si_a, np_a, idx_a, xb, si_b, np_b, idx_b, cl, st)
+        cl.build([idx_a, idx_b], st)
+    return {k: getattr(cl, k) for k in GEO_KEYS}
+
+
+def _sample_query(grouper, xa, si_a, np_a, idx_a, xb, si_b, np_b, idx_b, cl, st):
+    """centres of both sets (sampling gather) -> cl.centers, both ball queries -> idx_a, idx_b: one launch"""
+    _call("sample_query", 0.0, capi.load().o3d_sample_query, xa.data_ptr(), _ptr(si_a), xa.shape[1], np_a, idx_a.data_ptr(),
+          xb.data_ptr(), _ptr(si_b), xb.shape[1], np_b, idx_b.data_ptr(), cl.B, float(grouper.radius), cl.ns,
+          cl.centers.data_ptr(), st)
 
 
 def sa_pair_sampled(grouper, mlp, a, b, geo=None):
@@ -878,7 +841,7 @@ def sa_pair_sampled(grouper, mlp, a, b, geo=None):
         return None
     if (si_a is None and np_a > xyz_a.shape[1]) or (si_b is None and np_b > xyz_b.shape[1]):
         return None
-    dev, f32, i32 = xyz_a.device, torch.float32, torch.int32
+    dev, i32 = xyz_a.device, torch.int32
     xa, xb = xyz_a.detach().contiguous(), xyz_b.detach().contiguous()
     # sample_query_kernel reads sidx[b * npoint + j]: exactly a contiguous (B, npoint) int32 tensor on the clouds' device (a
     # prefetched or caller-supplied index of another width, batch or device takes the operator-by-operator route, which
@@ -886,28 +849,28 @@ def sa_pair_sampled(grouper, mlp, a, b, geo=None):
     for si, npt in ((si_a, np_a), (si_b, np_b)):
         if si is not None and not (si.dtype == i32 and si.is_contiguous() and tuple(si.shape) == (B, npt) and si.device == dev):
             return None
-    nb_a, nb_b = B * np_a, B * np_b
-    if geo is not None and not (mlp.training and tuple(geo["centers"].shape) == (nb_a + nb_b + 1, 3) and
-                                geo["gp"].numel() == (nb_a + nb_b) * ns and geo["gp"].device == dev):
-        geo = None          # (eval mode takes the one-kernel set abstraction, which wants the grouping indices themselves)
-    if geo is not None:     # the coordinate-only part came with the batch (pair_geometry, computed beside the previous step)
-        centers, idx_a, idx_b = geo["centers"], None, None
+    cl = gemm.Compact(B, ns, [np_a, np_b], [xa.shape[1], xb.shape[1]])
+    # a geometry that came with the batch (pair_geometry, computed beside the previous step) is used only when every one of its
+    # tensors is what this call's layout says (shape, dtype, device, contiguity): the kernels read them through raw pointers.
+    # (eval mode takes the one-kernel set abstraction, which wants the grouping indices themselves)
+    if geo is not None and mlp.training and cl.fits(geo, dev):
+        cl.take(geo)
+        idx_a = idx_b = None
     else:
-        centers = torch.empty((nb_a + nb_b + 1, 3), device=dev, dtype=f32)
+        geo = None
+        cl.centers = torch.empty(cl.tensors["centers"][0], device=dev, dtype=torch.float32)
         idx_a = torch.empty((B, np_a, ns), device=dev, dtype=i32)
         idx_b = torch.empty((B, np_b, ns), device=dev, dtype=i32)
         with torch.cuda.device(dev):
-            _call("sample_query", 0.0, capi.load().o3d_sample_query, xa.data_ptr(), _ptr(si_a), xa.shape[1], np_a,
-                  idx_a.data_ptr(), xb.data_ptr(), _ptr(si_b), xb.shape[1], np_b, idx_b.data_ptr(), B, float(grouper.radius), ns,
-                  centers.data_ptr(), _stream())
-    new_a, new_b = centers[:nb_a].view(B, np_a, 3), centers[nb_a:nb_a + nb_b].view(B, np_b, 3)
+            _sample_query(grouper, xa, si_a, np_a, idx_a, xb, si_b, np_b, idx_b, cl, _stream())
+    nb_a, nb_b = cl.nballs_s
+    new_a, new_b = cl.centers[:nb_a].view(B, np_a, 3), cl.centers[nb_a:nb_a + nb_b].view(B, np_b, 3)
     inv_r = float(1.0 / grouper.radius if grouper.normalize_xyz else 1.0)
     if geo is None and _eval_fused_ok(mlp, layers, [(xa, new_a, f_a, idx_a), (xb, new_b, f_b, idx_b)], 3):
         outs = _run_eval(mlp, layers, [(xa, new_a, f_a, idx_a), (xb, new_b, f_b, idx_b)], 3, inv_r)
         return new_a, outs[0], new_b, outs[1]
     cfg, params = _cfg_params(mlp, layers, 3, inv_r)
-    cfg.centers = centers
-    cfg.geo, cfg.geo_dims = geo, (B, ns, (np_a, np_b))
+    cfg.layout = cl
     outs = FusedGroupedMLPCompact.apply(cfg, 2, xa, new_a, f_a, idx_a, xb, new_b, f_b, idx_b, *params)
     return new_a, outs[0], new_b, outs[1]
 

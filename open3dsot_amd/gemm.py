@@ -8,6 +8,7 @@ One function per launch kind and layout -- flat (C, P) operands: `flat_fwd`, `fl
 `fused_heads._drive` consumes, plus `out` -- the `Partials` the launch writes (what `fused.bn_fin_job` / `bn_bwd_fin_job` are
 handed: tensor, rows per segment, live-row rule), or the scratch a weight gradient needs alive until it has been issued.
 `issue(launch)` launches at once and returns `out`; a generator of the heads yields the launch instead.
+The compact launchers take the layout as a `Compact`: the one record of its sizes and tensors, which also builds it.
 
 `family` names the roofline family of the caller: "pw" (1-D conv stacks: pw_conv_*), "grouped" (positions of a grouped
 MLP: conv_*), "points" (its per-point layer 0: conv_*_points).
@@ -240,9 +241,70 @@ def flush_wgrad_jobs(jobs, st):
 
 
 # ---- compact layout -----------------------------------------------------------------------------------------------------
-# ldp: worst-case column count; cw: column weights; meta: live column counts on the device; start1: first column of segment
-# 1; Pmaxs: worst-case columns per segment
-Compact = collections.namedtuple("Compact", "ldp cw meta start1 Pmaxs")
+class Compact:
+    """The distinct-neighbour layout of csrc/compact.hip for one or two segments (sets of B clouds: the template and the
+    search branch of a paired call): the ONE place that turns (B, ns, npoints, Ns) into its sizes, and the holder of its
+    tensors.  Per segment (lists): npoints balls of ns slots per cloud, Ns points per cloud padded to Npads columns of the
+    per-point operand, Pmaxs worst-case columns (every slot distinct), starts / pt_bases / ball_bases = first column / point
+    column / ball id, nballs_s balls; start1 = first column of segment 1 (0: one segment); ldp / ldz / nballs = columns /
+    point columns / balls of all segments.  Tensors (`tensors`: name -> (shape, dtype)): ball_cnt, ball_off per ball; gp
+    (source point), cball (ball id), cw (weight) per column; meta: the live column counts, on the device; centers: the ball
+    centres + the dummy ball of the padding columns (None without coordinates)."""
+
+    def __init__(self, B, ns, npoints, Ns):
+        self.B, self.ns, self.npoints, self.Ns, self.nseg = B, ns, list(npoints), list(Ns), len(npoints)
+        nseg = self.nseg
+        self.Npads = [_up(n, TILE) for n in self.Ns]
+        self.nballs_s = [B * npt for npt in self.npoints]
+        self.Pmaxs = [nb * ns for nb in self.nballs_s]
+        self.starts = [0, self.Pmaxs[0]][:nseg]
+        self.pt_bases = [0, B * self.Npads[0]][:nseg]
+        self.ball_bases = [0, self.nballs_s[0]][:nseg]
+        self.start1 = self.starts[1] if nseg == 2 else 0
+        self.ldp, self.ldz, self.nballs = sum(self.Pmaxs), sum(B * n for n in self.Npads), sum(self.nballs_s)
+        self.np1 = self.npoints[1] if nseg == 2 else 0            # (the pool entries' "no second segment")
+        # B, nseg, npoint and point columns of the first and the last segment: the argument group of the reduce entries
+        self.reduce_dims = (B, nseg, self.npoints[0], self.Npads[0], self.npoints[-1], self.Npads[-1])
+        f32, i32 = torch.float32, torch.int32
+        self.tensors = {"centers": ((self.nballs + 1, 3), f32), "ball_cnt": ((self.nballs,), i32),
+                        "ball_off": ((self.nballs + 1,), i32), "gp": ((self.ldp,), i32), "cball": ((self.ldp,), i32),
+                        "cw": ((self.ldp,), f32), "meta": ((nseg, 4), i32)}
+        self.centers = self.ball_cnt = self.ball_off = self.gp = self.cball = self.cw = self.meta = None
+
+    def fits(self, given, dev):
+        """`given` (a dict) holds every tensor of the layout with the table's shape and dtype, contiguous, on `dev`"""
+        return all(k in given and torch.is_tensor(given[k]) and tuple(given[k].shape) == sh and given[k].dtype == dt and
+                   given[k].device == dev and given[k].is_contiguous() for k, (sh, dt) in self.tensors.items())
+
+    def take(self, given):
+        """hold the tensors of `given` (which `fits`) -> self"""
+        for k in self.tensors:
+            setattr(self, k, given[k])
+        return self
+
+    def alloc(self, dev, centers=True):
+        """fresh tensors (centers: that one as well) -> self"""
+        for k, (sh, dt) in self.tensors.items():
+            if centers or k != "centers":
+                setattr(self, k, torch.empty(sh, device=dev, dtype=dt))
+        return self
+
+    def build(self, idxs, st):
+        """fill ball_cnt ... meta from the grouping indices idxs[s] (B, npoints[s], ns) int32: three launches"""
+        lib = capi.load()
+        out = [t.data_ptr() for t in (self.ball_cnt, self.ball_off, self.gp, self.cball, self.cw, self.meta)]
+        if self.nseg == 2:
+            _call("compact_build", 0.0, lib.o3d_compact_build2, idxs[0].data_ptr(), self.npoints[0], self.Npads[0],
+                  idxs[1].data_ptr(), self.npoints[1], self.Npads[1], self.B, self.ns, self.start1, self.pt_bases[1], self.nballs,
+                  *out, st)
+        else:
+            _call("compact_build", 0.0, lib.o3d_compact_build, idxs[0].data_ptr(), self.B, self.npoints[0], self.ns, self.Npads[0],
+                  0, 0, 0, self.nballs, *out, st)
+
+    def pooled(self, flat, C):
+        """the segments' (B, C, npoint_s) blocks of a flat pooled buffer (nballs * C), back to back"""
+        return [flat[b * C:(b + n) * C].view(self.B, C, npt) for b, n, npt in zip(self.ball_bases, self.nballs_s, self.npoints)]
+
 
 _TAIL = {"on": True, "applied": -1}       # "on": False = no split (tools/ab_hook.py fused._TAIL.on flips it for the same-box A/B)
 

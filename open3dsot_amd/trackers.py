@@ -133,10 +133,13 @@ class MatchingBaseModel(nn.Module):
 
     @staticmethod
     def _given_geometry(input_dict):
-        if "geo0.gp" not in input_dict:
-            return None
+        """the three levels' prefetched geometry, or None (computed inside the step) unless every tensor of every level is
+        there; whether each is what its level's layout wants is `fused.sa_pair_sampled`'s check"""
         from .fused import GEO_KEYS
-        return [{k: input_dict["geo%d.%s" % (i, k)] for k in GEO_KEYS} for i in range(3)]
+        keys = [["geo%d.%s" % (i, k) for k in GEO_KEYS] for i in range(3)]
+        if not all(k in input_dict for level in keys for k in level):
+            return None
+        return [{k: input_dict[name] for k, name in zip(GEO_KEYS, level)} for level in keys]
 
     def evaluate_one_sample(self, data_dict):
         """The network half of MatchingBaseModel.evaluate_one_sample (models/base_model.py:44-57) without its host round

@@ -180,6 +180,44 @@ def test_compact_build_one_segment_at_a_base(lib):
     assert np.array_equal(host(meta).reshape(2, 4), L.meta)
 
 
+def test_compact_build_one_block_segment(lib):
+    """A segment of ONE count workgroup (1 cloud x 8 balls x 32 slots = 256 slots, plus its padding workgroup): the smallest
+    grid at which the build kernels' pick of a segment from blockIdx.x can go wrong.  Built alone (o3d_compact_build) and
+    next to a copy of itself (o3d_compact_build2: once as segment 0, once as segment 1), each compared in full with the
+    oracle's layout of the same indices -- every column, the unwritten ones included, sentinel tails intact."""
+    B, npoint, ns, N, ld = 1, 8, 32, 40, 64
+    rng = np.random.RandomState(20)
+    cnts = rng.permutation(np.arange(1, ns + 1))[:npoint]
+    idx = np.empty((B, npoint, ns), np.int64)
+    for j, c in enumerate(cnts):             # c distinct points, then copies of the first hit (ball_query's padding)
+        hits = rng.permutation(N)[:c]
+        idx[0, j] = np.concatenate([hits, np.full(ns - c, hits[0])])
+    assert np.array_equal(O.ball_counts(idx), cnts)
+    didx = dev(idx, torch.int32)
+    for nseg in (1, 2):
+        L = O.Layout([(idx, ld)] * nseg)
+        assert L.ldp == 256 * nseg and L.start1 == 256 * (nseg - 1)
+        fs, t = {}, {}
+        for k, n, dt in (("ball_cnt", L.nballs, torch.int32), ("ball_off", L.nballs + 1, torch.int32), ("gp", L.ldp, torch.int32),
+                         ("cball", L.ldp, torch.int32), ("cw", L.ldp, torch.float32), ("meta", nseg * 4, torch.int32)):
+            fs[k], t[k] = outbuf((n,), dt)
+        t["cw"].fill_(float(SENT_I))
+        out = [ptr(t[k]) for k in ("ball_cnt", "ball_off", "gp", "cball", "cw", "meta")]
+        if nseg == 1:
+            rc = lib.o3d_compact_build(didx.data_ptr(), B, npoint, ns, ld, 0, 0, 0, L.dummy_ball, *out, st())
+        else:
+            rc = lib.o3d_compact_build2(didx.data_ptr(), npoint, ld, didx.data_ptr(), npoint, ld, B, ns, L.start1, L.pt_base[1],
+                                        L.dummy_ball, *out, st())
+        assert rc == 0
+        torch.cuda.synchronize()
+        tail_intact(*fs.values())
+        assert np.array_equal(host(t["ball_cnt"]), L.ball_cnt)
+        assert np.array_equal(host(t["ball_off"])[:L.nballs], L.ball_off)
+        assert np.array_equal(host(t["meta"]).reshape(nseg, 4), L.meta)
+        assert np.array_equal(host(t["gp"]), L.gp) and np.array_equal(host(t["cball"]), L.cball)
+        assert np.array_equal(host(t["cw"]), L.cw)
+
+
 # ---- expand ------------------------------------------------------------------------------------------------------------
 def _expand(lib, name, C0, draw):
     d = dlayout(lib, name)

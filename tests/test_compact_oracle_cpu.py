@@ -131,6 +131,33 @@ def test_layout_contract(name):
     assert np.array_equal(L.real[L.rstart], L.ball_off)
 
 
+@pytest.mark.parametrize("B,ns,npoints,Ns", [(1, 32, [8], [40]), (3, 16, [64], [128]), (2, 8, [32, 64], [64, 129]),
+                                            (48, 32, [256, 512], [512, 1024])])
+def test_host_record_states_the_oracles_sizes(B, ns, npoints, Ns):
+    """open3dsot_amd.gemm.Compact, the host side's one statement of the layout's sizes and tensor shapes, against the
+    oracle's independent one (clouds padded to 128 point columns, the worst case of all slots distinct)"""
+    from open3dsot_amd import gemm
+    ld = [(n + 127) // 128 * 128 for n in Ns]
+    L = O.Layout([(np.zeros((B, npt, ns), np.int64), l) for npt, l in zip(npoints, ld)])
+    c = gemm.Compact(B, ns, npoints, Ns)
+    assert (c.nseg, c.B, c.ns, c.npoints, c.Ns, c.Npads) == (L.nseg, B, ns, npoints, Ns, ld)
+    assert (c.starts, c.start1, c.pt_bases, c.ball_bases, c.nballs_s) == (L.start, L.start1, L.pt_base, L.ball_base, L.nballs_s)
+    assert (c.ldp, c.ldz, c.nballs) == (L.ldp, L.ldz, L.nballs) and c.Pmaxs == [n * ns for n in L.nballs_s]
+    assert c.np1 == (npoints[1] if len(npoints) == 2 else 0)
+    assert c.reduce_dims == (B, L.nseg, npoints[0], ld[0], npoints[-1], ld[-1])
+    shapes = {k: sh for k, (sh, _) in c.tensors.items()}
+    assert shapes == {"centers": (L.dummy_ball + 1, 3), "ball_cnt": L.ball_cnt.shape, "ball_off": (L.nballs + 1,),
+                      "gp": L.gp.shape, "cball": L.cball.shape, "cw": L.cw.shape, "meta": L.meta.shape}
+    assert {k for k, (_, dt) in c.tensors.items() if dt == torch.float32} == {"centers", "cw"}
+    assert {k for k, (_, dt) in c.tensors.items() if dt == torch.int32} == set(c.tensors) - {"centers", "cw"}
+    given = {k: torch.empty(sh, dtype=dt) for k, (sh, dt) in c.tensors.items()}
+    cpu = torch.device("cpu")
+    assert c.fits(given, cpu) and c.take(given).gp is given["gp"]
+    assert not c.fits({k: v for k, v in given.items() if k != "meta"}, cpu)
+    assert not c.fits(dict(given, cw=given["cw"].double()), cpu) and not c.fits(dict(given, gp=given["gp"][:-1]), cpu)
+    assert not c.fits(dict(given, centers=given["centers"].t().contiguous().t()), cpu) and not c.fits(given, torch.device("meta"))
+
+
 def _balls_starting(L, lo, hi):
     return int(((L.ball_off >= lo) & (L.ball_off < hi)).sum())
 

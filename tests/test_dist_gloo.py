@@ -198,7 +198,9 @@ def _bat_worker(rank, world, port, out):
     torch.distributed.destroy_process_group()
 
 
-def test_two_rank_gloo_real_tracker(tmp_path):
+def test_two_rank_gloo_real_tracker(tmp_path, cpu_ext):
+    # (cpu_ext: the oracle's operator shim for THIS process's emulation below, undone when the test ends whatever its outcome --
+    # a shim left in place hands host tensors to the device code of every later test of the session)
     port = _free_port()
     mp.spawn(_bat_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     r0, r1 = torch.load(tmp_path / "bat0.pt"), torch.load(tmp_path / "bat1.pt")
@@ -209,34 +211,29 @@ def test_two_rank_gloo_real_tracker(tmp_path):
     assert any(not torch.equal(r0["sd"][k], r1["sd"][k]) for k in r0["sd"] if "running_mean" in k)   # per-rank BN
     assert r0["lr"] == r1["lr"] and r0["lr"] > 0
     # single-process emulation: rank 0's initial weights, mean of the two shard gradients, the same Adam
-    _patch_ext_with_oracle()
-    try:
-        import copy
-        from open3dsot_amd import dist as D
-        ref = _bat_model(7)
-        opt = ref.configure_optimizers()["optimizer"]
-        reps = [copy.deepcopy(ref) for _ in range(2)]               # per-rank BatchNorm buffers
-        for step in range(2):
-            grads = []
-            for r in range(2):
-                reps[r].load_state_dict({k: (v if stat(k) else ref.state_dict()[k]) for k, v in reps[r].state_dict().items()})
-                reps[r].zero_grad(set_to_none=True)
-                first, n = D.shard_indices(step, r, 2, 2)
-                loss, _ = reps[r].training_loss(_bat_batch(first, n))
-                loss.backward()
-                if r == 0:
-                    assert abs(float(loss) - r0["losses"][step]) < 1e-4 * (1 + abs(float(loss)))
-                grads.append([p.grad.clone() if p.grad is not None else torch.zeros_like(p) for p in reps[r].parameters()])
-            for p, g0, g1 in zip(ref.parameters(), *grads):
-                p.grad = (g0 + g1) / 2
-            opt.step()
-        for k, p in ref.named_parameters():
-            # (SGD configuration of base_model.py:29-31 on purpose: Adam normalises every step to +-lr, which turns
-            # the rounding noise of near-zero gradients into sign flips of whole steps)
-            assert torch.allclose(r0["sd"][k], p.detach(), rtol=1e-4, atol=1e-5), k
-    finally:
-        from open3dsot_amd import sa_modules
-        sa_modules.set_fused(True)
+    import copy
+    from open3dsot_amd import dist as D
+    ref = _bat_model(7)
+    opt = ref.configure_optimizers()["optimizer"]
+    reps = [copy.deepcopy(ref) for _ in range(2)]               # per-rank BatchNorm buffers
+    for step in range(2):
+        grads = []
+        for r in range(2):
+            reps[r].load_state_dict({k: (v if stat(k) else ref.state_dict()[k]) for k, v in reps[r].state_dict().items()})
+            reps[r].zero_grad(set_to_none=True)
+            first, n = D.shard_indices(step, r, 2, 2)
+            loss, _ = reps[r].training_loss(_bat_batch(first, n))
+            loss.backward()
+            if r == 0:
+                assert abs(float(loss) - r0["losses"][step]) < 1e-4 * (1 + abs(float(loss)))
+            grads.append([p.grad.clone() if p.grad is not None else torch.zeros_like(p) for p in reps[r].parameters()])
+        for p, g0, g1 in zip(ref.parameters(), *grads):
+            p.grad = (g0 + g1) / 2
+        opt.step()
+    for k, p in ref.named_parameters():
+        # (SGD configuration of base_model.py:29-31 on purpose: Adam normalises every step to +-lr, which turns
+        # the rounding noise of near-zero gradients into sign flips of whole steps)
+        assert torch.allclose(r0["sd"][k], p.detach(), rtol=1e-4, atol=1e-5), k
 
 
 def _m2_worker(rank, world, port, out):

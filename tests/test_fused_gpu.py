@@ -708,6 +708,78 @@ def test_sample_query_launch_matches_gather_ball_query_cat(use_fps, train):
             assert l2rel(p1.grad, p2.grad) < 1e-5, n1
 
 
+def _launch_names(fn):
+    """fn() with every `_call` of the package recorded (as tools/launch_trace.py wraps it) -> (result, [launch names])"""
+    import sys
+    from open3dsot_amd import fused
+    orig, names = fused._call, []
+
+    def traced(name, flops, entry, *args, dims=None):
+        names.append(name)
+        return orig(name, flops, entry, *args, dims=dims)
+    mods = [m for m in list(sys.modules.values())
+            if getattr(m, "__name__", "").startswith("open3dsot_amd") and getattr(m, "_call", None) is orig]
+    for m in mods:
+        m._call = traced
+    try:
+        return fn(), names
+    finally:
+        for m in mods:
+            m._call = orig
+
+
+def test_mismatched_geometry_runs_inline():
+    """A prefetched geometry (fused.pair_geometry) is used only when all seven tensors are what the level's layout says; any
+    other dict is dropped ON THE HOST, before a launch reads it, and the level computes its geometry inline: the same launch
+    sequence (sample_query and compact_build included) and the same outputs as geo=None.  Two geo=None calls on fresh copies
+    of the module are checked first: when they are bit-equal (they are: no atomics in this forward) so must every other
+    call be, else the comparison is the forward rule of test_fused_sa_matches_composed (1e-4 of the tensor scale)."""
+    import copy
+    from open3dsot_amd import fused, sa_modules, trackers
+    torch.manual_seed(3)
+    sa = sa_modules.PointnetSAModule([0, 64, 64, 64], radius=0.3, nsample=8, use_fps=False).cuda().train()
+    g = torch.Generator().manual_seed(4)
+    xa, xb = torch.rand(2, 64, 3, generator=g).cuda(), torch.rand(2, 128, 3, generator=g).cuda()
+
+    def run(geo):
+        m = copy.deepcopy(sa)
+        (na, fa, _), (nb, fb, _) = m.forward_pair(xa, None, 32, xb, None, 64, geo=geo)
+        return na, fa, nb, fb
+
+    geo = sa.pair_geometry(xa, 32, xb, 64)
+    assert geo is not None and set(geo) == set(fused.GEO_KEYS)
+    ref, seq = _launch_names(lambda: run(None))
+    again, seq2 = _launch_names(lambda: run(None))
+    assert seq == seq2 and seq.count("sample_query") == 1 and seq.count("compact_build") == 1
+    exact = all(torch.equal(x, y) for x, y in zip(ref, again))
+    print("two geo=None calls bit-equal:", exact)
+
+    def same(outs):
+        return all(torch.equal(x, y) if exact else rel(x, y) < 1e-4 for x, y in zip(outs, ref))
+
+    got, seq_geo = _launch_names(lambda: run(geo))          # control: the geometry as computed IS taken
+    assert seq_geo == [n for n in seq if n not in ("sample_query", "compact_build")] and same(got)
+    odd = torch.empty((2 * geo["cball"].numel(),), device="cuda", dtype=torch.int32)[::2]
+    odd.copy_(geo["cball"])
+    bad = {"missing key": {k: v for k, v in geo.items() if k != "cw"},
+           "ball_cnt one short": dict(geo, ball_cnt=geo["ball_cnt"][:-1]),
+           "meta (1, 4)": dict(geo, meta=geo["meta"][:1]),
+           "cw float64": dict(geo, cw=geo["cw"].double()),
+           "cball not contiguous": dict(geo, cball=odd)}
+    assert not odd.is_contiguous() and torch.equal(odd, geo["cball"]) and bad["meta (1, 4)"]["meta"].shape == (1, 4)
+    for what, d in bad.items():
+        got, seq_bad = _launch_names(lambda: run(d))
+        assert seq_bad == seq, (what, seq_bad)
+        assert same(got), what
+    # the trackers' side: the input dict yields a geometry only when all 21 tensors are there
+    full = {"geo%d.%s" % (i, k): v for i in range(3) for k, v in geo.items()}
+    levels = trackers.MatchingBaseModel._given_geometry(full)
+    assert len(levels) == 3 and all(set(lv) == set(fused.GEO_KEYS) and lv["gp"] is geo["gp"] for lv in levels)
+    for name in ("geo0.gp", "geo1.cw", "geo2.meta"):
+        assert trackers.MatchingBaseModel._given_geometry({k: v for k, v in full.items() if k != name}) is None
+    assert trackers.MatchingBaseModel._given_geometry({}) is None
+
+
 @pytest.mark.parametrize("kind", ["sa1", "sa2", "sa3", "rpn"])
 def test_reduce_gather_matches_atomic_reduce(kind):
     """o3d_group_reduce_gather (transposed index + LDS gather) against o3d_group_reduce_c (LDS atomics): same S / T,
