@@ -408,16 +408,53 @@ __device__ __forceinline__ float reduce_scatter8(float (&x)[8], int l31) {
     return r;
 }
 
-template <int MODE, int EPI>
+// Operand ring of the split-K tile: D fragment sets per wave, a compile-time choice per (MODE, EPI).  A wave requests
+// min(D, slice) groups before its first MFMA and refills a set as soon as its group is consumed; waits stay counted (vmcnt(N):
+// group g computes while g+1.. are still landing) because the loop consists of two straight-line bodies with unconditional loads
+// (clamped, never predicated; behind the slice's end one cache line per wave instead of a re-load of the last group).
+// Measured, same box, parent library alternating (profiles/splitk_ring.txt): D = 8 at three waves per SIMD for the plain and the
+// BatchNorm+ReLU operand LOSES (per-point layer 0, 18 432 columns: 44 -> 56 us; step 5.21 -> 5.27 ms), D = 4 at four waves is
+// neutral to slower than D = 2 (same launch: 41 -> 53 us), D = 4 for the BatchNorm-backward operand equals D = 2 -- a wave's chain
+// of round trips is not what these launches wait for.  So every instantiation keeps D = 2.  What did pay:
+//  * operand addresses as wave-uniform base + one 32-bit lane offset, the wave index through readfirstlane (scalar loop control)
+//    and no padding re-load: every plain / BatchNorm+ReLU launch 1-4 us faster than round 4's loop, 5.20 -> 5.12 ms per step;
+//  * the per-k constants of the BatchNorm-backward operand (A1..A3: 12 VGPRs per set, the same for all lanes of a half-wave) out
+//    of the ring: a wave stages those of its slice ONCE in its own quarter of the LDS exchange buffer (nobody else touches that
+//    quarter before the barrier; a wave's LDS accesses execute in order) and reads the four k of a group back, broadcast, right
+//    before the group's MFMAs.  146 -> 128 VGPRs: four waves per SIMD instead of three; compact data gradient 256 x 256 x ~7 000 live
+//    columns 30 -> 23 us, x 24 576: 67 -> 62 us.  For the BatchNorm+ReLU operand (already at four waves) the same measured nothing.
+//    One float4 per lane and array: slices of at most 32 groups, K <= SK_STAGE_K; longer contractions keep the constants in VGPRs.
+constexpr int SK_STAGE_K = 1024;
+template <int MODE, int EPI> struct SkRing {
+    static constexpr int depth = 2;
+    static constexpr bool lds_consts = MODE == B_DY;
+    static constexpr int waves = MODE == B_DY ? 4 : 0;      // per SIMD (128 VGPRs at 4); 0: 3 to 4, as the round-4 kernel
+};
+
+template <int I, int N, class F>
+__device__ __forceinline__ void sk_for(F&& fn) {
+    if constexpr (I < N) {
+        fn(std::integral_constant<int, I>{});
+        sk_for<I + 1, N>(fn);
+    }
+}
+
+template <int MODE, int EPI, int D, bool CL>
 __device__ __forceinline__ void splitk_body(DirectArgs& a, const int bx, const int by, float* __restrict__ red) {
     static_assert(MODE <= B_DY && EPI <= 2, "split-K tile: plain / transformed / BatchNorm-backward operands only");
+    static_assert(D >= 2 && D % 2 == 0, "ring depth: whole pairs of groups");
     constexpr int NT = 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int NA = MODE == B_PLAIN ? 0 : MODE == B_XFORM ? 2 : 3;      // per-k constant arrays
+    constexpr bool CLDS = CL && NA > 0;                                     // ... staged in LDS, not carried in the ring
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, h = lane >> 5;
     const int tiles_per_b = a.P / SK_COLS;
     const int tile = bx;
     const int b = tile / tiles_per_b, p0 = (tile - b * tiles_per_b) * SK_COLS;
-    if (a.meta) {                                             // compact layout: dead tile?  which segment?
+    // compact layout: dead tile?  which segment?  (Looking at the live count only AFTER the first fragment sets are requested was
+    // measured with an 8-deep ring: most tiles of a compact launch are dead, and their requests cost the live ones far more
+    // than the count's round trip -- compact 256 x 256 x 6 912: 25 -> 75 us, 5.27 -> 5.50 ms per step, profiles/splitk_ring.txt)
+    if (a.meta) {
         const long c0 = (long)tile * SK_COLS;
         const int seg = (a.start1 > 0 && c0 >= a.start1) ? 1 : 0;
         if (c0 - (seg ? a.start1 : 0) >= a.meta[4 * seg]) return;      // (the whole workgroup: before any barrier)
@@ -434,9 +471,13 @@ __device__ __forceinline__ void splitk_body(DirectArgs& a, const int bx, const i
     float wv[NT] = {1.f, 1.f};
     if (a.w) ldv<NT>(wv, a.w + (long)b * a.P + p);
     const long rowP = a.P;
-    const float* xb = a.X + (long)b * a.K * rowP + p;
-    const float* yb = (MODE >= B_DY) ? a.Y + (long)b * a.K * rowP + p : nullptr;
-    const float* wa = a.A + (long)(m0 + l31) * a.K + 4 * h;
+    // operand addresses = wave-uniform base (computed per group by the scalar unit) + ONE 32-bit lane offset per operand
+    const float* xs = a.X + ((long)b * a.K * rowP + p0);
+    const float* ys = (MODE >= B_DY) ? a.Y + ((long)b * a.K * rowP + p0) : nullptr;
+    const float* was = a.A + (long)m0 * a.K;
+    const unsigned vb = (unsigned)(4 * h) * (unsigned)a.P + (unsigned)(NT * l31);      // (< 4*P + 64, and P <= 2^19 on this tile: splitk_max)
+    const unsigned va = (unsigned)l31 * (unsigned)a.K + (unsigned)(4 * h);
+    const unsigned vc = 4u * h;
 
     // ---- what the epilogue needs besides the accumulators: requested now, consumed after the LDS exchange
     const int mrow = m0 + 8 * wave + 4 * h;                  // this lane's rows: mrow + j, j < 4; positions p, p + 1
@@ -472,26 +513,83 @@ __device__ __forceinline__ void splitk_body(DirectArgs& a, const int bx, const i
     const int q = npair / 4, rem = npair - 4 * q;
     const int ps = wave * q + (wave < rem ? wave : rem);
     const int gs = 2 * ps, ge = 2 * (ps + q + (wave < rem ? 1 : 0));
-    RawB<NT> f[2];
-    float4 wa0[2];
-    auto load = [&](auto stc, int g) {
-        constexpr int st = decltype(stc)::value;
-        load_b<MODE, NT>(a, xb, yb, rowP, 8 * g + 4 * h, 0, 1, f[st]);
-        wa0[st] = *reinterpret_cast<const float4*>(wa + 8 * g);
-    };
-    if (gs < ge) {
-        load(std::integral_constant<int, 0>{}, gs);
-        for (int g = gs; g < ge; g += 2) {
-            load(std::integral_constant<int, 1>{}, g + 1);
+    const int n = ge - gs;                                   // even, >= 2 (K >= 64)
+    RawB<NT> f[D];
+    float4 wa0[D];
+    float* const cst = red + wave * (SK_ROWS * SK_COLS);     // this wave's quarter of the exchange buffer
+    float4 stg0, stg1, stg2;
+    const int su = lane < 2 * n ? lane : 2 * n - 1;          // staging unit: the constants of 4 k (clamped, not predicated)
+    if constexpr (CLDS) {                                    // requested before the ring: the oldest loads, waited for by count
+        stg0 = *reinterpret_cast<const float4*>(a.c1 + 8 * gs + 4 * su);
+        stg1 = *reinterpret_cast<const float4*>(a.c2 + 8 * gs + 4 * su);
+        if constexpr (NA == 3) stg2 = *reinterpret_cast<const float4*>(a.c3 + 8 * gs + 4 * su);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    auto stage = [&]() {                                     // after the first sets are requested
+        if constexpr (CLDS) {
             __builtin_amdgcn_sched_barrier(0);
-            compute_group<MODE, NT, 1>(f[0], wa0[0], wa0[0], 0, wv, acc);
-            __builtin_amdgcn_sched_barrier(0);
-            load(std::integral_constant<int, 0>{}, g + 2 < ge ? g + 2 : ge - 1);       // tail: harmless re-load
-            __builtin_amdgcn_sched_barrier(0);
-            compute_group<MODE, NT, 1>(f[1], wa0[1], wa0[1], 0, wv, acc);
+            if (lane < 2 * n) {
+                float4* c = reinterpret_cast<float4*>(cst) + su * NA;
+                c[0] = stg0;
+                c[1] = stg1;
+                if constexpr (NA == 3) c[2] = stg2;
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
-    }
+    };
+    // group g into set st; behind the slice's end (padding of the last chunk) the clamped group at lane offset 0: one cache line
+    // for the whole wave, never consumed
+    auto load = [&](auto stc, int g) {
+        constexpr int st = decltype(stc)::value;
+        const bool ok = g < ge;
+        const unsigned m = ok ? ~0u : 0u;
+        if (!ok) g = ge - 1;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            ldv<NT>(f[st].v[s], xs + (long)(8 * g + s) * rowP + (vb & m));
+            if constexpr (MODE >= B_DY) ldv<NT>(f[st].y[s], ys + (long)(8 * g + s) * rowP + (vb & m));
+        }
+        if constexpr (NA > 0 && !CLDS) {
+            f[st].c1 = *reinterpret_cast<const float4*>(a.c1 + 8 * g + (vc & m));
+            f[st].c2 = *reinterpret_cast<const float4*>(a.c2 + 8 * g + (vc & m));
+            if constexpr (NA == 3) f[st].c3 = *reinterpret_cast<const float4*>(a.c3 + 8 * g + (vc & m));
+        }
+        wa0[st] = *reinterpret_cast<const float4*>(was + 8 * g + (va & m));
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto comp = [&](auto stc, int g) {
+        constexpr int st = decltype(stc)::value;
+        if constexpr (CLDS) {
+            const float4* c = reinterpret_cast<const float4*>(cst) + (2 * (g - gs) + h) * NA;
+            f[st].c1 = c[0];
+            f[st].c2 = c[1];
+            if constexpr (NA == 3) f[st].c3 = c[2];
+        }
+        compute_group<MODE, NT, 1>(f[st], wa0[st], wa0[st], 0, wv, acc);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // Two straight-line bodies over the D sets, so that every wait is counted: the steady one (D whole groups to compute, every
+    // set refilled with the group D further on) runs while more than D groups are left; the last one refills nothing and leaves
+    // after any pair of groups.  Where they meet, D sets are in flight in the same order on both paths.
+    __builtin_amdgcn_sched_barrier(0);
+    sk_for<0, D>([&](auto ic) { load(ic, gs + decltype(ic)::value); });
+    stage();
+    int g = gs;
+    for (; ge - g > D; g += D)
+        sk_for<0, D>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            comp(ic, g + i);
+            load(ic, g + D + i);
+        });
+    bool more = true;
+    sk_for<0, D / 2>([&](auto jc) {
+        constexpr int i = 2 * decltype(jc)::value;
+        if (more) {
+            comp(std::integral_constant<int, i>{}, g + i);
+            comp(std::integral_constant<int, i + 1>{}, g + i + 1);
+            more = g + i + 2 < ge;
+        }
+    });
 
     // ---- the four partial tiles meet in LDS: red[wave][row][column], a lane's two positions as one 8-byte access
 #pragma unroll
@@ -541,23 +639,28 @@ __device__ __forceinline__ void splitk_body(DirectArgs& a, const int bx, const i
     }
 }
 
-template <int MODE, int EPI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4)))
+// CL: per-k constants staged in LDS; W: waves per SIMD the kernel is built for (0: 3 to 4, as in round 4)
+template <int MODE, int EPI, int D, bool CL, int W>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W ? W : 3, W ? W : 4)))
 void splitk_gemm_kernel(DirectArgs a) {
     __shared__ float red[4 * SK_ROWS * SK_COLS];
-    splitk_body<MODE, EPI>(a, blockIdx.x, blockIdx.y, red);
+    splitk_body<MODE, EPI, D, CL>(a, blockIdx.x, blockIdx.y, red);
 }
 
-template <int MODE, int EPI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4)))
+template <int MODE, int EPI, int D, bool CL, int W>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W ? W : 3, W ? W : 4)))
 void splitk_gemm_pair_kernel(DirectArgs a0, DirectArgs a1) {
     __shared__ float red[4 * SK_ROWS * SK_COLS];
     if (blockIdx.z == 0) {
-        if ((int)blockIdx.y * SK_ROWS < a0.M) splitk_body<MODE, EPI>(a0, blockIdx.x, blockIdx.y, red);
+        if ((int)blockIdx.y * SK_ROWS < a0.M) splitk_body<MODE, EPI, D, CL>(a0, blockIdx.x, blockIdx.y, red);
     } else {
-        if ((int)blockIdx.y * SK_ROWS < a1.M) splitk_body<MODE, EPI>(a1, blockIdx.x, blockIdx.y, red);
+        if ((int)blockIdx.y * SK_ROWS < a1.M) splitk_body<MODE, EPI, D, CL>(a1, blockIdx.x, blockIdx.y, red);
     }
 }
+
+// constants in LDS: a slice's per-k constants are staged with one float4 per lane and array -- contractions up to SK_STAGE_K
+template <int MODE, int EPI>
+static bool splitk_cfg_ok(const DirectArgs& a) { return !(SkRing<MODE, EPI>::lds_consts && MODE != B_PLAIN) || a.K <= SK_STAGE_K; }
 
 // which problems take the split-K tile: 64-column partial rows (the caller's `tile`), K in whole pairs of 8-k groups with
 // at least one pair per wave, and at most splitk_max() output elements in the worst case (beyond that the 8 row slabs of a
@@ -571,7 +674,12 @@ static bool splitk_ok(const DirectArgs& a, int tile) {
 template <int MODE, int EPI>
 int launch_splitk(const DirectArgs& a, hipStream_t st) {
     if constexpr (MODE <= B_DY && EPI <= 2) {
-        hipLaunchKernelGGL((splitk_gemm_kernel<MODE, EPI>), dim3(a.B * (a.P / SK_COLS), a.M / SK_ROWS), dim3(256), 0, st, a);
+        using R = SkRing<MODE, EPI>;
+        const dim3 grid(a.B * (a.P / SK_COLS), a.M / SK_ROWS);
+        if (splitk_cfg_ok<MODE, EPI>(a))
+            hipLaunchKernelGGL((splitk_gemm_kernel<MODE, EPI, R::depth, R::lds_consts, R::waves>), grid, dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL((splitk_gemm_kernel<MODE, EPI, 2, false, 0>), grid, dim3(256), 0, st, a);
         return o3d_launch_status();
     } else {
         return O3D_EINVAL;
@@ -802,7 +910,12 @@ template <int MODE, int EPI>
 int launch_pair(const DirectArgs& a, const DirectArgs& b, int cls, hipStream_t st) {
     if (cls == 4) {
         const int sa = a.M / SK_ROWS, sb = b.M / SK_ROWS;
-        hipLaunchKernelGGL((splitk_gemm_pair_kernel<MODE, EPI>), dim3(a.P / SK_COLS, sa > sb ? sa : sb, 2), dim3(256), 0, st, a, b);
+        using R = SkRing<MODE, EPI>;
+        const dim3 grid(a.P / SK_COLS, sa > sb ? sa : sb, 2);
+        if (splitk_cfg_ok<MODE, EPI>(a) && splitk_cfg_ok<MODE, EPI>(b))
+            hipLaunchKernelGGL((splitk_gemm_pair_kernel<MODE, EPI, R::depth, R::lds_consts, R::waves>), grid, dim3(256), 0, st, a, b);
+        else
+            hipLaunchKernelGGL((splitk_gemm_pair_kernel<MODE, EPI, 2, false, 0>), grid, dim3(256), 0, st, a, b);
         return o3d_launch_status();
     }
     return cls == 2 ? launch_pair_nt<MODE, EPI, 2, 2>(a, b, st) : launch_pair_nt<MODE, EPI, 4, 2>(a, b, st);
