@@ -962,7 +962,16 @@ int o3d_track_score(const float* a, const float* b, const int32_t* valid, int n,
  * O3D_EINVAL, before any HIP call: F outside 0..O3D_PRELOAD_MAX_FRAMES, raw_rows outside 0..O3D_PRELOAD_MAX_ROWS, a record with
  * a negative field, rows past raw_rows, more than O3D_PRELOAD_MAX_BOXES boxes or a plan other than o3d_preload_scratch's, boxes
  * that do not sum to B, a scratch beyond 2^31 - 1 words or shorter than planned, a NULL or misaligned operand that a launch
- * would read or write.  F = 0, B = 0, a frame of n = 0 and a record without boxes succeed; the first two launch nothing. */
+ * would read or write.  F = 0, B = 0, a frame of n = 0 and a record without boxes succeed; the first two launch nothing.
+ *
+ * o3d_preload_posed_count / o3d_preload_posed_scatter: the same launches with one transform PER FRAME RECORD -- what
+ * WaymoDataset._get_frame_from_anno does, whose frames carry a vehicle-to-global pose each.  poses (F,12) float64 on the
+ * DEVICE, 8-byte aligned: row f is the upper 3x4 of record f's transform, row-major; two records over the same raw rows carry
+ * the same pose twice.  The rule is the one above, p' = float(((T_i0*x + T_i1*y) + T_i2*z) + T_i3) with T = poses[f], fp64 on
+ * the float32 input and rounded once.  row_floats = 3 | 4: raw row r is floats [r*row_floats, r*row_floats + 3) of raw, which
+ * is 4-byte aligned, 16-byte when row_floats is 4.  Tables, planning (o3d_preload_scratch), compares, counting and limits are
+ * the pair's above.  O3D_EINVAL, before any HIP call: everything that pair refuses, row_floats outside {3,4}, poses NULL with
+ * F > 0, poses not 8-byte aligned.  F = 0 and B = 0 succeed without a launch. */
 #define O3D_PRELOAD_MAX_FRAMES 4096
 #define O3D_PRELOAD_MAX_BOXES 1024
 #define O3D_PRELOAD_MAX_ROWS 536870911
@@ -973,6 +982,12 @@ int o3d_preload_count(const float* raw, long raw_rows, const int32_t* frames, co
 int o3d_preload_scatter(const float* raw, long raw_rows, const int32_t* frames, const int32_t* frames_dev, int F,
                         const float* bounds, int B, const double* transform, int32_t* scratch, long scratch_len,
                         const long* out_row, float* pool, long pool_rows, void* stream);
+int o3d_preload_posed_count(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
+                            int F, const float* bounds, int B, const double* poses, int32_t* scratch, long scratch_len,
+                            int32_t* counts, void* stream);
+int o3d_preload_posed_scatter(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
+                              int F, const float* bounds, int B, const double* poses, int32_t* scratch, long scratch_len,
+                              const long* out_row, float* pool, long pool_rows, void* stream);
 
 #ifdef __cplusplus
 }

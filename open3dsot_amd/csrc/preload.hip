@@ -6,6 +6,9 @@
 //   o3d_preload_scratch   host only: plans the frame table (first box, workgroup start and scratch base of every frame)
 //   o3d_preload_count     launch 1 (count) and launch 2 (scan): the survivors of every box -> counts (B)
 //   o3d_preload_scatter   launch 3: the survivors of every box, in their original order, as xyz rows of the pool
+//   o3d_preload_posed_count / o3d_preload_posed_scatter   the same launches with ONE TRANSFORM PER FRAME RECORD, read from the
+//                         device, over raw rows of 3 or 4 floats: the reference's WaymoDataset (datasets/waymo_data.py:118-167
+//                         _get_frame_from_anno), whose frames carry a vehicle-to-global pose each
 // The host reads `counts` between the two calls (the only synchronisation of a chunk), sizes the pool and uploads the first
 // pool row of every box.
 //
@@ -31,6 +34,15 @@
 //   x'_i = float(((T_i0*x + T_i1*y) + T_i2*z) + T_i3)
 // which is PointCloud.transform stored back into its float32 array.  This file is compiled with -ffp-contract=off.
 //
+// ---- a pose per record --------------------------------------------------------------------------------------------------------------------
+// poses (F,12) fp64 on the device: the 3x4 upper rows of record f's global_from_car, row-major; two records over the same raw
+// rows carry the same pose twice.  The rule is the camera-mode rule above, word for word (preload_apply is the one statement of
+// it), and it is WaymoDataset's `pointcloud[:3,:] = global_from_car.dot(vstack(points, ones))[:3,:]`: fp64 on the float32
+// input, stored back into the float32 array, so rounded once.  With translations of kilometres that single rounding decides
+// bits, which is why the sum is ordered.  Raw row r is floats [r*row_floats, r*row_floats + 3): Waymo's points_xyz lie as
+// (n,3) rows, which are three 4-byte loads; rows of four floats stay one aligned 16-byte load.  The record, and with it the
+// pose, is uniform over a workgroup: the twelve doubles are scalar loads.
+//
 // ---- three launches, no workgroup ever waits for another ----------------------------------------------------------------------------------
 // The host knows every n and plans the table, as o3d_track_crop_groups_scratch does: record f owns workgroups [wg_start, wg_start
 // + W) of the count and scatter launches (W = ceil(n / 256), 1 for an empty frame, 0 for a record without boxes) and its boxes'
@@ -49,9 +61,14 @@ namespace {
 
 constexpr int PRELOAD_COLS = 6;                            // raw row, n, first box, boxes, wg_start, sbase
 
-struct preload_xf {
+struct preload_xf {                                          // one transform for the whole call, by value
     double m[12];
     int on;
+};
+
+struct preload_poses {                                       // one transform per frame record, on the device
+    const double* poses;
+    int row_floats;
 };
 
 // the record of workgroup (COL 4) or box (COL 2) `x`: the last f with frames[f][COL] <= x.  Records that own nothing share
@@ -66,13 +83,48 @@ __device__ __forceinline__ int preload_frame_of(const int32_t* __restrict__ fram
     return lo;
 }
 
-template <bool SCATTER>
+// the one statement of the transform: fp64 on the float32 input, this order of operations, rounded once
+__device__ __forceinline__ void preload_apply(const double* __restrict__ m, float fx, float fy, float fz, float& px, float& py,
+                                              float& pz) {
+    const double x = fx, y = fy, z = fz;
+    px = (float)(((m[0] * x + m[1] * y) + m[2] * z) + m[3]);
+    py = (float)(((m[4] * x + m[5] * y) + m[6] * z) + m[7]);
+    pz = (float)(((m[8] * x + m[9] * y) + m[10] * z) + m[11]);
+}
+
+// point `row` of the raw table as record f sees it.  preload_xf: one transform for the call, by value, rows of four floats
+__device__ __forceinline__ void preload_point(const float* __restrict__ raw, const preload_xf T, int f, long row, float& px, float& py,
+                                              float& pz) {
+    const float4 v = reinterpret_cast<const float4*>(raw)[row];
+    if (T.on) {
+        preload_apply(T.m, v.x, v.y, v.z, px, py, pz);
+    } else {
+        px = v.x; py = v.y; pz = v.z;
+    }
+}
+
+// preload_poses: the transform of record f from the device table, rows of 3 or 4 floats
+__device__ __forceinline__ void preload_point(const float* __restrict__ raw, const preload_poses P, int f, long row, float& px,
+                                              float& py, float& pz) {
+    float x, y, z;
+    if (P.row_floats == 4) {
+        const float4 v = reinterpret_cast<const float4*>(raw)[row];
+        x = v.x; y = v.y; z = v.z;
+    } else {
+        const float* r = raw + 3 * row;
+        x = r[0]; y = r[1]; z = r[2];
+    }
+    preload_apply(P.poses + 12 * (long)f, x, y, z, px, py, pz);
+}
+
+template <bool SCATTER, class XF>
 __global__ __launch_bounds__(CROP_WG) void preload_kernel(const float* __restrict__ raw, const int32_t* __restrict__ frames, int F,
-                                                          const float* __restrict__ bounds, preload_xf T, int32_t* __restrict__ scratch,
+                                                          const float* __restrict__ bounds, XF T, int32_t* __restrict__ scratch,
                                                           const long* __restrict__ out_row, float* __restrict__ pool, long pool_rows) {
     __shared__ float bnd[CROP_MULTI_CHUNK][6];
     __shared__ int wave_cnt[CROP_MULTI_CHUNK][CROP_WG / 64];
-    const int32_t* rec = frames + PRELOAD_COLS * preload_frame_of<4>(frames, F, (int)blockIdx.x);
+    const int f = preload_frame_of<4>(frames, F, (int)blockIdx.x);
+    const int32_t* rec = frames + PRELOAD_COLS * f;
     const int row0 = rec[0], n = rec[1], b0 = rec[2], nb = rec[3], w = (int)blockIdx.x - rec[4];
     const int W = n > 0 ? (n + CROP_WG - 1) / CROP_WG : 1;
     if (nb <= 0 || w < 0 || w >= W) return;               // a device table that disagrees with the planned grid: nothing is touched
@@ -81,17 +133,7 @@ __global__ __launch_bounds__(CROP_WG) void preload_kernel(const float* __restric
     const int i = w * CROP_WG + tid;
     const bool in = i < n;
     float px = 0.f, py = 0.f, pz = 0.f;
-    if (in) {
-        const float4 v = reinterpret_cast<const float4*>(raw)[(long)row0 + i];
-        if (T.on) {
-            const double x = v.x, y = v.y, z = v.z;
-            px = (float)(((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3]);
-            py = (float)(((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7]);
-            pz = (float)(((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11]);
-        } else {
-            px = v.x; py = v.y; pz = v.z;
-        }
-    }
+    if (in) preload_point(raw, T, f, (long)row0 + i, px, py, pz);
     for (int k0 = 0; k0 < nb; k0 += CROP_MULTI_CHUNK) {
         const int nc = nb - k0 < CROP_MULTI_CHUNK ? nb - k0 : CROP_MULTI_CHUNK;
         __syncthreads();                                   // the previous chunk's readers are done with bnd / wave_cnt
@@ -162,13 +204,13 @@ static bool preload_plan(const int32_t* frames, int F, long raw_rows, bool check
 }
 
 static bool preload_args_ok(const float* raw, long raw_rows, const int32_t* frames, const int32_t* frames_dev, int F, const float* bounds,
-                            int B, const int32_t* scratch, long scratch_len, long& wgs) {
+                            int B, const int32_t* scratch, long scratch_len, long& wgs, unsigned raw_align = 16u) {
     long boxes, need;
     bool any_points;
     if (B < 0 || !preload_plan(frames, F, raw_rows, true, nullptr, wgs, boxes, need, any_points) || boxes != B) return false;
     if (wgs == 0) return true;                             // nothing to launch: no pointer is needed
     if (!frames_dev || !bounds || !scratch || scratch_len < need) return false;
-    if (any_points && (!raw || (reinterpret_cast<uintptr_t>(raw) & 15u))) return false;
+    if (any_points && (!raw || (reinterpret_cast<uintptr_t>(raw) & (raw_align - 1u)))) return false;
     return true;
 }
 
@@ -177,6 +219,12 @@ static preload_xf preload_transform(const double* transform) {
     for (int i = 0; i < 12; ++i) T.m[i] = transform ? transform[i] : 0.0;
     T.on = transform ? 1 : 0;
     return T;
+}
+
+// what the posed pair refuses beyond preload_args_ok
+static bool preload_posed_ok(int row_floats, int F, const double* poses) {
+    if (row_floats != 3 && row_floats != 4) return false;
+    return F <= 0 || (poses && !(reinterpret_cast<uintptr_t>(poses) & 7u));
 }
 
 }  // namespace
@@ -199,7 +247,7 @@ extern "C" int o3d_preload_count(const float* raw, long raw_rows, const int32_t*
     if (!preload_args_ok(raw, raw_rows, frames, frames_dev, F, bounds, B, scratch, scratch_len, wgs) || (B > 0 && !counts))
         return O3D_EINVAL;
     if (B == 0) return O3D_OK;                             // wgs == 0 as well: every workgroup belongs to a box
-    hipLaunchKernelGGL(preload_kernel<false>, dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F, bounds,
+    hipLaunchKernelGGL((preload_kernel<false, preload_xf>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F, bounds,
                        preload_transform(transform), scratch, (const long*)nullptr, (float*)nullptr, 0L);
     hipLaunchKernelGGL(preload_scan_kernel, dim3(B), dim3(CROP_WG), 0, o3d_stream(stream), frames_dev, F, scratch, counts);
     return o3d_launch_status();
@@ -213,7 +261,38 @@ extern "C" int o3d_preload_scatter(const float* raw, long raw_rows, const int32_
         (B > 0 && !out_row) || (pool_rows > 0 && !pool))
         return O3D_EINVAL;
     if (B == 0 || pool_rows == 0) return O3D_OK;
-    hipLaunchKernelGGL(preload_kernel<true>, dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F, bounds,
+    hipLaunchKernelGGL((preload_kernel<true, preload_xf>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F, bounds,
                        preload_transform(transform), scratch, out_row, pool, pool_rows);
+    return o3d_launch_status();
+}
+
+// The same launches with a pose per frame record (poses (F,12) fp64 on the device) over raw rows of row_floats = 3 | 4 floats
+extern "C" int o3d_preload_posed_count(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
+                                       int F, const float* bounds, int B, const double* poses, int32_t* scratch, long scratch_len,
+                                       int32_t* counts, void* stream) {
+    long wgs;
+    if (!preload_posed_ok(row_floats, F, poses) ||
+        !preload_args_ok(raw, raw_rows, frames, frames_dev, F, bounds, B, scratch, scratch_len, wgs, row_floats == 4 ? 16u : 4u) ||
+        (B > 0 && !counts))
+        return O3D_EINVAL;
+    if (B == 0) return O3D_OK;
+    hipLaunchKernelGGL((preload_kernel<false, preload_poses>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F,
+                       bounds, preload_poses{poses, row_floats}, scratch, (const long*)nullptr, (float*)nullptr, 0L);
+    hipLaunchKernelGGL(preload_scan_kernel, dim3(B), dim3(CROP_WG), 0, o3d_stream(stream), frames_dev, F, scratch, counts);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_preload_posed_scatter(const float* raw, long raw_rows, int row_floats, const int32_t* frames,
+                                         const int32_t* frames_dev, int F, const float* bounds, int B, const double* poses,
+                                         int32_t* scratch, long scratch_len, const long* out_row, float* pool, long pool_rows,
+                                         void* stream) {
+    long wgs;
+    if (!preload_posed_ok(row_floats, F, poses) ||
+        !preload_args_ok(raw, raw_rows, frames, frames_dev, F, bounds, B, scratch, scratch_len, wgs, row_floats == 4 ? 16u : 4u) ||
+        pool_rows < 0 || (B > 0 && !out_row) || (pool_rows > 0 && !pool))
+        return O3D_EINVAL;
+    if (B == 0 || pool_rows == 0) return O3D_OK;
+    hipLaunchKernelGGL((preload_kernel<true, preload_poses>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F,
+                       bounds, preload_poses{poses, row_floats}, scratch, out_row, pool, pool_rows);
     return o3d_launch_status();
 }

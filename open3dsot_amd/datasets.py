@@ -1,4 +1,4 @@
-"""Dataset readers that leave the frames in HBM: the KITTI tracking set as a sampler.DeviceTracklets.
+"""Dataset readers that leave the frames in HBM: the KITTI tracking set and the Waymo SOT set as sampler.DeviceTracklets.
 
 KittiTracklets mirrors the reference's kittiDataset (datasets/kitti.py) with coordinate_mode `velodyne` / `camera` and
 preload_offset: the same scene list per split string, the same tracklet list (order of first appearance of track_id in the
@@ -21,8 +21,21 @@ one cloud object; here they share one slice of the pool.
 
 save(file) / KittiTracklets.load(file) stand in for the reference's pickle cache: one file with the pool, the row offsets,
 the boxes and the meta; loading is one upload.  There is no CPU fallback: a CPU device raises.
+
+WaymoTracklets mirrors the reference's WaymoDataset with preloading (datasets/waymo_data.py): the tracklets of
+sot_infos_<category>_<split>.pkl in the dict's order, one pickle per lidar frame and one per annotation frame, every frame
+with its own vehicle-to-global pose.  The host computes poses and boxes in fp64 (waymo_annotations); the device transforms
+the (n,3) float32 rows by the pose of their frame and crops them (o3d_preload_posed_count / o3d_preload_posed_scatter), the
+fp64 result rounded to float32 once, as the reference stores it back into its float32 array.  Quirks kept: `test` reads the
+`val` files; the annotation file is the lidar file's name with EVERY `lidar` replaced by `annos`; the pose's rotation goes
+through a quaternion and back; length and width of the box are swapped; with preload_offset <= 0 nothing is cropped but the
+points are still transformed.  Two stated deviations: points_xyz must be float32 (ValueError otherwise; the reference would
+keep a float64 array unrounded); and with preload_offset <= 0 the bounds are -inf / +inf under the same strict compares, so a
+point whose transformed coordinate is NaN or infinite is dropped where the reference, which does not compare at all, keeps it.  Non-preloading access (which swaps length and width back on a second read) is not restated.
 """
+import ast
 import os
+import pickle
 
 import numpy as np
 import torch
@@ -91,6 +104,27 @@ def _quat_matrix(q):
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _quat_from_matrix(m):
+    """the unit quaternion (w, x, y, z) of the rotation matrix m[:3,:3] (Shepperd's method: the largest of the trace and the
+    diagonal picks the branch), normalised"""
+    m = np.asarray(m, np.float64)
+    t = np.trace(m[:3, :3])
+    if t > 0:
+        s = 2 * np.sqrt(1 + t)
+        q = [s / 4, (m[2, 1] - m[1, 2]) / s, (m[0, 2] - m[2, 0]) / s, (m[1, 0] - m[0, 1]) / s]
+    else:
+        i = int(np.argmax([m[0, 0], m[1, 1], m[2, 2]]))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = 2 * np.sqrt(1 + m[i, i] - m[j, j] - m[k, k])
+        q = [0.0, 0.0, 0.0, 0.0]
+        q[0] = (m[k, j] - m[j, k]) / s
+        q[1 + i] = s / 4
+        q[1 + j] = (m[j, i] + m[i, j]) / s
+        q[1 + k] = (m[k, i] + m[i, k]) / s
+    q = np.asarray(q, np.float64)
+    return q / np.linalg.norm(q)
 
 
 def kitti_box(anno, velo_to_cam, coordinate_mode):
@@ -172,10 +206,10 @@ def preload_bounds(boxes, offset):
     return out
 
 
-def _device(device):
+def _device(device, who="KittiTracklets"):
     dev = torch.device("cuda" if device is None else device)
     if dev.type != "cuda":
-        raise RuntimeError("KittiTracklets: CPU not supported (the frames live on a GPU)")
+        raise RuntimeError("%s: CPU not supported (the frames live on a GPU)" % who)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     return dev
@@ -191,49 +225,75 @@ def velodyne_rows(path):
     return floats // 4 if floats % 4 == 0 else -1
 
 
-class PreloadChunk:
-    """The device half for one chunk of raw frames: plan, upload, count, read back, scatter.  files: [(path, n rows)],
-    boxes_per_file: for each file a (k,6) float32 array of bounds (k >= 0).  The steps are separate methods so that
-    tools/preload_bench.py can time them; run() is the sequence the reader uses."""
+def copy_rows(host, rows, n):
+    """the row loader for frames that are already arrays on the host: a copy into the pinned buffer"""
+    host[:] = rows
 
-    def __init__(self, files, bounds_per_file, transform, device, pinned=None):
+
+def _read_rows(host, path, n):
+    """the default row loader: a velodyne .bin, n rows of four floats, straight into the pinned buffer"""
+    with open(path, "rb") as f:
+        got = f.readinto(host)
+    if got != 16 * n:
+        raise OSError("%s changed while it was read" % path)
+
+
+class PreloadChunk:
+    """The device half for one chunk of raw frames: plan, upload, count, read back, scatter.  files: [(source, n rows)],
+    boxes_per_file: for each file a (k,6) float32 array of bounds (k >= 0).  A raw row is row_floats = 3 | 4 floats;
+    loader(host rows (n,row_floats), source, n) fills the pinned buffer's rows of one file (default: source is the path of a
+    velodyne .bin; with poses, source is the (n,row_floats) float32 array itself: copy_rows).  transform: one (3,4) fp64 for the chunk | None; poses: one (3,4) fp64 PER FILE instead (then transform is
+    None and the launches are o3d_preload_posed_*).  The steps are separate methods so that tools/preload_bench.py can time
+    them; run() is the sequence the readers use."""
+
+    def __init__(self, files, bounds_per_file, transform, device, pinned=None, row_floats=4, loader=None, poses=None):
+        assert poses is None or (transform is None and len(poses) == len(files))
+        assert row_floats == 4 or poses is not None
         self.device, self.transform = device, transform
-        recs, row = [], 0
-        for (_, n), b in zip(files, bounds_per_file):
+        self.loader = loader if loader is not None else copy_rows if poses is not None else _read_rows
+        recs, rec_pose, row = [], [], 0
+        for i, ((_, n), b) in enumerate(zip(files, bounds_per_file)):
             for k0 in range(0, len(b), PU.PRELOAD_MAX_BOXES):       # a frame with more boxes than a record takes: more records
                 recs.append((row, n, 0, min(PU.PRELOAD_MAX_BOXES, len(b) - k0), 0, 0))
+                rec_pose.append(i)                                  # ... that carry the frame's pose each
             row += n
         self.files, self.raw_rows = files, row
         self.frames = np.array(recs, np.int32).reshape(-1, PU.PRELOAD_COLS)
         self.need, self.wgs, self.B = PU.preload_plan(self.frames, row)
         self.bounds = np.concatenate([np.asarray(b, np.float32).reshape(-1, 6) for b in bounds_per_file] + [np.zeros((0, 6), np.float32)])
         assert self.bounds.shape[0] == self.B
-        if pinned is None or pinned.shape[0] < row:
-            pinned = torch.empty((max(row, 1), 4), dtype=torch.float32).pin_memory()
+        self.poses = None if poses is None else \
+            np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12)[np.array(rec_pose, np.int64)])
+        if pinned is None or pinned.shape[0] < row or pinned.shape[1] != row_floats:
+            pinned = torch.empty((max(row, 1), row_floats), dtype=torch.float32).pin_memory()
         self.pinned = pinned
 
     def read(self):
         host, row = self.pinned.numpy(), 0
-        for path, n in self.files:
+        for source, n in self.files:
             if n > 0:
-                with open(path, "rb") as f:
-                    got = f.readinto(host[row:row + n])
-                if got != 16 * n:
-                    raise OSError("%s changed while it was read" % path)
+                self.loader(host[row:row + n], source, n)
             row += n
 
     def upload(self):
         dev = self.device
         self.raw = self.pinned[:self.raw_rows].to(dev, non_blocking=True)
-        tables = np.concatenate([self.frames.reshape(-1).view(np.uint8), self.bounds.reshape(-1).view(np.uint8)])
-        t = torch.from_numpy(tables).to(dev)
-        nf = self.frames.size * 4
-        self.dev_frames, self.dev_bounds = t[:nf].view(torch.int32), t[nf:].view(torch.float32)
+        tables = [self.frames.reshape(-1).view(np.uint8), self.bounds.reshape(-1).view(np.uint8)]
+        if self.poses is not None:                # frames and bounds are 24 bytes a row: the doubles behind them are aligned
+            tables.append(self.poses.reshape(-1).view(np.uint8))
+        t = torch.from_numpy(np.concatenate(tables)).to(dev)
+        nf, nb = self.frames.size * 4, self.bounds.size * 4
+        self.dev_frames, self.dev_bounds = t[:nf].view(torch.int32), t[nf:nf + nb].view(torch.float32)
+        self.dev_poses = None if self.poses is None else t[nf + nb:].view(torch.float64)
         self.scratch = torch.empty((self.need,), dtype=torch.int32, device=dev)
         self.counts = torch.empty((self.B,), dtype=torch.int32, device=dev)
 
     def count(self):
-        PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.counts)
+        if self.dev_poses is None:
+            PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.counts)
+        else:
+            PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.counts,
+                             poses=self.dev_poses)
 
     def read_back(self):
         """-> counts (B,) int64 on the host; allocates the chunk's pool segment and uploads every box's first row"""
@@ -244,7 +304,12 @@ class PreloadChunk:
         return counts
 
     def scatter(self):
-        PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.out_row, self.pool)
+        if self.dev_poses is None:
+            PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.out_row,
+                               self.pool)
+        else:
+            PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.out_row, self.pool,
+                               poses=self.dev_poses)
 
     def run(self):
         self.read()
@@ -255,7 +320,26 @@ class PreloadChunk:
         return counts
 
 
-class KittiTracklets(DeviceTracklets):
+class _PoolTracklets(DeviceTracklets):
+    """what the readers share: every frame is a view of ONE pool tensor, and the reference's counting accessors"""
+
+    def _assemble(self, pool, rows, boxes64, meta):
+        self.pool, self.rows, self.boxes64, self.meta = pool, rows, boxes64, meta
+        del self[:]
+        for r, b in zip(rows, boxes64):
+            self.append(DeviceTracklet([pool[int(s):int(s) + int(c)] for s, c in r], b.astype(np.float32).reshape(-1, 15)))
+
+    def get_num_tracklets(self):
+        return len(self)
+
+    def get_num_frames_total(self):
+        return sum(len(t) for t in self)
+
+    def get_num_frames_tracklet(self, tracklet_id):
+        return len(self[tracklet_id])
+
+
+class KittiTracklets(_PoolTracklets):
     """KittiTracklets(path, split, ...): the tracklets of the KITTI tracking set under `path` (velodyne/, label_02/, calib/),
     cropped as the reference preloads them, resident in HBM.  A sampler.DeviceTracklets: goes unchanged into tracking.evaluate
     and DeviceBatchSampler.  meta[k] = (scene, track_id, frame numbers); pool = the one (rows,3) tensor all frames view;
@@ -318,24 +402,9 @@ class KittiTracklets(DeviceTracklets):
         meta = [(a["scene"], a["track_id"], a["frames"]) for a in annos]
         self._assemble(pool, rows, [a["boxes"] for a in annos], meta)
 
-    def _assemble(self, pool, rows, boxes64, meta):
-        self.pool, self.rows, self.boxes64, self.meta = pool, rows, boxes64, meta
-        del self[:]
-        for r, b in zip(rows, boxes64):
-            self.append(DeviceTracklet([pool[int(s):int(s) + int(c)] for s, c in r], b.astype(np.float32).reshape(-1, 15)))
-
     # ---- the reference's accessors ------------------------------------------------------------------------------------------
     def get_num_scenes(self):
         return len(self.scene_list)
-
-    def get_num_tracklets(self):
-        return len(self)
-
-    def get_num_frames_total(self):
-        return sum(len(t) for t in self)
-
-    def get_num_frames_tracklet(self, tracklet_id):
-        return len(self[tracklet_id])
 
     def get_frames(self, seq_id, frame_ids):
         t = self[seq_id]
@@ -368,5 +437,195 @@ class KittiTracklets(DeviceTracklets):
             self.preload_offset = float(z["info"][3])
             self.path, self.scene_list = None, [str(s) for s in z["scene_list"]]
             meta = [(str(s), int(t), f) for s, t, f in zip(z["scenes"], z["track_ids"], cut(z["frames"]))]
+            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
+        return self
+
+
+# ---- Waymo --------------------------------------------------------------------------------------------------------------------
+WAYMO_TYPES = ("UNKNOWN", "VEHICLE", "PEDESTRIAN", "SIGN", "CYCLIST")
+_WAYMO_CATEGORIES = ("vehicle", "pedestrian", "cyclist")
+
+
+def _unpickle(file):
+    with open(file, "rb") as f:
+        return pickle.load(f)
+
+
+def generate_waymo_sot_infos(root, category, split):
+    """The reference's generate_waymo_data(root, cla, split) (datasets/generate_waymo_sot.py): walks
+    <root>/infos_<split>_01sweeps_filter_zero_gt.pkl, reads every frame's annotation pickle and writes
+    <root>/sot_infos_<category lower-cased>_<split>.pkl: {object name: [{'PC': the frame's lidar path, 'Box': the object's box,
+    'Class': category}]}, objects in order of first appearance, frames in the order of the infos list.  `category` is the
+    UPPER-CASE class (VEHICLE, PEDESTRIAN, CYCLIST), as the reference's __main__ passes it; the reference's own call from
+    WaymoDataset passes the lower-cased name, which matches no object and writes an empty dict.  -> the dict"""
+    data = {}
+    for frame in _unpickle(os.path.join(root, "infos_%s_01sweeps_filter_zero_gt.pkl" % split)):
+        for obj in _unpickle(os.path.join(root, frame["anno_path"]))["objects"]:
+            if WAYMO_TYPES[obj["label"]] == category:
+                data.setdefault(obj["name"], []).append({"PC": frame["path"], "Box": obj["box"], "Class": category})
+    with open(os.path.join(root, "sot_infos_%s_%s.pkl" % (category.lower(), split)), "wb") as f:
+        pickle.dump(data, f)
+    return data
+
+
+def waymo_names(split, category_name):
+    """WaymoDataset.__init__: -> (split, category) lower-cased, `test` reads `val`; anything else is an error"""
+    split, category = split.lower(), category_name.lower()
+    split = "val" if split == "test" else split
+    if split not in ("train", "val"):
+        raise ValueError("split must be train, val or test, not %r" % split)
+    if category not in _WAYMO_CATEGORIES:
+        raise ValueError("category_name must be one of VEHICLE, PEDESTRIAN, CYCLIST, not %r" % category_name)
+    return split, category
+
+
+def waymo_pose(veh_to_global):
+    """veh_pos_to_transform's global_from_car: eye(4) whose rotation is the pose's rotation taken through a quaternion and
+    back, and whose last column is the pose's translation -> (4,4) fp64"""
+    ref_pose = np.reshape(np.asarray(veh_to_global, np.float64), [4, 4])
+    tm = np.eye(4)
+    tm[:3, :3] = _quat_matrix(_quat_from_matrix(ref_pose[:3, :3]))
+    tm[:3, 3] = ref_pose[:3, 3]
+    return tm
+
+
+def waymo_box(box9, global_from_car):
+    """The box of WaymoDataset._get_frame_from_anno in fp64 -> (15,) [centre | wlh | rotation row-major].  box9: the float32
+    annotation x y z length width height vx vy heading in the vehicle frame.  Length and width change places; the orientation
+    is the pose's quaternion times the rotation about z by -heading; the centre is rotated, then translated"""
+    box9 = np.asarray(box9)
+    q_pose = _quat_from_matrix(global_from_car)
+    centre = np.dot(_quat_matrix(q_pose), box9[0:3]) + global_from_car[:3, -1]
+    rot = _quat_matrix(_quat_mul(q_pose, _quat([0, 0, 1], float(-box9[-1]))))
+    return np.concatenate([centre, box9[[4, 3, 5]], rot.reshape(-1)]).astype(np.float64)
+
+
+def _waymo_open(name, root):
+    return name if root is None or os.path.isabs(name) else os.path.join(root, name)
+
+
+def waymo_annotations(path, split, category_name="VEHICLE", tiny=False, root=None):
+    """The host half of the Waymo reader (no device): -> (tracklets, files, poses).  tracklets: a list of dicts with key (the
+    object name), files (the 'PC' strings of its frames), frames (T,) int64 (indices into `files`) and boxes (T,15) float64,
+    in the order of the sot_infos dict; files: the distinct 'PC' strings in order of first use; poses (len(files),3,4) float64:
+    the upper rows of each file's global_from_car.  Every annotation pickle is read once.  root=None opens the 'PC' strings
+    as they stand, as the reference does; otherwise relative ones are resolved against root."""
+    split, category = waymo_names(split, category_name)
+    infos_file = os.path.join(path, "sot_infos_%s_%s.pkl" % (category, split))
+    if not os.path.exists(infos_file):
+        raise FileNotFoundError("%s is missing: write it with generate_waymo_sot_infos(%r, %r, %r)"
+                                % (infos_file, path, category.upper(), split))
+    infos = _unpickle(infos_file)
+    keys = list(infos)[:100] if tiny else list(infos)
+    index, files, poses, tracklets = {}, [], [], []
+    for key in keys:
+        frames, boxes = [], []
+        for anno in infos[key]:
+            pc = anno["PC"]
+            if pc not in index:
+                index[pc] = len(files)
+                files.append(pc)
+                poses.append(waymo_pose(_unpickle(_waymo_open(pc.replace("lidar", "annos"), root))["veh_to_global"]))
+            frames.append(index[pc])
+            boxes.append(waymo_box(anno["Box"], poses[index[pc]]))
+        tracklets.append({"key": key, "files": [a["PC"] for a in infos[key]], "frames": np.array(frames, np.int64),
+                          "boxes": np.array(boxes, np.float64).reshape(-1, 15)})
+    return tracklets, files, np.array([p[:3] for p in poses], np.float64).reshape(-1, 3, 4)
+
+
+def waymo_points(file):
+    """['lidars']['points_xyz'] of a lidar pickle -> (n,3) float32, C-contiguous.  Anything but float32 raises ValueError (the
+    reference would keep a float64 array unrounded: a stated deviation)"""
+    pts = _unpickle(file)["lidars"]["points_xyz"]
+    if not isinstance(pts, np.ndarray) or pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("%s: points_xyz must be an (n,3) float32 array, not %s %s"
+                         % (file, getattr(pts, "dtype", type(pts)), getattr(pts, "shape", "")))
+    return np.ascontiguousarray(pts)
+
+
+class WaymoTracklets(_PoolTracklets):
+    """WaymoTracklets(path, split, ...): the tracklets of <path>/sot_infos_<category>_<split>.pkl, transformed to the global
+    frame and cropped as the reference's WaymoDataset preloads them, resident in HBM.  A sampler.DeviceTracklets.  meta[k] =
+    (tracklet key, the 'PC' strings of its frames); pool / rows as in KittiTracklets.  With preload_offset <= 0 nothing is
+    cropped: the transformed cloud of a frame is written once and its tracklets share the slice."""
+
+    def __init__(self, path, split, category_name="VEHICLE", preload_offset=10, tiny=False, root=None, device=None, chunk_frames=64):
+        super().__init__()
+        dev = _device(device, "WaymoTracklets")
+        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
+            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        self.path, self.preload_offset, self.tiny = path, preload_offset, bool(tiny)
+        self.split, self.category_name = waymo_names(split, category_name)
+        annos, files, poses = waymo_annotations(path, split, category_name, tiny, root)
+        users = [[] for _ in files]               # per distinct file the tracklet frames that crop it
+        for k, a in enumerate(annos):
+            for t, f in enumerate(a["frames"]):
+                users[f].append((k, t))
+        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
+        shared = preload_offset <= 0
+        segments, base, pinned, i, held = [], 0, None, 0, None
+        with torch.cuda.device(dev):
+            while i < len(files):
+                # a chunk: at most chunk_frames files, PRELOAD_MAX_FRAMES records and PRELOAD_MAX_ROWS raw rows; a file is
+                # unpickled when its chunk is formed (its n is not known before) and dropped when the chunk is done
+                chunk_files, bounds, who_of, nrows, nrec, j = [], [], [], 0, 0, i
+                while j < len(files) and j - i < chunk_frames:
+                    pts = held if held is not None else waymo_points(_waymo_open(files[j], root))
+                    held = None
+                    rec = 1 if shared else max(1, -(-len(users[j]) // PU.PRELOAD_MAX_BOXES))
+                    if j > i and (nrows + pts.shape[0] > PU.PRELOAD_MAX_ROWS or nrec + rec > PU.PRELOAD_MAX_FRAMES):
+                        held = pts                # the first file of the next chunk
+                        break
+                    chunk_files.append((pts, pts.shape[0]))
+                    if shared:
+                        bounds.append(preload_bounds(np.zeros((1, 15)), preload_offset))
+                        who_of.append([users[j]])
+                    else:
+                        bounds.append(preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in users[j]]), preload_offset))
+                        who_of.append([[u] for u in users[j]])
+                    nrows, nrec, j = nrows + pts.shape[0], nrec + rec, j + 1
+                chunk = PreloadChunk(chunk_files, bounds, None, dev, pinned, row_floats=3, poses=poses[i:j])
+                counts = chunk.run()
+                pinned, b = chunk.pinned, 0
+                for whos in who_of:
+                    for who in whos:
+                        for k, f in who:
+                            rows[k][f] = (base + chunk.first[b], counts[b])
+                        b += 1
+                segments.append(chunk.pool)
+                base += int(chunk.first[-1])
+                i = j
+            segments.append(torch.zeros((0, 3), dtype=torch.float32, device=dev))
+            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
+        self._assemble(pool, rows, [a["boxes"] for a in annos], [(a["key"], a["files"]) for a in annos])
+
+    def get_frames(self, seq_id, frame_ids):
+        t, (key, files) = self[seq_id], self.meta[seq_id]
+        return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (key, files[f])} for f in frame_ids]
+
+    # ---- the cache ----------------------------------------------------------------------------------------------------------
+    def save(self, file):
+        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
+        lengths = np.array([len(t) for t in self], np.int64)
+        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
+        arrays = dict(pool=self.pool.cpu().numpy(), lengths=lengths, rows=cat(self.rows, (0, 2), np.int64),
+                      boxes=cat(self.boxes64, (0, 15), np.float64), keys=np.array([m[0] for m in self.meta], dtype=np.str_),
+                      files=np.array([f for m in self.meta for f in m[1]], dtype=np.str_),
+                      info=np.array([self.split, self.category_name, repr(self.preload_offset), repr(self.tiny)]))
+        with open(file, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, file, device=None):
+        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
+        dev = _device(device, "WaymoTracklets")
+        self = cls.__new__(cls)
+        DeviceTracklets.__init__(self)
+        with np.load(file) as z:
+            ends = np.cumsum(z["lengths"])
+            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
+            self.split, self.category_name = (str(s) for s in z["info"][:2])
+            self.preload_offset, self.tiny, self.path = ast.literal_eval(str(z["info"][2])), str(z["info"][3]) == "True", None
+            meta = [(str(k), [str(f) for f in fs]) for k, fs in zip(z["keys"], cut(z["files"]))]
             self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
         return self

@@ -598,40 +598,53 @@ def preload_plan(frames, raw_rows):
     return need, grid[0], grid[1]
 
 
-def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch):
+def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses=None):
     _need_gpu(raw, "preload")
-    assert raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2 and raw.shape[1] == 4
+    assert raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2 and raw.shape[1] in ((4,) if poses is None else (3, 4))
     assert frames.dtype == np.int32 and frames.ndim == 2 and frames.shape[1] == PRELOAD_COLS and frames.flags.c_contiguous
     for t, dt in ((dev_frames, torch.int32), (bounds, torch.float32), (scratch, torch.int32)):
         _need_gpu(t, "preload")
         assert t.dtype == dt and t.is_contiguous() and t.device == raw.device
     assert dev_frames.numel() == frames.size and bounds.numel() % 6 == 0
+    if poses is not None:
+        _need_gpu(poses, "preload")
+        assert transform is None and poses.dtype == torch.float64 and poses.is_contiguous() and poses.device == raw.device
+        assert poses.numel() == 12 * frames.shape[0]
     if transform is not None:
         transform = np.ascontiguousarray(transform, np.float64)
         assert transform.shape == (3, 4)
     return transform
 
 
-def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts):
+def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts, poses=None):
     """One o3d_preload_count call (two launches, no sync): raw (rows,4) float32 GPU, frames = the planned (F,6) int32 table on
     the host and dev_frames its GPU copy, bounds (B,6) float32 GPU, transform = (3,4) float64 on the host | None, scratch =
-    an int32 GPU tensor of at least preload_plan's length -> counts (B,) int32 GPU, written in place"""
-    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch)
+    an int32 GPU tensor of at least preload_plan's length -> counts (B,) int32 GPU, written in place.
+    poses = (F,12) float64 GPU, one transform per frame record: o3d_preload_posed_count instead, raw (rows, 3 | 4), transform
+    None"""
+    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses)
     _need_gpu(counts, "preload_count")
     B = bounds.numel() // 6
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= B
     dev = raw.device
     with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if poses is not None:
+            capi.check(capi.load().o3d_preload_posed_count(
+                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
+                B, poses.data_ptr(), scratch.data_ptr(), scratch.numel(), counts.data_ptr(), stream), "o3d_preload_posed_count")
+            return
         capi.check(capi.load().o3d_preload_count(
             raw.data_ptr(), raw.shape[0], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
             None if transform is None else transform.ctypes.data, scratch.data_ptr(), scratch.numel(), counts.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream), "o3d_preload_count")
+            stream), "o3d_preload_count")
 
 
-def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row, pool, pool_rows=None):
+def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row, pool, pool_rows=None, poses=None):
     """One o3d_preload_scatter launch after preload_count on the same operands: out_row (B,) int64 GPU = the first pool row of
-    every box, pool (rows,3) float32 GPU, written in place; no row at or beyond pool_rows (default: all of pool) is written"""
-    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch)
+    every box, pool (rows,3) float32 GPU, written in place; no row at or beyond pool_rows (default: all of pool) is written.
+    poses: as for preload_count (o3d_preload_posed_scatter)"""
+    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses)
     _need_gpu(out_row, "preload_scatter")
     _need_gpu(pool, "preload_scatter")
     B = bounds.numel() // 6
@@ -641,10 +654,17 @@ def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row
     assert 0 <= pool_rows <= pool.shape[0]
     dev = raw.device
     with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if poses is not None:
+            capi.check(capi.load().o3d_preload_posed_scatter(
+                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
+                B, poses.data_ptr(), scratch.data_ptr(), scratch.numel(), out_row.data_ptr(), pool.data_ptr(), pool_rows, stream),
+                "o3d_preload_posed_scatter")
+            return
         capi.check(capi.load().o3d_preload_scatter(
             raw.data_ptr(), raw.shape[0], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
             None if transform is None else transform.ctypes.data, scratch.data_ptr(), scratch.numel(), out_row.data_ptr(),
-            pool.data_ptr(), pool_rows, torch.cuda.current_stream(dev).cuda_stream), "o3d_preload_scatter")
+            pool.data_ptr(), pool_rows, stream), "o3d_preload_scatter")
 
 
 def train_select(counts, B, caps, sel, n_valid, overflow):

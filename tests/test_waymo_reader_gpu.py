@@ -1,0 +1,342 @@
+"""The Waymo reader on the GPU (csrc/preload.hip, open3dsot_amd/datasets.py): the posed launches against the numpy restatement
+of the device rule (tests/waymo_oracle.py) bit for bit, against the shipped one-transform launches byte for byte, the reader
+against the reference's own WaymoDataset (tests/golden/ref_waymo.npz) bit for bit, the cache, and the reader's output through
+DeviceBatchSampler with a MotionBatchBuilder and through tracking.evaluate_sequence.  Every comparison is exact."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import fixture_io
+import kitti_oracle as KO
+import tracking_oracle as TO
+import waymo_oracle as WO
+import waymo_tree
+from waymo_oracle import cases, ref_clouds
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SENTINEL = -777.0
+INF = np.inf
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return fixture_io.load(os.path.join(ROOT, "tests", "golden", "ref_waymo.npz"))
+
+
+@pytest.fixture(scope="module")
+def tree(tmp_path_factory):
+    from open3dsot_amd import datasets as D
+    return waymo_tree.build(str(tmp_path_factory.mktemp("waymo") / "tree"), D.generate_waymo_sot_infos)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+# ---- (a) the kernels against the oracle -----------------------------------------------------------------------------------------------
+# records: (index of the raw frame, boxes).  Frames of 0, 1, 255, 256, 257 and 600 points; 0, 1, 2 and 33 boxes (33 crosses the
+# LDS chunk of O3D_CROP_MULTI_CHUNK = 32); the last two records name the same raw rows and carry the same pose
+FRAME_N = [0, 1, 255, 256, 257, 600]
+RECORDS = [(0, 1), (1, 2), (2, 0), (3, 1), (4, 33), (5, 2), (5, 2)]
+NAN_POINT = 100                                             # of the 257-point frame: its x is NaN
+
+
+def some_pose(i):
+    """a rigid pose with a translation of kilometres, another for every i"""
+    return waymo_tree.pose(i % 3, i)[:3]
+
+
+def kernel_case(row_floats):
+    """-> raw (rows,row_floats), records [(first raw row, n, boxes)], poses (F,3,4), bounds (B,6) float32"""
+    rng = np.random.default_rng(23)
+    raws = [rng.uniform(-40, 40, size=(n, row_floats)).astype(np.float32) for n in FRAME_N]
+    raws[4][NAN_POINT, 0] = np.nan
+    if row_floats == 4:
+        for r in raws:
+            r[::3, 3] = np.nan                              # the fourth float is never looked at
+    first = np.concatenate([[0], np.cumsum(FRAME_N)[:-1]])
+    records = [(int(first[f]), FRAME_N[f], k) for f, k in RECORDS]
+    poses = np.stack([some_pose(i) for i in range(len(RECORDS))])
+    poses[6] = poses[5]
+    bounds = []
+    for (f, k), T in zip(RECORDS, poses):
+        c = T[:, 3]                                         # the vehicle's place: the points lie within 60 m of it
+        b = np.concatenate([c - rng.uniform(0, 45, size=(k, 3)), c + rng.uniform(0, 45, size=(k, 3))], 1).astype(np.float32)
+        bounds.append(b)
+    bounds[1][1] = [-INF] * 3 + [INF] * 3                   # the frame of one point keeps it
+    p = KO.transform(raws[4], poses[4])                     # the 257-point frame, 33 boxes
+    bounds[4][0] = [-INF] * 3 + [INF] * 3                   # keeps every point but the NaN one: survivors in two workgroups
+    bounds[4][1] = [p[5, 0], -INF, p[9, 2], INF, INF, INF]  # lo equal to a coordinate of points 5 (x) and 9 (z)
+    bounds[4][32] = [-INF, -INF, -INF, p[7, 0], p[8, 1], INF]         # beyond the chunk: hi equal to a coordinate of points 7, 8
+    bounds[5][0] = [0, 0, 0, 1, 1, 1]                       # kilometres away: keeps nothing
+    bounds[6][0] = bounds[5][1]                             # the same rows, pose and bounds as a box of the record before
+    bounds[6][1] = [-INF] * 3 + [INF] * 3                   # 600 points, all kept
+    return np.concatenate(raws), records, poses, np.concatenate(bounds)
+
+
+def device_tables(dev, records):
+    from open3dsot_amd import points_utils as PU
+    frames = np.zeros((len(records), PU.PRELOAD_COLS), np.int32)
+    frames[:, 0], frames[:, 1], frames[:, 3] = [r[0] for r in records], [r[1] for r in records], [r[2] for r in records]
+    need, wgs, B = PU.preload_plan(frames, sum(FRAME_N))
+    return frames, torch.from_numpy(frames).to(dev), need, B
+
+
+@pytest.mark.parametrize("row_floats", [3, 4])
+def test_posed_kernels_equal_the_oracle_bit_for_bit(dev, row_floats):
+    from open3dsot_amd import points_utils as PU
+    raw_h, records, poses_h, bounds_h = kernel_case(row_floats)
+    want = WO.crop_posed(raw_h, row_floats, records, bounds_h, poses_h)
+    B = len(want)
+    assert B == sum(k for _, k in RECORDS) == 41
+    b4 = 1 + 2 + 0 + 1                                      # the first box of the 33-box record
+    p = KO.transform(raw_h[sum(FRAME_N[:4]):sum(FRAME_N[:5]), :3], poses_h[4])
+    assert np.isnan(p[NAN_POINT]).all() and want[b4].shape[0] == 256        # the +-inf box: everything but the NaN point
+    for i, box in ((5, want[b4 + 1]), (9, want[b4 + 1]), (7, want[b4 + 32]), (8, want[b4 + 32])):
+        assert not (bits(box) == bits(p[i])).all(1).any()   # strict compares: a coordinate equal to a bound is out
+    assert 0 < want[b4 + 1].shape[0] < 256 and 0 < want[b4 + 32].shape[0] < 256
+    assert want[0].shape[0] == 0 and want[2].shape[0] == 1 and want[b4 + 33].shape[0] == 0 and want[B - 1].shape[0] == 600
+    assert want[B - 2].shape[0] > 0 and np.array_equal(bits(want[b4 + 34]), bits(want[B - 2]))      # two records, one frame
+    frames, dev_frames, need, nb = device_tables(dev, records)
+    assert nb == B
+    assert (list(frames[:, 2]), list(frames[:, 4]), list(frames[:, 5]), need) == KO.plan([r[1] for r in records], [r[2] for r in records])[:4]
+    raw = torch.from_numpy(raw_h).to(dev)
+    dev_bounds = torch.from_numpy(bounds_h).to(dev)
+    dev_poses = torch.from_numpy(poses_h.reshape(-1, 12)).to(dev)
+    scratch = torch.full((need + 8,), -1, dtype=torch.int32, device=dev)
+    counts = torch.full((B + 4,), -5, dtype=torch.int32, device=dev)
+    PU.preload_count(raw, frames, dev_frames, dev_bounds, None, scratch[:need], counts[:B], poses=dev_poses)
+    got_counts = counts.cpu().numpy()
+    assert list(got_counts[:B]) == [w.shape[0] for w in want] and (got_counts[B:] == -5).all()
+    assert (scratch[need:].cpu().numpy() == -1).all()
+    # every box's slice three rows after the one before; one box (with survivors) is sent nowhere: out_row = -1
+    skipped = b4 + 2
+    assert want[skipped].shape[0] > 0 and want[-1].shape[0] > 0
+    first = np.cumsum([3] + [w.shape[0] + 3 for w in want[:-1]]).astype(np.int64)
+    rows = int(first[-1]) + want[-1].shape[0]
+    first[skipped] = -1
+    out_row = torch.from_numpy(first).to(dev)
+    for short in (0, 1):                                    # the pool as planned, then one row short of the need
+        pool = torch.full((rows + 8, 3), SENTINEL, dtype=torch.float32, device=dev)     # 8 guard rows behind pool_rows
+        PU.preload_scatter(raw, frames, dev_frames, dev_bounds, None, scratch[:need], out_row, pool, pool_rows=rows - short,
+                           poses=dev_poses)
+        got = pool.cpu().numpy()
+        expect = np.full((rows + 8, 3), SENTINEL, np.float32)
+        for b, (f, w) in enumerate(zip(first, want)):
+            if b != skipped:
+                expect[f:f + w.shape[0]] = w
+        if short:
+            expect[rows - 1] = SENTINEL                     # the last survivor of the last box: not written
+        assert np.array_equal(bits(got), bits(expect)), (row_floats, short)
+
+
+def test_rows_of_three_floats_need_four_byte_alignment_only(dev):
+    """a raw table that starts one float into a device buffer (4-byte aligned, not 16): row_floats 3 is served, and equals the
+    oracle; row_floats 4 at such an address is refused"""
+    from open3dsot_amd import capi, points_utils as PU
+    raw_h, records, poses_h, bounds_h = kernel_case(3)
+    want = WO.crop_posed(raw_h, 3, records, bounds_h, poses_h)
+    B = len(want)
+    frames, dev_frames, need, _ = device_tables(dev, records)
+    buf = torch.full((raw_h.size + 8,), SENTINEL, dtype=torch.float32, device=dev)
+    raw = buf[1:1 + raw_h.size].view(-1, 3)
+    raw.copy_(torch.from_numpy(raw_h))
+    assert raw.data_ptr() % 16 == 4 and raw.is_contiguous()
+    dev_bounds = torch.from_numpy(bounds_h).to(dev)
+    dev_poses = torch.from_numpy(poses_h.reshape(-1, 12)).to(dev)
+    scratch = torch.empty((need,), dtype=torch.int32, device=dev)
+    counts = torch.full((B,), -5, dtype=torch.int32, device=dev)
+    PU.preload_count(raw, frames, dev_frames, dev_bounds, None, scratch, counts, poses=dev_poses)
+    n = counts.cpu().numpy().astype(np.int64)
+    assert list(n) == [w.shape[0] for w in want]
+    out_row = torch.from_numpy(np.concatenate([[0], np.cumsum(n)[:-1]])).to(dev)
+    pool = torch.full((int(n.sum()) + 2, 3), SENTINEL, dtype=torch.float32, device=dev)
+    PU.preload_scatter(raw, frames, dev_frames, dev_bounds, None, scratch, out_row, pool, pool_rows=int(n.sum()), poses=dev_poses)
+    expect = np.concatenate(want + [np.full((2, 3), SENTINEL, np.float32)])
+    assert np.array_equal(bits(pool.cpu().numpy()), bits(expect))
+    assert (buf[:1].cpu().numpy() == SENTINEL).all() and (buf[1 + raw_h.size:].cpu().numpy() == SENTINEL).all()
+    # the same address as rows of four floats: refused before any launch (raw_rows chosen so that the table still fits)
+    rows4 = (raw_h.size // 4)
+    f4 = np.zeros((1, PU.PRELOAD_COLS), np.int32)
+    f4[0, 1], f4[0, 3] = rows4, 1
+    need4, _, _ = PU.preload_plan(f4, rows4)
+    rc = capi.load().o3d_preload_posed_count(raw.data_ptr(), rows4, 4, f4.ctypes.data, dev_frames.data_ptr(), 1, dev_bounds.data_ptr(), 1,
+                                             dev_poses.data_ptr(), scratch.data_ptr(), scratch.numel(), counts.data_ptr(), None)
+    assert rc == capi.CONSTANTS["O3D_EINVAL"] and need4 <= scratch.numel()
+
+
+def test_posed_launches_equal_the_shipped_launches_byte_for_byte(dev):
+    """row_floats 4 with every pose equal to T gives the scratch, counts and pool of o3d_preload_count / o3d_preload_scatter
+    with transform T; identity poses give those of the call without a transform"""
+    from open3dsot_amd import points_utils as PU
+    raw_h, records, _, _ = kernel_case(4)
+    raw_h = np.nan_to_num(raw_h, nan=0.5)                   # no NaN here: the pools are compared whole
+    rng = np.random.default_rng(5)
+    frames, dev_frames, need, B = device_tables(dev, records)
+    raw = torch.from_numpy(raw_h).to(dev)
+    camera = np.array([[0.02, -0.999, 0.01, -0.004], [0.01, 0.03, -0.9995, -0.076], [0.9997, 0.02, 0.01, -0.27]], np.float64)
+    identity = np.hstack([np.eye(3), np.zeros((3, 1))])
+    for T, shipped_T in ((camera, camera), (waymo_tree.pose(1, 2)[:3], waymo_tree.pose(1, 2)[:3]), (identity, None)):
+        c = T[:, 3]
+        bounds_h = np.concatenate([c - rng.uniform(0, 45, size=(B, 3)), c + rng.uniform(0, 45, size=(B, 3))], 1).astype(np.float32)
+        bounds_h[7] = [-INF] * 3 + [INF] * 3
+        dev_bounds = torch.from_numpy(bounds_h).to(dev)
+        dev_poses = torch.from_numpy(np.tile(T.reshape(1, 12), (len(records), 1))).to(dev)
+        out = []
+        for posed in (False, True):
+            kw = dict(poses=dev_poses) if posed else {}
+            scratch = torch.full((need,), -1, dtype=torch.int32, device=dev)
+            counts = torch.full((B,), -5, dtype=torch.int32, device=dev)
+            PU.preload_count(raw, frames, dev_frames, dev_bounds, None if posed else shipped_T, scratch, counts, **kw)
+            n = counts.cpu().numpy().astype(np.int64)
+            out_row = torch.from_numpy(np.concatenate([[0], np.cumsum(n)[:-1]])).to(dev)
+            pool = torch.full((int(n.sum()) + 2, 3), SENTINEL, dtype=torch.float32, device=dev)
+            PU.preload_scatter(raw, frames, dev_frames, dev_bounds, None if posed else shipped_T, scratch, out_row, pool,
+                               pool_rows=int(n.sum()), **kw)
+            out.append((n, scratch.cpu().numpy(), pool.cpu().numpy()))
+        (n0, s0, p0), (n1, s1, p1) = out
+        assert n0.sum() > 1000 and np.array_equal(n0, n1) and np.array_equal(s0, s1)
+        assert p0.tobytes() == p1.tobytes()
+
+
+def test_empty_posed_calls_launch_nothing_and_succeed(dev):
+    from open3dsot_amd import points_utils as PU
+    z32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)      # noqa: E731
+    zf = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)      # noqa: E731
+    for n in ([], [0, 7]):                                  # no frame; frames without a box
+        frames = np.zeros((len(n), PU.PRELOAD_COLS), np.int32)
+        frames[:, 1] = n
+        frames[:, 0] = np.concatenate([[0], np.cumsum(n)[:-1]]) if n else []
+        assert PU.preload_plan(frames, sum(n)) == (0, 0, 0)
+        pool = torch.full((4, 3), SENTINEL, device=dev)
+        poses = torch.zeros((len(n), 12), dtype=torch.float64, device=dev)
+        PU.preload_count(zf(sum(n), 3), frames, z32(frames.size), zf(0, 6), None, z32(0), z32(0), poses=poses)
+        PU.preload_scatter(zf(sum(n), 3), frames, z32(frames.size), zf(0, 6), None, z32(0), torch.zeros(0, dtype=torch.int64, device=dev),
+                           pool, poses=poses)
+        assert (pool.cpu().numpy() == SENTINEL).all()
+
+
+# ---- (b) the reader against the reference ---------------------------------------------------------------------------------------------
+def check_against_ref(trk, ref, name, tree):
+    want = ref_clouds(ref, name)
+    assert [len(t) for t in trk] == list(ref[name + ".lengths"])
+    assert trk.get_num_tracklets() == len(want) and trk.get_num_frames_total() == sum(len(w) for w in want)
+    boxes = np.concatenate([t.boxes for t in trk])
+    assert boxes.dtype == np.float32 and np.array_equal(boxes, ref[name + ".boxes"].astype(np.float32))
+    assert np.concatenate(trk.boxes64).tobytes() == ref[name + ".boxes"].tobytes()
+    assert [m[0] for m in trk.meta] == [str(k) for k in ref[name + ".keys"]]
+    files = [f for m in trk.meta for f in m[1]]
+    assert [os.path.relpath(f, tree) if os.path.isabs(f) else f for f in files] == [str(f) for f in ref[name + ".files"]]
+    lo, hi = trk.pool.data_ptr(), trk.pool.data_ptr() + trk.pool.numel() * 4
+    store = trk.pool.untyped_storage().data_ptr()
+    for k, (t, w) in enumerate(zip(trk, want)):
+        assert trk.get_num_frames_tracklet(k) == len(w)
+        for f, (g, c) in enumerate(zip(t.frames, w)):
+            assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == c.shape, (name, k, f)
+            assert np.array_equal(bits(g.cpu().numpy()), bits(c)), (name, k, f)
+            assert g.untyped_storage().data_ptr() == store                    # a view of the pool: nothing was copied
+            if g.numel():
+                assert lo <= g.data_ptr() and g.data_ptr() + g.numel() * 4 <= hi
+
+
+def test_reader_equals_the_reference_bit_for_bit(dev, ref, tree):
+    from open3dsot_amd import datasets as D
+    for name, category, offset, split, tiny in cases(ref):
+        for chunk in (1, 64):
+            trk = D.WaymoTracklets(tree, split, category, preload_offset=offset, tiny=tiny, device=dev, chunk_frames=chunk)
+            check_against_ref(trk, ref, name, tree)
+            if offset <= 0:                                  # no crop: a frame's cloud is written once, its tracklets share it
+                assert trk.pool.shape[0] == sum({f: c.shape[0] for t, w in zip(trk.meta, ref_clouds(ref, name))
+                                                 for f, c in zip(t[1], w)}.values())
+    trk = D.WaymoTracklets(tree, "train", "VEHICLE", device=dev)
+    assert trk.preload_offset == 10 and (trk.split, trk.category_name) == ("train", "vehicle")
+    assert trk[0].frames[0].data_ptr() != trk[1].frames[0].data_ptr()       # cropped: a slice per tracklet frame
+    shared = D.WaymoTracklets(tree, "train", "VEHICLE", preload_offset=-1, device=dev)
+    assert shared[0].frames[0].data_ptr() == shared[1].frames[0].data_ptr()
+    fr = trk.get_frames(0, [0, 1])
+    assert len(fr) == 2 and fr[1]["pc"] is trk[0].frames[1] and fr[1]["3d_bbox"].shape == (15,)
+    assert fr[1]["meta"] == ("s0_veh_a", trk.meta[0][1][1])
+    assert (D.WaymoTracklets(tree, "TEST", "Vehicle", tiny=True, device=dev).get_num_tracklets()) == 100
+    with pytest.raises(ValueError):
+        D.WaymoTracklets(tree, "train", device=dev, chunk_frames=0)
+
+
+def test_every_lidar_file_is_read_once(dev, tree, monkeypatch):
+    """several tracklets share frames: each distinct 'PC' file is unpickled once, whatever the chunking and the crop"""
+    from open3dsot_amd import datasets as D
+    real = D.waymo_points
+    for offset, chunk in ((10, 1), (10, 4), (-1, 64)):
+        opened = []
+        monkeypatch.setattr(D, "waymo_points", lambda f: (opened.append(f), real(f))[1])
+        trk = D.WaymoTracklets(tree, "train", "VEHICLE", preload_offset=offset, device=dev, chunk_frames=chunk)
+        files = [f for m in trk.meta for f in m[1]]
+        assert len(files) == 22 and len(opened) == 11 and sorted(opened) == sorted(set(files))
+
+
+def test_reader_resolves_relative_paths_against_root(dev, ref, tmp_path):
+    from open3dsot_amd import datasets as D
+    rel = waymo_tree.build(str(tmp_path / "rel"), D.generate_waymo_sot_infos, absolute=False)
+    check_against_ref(D.WaymoTracklets(rel, "train", "CYCLIST", root=rel, device=dev), ref, "CYCLIST.10.train", rel)
+
+
+def test_cache_round_trip(dev, ref, tree, tmp_path):
+    from open3dsot_amd import datasets as D
+    name = "PEDESTRIAN.10.train"
+    a = D.WaymoTracklets(tree, "train", "PEDESTRIAN", preload_offset=10, device=dev)
+    file = str(tmp_path / "cache.dat")
+    a.save(file)
+    assert os.path.exists(file)                              # the name as given
+    b = D.WaymoTracklets.load(file, device=dev)
+    check_against_ref(b, ref, name, tree)
+    assert (b.split, b.category_name, b.preload_offset, b.tiny) == ("train", "pedestrian", 10, False)
+    assert type(b.preload_offset) is int                     # the offset comes back as it was given
+    assert np.array_equal(bits(a.pool.cpu().numpy()), bits(b.pool.cpu().numpy()))
+    for x, y in zip(a.boxes64, b.boxes64):
+        assert np.array_equal(x, y)
+    assert b.meta == a.meta
+
+
+# ---- (c) plumbing ---------------------------------------------------------------------------------------------------------------------
+def test_the_motion_batch_sampler_takes_the_reader(dev, ref, tree):
+    """DeviceBatchSampler with a MotionBatchBuilder over the reader's tracklets yields the batch that the fixture's clouds,
+    uploaded by hand, yield"""
+    from open3dsot_amd import datasets as D, sampler as S
+    name = "VEHICLE.10.train"
+    trk = D.WaymoTracklets(tree, "train", "VEHICLE", preload_offset=10, device=dev)
+    clouds = ref_clouds(ref, name)
+    ends = np.cumsum(ref[name + ".lengths"])
+    boxes = np.split(ref[name + ".boxes"].astype(np.float32), ends[:-1])
+    by_hand = S.DeviceTracklets([[torch.from_numpy(c.copy()) for c in w] for w in clouds], boxes, device=dev)
+    batches = []
+    for tracklets in (trk[:1], by_hand[:1]):                 # one tracklet: s0_veh_a, every frame of sequence 0
+        it = iter(S.DeviceBatchSampler(tracklets, S.MotionBatchBuilder({}, 4, seed=3), seed=3))
+        batches.append({k: v.clone() if torch.is_tensor(v) else v for k, v in next(it).items()})
+    a, b = batches
+    assert set(a) == set(b) and len(a) >= 5 and int(a["n_valid"]) >= 1
+    for k in a:
+        if torch.is_tensor(a[k]):
+            assert a[k].shape == b[k].shape and torch.equal(a[k].cpu().view(torch.uint8), b[k].cpu().view(torch.uint8)), k
+        else:
+            assert a[k] == b[k], k
+
+
+def test_evaluate_sequence_takes_a_tracklet_of_the_reader(dev, tree):
+    """the tracklet with a (0,3) frame (the frame of 0 points), in global coordinates of kilometres: finite boxes come back"""
+    from open3dsot_amd import datasets as D, tracking, trackers
+    trk = D.WaymoTracklets(tree, "train", "VEHICLE", preload_offset=10, device=dev)
+    t = trk[0]
+    assert len(t) == 6 and t.frames[4].shape[0] == 0 and t.frames[0].shape[0] > 20
+    cfg = dict(trackers.BAT_CAR)
+    cfg.update(TO.TEST_KEYS)
+    model = TO.init_weights(trackers.get_model("BAT")(trackers.make_config(cfg))).to(dev).eval()
+    ious, distances, results = tracking.evaluate_sequence(model, t.frames, t.boxes)
+    assert tuple(results.shape) == (len(t), 15) and torch.isfinite(results).all()
+    assert torch.isfinite(ious).all() and torch.isfinite(distances).all()

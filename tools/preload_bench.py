@@ -1,8 +1,8 @@
-"""What reading a KITTI tree into HBM costs with the device-side preload crop (open3dsot_amd/datasets.py, csrc/preload.hip),
+"""What reading a KITTI or a Waymo tree into HBM costs with the device-side preload crop (open3dsot_amd/datasets.py, csrc/preload.hip),
 against the host preload restated in numpy.  Not bench.py: that measures the training step on resident batches.
 
-  python tools/preload_bench.py [--scenes 2] [--frames 50] [--points 120000] [--tracklets 8] [--offset 10] [--runs 7]
-                                [--chunk-frames 64] [--mode velodyne|camera] [--host-only]
+  python tools/preload_bench.py [--dataset kitti|waymo] [--scenes 2] [--frames 50] [--points 120000] [--tracklets 8]
+                                [--offset 10] [--runs 7] [--chunk-frames 64] [--mode velodyne|camera] [--host-only]
 
 Setup: a synthetic tree in a temporary directory -- `--scenes` scenes (0019, 0020: the split `test`) of `--frames`
 velodyne files of `--points` points (uniform in 80 m x 80 m x 4 m), `--tracklets` Car tracklets per scene annotated in every
@@ -17,6 +17,13 @@ of `--runs` runs with the smallest and the largest, one JSON line at the end:
                       axis-aligned crop per annotated object per frame, float32 coordinates against fp64 bounds) -- NOT the
                       reference itself, which also builds a pandas frame and Box / PointCloud objects per annotation
 The clouds of the restatement and of the reader are compared bit for bit before the result is printed.
+
+--dataset waymo: the tree is `--scenes` sequences of `--frames` lidar and annotation pickles ((n,3) float32 points, a pose of
+kilometres per frame), `--tracklets` VEHICLE objects per sequence annotated in every frame; the reader is WaymoTracklets, the
+launches are the posed pair (a pose per frame record, rows of three floats), and read_s is the unpickling plus the copy
+into the pinned buffer (the bounds and the plan are outside it, as for KITTI).  The yardstick transforms with numpy's `dot`, as the reference does; the bit-for-bit comparison is
+against the same restatement with the ordered fp64 sum (BLAS may sum in another order, which reaches a float32 coordinate only
+at a rounding boundary), and `dot_clouds_differing` counts the clouds where the two restatements differ.
 """
 import argparse
 import json
@@ -88,6 +95,145 @@ def host_preload(D, root, split, mode, offset):
     return out
 
 
+def write_waymo_tree(D, root, scenes, frames, points, tracklets, seed=0):
+    import pickle
+    rng = np.random.default_rng(seed)
+    for sub in ("lidar", "annos"):
+        os.makedirs(os.path.join(root, "train", sub), exist_ok=True)
+    infos = []
+    for s in range(scenes):
+        start = rng.uniform([-25.0, -25.0, -1.0], [25.0, 25.0, -0.6], size=(tracklets, 3))
+        speed = rng.uniform(-0.3, 0.3, size=(tracklets, 3)) * [1.0, 1.0, 0.0]
+        for frame in range(frames):
+            yaw, pitch = 0.5 + s + 0.01 * frame, 0.02
+            T = np.eye(4)
+            T[:3, :3] = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]]) @ \
+                np.array([[np.cos(pitch), 0.0, np.sin(pitch)], [0.0, 1.0, 0.0], [-np.sin(pitch), 0.0, np.cos(pitch)]])
+            T[:3, 3] = [2913.37 + 5000.0 * s + 1.5 * frame, -17842.61 - 0.8 * frame, 120.5]
+            objects = [{"name": "s%d_%d" % (s, k), "label": 1,
+                        "box": np.array(list(start[k] + frame * speed[k]) + [3.9, 1.6, 1.5, 0.0, 0.0, 0.2 * k + 0.01 * frame], np.float32)}
+                       for k in range(tracklets)]
+            name = "seq_%d_frame_%d.pkl" % (s, frame)
+            pts = rng.uniform([-40.0, -40.0, -2.5], [40.0, 40.0, 1.5], size=(points, 3)).astype(np.float32)
+            with open(os.path.join(root, "train", "lidar", name), "wb") as f:
+                pickle.dump({"lidars": {"points_xyz": pts}}, f, protocol=4)
+            with open(os.path.join(root, "train", "annos", name), "wb") as f:
+                pickle.dump({"veh_to_global": T.reshape(-1), "objects": objects}, f, protocol=4)
+            infos.append({"path": os.path.join(root, "train", "lidar", name), "anno_path": os.path.join("train", "annos", name)})
+    with open(os.path.join(root, "infos_train_01sweeps_filter_zero_gt.pkl"), "wb") as f:
+        pickle.dump(infos, f, protocol=4)
+    D.generate_waymo_sot_infos(root, "VEHICLE", "train")
+    return "train"
+
+
+def host_preload_waymo(D, root, split, offset, ordered=False):
+    """the host preload of WaymoDataset in numpy: -> a list (per tracklet) of lists of (3,n) float32"""
+    annos, files, poses = D.waymo_annotations(root, split, "VEHICLE")
+    cache, out = {}, []
+    signs = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
+    for a in annos:
+        clouds = []
+        for f, box in zip(a["frames"], a["boxes"]):
+            if f not in cache:
+                pc = D.waymo_points(files[f]).transpose((1, 0)).copy()
+                if ordered:
+                    x, y, z = (pc[i].astype(np.float64) for i in range(3))
+                    T = poses[f]
+                    for i in range(3):
+                        pc[i] = ((T[i, 0] * x + T[i, 1] * y) + T[i, 2] * z) + T[i, 3]
+                else:
+                    pc[:3] = poses[f].dot(np.vstack((pc, np.ones(pc.shape[1]))))
+                cache[f] = pc
+            pc = cache[f]
+            if offset > 0:
+                w, l, h = box[3:6]
+                corners = box[6:15].reshape(3, 3) @ (signs * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
+                hi, lo = corners.max(1) + offset, corners.min(1) - offset
+                keep = (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])
+                pc = pc[:, keep]
+            clouds.append(pc)
+        out.append(clouds)
+    return out
+
+
+def main_waymo(args, torch, D):
+    with tempfile.TemporaryDirectory() as root:
+        split = write_waymo_tree(D, root, args.scenes, args.frames, args.points, args.tracklets)
+        host = host_preload_waymo(D, root, split, args.offset, ordered=True)       # reads every file once: the page cache is warm
+        by_dot = host_preload_waymo(D, root, split, args.offset)
+        differing = sum(a.tobytes() != b.tobytes() for x, y in zip(host, by_dot) for a, b in zip(x, y))
+        del by_dot
+        host_s = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            host_preload_waymo(D, root, split, args.offset)
+            host_s.append(time.perf_counter() - t0)
+        res = {"tool": "preload_bench", "dataset": "waymo", "scenes": args.scenes, "frames": args.frames, "points": args.points,
+               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, "crops": sum(len(c) for c in host),
+               "dot_clouds_differing": differing, "host_numpy_s": stat(host_s)}
+        if args.host_only:
+            print(json.dumps(res))
+            return
+        dev = torch.device("cuda", 0)
+        kw = dict(category_name="VEHICLE", preload_offset=args.offset, device=dev, chunk_frames=args.chunk_frames)
+        trk = D.WaymoTracklets(root, split, **kw)                           # warm-up: code objects, the allocator, pinned memory
+        torch.cuda.synchronize(dev)
+        for t, h in zip(trk, host):                                         # faster and different is not faster
+            for g, c in zip(t.frames, h):
+                c = np.ascontiguousarray(c.T, np.float32)
+                assert tuple(g.shape) == c.shape and np.array_equal(g.cpu().numpy().view(np.int32), c.view(np.int32))
+        reader_s = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            trk = D.WaymoTracklets(root, split, **kw)
+            torch.cuda.synchronize(dev)
+            reader_s.append(time.perf_counter() - t0)
+        # the split: the same chunks, step by step
+        annos, files, poses = D.waymo_annotations(root, split, "VEHICLE")
+        per_file = [[] for _ in files]
+        for a in annos:
+            for f, box in zip(a["frames"], a["boxes"]):
+                per_file[f].append(box)
+        chunks = [range(i, min(i + args.chunk_frames, len(files))) for i in range(0, len(files), args.chunk_frames)]
+        read_s, upload_ms, count_ms, scatter_ms, raw_bytes, pool_bytes = [], [], [], [], 0, 0
+        ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
+        for run in range(args.runs + 1):                                    # run 0 warms up
+            tot = {"read": 0.0, "upload": 0.0, "count": 0.0, "scatter": 0.0}
+            raw_bytes = pool_bytes = 0
+            pinned = None
+            for ck in chunks:
+                bounds = [D.preload_bounds(np.stack(per_file[f]), args.offset) for f in ck]
+                t0 = time.perf_counter()
+                rows = [D.waymo_points(files[f]) for f in ck]               # the file reads: unpickling ...
+                tot["read"] += time.perf_counter() - t0
+                c = D.PreloadChunk([(r, r.shape[0]) for r in rows], bounds, None, dev, pinned, row_floats=3, poses=poses[ck.start:ck.stop])
+                pinned = c.pinned
+                t0 = time.perf_counter()
+                c.read()                                                    # ... and the copy into the pinned buffer
+                tot["read"] += time.perf_counter() - t0
+                e = [ev() for _ in range(5)]
+                with torch.cuda.device(dev):
+                    e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
+                    c.read_back()
+                    e[3].record(); c.scatter(); e[4].record()
+                torch.cuda.synchronize(dev)
+                tot["upload"] += e[0].elapsed_time(e[1])
+                tot["count"] += e[1].elapsed_time(e[2])
+                tot["scatter"] += e[3].elapsed_time(e[4])
+                raw_bytes += 12 * c.raw_rows
+                pool_bytes += 12 * c.pool.shape[0]
+            if run:
+                read_s.append(tot["read"]); upload_ms.append(tot["upload"]); count_ms.append(tot["count"]); scatter_ms.append(tot["scatter"])
+        launch_ms = [a + b for a, b in zip(count_ms, scatter_ms)]
+        moved = 2 * raw_bytes + pool_bytes
+        res.update(reader_s=stat(reader_s), read_s=stat(read_s), upload_ms=stat(upload_ms), count_ms=stat(count_ms),
+                   scatter_ms=stat(scatter_ms), raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
+                   launch_GBps=stat([moved / (ms * 1e-3) / 1e9 for ms in launch_ms]),
+                   upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in upload_ms]), chunks=len(chunks),
+                   host_over_reader=statistics.median(host_s) / statistics.median(reader_s))
+        print(json.dumps(res))
+
+
 def stat(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": len(xs)}
 
@@ -99,6 +245,7 @@ def main():
     ap.add_argument("--offset", type=float, default=10.0)
     ap.add_argument("--scenes", type=int, choices=(1, 2), default=2)
     ap.add_argument("--mode", choices=("velodyne", "camera"), default="velodyne")
+    ap.add_argument("--dataset", choices=("kitti", "waymo"), default="kitti")
     ap.add_argument("--host-only", action="store_true", help="write the tree and time the numpy restatement only (no device)")
     args = ap.parse_args()
     assert args.runs >= 7 or args.host_only, "a median of at least 7 runs"
@@ -106,6 +253,8 @@ def main():
     from open3dsot_amd import datasets as D
     if not args.host_only and not torch.cuda.is_available():
         raise SystemExit("preload_bench needs a GPU: the reader cannot be measured on the host")
+    if args.dataset == "waymo":
+        return main_waymo(args, torch, D)
     with tempfile.TemporaryDirectory() as root:
         split = write_tree(root, args.scenes, args.frames, args.points, args.tracklets)
         host = host_preload(D, root, split, args.mode, args.offset)          # reads every file once: the page cache is warm

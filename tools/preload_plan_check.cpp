@@ -45,6 +45,21 @@ int main() {
         CHECK(o3d_preload_scatter(word, row, t.data(), iw, F, word, B, nullptr, iw, need, nullptr, word, 1, nullptr) == O3D_EINVAL);
         CHECK(o3d_preload_scatter(word, row, t.data(), iw, F, word, B, nullptr, iw, need, (const long*)word, nullptr, 1, nullptr) == O3D_EINVAL);
         CHECK(o3d_preload_scatter(word, row, t.data(), iw, F, word, B, nullptr, iw, need, (const long*)word, word, -1, nullptr) == O3D_EINVAL);
+        // the posed pair: the same refusals, and its own (row_floats, the poses)
+        const double* dp = reinterpret_cast<const double*>(word);
+        for (int rf : {3, 4}) {
+            CHECK(o3d_preload_posed_count(word, row, rf, t.data(), nullptr, F, word, B, dp, iw, need, iw, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_count(word, row, rf, t.data(), iw, F, word, B, dp, iw, need - 1, iw, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_count(word, row, rf, t.data(), iw, F, word, B + 1, dp, iw, need, iw, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_count(word, row, rf, t.data(), iw, F, word, B, nullptr, iw, need, iw, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_count(word, row, rf, t.data(), iw, F, word, B, (const double*)(word + 1), iw, need, iw, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_scatter(word, row, rf, t.data(), iw, F, word, B, dp, iw, need, nullptr, word, 1, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_scatter(word, row, rf, t.data(), iw, F, word, B, dp, iw, need, (const long*)word, word, -1, nullptr) == O3D_EINVAL);
+            CHECK(o3d_preload_posed_scatter(word, row, rf, t.data(), iw, F, word, B, nullptr, iw, need, (const long*)word, word, 1, nullptr) == O3D_EINVAL);
+        }
+        CHECK(o3d_preload_posed_count(word + 1, row, 4, t.data(), iw, F, word, B, dp, iw, need, iw, nullptr) == O3D_EINVAL);
+        for (int rf : {-1, 0, 2, 5})
+            CHECK(o3d_preload_posed_count(word, row, rf, t.data(), iw, F, word, B, dp, iw, need, iw, nullptr) == O3D_EINVAL);
         if (row > 0) CHECK(o3d_preload_count(word, row - 1, t.data(), iw, F, word, B, nullptr, iw, need, iw, nullptr) == O3D_EINVAL);
         t[6 * (F - 1) + 5] += 1;
         CHECK(o3d_preload_count(word, row, t.data(), iw, F, word, B, nullptr, iw, need + 1, iw, nullptr) == O3D_EINVAL);
@@ -61,6 +76,9 @@ int main() {
     CHECK(o3d_preload_scratch(one.data(), 1, 3, nullptr) == -1);
     CHECK(o3d_preload_count(nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr) == O3D_OK);
     CHECK(o3d_preload_scatter(nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr) == O3D_OK);
+    CHECK(o3d_preload_posed_count(nullptr, 0, 3, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr) == O3D_OK);
+    CHECK(o3d_preload_posed_scatter(nullptr, 0, 4, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr) == O3D_OK);
+    CHECK(o3d_preload_posed_count(nullptr, 0, 2, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr) == O3D_EINVAL);
     std::printf("preload planner: ok\n");
     return 0;
 }
