@@ -786,6 +786,56 @@ int o3d_track_motion_input_drawn(const float* prev, const float* cur, const int3
                                  int key_this, int N, const float* wlh, int first_frame, float* points, float* candidate_bc,
                                  int32_t* used, void* stream);
 
+/* ---- the free-running loop L lanes wide (tracking.LaneTracker / MotionLaneTracker: the test epoch, one tracklet per lane) -------
+ * Every buffer is regular and a lane is its leading axis; L is 1..O3D_CROP_MULTI_MAX_TARGETS.  What changes per step and lane
+ * travels in `lanes` (L, O3D_LANE_COLS) int32 on the device, row l = {active, first, has_crop, t, row, ref_row, rebase}: whether
+ * the lane tracks at all, whether this is its tracklet's first tracked frame, whether a model crop was made, the frame index
+ * (>= 1), the lane's row of the result pool, the row of the ground-truth pool that is its reference box (-1: its own current
+ * box) and whether the yaw state restarts from that reference.  Each entry calls the device function of its single form on
+ * lane l's operands: lane l's output is that entry's, bit for bit.
+ *
+ * o3d_track_bank_update_lanes: o3d_track_bank_update per lane.  crop (L,crop_cap,3), lane l's count = counts[l * count_stride],
+ * bank (L,bank_cap,3), state_in / state_out (L,2).  An inactive lane, or one without a crop, copies its state through and
+ * writes nothing else. */
+#define O3D_LANE_ACTIVE 0
+#define O3D_LANE_FIRST 1
+#define O3D_LANE_HAS_CROP 2
+#define O3D_LANE_T 3
+#define O3D_LANE_ROW 4
+#define O3D_LANE_REF_ROW 5
+#define O3D_LANE_REBASE 6
+#define O3D_LANE_COLS 7
+int o3d_track_bank_update_lanes(const float* crop, const int32_t* counts, int count_stride, int crop_cap, float* bank, int bank_cap,
+                                int rule, const int32_t* lanes, int L, const int32_t* state_in, int32_t* state_out, void* stream);
+
+/* o3d_track_resample_drawn for two clouds times L lanes in one launch.  Per cloud: src (L,cap,3), lane l's count =
+ * n_dev[l * stride], the key, dst (L,S,3), used (L,S) | NULL.  Row l is what o3d_track_resample_drawn writes for that job. */
+int o3d_track_resample_drawn_lanes(const float* src0, const int32_t* n_dev0, int stride0, int cap0, int key0, float* dst0, int S0,
+                                   int32_t* used0, const float* src1, const int32_t* n_dev1, int stride1, int cap1, int key1,
+                                   float* dst1, int S1, int32_t* used1, int L, void* stream);
+
+/* o3d_track_motion_input_drawn per lane: prev / cur (L,capacity,3), counts (L,2), wlh (L,3), first_frame = the lane's `first`;
+ * points (L,2N,5), candidate_bc (L,2N,9) | NULL, used (L,2N) | NULL. */
+int o3d_track_motion_input_drawn_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
+                                       int key_this, int N, const float* wlh, const int32_t* lanes, int L, float* points,
+                                       float* candidate_bc, int32_t* used, void* stream);
+
+/* o3d_track_offset_box per lane, one thread each.  ref = row ref_row[l] of gt (R,15), or cur[l] of cur (L,15) when ref_row[l] is
+ * -1; offset (L,4), yaw_state (L,10).  The new box goes to out[l] (out (L,15) may be cur) and to results[row[l]] of the pool
+ * results (R,15); limit_box's draw hashes (seed, t[l], component), so lane l's box is o3d_track_offset_box's with that seed and
+ * frame[0] = t[l].  counts_log (R,2) | NULL with counts (L,2): row row[l] receives the lane's two crop counts (-1 for the second
+ * without a crop).  An inactive lane writes nothing; neither does one whose ref_row lies outside [-1, R). */
+int o3d_track_offset_box_lanes(const float* cur, const float* gt, int R, const float* offset, float* yaw_state, const int32_t* lanes,
+                               int L, int degrees, int use_z, int limit_box, int seed, float* out, float* results,
+                               const int32_t* counts, int32_t* counts_log, void* stream);
+
+/* A lane's start: every lane that is active and first takes row row[l] - t[l] of gt (R,15) -- its tracklet's first box -- as
+ * cur[l], restarts yaw_state[l] = {that rotation, 0}, takes its wlh as the canonical box wlh[l] (L,3) and, with state (L,2) int32
+ * | NULL (the template banks' {fixed, total} that the step's o3d_track_bank_update_lanes reads), sets state[l] = {0, 0}: what
+ * the single trackers' init() sets, in the same bits. */
+int o3d_track_lane_start(const float* gt, int R, const int32_t* lanes, int L, float* cur, float* yaw_state, float* wlh,
+                         int32_t* state, void* stream);
+
 /* ---- training batches built on the device (csrc/train_batch.hip): the device form of PointTrackingSampler +
  * siamese_processing (datasets/sampler.py:16-79) for BAT and P2B.  Frames and ground-truth boxes resident in HBM go in, the
  * training dict comes out; no host synchronisation.  The formulas are written at the head of csrc/train_batch.hip.

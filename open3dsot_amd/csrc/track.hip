@@ -14,6 +14,11 @@
 //                         the free-running loop (tracking.py, sampling="device"): the counts are read where the crop left
 //                         them, the indices are the keyed draw of track_common.hpp, the template bank's {fixed, total} is
 //                         device state -- nothing of a frame crosses to the host
+//   o3d_track_bank_update_lanes / o3d_track_resample_drawn_lanes / o3d_track_motion_input_drawn_lanes /
+//   o3d_track_offset_box_lanes / o3d_track_lane_start
+//                         the free-running loop L tracklets wide (tracking.LaneTracker, tracking.MotionLaneTracker): a lane is a
+//                         leading axis, its row of the (L, O3D_LANE_COLS) int32 lane table says what it does at this step, and
+//                         every kernel calls the device function of the single form
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -200,9 +205,8 @@ struct DrawnJob {
 __device__ __forceinline__ int drawn_index(unsigned key, int i, int n, int S) { return n > 2 ? sample_index(key, i, n, S) : -1; }
 
 // resample_kernel with the count read from the device and the index drawn in place: reads n_dev and src, writes dst and used
-__global__ __launch_bounds__(256) void resample_drawn_kernel(DrawnJob a, DrawnJob b) {
-    const DrawnJob& J = blockIdx.y == 0 ? a : b;
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// THE row of both o3d_track_resample_drawn and o3d_track_resample_drawn_lanes
+__device__ __forceinline__ void resample_drawn_row(const DrawnJob& J, int i) {
     if (i >= J.S) return;
     const int n = min(J.n_dev[0], J.cap);
     const int s = drawn_index(J.key, i, n, J.S);
@@ -213,6 +217,10 @@ __global__ __launch_bounds__(256) void resample_drawn_kernel(DrawnJob a, DrawnJo
     if (J.used) J.used[i] = s;
 }
 
+__global__ __launch_bounds__(256) void resample_drawn_kernel(DrawnJob a, DrawnJob b) {
+    resample_drawn_row(blockIdx.y == 0 ? a : b, blockIdx.x * 256 + threadIdx.x);
+}
+
 struct BankArgs {
     const float* crop; const int32_t* count; int crop_cap; float* bank; int bank_cap;
     const int32_t* state_in; int32_t* state_out; int rule, first, has_crop;
@@ -220,9 +228,9 @@ struct BankArgs {
 
 // The template bank's book-keeping as device state {fixed, total}: every thread reads state_in and count, thread 0 of
 // workgroup 0 writes state_out (another two words: the tracker alternates two slots), so no workgroup reads a word that
-// another one of the launch writes.  Thread i carries row i of the staged crop to row slot + i of the bank.
-__global__ __launch_bounds__(256) void bank_update_kernel(BankArgs a) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// another one of the launch writes.  Thread i carries row i of the staged crop to row slot + i of the bank.  THE body of both
+// o3d_track_bank_update and o3d_track_bank_update_lanes
+__device__ __forceinline__ void bank_update_rows(const BankArgs& a, int i) {
     const int fixed = a.state_in[0], total = a.state_in[1];
     if (!a.has_crop) {                                     // rule `first` after frame 1: the template does not change
         if (i == 0) { a.state_out[0] = fixed; a.state_out[1] = total; }
@@ -248,15 +256,17 @@ __global__ __launch_bounds__(256) void bank_update_kernel(BankArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void bank_update_kernel(BankArgs a) { bank_update_rows(a, blockIdx.x * 256 + threadIdx.x); }
+
 struct MotionDrawnArgs {
     const float* src[2]; const int32_t* counts; int cap; unsigned key[2];      // [0] the previous crop, [1] the current crop
     const float* wlh; int N, first_frame;
     float* points; float* bc; int32_t* used;
 };
 
-// motion_input_kernel with the two counts read from the device and the indices drawn in place
-__global__ __launch_bounds__(256) void motion_input_drawn_kernel(MotionDrawnArgs a) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// motion_input_kernel with the two counts read from the device and the indices drawn in place: THE row of both
+// o3d_track_motion_input_drawn and o3d_track_motion_input_drawn_lanes
+__device__ __forceinline__ void motion_drawn_row(const MotionDrawnArgs& a, int i) {
     if (i >= 2 * a.N) return;
     const int half = i >= a.N ? 1 : 0;
     const int n = min(a.counts[half], a.cap);
@@ -266,6 +276,8 @@ __global__ __launch_bounds__(256) void motion_input_drawn_kernel(MotionDrawnArgs
     motion_row(px, py, pz, half, a.wlh, a.first_frame, a.points + 5 * (long)i, a.bc ? a.bc + 9 * (long)i : nullptr);
     if (a.used) a.used[i] = s;
 }
+
+__global__ __launch_bounds__(256) void motion_input_drawn_kernel(MotionDrawnArgs a) { motion_drawn_row(a, blockIdx.x * 256 + threadIdx.x); }
 
 struct OffsetArgs {
     const float* ref; const float* offset; float* yaw_state; float* out; float* results; int32_t* frame;
@@ -283,6 +295,96 @@ __global__ void offset_box_kernel(OffsetArgs a) {
         if (a.results && k >= 0 && k < a.T) a.results[15 * (long)k + i] = box[i];
     }
     if (a.frame) a.frame[0] = k + 1;
+}
+
+// ---- L lanes per launch (tracking.LaneTracker / MotionLaneTracker: the test epoch, one tracklet per lane) ---------------------------
+// A lane is a leading axis of every buffer; what changes per step and lane is row l of `lanes` (L, O3D_LANE_COLS) int32:
+// {active, first, has_crop, t, row, ref_row, rebase}.  Every kernel below hands lane l's operands to the device function of
+// the single form, so lane l's rows are that entry point's, bit for bit.
+struct BankLanesArgs {
+    const float* crop; const int32_t* counts; int count_stride, crop_cap; float* bank; int bank_cap, rule;
+    const int32_t* lanes; const int32_t* state_in; int32_t* state_out;
+};
+
+// blockIdx.y = the lane; an inactive lane and a lane without a crop take bank_update_rows' copy-through path
+__global__ __launch_bounds__(256) void bank_update_lanes_kernel(BankLanesArgs a) {
+    const long l = blockIdx.y;
+    const int32_t* f = a.lanes + O3D_LANE_COLS * l;
+    const BankArgs b{a.crop + 3 * l * a.crop_cap, a.counts + l * a.count_stride, a.crop_cap, a.bank + 3 * l * a.bank_cap, a.bank_cap,
+                     a.state_in + 2 * l, a.state_out + 2 * l, a.rule, f[O3D_LANE_FIRST] != 0,
+                     f[O3D_LANE_ACTIVE] != 0 && f[O3D_LANE_HAS_CROP] != 0};
+    bank_update_rows(b, blockIdx.x * 256 + threadIdx.x);
+}
+
+// one cloud of o3d_track_resample_drawn_lanes: lane l reads src + 3 l cap and n_dev[l stride], writes dst + 3 l S and used + l S
+struct DrawnLanes {
+    const float* src; const int32_t* n_dev; int stride, cap; unsigned key; float* dst; int S; int32_t* used;
+};
+
+// blockIdx.y = the cloud, blockIdx.z = the lane
+__global__ __launch_bounds__(256) void resample_drawn_lanes_kernel(DrawnLanes a, DrawnLanes b) {
+    const DrawnLanes& C = blockIdx.y == 0 ? a : b;
+    const long l = blockIdx.z;
+    const DrawnJob J{C.src + 3 * l * C.cap, C.n_dev + l * C.stride, C.cap, C.key, C.dst + 3 * l * C.S, C.S, C.used ? C.used + l * C.S : nullptr};
+    resample_drawn_row(J, blockIdx.x * 256 + threadIdx.x);
+}
+
+// blockIdx.y = the lane: a.src / counts / wlh / points / bc / used are the (L, ...) buffers, lane l's MotionDrawnArgs is cut out here
+__global__ __launch_bounds__(256) void motion_input_drawn_lanes_kernel(MotionDrawnArgs a, const int32_t* __restrict__ lanes) {
+    const long l = blockIdx.y, rows = 2 * (long)a.N;
+    const MotionDrawnArgs m{{a.src[0] + 3 * l * a.cap, a.src[1] + 3 * l * a.cap}, a.counts + 2 * l, a.cap, {a.key[0], a.key[1]}, a.wlh + 3 * l,
+                            a.N, lanes[O3D_LANE_COLS * l + O3D_LANE_FIRST] != 0, a.points + 5 * l * rows, a.bc ? a.bc + 9 * l * rows : nullptr,
+                            a.used ? a.used + l * rows : nullptr};
+    motion_drawn_row(m, blockIdx.x * 256 + threadIdx.x);
+}
+
+struct OffsetLanesArgs {
+    const float* cur; const float* gt; const float* offset; float* yaw_state; const int32_t* lanes; float* out; float* results;
+    const int32_t* counts; int32_t* counts_log;
+    int L, R, degrees, use_z, limit_box, seed;
+};
+
+// One thread per lane.  Thread l reads cur[l] (or a row of gt, which nothing writes), offset[l], yaw_state[l], counts[l] and
+// writes out[l] (which may be cur[l]: its own row), yaw_state[l] and row[l] of results / counts_log (a row belongs to one
+// tracklet, a tracklet to one lane): no thread reads what another one writes.
+__global__ __launch_bounds__(256) void offset_box_lanes_kernel(OffsetLanesArgs a) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= a.L) return;
+    const int32_t* f = a.lanes + O3D_LANE_COLS * (long)l;
+    const int ref_row = f[O3D_LANE_REF_ROW], row = f[O3D_LANE_ROW];
+    if (!f[O3D_LANE_ACTIVE] || ref_row < -1 || ref_row >= a.R) return;
+    const float* ref = ref_row >= 0 ? a.gt + 15 * (long)ref_row : a.cur + 15 * (long)l;
+    float box[15];
+    offset_box_one(ref, a.offset + 4 * (long)l, a.yaw_state + 10 * (long)l, f[O3D_LANE_REBASE] != 0, a.degrees, a.use_z, a.limit_box,
+                   (unsigned)a.seed, (unsigned)f[O3D_LANE_T], box);
+    const bool logged = row >= 0 && row < a.R;
+    for (int i = 0; i < 15; ++i) {
+        a.out[15 * (long)l + i] = box[i];
+        if (logged) a.results[15 * (long)row + i] = box[i];
+    }
+    if (logged && a.counts_log) {                          // the frame's record: what the crops counted, -1 where none was made
+        a.counts_log[2 * (long)row] = a.counts[2 * (long)l];
+        a.counts_log[2 * (long)row + 1] = f[O3D_LANE_HAS_CROP] ? a.counts[2 * (long)l + 1] : -1;
+    }
+}
+
+// One thread per lane: a lane that starts a tracklet (active and first) takes the tracklet's first ground-truth box, row
+// row[l] - t[l] of gt, as its current box, restarts its yaw state from that rotation, takes its wlh as the canonical box and
+// empties its template bank (state (L,2) | NULL = {fixed, total}, the slot that the step's bank update reads)
+__global__ __launch_bounds__(256) void lane_start_kernel(const float* __restrict__ gt, int R, const int32_t* __restrict__ lanes, int L,
+                                                         float* __restrict__ cur, float* __restrict__ yaw_state, float* __restrict__ wlh,
+                                                         int32_t* __restrict__ state) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= L) return;
+    const int32_t* f = lanes + O3D_LANE_COLS * (long)l;
+    const long row0 = (long)f[O3D_LANE_ROW] - f[O3D_LANE_T];
+    if (!f[O3D_LANE_ACTIVE] || !f[O3D_LANE_FIRST] || row0 < 0 || row0 >= R) return;
+    const float* b = gt + 15 * row0;
+    for (int i = 0; i < 15; ++i) cur[15 * (long)l + i] = b[i];
+    for (int i = 0; i < 9; ++i) yaw_state[10 * (long)l + i] = b[6 + i];
+    yaw_state[10 * (long)l + 9] = 0.f;
+    for (int i = 0; i < 3; ++i) wlh[3 * (long)l + i] = b[3 + i];
+    if (state) { state[2 * (long)l] = 0; state[2 * (long)l + 1] = 0; }
 }
 
 // ---- K targets per launch ------------------------------------------------------------------------------------------------------
@@ -549,6 +651,58 @@ extern "C" int o3d_track_motion_input_drawn(const float* prev, const float* cur,
     const MotionDrawnArgs a{{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this}, wlh, N, first_frame != 0, points,
                             candidate_bc, used};
     hipLaunchKernelGGL(motion_input_drawn_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+// ---- L lanes per launch: validation first, the contracts are include/o3dsot.h's ------------------------------------------------------
+static bool lanes_ok(const int32_t* lanes, int L) { return lanes && L >= 1 && L <= O3D_CROP_MULTI_MAX_TARGETS; }
+
+extern "C" int o3d_track_bank_update_lanes(const float* crop, const int32_t* counts, int count_stride, int crop_cap, float* bank, int bank_cap,
+                                           int rule, const int32_t* lanes, int L, const int32_t* state_in, int32_t* state_out, void* stream) {
+    if (!crop || !counts || !bank || !state_in || !state_out || state_in == state_out || !lanes_ok(lanes, L) || count_stride < 1 ||
+        crop_cap < 1 || crop_cap > (1 << 29) || bank_cap < 1 || bank_cap > (1 << 29) || rule < O3D_BANK_FIRST || rule > O3D_BANK_ALL)
+        return O3D_EINVAL;
+    const BankLanesArgs a{crop, counts, count_stride, crop_cap, bank, bank_cap, rule, lanes, state_in, state_out};
+    hipLaunchKernelGGL(bank_update_lanes_kernel, dim3(o3d_cdiv(crop_cap, 256), L), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_resample_drawn_lanes(const float* src0, const int32_t* n_dev0, int stride0, int cap0, int key0, float* dst0, int S0,
+                                              int32_t* used0, const float* src1, const int32_t* n_dev1, int stride1, int cap1, int key1,
+                                              float* dst1, int S1, int32_t* used1, int L, void* stream) {
+    if (L < 1 || L > O3D_CROP_MULTI_MAX_TARGETS || stride0 < 1 || stride1 < 1 || !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) ||
+        !drawn_job_ok(src1, n_dev1, cap1, dst1, S1))
+        return O3D_EINVAL;
+    const DrawnLanes a{src0, n_dev0, stride0, cap0, (unsigned)key0, dst0, S0, used0}, b{src1, n_dev1, stride1, cap1, (unsigned)key1, dst1, S1, used1};
+    hipLaunchKernelGGL(resample_drawn_lanes_kernel, dim3(o3d_cdiv(S0 > S1 ? S0 : S1, 256), 2, L), dim3(256), 0, o3d_stream(stream), a, b);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_motion_input_drawn_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
+                                                  int key_this, int N, const float* wlh, const int32_t* lanes, int L, float* points,
+                                                  float* candidate_bc, int32_t* used, void* stream) {
+    if (!prev || !cur || !counts || !wlh || !points || !lanes_ok(lanes, L) || capacity < 1 || capacity > (1 << 29) || N < 1 || N > (1 << 20))
+        return O3D_EINVAL;
+    const MotionDrawnArgs a{{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this}, wlh, N, 0, points, candidate_bc, used};
+    hipLaunchKernelGGL(motion_input_drawn_lanes_kernel, dim3(o3d_cdiv(2 * N, 256), L), dim3(256), 0, o3d_stream(stream), a, lanes);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_offset_box_lanes(const float* cur, const float* gt, int R, const float* offset, float* yaw_state, const int32_t* lanes,
+                                          int L, int degrees, int use_z, int limit_box, int seed, float* out, float* results,
+                                          const int32_t* counts, int32_t* counts_log, void* stream) {
+    if (!cur || !gt || !offset || !yaw_state || !out || !results || !lanes_ok(lanes, L) || R < 1 || R > (1 << 26) || seed < 0 ||
+        (counts_log && !counts))
+        return O3D_EINVAL;
+    const OffsetLanesArgs a{cur, gt, offset, yaw_state, lanes, out, results, counts, counts_log, L, R, degrees, use_z, limit_box, seed};
+    hipLaunchKernelGGL(offset_box_lanes_kernel, dim3(o3d_cdiv(L, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_lane_start(const float* gt, int R, const int32_t* lanes, int L, float* cur, float* yaw_state, float* wlh,
+                                    int32_t* state, void* stream) {
+    if (!gt || !cur || !yaw_state || !wlh || !lanes_ok(lanes, L) || R < 1 || R > (1 << 26)) return O3D_EINVAL;
+    hipLaunchKernelGGL(lane_start_kernel, dim3(o3d_cdiv(L, 256)), dim3(256), 0, o3d_stream(stream), gt, R, lanes, L, cur, yaw_state, wlh, state);
     return o3d_launch_status();
 }
 

@@ -505,6 +505,144 @@ def motion_input_drawn(prev_crop, this_crop, counts, keys, wlh, first_frame, out
     return out_points, out_bc
 
 
+# ---- the free-running loop L lanes wide (tracking.LaneTracker / MotionLaneTracker; o3d_track_*_lanes) -----------------------------
+# A lane is the leading axis of every buffer; `lanes` is the (L, LANE_COLS) int32 GPU table of the step.
+LANE_FIELDS = ("active", "first", "has_crop", "t", "row", "ref_row", "rebase")
+LANE_COLS = capi.CONSTANTS["O3D_LANE_COLS"]
+LANE = {name: capi.CONSTANTS["O3D_%s" % ("lane_" + name).upper()] for name in LANE_FIELDS}      # O3D_LANE_ACTIVE, ...
+
+
+def _f32(t, shape, what):
+    _need_gpu(t, what)
+    assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), (what, tuple(t.shape), tuple(shape))
+
+
+def _i32(t, numel, what):
+    _need_gpu(t, what)
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == numel, (what, tuple(t.shape), numel)
+
+
+def _lane_table(lanes, what):
+    _need_gpu(lanes, what)
+    assert lanes.dtype == torch.int32 and lanes.is_contiguous() and lanes.dim() == 2 and lanes.shape[1] == LANE_COLS
+    return lanes.shape[0]
+
+
+def _strided_count(t, stride, L):
+    """a count per lane: element l * stride of the int32 GPU tensor (or view) t"""
+    assert t.is_cuda and t.dtype == torch.int32 and t.stride(-1) == 1 and stride >= 1
+    assert t.storage_offset() + (L - 1) * stride < t.untyped_storage().nbytes() // 4
+
+
+def bank_update_lanes(crop, counts, count_stride, bank, rule, lanes, state_in, state_out):
+    """One o3d_track_bank_update_lanes launch (no sync): bank_update per lane.  crop (L,crop_cap,3), lane l's count =
+    counts.flatten()[l * count_stride], bank (L,bank_cap,3), lanes (L,LANE_COLS), state_in / state_out (L,2) int32."""
+    L = _lane_table(lanes, "bank_update_lanes")
+    _f32(crop, (L, crop.shape[1], 3), "bank_update_lanes")
+    _f32(bank, (L, bank.shape[1], 3), "bank_update_lanes")
+    _strided_count(counts, count_stride, L)
+    _i32(state_in, 2 * L, "bank_update_lanes")
+    _i32(state_out, 2 * L, "bank_update_lanes")
+    dev = bank.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_bank_update_lanes(
+            crop.data_ptr(), counts.data_ptr(), int(count_stride), crop.shape[1], bank.data_ptr(), bank.shape[1], BANK_RULES[rule],
+            lanes.data_ptr(), L, state_in.data_ptr(), state_out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_bank_update_lanes")
+
+
+def resample_drawn_lanes(jobs):
+    """One o3d_track_resample_drawn_lanes launch (no sync).  jobs: 2 tuples (src (L,cap,3), n_dev, stride, key, dst (L,S,3),
+    used (L,S) int32 | None); lane l's count is element l * stride of n_dev (an int32 GPU tensor or view)."""
+    assert len(jobs) == 2
+    L, args = jobs[0][0].shape[0], []
+    for src, n_dev, stride, key, dst, used in jobs:
+        _f32(src, (L, src.shape[1], 3), "resample_drawn_lanes")
+        _f32(dst, (L, dst.shape[1], 3), "resample_drawn_lanes")
+        _strided_count(n_dev, stride, L)
+        if used is not None:
+            _i32(used, L * dst.shape[1], "resample_drawn_lanes")
+        args += [src.data_ptr(), n_dev.data_ptr(), int(stride), src.shape[1], _key_bits(key), dst.data_ptr(), dst.shape[1],
+                 used.data_ptr() if used is not None else None]
+    dev = jobs[0][4].device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_resample_drawn_lanes(*args, L, torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_track_resample_drawn_lanes")
+
+
+def motion_input_drawn_lanes(prev_crop, this_crop, counts, keys, wlh, lanes, out_points, out_bc=None, used=None):
+    """One o3d_track_motion_input_drawn_lanes launch (no sync): motion_input_drawn per lane.  prev_crop / this_crop (L,cap,3),
+    counts (L,2) int32, wlh (L,3), lanes (L,LANE_COLS): `first` is the lane's first_frame; out_points (L,2N,5), out_bc
+    (L,2N,9) | None / False, used (L,2N) int32 | None."""
+    L = _lane_table(lanes, "motion_input_drawn_lanes")
+    cap, n2 = prev_crop.shape[1], out_points.shape[1]
+    _f32(prev_crop, (L, cap, 3), "motion_input_drawn_lanes")
+    _f32(this_crop, (L, cap, 3), "motion_input_drawn_lanes")
+    _f32(wlh, (L, 3), "motion_input_drawn_lanes")
+    _f32(out_points, (L, n2, 5), "motion_input_drawn_lanes")
+    _i32(counts, 2 * L, "motion_input_drawn_lanes")
+    assert n2 % 2 == 0
+    if out_bc is None or out_bc is False:
+        out_bc = None
+    else:
+        _f32(out_bc, (L, n2, 9), "motion_input_drawn_lanes")
+    if used is not None:
+        _i32(used, L * n2, "motion_input_drawn_lanes")
+    dev = wlh.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_motion_input_drawn_lanes(
+            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), cap, _key_bits(keys[0]), _key_bits(keys[1]), n2 // 2,
+            wlh.data_ptr(), lanes.data_ptr(), L, out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
+            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_motion_input_drawn_lanes")
+    return out_points, out_bc
+
+
+def offset_box_lanes(cur, gt, offset, yaw_state, lanes, out, results, counts=None, counts_log=None, degrees=True, use_z=False,
+                     limit_box=True, seed=0):
+    """One o3d_track_offset_box_lanes launch (no sync): offset_box per lane.  cur (L,15), gt (R,15) the ground-truth pool,
+    offset (L,4), yaw_state (L,10), lanes (L,LANE_COLS), out (L,15) (may be cur), results (R,15) the result pool; counts (L,2)
+    with counts_log (R,2) int32 | None: the frame's crop counts go to the lane's row of the log."""
+    L = _lane_table(lanes, "offset_box_lanes")
+    R = gt.shape[0]
+    _f32(cur, (L, 15), "offset_box_lanes")
+    _f32(gt, (R, 15), "offset_box_lanes")
+    _f32(yaw_state, (L, 10), "offset_box_lanes")
+    _f32(out, (L, 15), "offset_box_lanes")
+    _f32(results, (R, 15), "offset_box_lanes")
+    _need_gpu(offset, "offset_box_lanes")
+    assert offset.dtype == torch.float32 and offset.is_contiguous() and offset.numel() == 4 * L
+    if counts_log is not None:
+        _i32(counts, 2 * L, "offset_box_lanes")
+        _i32(counts_log, 2 * R, "offset_box_lanes")
+    dev = cur.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_offset_box_lanes(
+            cur.data_ptr(), gt.data_ptr(), R, offset.data_ptr(), yaw_state.data_ptr(), lanes.data_ptr(), L, int(bool(degrees)),
+            int(bool(use_z)), int(bool(limit_box)), int(seed) & 0x7fffffff, out.data_ptr(), results.data_ptr(),
+            counts.data_ptr() if counts_log is not None else None, counts_log.data_ptr() if counts_log is not None else None,
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_offset_box_lanes")
+    return out
+
+
+def lane_start(gt, lanes, cur, yaw_state, wlh, state=None):
+    """One o3d_track_lane_start launch (no sync): every lane of lanes (L,LANE_COLS) that is active and first takes its
+    tracklet's first box, row (row - t) of gt (R,15), into cur (L,15), yaw_state (L,10) and wlh (L,3), and zeroes its row of
+    state (L,2) int32 | None (the template bank's {fixed, total})."""
+    L = _lane_table(lanes, "lane_start")
+    _f32(gt, (gt.shape[0], 15), "lane_start")
+    _f32(cur, (L, 15), "lane_start")
+    _f32(yaw_state, (L, 10), "lane_start")
+    _f32(wlh, (L, 3), "lane_start")
+    if state is not None:
+        _i32(state, 2 * L, "lane_start")
+    dev = cur.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_lane_start(gt.data_ptr(), gt.shape[0], lanes.data_ptr(), L, cur.data_ptr(), yaw_state.data_ptr(),
+                                                    wlh.data_ptr(), state.data_ptr() if state is not None else None,
+                                                    torch.cuda.current_stream(dev).cuda_stream), "o3d_track_lane_start")
+
+
 def _box_device(box, what):
     """the GPU a box lives on (a (15,) tensor or a (center, wlh, rot) triple of tensors); anything else is refused"""
     parts = (box,) if torch.is_tensor(box) else tuple(box)

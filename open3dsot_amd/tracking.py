@@ -33,6 +33,11 @@ No copy in either direction and no synchronisation after the first update() (who
 every buffer has a fixed capacity (a longer crop keeps its first `capacity` survivors), and the indices are not numpy's -- the
 same rule (n <= 2 zero-fills, n == S is the identity, S > n draws with replacement, S < n without), other numbers.
 
+The test epoch on L lanes (LaneTracker, MotionLaneTracker, evaluate(..., lanes=L)): that free-running
+loop L tracklets wide, each lane on its own tracklet's frames.  Which tracklet runs on which lane at which step (lane_schedule),
+every crop group and every lane table are host knowledge before the first frame: begin() plans them, uploads them in chunks,
+and step() only launches.
+
 The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
 (`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
 """
@@ -421,12 +426,13 @@ class _MatchingTracker(_DeviceTracker):
         if self.free_running:         # fixed sizes: nothing can grow a buffer without reading a count
             if min(int(search_capacity), self.model_capacity, self.bank_capacity) < 1:
                 raise ValueError("search_capacity, model_capacity and bank_capacity must be positive")
-            self.staging = torch.empty((self.model_capacity, 3), **f32)      # the frame's model crop, before it enters the bank
-            self.bank = torch.empty((self.bank_capacity, 3), **f32)
-            self.bank_state = torch.zeros((2, 2), dtype=torch.int32, device=self.dev)      # {fixed, total}, two slots by frame parity
+            lead = self.lead                   # () for the single tracker, (L,) for the lanes of LaneTracker
+            self.staging = torch.empty(lead + (self.model_capacity, 3), **f32)      # the frame's model crop, before it enters the bank
+            self.bank = torch.empty(lead + (self.bank_capacity, 3), **f32)
+            self.bank_state = torch.zeros((2,) + lead + (2,), dtype=torch.int32, device=self.dev)      # {fixed, total}, two slots by frame parity
             i32 = dict(dtype=torch.int32, device=self.dev)
-            self.used_t = torch.full((M,), -1, **i32) if self.record_indices else None
-            self.used_s = torch.full((N,), -1, **i32) if self.record_indices else None
+            self.used_t = torch.full(lead + (M,), -1, **i32) if self.record_indices else None
+            self.used_s = torch.full(lead + (N,), -1, **i32) if self.record_indices else None
         else:
             self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
         # log, per frame: (search count, model count of the crop made this frame | None, template points)
@@ -483,6 +489,23 @@ class _MatchingTracker(_DeviceTracker):
         if self.with_boxcloud:
             PU.boxcloud_into(self.inputs["points2cc_dist_t"], self.inputs["template_points"], self.canon_centre, self.canon_wlh,
                              self.canon_rot)
+
+
+def _matching_overflow(counts, search_capacity, model_capacity, bank_capacity, aggregation):
+    """counts (t,2) of one tracked sequence (row 0 unused) -> (truncated search crops, truncated model crops, frames on which
+    the bank was full) under the fixed capacities of a free-running matching tracker"""
+    over_s = int((counts[1:, 0] > search_capacity).sum())
+    over_m = int((counts[1:, 1] > model_capacity).sum())
+    fixed = total = full = 0
+    for t in range(1, counts.shape[0]):                    # the transitions of o3d_track_bank_update, before its clip
+        if counts[t, 1] < 0:
+            continue
+        nm, first = min(int(counts[t, 1]), model_capacity), t == 1
+        slot = total if aggregation == "all" else fixed if aggregation == "firstandprevious" and not first else 0
+        need = 2 * nm if aggregation == "firstandprevious" and first else slot + nm
+        full += need > bank_capacity
+        fixed, total = (nm if first else fixed), min(need, bank_capacity)
+    return over_s, over_m, int(full)
 
 
 class SequenceTracker(_MatchingTracker):
@@ -558,19 +581,7 @@ class SequenceTracker(_MatchingTracker):
     def overflow(self):
         """sampling="device" only -> (truncated search crops, truncated model crops, frames on which the bank was full): how
         often a fixed capacity cut something, worked out on the host from counts() and the capacities (one sync)."""
-        counts = self.counts()
-        over_s = int((counts[1:, 0] > self.search_buf.shape[0]).sum())
-        over_m = int((counts[1:, 1] > self.model_capacity).sum())
-        fixed = total = full = 0
-        for t in range(1, counts.shape[0]):                # the transitions of o3d_track_bank_update, before its clip
-            if counts[t, 1] < 0:
-                continue
-            nm, first = min(int(counts[t, 1]), self.model_capacity), t == 1
-            slot = total if self.aggregation == "all" else fixed if self.aggregation == "firstandprevious" and not first else 0
-            need = 2 * nm if self.aggregation == "firstandprevious" and first else slot + nm
-            full += need > self.bank_capacity
-            fixed, total = (nm if first else fixed), min(need, self.bank_capacity)
-        return over_s, over_m, int(full)
+        return _matching_overflow(self.counts(), self.search_buf.shape[0], self.model_capacity, self.bank_capacity, self.aggregation)
 
     def _update(self, pts, ref_box):
         if self.free_running:
@@ -911,6 +922,346 @@ def _is_motion(model):
     return isinstance(model, M2TRACK)
 
 
+# ---- the test epoch on L lanes --------------------------------------------------------------------------
+ORDERS = ("given", "longest_first")
+
+
+def lane_schedule(lengths, lanes, order="given"):
+    """Which tracklet runs on which lane at which step.  lengths: the tracklets' frame counts; -> (tracklet, frame), two
+    (steps, lanes) int32 arrays: tracklet[s, l] = the tracklet lane l tracks at step s (-1: idle), frame[s, l] = its frame
+    index t >= 1 (0 when idle).  Tracklets are taken in the given order (order="longest_first": by decreasing length, a stable
+    sort); at each step every idle lane, in lane order, takes the next unassigned tracklet of at least 2 frames and starts it
+    at t = 1, a busy lane advances by one frame.  A tracklet of length 1 takes no lane (its only result is its first box); a
+    length below 1 raises ValueError.  steps = the step after which all tracklets are done."""
+    L = int(lanes)
+    if L < 1:
+        raise ValueError("lanes must be positive")
+    if order not in ORDERS:
+        raise ValueError("order %r: expected \"given\" or \"longest_first\"" % (order,))
+    lengths = [int(n) for n in lengths]
+    if any(n < 1 for n in lengths):
+        raise ValueError("a tracklet needs at least one frame")
+    todo = sorted(range(len(lengths)), key=lambda j: -lengths[j]) if order == "longest_first" else list(range(len(lengths)))
+    todo = [j for j in todo if lengths[j] >= 2]
+    on, at, taken = [-1] * L, [0] * L, 0
+    tracklet, frame = [], []
+    while True:
+        for l in range(L):
+            if on[l] >= 0:
+                if at[l] + 1 < lengths[on[l]]:
+                    at[l] += 1
+                else:
+                    on[l], at[l] = -1, 0
+        for l in range(L):
+            if on[l] < 0 and taken < len(todo):
+                on[l], at[l], taken = todo[taken], 1, taken + 1
+        if all(j < 0 for j in on):
+            break
+        tracklet.append(list(on))
+        frame.append(list(at))
+    return np.array(tracklet, np.int32).reshape(-1, L), np.array(frame, np.int32).reshape(-1, L)
+
+
+class _Lanes:
+    """What LaneTracker and MotionLaneTracker put on top of their single-target bases' state with a leading L axis: the epoch
+    plan.  begin() lays all tracklets' ground-truth boxes end to end in one pool (R,15) and gives the results the same rows
+    (tracklet j owns rows [row0_j, row0_j + T_j)), runs lane_schedule, and from then on everything a step needs is host
+    knowledge: per step the lane table (L, LANE_COLS) and one o3d_crop_plan group with one o3d_crop_target per (lane, cloud).
+    They are built for plan_steps steps at a time in one host buffer and uploaded with ONE copy before the chunk's first step;
+    step() only launches.  A subclass provides _clouds() (its two crops per lane), _has_crop() and _launch() (the step behind
+    the crops)."""
+
+    def _lane_state(self, L, plan_steps):
+        self.L, self.plan_steps = L, int(plan_steps)
+        if self.plan_steps < 1:
+            raise ValueError("plan_steps must be positive")
+        P, G = self.plan_steps, 2 * L
+        self.counts2 = self.counts_dev.view(L, 2)
+        ends = np.cumsum([0, -(-P * L * PU.LANE_COLS * 4 // 16) * 16, P * G * PU.CROP_PLAN.itemsize, P * G * PU.CROP_TARGET.itemsize])
+        self._tab_host = np.zeros((int(ends[-1]),), np.uint8)
+        self._tab = torch.zeros((int(ends[-1]),), dtype=torch.uint8, device=self.dev)
+        self._lanes_h = self._tab_host[:P * L * PU.LANE_COLS * 4].view(np.int32).reshape(P, L, PU.LANE_COLS)
+        self._plan_h = self._tab_host[ends[1]:ends[2]].view(PU.CROP_PLAN).reshape(P, G)
+        self._targ_h = self._tab_host[ends[2]:ends[3]].view(PU.CROP_TARGET).reshape(P, G)
+        lanes_d = self._tab[:P * L * PU.LANE_COLS * 4].view(torch.int32).view(P, L, PU.LANE_COLS)
+        self._lane_rows = [lanes_d[k] for k in range(P)]                   # step k of the chunk: its (L, LANE_COLS) table on the device
+        self._plan_d, self._targ_d = self._tab.data_ptr() + int(ends[1]), self._tab.data_ptr() + int(ends[2])
+        self._groups, self._starts = [0] * P, [False] * P
+        self.steps, self.s, self.uploads = 0, 0, 0
+        self.schedule = None
+
+    def init(self, *a, **k):
+        raise RuntimeError("%s: begin(tracklets) and step() run the epoch; init / update belong to the single trackers" % self._NAME)
+
+    update = init
+
+    # ---- the plan ----------------------------------------------------------------------------------------------------------
+    def begin(self, tracklets, order="given"):
+        """Plan the epoch over `tracklets` -- a sampler.DeviceTracklets, or any iterable of (frames, boxes) -- and enqueue what
+        precedes its first step: the two pools, the first chunk's tables, the first lanes' start.  -> the number of steps."""
+        frames, boxes = [], []
+        for item in tracklets:
+            f, b = (item.frames, item.boxes) if hasattr(item, "frames") else item
+            f = list(f)
+            for x in f:
+                PU._need_gpu(x, self._NAME + ".begin")
+            b = PU._dev32(b, self.dev).reshape(-1, 15)
+            if len(f) != b.shape[0]:
+                raise ValueError("%d frames, %d ground-truth boxes" % (len(f), b.shape[0]))
+            frames.append([x.contiguous().float() for x in f])
+            boxes.append(b)
+        self.lengths = [len(f) for f in frames]
+        self.schedule = lane_schedule(self.lengths, self.L, order)
+        self.frames, self.steps, self.s, self.uploads = frames, self.schedule[0].shape[0], 0, 0
+        self.row0 = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self._fptr = np.array([x.data_ptr() for f in frames for x in f], np.int64)          # per pool row: the frame's address and size
+        self._fn = np.array([x.shape[0] for f in frames for x in f], np.int64)
+        R = int(self.row0[-1])
+        with torch.cuda.device(self.dev):
+            self.gt = torch.cat(boxes).contiguous() if R else torch.zeros((0, 15), dtype=torch.float32, device=self.dev)
+            self.boxes = torch.zeros((R, 15), dtype=torch.float32, device=self.dev)          # the result pool
+            self.counts_log = torch.full((R, 2), -1, dtype=torch.int32, device=self.dev)
+            if R:
+                first = torch.from_numpy(self.row0[:-1]).to(self.dev)
+                self.boxes.index_copy_(0, first, self.gt.index_select(0, first))             # row 0 of every tracklet: its first box
+            # the crop scratch of the worst step: one row of ceil(n / 256) counts per (lane, cloud)
+            wgs = np.maximum(1, -(-self._fn // 256))
+            js, ts = self.schedule[0].astype(np.int64), self.schedule[1].astype(np.int64)
+            rows = np.where(js >= 0, self.row0[np.maximum(js, 0)] + ts, 1)
+            worst = int(np.where(js >= 0, wgs[rows] + wgs[rows - 1], 0).sum(1).max()) if self.steps else 0
+            if self.scratch is None or self.scratch.numel() < worst:
+                self.scratch = torch.empty((max(worst, 1),), dtype=torch.int32, device=self.dev)
+            if self.free_running and hasattr(self, "bank_state"):
+                self.bank_state.zero_()
+            self._enter(0)
+        return self.steps
+
+    def _plan_chunk(self, c):
+        """the tables of steps [c P, (c + 1) P) into the host buffer, in whole-chunk numpy"""
+        P, L, F = self.plan_steps, self.L, PU.LANE
+        s0, s1 = c * P, min((c + 1) * P, self.steps)
+        S = s1 - s0
+        js, ts = self.schedule[0][s0:s1].astype(np.int64), self.schedule[1][s0:s1].astype(np.int64)      # (S,L)
+        on = js >= 0
+        row = np.where(on, self.row0[np.maximum(js, 0)] + ts, 0)           # the pool row of frame t (frames, boxes and results share it)
+        first = on & (ts == 1)
+        has_crop = on & self._has_crop(first)
+        by_gt = bool(getattr(self, "needs_ref_box", False))
+        back = 1 if "PREVIOUS_GT" in str(getattr(self, "reference_BB", "")).upper() else 0
+        ref_row = np.where(on, row - back, -1) if by_gt else np.full_like(row, -1)
+        lanes = self._lanes_h[:S]
+        for name, v in (("active", on), ("first", first), ("has_crop", has_crop), ("t", ts), ("row", np.where(on, row, -1)),
+                        ("ref_row", ref_row), ("rebase", on & by_gt)):
+            lanes[:, :, F[name]] = v
+        ll = np.arange(L, dtype=np.int64)
+        cur_ptr = np.broadcast_to(self.cur.data_ptr() + 60 * ll, (S, L))
+        ref_ptr = self.gt.data_ptr() + 60 * ref_row if by_gt else cur_ptr
+        # the candidate groups of a step: cloud c of lane l in slot c L + l, then the valid ones moved to the front
+        valid = np.zeros((S, 2 * L), bool)
+        col = {k: np.zeros((S, 2 * L), np.float64 if k in ("scale", "offset") else np.int64)
+               for k in ("points", "n", "box", "scale", "offset", "mode", "out", "capacity", "count")}
+        for cl, (shift, by_ref, scale, offset, mode, out, cap, gated) in enumerate(self._clouds()):
+            sl = slice(cl * L, (cl + 1) * L)
+            frow = np.where(on, row - shift, 0)
+            valid[:, sl] = has_crop if gated else on
+            col["points"][:, sl], col["n"][:, sl] = self._fptr[frow], self._fn[frow]
+            col["box"][:, sl] = ref_ptr if by_ref else cur_ptr
+            col["scale"][:, sl], col["offset"][:, sl], col["mode"][:, sl] = scale, offset, mode
+            col["out"][:, sl], col["capacity"][:, sl] = out.data_ptr() + 12 * cap * ll, cap
+            col["count"][:, sl] = self.counts_dev.data_ptr() + 8 * ll + 4 * cl
+        order = np.argsort(~valid, axis=1, kind="stable")
+        groups = valid.sum(1)
+        targ, plan = self._targ_h[:S], self._plan_h[:S]
+        for k in ("box", "scale", "offset", "mode", "out", "capacity", "count"):
+            targ[k] = np.take_along_axis(col[k], order, 1)
+        plan["points"], plan["n"] = np.take_along_axis(col["points"], order, 1), np.take_along_axis(col["n"], order, 1)
+        plan["targets"] = self._targ_d + PU.CROP_TARGET.itemsize * (2 * L * np.arange(S, dtype=np.int64)[:, None] + np.arange(2 * L, dtype=np.int64))
+        plan["n_targets"] = 1
+        # the planned columns (what o3d_track_crop_groups_scratch fills, for one target per group): prefix sums of the groups'
+        # workgroups; o3d_track_crop_groups checks them again before any launch
+        wgs = np.where(np.take_along_axis(valid, order, 1), np.maximum(1, -(-plan["n"].astype(np.int64) // 256)), 0)
+        before = np.cumsum(wgs, 1) - wgs
+        plan["wg_start"], plan["row_start"], plan["sbase"] = before, np.arange(2 * L), before
+        need = int(wgs.sum(1).max())
+        if need > self.scratch.numel():
+            self.scratch = torch.empty((need,), dtype=torch.int32, device=self.dev)
+        self._groups[:S], self._starts[:S] = groups.tolist(), first.any(1).tolist()
+
+    def _enter(self, s):
+        """what precedes step s: at a chunk boundary the chunk's one upload; where a lane starts a tracklet, its start"""
+        if s >= self.steps:
+            return
+        k = s % self.plan_steps
+        if k == 0:
+            self._plan_chunk(s // self.plan_steps)
+            self._tab.copy_(torch.from_numpy(self._tab_host).pin_memory(), non_blocking=True)      # the pinned copy is the allocator's to recycle
+            self.uploads += 1
+        if self._starts[k]:
+            PU.lane_start(self.gt, self._lane_rows[k], self.cur, self.yaw_state, self.canon_wlh,
+                          self.bank_state[(s + 1) & 1] if hasattr(self, "bank_state") else None)
+
+    # ---- the loop ----------------------------------------------------------------------------------------------------------
+    def step(self):
+        """Enqueue one step of the schedule: no host synchronisation, no copy to the host, and no upload outside a chunk
+        boundary.  -> False when the epoch is done (the call that enqueued its last step included)."""
+        if self.schedule is None:
+            raise RuntimeError(self._NAME + ".step before begin")
+        s = self.s
+        if s >= self.steps:
+            return False
+        k = s % self.plan_steps
+        with torch.cuda.device(self.dev):
+            PU.crop_groups(self._plan_h[k, :self._groups[k]], self._plan_d + PU.CROP_PLAN.itemsize * k * 2 * self.L, self.scratch)
+            self._launch(s, self._lane_rows[k])
+            self.s = s + 1
+            self._enter(self.s)
+        return self.s < self.steps
+
+    def run(self, tracklets, order="given"):
+        """begin(), then every step -> the result pool (R,15), a device tensor; nothing is read back"""
+        self.begin(tracklets, order)
+        while self.step():
+            pass
+        return self.boxes
+
+    def _offset(self, lanes, offset):
+        c = self
+        PU.offset_box_lanes(c.cur, c.gt, offset, c.yaw_state, lanes, c.cur, c.boxes, c.counts2, c.counts_log, degrees=c.degrees,
+                            use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+
+    # ---- state and results -------------------------------------------------------------------------------------------------
+    def set_box(self, lane, box):
+        """Overwrite lane `lane`'s current box (teacher forcing in the tests): a device copy; its yaw state restarts from the
+        box's rotation.  No result row changes."""
+        b = PU.pack_box(box, self.dev)
+        self.cur[lane].copy_(b)
+        self.yaw_state[lane, :9].copy_(b[6:15])
+        self.yaw_state[lane, 9] = 0.0
+
+    def _rows(self, j):
+        return slice(int(self.row0[j]), int(self.row0[j + 1]))
+
+    def results(self, j):
+        """(T_j,15): tracklet j's rows of the result pool, a device VIEW; row 0 its first box, row t the result of frame t"""
+        return self.boxes[self._rows(j)]
+
+    def counts(self, j):
+        """(T_j,2) int32 on the host: tracklet j's rows of the counts log, as the single trackers' counts() (one sync)"""
+        return self.counts_log[self._rows(j)].cpu().numpy()
+
+    def score(self, metrics=None):
+        """Score the result pool against the ground-truth pool in ONE o3d_track_score launch (every tracklet's frame 0 scores
+        its first box against itself, as the reference does); metrics: a SuccessPrecision that the same launch adds to.
+        -> (overlaps (R), distances (R)) device tensors; no sync."""
+        from . import metrics as MT
+        cfg = self.model.config
+        return MT.score_boxes(self.gt, self.boxes, int(getattr(cfg, "IoU_space", 3)), tuple(getattr(cfg, "up_axis", (0, 0, 1))),
+                              accumulate=metrics)
+
+
+class LaneTracker(_Lanes, _MatchingTracker):
+    """The test epoch of the matching trackers (trackers.BAT, trackers.P2B) on L lanes: SequenceTracker's free-running loop
+    (sampling="device"), L tracklets wide, each lane on its own tracklet's frames.
+
+        trk = LaneTracker(model, 4)             # model on the GPU, eval mode
+        trk.run(tracklets)                      # every step enqueued; nothing read back
+        boxes = trk.results(j)                  # (T_j,15) device view
+
+    Per step, whatever L: o3d_track_crop_groups (3 launches: one group per (lane, cloud), the search window by the lane's
+    reference box and the model crop of the previous frame by its own result box), o3d_track_bank_update_lanes,
+    o3d_track_resample_drawn_lanes, o3d_boxcloud (BAT), the batch-L network as one replayed HIP graph,
+    o3d_track_offset_box_lanes (which also writes the step's rows of the counts log); o3d_track_lane_start in front of a step
+    on which a lane starts a tracklet.  An idle lane keeps its slot: no crop, no state change, no result.  The capacities are
+    fixed, as for SequenceTracker(sampling="device"); overflow() reports what they cut.  reference_BB previous_gt / current_gt
+    read the ground-truth pool on the device.  record_indices=True keeps the last step's indices in used_t (L,template_size)
+    and used_s (L,search_size)."""
+    _NAME = "LaneTracker"
+
+    def __init__(self, model, lanes, seed=0, use_graph=None, search_capacity=32768, model_capacity=8192, bank_capacity=None,
+                 record_indices=False, plan_steps=256):
+        if _is_motion(model):
+            raise TypeError("LaneTracker serves the matching trackers (BAT, P2B); the motion tracker runs on MotionLaneTracker")
+        L = _KTargets._n_targets(lanes)
+        super().__init__(model, seed, use_graph, 1, search_capacity, model_capacity, L, "device", record_indices, bank_capacity)
+        self._lane_state(L, plan_steps)
+        # by step parity: (state_in, state_out, the template counts = column 1 of state_out at stride 2); the model counts
+        self._states = [(self.bank_state[1 - p], self.bank_state[p], self.bank_state[p].view(-1)[1:]) for p in (0, 1)]
+        self._model_counts = self.counts_dev[1:]
+
+    def _clouds(self):
+        """per cloud: (frames back from t, cropped by the reference box?, scale, offset, mode, out (L,cap,3), cap, only with has_crop?)"""
+        c = self
+        return ((0, True, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.search_buf.shape[1], False),
+                (1, False, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, c.staging, c.model_capacity, True))
+
+    def _has_crop(self, first):
+        return first | (self.aggregation != "first")
+
+    def _launch(self, s, lanes):
+        c = self
+        state_in, state_out, totals = c._states[s & 1]
+        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
+        PU.resample_drawn_lanes([(c.bank, totals, 2, c.keys[0], c.inputs["template_points"], c.used_t),
+                                 (c.search_buf, c.counts_dev, 2, c.keys[1], c.inputs["search_points"], c.used_s)])
+        c._boxcloud()
+        best, _ = c._network()
+        c._offset(lanes, best)
+
+    def overflow(self):
+        """-> (truncated search crops, truncated model crops, frames on which a bank was full) over all tracklets, on the host
+        from the counts log and the capacities (one sync)"""
+        log = self.counts_log.cpu().numpy()
+        per = [_matching_overflow(log[self._rows(j)], self.search_buf.shape[1], self.model_capacity, self.bank_capacity, self.aggregation)
+               for j in range(len(self.lengths))]
+        return tuple(int(sum(p[i] for p in per)) for i in range(3))
+
+
+class MotionLaneTracker(_Lanes, _DeviceTracker):
+    """The test epoch of the motion tracker (m2track.M2TRACK) on L lanes: MotionSequenceTracker's free-running loop, L
+    tracklets wide.  The surface is LaneTracker's.  Per step: o3d_track_crop_groups (3 launches: the previous and the current
+    frame of every busy lane by its last result box), o3d_track_motion_input_drawn_lanes, the batch-L network as one replayed
+    HIP graph, o3d_track_offset_box_lanes.  `capacity` is the fixed size of every crop buffer; record_indices=True keeps the
+    last step's indices in used (L,2N)."""
+    _NAME = "MotionLaneTracker"
+
+    def __init__(self, model, lanes, seed=0, use_graph=None, capacity=32768, record_indices=False, plan_steps=256):
+        if not _is_motion(model):
+            raise TypeError("MotionLaneTracker serves the motion tracker (M2TRACK); the matching trackers run on LaneTracker")
+        L = _KTargets._n_targets(lanes)
+        if int(capacity) < 1:
+            raise ValueError("capacity must be positive")
+        super().__init__(model, seed, use_graph, 1, _MOTION_DEFAULTS, L, "device", record_indices)
+        dev, N = self.dev, int(self.point_sample_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.box_aware = bool(getattr(model, "box_aware", False))
+        self.inputs = {"points": torch.zeros((L, 2 * N, 5), **f32)}
+        if self.box_aware:
+            self.inputs["candidate_bc"] = torch.zeros((L, 2 * N, 9), **f32)
+        self.crop_buf = torch.empty((2, L, int(capacity), 3), **f32)       # [0] the previous frame's crops, [1] the current one's
+        self._crops = (self.crop_buf[0], self.crop_buf[1])
+        self.used = torch.full((L, 2 * N), -1, dtype=torch.int32, device=dev) if self.record_indices else None
+        self._lane_state(L, plan_steps)
+
+    def _clouds(self):
+        c, cap = self, self.crop_buf.shape[2]
+        return tuple((1 - h, True, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], cap, False) for h in (0, 1))
+
+    def _has_crop(self, first):
+        return True
+
+    def _launch(self, s, lanes):
+        c = self
+        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.keys, c.canon_wlh, lanes, c.inputs["points"],
+                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        c._offset(lanes, c._network())
+
+    def overflow(self):
+        """-> (truncated previous-frame crops, truncated current-frame crops, 0) over all tracklets (one sync)"""
+        log, cap = self.counts_log.cpu().numpy(), self.crop_buf.shape[2]
+        return int((log[:, 0] > cap).sum()), int((log[:, 1] > cap).sum()), 0
+
+
+
 def tracker_for(model, **kw):
     """the tracker class of a model: MotionSequenceTracker for m2track.M2TRACK, SequenceTracker for the matching trackers"""
     return (MotionSequenceTracker if _is_motion(model) else SequenceTracker)(model, **kw)
@@ -919,6 +1270,11 @@ def tracker_for(model, **kw):
 def multi_tracker_for(model, n_targets, **kw):
     """tracker_for for K targets: MultiMotionTracker for m2track.M2TRACK, MultiTargetTracker for the matching trackers"""
     return (MultiMotionTracker if _is_motion(model) else MultiTargetTracker)(model, n_targets, **kw)
+
+
+def lane_tracker_for(model, lanes, **kw):
+    """the lane tracker class of a model: MotionLaneTracker for m2track.M2TRACK, LaneTracker for the matching trackers"""
+    return (MotionLaneTracker if _is_motion(model) else LaneTracker)(model, lanes, **kw)
 
 
 def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None, sampling="reference"):
@@ -1016,12 +1372,28 @@ def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None
     return ious, distances, trk.boxes[:trk.t]
 
 
-def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None, sampling="reference"):
+def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None, sampling="reference", lanes=None, order="given"):
     """The test epoch (test_step / validation_step of the reference over its tracklets): every tracklet of `tracklets` -- a
     sampler.DeviceTracklets, or any iterable of (frames, boxes) -- goes through evaluate_sequence on ONE tracker (one captured
     graph for the epoch) and adds to ONE metrics.SuccessPrecision (`metrics` | None: a new one); the metric is read back once,
-    at the end.  -> {"success", "precision", "frames", "tracklets"}."""
+    at the end.  -> {"success", "precision", "frames", "tracklets"}.
+    lanes=L (with sampling="device"; `order` as lane_schedule takes it): the epoch runs L tracklets at a time on a lane tracker
+    (LaneTracker / MotionLaneTracker) and the two pools are scored in one launch.  sampling="reference" cannot run on lanes:
+    numpy's index draw needs every count on the host."""
     from . import metrics as MT
+    _sampling(sampling)
+    if lanes is not None:
+        if sampling != "device":
+            raise ValueError("evaluate: lanes=%r needs sampling=\"device\" (sampling=\"reference\" draws its indices on the host, "
+                             "from counts that a lane tracker never reads back)" % (lanes,))
+        trk = lane_tracker_for(model, lanes, seed=seed, use_graph=use_graph)
+        m = metrics if metrics is not None else MT.SuccessPrecision(device=trk.dev)
+        trk.run(tracklets, order=order)
+        if trk.lengths:                        # an empty epoch scores nothing, as the loop below
+            trk.score(metrics=m)
+        out = m.compute()
+        out["tracklets"] = len(trk.lengths)
+        return out
     trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
     m = metrics if metrics is not None else MT.SuccessPrecision(device=trk.dev)
     count = 0

@@ -28,6 +28,14 @@ per frame), on the same frames and the same model (fixture weights, so that the 
 frames resident in HBM, each timed from the first update() to the read-back of its boxes, --repeats times in turn.  Prints one
 JSON line: frames/s of both (median, smallest and largest run), their ratio, the crop counts of the last frame and overflow()
 of the free-running loop.
+
+--lanes L: the test epoch on L lanes (tracking.lane_tracker_for(model, L): --tracklets tracklets of --frames frames each, L at a
+time in one free-running loop) against the sequential epoch of evaluate(..., sampling="device") (one free-running tracker, one
+tracklet after the other) on the same tracklets, the same model (fixture weights) and the same SuccessPrecision scoring, both
+from frames resident in HBM and both with their tracker and its captured graph reused, each timed from its first enqueue to
+the read-back of the metric, --repeats times in turn.  The tracklets are --distinct different synth sequences used in
+rotation.  Prints one JSON line: tracklet-frames/s of both (median, smallest and largest run), their ratio, the schedule's
+steps and idle-lane share, overflow() and the batch-L forward replay.
 """
 import argparse
 import json
@@ -204,6 +212,73 @@ def sampling_main(args, dev):
             np.linalg.norm(boxes["device"][:, :3] - boxes["reference"][:, :3], axis=1).max())}))
 
 
+def lanes_main(args, dev):
+    from open3dsot_amd import metrics as MT
+    L = args.lanes
+    if args.model.upper() == "M2TRACK":
+        model, cfg = motion_model(dev)
+    else:
+        cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+        cfg.update(TO.TEST_KEYS)
+        model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+    distinct = []
+    for j in range(min(args.distinct, args.tracklets)):
+        frames, gt = synth.make_sequence(args.seed + j, args.frames, args.points)
+        distinct.append(([torch.from_numpy(f).to(dev) for f in frames], torch.from_numpy(gt).to(dev)))
+    tracklets = [distinct[j % len(distinct)] for j in range(args.tracklets)]
+    tracked = args.tracklets * (args.frames - 1)
+    lane, one = tracking.lane_tracker_for(model, L), tracking.tracker_for(model, sampling="device")
+    results = {}
+
+    def run_lanes():
+        m = MT.SuccessPrecision(device=dev)
+        lane.run(tracklets)
+        lane.score(metrics=m)
+        return m.compute()                                              # the one read-back (a sync)
+
+    def run_sequential():
+        m = MT.SuccessPrecision(device=dev)
+        for frames, gt in tracklets:
+            tracking.evaluate_sequence(model, frames, gt, tracker=one, metrics=m)
+        return m.compute()
+
+    loops = {"lanes": run_lanes, "sequential": run_sequential}
+    warm = [distinct[0]] * min(2 * L, args.tracklets)
+    lane.run(warm)                                                      # capture + warm-up
+    tracking.evaluate_sequence(model, *distinct[0], tracker=one)
+    torch.cuda.synchronize()
+    times = {k: [] for k in loops}
+    for _ in range(args.repeats):                                       # the two epochs in turn: what disturbs one disturbs the other
+        for k, loop in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            results[k] = loop()
+            times[k].append(time.perf_counter() - t0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        lane._network()
+    torch.cuda.synchronize()
+    fwd_ms = (time.perf_counter() - t0) / 200 * 1e3
+    fps = {k: sorted(tracked / dt for dt in times[k]) for k in loops}
+    mid = {k: fps[k][len(fps[k]) // 2] for k in loops}
+    idle = float((lane.schedule[0] < 0).mean())
+    print(json.dumps({
+        "workload": "%s test epoch: %d tracklets of %d frames of %d points (%d distinct synthetic sequences, fixture weights, eval, "
+                    "fp32), median of %d runs, the two epochs in turn" % (args.model.upper(), args.tracklets, args.frames, args.points,
+                                                                          len(distinct), args.repeats),
+        "lanes": L, "steps": int(lane.steps), "idle_lane_share": round(idle, 4), "chunk_uploads": lane.uploads,
+        "lanes_tracklet_frames_per_s": round(mid["lanes"], 1), "sequential_tracklet_frames_per_s": round(mid["sequential"], 1),
+        "lanes_over_sequential": round(mid["lanes"] / mid["sequential"], 3),
+        "lanes_tracklet_frames_per_s_min_max": [round(fps["lanes"][0], 1), round(fps["lanes"][-1], 1)],
+        "sequential_tracklet_frames_per_s_min_max": [round(fps["sequential"][0], 1), round(fps["sequential"][-1], 1)],
+        "lanes_ms_per_step": round(1e3 * tracked / mid["lanes"] / max(lane.steps, 1), 4),
+        "sequential_ms_per_frame": round(1e3 / mid["sequential"], 4), "batch_L_forward_replay_ms": round(fwd_ms, 4),
+        "hip_graph": [lane.graph is not None, one.graph is not None], "lanes_overflow": list(lane.overflow()),
+        "success_precision": {k: [round(float(v["success"]), 3), round(float(v["precision"]), 3)] for k, v in results.items()},
+        "scored_frames": [int(v["frames"]) for v in results.values()]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
@@ -213,12 +288,19 @@ def main():
     ap.add_argument("--targets", type=int, default=0, help="K > 0: the batched K-target loop against K single-target trackers in turn")
     ap.add_argument("--sampling", default="reference", choices=tracking.SAMPLING,
                     help="device: the free-running loop against the reference-sampling loop, frames/s of both")
-    ap.add_argument("--repeats", type=int, default=15, help="--sampling device: timed runs per loop (the median is reported)")
+    ap.add_argument("--repeats", type=int, default=15, help="--sampling device, --lanes: timed runs per loop (the median is reported)")
+    ap.add_argument("--lanes", type=int, default=0, help="L > 0: the test epoch on L lanes against the sequential free-running epoch")
+    ap.add_argument("--tracklets", type=int, default=64, help="--lanes: tracklets of the epoch, --frames frames each")
+    ap.add_argument("--distinct", type=int, default=8, help="--lanes: different synthetic sequences, used in rotation")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("track_bench.py needs a GPU: the HIP library is the only compute path (no CPU fallback)")
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
+    if args.lanes > 0:
+        if args.targets > 0 or args.frames < 2:
+            raise SystemExit("--lanes times the test epoch: no --targets, at least 2 frames per tracklet")
+        return lanes_main(args, dev)
     if args.targets > 0:
         if args.sampling == "device":
             raise SystemExit("--sampling device times the single-target loops; the K-target loops have no device sampling yet")
