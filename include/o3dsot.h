@@ -973,6 +973,28 @@ typedef struct {
 } o3d_train_motion_sample_args;
 int o3d_train_motion_sample(const o3d_train_motion_sample_args* args, void* stream);
 
+/* ---- the planned training epoch (csrc/train_batch.hip; sampler.py's build_planned is the caller): what the host wrote into
+ * the per-batch upload -- the candidates' ground-truth boxes and their random draws -- made on the device instead.  One
+ * launch per batch, one thread per candidate, no LDS, no atomics.  gt (R,15): the box pool of all tracklets, resident.
+ * rows: the pool rows of candidate j's frames, (J,3) int32 = first / template / search (O3D_TRAIN_DRAW_SIAMESE) or (J,2) =
+ * previous / current (the motion modes); cand (J) int32: the candidate ids.  A row outside [0, R) is never read and gives a
+ * zero box.  seed, counter: the uint32 of the index draw, carried in the bits of an int.
+ *   O3D_TRAIN_DRAW_SIAMESE     refs (2J,15) = [template boxes | search boxes], first (J,15), offs (2J,4) = [template jitter |
+ *                              search offset] as (x, y, 0, theta); aug is not used
+ *   O3D_TRAIN_DRAW_MOTION      refs (2J,15) = [previous | current], offs (J,4) the jitter; first and aug are not used
+ *   O3D_TRAIN_DRAW_MOTION_AUG  and aug (2J,6) = [previous | current] rows of (tx, ty, tz, rotation in degrees, flip_x, flip_y)
+ * The draw is keyed by (seed, counter, j, tag, component) and written down at the head of csrc/train_batch.hip
+ * (tests/epoch_plan_oracle.py restates it): uniform +-0.3 jitter with the angle x5 (`degrees`) or x deg2rad(5), standard
+ * normal x sqrt((1, 1, 5 | deg2rad(5))) for the search offset, translation +-0.3 / rotation +-10 degrees / two fair bits for
+ * the augmentation.  Candidate id 0: a zero jitter; a zero search offset when num_candidates > 1.
+ * O3D_EINVAL, before any HIP call: a NULL operand that the mode uses, J outside 1..O3D_TRAIN_MAX_CANDIDATES, R < 1,
+ * num_candidates < 1, an unknown mode. */
+#define O3D_TRAIN_DRAW_SIAMESE 0
+#define O3D_TRAIN_DRAW_MOTION 1
+#define O3D_TRAIN_DRAW_MOTION_AUG 2
+int o3d_train_draw(const float* gt, int R, const int32_t* rows, const int32_t* cand, int J, int seed, int counter, int degrees,
+                   int num_candidates, int mode, float* refs, float* first, float* offs, float* aug, void* stream);
+
 /* estimateOverlap / estimateAccuracy (utils/metrics.py:27-72) for n box pairs in one launch: a (n,15) the annotation boxes,
  * b (n,15) the result boxes, e.g. the flattened (T,K) rows of a tracker's results buffer.  valid (n) int32 | NULL: a row with
  * valid == 0 is skipped entirely (its outputs are not written, nothing is counted).  dim = 2 (BEV) | 3; up = 1 | 2, the index

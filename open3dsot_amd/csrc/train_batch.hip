@@ -20,6 +20,8 @@
 //   o3d_train_select_motion     which candidates fill the batch (sampler.py:99,120)
 //   o3d_train_motion_sample     (track.hip, beside motion_row) regularize_pc of both halves, the row's channels, seg_label, the label rows
 //   o3d_boxcloud (2)            prev_bc, this_bc
+// and in front of either list on the planned route (sampler.py's build_planned), in place of the per-batch upload:
+//   o3d_train_draw              the candidates' boxes gathered from the resident pool, and the draws of the batch
 //
 // Every keep decision (the crops and seg_label) is crop_test or inside_box, every row gather gather_row: the definitions of
 // track_common.hpp, which track.hip uses.  This file is compiled with -ffp-contract=off like track.hip.
@@ -64,6 +66,25 @@
 //       P(i):  x = E(i);  while x >= n: x = E(x)                                cycle walking
 //   The walk stays on the cycle of E through i, which comes back to i < n: it ends after at most 2^(2h) - n + 1 < 4 n
 //   applications, 2^(2h) / n < 4 in the mean.  It is a register-only loop that reads no memory.
+//
+// ---- o3d_train_draw: the boxes and the random numbers of a planned batch (tests/epoch_plan_oracle.py restates it) ------------------------
+// One thread per candidate j gathers its frames' boxes from the resident pool and draws what the host drew from a numpy
+// Generator on the per-batch route.  The key is the index draw's with tags beyond its clouds 0 / 1, one tag per drawn vector:
+//   key(tag) = mix32( (seed * 0x9E3779B1) ^ (counter * 0x85EBCA77 + j * 0xC2B2AE3D + tag * 0x27D4EB2F + 0x165667B1) )
+//         tag = 2 the (template) jitter | 3 the search offset | 4 the previous frame's augmentation | 5 the current frame's
+//   h(c) = mix32( key(tag) ^ (c * 0x9E3779B1 + 0x85EBCA77) )                       component c of the vector, a uint32
+// In double, rounded to fp32 once at the end:
+//   u(h)            = ((h >> 8) + 0.5) * 2^-24                                      in (0, 1)
+//   uniform(lo, hi) = lo + (hi - lo) * u(h)
+//   normal(ha, hb)  = sqrt(-2 log u(ha)) * cos((2 pi) * ((hb >> 8) * 2^-24))        Box-Muller
+//   ang             = 5 with `degrees`, 5 * (pi / 180) otherwise
+//   jitter (tag 2)          (x, y) = uniform(-0.3, 0.3) of h(0), h(1);  theta = uniform(-0.3, 0.3) of h(2), times ang
+//   search offset (tag 3)   (x, y) = normal(h(0), h(1)), normal(h(2), h(3));  theta = normal(h(4), h(5)) * sqrt(ang)
+//   augmentation (tag 4, 5) (tx, ty, tz) = uniform(-0.3, 0.3) of h(0..2);  rot = uniform(-10, 10) of h(3);
+//                           flip_x = h(4) >> 31, flip_y = h(5) >> 31                (1.0 | 0.0)
+// Zero rows (the reference's): candidate id 0 has a zero jitter, and with num_candidates > 1 a zero search offset; the
+// augmentation is drawn for every candidate.  offs rows are (x, y, 0, theta).  A pool row outside [0, R) is not read: its box
+// is 15 zeros, whose crops (scale 1 or model mode, offset 0) count nothing, so the candidate is invalid.
 //
 // ---- fixed capacities -----------------------------------------------------------------------------------------------------------------
 // A crop is written into a buffer of `capacity` rows; a longer one is truncated to its first `capacity` survivors (the crop's
@@ -297,6 +318,72 @@ __global__ __launch_bounds__(256) void train_augment_kernel(AugmentArgs a) {
     a.aug[i] = rec;
 }
 
+// ---- o3d_train_draw -------------------------------------------------------------------------------------------------------------------
+struct DrawArgs {
+    const float* gt; int R; const int32_t* rows; const int32_t* cand; int J; unsigned seed, counter; int degrees, num_candidates, mode;
+    float* refs; float* first; float* offs; float* aug;
+};
+
+__device__ __forceinline__ unsigned draw_key(unsigned seed, unsigned counter, unsigned j, unsigned tag) {
+    return mix32((seed * 0x9E3779B1u) ^ (counter * 0x85EBCA77u + j * 0xC2B2AE3Du + tag * 0x27D4EB2Fu + 0x165667B1u));
+}
+__device__ __forceinline__ unsigned draw_bits(unsigned key, unsigned c) { return mix32(key ^ (c * 0x9E3779B1u + 0x85EBCA77u)); }
+__device__ __forceinline__ double draw_u(unsigned h) { return ((double)(h >> 8) + 0.5) * (1.0 / 16777216.0); }
+__device__ __forceinline__ double draw_uniform(unsigned h, double lo, double hi) { return lo + (hi - lo) * draw_u(h); }
+__device__ __forceinline__ double draw_normal(unsigned ha, unsigned hb) {
+    return sqrt(-2.0 * log(draw_u(ha))) * cos((2.0 * 3.14159265358979323846) * ((double)(hb >> 8) * (1.0 / 16777216.0)));
+}
+
+// box `row` of the pool -> dst (15); a row outside the pool is not read
+__device__ __forceinline__ void draw_gather(const float* __restrict__ gt, int R, int row, float* __restrict__ dst) {
+    const bool ok = row >= 0 && row < R;
+    const float* src = gt + 15 * (long)(ok ? row : 0);
+    for (int e = 0; e < 15; ++e) dst[e] = ok ? src[e] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void train_draw_kernel(DrawArgs a) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.J) return;
+    const int J = a.J, cid = a.cand[j];
+    const bool siamese = a.mode == O3D_TRAIN_DRAW_SIAMESE;
+    const double ang = a.degrees ? 5.0 : 5.0 * (3.14159265358979323846 / 180.0);
+    const int32_t* rows = a.rows + (siamese ? 3 : 2) * (long)j;
+    if (siamese) draw_gather(a.gt, a.R, rows[0], a.first + 15 * (long)j);
+    draw_gather(a.gt, a.R, rows[siamese ? 1 : 0], a.refs + 15 * (long)j);
+    draw_gather(a.gt, a.R, rows[siamese ? 2 : 1], a.refs + 15 * (long)(J + j));
+    float* o = a.offs + 4 * (long)j;                       // the jitter
+    if (cid == 0) {
+        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
+    } else {
+        const unsigned key = draw_key(a.seed, a.counter, (unsigned)j, 2u);
+        o[0] = (float)draw_uniform(draw_bits(key, 0u), -0.3, 0.3);
+        o[1] = (float)draw_uniform(draw_bits(key, 1u), -0.3, 0.3);
+        o[2] = 0.f;
+        o[3] = (float)(draw_uniform(draw_bits(key, 2u), -0.3, 0.3) * ang);
+    }
+    if (siamese) {                                         // the search offset
+        float* s = a.offs + 4 * (long)(J + j);
+        if (cid == 0 && a.num_candidates > 1) {
+            s[0] = 0.f; s[1] = 0.f; s[2] = 0.f; s[3] = 0.f;
+        } else {
+            const unsigned key = draw_key(a.seed, a.counter, (unsigned)j, 3u);
+            s[0] = (float)draw_normal(draw_bits(key, 0u), draw_bits(key, 1u));
+            s[1] = (float)draw_normal(draw_bits(key, 2u), draw_bits(key, 3u));
+            s[2] = 0.f;
+            s[3] = (float)(draw_normal(draw_bits(key, 4u), draw_bits(key, 5u)) * sqrt(ang));
+        }
+    } else if (a.mode == O3D_TRAIN_DRAW_MOTION_AUG) {
+        for (int f = 0; f < 2; ++f) {                      // the previous frame's draw, the current frame's
+            const unsigned key = draw_key(a.seed, a.counter, (unsigned)j, 4u + (unsigned)f);
+            float* g = a.aug + 6 * (long)(f * J + j);
+            for (unsigned c = 0; c < 3; ++c) g[c] = (float)draw_uniform(draw_bits(key, c), -0.3, 0.3);
+            g[3] = (float)draw_uniform(draw_bits(key, 3u), -10.0, 10.0);
+            g[4] = (float)(draw_bits(key, 4u) >> 31);
+            g[5] = (float)(draw_bits(key, 5u) >> 31);
+        }
+    }
+}
+
 // ---- o3d_train_inside_box -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void train_inside_box_kernel(const float* __restrict__ points, int n, const float* __restrict__ box,
                                                                float factor, int32_t* __restrict__ mask) {
@@ -461,6 +548,17 @@ extern "C" int o3d_train_augment(const float* gt, const float* draw, const int32
         return O3D_EINVAL;
     AugmentArgs a{gt, draw, slot_src, K, n_slots, out_box, aug};
     hipLaunchKernelGGL(train_augment_kernel, dim3(o3d_cdiv(n_slots, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_train_draw(const float* gt, int R, const int32_t* rows, const int32_t* cand, int J, int seed, int counter, int degrees,
+                              int num_candidates, int mode, float* refs, float* first, float* offs, float* aug, void* stream) {
+    if (mode != O3D_TRAIN_DRAW_SIAMESE && mode != O3D_TRAIN_DRAW_MOTION && mode != O3D_TRAIN_DRAW_MOTION_AUG) return O3D_EINVAL;
+    if (!gt || !rows || !cand || !refs || !offs || (mode == O3D_TRAIN_DRAW_SIAMESE && !first) || (mode == O3D_TRAIN_DRAW_MOTION_AUG && !aug) ||
+        J < 1 || J > O3D_TRAIN_MAX_CANDIDATES || R < 1 || num_candidates < 1)
+        return O3D_EINVAL;
+    DrawArgs a{gt, R, rows, cand, J, (unsigned)seed, (unsigned)counter, degrees != 0, num_candidates, mode, refs, first, offs, aug};
+    hipLaunchKernelGGL(train_draw_kernel, dim3(o3d_cdiv(J, 256)), dim3(256), 0, o3d_stream(stream), a);
     return o3d_launch_status();
 }
 

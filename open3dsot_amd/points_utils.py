@@ -850,16 +850,19 @@ def _addr(t):
     return None if t is None else (t.data_ptr() if torch.is_tensor(t) else int(t))
 
 
-def train_augment(gt, draw, out_box, aug, slot_src=None):
+def train_augment(gt, draw, out_box, aug, slot_src=None, n_slots=None):
     """One o3d_train_augment launch: gt (K,15), draw (K,6) float32 GPU -> out_box (K,15) and the records `aug` (a uint8 GPU
-    tensor of n_slots CROP_AUG records, or an address with slot_src given); slot_src (n_slots,) int32 GPU | None"""
+    tensor of n_slots CROP_AUG records, or an address with slot_src given); slot_src (n_slots,) int32 GPU | None, or an
+    address with n_slots given"""
     for t, width in ((gt, 15), (draw, 6), (out_box, 15)):
         _need_gpu(t, "train_augment")
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() % width == 0
     K = gt.numel() // 15
     assert draw.numel() == 6 * K and out_box.numel() == 15 * K
-    n_slots = K if slot_src is None else slot_src.numel()
-    assert slot_src is None or (slot_src.is_cuda and slot_src.dtype == torch.int32 and slot_src.is_contiguous())
+    if torch.is_tensor(slot_src):
+        assert slot_src.is_cuda and slot_src.dtype == torch.int32 and slot_src.is_contiguous()
+        n_slots = slot_src.numel()
+    n_slots = K if slot_src is None else int(n_slots)
     assert not torch.is_tensor(aug) or (aug.is_cuda and aug.is_contiguous() and aug.numel() * aug.element_size() >= n_slots * CROP_AUG.itemsize)
     dev = gt.device
     with torch.cuda.device(dev):
@@ -933,3 +936,31 @@ def train_motion_sample(args, device):
     with torch.cuda.device(device):
         capi.check(capi.load().o3d_train_motion_sample(ctypes.addressof(args), torch.cuda.current_stream(device).cuda_stream),
                    "o3d_train_motion_sample")
+
+
+# ---- the planned training epoch (csrc/train_batch.hip; sampler.py's build_planned is the caller) ------------------------------
+TRAIN_DRAW_SIAMESE = capi.CONSTANTS["O3D_TRAIN_DRAW_SIAMESE"]
+TRAIN_DRAW_MOTION = capi.CONSTANTS["O3D_TRAIN_DRAW_MOTION"]
+TRAIN_DRAW_MOTION_AUG = capi.CONSTANTS["O3D_TRAIN_DRAW_MOTION_AUG"]
+
+
+def train_draw(gt, rows, cand, J, seed, counter, degrees, num_candidates, mode, refs, first, offs, aug):
+    """One o3d_train_draw launch (no sync): gt (R,15) float32 GPU = the box pool; rows (J,3 | J,2) and cand (J,) int32 GPU
+    tensors, or addresses inside an uploaded chunk -> refs (2J,15), first (J,15) | None, offs (2J,4 | J,4), aug (2J,6) | None,
+    float32 GPU tensors written in place"""
+    _need_gpu(gt, "train_draw")
+    assert gt.dtype == torch.float32 and gt.is_contiguous() and gt.dim() == 2 and gt.shape[1] == 15
+    siamese = mode == TRAIN_DRAW_SIAMESE
+    for t, numel in ((refs, 30 * J), (first, 15 * J if siamese else None), (offs, (8 if siamese else 4) * J),
+                     (aug, 12 * J if mode == TRAIN_DRAW_MOTION_AUG else None)):
+        if numel is not None:
+            _need_gpu(t, "train_draw")
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= numel and t.device == gt.device
+    for t, numel in ((rows, (3 if siamese else 2) * J), (cand, J)):
+        assert not torch.is_tensor(t) or (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= numel)
+    dev = gt.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_train_draw(
+            gt.data_ptr(), gt.shape[0], _addr(rows), _addr(cand), int(J), _key_bits(seed), _key_bits(counter), int(bool(degrees)),
+            int(num_candidates), int(mode), _addr(refs), _addr(first), _addr(offs), _addr(aug),
+            torch.cuda.current_stream(dev).cuda_stream), "o3d_train_draw")

@@ -21,6 +21,14 @@ points_utils.py:299-361) come from MotionBatchBuilder: one pinned upload and ten
     o3d_train_motion_sample      regularize_pc of both halves, the five point channels, candidate_bc, seg_label, the label rows
     o3d_boxcloud (2, box_aware)  prev_bc / this_bc
 
+The planned epoch (DeviceBatchSampler(plan_batches=P)): the epoch's order (epoch_order: shuffled like
+the reference's DataLoader) and frame choice are made for all samples at once, the tables of P batches travel in one pinned
+copy (plan_chunk), and a batch is build_planned: no per-batch upload, no numpy Generator, and one launch in front of the ones
+above
+
+    o3d_train_draw               the candidates' boxes gathered from the resident pool; the box jitter, the search offset and
+                                 the augmentation drawn with the keyed generator of the resampling indices
+
 Not covered (DESIGN.md sections 13, 13b): use_augmentation for the siamese builder (a small follow-up now: one more fixture and
 the search frame's record only).  Real data arrives through datasets.KittiTracklets, which is a
 DeviceTracklets.
@@ -84,6 +92,121 @@ def _section(layout, name, nbytes):
     off = layout["_end"]
     layout[name] = (off, nbytes)
     layout["_end"] = off + -(-nbytes // 64) * 64
+
+
+# ---- the planned epoch: order, frame choice and the tables of P batches, all whole-array numpy (no device) -------------------
+def epoch_order(length, J, shuffle, seed, epoch, rank=0, world=1):
+    """-> (n_batches, J) int64 sample indices of `rank`'s batches of epoch `epoch`.  shuffle=False: arange; True:
+    default_rng([seed, epoch]).permutation(length) -- DataLoader(shuffle=True, drop_last=True), main.py:75.  Either is cut to
+    whole batches of J and to a whole number of rounds over the ranks; every rank computes the same order and takes batches
+    rank, rank + world, ... (no collective)."""
+    length, J, world = int(length), int(J), int(world)
+    if not (J >= 1 and 0 <= rank < world):
+        raise ValueError("epoch_order: J >= 1 and 0 <= rank < world")
+    order = np.random.default_rng([int(seed), int(epoch)]).permutation(length) if shuffle else np.arange(length)
+    n = length // J // world * world
+    return order[:n * J].astype(np.int64).reshape(n, J)[rank::world]
+
+
+def epoch_frames(index, starts, num_candidates, motion, draw=None):
+    """The frame choice of PointTrackingSampler / MotionTrackingSampler.__getitem__ for an array of sample indices ->
+    (tracklet, frames, candidate id): frames (..., 3) = (0, max(this - 1, 0), this), or (..., 2) = (max(this - 1, 0), this)
+    with `motion`; the annotations in order.  draw = random_draw(...)'s arrays: (0, two distinct random frames) of a random
+    tracklet instead, sample i taking entry i of the draw."""
+    index = np.asarray(index, np.int64)
+    anno, cand = index // num_candidates, index % num_candidates
+    if draw is not None:
+        t, a, b = (d[index] for d in draw)
+        return t, np.stack([np.zeros_like(a), a, b], -1), cand
+    t = np.searchsorted(starts, anno, side="right") - 1
+    this = anno - np.asarray(starts, np.int64)[t]
+    prev = np.maximum(this - 1, 0)
+    return t, np.stack([prev, this] if motion else [np.zeros_like(this), prev, this], -1), cand
+
+
+def random_draw(lengths, count, seed, epoch):
+    """random_sample for a whole epoch at once, from default_rng([seed, epoch, 1]): per sample a tracklet and two distinct
+    frames of it ((0, 0) for a one-frame tracklet) -> (tracklet, a, b), three (count,) int64 arrays"""
+    rng = np.random.default_rng([int(seed), int(epoch), 1])
+    lengths = np.asarray(lengths, np.int64)
+    t = rng.integers(0, len(lengths), count)
+    n = lengths[t]
+    a = rng.integers(0, n)
+    b = (a + 1 + rng.integers(0, np.maximum(n - 1, 1))) % n          # a + 1 .. a + n - 1 (mod n): never a again, unless n == 1
+    return t, a, b
+
+
+class ChunkTables:
+    """The tables of P planned batches of J candidates in ONE host buffer (`host`, uint8), which travels to the device in one
+    copy; `base` is the address of that copy (a plain integer: nothing here touches a device).  Views, batch-major: rows
+    (P,J,cols) and cand (P,J) int32, targets (P,3J) CROP_TARGET, plan (P,3J) CROP_PLAN of which batch k uses the first
+    groups[k], and with `aug` slots (P,3J) int32 / augptr (P,3J) uint64.  need[k] = batch k's scratch length, grid[k] = its
+    workgroups of the count / scatter launches."""
+
+    def __init__(self, P, J, cols, aug=False, base=0):
+        self.P, self.J, self.cols, self.aug, self.base = int(P), int(J), int(cols), bool(aug), int(base)
+        n_rec = 3 * self.J
+        self._per = {"rows": (self.J * self.cols * 4, np.int32, (self.J, self.cols)), "cand": (self.J * 4, np.int32, (self.J,))}
+        if self.aug:
+            self._per.update(slots=(n_rec * 4, np.int32, (n_rec,)), augptr=(n_rec * 8, np.uint64, (n_rec,)))
+        self._per.update(targets=(n_rec * PU.CROP_TARGET.itemsize, PU.CROP_TARGET, (n_rec,)),
+                         plan=(n_rec * PU.CROP_PLAN.itemsize, PU.CROP_PLAN, (n_rec,)))
+        self._layout = {"_end": 0}
+        for name, (nbytes, _, _) in self._per.items():
+            _section(self._layout, name, self.P * nbytes)
+        self.host = np.zeros(self._layout["_end"], np.uint8)
+        for name, (nbytes, dtype, shape) in self._per.items():
+            off = self._layout[name][0]
+            setattr(self, name, self.host[off:off + self.P * nbytes].view(dtype).reshape((self.P,) + shape))
+        self.groups, self.need, self.grid = (np.zeros(self.P, np.int64) for _ in range(3))
+
+    def dev(self, name, k=0):
+        """the device address of batch k's part of section `name`"""
+        return self.base + self._layout[name][0] + self._per[name][0] * k
+
+
+def plan_chunk(chunk, fptr, fn, rows, cand, rec, crop_cols, aug_base=None):
+    """Fill `chunk` for S <= P batches, in whole-chunk numpy: a pure function of integer arrays.  fptr, fn: per pool row the
+    frame's address and size; rows (S,J,cols) the pool rows of the candidates' frames, cand (S,J) their ids; rec (3,J) the
+    builder's fixed CROP_TARGET records; crop c of candidate j reads frame rows[:, j, crop_cols[c]].  Every distinct frame of
+    a batch is one group that holds the targets reading it; wg_start / row_start / sbase are prefix sums over the groups, what
+    o3d_track_crop_groups_scratch computes (o3d_track_crop_groups checks them again before it launches).  aug_base: the address
+    of the builder's CROP_AUG records -> slots (the record of target slot i: -1 for crop 0, else (c - 1) J + j) and augptr (per
+    group: its first record)."""
+    rows, cand = np.asarray(rows, np.int64), np.asarray(cand, np.int64)
+    S, J = rows.shape[0], chunk.J
+    n_rec = 3 * J
+    assert S <= chunk.P and rows.shape == (S, J, chunk.cols) and cand.shape == (S, J) and rec.shape == (3, J)
+    chunk.rows[:S], chunk.cand[:S] = rows, cand
+    frame = rows[:, :, list(crop_cols)].transpose(0, 2, 1).reshape(S, n_rec)        # of crop (c, j), at c J + j
+    order = np.argsort(frame, axis=1, kind="stable")                               # the targets of a frame side by side
+    frame = np.take_along_axis(frame, order, 1)
+    chunk.targets[:S] = rec.reshape(-1)[order]
+    new = np.ones((S, n_rec), bool)
+    new[:, 1:] = frame[:, 1:] != frame[:, :-1]
+    gid = np.cumsum(new, 1) - 1
+    p, pos = np.nonzero(new)                                                       # one entry per group, batch-major
+    g = gid[p, pos]
+    last = np.append(p[1:] != p[:-1], True)
+    k = np.where(last, n_rec, np.append(pos[1:], n_rec)) - pos                     # the group's targets
+    key = frame[p, pos]
+    n = fn[key]
+    wgs = np.maximum(1, -(-n // 256))
+    head = np.flatnonzero(g == 0)
+
+    def before(v):                                                                 # the sum over the earlier groups of the batch
+        c = np.cumsum(v) - v
+        return c - c[head][p]
+    plan = chunk.plan[:S]
+    plan["points"][p, g], plan["n"][p, g], plan["n_targets"][p, g] = fptr[key], n, k
+    plan["targets"][p, g] = chunk.dev("targets") + PU.CROP_TARGET.itemsize * (p * n_rec + pos)
+    plan["wg_start"][p, g], plan["row_start"][p, g], plan["sbase"][p, g] = before(wgs), pos, before(wgs * k)
+    chunk.groups[:S] = gid[:, -1] + 1
+    chunk.need[:S], chunk.grid[:S] = np.bincount(p, wgs * k, S), np.bincount(p, wgs, S)
+    if aug_base is not None:
+        c, j = order // J, order % J
+        chunk.slots[:S] = np.where(c == 0, -1, (c - 1) * J + j)
+        chunk.augptr[p, g] = int(aug_base) + PU.CROP_AUG.itemsize * pos
 
 
 class _DeviceBatchBuilder:
@@ -169,6 +292,40 @@ class _DeviceBatchBuilder:
         self._up[:nbytes].copy_(self._pinned[slot][:nbytes], non_blocking=True)       # THE upload of this batch
         self._events[slot].record(stream)
         self._used[slot] = True
+
+    # ---- the planned route (DeviceBatchSampler(plan_batches=P) drives it) -------------------------------------------------------------
+    def bind(self, tracklets):
+        """The resident state of the planned route, made once: every tracklet's boxes end to end in one device pool `_gt` (R,15)
+        (tracklet t owns rows [row0[t], row0[t + 1])), per pool row the frame's address and size, the fixed buffers that
+        o3d_train_draw writes and the target records that point at them"""
+        frames = [x for t in tracklets for x in t.frames]
+        dev = frames[0].device
+        if self.device is None:
+            with torch.cuda.device(dev):
+                self._allocate(dev)
+        assert dev == self.device
+        self._bound = tracklets                            # the frames stay alive as long as their addresses are planned
+        self.row0 = np.concatenate([[0], np.cumsum([len(t) for t in tracklets])]).astype(np.int64)
+        self._fptr = np.array([x.data_ptr() for x in frames], np.int64)
+        self._fn = np.array([x.shape[0] for x in frames], np.int64)
+        with torch.cuda.device(dev):
+            self._gt = torch.from_numpy(np.concatenate([t.boxes for t in tracklets])).to(dev)
+            self._bind_buffers(dev)
+
+    def reserve_scratch(self, need):
+        if self._scratch.numel() < need:
+            with torch.cuda.device(self.device):
+                self._scratch = torch.empty(int(need), dtype=torch.int32, device=self.device)
+
+    def plan(self, chunk, rows, cand):
+        """plan_chunk for this builder's records: rows (S,J,cols) pool rows, cand (S,J) -> the chunk's host tables"""
+        plan_chunk(chunk, self._fptr, self._fn, rows, cand, self._rec_planned, self.crop_cols,
+                   self._aug.data_ptr() if getattr(self, "augment", False) else None)
+
+    def draws(self):
+        """what o3d_train_draw wrote for the last planned build: {refs, first, offs, aug} device tensors (None where the
+        builder has none); the next planned build overwrites them"""
+        return {"refs": self._p_refs, "first": self._p_first, "offs": self._p_offs, "aug": self._p_aug}
 
     def _outputs(self, out, dev):
         res = {}
@@ -305,28 +462,53 @@ class SiameseBatchBuilder(_DeviceBatchBuilder):
             idx_t, idx_s = self._dev("idx_t"), self._dev("idx_s")
         with torch.cuda.device(dev):
             self._upload(slot, nbytes, stream)
-            refs_d, offs_d = self._dev32("refs", 2 * J * 15), self._dev32("offs", 2 * J * 4)
-            PU.offset_box_multi(refs_d, offs_d, out=self._jit, degrees=self.degrees, use_z=False, limit_box=self.limit_box,
-                                seed=(self.seed + 7919 * self.counter) & 0x3fffffff)
-            PU.train_labels(refs_d[J * 15:], self._jit[J:], self._jit[:J], offs_d[J * 4:], self._search_box, self._cand_label,
-                            self._cand_size, self._model_box)
-            PU.crop_groups(plan, self._dev("plan"), self._scratch)
-            res = self._outputs(out, dev)
-            PU.train_select(self.counts, B, self.caps, self.sel, res["n_valid"], res["overflow"])
-            a = PU._TrainSampleArgs(
-                self.sel.data_ptr(), self.counts.data_ptr(), self.crops[0].data_ptr(), self.crops[1].data_ptr(), self.crops[2].data_ptr(),
-                self.caps[0], self.caps[1], self.caps[2], J, B, M, N, idx_t, idx_s, self.seed & 0xffffffff, self.counter & 0xffffffff,
-                self._search_box.data_ptr(), self._model_box.data_ptr(), self._cand_label.data_ptr(), self._cand_size.data_ptr(),
-                res["template_points"].data_ptr(), res["search_points"].data_ptr(), res["seg_label"].data_ptr(),
-                res["box_label"].data_ptr(), res["bbox_size"].data_ptr(), self._bc_boxes.data_ptr() if self.box_aware else None,
-                self.used_t.data_ptr() if self.record_indices else None, self.used_s.data_ptr() if self.record_indices else None)
-            PU.train_sample(a, dev)
-            if self.box_aware:
-                for w, (pts, key) in enumerate(((res["template_points"], "points2cc_dist_t"), (res["search_points"], "points2cc_dist_s"))):
-                    b = self._bc_boxes[w]
-                    PU.boxcloud_into(res[key], pts, b[:3 * B], b[3 * B:6 * B], b[6 * B:])
+            return self._launch(self._dev32("refs", 2 * J * 15), self._dev32("offs", 2 * J * 4), plan, self._dev("plan"), idx_t, idx_s, out, dev)
+
+    def _launch(self, refs_d, offs_d, plan, dev_plan, idx_t, idx_s, out, dev):
+        """the launches of a build behind its tables, shared by build() and build_planned(): refs_d (2J*15), offs_d (2J*4) on
+        the device, plan = the batch's planned CROP_PLAN rows on the host and dev_plan their device copy"""
+        J, B, M, N = self.J, self.B, self.M, self.N
+        PU.offset_box_multi(refs_d, offs_d, out=self._jit, degrees=self.degrees, use_z=False, limit_box=self.limit_box,
+                            seed=(self.seed + 7919 * self.counter) & 0x3fffffff)
+        PU.train_labels(refs_d[J * 15:], self._jit[J:], self._jit[:J], offs_d[J * 4:], self._search_box, self._cand_label,
+                        self._cand_size, self._model_box)
+        PU.crop_groups(plan, dev_plan, self._scratch)
+        res = self._outputs(out, dev)
+        PU.train_select(self.counts, B, self.caps, self.sel, res["n_valid"], res["overflow"])
+        a = PU._TrainSampleArgs(
+            self.sel.data_ptr(), self.counts.data_ptr(), self.crops[0].data_ptr(), self.crops[1].data_ptr(), self.crops[2].data_ptr(),
+            self.caps[0], self.caps[1], self.caps[2], J, B, M, N, idx_t, idx_s, self.seed & 0xffffffff, self.counter & 0xffffffff,
+            self._search_box.data_ptr(), self._model_box.data_ptr(), self._cand_label.data_ptr(), self._cand_size.data_ptr(),
+            res["template_points"].data_ptr(), res["search_points"].data_ptr(), res["seg_label"].data_ptr(),
+            res["box_label"].data_ptr(), res["bbox_size"].data_ptr(), self._bc_boxes.data_ptr() if self.box_aware else None,
+            self.used_t.data_ptr() if self.record_indices else None, self.used_s.data_ptr() if self.record_indices else None)
+        PU.train_sample(a, dev)
+        if self.box_aware:
+            for w, (pts, key) in enumerate(((res["template_points"], "points2cc_dist_t"), (res["search_points"], "points2cc_dist_s"))):
+                b = self._bc_boxes[w]
+                PU.boxcloud_into(res[key], pts, b[:3 * B], b[3 * B:6 * B], b[6 * B:])
         self.counter += 1
         return res
+
+    # ---- the planned route ------------------------------------------------------------------------------------------------------------
+    crop_cols = (0, 1, 2)                                  # crop c of a candidate reads the frame of column crop_cols[c] of `rows`
+
+    def _bind_buffers(self, dev):
+        J = self.J
+        self._p_refs, self._p_first = (torch.zeros((n, 15), dtype=torch.float32, device=dev) for n in (2 * J, J))
+        self._p_offs, self._p_aug = torch.zeros((2 * J, 4), dtype=torch.float32, device=dev), None
+        self._rec_planned = self._rec.copy()
+        self._rec_planned["box"][0] = self._p_first.data_ptr() + 60 * np.arange(J, dtype=np.uint64)
+
+    def build_planned(self, chunk, k, out=None):
+        """batch k of the uploaded `chunk` (a ChunkTables that plan_chunk filled, its device copy at chunk.base): o3d_train_draw,
+        then build()'s launches.  No numpy Generator, no pinned write, no upload, no synchronisation."""
+        J, dev = self.J, self.device
+        with torch.cuda.device(dev):
+            PU.train_draw(self._gt, chunk.dev("rows", k), chunk.dev("cand", k), J, self.seed & 0xffffffff, self.counter & 0xffffffff,
+                          self.degrees, self.num_candidates, PU.TRAIN_DRAW_SIAMESE, self._p_refs, self._p_first, self._p_offs, None)
+            return self._launch(self._p_refs.view(-1), self._p_offs.view(-1), chunk.plan[k, :chunk.groups[k]], chunk.dev("plan", k),
+                                None, None, out, dev)
 
     def _shapes(self):
         B, M, N = self.B, self.M, self.N
@@ -470,41 +652,71 @@ class MotionBatchBuilder(_DeviceBatchBuilder):
             idx_prev, idx_this = self._dev("idx_prev"), self._dev("idx_this")
         with torch.cuda.device(dev):
             self._upload(slot, nbytes, stream)
-            gt = self._dev32("refs", 2 * J * 15)
+            aug_d = slots_d = None
             if self.augment:
                 s0 = self._layout["slots"][0] // 4
-                PU.train_augment(gt, self._dev32("aug", 2 * J * 6), self._gt_aug, self._aug,
-                                 self._up.view(torch.int32)[s0:s0 + 3 * J])
-                gt = self._gt_aug.view(-1)
-            PU.offset_box_multi(gt[:J * 15], self._dev32("offs", J * 4), out=self._ref_box, degrees=self.degrees, use_z=False,
-                                limit_box=self.limit_box, seed=(self.seed + 7919 * self.counter) & 0x3fffffff)
-            PU.train_motion_labels(gt[:J * 15], gt[J * 15:], self._ref_box, self.degrees, self.motion_threshold, self._this_box,
-                                   self._prev_box, self._canon_box, self._cand_label, self._cand_label_prev, self._cand_motion,
-                                   self._cand_state, self._cand_size)
-            if self.augment:
-                PU.crop_groups_aug(plan, self._dev("plan"), self._dev("augptr"), self._scratch)
-            else:
-                PU.crop_groups(plan, self._dev("plan"), self._scratch)
-            res = self._outputs(out, dev)
-            PU.train_select_motion(self.counts, B, self.caps, self.sel, res["n_valid"], res["overflow"])
-            bc = self.box_aware
-            a = PU._TrainMotionSampleArgs(
-                self.sel.data_ptr(), self.counts.data_ptr(), self.crops[0].data_ptr(), self.crops[1].data_ptr(), self.caps[0],
-                self.caps[1], J, B, N, idx_prev, idx_this, self._dev("cand"), self.seed & 0xffffffff, self.counter & 0xffffffff,
-                self._prev_box.data_ptr(), self._this_box.data_ptr(), self._canon_box.data_ptr(), self._cand_label.data_ptr(),
-                self._cand_label_prev.data_ptr(), self._cand_motion.data_ptr(), self._cand_state.data_ptr(), self._cand_size.data_ptr(),
-                res["points"].data_ptr(), res["candidate_bc"].data_ptr() if bc else None, res["seg_label"].data_ptr(),
-                res["box_label"].data_ptr(), res["box_label_prev"].data_ptr(), res["motion_label"].data_ptr(),
-                res["motion_state_label"].data_ptr(), res["bbox_size"].data_ptr(), self._bc_boxes.data_ptr() if bc else None,
-                self._xyz.data_ptr() if bc else None, self.used_prev.data_ptr() if self.record_indices else None,
-                self.used_this.data_ptr() if self.record_indices else None)
-            PU.train_motion_sample(a, dev)
-            if bc:
-                for w, key in enumerate(("prev_bc", "this_bc")):
-                    b = self._bc_boxes[w]
-                    PU.boxcloud_into(res[key], self._xyz[w], b[:3 * B], b[3 * B:6 * B], b[6 * B:])
+                aug_d, slots_d = self._dev32("aug", 2 * J * 6), self._up.view(torch.int32)[s0:s0 + 3 * J]
+            return self._launch(self._dev32("refs", 2 * J * 15), self._dev32("offs", J * 4), aug_d, slots_d, self._dev("augptr"),
+                                self._dev("cand"), plan, self._dev("plan"), idx_prev, idx_this, out, dev)
+
+    def _launch(self, gt, offs_d, aug_d, slots_d, augptr_d, cand_d, plan, dev_plan, idx_prev, idx_this, out, dev):
+        """the launches of a build behind its tables, shared by build() and build_planned(): gt (2J*15), offs_d (J*4), aug_d
+        (2J*6) on the device; slots_d = the record slots (a tensor or an address), augptr_d, cand_d, dev_plan = addresses"""
+        J, B, N = self.J, self.B, self.N
+        if self.augment:
+            PU.train_augment(gt, aug_d, self._gt_aug, self._aug, slots_d, n_slots=3 * J)
+            gt = self._gt_aug.view(-1)
+        PU.offset_box_multi(gt[:J * 15], offs_d, out=self._ref_box, degrees=self.degrees, use_z=False,
+                            limit_box=self.limit_box, seed=(self.seed + 7919 * self.counter) & 0x3fffffff)
+        PU.train_motion_labels(gt[:J * 15], gt[J * 15:], self._ref_box, self.degrees, self.motion_threshold, self._this_box,
+                               self._prev_box, self._canon_box, self._cand_label, self._cand_label_prev, self._cand_motion,
+                               self._cand_state, self._cand_size)
+        if self.augment:
+            PU.crop_groups_aug(plan, dev_plan, augptr_d, self._scratch)
+        else:
+            PU.crop_groups(plan, dev_plan, self._scratch)
+        res = self._outputs(out, dev)
+        PU.train_select_motion(self.counts, B, self.caps, self.sel, res["n_valid"], res["overflow"])
+        bc = self.box_aware
+        a = PU._TrainMotionSampleArgs(
+            self.sel.data_ptr(), self.counts.data_ptr(), self.crops[0].data_ptr(), self.crops[1].data_ptr(), self.caps[0],
+            self.caps[1], J, B, N, idx_prev, idx_this, cand_d, self.seed & 0xffffffff, self.counter & 0xffffffff,
+            self._prev_box.data_ptr(), self._this_box.data_ptr(), self._canon_box.data_ptr(), self._cand_label.data_ptr(),
+            self._cand_label_prev.data_ptr(), self._cand_motion.data_ptr(), self._cand_state.data_ptr(), self._cand_size.data_ptr(),
+            res["points"].data_ptr(), res["candidate_bc"].data_ptr() if bc else None, res["seg_label"].data_ptr(),
+            res["box_label"].data_ptr(), res["box_label_prev"].data_ptr(), res["motion_label"].data_ptr(),
+            res["motion_state_label"].data_ptr(), res["bbox_size"].data_ptr(), self._bc_boxes.data_ptr() if bc else None,
+            self._xyz.data_ptr() if bc else None, self.used_prev.data_ptr() if self.record_indices else None,
+            self.used_this.data_ptr() if self.record_indices else None)
+        PU.train_motion_sample(a, dev)
+        if bc:
+            for w, key in enumerate(("prev_bc", "this_bc")):
+                b = self._bc_boxes[w]
+                PU.boxcloud_into(res[key], self._xyz[w], b[:3 * B], b[3 * B:6 * B], b[6 * B:])
         self.counter += 1
         return res
+
+    # ---- the planned route ------------------------------------------------------------------------------------------------------------
+    crop_cols = (0, 0, 1)                                  # the in-box count and the previous crop read `prev`, the current crop `this`
+
+    def _bind_buffers(self, dev):
+        J = self.J
+        self._p_refs, self._p_first = torch.zeros((2 * J, 15), dtype=torch.float32, device=dev), None
+        self._p_offs = torch.zeros((J, 4), dtype=torch.float32, device=dev)
+        self._p_aug = torch.zeros((2 * J, 6), dtype=torch.float32, device=dev) if self.augment else None
+        self._rec_planned = self._rec.copy()
+        self._rec_planned["box"][0] = self._p_refs.data_ptr() + 60 * np.arange(J, dtype=np.uint64)
+
+    def build_planned(self, chunk, k, out=None):
+        """batch k of the uploaded `chunk` (SiameseBatchBuilder.build_planned): o3d_train_draw, then build()'s launches"""
+        J, dev = self.J, self.device
+        with torch.cuda.device(dev):
+            PU.train_draw(self._gt, chunk.dev("rows", k), chunk.dev("cand", k), J, self.seed & 0xffffffff, self.counter & 0xffffffff,
+                          self.degrees, self.num_candidates, PU.TRAIN_DRAW_MOTION_AUG if self.augment else PU.TRAIN_DRAW_MOTION,
+                          self._p_refs, None, self._p_offs, self._p_aug)
+            return self._launch(self._p_refs.view(-1), self._p_offs.view(-1), self._p_aug.view(-1) if self.augment else None,
+                                chunk.dev("slots", k) if self.augment else None, chunk.dev("augptr", k) if self.augment else None,
+                                chunk.dev("cand", k), chunk.plan[k, :chunk.groups[k]], chunk.dev("plan", k), None, None, out, dev)
 
     def _shapes(self):
         B, N = self.B, self.N
@@ -525,20 +737,38 @@ class DeviceBatchSampler:
     (0, max(this - 1, 0), this).  The candidate id is index % num_candidates.  Every batch is over-provisioned to the
     builder's J candidates, so that invalid ones (too few points) are skipped on the device.  With a MotionBatchBuilder the
     frame choice is MotionTrackingSampler's (sampler.py:262-288): the annotations in order, frames (max(this - 1, 0), this);
-    random_sample is refused, because the reference forces it off (sampler.py:264)."""
+    random_sample is refused, because the reference forces it off (sampler.py:264).
 
-    def __init__(self, tracklets, builder, random_sample=False, seed=0, sample_per_epoch=10000):
+    plan_batches=P >= 1: the PLANNED epoch.  begin(epoch) makes the epoch's order (epoch_order: with `shuffle` the
+    reference's DataLoader(shuffle=True, drop_last=True), rank `rank` of `world` taking every world-th batch) and its frame
+    choice for all samples at once, and enqueues the tables of the first P batches as one pinned copy; __next__ only
+    launches (builder.build_planned: the boxes and the random draws of a batch are made on the device) and, at a chunk
+    boundary, plans and uploads the next P batches.  `uploads` counts the copies of the epoch.  __iter__ begins the next
+    epoch (0 first).  Without plan_batches the sampler works batch by batch as it always did."""
+
+    def __init__(self, tracklets, builder, random_sample=False, seed=0, sample_per_epoch=10000, shuffle=False, plan_batches=None,
+                 rank=0, world=1):
         self.motion = bool(getattr(builder, "motion", False))
         if self.motion and random_sample:
             raise ValueError("DeviceBatchSampler: MotionTrackingSampler has no random_sample (datasets/sampler.py:264)")
+        if plan_batches is None and (shuffle or world != 1):
+            raise ValueError("DeviceBatchSampler: shuffle and rank / world belong to the planned epoch (plan_batches=P)")
+        if plan_batches is not None and int(plan_batches) < 1:
+            raise ValueError("plan_batches must be positive")
         self.tracklets, self.builder, self.random_sample = tracklets, builder, bool(random_sample)
-        self.rng = np.random.default_rng(int(seed))
+        self.seed = int(seed)
+        self.rng = np.random.default_rng(self.seed)
         self.num_candidates = builder.num_candidates
         self.starts = np.concatenate([[0], np.cumsum([len(t) for t in tracklets])])
         self.length = (int(sample_per_epoch) if self.random_sample else int(self.starts[-1])) * self.num_candidates
         self.index = 0
+        self.shuffle, self.rank, self.world = bool(shuffle), int(rank), int(world)
+        self.plan_batches = None if plan_batches is None else int(plan_batches)
+        self.epoch, self.batches, self.s, self.uploads, self._chunk = -1, 0, 0, 0, None
 
     def __len__(self):
+        if self.plan_batches is not None:
+            return self.length // self.builder.J // self.world
         return self.length // self.builder.J
 
     def sample(self, index):
@@ -555,11 +785,62 @@ class DeviceBatchSampler:
             return self.tracklets[t], max(this - 1, 0), this, cand
         return self.tracklets[t], 0, max(this - 1, 0), this, cand
 
+    # ---- the planned epoch --------------------------------------------------------------------------------------------------------------
+    def begin(self, epoch):
+        """Plan epoch `epoch` and enqueue the upload of its first chunk -> the number of batches"""
+        if self.plan_batches is None:
+            raise RuntimeError("DeviceBatchSampler.begin belongs to the planned epoch (plan_batches=P)")
+        b, P = self.builder, self.plan_batches
+        if getattr(b, "_bound", None) is not self.tracklets:
+            b.bind(self.tracklets)
+        self.epoch = int(epoch)
+        order = epoch_order(self.length, b.J, self.shuffle, self.seed, self.epoch, self.rank, self.world)
+        draw = random_draw(np.diff(self.starts), self.length, self.seed, self.epoch) if self.random_sample else None
+        self._trk, self._frames, self._cand = epoch_frames(order, self.starts, self.num_candidates, self.motion, draw)
+        self._rows = b.row0[self._trk][..., None] + self._frames                   # (n, J, cols): the pool rows
+        self.batches, self.s, self.uploads = order.shape[0], 0, 0
+        if self._chunk is None:
+            with torch.cuda.device(b.device):
+                self._chunk = ChunkTables(P, b.J, self._rows.shape[-1], bool(getattr(b, "augment", False)))
+                self._tab = torch.zeros(self._chunk.host.size, dtype=torch.uint8, device=b.device)
+                self._chunk.base = self._tab.data_ptr()
+        if self.batches:
+            # the crop scratch of the worst batch: one word per (target, workgroup of its frame), known from the frame sizes
+            wgs = np.maximum(1, -(-b._fn // 256))
+            b.reserve_scratch(int(wgs[self._rows[:, :, list(b.crop_cols)]].sum((1, 2)).max()))
+        self._enter(0)
+        return self.batches
+
+    def _enter(self, s):
+        """what precedes batch s: at a chunk boundary the chunk's plan and its one upload"""
+        if s >= self.batches or s % self.plan_batches:
+            return
+        sl = slice(s, min(s + self.plan_batches, self.batches))
+        self.builder.plan(self._chunk, self._rows[sl], self._cand[sl])
+        with torch.cuda.device(self.builder.device):
+            self._tab.copy_(torch.from_numpy(self._chunk.host).pin_memory(), non_blocking=True)      # the pinned copy is the allocator's to recycle
+        self.uploads += 1
+
+    def samples(self, s):
+        """batch s of the planned epoch as the tuples build() takes (the per-batch route: tests and tools)"""
+        return [(self.tracklets[int(t)],) + tuple(int(v) for v in f) + (int(c),)
+                for t, f, c in zip(self._trk[s], self._frames[s], self._cand[s])]
+
     def __iter__(self):
+        if self.plan_batches is not None:
+            self.begin(self.epoch + 1)
+            return self
         self.index = 0
         return self
 
-    def __next__(self):
+    def __next__(self, out=None):
+        if self.plan_batches is not None:
+            if self.s >= self.batches:
+                raise StopIteration
+            res = self.builder.build_planned(self._chunk, self.s % self.plan_batches, out)
+            self.s += 1
+            self._enter(self.s)
+            return res
         J = self.builder.J
         if self.index + J > self.length:
             raise StopIteration

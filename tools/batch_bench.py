@@ -3,7 +3,7 @@ training step.  Not bench.py: that measures the step on batches that are already
 
   python tools/batch_bench.py [--tracklets 16] [--frames 8] [--points 120000] [--batch 48] [--candidates 60]
                               [--builds 200] [--warmup 20] [--steps 40] [--repeats 3] [--host-batches 2]
-                              [--model BAT|M2TRACK]
+                              [--model BAT|M2TRACK] [--plan-batches P [--shuffle]]
 
 Setup: `--tracklets` synth.make_sequence tracklets of `--frames` frames of `--points` points resident in HBM, the BAT data
 config (cfgs/BAT_Car.yaml), the frame choice of DeviceBatchSampler(random_sample=True).  Three measurements, one JSON line:
@@ -14,10 +14,17 @@ config (cfgs/BAT_Car.yaml), the frame choice of DeviceBatchSampler(random_sample
   step_ms_resident / step_ms_side / step_ms_inline   DataParallelStep (BAT, captured) fed resident synth batches, against the
                       same trainer fed builder batches that are built on a side stream while a step runs, against the same
                       trainer with every batch built on the main stream between two steps; blocks of `--steps` steps, the
-                      three alternated `--repeats` times in the same process (the spread is in the lists)
+                      three alternated `--repeats` times in the same process (the spread is in the lists).
+                      step_ms_built_resident: the same trainer on the last three builder batches with no build running --
+                      what the builder's DATA costs the step (its neighbourhoods are denser than the synth batches')
 --model M2TRACK: the same three measurements for sampler.MotionBatchBuilder with the M2-Track data config
 (cfgs/M2_track_kitti.yaml: augmentation and BoxCloud on), the annotations in order as MotionTrackingSampler walks them (wrapping
 at the end of the data), tests/motion_sampler_oracle.py::build as the host port, and m2track.M2TRACK as the step.
+--plan-batches P: the planned epoch beside the per-batch route.  A second builder of the same sizes
+is driven by DeviceBatchSampler(plan_batches=P[, shuffle=True]) -- the same frame choice, planned for the whole epoch, the
+tables uploaded P batches at a time, the draws made on the device; an epoch that ends begins the next one inside the timed
+loop.  build_ms / build_wall_ms / build_host_ms and the side / inline blocks are measured for it as for the per-batch route,
+the blocks of the two routes alternated in the same process, and reported under "planned".
 """
 import argparse
 import json
@@ -41,6 +48,8 @@ def main():
                           ("warmup", 20), ("steps", 40), ("repeats", 3), ("host-batches", 2)):
         ap.add_argument("--" + name, type=int, default=default)
     ap.add_argument("--model", choices=("BAT", "M2TRACK"), default="BAT")
+    ap.add_argument("--plan-batches", type=int, default=0)
+    ap.add_argument("--shuffle", action="store_true")
     args = ap.parse_args()
     motion = args.model == "M2TRACK"
     if not torch.cuda.is_available():
@@ -64,6 +73,43 @@ def main():
         s = [it.sample((index[0] + i) % it.length) for i in range(J)]
         index[0] += J
         return s
+
+    routes = {"per_batch": lambda out: builder.build(next_samples(), out=out)}
+    if args.plan_batches:
+        planned = type(builder)(cfg, B, candidates=J, capacity=builder.caps, seed=0)
+        pit = sampler.DeviceBatchSampler(tracklets, planned, random_sample=not motion, seed=0, sample_per_epoch=1 << 16,
+                                         shuffle=args.shuffle, plan_batches=args.plan_batches)
+        epochs = [0]
+
+        def build_planned(out):
+            if pit.s >= pit.batches:                             # the first call, and every end of an epoch
+                pit.begin(pit.epoch + 1)
+                epochs[0] += 1
+            return pit.__next__(out)
+        routes["planned"] = build_planned
+
+    def build_alone(build):
+        """-> (device ms per build, wall ms per build, the median host ms of the call with the device idle, the last batch)"""
+        out = None
+        for _ in range(args.warmup):
+            out = build(out)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(args.builds):
+            out = build(out)
+        e1.record()
+        torch.cuda.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3 / args.builds
+        host = []
+        for _ in range(20):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = build(out)
+            host.append((time.perf_counter() - t0) * 1e3)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.builds, wall, float(sorted(host)[len(host) // 2]), out
 
     # ---- 1. the build alone ---------------------------------------------------------------------------------------------------
     out = None
@@ -124,42 +170,56 @@ def main():
     side, main = torch.cuda.Stream(), torch.cuda.current_stream()
     ready = [torch.cuda.Event() for _ in range(3)]
 
-    def build_into(k):
+    def build_into(k, build):
         side.wait_stream(main)                                   # the step that last read built[k] has been enqueued
         with torch.cuda.stream(side):
-            builder.build(next_samples(), out=built[k])
+            build(built[k])
             ready[k].record(side)
 
-    def block(mode):
+    def block(mode, build=routes["per_batch"]):
         if mode == "side":
-            build_into(0)
-            build_into(1)
+            build_into(0, build)
+            build_into(1, build)
         elif mode == "inline":
-            builder.build(next_samples(), out=built[0])
-            builder.build(next_samples(), out=built[1])
+            build(built[0])
+            build(built[1])
         torch.cuda.synchronize()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for i in range(args.steps):
             if mode == "side":
-                build_into((i + 2) % 3)                          # beside step i
+                build_into((i + 2) % 3, build)                   # beside step i
                 main.wait_event(ready[(i + 1) % 3])
                 main.wait_event(ready[i % 3])
                 trainer.step(built[i % 3], next_batch=built[(i + 1) % 3])
             elif mode == "inline":
-                builder.build(next_samples(), out=built[(i + 2) % 3])     # on the main stream, before step i
+                build(built[(i + 2) % 3])                        # on the main stream, before step i
                 trainer.step(built[i % 3], next_batch=built[(i + 1) % 3])
+            elif mode == "built":
+                trainer.step(built[i % 3], next_batch=built[(i + 1) % 3])   # the last three builder batches, no build
             else:
                 trainer.step(pool[i % 3], next_batch=pool[(i + 1) % 3])
         b.record()
         torch.cuda.synchronize()
         return a.elapsed_time(b) / args.steps
-    times = {"resident": [], "side": [], "inline": []}
-    for mode in times:
-        block(mode)                                              # every route warm
+    times = {"resident": [], "built": [], "side": [], "inline": []}
+    blocks = [(mode, "per_batch", times[mode]) for mode in times]
+    extra_out = {}
+    if args.plan_batches:
+        alone = build_alone(routes["planned"])                   # (an epoch's tables are planned inside the timed loop)
+        ptimes = {"side": [], "inline": []}
+        blocks += [(mode, "planned", ptimes[mode]) for mode in ptimes]
+    for mode, route, _ in blocks:
+        block(mode, routes[route])                               # every route warm
     for _ in range(args.repeats):
-        for mode in times:
-            times[mode].append(round(block(mode), 4))
+        for mode, route, log in blocks:
+            log.append(round(block(mode, routes[route]), 4))
+    if args.plan_batches:
+        extra_out["planned"] = {
+            "plan_batches": args.plan_batches, "shuffle": args.shuffle, "batches_per_epoch": pit.batches, "epochs_begun": epochs[0],
+            "build_ms": round(alone[0], 4), "build_wall_ms": round(alone[1], 4), "build_host_ms": round(alone[2], 4),
+            "last_n_valid": int(alone[3]["n_valid"][0]), "last_overflow": int(alone[3]["overflow"][0]),
+            "step_ms_side": ptimes["side"], "step_ms_inline": ptimes["inline"]}
     print(json.dumps({
         "tool": "batch_bench", "device": torch.cuda.get_device_name(0), "model": args.model,
         "config": "M2_track_kitti data keys" if motion else "BAT_Car data keys", "batch": B, "candidates": J,
@@ -170,8 +230,9 @@ def main():
         "frame_gb_per_s": round(frame_bytes / args.builds / build_ms / 1e6, 1), "last_n_valid": n_valid, "last_overflow": overflow,
         "host_port": "tests/%s.py::build (numpy port of the reference's sampler, one process)" % ("motion_sampler_oracle" if motion else "sampler_oracle"),
         "host_port_s_per_batch": round(host_s, 3), "host_port_pairs_per_s": round(B / host_s, 1),
-        "step_ms_resident": times["resident"], "step_ms_side": times["side"], "step_ms_inline": times["inline"],
-        "steps_per_block": args.steps}))
+        "step_ms_resident": times["resident"], "step_ms_built_resident": times["built"], "step_ms_side": times["side"],
+        "step_ms_inline": times["inline"],
+        "steps_per_block": args.steps, **extra_out}))
 
 
 if __name__ == "__main__":
