@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import points_utils as PU
+from .crop_plan import FramePool, Tables, _section, plan_groups, upload
 
 # the data keys of cfgs/BAT_Car.yaml:5-15,23 (P2B_Car.yaml: the same but box_aware False)
 DATA_KEYS = dict(search_bb_scale=1.25, search_bb_offset=2, model_bb_scale=1.25, model_bb_offset=0, template_size=512,
@@ -88,12 +89,6 @@ class DeviceTracklets(list):
             self.append(DeviceTracklet(frames, boxes, device))
 
 
-def _section(layout, name, nbytes):
-    off = layout["_end"]
-    layout[name] = (off, nbytes)
-    layout["_end"] = off + -(-nbytes // 64) * 64
-
-
 # ---- the planned epoch: order, frame choice and the tables of P batches, all whole-array numpy (no device) -------------------
 def epoch_order(length, J, shuffle, seed, epoch, rank=0, world=1):
     """-> (n_batches, J) int64 sample indices of `rank`'s batches of epoch `epoch`.  shuffle=False: arange; True:
@@ -136,77 +131,43 @@ def random_draw(lengths, count, seed, epoch):
     return t, a, b
 
 
-class ChunkTables:
-    """The tables of P planned batches of J candidates in ONE host buffer (`host`, uint8), which travels to the device in one
-    copy; `base` is the address of that copy (a plain integer: nothing here touches a device).  Views, batch-major: rows
-    (P,J,cols) and cand (P,J) int32, targets (P,3J) CROP_TARGET, plan (P,3J) CROP_PLAN of which batch k uses the first
-    groups[k], and with `aug` slots (P,3J) int32 / augptr (P,3J) uint64.  need[k] = batch k's scratch length, grid[k] = its
-    workgroups of the count / scatter launches."""
+class ChunkTables(Tables):
+    """The tables of P planned batches of J candidates (crop_plan.Tables: one host buffer, one copy; `base` is the address of
+    that copy).  Views, batch-major: rows (P,J,cols) and cand (P,J) int32, targets (P,3J) CROP_TARGET, plan (P,3J) CROP_PLAN of
+    which batch k uses the first groups[k], and with `aug` slots (P,3J) int32 / augptr (P,3J) uint64.  need[k] = batch k's
+    scratch length, grid[k] = its workgroups of the count / scatter launches."""
 
     def __init__(self, P, J, cols, aug=False, base=0):
-        self.P, self.J, self.cols, self.aug, self.base = int(P), int(J), int(cols), bool(aug), int(base)
+        self.J, self.cols, self.aug = int(J), int(cols), bool(aug)
         n_rec = 3 * self.J
-        self._per = {"rows": (self.J * self.cols * 4, np.int32, (self.J, self.cols)), "cand": (self.J * 4, np.int32, (self.J,))}
+        sections = {"rows": (np.int32, (self.J, self.cols)), "cand": (np.int32, (self.J,))}
         if self.aug:
-            self._per.update(slots=(n_rec * 4, np.int32, (n_rec,)), augptr=(n_rec * 8, np.uint64, (n_rec,)))
-        self._per.update(targets=(n_rec * PU.CROP_TARGET.itemsize, PU.CROP_TARGET, (n_rec,)),
-                         plan=(n_rec * PU.CROP_PLAN.itemsize, PU.CROP_PLAN, (n_rec,)))
-        self._layout = {"_end": 0}
-        for name, (nbytes, _, _) in self._per.items():
-            _section(self._layout, name, self.P * nbytes)
-        self.host = np.zeros(self._layout["_end"], np.uint8)
-        for name, (nbytes, dtype, shape) in self._per.items():
-            off = self._layout[name][0]
-            setattr(self, name, self.host[off:off + self.P * nbytes].view(dtype).reshape((self.P,) + shape))
+            sections.update(slots=(np.int32, (n_rec,)), augptr=(np.uint64, (n_rec,)))
+        sections.update(targets=(PU.CROP_TARGET, (n_rec,)), plan=(PU.CROP_PLAN, (n_rec,)))
+        super().__init__(P, sections, base)
+        for name in sections:
+            setattr(self, name, self.view(name))
         self.groups, self.need, self.grid = (np.zeros(self.P, np.int64) for _ in range(3))
-
-    def dev(self, name, k=0):
-        """the device address of batch k's part of section `name`"""
-        return self.base + self._layout[name][0] + self._per[name][0] * k
 
 
 def plan_chunk(chunk, fptr, fn, rows, cand, rec, crop_cols, aug_base=None):
-    """Fill `chunk` for S <= P batches, in whole-chunk numpy: a pure function of integer arrays.  fptr, fn: per pool row the
-    frame's address and size; rows (S,J,cols) the pool rows of the candidates' frames, cand (S,J) their ids; rec (3,J) the
-    builder's fixed CROP_TARGET records; crop c of candidate j reads frame rows[:, j, crop_cols[c]].  Every distinct frame of
-    a batch is one group that holds the targets reading it; wg_start / row_start / sbase are prefix sums over the groups, what
-    o3d_track_crop_groups_scratch computes (o3d_track_crop_groups checks them again before it launches).  aug_base: the address
-    of the builder's CROP_AUG records -> slots (the record of target slot i: -1 for crop 0, else (c - 1) J + j) and augptr (per
-    group: its first record)."""
+    """Fill `chunk` for S <= P batches (crop_plan.plan_groups: whole-chunk numpy, a pure function of integer arrays).  fptr, fn:
+    per pool row the frame's address and size; rows (S,J,cols) the pool rows of the candidates' frames, cand (S,J) their ids;
+    rec (3,J) the builder's fixed CROP_TARGET records; crop c of candidate j reads frame rows[:, j, crop_cols[c]].  Every
+    distinct frame of a batch is one group that holds the targets reading it, the groups in the order of their pool rows.
+    aug_base: the address of the builder's CROP_AUG records -> slots (the record of target slot i: -1 for crop 0, else
+    (c - 1) J + j) and augptr (per group: its first record)."""
     rows, cand = np.asarray(rows, np.int64), np.asarray(cand, np.int64)
     S, J = rows.shape[0], chunk.J
-    n_rec = 3 * J
     assert S <= chunk.P and rows.shape == (S, J, chunk.cols) and cand.shape == (S, J) and rec.shape == (3, J)
     chunk.rows[:S], chunk.cand[:S] = rows, cand
-    frame = rows[:, :, list(crop_cols)].transpose(0, 2, 1).reshape(S, n_rec)        # of crop (c, j), at c J + j
-    order = np.argsort(frame, axis=1, kind="stable")                               # the targets of a frame side by side
-    frame = np.take_along_axis(frame, order, 1)
-    chunk.targets[:S] = rec.reshape(-1)[order]
-    new = np.ones((S, n_rec), bool)
-    new[:, 1:] = frame[:, 1:] != frame[:, :-1]
-    gid = np.cumsum(new, 1) - 1
-    p, pos = np.nonzero(new)                                                       # one entry per group, batch-major
-    g = gid[p, pos]
-    last = np.append(p[1:] != p[:-1], True)
-    k = np.where(last, n_rec, np.append(pos[1:], n_rec)) - pos                     # the group's targets
-    key = frame[p, pos]
-    n = fn[key]
-    wgs = np.maximum(1, -(-n // 256))
-    head = np.flatnonzero(g == 0)
-
-    def before(v):                                                                 # the sum over the earlier groups of the batch
-        c = np.cumsum(v) - v
-        return c - c[head][p]
-    plan = chunk.plan[:S]
-    plan["points"][p, g], plan["n"][p, g], plan["n_targets"][p, g] = fptr[key], n, k
-    plan["targets"][p, g] = chunk.dev("targets") + PU.CROP_TARGET.itemsize * (p * n_rec + pos)
-    plan["wg_start"][p, g], plan["row_start"][p, g], plan["sbase"][p, g] = before(wgs), pos, before(wgs * k)
-    chunk.groups[:S] = gid[:, -1] + 1
-    chunk.need[:S], chunk.grid[:S] = np.bincount(p, wgs * k, S), np.bincount(p, wgs, S)
+    frame = rows[:, :, list(crop_cols)].transpose(0, 2, 1).reshape(S, 3 * J)        # of crop (c, j), at c J + j
+    chunk.groups[:S], chunk.need[:S], chunk.grid[:S], order = plan_groups(frame, frame, rec.reshape(-1), fptr, fn, chunk.targets,
+                                                                          chunk.plan, chunk.dev("targets"))
     if aug_base is not None:
         c, j = order // J, order % J
         chunk.slots[:S] = np.where(c == 0, -1, (c - 1) * J + j)
-        chunk.augptr[p, g] = int(aug_base) + PU.CROP_AUG.itemsize * pos
+        chunk.augptr[:S] = int(aug_base) + PU.CROP_AUG.itemsize * chunk.plan["row_start"][:S].astype(np.int64)
 
 
 class _DeviceBatchBuilder:
@@ -258,35 +219,24 @@ class _DeviceBatchBuilder:
             self._events[slot].synchronize()          # the upload of two builds ago: long done in a running loop
         return dev, torch.cuda.current_stream(dev), slot
 
-    def _crop_tables(self, slot, wanted):
-        """wanted: (tracklet, frame, c, j) for every crop, in the order of the candidates -> (the planned CROP_PLAN rows of
-        this batch in the pinned slot, the scratch length, [(first target, c list, j list)] per group): every distinct frame
-        is one group whose targets are self._rec[c, j] of the crops that read it"""
-        groups, order = {}, []
-        for trk, f, c, j in wanted:
-            key = (id(trk), f)
-            if key not in groups:
-                groups[key] = (trk.frames[f], [], [])
-                order.append(key)
-            groups[key][1].append(c)
-            groups[key][2].append(j)
-        n_rec = self._rec.shape[0] * self.J
-        targets = self._view(slot, "targets", PU.CROP_TARGET, (n_rec,))
-        plan = self._view(slot, "plan", PU.CROP_PLAN, (n_rec,))[:len(order)]
-        pos, where = 0, []
-        tab = self._dev("targets")
-        for g, key in enumerate(order):
-            pts, cs, js = groups[key]
-            k = len(cs)
-            targets[pos:pos + k] = self._rec[cs, js]
-            plan[g] = (pts.data_ptr(), pts.shape[0], tab + PU.CROP_TARGET.itemsize * pos, k, 0, 0, 0)
-            where.append((pos, cs, js))
-            pos += k
-        need = PU.crop_groups_plan(plan)[0]
-        if self._scratch.numel() < need:
-            with torch.cuda.device(self.device):
-                self._scratch = torch.empty(need, dtype=torch.int32, device=self.device)
-        return plan, need, where
+    def _crop_tables(self, slot, samples):
+        """-> (the planned CROP_PLAN rows of this batch in the pinned slot, order): crop c of candidate j reads frame
+        crop_cols[c] of its sample; every distinct (tracklet, frame) is one group, the groups in the order in which the
+        candidates first read them, and a group's targets are self._rec[c, j] of the crops that read it, in the order of the
+        candidates (target slot i holds crop order[i] = j C + c)"""
+        wanted = [(s[0], s[1 + col]) for s in samples for col in self.crop_cols]
+        clouds = {}
+        for trk, f in wanted:
+            clouds.setdefault((id(trk), f), trk.frames[f])
+        ids = {at: i for i, at in enumerate(clouds)}
+        key = np.array([[ids[id(trk), f] for trk, f in wanted]], np.int64)
+        pool = FramePool([clouds.values()])
+        n_rec = key.shape[1]
+        plan = self._view(slot, "plan", PU.CROP_PLAN, (1, n_rec))
+        groups, need, _, order = plan_groups(key, key, self._rec.T.reshape(-1), pool.fptr, pool.fn,
+                                             self._view(slot, "targets", PU.CROP_TARGET, (1, n_rec)), plan, self._dev("targets"))
+        self.reserve_scratch(int(need[0]))
+        return plan[0, :groups[0]], order[0]
 
     def _upload(self, slot, nbytes, stream):
         self._up[:nbytes].copy_(self._pinned[slot][:nbytes], non_blocking=True)       # THE upload of this batch
@@ -305,9 +255,8 @@ class _DeviceBatchBuilder:
                 self._allocate(dev)
         assert dev == self.device
         self._bound = tracklets                            # the frames stay alive as long as their addresses are planned
-        self.row0 = np.concatenate([[0], np.cumsum([len(t) for t in tracklets])]).astype(np.int64)
-        self._fptr = np.array([x.data_ptr() for x in frames], np.int64)
-        self._fn = np.array([x.shape[0] for x in frames], np.int64)
+        self._pool = FramePool([t.frames for t in tracklets])
+        self.row0 = self._pool.row0
         with torch.cuda.device(dev):
             self._gt = torch.from_numpy(np.concatenate([t.boxes for t in tracklets])).to(dev)
             self._bind_buffers(dev)
@@ -319,7 +268,7 @@ class _DeviceBatchBuilder:
 
     def plan(self, chunk, rows, cand):
         """plan_chunk for this builder's records: rows (S,J,cols) pool rows, cand (S,J) -> the chunk's host tables"""
-        plan_chunk(chunk, self._fptr, self._fn, rows, cand, self._rec_planned, self.crop_cols,
+        plan_chunk(chunk, self._pool.fptr, self._pool.fn, rows, cand, self._rec_planned, self.crop_cols,
                    self._aug.data_ptr() if getattr(self, "augment", False) else None)
 
     def draws(self):
@@ -447,12 +396,9 @@ class SiameseBatchBuilder(_DeviceBatchBuilder):
         offs[:] = 0
         offs[:J, :2], offs[:J, 3] = off_t[:, :2], off_t[:, 2]
         offs[J:, :2], offs[J:, 3] = off_s[:, :2], off_s[:, 2]
-        # the groups: every distinct frame once, with the crops that read it
-        wanted = []
         for j, (trk, f0, f1, f2, _) in enumerate(samples):
             first[j], refs[j], refs[J + j] = trk.boxes[f0], trk.boxes[f1], trk.boxes[f2]
-            wanted += [(trk, f, c, j) for c, f in enumerate((f0, f1, f2))]
-        plan = self._crop_tables(slot, wanted)[0]
+        plan = self._crop_tables(slot, samples)[0]              # the groups: every distinct frame once, with the crops that read it
         nbytes = self._base_bytes
         idx_t = idx_s = None
         if draws is not None and draws.get("idx_t") is not None:
@@ -632,17 +578,11 @@ class MotionBatchBuilder(_DeviceBatchBuilder):
         if self.augment:
             aug = self._view(slot, "aug", np.float32, (2 * J, 6))
             aug[:J], aug[J:] = self.draw_augmentation(J) if draws is None else (draws["aug_prev"], draws["aug_this"])
-        wanted = []
         for j, (trk, f1, f2, _) in enumerate(samples):
             refs[j], refs[J + j] = trk.boxes[f1], trk.boxes[f2]
-            wanted += [(trk, f1, 0, j), (trk, f1, 1, j), (trk, f2, 2, j)]
-        plan, _, where = self._crop_tables(slot, wanted)
+        plan, order = self._crop_tables(slot, samples)
         if self.augment:
-            slots = self._view(slot, "slots", np.int32, (3 * J,))
-            augptr = self._view(slot, "augptr", np.uint64, (3 * J,))
-            for g, (pos, cs, js) in enumerate(where):
-                slots[pos:pos + len(cs)] = [-1 if c == 0 else (c - 1) * J + j for c, j in zip(cs, js)]
-                augptr[g] = self._aug.data_ptr() + PU.CROP_AUG.itemsize * pos
+            self._aug_tables(slot, plan, order)
         nbytes = self._base_bytes
         idx_prev = idx_this = None
         if draws is not None and draws.get("idx_prev") is not None:
@@ -658,6 +598,13 @@ class MotionBatchBuilder(_DeviceBatchBuilder):
                 aug_d, slots_d = self._dev32("aug", 2 * J * 6), self._up.view(torch.int32)[s0:s0 + 3 * J]
             return self._launch(self._dev32("refs", 2 * J * 15), self._dev32("offs", J * 4), aug_d, slots_d, self._dev("augptr"),
                                 self._dev("cand"), plan, self._dev("plan"), idx_prev, idx_this, out, dev)
+
+    def _aug_tables(self, slot, plan, order):
+        """slots (the record of target slot i: -1 for the in-box count, else (c - 1) J + j) and augptr (per group: its first
+        record) of a batch, as plan_chunk writes them"""
+        c, j = order % 3, order // 3
+        self._view(slot, "slots", np.int32, (3 * self.J,))[:] = np.where(c == 0, -1, (c - 1) * self.J + j)
+        self._view(slot, "augptr", np.uint64, (3 * self.J,))[:len(plan)] = self._aug.data_ptr() + PU.CROP_AUG.itemsize * plan["row_start"].astype(np.int64)
 
     def _launch(self, gt, offs_d, aug_d, slots_d, augptr_d, cand_d, plan, dev_plan, idx_prev, idx_this, out, dev):
         """the launches of a build behind its tables, shared by build() and build_planned(): gt (2J*15), offs_d (J*4), aug_d
@@ -805,9 +752,8 @@ class DeviceBatchSampler:
                 self._tab = torch.zeros(self._chunk.host.size, dtype=torch.uint8, device=b.device)
                 self._chunk.base = self._tab.data_ptr()
         if self.batches:
-            # the crop scratch of the worst batch: one word per (target, workgroup of its frame), known from the frame sizes
-            wgs = np.maximum(1, -(-b._fn // 256))
-            b.reserve_scratch(int(wgs[self._rows[:, :, list(b.crop_cols)]].sum((1, 2)).max()))
+            # the crop scratch of the worst batch, known from the frame sizes
+            b.reserve_scratch(b._pool.worst_scratch(self._rows[:, :, list(b.crop_cols)].reshape(self.batches, -1)))
         self._enter(0)
         return self.batches
 
@@ -817,8 +763,7 @@ class DeviceBatchSampler:
             return
         sl = slice(s, min(s + self.plan_batches, self.batches))
         self.builder.plan(self._chunk, self._rows[sl], self._cand[sl])
-        with torch.cuda.device(self.builder.device):
-            self._tab.copy_(torch.from_numpy(self._chunk.host).pin_memory(), non_blocking=True)      # the pinned copy is the allocator's to recycle
+        upload(self._chunk, self._tab)
         self.uploads += 1
 
     def samples(self, s):

@@ -48,6 +48,7 @@ import numpy as np
 import torch
 
 from . import capi, points_utils as PU
+from .crop_plan import FramePool, Tables, plan_groups, upload
 
 _DEFAULTS = dict(search_bb_scale=1.25, search_bb_offset=2, model_bb_scale=1.25, model_bb_offset=0, template_size=512,
                  search_size=1024, degrees=True, use_z=True, limit_box=False, shape_aggregation="firstandprevious",
@@ -962,30 +963,66 @@ def lane_schedule(lengths, lanes, order="given"):
     return np.array(tracklet, np.int32).reshape(-1, L), np.array(frame, np.int32).reshape(-1, L)
 
 
+def plan_lane_steps(tables, tracklet, frame, row0, pool, clouds, addr, by_gt, back, crop_all=True):
+    """The tables of S steps of L lanes into `tables` (a crop_plan.Tables with the sections lanes (L, LANE_COLS) int32, plan
+    (2L,) CROP_PLAN and targets (2L,) CROP_TARGET, its device copy at tables.base): a pure function of integer arrays.
+    tracklet, frame (S,L): the steps' slice of lane_schedule; row0, pool: the crop_plan.FramePool of the tracklets' frames
+    (boxes and results share its rows); clouds: per cloud (frames back from t, cropped by the reference box?, scale, offset,
+    mode, the address of out (L,cap,3), cap, gated?); addr = {"cur", "gt", "counts"}: the addresses of the lanes' current boxes
+    (L,15), the ground-truth pool (R,15) and the counts (L,2).  by_gt: the reference box of frame t is the ground truth of
+    pool row t - back (reference_BB previous_gt: back = 1, current_gt: 0), else the lane's current box.  A gated cloud is
+    cropped only where the step has_crop: everywhere with crop_all, else on a tracklet's first step (shape_aggregation
+    `first`).  Every active (lane, cloud) is one group of one target, cloud c of lane l in the order of its slot c L + l; an
+    idle lane has none.  -> (groups, need = the scratch length, starts = a lane starts a tracklet: three (S,) arrays)"""
+    js, ts = np.asarray(tracklet, np.int64), np.asarray(frame, np.int64)
+    (S, L), F = js.shape, PU.LANE
+    on = js >= 0
+    row = np.where(on, row0[np.maximum(js, 0)] + ts, 0)                    # the pool row of frame t
+    first = on & (ts == 1)
+    has_crop = on & (first | bool(crop_all))
+    ref_row = np.where(on & bool(by_gt), row - back, -1)
+    lanes = tables.view("lanes")[:S]
+    for name, v in (("active", on), ("first", first), ("has_crop", has_crop), ("t", ts), ("row", np.where(on, row, -1)),
+                    ("ref_row", ref_row), ("rebase", on & bool(by_gt))):
+        lanes[:, :, F[name]] = v
+    ll = np.arange(L, dtype=np.int64)
+    cur = np.broadcast_to(addr["cur"] + 60 * ll, (S, L))
+    ref = addr["gt"] + 60 * ref_row if by_gt else cur
+    n = len(clouds) * L
+    rec, cloud, valid = np.zeros((S, n), PU.CROP_TARGET), np.zeros((S, n), np.int64), np.zeros((S, n), bool)
+    for c, (shift, by_ref, scale, offset, mode, out, cap, gated) in enumerate(clouds):
+        sl = slice(c * L, (c + 1) * L)
+        cloud[:, sl], valid[:, sl] = np.where(on, row - shift, 0), has_crop if gated else on
+        r = rec[:, sl]
+        r["box"], r["scale"], r["offset"], r["mode"] = ref if by_ref else cur, scale, offset, mode
+        r["out"], r["capacity"], r["count"] = out + 12 * cap * ll, cap, addr["counts"] + 8 * ll + 4 * c
+    groups, need, _, _ = plan_groups(np.broadcast_to(np.arange(n), (S, n)), cloud, rec, pool.fptr, pool.fn, tables.view("targets"),
+                                     tables.view("plan"), tables.dev("targets"), valid)
+    return groups, need, first.any(1)
+
+
 class _Lanes:
     """What LaneTracker and MotionLaneTracker put on top of their single-target bases' state with a leading L axis: the epoch
     plan.  begin() lays all tracklets' ground-truth boxes end to end in one pool (R,15) and gives the results the same rows
     (tracklet j owns rows [row0_j, row0_j + T_j)), runs lane_schedule, and from then on everything a step needs is host
     knowledge: per step the lane table (L, LANE_COLS) and one o3d_crop_plan group with one o3d_crop_target per (lane, cloud).
-    They are built for plan_steps steps at a time in one host buffer and uploaded with ONE copy before the chunk's first step;
-    step() only launches.  A subclass provides _clouds() (its two crops per lane), _has_crop() and _launch() (the step behind
-    the crops)."""
+    They are built for plan_steps steps at a time in one host buffer (plan_lane_steps) and uploaded with ONE copy before the
+    chunk's first step; step() only launches.  A subclass provides _clouds() (its two crops per lane) and _launch() (the step
+    behind the crops), and tells _lane_state its reference rule: by_gt, back and crop_all of plan_lane_steps."""
 
-    def _lane_state(self, L, plan_steps):
-        self.L, self.plan_steps = L, int(plan_steps)
+    def _lane_state(self, L, plan_steps, by_gt=False, back=0, crop_all=True):
+        self.L, self.plan_steps, self._rule = L, int(plan_steps), (bool(by_gt), int(back), bool(crop_all))
         if self.plan_steps < 1:
             raise ValueError("plan_steps must be positive")
-        P, G = self.plan_steps, 2 * L
+        P = self.plan_steps
         self.counts2 = self.counts_dev.view(L, 2)
-        ends = np.cumsum([0, -(-P * L * PU.LANE_COLS * 4 // 16) * 16, P * G * PU.CROP_PLAN.itemsize, P * G * PU.CROP_TARGET.itemsize])
-        self._tab_host = np.zeros((int(ends[-1]),), np.uint8)
-        self._tab = torch.zeros((int(ends[-1]),), dtype=torch.uint8, device=self.dev)
-        self._lanes_h = self._tab_host[:P * L * PU.LANE_COLS * 4].view(np.int32).reshape(P, L, PU.LANE_COLS)
-        self._plan_h = self._tab_host[ends[1]:ends[2]].view(PU.CROP_PLAN).reshape(P, G)
-        self._targ_h = self._tab_host[ends[2]:ends[3]].view(PU.CROP_TARGET).reshape(P, G)
-        lanes_d = self._tab[:P * L * PU.LANE_COLS * 4].view(torch.int32).view(P, L, PU.LANE_COLS)
+        self._tables = Tables(P, {"lanes": (np.int32, (L, PU.LANE_COLS)), "plan": (PU.CROP_PLAN, (2 * L,)),
+                                  "targets": (PU.CROP_TARGET, (2 * L,))})
+        self._tab = torch.zeros((self._tables.host.size,), dtype=torch.uint8, device=self.dev)
+        self._tables.base = self._tab.data_ptr()
+        self._plan_h = self._tables.view("plan")
+        lanes_d = self._tab[:P * L * PU.LANE_COLS * 4].view(torch.int32).view(P, L, PU.LANE_COLS)        # the first section
         self._lane_rows = [lanes_d[k] for k in range(P)]                   # step k of the chunk: its (L, LANE_COLS) table on the device
-        self._plan_d, self._targ_d = self._tab.data_ptr() + int(ends[1]), self._tab.data_ptr() + int(ends[2])
         self._groups, self._starts = [0] * P, [False] * P
         self.steps, self.s, self.uploads = 0, 0, 0
         self.schedule = None
@@ -1013,9 +1050,8 @@ class _Lanes:
         self.lengths = [len(f) for f in frames]
         self.schedule = lane_schedule(self.lengths, self.L, order)
         self.frames, self.steps, self.s, self.uploads = frames, self.schedule[0].shape[0], 0, 0
-        self.row0 = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        self._fptr = np.array([x.data_ptr() for f in frames for x in f], np.int64)          # per pool row: the frame's address and size
-        self._fn = np.array([x.shape[0] for f in frames for x in f], np.int64)
+        self._pool = FramePool(frames)                                                     # per pool row: the frame's address and size
+        self.row0 = self._pool.row0
         R = int(self.row0[-1])
         with torch.cuda.device(self.dev):
             self.gt = torch.cat(boxes).contiguous() if R else torch.zeros((0, 15), dtype=torch.float32, device=self.dev)
@@ -1024,11 +1060,10 @@ class _Lanes:
             if R:
                 first = torch.from_numpy(self.row0[:-1]).to(self.dev)
                 self.boxes.index_copy_(0, first, self.gt.index_select(0, first))             # row 0 of every tracklet: its first box
-            # the crop scratch of the worst step: one row of ceil(n / 256) counts per (lane, cloud)
-            wgs = np.maximum(1, -(-self._fn // 256))
+            # the crop scratch of the worst step: every busy lane reads frame t and frame t - 1
             js, ts = self.schedule[0].astype(np.int64), self.schedule[1].astype(np.int64)
-            rows = np.where(js >= 0, self.row0[np.maximum(js, 0)] + ts, 1)
-            worst = int(np.where(js >= 0, wgs[rows] + wgs[rows - 1], 0).sum(1).max()) if self.steps else 0
+            rows = np.where(js >= 0, self.row0[np.maximum(js, 0)] + ts, -1)
+            worst = self._pool.worst_scratch(np.concatenate([rows, rows - 1], 1))
             if self.scratch is None or self.scratch.numel() < worst:
                 self.scratch = torch.empty((max(worst, 1),), dtype=torch.int32, device=self.dev)
             if self.free_running and hasattr(self, "bank_state"):
@@ -1037,55 +1072,14 @@ class _Lanes:
         return self.steps
 
     def _plan_chunk(self, c):
-        """the tables of steps [c P, (c + 1) P) into the host buffer, in whole-chunk numpy"""
-        P, L, F = self.plan_steps, self.L, PU.LANE
-        s0, s1 = c * P, min((c + 1) * P, self.steps)
-        S = s1 - s0
-        js, ts = self.schedule[0][s0:s1].astype(np.int64), self.schedule[1][s0:s1].astype(np.int64)      # (S,L)
-        on = js >= 0
-        row = np.where(on, self.row0[np.maximum(js, 0)] + ts, 0)           # the pool row of frame t (frames, boxes and results share it)
-        first = on & (ts == 1)
-        has_crop = on & self._has_crop(first)
-        by_gt = bool(getattr(self, "needs_ref_box", False))
-        back = 1 if "PREVIOUS_GT" in str(getattr(self, "reference_BB", "")).upper() else 0
-        ref_row = np.where(on, row - back, -1) if by_gt else np.full_like(row, -1)
-        lanes = self._lanes_h[:S]
-        for name, v in (("active", on), ("first", first), ("has_crop", has_crop), ("t", ts), ("row", np.where(on, row, -1)),
-                        ("ref_row", ref_row), ("rebase", on & by_gt)):
-            lanes[:, :, F[name]] = v
-        ll = np.arange(L, dtype=np.int64)
-        cur_ptr = np.broadcast_to(self.cur.data_ptr() + 60 * ll, (S, L))
-        ref_ptr = self.gt.data_ptr() + 60 * ref_row if by_gt else cur_ptr
-        # the candidate groups of a step: cloud c of lane l in slot c L + l, then the valid ones moved to the front
-        valid = np.zeros((S, 2 * L), bool)
-        col = {k: np.zeros((S, 2 * L), np.float64 if k in ("scale", "offset") else np.int64)
-               for k in ("points", "n", "box", "scale", "offset", "mode", "out", "capacity", "count")}
-        for cl, (shift, by_ref, scale, offset, mode, out, cap, gated) in enumerate(self._clouds()):
-            sl = slice(cl * L, (cl + 1) * L)
-            frow = np.where(on, row - shift, 0)
-            valid[:, sl] = has_crop if gated else on
-            col["points"][:, sl], col["n"][:, sl] = self._fptr[frow], self._fn[frow]
-            col["box"][:, sl] = ref_ptr if by_ref else cur_ptr
-            col["scale"][:, sl], col["offset"][:, sl], col["mode"][:, sl] = scale, offset, mode
-            col["out"][:, sl], col["capacity"][:, sl] = out.data_ptr() + 12 * cap * ll, cap
-            col["count"][:, sl] = self.counts_dev.data_ptr() + 8 * ll + 4 * cl
-        order = np.argsort(~valid, axis=1, kind="stable")
-        groups = valid.sum(1)
-        targ, plan = self._targ_h[:S], self._plan_h[:S]
-        for k in ("box", "scale", "offset", "mode", "out", "capacity", "count"):
-            targ[k] = np.take_along_axis(col[k], order, 1)
-        plan["points"], plan["n"] = np.take_along_axis(col["points"], order, 1), np.take_along_axis(col["n"], order, 1)
-        plan["targets"] = self._targ_d + PU.CROP_TARGET.itemsize * (2 * L * np.arange(S, dtype=np.int64)[:, None] + np.arange(2 * L, dtype=np.int64))
-        plan["n_targets"] = 1
-        # the planned columns (what o3d_track_crop_groups_scratch fills, for one target per group): prefix sums of the groups'
-        # workgroups; o3d_track_crop_groups checks them again before any launch
-        wgs = np.where(np.take_along_axis(valid, order, 1), np.maximum(1, -(-plan["n"].astype(np.int64) // 256)), 0)
-        before = np.cumsum(wgs, 1) - wgs
-        plan["wg_start"], plan["row_start"], plan["sbase"] = before, np.arange(2 * L), before
-        need = int(wgs.sum(1).max())
-        if need > self.scratch.numel():
-            self.scratch = torch.empty((need,), dtype=torch.int32, device=self.dev)
-        self._groups[:S], self._starts[:S] = groups.tolist(), first.any(1).tolist()
+        """the tables of steps [c P, (c + 1) P) into the host buffer"""
+        sl = slice(c * self.plan_steps, min((c + 1) * self.plan_steps, self.steps))
+        addr = {"cur": self.cur.data_ptr(), "gt": self.gt.data_ptr(), "counts": self.counts_dev.data_ptr()}
+        groups, need, starts = plan_lane_steps(self._tables, self.schedule[0][sl], self.schedule[1][sl], self.row0, self._pool,
+                                               self._clouds(), addr, *self._rule)
+        assert need.max() <= self.scratch.numel()                          # begin() sized it for the worst step
+        S = sl.stop - sl.start
+        self._groups[:S], self._starts[:S] = groups.tolist(), starts.tolist()
 
     def _enter(self, s):
         """what precedes step s: at a chunk boundary the chunk's one upload; where a lane starts a tracklet, its start"""
@@ -1094,7 +1088,7 @@ class _Lanes:
         k = s % self.plan_steps
         if k == 0:
             self._plan_chunk(s // self.plan_steps)
-            self._tab.copy_(torch.from_numpy(self._tab_host).pin_memory(), non_blocking=True)      # the pinned copy is the allocator's to recycle
+            upload(self._tables, self._tab)
             self.uploads += 1
         if self._starts[k]:
             PU.lane_start(self.gt, self._lane_rows[k], self.cur, self.yaw_state, self.canon_wlh,
@@ -1111,7 +1105,7 @@ class _Lanes:
             return False
         k = s % self.plan_steps
         with torch.cuda.device(self.dev):
-            PU.crop_groups(self._plan_h[k, :self._groups[k]], self._plan_d + PU.CROP_PLAN.itemsize * k * 2 * self.L, self.scratch)
+            PU.crop_groups(self._plan_h[k, :self._groups[k]], self._tables.dev("plan", k), self.scratch)
             self._launch(s, self._lane_rows[k])
             self.s = s + 1
             self._enter(self.s)
@@ -1183,19 +1177,17 @@ class LaneTracker(_Lanes, _MatchingTracker):
             raise TypeError("LaneTracker serves the matching trackers (BAT, P2B); the motion tracker runs on MotionLaneTracker")
         L = _KTargets._n_targets(lanes)
         super().__init__(model, seed, use_graph, 1, search_capacity, model_capacity, L, "device", record_indices, bank_capacity)
-        self._lane_state(L, plan_steps)
+        self._lane_state(L, plan_steps, self.needs_ref_box, 1 if "PREVIOUS_GT" in str(self.reference_BB).upper() else 0,
+                         self.aggregation != "first")
         # by step parity: (state_in, state_out, the template counts = column 1 of state_out at stride 2); the model counts
         self._states = [(self.bank_state[1 - p], self.bank_state[p], self.bank_state[p].view(-1)[1:]) for p in (0, 1)]
         self._model_counts = self.counts_dev[1:]
 
     def _clouds(self):
-        """per cloud: (frames back from t, cropped by the reference box?, scale, offset, mode, out (L,cap,3), cap, only with has_crop?)"""
+        """the clouds of plan_lane_steps: the search window of frame t, the model crop of frame t - 1 where the bank takes one"""
         c = self
-        return ((0, True, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf, c.search_buf.shape[1], False),
-                (1, False, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, c.staging, c.model_capacity, True))
-
-    def _has_crop(self, first):
-        return first | (self.aggregation != "first")
+        return ((0, True, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf.data_ptr(), c.search_buf.shape[1], False),
+                (1, False, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, c.staging.data_ptr(), c.model_capacity, True))
 
     def _launch(self, s, lanes):
         c = self
@@ -1244,10 +1236,7 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
 
     def _clouds(self):
         c, cap = self, self.crop_buf.shape[2]
-        return tuple((1 - h, True, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], cap, False) for h in (0, 1))
-
-    def _has_crop(self, first):
-        return True
+        return tuple((1 - h, True, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h].data_ptr(), cap, False) for h in (0, 1))
 
     def _launch(self, s, lanes):
         c = self
