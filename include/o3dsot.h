@@ -820,6 +820,28 @@ int o3d_track_motion_input_drawn_lanes(const float* prev, const float* cur, cons
                                        int key_this, int N, const float* wlh, const int32_t* lanes, int L, float* points,
                                        float* candidate_bc, int32_t* used, void* stream);
 
+/* ---- the tabled forms (tracking.py, sampling="table"): the four drawn entries above with a device table of indices where they
+ * take a key, so that the free-running loop resamples with the reference's own draw.  table (cap + 1, S) int32, row-major: row n
+ * holds the S indices for a cloud of n rows (tracking.draw_table fills it with regularize_pc's numpy draw); that it has cap + 1
+ * rows of S entries is the CALLER's guarantee.  With n = min(count, cap), output row i reads
+ *     index = (n > 2) ? table[(long)n * S + i] : -1
+ * and is zero for -1.  An entry outside [0, n) leaves its row zero, as an index outside the source does in o3d_track_resample;
+ * used receives the entry as read (-1 for a zero row).  Everything else -- operands, ranges (cap 1..2^29, S and N 1..2^20),
+ * n_jobs, strides, lanes -- is the drawn twin's; a NULL table returns O3D_EINVAL before any launch.  With the same indices the
+ * outputs are o3d_track_resample's / o3d_track_motion_input's bit for bit, and row l of a lane form is the single form's.
+ * o3d_track_motion_input_tabled[_lanes] reads ONE table (capacity + 1, N) for both halves. */
+int o3d_track_resample_tabled(const float* src0, const int32_t* n_dev0, int cap0, const int32_t* table0, float* dst0, int S0,
+                              int32_t* used0, const float* src1, const int32_t* n_dev1, int cap1, const int32_t* table1, float* dst1,
+                              int S1, int32_t* used1, int n_jobs, void* stream);
+int o3d_track_motion_input_tabled(const float* prev, const float* cur, const int32_t* counts, int capacity, const int32_t* table, int N,
+                                  const float* wlh, int first_frame, float* points, float* candidate_bc, int32_t* used, void* stream);
+int o3d_track_resample_tabled_lanes(const float* src0, const int32_t* n_dev0, int stride0, int cap0, const int32_t* table0, float* dst0,
+                                    int S0, int32_t* used0, const float* src1, const int32_t* n_dev1, int stride1, int cap1,
+                                    const int32_t* table1, float* dst1, int S1, int32_t* used1, int L, void* stream);
+int o3d_track_motion_input_tabled_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity, const int32_t* table,
+                                        int N, const float* wlh, const int32_t* lanes, int L, float* points, float* candidate_bc,
+                                        int32_t* used, void* stream);
+
 /* o3d_track_offset_box per lane, one thread each.  ref = row ref_row[l] of gt (R,15), or cur[l] of cur (L,15) when ref_row[l] is
  * -1; offset (L,4), yaw_state (L,10).  The new box goes to out[l] (out (L,15) may be cur) and to results[row[l]] of the pool
  * results (R,15); limit_box's draw hashes (seed, t[l], component), so lane l's box is o3d_track_offset_box's with that seed and

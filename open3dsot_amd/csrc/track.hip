@@ -14,6 +14,9 @@
 //                         the free-running loop (tracking.py, sampling="device"): the counts are read where the crop left
 //                         them, the indices are the keyed draw of track_common.hpp, the template bank's {fixed, total} is
 //                         device state -- nothing of a frame crosses to the host
+//   o3d_track_resample_tabled / o3d_track_motion_input_tabled / o3d_track_resample_tabled_lanes / o3d_track_motion_input_tabled_lanes
+//                         the same loop with every index read from a device table of the reference's draw (sampling="table"):
+//                         the row functions of the drawn forms, instantiated for the other index source
 //   o3d_track_bank_update_lanes / o3d_track_resample_drawn_lanes / o3d_track_motion_input_drawn_lanes /
 //   o3d_track_offset_box_lanes / o3d_track_lane_start
 //                         the free-running loop L tracklets wide (tracking.LaneTracker, tracking.MotionLaneTracker): a lane is a
@@ -196,20 +199,29 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
 }
 
 // ---- the free-running loop (tracking.py, sampling="device"): counts stay on the device, the indices are drawn here ---------------
-// One job of o3d_track_resample_drawn: dst (S,3) resampled from the first min(n_dev[0], cap) rows of src with the keyed draw
-struct DrawnJob {
-    const float* src; const int32_t* n_dev; int cap; unsigned key; float* dst; int S; int32_t* used;
-};
+// The two index sources of the free-running loop: draw_index(source, i, n, S) -> the row of a cloud of n rows that output row i of
+// S reads, -1 (zero-fill) for n <= 2.  A key (unsigned): sample_index, always inside [0, n).  A table (sampling="table"): entry i
+// of row n of a device table of cap + 1 rows of S int32 (tracking.draw_table: the reference's own draw for every count),
+// whatever it holds.  The structs and row functions below are templates over the source's type
+__device__ __forceinline__ int draw_index(unsigned key, int i, int n, int S) { return n > 2 ? sample_index(key, i, n, S) : -1; }
+__device__ __forceinline__ int draw_index(const int32_t* table, int i, int n, int S) { return n > 2 ? table[(long)n * S + i] : -1; }
 
-// the row a drawn gather reads: -1 (zero-fill) for a cloud of n <= 2 rows, else sample_index -- always inside [0, n)
-__device__ __forceinline__ int drawn_index(unsigned key, int i, int n, int S) { return n > 2 ? sample_index(key, i, n, S) : -1; }
+// One job of o3d_track_resample_drawn / _tabled: dst (S,3) resampled from the first min(n_dev[0], cap) rows of src by `draw`
+template <class Draw>
+struct DrawnJobT {
+    const float* src; const int32_t* n_dev; int cap; Draw draw; float* dst; int S; int32_t* used;
+};
+using DrawnJob = DrawnJobT<unsigned>;
+using TabledJob = DrawnJobT<const int32_t*>;
 
 // resample_kernel with the count read from the device and the index drawn in place: reads n_dev and src, writes dst and used
-// THE row of both o3d_track_resample_drawn and o3d_track_resample_drawn_lanes
-__device__ __forceinline__ void resample_drawn_row(const DrawnJob& J, int i) {
+// THE row of o3d_track_resample_drawn[_lanes] and o3d_track_resample_tabled[_lanes].  An index outside [0, n) (a table's entry
+// only) leaves the row zero, as o3d_track_resample does; used receives it as read
+template <class Draw>
+__device__ __forceinline__ void resample_drawn_row(const DrawnJobT<Draw>& J, int i) {
     if (i >= J.S) return;
     const int n = min(J.n_dev[0], J.cap);
-    const int s = drawn_index(J.key, i, n, J.S);
+    const int s = draw_index(J.draw, i, n, J.S);
     float x, y, z;
     gather_row(J.src, n, &s, 0, s < 0, x, y, z);
     float* o = J.dst + 3 * (long)i;
@@ -218,6 +230,10 @@ __device__ __forceinline__ void resample_drawn_row(const DrawnJob& J, int i) {
 }
 
 __global__ __launch_bounds__(256) void resample_drawn_kernel(DrawnJob a, DrawnJob b) {
+    resample_drawn_row(blockIdx.y == 0 ? a : b, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void resample_tabled_kernel(TabledJob a, TabledJob b) {
     resample_drawn_row(blockIdx.y == 0 ? a : b, blockIdx.x * 256 + threadIdx.x);
 }
 
@@ -258,19 +274,23 @@ __device__ __forceinline__ void bank_update_rows(const BankArgs& a, int i) {
 
 __global__ __launch_bounds__(256) void bank_update_kernel(BankArgs a) { bank_update_rows(a, blockIdx.x * 256 + threadIdx.x); }
 
-struct MotionDrawnArgs {
-    const float* src[2]; const int32_t* counts; int cap; unsigned key[2];      // [0] the previous crop, [1] the current crop
+template <class Draw>
+struct MotionDrawnArgsT {
+    const float* src[2]; const int32_t* counts; int cap; Draw draw[2];      // [0] the previous crop, [1] the current crop
     const float* wlh; int N, first_frame;
     float* points; float* bc; int32_t* used;
 };
+using MotionDrawnArgs = MotionDrawnArgsT<unsigned>;
+using MotionTabledArgs = MotionDrawnArgsT<const int32_t*>;
 
-// motion_input_kernel with the two counts read from the device and the indices drawn in place: THE row of both
-// o3d_track_motion_input_drawn and o3d_track_motion_input_drawn_lanes
-__device__ __forceinline__ void motion_drawn_row(const MotionDrawnArgs& a, int i) {
+// motion_input_kernel with the two counts read from the device and the indices drawn in place: THE row of
+// o3d_track_motion_input_drawn[_lanes] and o3d_track_motion_input_tabled[_lanes]
+template <class Draw>
+__device__ __forceinline__ void motion_drawn_row(const MotionDrawnArgsT<Draw>& a, int i) {
     if (i >= 2 * a.N) return;
     const int half = i >= a.N ? 1 : 0;
     const int n = min(a.counts[half], a.cap);
-    const int s = drawn_index(a.key[half], i - half * a.N, n, a.N);
+    const int s = draw_index(a.draw[half], i - half * a.N, n, a.N);
     float px, py, pz;
     gather_row(a.src[half], n, &s, 0, s < 0, px, py, pz);
     motion_row(px, py, pz, half, a.wlh, a.first_frame, a.points + 5 * (long)i, a.bc ? a.bc + 9 * (long)i : nullptr);
@@ -278,6 +298,8 @@ __device__ __forceinline__ void motion_drawn_row(const MotionDrawnArgs& a, int i
 }
 
 __global__ __launch_bounds__(256) void motion_input_drawn_kernel(MotionDrawnArgs a) { motion_drawn_row(a, blockIdx.x * 256 + threadIdx.x); }
+
+__global__ __launch_bounds__(256) void motion_input_tabled_kernel(MotionTabledArgs a) { motion_drawn_row(a, blockIdx.x * 256 + threadIdx.x); }
 
 struct OffsetArgs {
     const float* ref; const float* offset; float* yaw_state; float* out; float* results; int32_t* frame;
@@ -316,25 +338,45 @@ __global__ __launch_bounds__(256) void bank_update_lanes_kernel(BankLanesArgs a)
     bank_update_rows(b, blockIdx.x * 256 + threadIdx.x);
 }
 
-// one cloud of o3d_track_resample_drawn_lanes: lane l reads src + 3 l cap and n_dev[l stride], writes dst + 3 l S and used + l S
-struct DrawnLanes {
-    const float* src; const int32_t* n_dev; int stride, cap; unsigned key; float* dst; int S; int32_t* used;
+// one cloud of o3d_track_resample_drawn_lanes / o3d_track_resample_tabled_lanes: lane l reads src + 3 l cap and n_dev[l stride],
+// writes dst + 3 l S and used + l S; the index source is the same for every lane
+template <class Draw>
+struct DrawnLanesT {
+    const float* src; const int32_t* n_dev; int stride, cap; Draw draw; float* dst; int S; int32_t* used;
 };
+using DrawnLanes = DrawnLanesT<unsigned>;
+using TabledLanes = DrawnLanesT<const int32_t*>;
 
-// blockIdx.y = the cloud, blockIdx.z = the lane
+// blockIdx.y = the cloud, blockIdx.z = the lane.  (The two lane kernels of a form hold the same statements: written out in each
+// kernel, the cloud is chosen by the ADDRESS of its kernel argument; behind a shared function the compiler loads both clouds.)
 __global__ __launch_bounds__(256) void resample_drawn_lanes_kernel(DrawnLanes a, DrawnLanes b) {
     const DrawnLanes& C = blockIdx.y == 0 ? a : b;
     const long l = blockIdx.z;
-    const DrawnJob J{C.src + 3 * l * C.cap, C.n_dev + l * C.stride, C.cap, C.key, C.dst + 3 * l * C.S, C.S, C.used ? C.used + l * C.S : nullptr};
+    const DrawnJob J{C.src + 3 * l * C.cap, C.n_dev + l * C.stride, C.cap, C.draw, C.dst + 3 * l * C.S, C.S, C.used ? C.used + l * C.S : nullptr};
     resample_drawn_row(J, blockIdx.x * 256 + threadIdx.x);
 }
 
-// blockIdx.y = the lane: a.src / counts / wlh / points / bc / used are the (L, ...) buffers, lane l's MotionDrawnArgs is cut out here
+__global__ __launch_bounds__(256) void resample_tabled_lanes_kernel(TabledLanes a, TabledLanes b) {
+    const TabledLanes& C = blockIdx.y == 0 ? a : b;
+    const long l = blockIdx.z;
+    const TabledJob J{C.src + 3 * l * C.cap, C.n_dev + l * C.stride, C.cap, C.draw, C.dst + 3 * l * C.S, C.S, C.used ? C.used + l * C.S : nullptr};
+    resample_drawn_row(J, blockIdx.x * 256 + threadIdx.x);
+}
+
+// blockIdx.y = the lane: a.src / counts / wlh / points / bc / used are the (L, ...) buffers, lane l's arguments are cut out here
 __global__ __launch_bounds__(256) void motion_input_drawn_lanes_kernel(MotionDrawnArgs a, const int32_t* __restrict__ lanes) {
     const long l = blockIdx.y, rows = 2 * (long)a.N;
-    const MotionDrawnArgs m{{a.src[0] + 3 * l * a.cap, a.src[1] + 3 * l * a.cap}, a.counts + 2 * l, a.cap, {a.key[0], a.key[1]}, a.wlh + 3 * l,
+    const MotionDrawnArgs m{{a.src[0] + 3 * l * a.cap, a.src[1] + 3 * l * a.cap}, a.counts + 2 * l, a.cap, {a.draw[0], a.draw[1]}, a.wlh + 3 * l,
                             a.N, lanes[O3D_LANE_COLS * l + O3D_LANE_FIRST] != 0, a.points + 5 * l * rows, a.bc ? a.bc + 9 * l * rows : nullptr,
                             a.used ? a.used + l * rows : nullptr};
+    motion_drawn_row(m, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void motion_input_tabled_lanes_kernel(MotionTabledArgs a, const int32_t* __restrict__ lanes) {
+    const long l = blockIdx.y, rows = 2 * (long)a.N;
+    const MotionTabledArgs m{{a.src[0] + 3 * l * a.cap, a.src[1] + 3 * l * a.cap}, a.counts + 2 * l, a.cap, {a.draw[0], a.draw[1]}, a.wlh + 3 * l,
+                             a.N, lanes[O3D_LANE_COLS * l + O3D_LANE_FIRST] != 0, a.points + 5 * l * rows, a.bc ? a.bc + 9 * l * rows : nullptr,
+                             a.used ? a.used + l * rows : nullptr};
     motion_drawn_row(m, blockIdx.x * 256 + threadIdx.x);
 }
 
@@ -685,6 +727,52 @@ extern "C" int o3d_track_motion_input_drawn_lanes(const float* prev, const float
         return O3D_EINVAL;
     const MotionDrawnArgs a{{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this}, wlh, N, 0, points, candidate_bc, used};
     hipLaunchKernelGGL(motion_input_drawn_lanes_kernel, dim3(o3d_cdiv(2 * N, 256), L), dim3(256), 0, o3d_stream(stream), a, lanes);
+    return o3d_launch_status();
+}
+
+// ---- the tabled forms (tracking.py, sampling="table"): the drawn forms with a table (cap + 1, S) int32 where they take a key ----
+extern "C" int o3d_track_resample_tabled(const float* src0, const int32_t* n_dev0, int cap0, const int32_t* table0, float* dst0, int S0,
+                                         int32_t* used0, const float* src1, const int32_t* n_dev1, int cap1, const int32_t* table1,
+                                         float* dst1, int S1, int32_t* used1, int n_jobs, void* stream) {
+    if (n_jobs < 1 || n_jobs > 2 || !table0 || !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) ||
+        (n_jobs == 2 && (!table1 || !drawn_job_ok(src1, n_dev1, cap1, dst1, S1))))
+        return O3D_EINVAL;
+    const TabledJob a{src0, n_dev0, cap0, table0, dst0, S0, used0};
+    const TabledJob b = n_jobs == 2 ? TabledJob{src1, n_dev1, cap1, table1, dst1, S1, used1} : a;
+    const int smax = a.S > b.S ? a.S : b.S;
+    hipLaunchKernelGGL(resample_tabled_kernel, dim3(o3d_cdiv(smax, 256), n_jobs), dim3(256), 0, o3d_stream(stream), a, b);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_motion_input_tabled(const float* prev, const float* cur, const int32_t* counts, int capacity, const int32_t* table,
+                                             int N, const float* wlh, int first_frame, float* points, float* candidate_bc, int32_t* used,
+                                             void* stream) {
+    if (!prev || !cur || !counts || !table || !wlh || !points || capacity < 1 || capacity > (1 << 29) || N < 1 || N > (1 << 20))
+        return O3D_EINVAL;
+    const MotionTabledArgs a{{prev, cur}, counts, capacity, {table, table}, wlh, N, first_frame != 0, points, candidate_bc, used};
+    hipLaunchKernelGGL(motion_input_tabled_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_resample_tabled_lanes(const float* src0, const int32_t* n_dev0, int stride0, int cap0, const int32_t* table0,
+                                               float* dst0, int S0, int32_t* used0, const float* src1, const int32_t* n_dev1, int stride1,
+                                               int cap1, const int32_t* table1, float* dst1, int S1, int32_t* used1, int L, void* stream) {
+    if (L < 1 || L > O3D_CROP_MULTI_MAX_TARGETS || stride0 < 1 || stride1 < 1 || !table0 || !table1 ||
+        !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) || !drawn_job_ok(src1, n_dev1, cap1, dst1, S1))
+        return O3D_EINVAL;
+    const TabledLanes a{src0, n_dev0, stride0, cap0, table0, dst0, S0, used0}, b{src1, n_dev1, stride1, cap1, table1, dst1, S1, used1};
+    hipLaunchKernelGGL(resample_tabled_lanes_kernel, dim3(o3d_cdiv(S0 > S1 ? S0 : S1, 256), 2, L), dim3(256), 0, o3d_stream(stream), a, b);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_track_motion_input_tabled_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity,
+                                                   const int32_t* table, int N, const float* wlh, const int32_t* lanes, int L, float* points,
+                                                   float* candidate_bc, int32_t* used, void* stream) {
+    if (!prev || !cur || !counts || !table || !wlh || !points || !lanes_ok(lanes, L) || capacity < 1 || capacity > (1 << 29) || N < 1 ||
+        N > (1 << 20))
+        return O3D_EINVAL;
+    const MotionTabledArgs a{{prev, cur}, counts, capacity, {table, table}, wlh, N, 0, points, candidate_bc, used};
+    hipLaunchKernelGGL(motion_input_tabled_lanes_kernel, dim3(o3d_cdiv(2 * N, 256), L), dim3(256), 0, o3d_stream(stream), a, lanes);
     return o3d_launch_status();
 }
 

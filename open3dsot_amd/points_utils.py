@@ -458,6 +458,39 @@ def resample_drawn(jobs):
                    "o3d_track_resample_drawn")
 
 
+def _draw_table(table, cap, S, what):
+    """a table of tracking.draw_table for clouds of up to `cap` rows resampled to S: (cap + 1, S) int32 on the GPU.  The kernels
+    index it with a device-resident count up to cap, so its shape is checked here, on every call."""
+    _need_gpu(table, what)
+    assert table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (cap + 1, S), (what, tuple(table.shape), (cap + 1, S))
+
+
+def resample_tabled(jobs):
+    """One o3d_track_resample_tabled launch (no sync): resample_drawn with a device table where it takes a key.  jobs: 1 or 2
+    tuples (src (cap,3) f32 GPU, n_dev (1,) int32 GPU, table (cap + 1, S) int32 GPU, dst (S,3), used (S,) int32 GPU | None): with
+    n = min(n_dev[0], cap), row i of dst is src[table[n, i]] (zeros when n <= 2, or where the entry lies outside [0, n)); used
+    receives the entries read (-1 for a zero-filled cloud)."""
+    assert 1 <= len(jobs) <= 2
+    args = []
+    for src, n_dev, table, dst, used in jobs:
+        _need_gpu(src, "resample_tabled")
+        _need_gpu(dst, "resample_tabled")
+        assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == 3
+        assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() % 3 == 0
+        _count_operand(n_dev)
+        S = dst.numel() // 3
+        _draw_table(table, src.shape[0], S, "resample_tabled")
+        assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= S)
+        args += [src.data_ptr(), n_dev.data_ptr(), src.shape[0], table.data_ptr(), dst.data_ptr(), S,
+                 used.data_ptr() if used is not None else None]
+    if len(jobs) == 1:
+        args += [None, None, 0, None, None, 0, None]
+    dev = jobs[0][3].device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_resample_tabled(*args, len(jobs), torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_track_resample_tabled")
+
+
 def bank_update(crop, count, bank, rule, first, has_crop, state_in, state_out):
     """One o3d_track_bank_update launch (no sync): the staged model crop `crop` (crop_cap,3) with its device count (1,) int32
     goes into `bank` (bank_cap,3) by the shape_aggregation `rule` (a key of BANK_RULES); state_in / state_out (2,) int32 GPU =
@@ -502,6 +535,35 @@ def motion_input_drawn(prev_crop, this_crop, counts, keys, wlh, first_frame, out
             _key_bits(keys[1]), n2 // 2, wlh.data_ptr(), int(bool(first_frame)), out_points.data_ptr(),
             out_bc.data_ptr() if out_bc is not None else None, used.data_ptr() if used is not None else None,
             torch.cuda.current_stream(dev).cuda_stream), "o3d_track_motion_input_drawn")
+    return out_points, out_bc
+
+
+def motion_input_tabled(prev_crop, this_crop, counts, table, wlh, first_frame, out_points, out_bc=None, used=None):
+    """One o3d_track_motion_input_tabled launch (no sync): motion_input_drawn with the 2N indices read from ONE device table
+    (cap + 1, N) int32 (both halves: the reference draws both with seed=1) where it takes two keys; the other operands are
+    motion_input_drawn's."""
+    for t in (prev_crop, this_crop):
+        _need_gpu(t, "motion_input_tabled")
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3
+    assert prev_crop.shape[0] == this_crop.shape[0]
+    _need_gpu(out_points, "motion_input_tabled")
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 2
+    assert wlh.is_cuda and wlh.dtype == torch.float32 and wlh.is_contiguous() and wlh.numel() == 3
+    assert out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.numel() % 10 == 0
+    n2 = out_points.numel() // 5
+    _draw_table(table, prev_crop.shape[0], n2 // 2, "motion_input_tabled")
+    if out_bc is None or out_bc is False:
+        out_bc = None
+    else:
+        assert out_bc.is_cuda and out_bc.dtype == torch.float32 and out_bc.is_contiguous() and out_bc.numel() == 9 * n2
+    assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= n2)
+    dev = wlh.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_motion_input_tabled(
+            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), prev_crop.shape[0], table.data_ptr(), n2 // 2,
+            wlh.data_ptr(), int(bool(first_frame)), out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
+            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_motion_input_tabled")
     return out_points, out_bc
 
 
@@ -595,6 +657,55 @@ def motion_input_drawn_lanes(prev_crop, this_crop, counts, keys, wlh, lanes, out
             wlh.data_ptr(), lanes.data_ptr(), L, out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
             used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
             "o3d_track_motion_input_drawn_lanes")
+    return out_points, out_bc
+
+
+def resample_tabled_lanes(jobs):
+    """One o3d_track_resample_tabled_lanes launch (no sync): resample_drawn_lanes with a device table where it takes a key.
+    jobs: 2 tuples (src (L,cap,3), n_dev, stride, table (cap + 1, S) int32, dst (L,S,3), used (L,S) int32 | None); every lane of
+    a cloud reads the same table."""
+    assert len(jobs) == 2
+    L, args = jobs[0][0].shape[0], []
+    for src, n_dev, stride, table, dst, used in jobs:
+        _f32(src, (L, src.shape[1], 3), "resample_tabled_lanes")
+        _f32(dst, (L, dst.shape[1], 3), "resample_tabled_lanes")
+        _strided_count(n_dev, stride, L)
+        _draw_table(table, src.shape[1], dst.shape[1], "resample_tabled_lanes")
+        if used is not None:
+            _i32(used, L * dst.shape[1], "resample_tabled_lanes")
+        args += [src.data_ptr(), n_dev.data_ptr(), int(stride), src.shape[1], table.data_ptr(), dst.data_ptr(), dst.shape[1],
+                 used.data_ptr() if used is not None else None]
+    dev = jobs[0][4].device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_resample_tabled_lanes(*args, L, torch.cuda.current_stream(dev).cuda_stream),
+                   "o3d_track_resample_tabled_lanes")
+
+
+def motion_input_tabled_lanes(prev_crop, this_crop, counts, table, wlh, lanes, out_points, out_bc=None, used=None):
+    """One o3d_track_motion_input_tabled_lanes launch (no sync): motion_input_tabled per lane, every lane on the one table
+    (cap + 1, N) int32; the other operands are motion_input_drawn_lanes'."""
+    L = _lane_table(lanes, "motion_input_tabled_lanes")
+    cap, n2 = prev_crop.shape[1], out_points.shape[1]
+    _f32(prev_crop, (L, cap, 3), "motion_input_tabled_lanes")
+    _f32(this_crop, (L, cap, 3), "motion_input_tabled_lanes")
+    _f32(wlh, (L, 3), "motion_input_tabled_lanes")
+    _f32(out_points, (L, n2, 5), "motion_input_tabled_lanes")
+    _i32(counts, 2 * L, "motion_input_tabled_lanes")
+    assert n2 % 2 == 0
+    _draw_table(table, cap, n2 // 2, "motion_input_tabled_lanes")
+    if out_bc is None or out_bc is False:
+        out_bc = None
+    else:
+        _f32(out_bc, (L, n2, 9), "motion_input_tabled_lanes")
+    if used is not None:
+        _i32(used, L * n2, "motion_input_tabled_lanes")
+    dev = wlh.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_track_motion_input_tabled_lanes(
+            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), cap, table.data_ptr(), n2 // 2, wlh.data_ptr(),
+            lanes.data_ptr(), L, out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
+            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
+            "o3d_track_motion_input_tabled_lanes")
     return out_points, out_bc
 
 

@@ -33,6 +33,12 @@ No copy in either direction and no synchronisation after the first update() (who
 every buffer has a fixed capacity (a longer crop keeps its first `capacity` survivors), and the indices are not numpy's -- the
 same rule (n <= 2 zero-fills, n == S is the identity, S > n draws with replacement, S < n without), other numbers.
 
+sampling="table" (the same four trackers): that free-running loop with the REFERENCE's indices.  The draw
+is a function of (point count, sample size) alone and the count is bounded by a fixed capacity, so the whole function is a table
+(capacity + 1, sample size) int32, built once per process with draw_indices and kept in HBM (draw_table); the kernels read row
+min(count, capacity) where the "device" mode draws (o3d_track_resample_tabled, o3d_track_motion_input_tabled and their lane
+forms).  As long as no capacity cuts a crop (overflow() == (0, 0, 0)), inputs and boxes are those of sampling="reference".
+
 The test epoch on L lanes (LaneTracker, MotionLaneTracker, evaluate(..., lanes=L)): that free-running
 loop L tracklets wide, each lane on its own tracklet's frames.  Which tracklet runs on which lane at which step (lane_schedule),
 every crop group and every lane table are host knowledge before the first frame: begin() plans them, uploads them in chunks,
@@ -73,17 +79,53 @@ def draw_indices(num_points, sample_size):
     return np.random.default_rng(1).choice(num_points, size=sample_size, replace=sample_size > num_points)
 
 
-SAMPLING = ("reference", "device")
+SAMPLING = ("reference", "device", "table")
+FREE_RUNNING = ("device", "table")
 
 
 def _sampling(name, multi=None):
-    """the `sampling` keyword checked before anything else; multi: the name of a K-target loop, which has no device mode yet"""
+    """the `sampling` keyword checked before anything else; multi: the name of a K-target loop, which has no free-running mode yet"""
     if name not in SAMPLING:
-        raise ValueError("sampling %r: expected \"reference\" or \"device\"" % (name,))
-    if multi and name == "device":
-        raise ValueError("%s: sampling=\"device\" serves the single-target trackers (SequenceTracker, MotionSequenceTracker); "
-                         "the K-target loops are a follow-up" % multi)
+        raise ValueError("sampling %r: expected \"reference\", \"device\" or \"table\"" % (name,))
+    if multi and name in FREE_RUNNING:
+        raise ValueError("%s: sampling=\"%s\" serves the single-target trackers (SequenceTracker, MotionSequenceTracker) and the "
+                         "lane trackers; the K-target loops are a follow-up" % (multi, name))
     return name
+
+
+def draw_table_host(capacity, sample_size):
+    """The reference's index draw for EVERY point count up to `capacity`, as one array: (capacity + 1, sample_size) int32, row n
+    = draw_indices(n, sample_size) for n > 2 (so row n == sample_size is the identity), rows 0..2 all -1 (the zero-fill case).
+    Pure host work, one draw_indices call per row: about a second for the default sizes."""
+    capacity, sample_size = int(capacity), int(sample_size)
+    if capacity < 1 or sample_size < 1:
+        raise ValueError("draw_table: capacity and sample_size must be positive")
+    table = np.full((capacity + 1, sample_size), -1, np.int32)
+    for n in range(3, capacity + 1):
+        table[n] = draw_indices(n, sample_size)
+    return table
+
+
+_DRAW_TABLES = {}
+
+
+def draw_table(capacity, sample_size, device):
+    """draw_table_host on `device`, built and uploaded once per process: the tables are cached by (device, capacity,
+    sample_size), so every tracker with the same sizes shares one.  A kernel of sampling="table" indexes it with the
+    device-resident point count.  Memory: 4 * (capacity + 1) * sample_size bytes (134 MB for 32768 x 1024 and for 65536 x
+    512, the default sizes), until clear_draw_tables()."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, int(capacity), int(sample_size))
+    if key not in _DRAW_TABLES:
+        _DRAW_TABLES[key] = torch.from_numpy(draw_table_host(capacity, sample_size)).to(device)
+    return _DRAW_TABLES[key]
+
+
+def clear_draw_tables():
+    """Forget the cached tables of draw_table (a tracker keeps the ones it holds)."""
+    _DRAW_TABLES.clear()
 
 
 def draw_keys(seed):
@@ -133,7 +175,7 @@ class _DeviceTracker:
 
     def __init__(self, model, seed, use_graph, max_frames, defaults, n_targets=None, sampling="reference", record_indices=False):
         self.sampling = _sampling(sampling)
-        self.free_running, self.record_indices = sampling == "device", bool(record_indices)
+        self.free_running, self.tabled, self.record_indices = sampling in FREE_RUNNING, sampling == "table", bool(record_indices)
         p = next(model.parameters())
         if not p.is_cuda:
             raise RuntimeError("%s: CPU not supported (the model must live on a GPU)" % self._NAME)
@@ -149,7 +191,7 @@ class _DeviceTracker:
         self.counts_host, self.counts_log = None, None
         if self.free_running:         # the counts stay on the device: row t of counts_log, written by a stream-ordered copy
             self.counts_log = torch.full((int(max_frames), 2), -1, dtype=torch.int32, device=self.dev)
-            self.keys = draw_keys(self.seed)
+            self.keys = None if self.tabled else draw_keys(self.seed)      # "table": the indices come from draw_table
         else:
             self.counts_host = torch.zeros(self.counts_dev.shape, dtype=torch.int32).pin_memory()
         self.cur = torch.zeros(lead + (15,), **f32)        # the last result box: the next frame's crops read it
@@ -302,7 +344,7 @@ class _DeviceTracker:
         self.counts_log[self.t, :k].copy_(self.counts_dev[:k])
 
     def counts(self):
-        """sampling="device" only: (t,2) int32 on the host, row f the two crop counts of frame f as the crop kernel counted
+        """sampling="device" / "table" only: (t,2) int32 on the host, row f the two crop counts of frame f as the crop kernel counted
         them (before the cut to the buffers' capacities), -1 where no crop was made (row 0; the model crop under `first`
         after frame 1).  One sync."""
         if not self.free_running:
@@ -434,6 +476,9 @@ class _MatchingTracker(_DeviceTracker):
             i32 = dict(dtype=torch.int32, device=self.dev)
             self.used_t = torch.full(lead + (M,), -1, **i32) if self.record_indices else None
             self.used_s = torch.full(lead + (N,), -1, **i32) if self.record_indices else None
+            if self.tabled:           # the reference's draw for every count a buffer can hold: shared between trackers
+                self.table_t = draw_table(self.bank_capacity, M, self.dev)
+                self.table_s = draw_table(int(search_capacity), N, self.dev)
         else:
             self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
         # log, per frame: (search count, model count of the crop made this frame | None, template points)
@@ -530,6 +575,12 @@ class SequenceTracker(_MatchingTracker):
     (t,2) (search count, model-crop count | -1) on the host, overflow() -> how often a capacity cut something (one sync each).
     record_indices=True keeps the last frame's indices in used_t (template_size,) / used_s (search_size,), device int32, -1
     for a zero-filled cloud.  update(points, ref_box=<device tensor>) stays free of host stops as well.
+
+    sampling="table": that free-running loop with o3d_track_resample_tabled in place of the drawn launch -- every index is read
+    from draw_table(bank_capacity, template_size) / draw_table(search_capacity, search_size), the reference's own draw for every
+    count, so the network's inputs and the boxes are those of sampling="reference" bit for bit as long as overflow() is
+    (0, 0, 0).  `seed` feeds limit_box only, as in "reference".  The tables cost 4 * (capacity + 1) * size bytes each, once per
+    process and device.
     """
     _NAME = "SequenceTracker"
 
@@ -571,8 +622,12 @@ class SequenceTracker(_MatchingTracker):
         c._log_counts(len(jobs))
         state_in, state_out = c.bank_state[(c.t + 1) & 1], c.bank_state[c.t & 1]
         PU.bank_update(c.staging, c.counts_dev[1:2], c.bank, c.aggregation, first, has_crop, state_in, state_out)
-        PU.resample_drawn([(c.bank, state_out[1:2], c.keys[0], c.inputs["template_points"], c.used_t),
-                           (c.search_buf, c.counts_dev[0:1], c.keys[1], c.inputs["search_points"], c.used_s)])
+        if c.tabled:
+            PU.resample_tabled([(c.bank, state_out[1:2], c.table_t, c.inputs["template_points"], c.used_t),
+                                (c.search_buf, c.counts_dev[0:1], c.table_s, c.inputs["search_points"], c.used_s)])
+        else:
+            PU.resample_drawn([(c.bank, state_out[1:2], c.keys[0], c.inputs["template_points"], c.used_t),
+                               (c.search_buf, c.counts_dev[0:1], c.keys[1], c.inputs["search_points"], c.used_s)])
         c._boxcloud()
         best, _ = c._network()
         PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
@@ -580,7 +635,7 @@ class SequenceTracker(_MatchingTracker):
         return c._done(pts, None)
 
     def overflow(self):
-        """sampling="device" only -> (truncated search crops, truncated model crops, frames on which the bank was full): how
+        """sampling="device" / "table" only -> (truncated search crops, truncated model crops, frames on which the bank was full): how
         often a fixed capacity cut something, worked out on the host from counts() and the capacities (one sync)."""
         return _matching_overflow(self.counts(), self.search_buf.shape[0], self.model_capacity, self.bank_capacity, self.aggregation)
 
@@ -632,7 +687,7 @@ class MultiTargetTracker(_KTargets, _MatchingTracker):
     shape_aggregation modes.  `update(points, ref_boxes=...)` (K,15): the reference's `reference_BB: previous_gt / current_gt`.
     `seed`: target k's limit_box draws use seed + k.  log, per frame: (search counts (K), model counts (K) | None, template
     counts (K)); crop_calls: the crop calls since init (one per frame, one more whenever a crop outgrew its buffer).
-    sampling: "reference" only ("device" raises ValueError: the K-target free-running loop is a follow-up)."""
+    sampling: "reference" only ("device" and "table" raise ValueError: the K-target free-running loop is a follow-up)."""
     _NAME, _REF_KW = "MultiTargetTracker", "ref_boxes"
 
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
@@ -748,7 +803,10 @@ class MotionSequenceTracker(_DeviceTracker):
     be rewritten from another stream before the NEXT frame has been enqueued (`prev_points` keeps the reference alive).
     `capacity` is then the fixed size of both crop buffers (a longer crop keeps its first survivors); `log` stays empty,
     counts() -> (t,2) (previous-frame count, current-frame count), overflow() -> (truncated previous, truncated current, 0);
-    record_indices=True keeps the last frame's indices in used_prev / used_this (point_sample_size,), -1 for a zero-filled half."""
+    record_indices=True keeps the last frame's indices in used_prev / used_this (point_sample_size,), -1 for a zero-filled half.
+
+    sampling="table": that loop with o3d_track_motion_input_tabled -- both halves read draw_table(capacity, point_sample_size), the
+    reference's own draw, so inputs and boxes are those of sampling="reference" bit for bit while overflow() is (0, 0, 0)."""
     _NAME = "MotionSequenceTracker"
 
     def __init__(self, model, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference", record_indices=False):
@@ -765,6 +823,8 @@ class MotionSequenceTracker(_DeviceTracker):
                 raise ValueError("capacity must be positive")
             self.used = torch.full((2 * N,), -1, dtype=torch.int32, device=dev) if self.record_indices else None
             self.used_prev, self.used_this = (self.used[:N], self.used[N:]) if self.record_indices else (None, None)
+            if self.tabled:           # one table for both halves: the reference draws both with seed=1
+                self.table = draw_table(int(capacity), N, dev)
         else:
             self._index_buffers(2 * N)
 
@@ -789,15 +849,16 @@ class MotionSequenceTracker(_DeviceTracker):
         c.scratch = PU.crop_jobs([(src, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], c.counts_dev[h:h + 1])
                                   for h, src in enumerate((c.prev_points, pts))], c.scratch)
         c._log_counts()
-        PU.motion_input_drawn(c.crop_buf[0], c.crop_buf[1], c.counts_dev, c.keys, c.canon_wlh, c.t == 1, c.inputs["points"],
-                              c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        (PU.motion_input_tabled if c.tabled else PU.motion_input_drawn)(
+            c.crop_buf[0], c.crop_buf[1], c.counts_dev, c.table if c.tabled else c.keys, c.canon_wlh, c.t == 1, c.inputs["points"],
+            c.inputs["candidate_bc"] if c.box_aware else False, c.used)
         est = c._network()
         PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
                       limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
         return c._done(pts, None)
 
     def overflow(self):
-        """sampling="device" only -> (truncated previous-frame crops, truncated current-frame crops, 0: there is no bank), on the
+        """sampling="device" / "table" only -> (truncated previous-frame crops, truncated current-frame crops, 0: there is no bank), on the
         host from counts() and the capacity (one sync)."""
         counts = self.counts()
         cap = self.crop_buf.shape[1]
@@ -843,7 +904,7 @@ class MultiMotionTracker(_KTargets, _DeviceTracker):
 
     log, per frame: (previous-frame counts (K), current-frame counts (K)); crop_calls: the crop calls since init (one per
     frame, one more whenever a crop outgrew the buffer: all 2K rows then grow to twice the largest count).
-    sampling: "reference" only ("device" raises ValueError: the K-target free-running loop is a follow-up)."""
+    sampling: "reference" only ("device" and "table" raise ValueError: the K-target free-running loop is a follow-up)."""
     _NAME = "MultiMotionTracker"
 
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference"):
@@ -916,6 +977,14 @@ class MultiMotionTracker(_KTargets, _DeviceTracker):
         PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
                             degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
         return c._done(pts, (n_prev, n_this))
+
+
+def _lane_sampling(name, who):
+    """the `sampling` keyword of a lane tracker: a lane never reads a count back, so only the free-running modes run on lanes"""
+    if _sampling(name) not in FREE_RUNNING:
+        raise ValueError("%s: sampling=%r draws its indices on the host, from counts that a lane tracker never reads back; "
+                         "expected \"device\" or \"table\"" % (who, name))
+    return name
 
 
 def _is_motion(model):
@@ -1168,15 +1237,17 @@ class LaneTracker(_Lanes, _MatchingTracker):
     on which a lane starts a tracklet.  An idle lane keeps its slot: no crop, no state change, no result.  The capacities are
     fixed, as for SequenceTracker(sampling="device"); overflow() reports what they cut.  reference_BB previous_gt / current_gt
     read the ground-truth pool on the device.  record_indices=True keeps the last step's indices in used_t (L,template_size)
-    and used_s (L,search_size)."""
+    and used_s (L,search_size).  sampling="table": o3d_track_resample_tabled_lanes in place of the drawn launch -- every lane
+    reads the two tables of SequenceTracker(sampling="table"), and its indices are the reference's."""
     _NAME = "LaneTracker"
 
     def __init__(self, model, lanes, seed=0, use_graph=None, search_capacity=32768, model_capacity=8192, bank_capacity=None,
-                 record_indices=False, plan_steps=256):
+                 record_indices=False, plan_steps=256, sampling="device"):
+        _lane_sampling(sampling, self._NAME)
         if _is_motion(model):
             raise TypeError("LaneTracker serves the matching trackers (BAT, P2B); the motion tracker runs on MotionLaneTracker")
         L = _KTargets._n_targets(lanes)
-        super().__init__(model, seed, use_graph, 1, search_capacity, model_capacity, L, "device", record_indices, bank_capacity)
+        super().__init__(model, seed, use_graph, 1, search_capacity, model_capacity, L, sampling, record_indices, bank_capacity)
         self._lane_state(L, plan_steps, self.needs_ref_box, 1 if "PREVIOUS_GT" in str(self.reference_BB).upper() else 0,
                          self.aggregation != "first")
         # by step parity: (state_in, state_out, the template counts = column 1 of state_out at stride 2); the model counts
@@ -1193,8 +1264,12 @@ class LaneTracker(_Lanes, _MatchingTracker):
         c = self
         state_in, state_out, totals = c._states[s & 1]
         PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
-        PU.resample_drawn_lanes([(c.bank, totals, 2, c.keys[0], c.inputs["template_points"], c.used_t),
-                                 (c.search_buf, c.counts_dev, 2, c.keys[1], c.inputs["search_points"], c.used_s)])
+        if c.tabled:
+            PU.resample_tabled_lanes([(c.bank, totals, 2, c.table_t, c.inputs["template_points"], c.used_t),
+                                      (c.search_buf, c.counts_dev, 2, c.table_s, c.inputs["search_points"], c.used_s)])
+        else:
+            PU.resample_drawn_lanes([(c.bank, totals, 2, c.keys[0], c.inputs["template_points"], c.used_t),
+                                     (c.search_buf, c.counts_dev, 2, c.keys[1], c.inputs["search_points"], c.used_s)])
         c._boxcloud()
         best, _ = c._network()
         c._offset(lanes, best)
@@ -1213,16 +1288,18 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
     tracklets wide.  The surface is LaneTracker's.  Per step: o3d_track_crop_groups (3 launches: the previous and the current
     frame of every busy lane by its last result box), o3d_track_motion_input_drawn_lanes, the batch-L network as one replayed
     HIP graph, o3d_track_offset_box_lanes.  `capacity` is the fixed size of every crop buffer; record_indices=True keeps the
-    last step's indices in used (L,2N)."""
+    last step's indices in used (L,2N).  sampling="table": o3d_track_motion_input_tabled_lanes, every lane and both halves on
+    the one table of MotionSequenceTracker(sampling="table")."""
     _NAME = "MotionLaneTracker"
 
-    def __init__(self, model, lanes, seed=0, use_graph=None, capacity=32768, record_indices=False, plan_steps=256):
+    def __init__(self, model, lanes, seed=0, use_graph=None, capacity=32768, record_indices=False, plan_steps=256, sampling="device"):
+        _lane_sampling(sampling, self._NAME)
         if not _is_motion(model):
             raise TypeError("MotionLaneTracker serves the motion tracker (M2TRACK); the matching trackers run on LaneTracker")
         L = _KTargets._n_targets(lanes)
         if int(capacity) < 1:
             raise ValueError("capacity must be positive")
-        super().__init__(model, seed, use_graph, 1, _MOTION_DEFAULTS, L, "device", record_indices)
+        super().__init__(model, seed, use_graph, 1, _MOTION_DEFAULTS, L, sampling, record_indices)
         dev, N = self.dev, int(self.point_sample_size)
         f32 = dict(dtype=torch.float32, device=dev)
         self.box_aware = bool(getattr(model, "box_aware", False))
@@ -1232,6 +1309,8 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
         self.crop_buf = torch.empty((2, L, int(capacity), 3), **f32)       # [0] the previous frame's crops, [1] the current one's
         self._crops = (self.crop_buf[0], self.crop_buf[1])
         self.used = torch.full((L, 2 * N), -1, dtype=torch.int32, device=dev) if self.record_indices else None
+        if self.tabled:
+            self.table = draw_table(int(capacity), N, dev)
         self._lane_state(L, plan_steps)
 
     def _clouds(self):
@@ -1240,8 +1319,9 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
 
     def _launch(self, s, lanes):
         c = self
-        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.keys, c.canon_wlh, lanes, c.inputs["points"],
-                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        (PU.motion_input_tabled_lanes if c.tabled else PU.motion_input_drawn_lanes)(
+            c._crops[0], c._crops[1], c.counts2, c.table if c.tabled else c.keys, c.canon_wlh, lanes, c.inputs["points"],
+            c.inputs["candidate_bc"] if c.box_aware else False, c.used)
         c._offset(lanes, c._network())
 
     def overflow(self):
@@ -1269,7 +1349,8 @@ def lane_tracker_for(model, lanes, **kw):
 def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None, sampling="reference"):
     """The convenience loop: frames = a sequence of (N_t,3) GPU tensors, box0 the target's box in frames[0]; ref_boxes[t]
     (optional, matching trackers only) is handed to update() of frame t.  The tracker class follows the model's type.
-    sampling: "reference" (numpy's index draw, one host sync per frame) | "device" (the free-running loop).
+    sampling: "reference" (numpy's index draw, one host sync per frame) | "device" (the free-running loop, its own draw) |
+    "table" (the free-running loop on the reference's draw, read from a device table).
     -> (T,15) result boxes on the host."""
     trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
     if isinstance(trk, MotionSequenceTracker) and ref_boxes is not None:
@@ -1361,21 +1442,23 @@ def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None
     return ious, distances, trk.boxes[:trk.t]
 
 
-def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None, sampling="reference", lanes=None, order="given"):
+def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None, sampling="reference", lanes=None, order="given", **capacities):
     """The test epoch (test_step / validation_step of the reference over its tracklets): every tracklet of `tracklets` -- a
     sampler.DeviceTracklets, or any iterable of (frames, boxes) -- goes through evaluate_sequence on ONE tracker (one captured
     graph for the epoch) and adds to ONE metrics.SuccessPrecision (`metrics` | None: a new one); the metric is read back once,
     at the end.  -> {"success", "precision", "frames", "tracklets"}.
-    lanes=L (with sampling="device"; `order` as lane_schedule takes it): the epoch runs L tracklets at a time on a lane tracker
-    (LaneTracker / MotionLaneTracker) and the two pools are scored in one launch.  sampling="reference" cannot run on lanes:
-    numpy's index draw needs every count on the host."""
+    lanes=L (with sampling="device" or "table"; `order` as lane_schedule takes it): the epoch runs L tracklets at a time on a
+    lane tracker (LaneTracker / MotionLaneTracker) and the two pools are scored in one launch.  sampling="reference" cannot run
+    on lanes: numpy's index draw needs every count on the host; sampling="table" is the lane epoch on the reference's indices.
+    capacities: the tracker's fixed sizes (search_capacity, model_capacity, bank_capacity | capacity), which under "table" are
+    also the sizes of its draw tables."""
     from . import metrics as MT
     _sampling(sampling)
     if lanes is not None:
-        if sampling != "device":
-            raise ValueError("evaluate: lanes=%r needs sampling=\"device\" (sampling=\"reference\" draws its indices on the host, "
-                             "from counts that a lane tracker never reads back)" % (lanes,))
-        trk = lane_tracker_for(model, lanes, seed=seed, use_graph=use_graph)
+        if sampling not in FREE_RUNNING:
+            raise ValueError("evaluate: lanes=%r needs sampling=\"device\" or \"table\" (sampling=\"reference\" draws its indices on "
+                             "the host, from counts that a lane tracker never reads back)" % (lanes,))
+        trk = lane_tracker_for(model, lanes, seed=seed, use_graph=use_graph, sampling=sampling, **capacities)
         m = metrics if metrics is not None else MT.SuccessPrecision(device=trk.dev)
         trk.run(tracklets, order=order)
         if trk.lengths:                        # an empty epoch scores nothing, as the loop below
@@ -1383,7 +1466,7 @@ def evaluate(model, tracklets, metrics=None, seed=0, use_graph=None, sampling="r
         out = m.compute()
         out["tracklets"] = len(trk.lengths)
         return out
-    trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
+    trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling, **capacities)
     m = metrics if metrics is not None else MT.SuccessPrecision(device=trk.dev)
     count = 0
     for item in tracklets:

@@ -29,13 +29,20 @@ frames resident in HBM, each timed from the first update() to the read-back of i
 JSON line: frames/s of both (median, smallest and largest run), their ratio, the crop counts of the last frame and overflow()
 of the free-running loop.
 
+--sampling table: the same measurement with a third loop in the rotation, sampling="table" (the free-running loop on the
+reference's own indices, read from tracking.draw_table): frames/s of all three, table over device and over reference, the
+build time and the bytes of the draw tables (built once, before the timed runs), and whether the table loop's boxes equal the
+reference loop's in bits.  A scratch tracker is created and warmed before the three (first_capture: the first tracker of a
+process is the slow one, whatever its mode).
+
 --lanes L: the test epoch on L lanes (tracking.lane_tracker_for(model, L): --tracklets tracklets of --frames frames each, L at a
 time in one free-running loop) against the sequential epoch of evaluate(..., sampling="device") (one free-running tracker, one
 tracklet after the other) on the same tracklets, the same model (fixture weights) and the same SuccessPrecision scoring, both
 from frames resident in HBM and both with their tracker and its captured graph reused, each timed from its first enqueue to
 the read-back of the metric, --repeats times in turn.  The tracklets are --distinct different synth sequences used in
 rotation.  Prints one JSON line: tracklet-frames/s of both (median, smallest and largest run), their ratio, the schedule's
-steps and idle-lane share, overflow() and the batch-L forward replay.
+steps and idle-lane share, overflow() and the batch-L forward replay.  With --sampling table a second lane tracker with
+sampling="table" joins the rotation: tracklet-frames/s of both lane epochs and their ratio.
 """
 import argparse
 import json
@@ -166,6 +173,19 @@ def multi_target_main(args, dev):
         "largest_box_difference_frame_1": float(diff[1]), "largest_box_difference": float(diff.max())}))
 
 
+def first_capture(model, dframes, box0):
+    """The first tracker of a process replays its captured forward 6-9 % slower than every tracker created after it, whichever
+    sampling mode it runs (measured in both creation orders).  Where --sampling table compares the two
+    free-running modes, a scratch tracker takes that place before the timed ones are created -> the tracker, for the caller to
+    keep alive (its buffers stay where they are)."""
+    scratch = tracking.tracker_for(model)
+    scratch.init(dframes[0], box0)
+    for t in range(1, min(5, len(dframes))):
+        scratch.update(dframes[t])
+    torch.cuda.synchronize()
+    return scratch
+
+
 def sampling_main(args, dev):
     if args.model.upper() == "M2TRACK":
         model, cfg = motion_model(dev)
@@ -176,10 +196,20 @@ def sampling_main(args, dev):
     frames, gt = synth.make_sequence(args.seed, args.frames, args.points)
     dframes = [torch.from_numpy(f).to(dev) for f in frames]
     warm = min(20, args.frames)
-    modes = ("device", "reference")
-    trks, times, boxes = {}, {m: [] for m in modes}, {}
+    modes = ("device", "table", "reference") if args.sampling == "table" else ("device", "reference")
+    trks, times, boxes, tables = {}, {m: [] for m in modes}, {}, {}
+    scratch = first_capture(model, dframes, gt[0]) if args.sampling == "table" else None      # noqa: F841  (kept alive)
     for m in modes:
+        if m == "table":                                                # the tables are built here, once: timed on their own
+            tracking.clear_draw_tables()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
         trks[m] = tracking.tracker_for(model, sampling=m)
+        if m == "table":
+            torch.cuda.synchronize()
+            held = list(tracking._DRAW_TABLES.values())
+            tables = {"draw_tables_build_s": round(time.perf_counter() - t0, 3), "draw_tables_shapes": [list(t.shape) for t in held],
+                      "draw_tables_bytes": int(sum(t.numel() * t.element_size() for t in held))}
         trks[m].init(dframes[0], gt[0])
         for t in range(1, warm):                                        # capture + warm-up
             trks[m].update(dframes[t])
@@ -197,9 +227,18 @@ def sampling_main(args, dev):
     fps = {m: sorted((args.frames - 1) / dt for dt in times[m]) for m in modes}
     mid = {m: fps[m][len(fps[m]) // 2] for m in modes}
     free, ref = trks["device"], trks["reference"]
+    if "table" in modes:
+        tab = trks["table"]
+        tables.update({
+            "table_sampling_frames_per_s": round(mid["table"], 1),
+            "table_sampling_frames_per_s_min_max": [round(fps["table"][0], 1), round(fps["table"][-1], 1)],
+            "table_sampling_ms_per_frame": round(1e3 / mid["table"], 4),
+            "table_over_device": round(mid["table"] / mid["device"], 3), "table_over_reference": round(mid["table"] / mid["reference"], 3),
+            "table_sampling_overflow": list(tab.overflow()), "table_sampling_hip_graph": tab.graph is not None,
+            "table_boxes_equal_reference_boxes_in_bits": bool(np.array_equal(boxes["table"].view(np.int32), boxes["reference"].view(np.int32)))})
     print(json.dumps({
-        "workload": "%s tracking a %d-frame, %d-point synthetic sequence (fixture weights, eval, fp32), median of %d runs, the two "
-                    "loops in turn" % (args.model.upper(), args.frames, args.points, args.repeats),
+        "workload": "%s tracking a %d-frame, %d-point synthetic sequence (fixture weights, eval, fp32), median of %d runs, the %d "
+                    "loops in turn" % (args.model.upper(), args.frames, args.points, args.repeats, len(modes)),
         "device_sampling_frames_per_s": round(mid["device"], 1), "reference_sampling_frames_per_s": round(mid["reference"], 1),
         "device_over_reference": round(mid["device"] / mid["reference"], 3),
         "device_sampling_frames_per_s_min_max": [round(fps["device"][0], 1), round(fps["device"][-1], 1)],
@@ -209,7 +248,7 @@ def sampling_main(args, dev):
         "device_sampling_counts_last_frame": free.counts()[-1].tolist(), "device_sampling_overflow": list(free.overflow()),
         "reference_sampling_counts_last_frame": [int(v) if v is not None else -1 for v in ref.log[-1][:2]],
         "largest_centre_distance_between_the_two_trajectories": float(
-            np.linalg.norm(boxes["device"][:, :3] - boxes["reference"][:, :3], axis=1).max())}))
+            np.linalg.norm(boxes["device"][:, :3] - boxes["reference"][:, :3], axis=1).max()), **tables}))
 
 
 def lanes_main(args, dev):
@@ -227,6 +266,7 @@ def lanes_main(args, dev):
         distinct.append(([torch.from_numpy(f).to(dev) for f in frames], torch.from_numpy(gt).to(dev)))
     tracklets = [distinct[j % len(distinct)] for j in range(args.tracklets)]
     tracked = args.tracklets * (args.frames - 1)
+    scratch = first_capture(model, distinct[0][0], distinct[0][1][0]) if args.sampling == "table" else None      # noqa: F841  (kept alive)
     lane, one = tracking.lane_tracker_for(model, L), tracking.tracker_for(model, sampling="device")
     results = {}
 
@@ -245,6 +285,17 @@ def lanes_main(args, dev):
     loops = {"lanes": run_lanes, "sequential": run_sequential}
     warm = [distinct[0]] * min(2 * L, args.tracklets)
     lane.run(warm)                                                      # capture + warm-up
+    extra = {}
+    if args.sampling == "table":                                        # a second lane epoch, on the reference's indices
+        lane_tab = tracking.lane_tracker_for(model, L, sampling="table")
+
+        def run_lanes_table():
+            m = MT.SuccessPrecision(device=dev)
+            lane_tab.run(tracklets)
+            lane_tab.score(metrics=m)
+            return m.compute()
+        loops = {"lanes": run_lanes, "lanes_table": run_lanes_table, "sequential": run_sequential}
+        lane_tab.run(warm)
     tracking.evaluate_sequence(model, *distinct[0], tracker=one)
     torch.cuda.synchronize()
     times = {k: [] for k in loops}
@@ -263,10 +314,15 @@ def lanes_main(args, dev):
     fps = {k: sorted(tracked / dt for dt in times[k]) for k in loops}
     mid = {k: fps[k][len(fps[k]) // 2] for k in loops}
     idle = float((lane.schedule[0] < 0).mean())
+    if args.sampling == "table":
+        extra = {"lanes_table_tracklet_frames_per_s": round(mid["lanes_table"], 1),
+                 "lanes_table_tracklet_frames_per_s_min_max": [round(fps["lanes_table"][0], 1), round(fps["lanes_table"][-1], 1)],
+                 "lanes_table_over_lanes": round(mid["lanes_table"] / mid["lanes"], 3), "lanes_table_overflow": list(lane_tab.overflow()),
+                 "lanes_table_hip_graph": lane_tab.graph is not None}
     print(json.dumps({
         "workload": "%s test epoch: %d tracklets of %d frames of %d points (%d distinct synthetic sequences, fixture weights, eval, "
-                    "fp32), median of %d runs, the two epochs in turn" % (args.model.upper(), args.tracklets, args.frames, args.points,
-                                                                          len(distinct), args.repeats),
+                    "fp32), median of %d runs, the %d epochs in turn" % (args.model.upper(), args.tracklets, args.frames, args.points,
+                                                                         len(distinct), args.repeats, len(loops)),
         "lanes": L, "steps": int(lane.steps), "idle_lane_share": round(idle, 4), "chunk_uploads": lane.uploads,
         "lanes_tracklet_frames_per_s": round(mid["lanes"], 1), "sequential_tracklet_frames_per_s": round(mid["sequential"], 1),
         "lanes_over_sequential": round(mid["lanes"] / mid["sequential"], 3),
@@ -276,7 +332,7 @@ def lanes_main(args, dev):
         "sequential_ms_per_frame": round(1e3 / mid["sequential"], 4), "batch_L_forward_replay_ms": round(fwd_ms, 4),
         "hip_graph": [lane.graph is not None, one.graph is not None], "lanes_overflow": list(lane.overflow()),
         "success_precision": {k: [round(float(v["success"]), 3), round(float(v["precision"]), 3)] for k, v in results.items()},
-        "scored_frames": [int(v["frames"]) for v in results.values()]}))
+        "scored_frames": [int(v["frames"]) for v in results.values()], **extra}))
 
 
 def main():
@@ -287,7 +343,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--targets", type=int, default=0, help="K > 0: the batched K-target loop against K single-target trackers in turn")
     ap.add_argument("--sampling", default="reference", choices=tracking.SAMPLING,
-                    help="device: the free-running loop against the reference-sampling loop, frames/s of both")
+                    help="device: the free-running loop against the reference-sampling loop, frames/s of both; table: the "
+                         "free-running loop on the reference's indices as a third loop (with --lanes: a second lane epoch)")
     ap.add_argument("--repeats", type=int, default=15, help="--sampling device, --lanes: timed runs per loop (the median is reported)")
     ap.add_argument("--lanes", type=int, default=0, help="L > 0: the test epoch on L lanes against the sequential free-running epoch")
     ap.add_argument("--tracklets", type=int, default=64, help="--lanes: tracklets of the epoch, --frames frames each")
@@ -302,10 +359,10 @@ def main():
             raise SystemExit("--lanes times the test epoch: no --targets, at least 2 frames per tracklet")
         return lanes_main(args, dev)
     if args.targets > 0:
-        if args.sampling == "device":
-            raise SystemExit("--sampling device times the single-target loops; the K-target loops have no device sampling yet")
+        if args.sampling in tracking.FREE_RUNNING:
+            raise SystemExit("--sampling %s times the single-target loops; the K-target loops have no free-running mode yet" % args.sampling)
         return multi_target_main(args, dev)
-    if args.sampling == "device":
+    if args.sampling in tracking.FREE_RUNNING:
         return sampling_main(args, dev)
     motion = args.model.upper() == "M2TRACK"
     if motion:
