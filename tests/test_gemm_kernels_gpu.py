@@ -1,7 +1,8 @@
 """The flat-layout (C, P) GEMM entry points -- o3d_pw_fwd, o3d_pw_dgrad, their pairs, o3d_pw_fwd_cloud (csrc/mlp_direct.hip),
 o3d_mlp_conv_wgrad2 (B = 1, dense dN) and o3d_mlp_conv_wgrad2_group (csrc/mlp_wgrad.hip) -- called through the C ABI with raw
 pointers, launch by launch and per LAUNCH CLASS, against the plain numpy fp64 reference tests/gemm_oracle.py (tied to
-Conv1d / BatchNorm1d / ReLU under autograd by tests/test_gemm_oracle_cpu.py).  Same method as
+Conv1d / BatchNorm1d / ReLU under autograd by tests/test_gemm_oracle_cpu.py).  The packed max-gradient source of the weight and
+data gradient (dN = NULL, pk) is pinned next to its producers in tests/test_pointwise_kernels_gpu.py.  Same method as
 tests/test_compact_kernels_gpu.py:
 
 EXACT leg: every floating-point input lies on a small dyadic grid (sparse weights for the larger K), so every product and
