@@ -13,10 +13,9 @@
 //   o3d_track_resample_drawn / o3d_track_bank_update / o3d_track_motion_input_drawn
 //                         the free-running loop (tracking.py, sampling="device"): the counts are read where the crop left
 //                         them, the indices are the keyed draw of track_common.hpp, the template bank's {fixed, total} is
-//                         device state -- nothing of a frame crosses to the host
-//   o3d_track_resample_tabled / o3d_track_motion_input_tabled / o3d_track_resample_tabled_lanes / o3d_track_motion_input_tabled_lanes
-//                         the same loop with every index read from a device table of the reference's draw (sampling="table"):
-//                         the row functions of the drawn forms, instantiated for the other index source
+//                         device state -- nothing of a frame crosses to the host.  Each _drawn entry point, here and on lanes,
+//                         has a _tabled twin (sampling="table"): the same launcher, kernel body and row function with the other
+//                         index source, a device table of the reference's draw
 //   o3d_track_bank_update_lanes / o3d_track_resample_drawn_lanes / o3d_track_motion_input_drawn_lanes /
 //   o3d_track_offset_box_lanes / o3d_track_lane_start
 //                         the free-running loop L tracklets wide (tracking.LaneTracker, tracking.MotionLaneTracker): a lane is a
@@ -205,6 +204,8 @@ __global__ __launch_bounds__(256) void motion_input_kernel(MotionInputArgs a) {
 // whatever it holds.  The structs and row functions below are templates over the source's type
 __device__ __forceinline__ int draw_index(unsigned key, int i, int n, int S) { return n > 2 ? sample_index(key, i, n, S) : -1; }
 __device__ __forceinline__ int draw_index(const int32_t* table, int i, int n, int S) { return n > 2 ? table[(long)n * S + i] : -1; }
+static bool draw_ok(unsigned) { return true; }                                        // host: a key is always a source,
+static bool draw_ok(const int32_t* table) { return table != nullptr; }                // a table must be there
 
 // One job of o3d_track_resample_drawn / _tabled: dst (S,3) resampled from the first min(n_dev[0], cap) rows of src by `draw`
 template <class Draw>
@@ -660,20 +661,46 @@ extern "C" int o3d_track_motion_input(const float* prev, int n_prev, const float
 }
 
 // ---- the free-running loop: no count and no index ever crosses to the host (include/o3dsot.h states the contracts) ---------------
-static bool drawn_job_ok(const float* src, const int32_t* n_dev, int cap, const float* dst, int S) {
-    return src && n_dev && dst && cap >= 1 && cap <= (1 << 29) && S >= 1 && S <= (1 << 20);
+// One host launcher per launch form, a template over the index source like the kernels: (unsigned)key for the _drawn entry point of
+// a form, a table (cap + 1, S) int32 for its _tabled one (tracking.py, sampling="table").  Job: DrawnJobT or DrawnLanesT
+template <class Job>
+static bool drawn_job_ok(const Job& j) {
+    return j.src && j.n_dev && draw_ok(j.draw) && j.dst && j.cap >= 1 && j.cap <= (1 << 29) && j.S >= 1 && j.S <= (1 << 20);
+}
+
+template <class Draw, class Job = DrawnJobT<Draw>>      // job1 is read when n_jobs == 2 only
+static int launch_resample_drawn(void (*kernel)(Job, Job), const Job& a, const Job& job1, int n_jobs, void* stream) {
+    if (n_jobs < 1 || n_jobs > 2 || !drawn_job_ok(a) || (n_jobs == 2 && !drawn_job_ok(job1))) return O3D_EINVAL;
+    const Job& b = n_jobs == 2 ? job1 : a;
+    hipLaunchKernelGGL(kernel, dim3(o3d_cdiv(a.S > b.S ? a.S : b.S, 256), n_jobs), dim3(256), 0, o3d_stream(stream), a, b);
+    return o3d_launch_status();
+}
+
+template <class Args>      // MotionDrawnArgsT, either source
+static bool motion_drawn_ok(const Args& a) {
+    return a.src[0] && a.src[1] && a.counts && draw_ok(a.draw[0]) && draw_ok(a.draw[1]) && a.wlh && a.points && a.cap >= 1 &&
+           a.cap <= (1 << 29) && a.N >= 1 && a.N <= (1 << 20);
+}
+
+template <class Draw, class Args = MotionDrawnArgsT<Draw>>
+static int launch_motion_drawn(void (*kernel)(Args), const Args& a, void* stream) {
+    if (!motion_drawn_ok(a)) return O3D_EINVAL;
+    hipLaunchKernelGGL(kernel, dim3(o3d_cdiv(2 * a.N, 256)), dim3(256), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
 }
 
 extern "C" int o3d_track_resample_drawn(const float* src0, const int32_t* n_dev0, int cap0, int key0, float* dst0, int S0, int32_t* used0,
                                         const float* src1, const int32_t* n_dev1, int cap1, int key1, float* dst1, int S1, int32_t* used1,
                                         int n_jobs, void* stream) {
-    if (n_jobs < 1 || n_jobs > 2 || !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) || (n_jobs == 2 && !drawn_job_ok(src1, n_dev1, cap1, dst1, S1)))
-        return O3D_EINVAL;
-    const DrawnJob a{src0, n_dev0, cap0, (unsigned)key0, dst0, S0, used0};
-    const DrawnJob b = n_jobs == 2 ? DrawnJob{src1, n_dev1, cap1, (unsigned)key1, dst1, S1, used1} : a;
-    const int smax = a.S > b.S ? a.S : b.S;
-    hipLaunchKernelGGL(resample_drawn_kernel, dim3(o3d_cdiv(smax, 256), n_jobs), dim3(256), 0, o3d_stream(stream), a, b);
-    return o3d_launch_status();
+    return launch_resample_drawn<unsigned>(resample_drawn_kernel, {src0, n_dev0, cap0, (unsigned)key0, dst0, S0, used0},
+                                           {src1, n_dev1, cap1, (unsigned)key1, dst1, S1, used1}, n_jobs, stream);
+}
+
+extern "C" int o3d_track_resample_tabled(const float* src0, const int32_t* n_dev0, int cap0, const int32_t* table0, float* dst0, int S0,
+                                         int32_t* used0, const float* src1, const int32_t* n_dev1, int cap1, const int32_t* table1,
+                                         float* dst1, int S1, int32_t* used1, int n_jobs, void* stream) {
+    return launch_resample_drawn<const int32_t*>(resample_tabled_kernel, {src0, n_dev0, cap0, table0, dst0, S0, used0},
+                                                 {src1, n_dev1, cap1, table1, dst1, S1, used1}, n_jobs, stream);
 }
 
 extern "C" int o3d_track_bank_update(const float* crop, const int32_t* count, int crop_cap, float* bank, int bank_cap, int rule, int first,
@@ -689,11 +716,15 @@ extern "C" int o3d_track_bank_update(const float* crop, const int32_t* count, in
 extern "C" int o3d_track_motion_input_drawn(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
                                             int key_this, int N, const float* wlh, int first_frame, float* points, float* candidate_bc,
                                             int32_t* used, void* stream) {
-    if (!prev || !cur || !counts || !wlh || !points || capacity < 1 || capacity > (1 << 29) || N < 1 || N > (1 << 20)) return O3D_EINVAL;
-    const MotionDrawnArgs a{{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this}, wlh, N, first_frame != 0, points,
-                            candidate_bc, used};
-    hipLaunchKernelGGL(motion_input_drawn_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
-    return o3d_launch_status();
+    return launch_motion_drawn<unsigned>(motion_input_drawn_kernel, {{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this},
+                                         wlh, N, first_frame != 0, points, candidate_bc, used}, stream);
+}
+
+extern "C" int o3d_track_motion_input_tabled(const float* prev, const float* cur, const int32_t* counts, int capacity, const int32_t* table,
+                                             int N, const float* wlh, int first_frame, float* points, float* candidate_bc, int32_t* used,
+                                             void* stream) {      // one table for both halves
+    return launch_motion_drawn<const int32_t*>(motion_input_tabled_kernel, {{prev, cur}, counts, capacity, {table, table}, wlh, N,
+                                               first_frame != 0, points, candidate_bc, used}, stream);
 }
 
 // ---- L lanes per launch: validation first, the contracts are include/o3dsot.h's ------------------------------------------------------
@@ -709,71 +740,46 @@ extern "C" int o3d_track_bank_update_lanes(const float* crop, const int32_t* cou
     return o3d_launch_status();
 }
 
+template <class Draw, class Job = DrawnLanesT<Draw>>
+static int launch_resample_drawn_lanes(void (*kernel)(Job, Job), const Job& a, const Job& b, int L, void* stream) {
+    if (L < 1 || L > O3D_CROP_MULTI_MAX_TARGETS || a.stride < 1 || b.stride < 1 || !drawn_job_ok(a) || !drawn_job_ok(b)) return O3D_EINVAL;
+    hipLaunchKernelGGL(kernel, dim3(o3d_cdiv(a.S > b.S ? a.S : b.S, 256), 2, L), dim3(256), 0, o3d_stream(stream), a, b);
+    return o3d_launch_status();
+}
+
+template <class Draw, class Args = MotionDrawnArgsT<Draw>>
+static int launch_motion_drawn_lanes(void (*kernel)(Args, const int32_t*), const Args& a, const int32_t* lanes, int L, void* stream) {
+    if (!motion_drawn_ok(a) || !lanes_ok(lanes, L)) return O3D_EINVAL;
+    hipLaunchKernelGGL(kernel, dim3(o3d_cdiv(2 * a.N, 256), L), dim3(256), 0, o3d_stream(stream), a, lanes);
+    return o3d_launch_status();
+}
+
 extern "C" int o3d_track_resample_drawn_lanes(const float* src0, const int32_t* n_dev0, int stride0, int cap0, int key0, float* dst0, int S0,
                                               int32_t* used0, const float* src1, const int32_t* n_dev1, int stride1, int cap1, int key1,
                                               float* dst1, int S1, int32_t* used1, int L, void* stream) {
-    if (L < 1 || L > O3D_CROP_MULTI_MAX_TARGETS || stride0 < 1 || stride1 < 1 || !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) ||
-        !drawn_job_ok(src1, n_dev1, cap1, dst1, S1))
-        return O3D_EINVAL;
-    const DrawnLanes a{src0, n_dev0, stride0, cap0, (unsigned)key0, dst0, S0, used0}, b{src1, n_dev1, stride1, cap1, (unsigned)key1, dst1, S1, used1};
-    hipLaunchKernelGGL(resample_drawn_lanes_kernel, dim3(o3d_cdiv(S0 > S1 ? S0 : S1, 256), 2, L), dim3(256), 0, o3d_stream(stream), a, b);
-    return o3d_launch_status();
-}
-
-extern "C" int o3d_track_motion_input_drawn_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
-                                                  int key_this, int N, const float* wlh, const int32_t* lanes, int L, float* points,
-                                                  float* candidate_bc, int32_t* used, void* stream) {
-    if (!prev || !cur || !counts || !wlh || !points || !lanes_ok(lanes, L) || capacity < 1 || capacity > (1 << 29) || N < 1 || N > (1 << 20))
-        return O3D_EINVAL;
-    const MotionDrawnArgs a{{prev, cur}, counts, capacity, {(unsigned)key_prev, (unsigned)key_this}, wlh, N, 0, points, candidate_bc, used};
-    hipLaunchKernelGGL(motion_input_drawn_lanes_kernel, dim3(o3d_cdiv(2 * N, 256), L), dim3(256), 0, o3d_stream(stream), a, lanes);
-    return o3d_launch_status();
-}
-
-// ---- the tabled forms (tracking.py, sampling="table"): the drawn forms with a table (cap + 1, S) int32 where they take a key ----
-extern "C" int o3d_track_resample_tabled(const float* src0, const int32_t* n_dev0, int cap0, const int32_t* table0, float* dst0, int S0,
-                                         int32_t* used0, const float* src1, const int32_t* n_dev1, int cap1, const int32_t* table1,
-                                         float* dst1, int S1, int32_t* used1, int n_jobs, void* stream) {
-    if (n_jobs < 1 || n_jobs > 2 || !table0 || !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) ||
-        (n_jobs == 2 && (!table1 || !drawn_job_ok(src1, n_dev1, cap1, dst1, S1))))
-        return O3D_EINVAL;
-    const TabledJob a{src0, n_dev0, cap0, table0, dst0, S0, used0};
-    const TabledJob b = n_jobs == 2 ? TabledJob{src1, n_dev1, cap1, table1, dst1, S1, used1} : a;
-    const int smax = a.S > b.S ? a.S : b.S;
-    hipLaunchKernelGGL(resample_tabled_kernel, dim3(o3d_cdiv(smax, 256), n_jobs), dim3(256), 0, o3d_stream(stream), a, b);
-    return o3d_launch_status();
-}
-
-extern "C" int o3d_track_motion_input_tabled(const float* prev, const float* cur, const int32_t* counts, int capacity, const int32_t* table,
-                                             int N, const float* wlh, int first_frame, float* points, float* candidate_bc, int32_t* used,
-                                             void* stream) {
-    if (!prev || !cur || !counts || !table || !wlh || !points || capacity < 1 || capacity > (1 << 29) || N < 1 || N > (1 << 20))
-        return O3D_EINVAL;
-    const MotionTabledArgs a{{prev, cur}, counts, capacity, {table, table}, wlh, N, first_frame != 0, points, candidate_bc, used};
-    hipLaunchKernelGGL(motion_input_tabled_kernel, dim3(o3d_cdiv(2 * N, 256)), dim3(256), 0, o3d_stream(stream), a);
-    return o3d_launch_status();
+    return launch_resample_drawn_lanes<unsigned>(resample_drawn_lanes_kernel, {src0, n_dev0, stride0, cap0, (unsigned)key0, dst0, S0, used0},
+                                                 {src1, n_dev1, stride1, cap1, (unsigned)key1, dst1, S1, used1}, L, stream);
 }
 
 extern "C" int o3d_track_resample_tabled_lanes(const float* src0, const int32_t* n_dev0, int stride0, int cap0, const int32_t* table0,
                                                float* dst0, int S0, int32_t* used0, const float* src1, const int32_t* n_dev1, int stride1,
                                                int cap1, const int32_t* table1, float* dst1, int S1, int32_t* used1, int L, void* stream) {
-    if (L < 1 || L > O3D_CROP_MULTI_MAX_TARGETS || stride0 < 1 || stride1 < 1 || !table0 || !table1 ||
-        !drawn_job_ok(src0, n_dev0, cap0, dst0, S0) || !drawn_job_ok(src1, n_dev1, cap1, dst1, S1))
-        return O3D_EINVAL;
-    const TabledLanes a{src0, n_dev0, stride0, cap0, table0, dst0, S0, used0}, b{src1, n_dev1, stride1, cap1, table1, dst1, S1, used1};
-    hipLaunchKernelGGL(resample_tabled_lanes_kernel, dim3(o3d_cdiv(S0 > S1 ? S0 : S1, 256), 2, L), dim3(256), 0, o3d_stream(stream), a, b);
-    return o3d_launch_status();
+    return launch_resample_drawn_lanes<const int32_t*>(resample_tabled_lanes_kernel, {src0, n_dev0, stride0, cap0, table0, dst0, S0, used0},
+                                                       {src1, n_dev1, stride1, cap1, table1, dst1, S1, used1}, L, stream);
+}
+
+extern "C" int o3d_track_motion_input_drawn_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity, int key_prev,
+                                                  int key_this, int N, const float* wlh, const int32_t* lanes, int L, float* points,
+                                                  float* candidate_bc, int32_t* used, void* stream) {      // first_frame is the lane's
+    return launch_motion_drawn_lanes<unsigned>(motion_input_drawn_lanes_kernel, {{prev, cur}, counts, capacity,
+                                               {(unsigned)key_prev, (unsigned)key_this}, wlh, N, 0, points, candidate_bc, used}, lanes, L, stream);
 }
 
 extern "C" int o3d_track_motion_input_tabled_lanes(const float* prev, const float* cur, const int32_t* counts, int capacity,
                                                    const int32_t* table, int N, const float* wlh, const int32_t* lanes, int L, float* points,
                                                    float* candidate_bc, int32_t* used, void* stream) {
-    if (!prev || !cur || !counts || !table || !wlh || !points || !lanes_ok(lanes, L) || capacity < 1 || capacity > (1 << 29) || N < 1 ||
-        N > (1 << 20))
-        return O3D_EINVAL;
-    const MotionTabledArgs a{{prev, cur}, counts, capacity, {table, table}, wlh, N, 0, points, candidate_bc, used};
-    hipLaunchKernelGGL(motion_input_tabled_lanes_kernel, dim3(o3d_cdiv(2 * N, 256), L), dim3(256), 0, o3d_stream(stream), a, lanes);
-    return o3d_launch_status();
+    return launch_motion_drawn_lanes<const int32_t*>(motion_input_tabled_lanes_kernel, {{prev, cur}, counts, capacity, {table, table}, wlh, N,
+                                                     0, points, candidate_bc, used}, lanes, L, stream);
 }
 
 extern "C" int o3d_track_offset_box_lanes(const float* cur, const float* gt, int R, const float* offset, float* yaw_state, const int32_t* lanes,

@@ -434,30 +434,6 @@ def _count_operand(t):
     assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= 1
 
 
-def resample_drawn(jobs):
-    """One o3d_track_resample_drawn launch (no sync).  jobs: 1 or 2 tuples (src (cap,3) f32 GPU, n_dev (1,) int32 GPU, key,
-    dst (S,3), used (S,) int32 GPU | None): dst is resampled from the first min(n_dev[0], cap) rows of src with the keyed draw
-    (zeros when that count is <= 2); used receives the indices (-1 for a zero row)."""
-    assert 1 <= len(jobs) <= 2
-    args = []
-    for src, n_dev, key, dst, used in jobs:
-        _need_gpu(src, "resample_drawn")
-        _need_gpu(dst, "resample_drawn")
-        assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == 3
-        assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() % 3 == 0
-        _count_operand(n_dev)
-        S = dst.numel() // 3
-        assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= S)
-        args += [src.data_ptr(), n_dev.data_ptr(), src.shape[0], _key_bits(key), dst.data_ptr(), S,
-                 used.data_ptr() if used is not None else None]
-    if len(jobs) == 1:
-        args += [None, None, 0, 0, None, 0, None]
-    dev = jobs[0][3].device
-    with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_resample_drawn(*args, len(jobs), torch.cuda.current_stream(dev).cuda_stream),
-                   "o3d_track_resample_drawn")
-
-
 def _draw_table(table, cap, S, what):
     """a table of tracking.draw_table for clouds of up to `cap` rows resampled to S: (cap + 1, S) int32 on the GPU.  The kernels
     index it with a device-resident count up to cap, so its shape is checked here, on every call."""
@@ -465,30 +441,52 @@ def _draw_table(table, cap, S, what):
     assert table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (cap + 1, S), (what, tuple(table.shape), (cap + 1, S))
 
 
-def resample_tabled(jobs):
-    """One o3d_track_resample_tabled launch (no sync): resample_drawn with a device table where it takes a key.  jobs: 1 or 2
-    tuples (src (cap,3) f32 GPU, n_dev (1,) int32 GPU, table (cap + 1, S) int32 GPU, dst (S,3), used (S,) int32 GPU | None): with
-    n = min(n_dev[0], cap), row i of dst is src[table[n, i]] (zeros when n <= 2, or where the entry lies outside [0, n)); used
-    receives the entries read (-1 for a zero-filled cloud)."""
+_DRAW_ENTRIES = {      # the wrapper -> its C entry point for keys, for tables
+    "resample_drawn": ("o3d_track_resample_drawn", "o3d_track_resample_tabled"),
+    "motion_input_drawn": ("o3d_track_motion_input_drawn", "o3d_track_motion_input_tabled"),
+    "resample_drawn_lanes": ("o3d_track_resample_drawn_lanes", "o3d_track_resample_tabled_lanes"),
+    "motion_input_drawn_lanes": ("o3d_track_motion_input_drawn_lanes", "o3d_track_motion_input_tabled_lanes")}
+
+
+def _draw_sources(what, sources, caps_sizes):
+    """The index sources of one launch of the wrapper `what` -> (the name of the C entry point, their C arguments, the C argument
+    of an absent source).  Key and table are two values of one argument here and two entry points in the C ABI: a Python or numpy
+    integer is a KEY (the keyed draw), a tensor is a TABLE (tracking.draw_table: the reference's draw), checked against the
+    (cap, S) of its cloud.  All sources of a launch are of one kind."""
+    tables = [torch.is_tensor(s) for s in sources]
+    if any(tables) != all(tables):
+        raise ValueError("%s: the index sources of one launch must be all keys or all tables" % what)
+    if not tables[0]:
+        return _DRAW_ENTRIES[what][0], [_key_bits(s) for s in sources], 0
+    for table, (cap, S) in zip(sources, caps_sizes):
+        _draw_table(table, cap, S, what)
+    return _DRAW_ENTRIES[what][1], [t.data_ptr() for t in sources], None
+
+
+def resample_drawn(jobs):
+    """One o3d_track_resample_drawn launch, or its table twin's (no sync).  jobs: 1 or 2 tuples (src (cap,3) f32 GPU, n_dev (1,)
+    int32 GPU, source, dst (S,3), used (S,) int32 GPU | None): with n = min(n_dev[0], cap), dst is resampled from the first n rows
+    of src (zeros when n <= 2).  source (_draw_sources): a key draws the indices on the device; with a table (cap + 1, S) int32
+    GPU, row i of dst is src[table[n, i]], zeros where that entry lies outside [0, n).  used receives the indices (-1 for a
+    zero-filled cloud)."""
     assert 1 <= len(jobs) <= 2
-    args = []
-    for src, n_dev, table, dst, used in jobs:
-        _need_gpu(src, "resample_tabled")
-        _need_gpu(dst, "resample_tabled")
+    for src, n_dev, _, dst, used in jobs:
+        _need_gpu(src, "resample_drawn")
+        _need_gpu(dst, "resample_drawn")
         assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.shape[1] == 3
         assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() % 3 == 0
         _count_operand(n_dev)
-        S = dst.numel() // 3
-        _draw_table(table, src.shape[0], S, "resample_tabled")
-        assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= S)
-        args += [src.data_ptr(), n_dev.data_ptr(), src.shape[0], table.data_ptr(), dst.data_ptr(), S,
+        assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= dst.numel() // 3)
+    entry, draws, absent = _draw_sources("resample_drawn", [j[2] for j in jobs], [(j[0].shape[0], j[3].numel() // 3) for j in jobs])
+    args = []
+    for (src, n_dev, _, dst, used), draw in zip(jobs, draws):
+        args += [src.data_ptr(), n_dev.data_ptr(), src.shape[0], draw, dst.data_ptr(), dst.numel() // 3,
                  used.data_ptr() if used is not None else None]
     if len(jobs) == 1:
-        args += [None, None, 0, None, None, 0, None]
+        args += [None, None, 0, absent, None, 0, None]
     dev = jobs[0][3].device
     with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_resample_tabled(*args, len(jobs), torch.cuda.current_stream(dev).cuda_stream),
-                   "o3d_track_resample_tabled")
+        capi.check(getattr(capi.load(), entry)(*args, len(jobs), torch.cuda.current_stream(dev).cuda_stream), entry)
 
 
 def bank_update(crop, count, bank, rule, first, has_crop, state_in, state_out):
@@ -509,9 +507,18 @@ def bank_update(crop, count, bank, rule, first, has_crop, state_in, state_out):
             "o3d_track_bank_update")
 
 
+def _motion_sources(what, source, cap, N):
+    """the index source of a motion form: (key of the previous crop, key of the current one), or ONE table (cap + 1, N) for both
+    halves (the reference draws both with seed=1) -> _draw_sources' entry point and C arguments"""
+    if torch.is_tensor(source):
+        return _draw_sources(what, [source], [(cap, N)])[:2]
+    key_prev, key_this = source
+    return _draw_sources(what, [key_prev, key_this], [(cap, N), (cap, N)])[:2]
+
+
 def motion_input_drawn(prev_crop, this_crop, counts, keys, wlh, first_frame, out_points, out_bc=None, used=None):
-    """One o3d_track_motion_input_drawn launch (no sync): motion_input with the two counts read from `counts` (2,) int32 GPU
-    (capped at the crops' common capacity) and the 2N indices drawn on the device with keys = (previous, current).
+    """One o3d_track_motion_input_drawn launch, or its table twin's (no sync): motion_input with the two counts read from `counts`
+    (2,) int32 GPU (capped at the crops' common capacity) and the 2N indices taken on the device from `keys` (_motion_sources).
     out_points (2N,5); out_bc (2N,9) | None / False (box_aware=False); used (2N,) int32 GPU | None: the indices, -1 for a
     zero-filled row."""
     for t in (prev_crop, this_crop):
@@ -523,6 +530,7 @@ def motion_input_drawn(prev_crop, this_crop, counts, keys, wlh, first_frame, out
     assert wlh.is_cuda and wlh.dtype == torch.float32 and wlh.is_contiguous() and wlh.numel() == 3
     assert out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.numel() % 10 == 0
     n2 = out_points.numel() // 5
+    entry, draws = _motion_sources("motion_input_drawn", keys, prev_crop.shape[0], n2 // 2)
     if out_bc is None or out_bc is False:
         out_bc = None
     else:
@@ -530,40 +538,10 @@ def motion_input_drawn(prev_crop, this_crop, counts, keys, wlh, first_frame, out
     assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= n2)
     dev = wlh.device
     with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_motion_input_drawn(
-            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), prev_crop.shape[0], _key_bits(keys[0]),
-            _key_bits(keys[1]), n2 // 2, wlh.data_ptr(), int(bool(first_frame)), out_points.data_ptr(),
-            out_bc.data_ptr() if out_bc is not None else None, used.data_ptr() if used is not None else None,
-            torch.cuda.current_stream(dev).cuda_stream), "o3d_track_motion_input_drawn")
-    return out_points, out_bc
-
-
-def motion_input_tabled(prev_crop, this_crop, counts, table, wlh, first_frame, out_points, out_bc=None, used=None):
-    """One o3d_track_motion_input_tabled launch (no sync): motion_input_drawn with the 2N indices read from ONE device table
-    (cap + 1, N) int32 (both halves: the reference draws both with seed=1) where it takes two keys; the other operands are
-    motion_input_drawn's."""
-    for t in (prev_crop, this_crop):
-        _need_gpu(t, "motion_input_tabled")
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3
-    assert prev_crop.shape[0] == this_crop.shape[0]
-    _need_gpu(out_points, "motion_input_tabled")
-    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= 2
-    assert wlh.is_cuda and wlh.dtype == torch.float32 and wlh.is_contiguous() and wlh.numel() == 3
-    assert out_points.dtype == torch.float32 and out_points.is_contiguous() and out_points.numel() % 10 == 0
-    n2 = out_points.numel() // 5
-    _draw_table(table, prev_crop.shape[0], n2 // 2, "motion_input_tabled")
-    if out_bc is None or out_bc is False:
-        out_bc = None
-    else:
-        assert out_bc.is_cuda and out_bc.dtype == torch.float32 and out_bc.is_contiguous() and out_bc.numel() == 9 * n2
-    assert used is None or (used.is_cuda and used.dtype == torch.int32 and used.is_contiguous() and used.numel() >= n2)
-    dev = wlh.device
-    with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_motion_input_tabled(
-            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), prev_crop.shape[0], table.data_ptr(), n2 // 2,
-            wlh.data_ptr(), int(bool(first_frame)), out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
-            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
-            "o3d_track_motion_input_tabled")
+        capi.check(getattr(capi.load(), entry)(
+            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), prev_crop.shape[0], *draws, n2 // 2, wlh.data_ptr(),
+            int(bool(first_frame)), out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
+            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream), entry)
     return out_points, out_bc
 
 
@@ -614,28 +592,31 @@ def bank_update_lanes(crop, counts, count_stride, bank, rule, lanes, state_in, s
 
 
 def resample_drawn_lanes(jobs):
-    """One o3d_track_resample_drawn_lanes launch (no sync).  jobs: 2 tuples (src (L,cap,3), n_dev, stride, key, dst (L,S,3),
-    used (L,S) int32 | None); lane l's count is element l * stride of n_dev (an int32 GPU tensor or view)."""
+    """One o3d_track_resample_drawn_lanes launch, or its table twin's (no sync).  jobs: 2 tuples (src (L,cap,3), n_dev, stride,
+    source, dst (L,S,3), used (L,S) int32 | None); lane l's count is element l * stride of n_dev (an int32 GPU tensor or view);
+    source: resample_drawn's, a key or a table (cap + 1, S) int32, the same for every lane of its cloud."""
     assert len(jobs) == 2
-    L, args = jobs[0][0].shape[0], []
-    for src, n_dev, stride, key, dst, used in jobs:
+    L = jobs[0][0].shape[0]
+    for src, n_dev, stride, _, dst, used in jobs:
         _f32(src, (L, src.shape[1], 3), "resample_drawn_lanes")
         _f32(dst, (L, dst.shape[1], 3), "resample_drawn_lanes")
         _strided_count(n_dev, stride, L)
         if used is not None:
             _i32(used, L * dst.shape[1], "resample_drawn_lanes")
-        args += [src.data_ptr(), n_dev.data_ptr(), int(stride), src.shape[1], _key_bits(key), dst.data_ptr(), dst.shape[1],
+    entry, draws, _ = _draw_sources("resample_drawn_lanes", [j[3] for j in jobs], [(j[0].shape[1], j[4].shape[1]) for j in jobs])
+    args = []
+    for (src, n_dev, stride, _, dst, used), draw in zip(jobs, draws):
+        args += [src.data_ptr(), n_dev.data_ptr(), int(stride), src.shape[1], draw, dst.data_ptr(), dst.shape[1],
                  used.data_ptr() if used is not None else None]
     dev = jobs[0][4].device
     with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_resample_drawn_lanes(*args, L, torch.cuda.current_stream(dev).cuda_stream),
-                   "o3d_track_resample_drawn_lanes")
+        capi.check(getattr(capi.load(), entry)(*args, L, torch.cuda.current_stream(dev).cuda_stream), entry)
 
 
 def motion_input_drawn_lanes(prev_crop, this_crop, counts, keys, wlh, lanes, out_points, out_bc=None, used=None):
-    """One o3d_track_motion_input_drawn_lanes launch (no sync): motion_input_drawn per lane.  prev_crop / this_crop (L,cap,3),
-    counts (L,2) int32, wlh (L,3), lanes (L,LANE_COLS): `first` is the lane's first_frame; out_points (L,2N,5), out_bc
-    (L,2N,9) | None / False, used (L,2N) int32 | None."""
+    """One o3d_track_motion_input_drawn_lanes launch, or its table twin's (no sync): motion_input_drawn per lane, every lane on
+    the same `keys` (_motion_sources).  prev_crop / this_crop (L,cap,3), counts (L,2) int32, wlh (L,3), lanes (L,LANE_COLS):
+    `first` is the lane's first_frame; out_points (L,2N,5), out_bc (L,2N,9) | None / False, used (L,2N) int32 | None."""
     L = _lane_table(lanes, "motion_input_drawn_lanes")
     cap, n2 = prev_crop.shape[1], out_points.shape[1]
     _f32(prev_crop, (L, cap, 3), "motion_input_drawn_lanes")
@@ -644,6 +625,7 @@ def motion_input_drawn_lanes(prev_crop, this_crop, counts, keys, wlh, lanes, out
     _f32(out_points, (L, n2, 5), "motion_input_drawn_lanes")
     _i32(counts, 2 * L, "motion_input_drawn_lanes")
     assert n2 % 2 == 0
+    entry, draws = _motion_sources("motion_input_drawn_lanes", keys, cap, n2 // 2)
     if out_bc is None or out_bc is False:
         out_bc = None
     else:
@@ -652,60 +634,10 @@ def motion_input_drawn_lanes(prev_crop, this_crop, counts, keys, wlh, lanes, out
         _i32(used, L * n2, "motion_input_drawn_lanes")
     dev = wlh.device
     with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_motion_input_drawn_lanes(
-            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), cap, _key_bits(keys[0]), _key_bits(keys[1]), n2 // 2,
-            wlh.data_ptr(), lanes.data_ptr(), L, out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
-            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
-            "o3d_track_motion_input_drawn_lanes")
-    return out_points, out_bc
-
-
-def resample_tabled_lanes(jobs):
-    """One o3d_track_resample_tabled_lanes launch (no sync): resample_drawn_lanes with a device table where it takes a key.
-    jobs: 2 tuples (src (L,cap,3), n_dev, stride, table (cap + 1, S) int32, dst (L,S,3), used (L,S) int32 | None); every lane of
-    a cloud reads the same table."""
-    assert len(jobs) == 2
-    L, args = jobs[0][0].shape[0], []
-    for src, n_dev, stride, table, dst, used in jobs:
-        _f32(src, (L, src.shape[1], 3), "resample_tabled_lanes")
-        _f32(dst, (L, dst.shape[1], 3), "resample_tabled_lanes")
-        _strided_count(n_dev, stride, L)
-        _draw_table(table, src.shape[1], dst.shape[1], "resample_tabled_lanes")
-        if used is not None:
-            _i32(used, L * dst.shape[1], "resample_tabled_lanes")
-        args += [src.data_ptr(), n_dev.data_ptr(), int(stride), src.shape[1], table.data_ptr(), dst.data_ptr(), dst.shape[1],
-                 used.data_ptr() if used is not None else None]
-    dev = jobs[0][4].device
-    with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_resample_tabled_lanes(*args, L, torch.cuda.current_stream(dev).cuda_stream),
-                   "o3d_track_resample_tabled_lanes")
-
-
-def motion_input_tabled_lanes(prev_crop, this_crop, counts, table, wlh, lanes, out_points, out_bc=None, used=None):
-    """One o3d_track_motion_input_tabled_lanes launch (no sync): motion_input_tabled per lane, every lane on the one table
-    (cap + 1, N) int32; the other operands are motion_input_drawn_lanes'."""
-    L = _lane_table(lanes, "motion_input_tabled_lanes")
-    cap, n2 = prev_crop.shape[1], out_points.shape[1]
-    _f32(prev_crop, (L, cap, 3), "motion_input_tabled_lanes")
-    _f32(this_crop, (L, cap, 3), "motion_input_tabled_lanes")
-    _f32(wlh, (L, 3), "motion_input_tabled_lanes")
-    _f32(out_points, (L, n2, 5), "motion_input_tabled_lanes")
-    _i32(counts, 2 * L, "motion_input_tabled_lanes")
-    assert n2 % 2 == 0
-    _draw_table(table, cap, n2 // 2, "motion_input_tabled_lanes")
-    if out_bc is None or out_bc is False:
-        out_bc = None
-    else:
-        _f32(out_bc, (L, n2, 9), "motion_input_tabled_lanes")
-    if used is not None:
-        _i32(used, L * n2, "motion_input_tabled_lanes")
-    dev = wlh.device
-    with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_track_motion_input_tabled_lanes(
-            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), cap, table.data_ptr(), n2 // 2, wlh.data_ptr(),
-            lanes.data_ptr(), L, out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
-            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream),
-            "o3d_track_motion_input_tabled_lanes")
+        capi.check(getattr(capi.load(), entry)(
+            prev_crop.data_ptr(), this_crop.data_ptr(), counts.data_ptr(), cap, *draws, n2 // 2, wlh.data_ptr(), lanes.data_ptr(), L,
+            out_points.data_ptr(), out_bc.data_ptr() if out_bc is not None else None,
+            used.data_ptr() if used is not None else None, torch.cuda.current_stream(dev).cuda_stream), entry)
     return out_points, out_bc
 
 

@@ -36,8 +36,10 @@ same rule (n <= 2 zero-fills, n == S is the identity, S > n draws with replaceme
 sampling="table" (the same four trackers): that free-running loop with the REFERENCE's indices.  The draw
 is a function of (point count, sample size) alone and the count is bounded by a fixed capacity, so the whole function is a table
 (capacity + 1, sample size) int32, built once per process with draw_indices and kept in HBM (draw_table); the kernels read row
-min(count, capacity) where the "device" mode draws (o3d_track_resample_tabled, o3d_track_motion_input_tabled and their lane
-forms).  As long as no capacity cuts a crop (overflow() == (0, 0, 0)), inputs and boxes are those of sampling="reference".
+min(count, capacity) where the "device" mode draws.  As long as no capacity cuts a crop (overflow() == (0, 0, 0)), inputs and
+boxes are those of sampling="reference".  Above the C ABI, key and table are two values of ONE argument, the index source of
+PU.resample_drawn / motion_input_drawn and their lane forms, which a tracker chooses once, when it is built (draw_src); in the
+ABI each o3d_track_*_drawn* entry point named here has a _tabled twin that takes the table.
 
 The test epoch on L lanes (LaneTracker, MotionLaneTracker, evaluate(..., lanes=L)): that free-running
 loop L tracklets wide, each lane on its own tracklet's frames.  Which tracklet runs on which lane at which step (lane_schedule),
@@ -479,6 +481,7 @@ class _MatchingTracker(_DeviceTracker):
             if self.tabled:           # the reference's draw for every count a buffer can hold: shared between trackers
                 self.table_t = draw_table(self.bank_capacity, M, self.dev)
                 self.table_s = draw_table(int(search_capacity), N, self.dev)
+            self.draw_src = (self.table_t, self.table_s) if self.tabled else self.keys      # PU.resample_drawn's sources: (template, search)
         else:
             self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
         # log, per frame: (search count, model count of the crop made this frame | None, template points)
@@ -576,7 +579,7 @@ class SequenceTracker(_MatchingTracker):
     record_indices=True keeps the last frame's indices in used_t (template_size,) / used_s (search_size,), device int32, -1
     for a zero-filled cloud.  update(points, ref_box=<device tensor>) stays free of host stops as well.
 
-    sampling="table": that free-running loop with o3d_track_resample_tabled in place of the drawn launch -- every index is read
+    sampling="table": that free-running loop with tables as the index sources of the resample launch -- every index is read
     from draw_table(bank_capacity, template_size) / draw_table(search_capacity, search_size), the reference's own draw for every
     count, so the network's inputs and the boxes are those of sampling="reference" bit for bit as long as overflow() is
     (0, 0, 0).  `seed` feeds limit_box only, as in "reference".  The tables cost 4 * (capacity + 1) * size bytes each, once per
@@ -622,12 +625,8 @@ class SequenceTracker(_MatchingTracker):
         c._log_counts(len(jobs))
         state_in, state_out = c.bank_state[(c.t + 1) & 1], c.bank_state[c.t & 1]
         PU.bank_update(c.staging, c.counts_dev[1:2], c.bank, c.aggregation, first, has_crop, state_in, state_out)
-        if c.tabled:
-            PU.resample_tabled([(c.bank, state_out[1:2], c.table_t, c.inputs["template_points"], c.used_t),
-                                (c.search_buf, c.counts_dev[0:1], c.table_s, c.inputs["search_points"], c.used_s)])
-        else:
-            PU.resample_drawn([(c.bank, state_out[1:2], c.keys[0], c.inputs["template_points"], c.used_t),
-                               (c.search_buf, c.counts_dev[0:1], c.keys[1], c.inputs["search_points"], c.used_s)])
+        PU.resample_drawn([(c.bank, state_out[1:2], c.draw_src[0], c.inputs["template_points"], c.used_t),
+                           (c.search_buf, c.counts_dev[0:1], c.draw_src[1], c.inputs["search_points"], c.used_s)])
         c._boxcloud()
         best, _ = c._network()
         PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
@@ -805,7 +804,7 @@ class MotionSequenceTracker(_DeviceTracker):
     counts() -> (t,2) (previous-frame count, current-frame count), overflow() -> (truncated previous, truncated current, 0);
     record_indices=True keeps the last frame's indices in used_prev / used_this (point_sample_size,), -1 for a zero-filled half.
 
-    sampling="table": that loop with o3d_track_motion_input_tabled -- both halves read draw_table(capacity, point_sample_size), the
+    sampling="table": that loop with a table as the index source -- both halves read draw_table(capacity, point_sample_size), the
     reference's own draw, so inputs and boxes are those of sampling="reference" bit for bit while overflow() is (0, 0, 0)."""
     _NAME = "MotionSequenceTracker"
 
@@ -825,6 +824,7 @@ class MotionSequenceTracker(_DeviceTracker):
             self.used_prev, self.used_this = (self.used[:N], self.used[N:]) if self.record_indices else (None, None)
             if self.tabled:           # one table for both halves: the reference draws both with seed=1
                 self.table = draw_table(int(capacity), N, dev)
+            self.draw_src = self.table if self.tabled else self.keys      # PU.motion_input_drawn's source
         else:
             self._index_buffers(2 * N)
 
@@ -849,9 +849,8 @@ class MotionSequenceTracker(_DeviceTracker):
         c.scratch = PU.crop_jobs([(src, c.cur, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h], c.counts_dev[h:h + 1])
                                   for h, src in enumerate((c.prev_points, pts))], c.scratch)
         c._log_counts()
-        (PU.motion_input_tabled if c.tabled else PU.motion_input_drawn)(
-            c.crop_buf[0], c.crop_buf[1], c.counts_dev, c.table if c.tabled else c.keys, c.canon_wlh, c.t == 1, c.inputs["points"],
-            c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        PU.motion_input_drawn(c.crop_buf[0], c.crop_buf[1], c.counts_dev, c.draw_src, c.canon_wlh, c.t == 1, c.inputs["points"],
+                              c.inputs["candidate_bc"] if c.box_aware else False, c.used)
         est = c._network()
         PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
                       limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
@@ -1237,7 +1236,7 @@ class LaneTracker(_Lanes, _MatchingTracker):
     on which a lane starts a tracklet.  An idle lane keeps its slot: no crop, no state change, no result.  The capacities are
     fixed, as for SequenceTracker(sampling="device"); overflow() reports what they cut.  reference_BB previous_gt / current_gt
     read the ground-truth pool on the device.  record_indices=True keeps the last step's indices in used_t (L,template_size)
-    and used_s (L,search_size).  sampling="table": o3d_track_resample_tabled_lanes in place of the drawn launch -- every lane
+    and used_s (L,search_size).  sampling="table": tables as the index sources of the resample launch -- every lane
     reads the two tables of SequenceTracker(sampling="table"), and its indices are the reference's."""
     _NAME = "LaneTracker"
 
@@ -1264,12 +1263,8 @@ class LaneTracker(_Lanes, _MatchingTracker):
         c = self
         state_in, state_out, totals = c._states[s & 1]
         PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
-        if c.tabled:
-            PU.resample_tabled_lanes([(c.bank, totals, 2, c.table_t, c.inputs["template_points"], c.used_t),
-                                      (c.search_buf, c.counts_dev, 2, c.table_s, c.inputs["search_points"], c.used_s)])
-        else:
-            PU.resample_drawn_lanes([(c.bank, totals, 2, c.keys[0], c.inputs["template_points"], c.used_t),
-                                     (c.search_buf, c.counts_dev, 2, c.keys[1], c.inputs["search_points"], c.used_s)])
+        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
+                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
         c._boxcloud()
         best, _ = c._network()
         c._offset(lanes, best)
@@ -1288,7 +1283,7 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
     tracklets wide.  The surface is LaneTracker's.  Per step: o3d_track_crop_groups (3 launches: the previous and the current
     frame of every busy lane by its last result box), o3d_track_motion_input_drawn_lanes, the batch-L network as one replayed
     HIP graph, o3d_track_offset_box_lanes.  `capacity` is the fixed size of every crop buffer; record_indices=True keeps the
-    last step's indices in used (L,2N).  sampling="table": o3d_track_motion_input_tabled_lanes, every lane and both halves on
+    last step's indices in used (L,2N).  sampling="table": a table as the index source, every lane and both halves on
     the one table of MotionSequenceTracker(sampling="table")."""
     _NAME = "MotionLaneTracker"
 
@@ -1311,6 +1306,7 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
         self.used = torch.full((L, 2 * N), -1, dtype=torch.int32, device=dev) if self.record_indices else None
         if self.tabled:
             self.table = draw_table(int(capacity), N, dev)
+        self.draw_src = self.table if self.tabled else self.keys      # PU.motion_input_drawn_lanes' source
         self._lane_state(L, plan_steps)
 
     def _clouds(self):
@@ -1319,9 +1315,8 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
 
     def _launch(self, s, lanes):
         c = self
-        (PU.motion_input_tabled_lanes if c.tabled else PU.motion_input_drawn_lanes)(
-            c._crops[0], c._crops[1], c.counts2, c.table if c.tabled else c.keys, c.canon_wlh, lanes, c.inputs["points"],
-            c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.draw_src, c.canon_wlh, lanes, c.inputs["points"],
+                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
         c._offset(lanes, c._network())
 
     def overflow(self):

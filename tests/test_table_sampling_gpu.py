@@ -90,7 +90,7 @@ def test_resample_tabled_equals_resample_on_the_reference_indices(dev):
         for n in counts_of(cap, S):
             ne = min(n, cap)
             job, dguard, uguard = tabled_alone(src, n, table, S, dev)
-            PU.resample_tabled([job])                                                  # n_jobs = 1
+            PU.resample_drawn([job])                                                  # n_jobs = 1
             idx, want_used = drawn(ne, S, dev)
             want = torch.full((S, 3), SENT, device=dev)
             PU.resample_jobs([(None if idx is None else src[:ne], idx, want)])
@@ -100,7 +100,7 @@ def test_resample_tabled_equals_resample_on_the_reference_indices(dev):
             if ne <= 2:
                 assert not bool(job[3].any())
             alone[cap, n] = (job, job[3].clone(), job[4].clone())
-        PU.resample_tabled([alone[cap, cap][0][:4] + (None,)])                          # used may be NULL
+        PU.resample_drawn([alone[cap, cap][0][:4] + (None,)])                          # used may be NULL
     # both jobs in one launch, each on its own table: every count of one against a count of the other, in both orders
     (ca, sa), (cb, sb) = TABLES
     for na, nb in zip(counts_of(ca, sa), reversed(counts_of(cb, sb))):
@@ -109,7 +109,7 @@ def test_resample_tabled_equals_resample_on_the_reference_indices(dev):
             for j in (ja, jb):
                 j[3].fill_(SENT)
                 j[4].fill_(ISENT)
-            PU.resample_tabled([ja, jb])
+            PU.resample_drawn([ja, jb])
             for j, key in ((ja, first), (jb, second)):
                 assert torch.equal(tbits(j[3]), tbits(alone[key][1])) and torch.equal(j[4], alone[key][2]), (first, second)
 
@@ -122,11 +122,31 @@ def test_a_table_entry_outside_the_cloud_leaves_its_row_zero(dev):
     table[n] = torch.tensor([0, 9, 10, -1, 40, 3, -5, 1 << 30], dtype=torch.int32, device=dev)
     src = up(np.random.default_rng(0).normal(size=(cap, 3)).astype(np.float32), dev)
     job, dguard, uguard = tabled_alone(src, n, table, S, dev)
-    PU.resample_tabled([job])
+    PU.resample_drawn([job])
     inside = [0, 1, 5]
     assert torch.equal(job[4], table[n]) and untouched(dguard) and untouched(uguard, ISENT)
     assert torch.equal(tbits(job[3][inside]), tbits(src[table[n][inside].long()]))
     assert not bool(job[3][[2, 3, 4, 6, 7]].any())
+
+
+def test_a_launch_with_a_key_and_a_table_is_refused_before_anything_is_launched(dev):
+    """key and table are two entry points of the C ABI: one launch takes one kind.  Both orders, single form and L = 2 lanes"""
+    from open3dsot_amd import points_utils as PU, tracking
+    cap, S, n, L = 8, 4, 5, 2
+    table = tracking.draw_table(cap, S, dev)
+    src = up(np.random.default_rng(3).normal(size=(L, cap, 3)).astype(np.float32), dev)
+    for sources in ((1234, table), (table, 1234)):
+        jobs = [tabled_alone(src[0], n, source, S, dev)[0] for source in sources]
+        with pytest.raises(ValueError):
+            PU.resample_drawn(jobs)
+        dst = [torch.full((L, S, 3), SENT, device=dev) for _ in sources]
+        used = [torch.full((L, S), ISENT, dtype=torch.int32, device=dev) for _ in sources]
+        counts = up(np.full((L,), n, np.int32), dev)
+        with pytest.raises(ValueError):
+            PU.resample_drawn_lanes([(src, counts, 1, source, d, u) for source, d, u in zip(sources, dst, used)])
+        torch.cuda.synchronize()
+        for d, u in [(j[3], j[4]) for j in jobs] + list(zip(dst, used)):
+            assert untouched(d) and untouched(u, ISENT)
 
 
 @pytest.mark.parametrize("N", [1, 128, 129])
@@ -150,7 +170,7 @@ def test_motion_input_tabled_equals_motion_input_on_the_reference_indices(dev, N
             pts, pguard = guarded((2 * N, 5), dev)
             bc, bguard = guarded((2 * N, 9), dev)
             used, uguard = guarded((2 * N,), dev, ISENT, torch.int32)
-            PU.motion_input_tabled(tp, tc, up(np.array(counts, np.int32), dev), table, tw, first, pts, bc if with_bc else False, used)
+            PU.motion_input_drawn(tp, tc, up(np.array(counts, np.int32), dev), table, tw, first, pts, bc if with_bc else False, used)
             want_pts, want_bc = PU.motion_input(None if zero[0] else tp[:ns[0]], None if zero[1] else tc[:ns[1]], idx, tw, first, zero=zero,
                                                 out_points=torch.full((2 * N, 5), SENT, device=dev), out_bc=None if with_bc else False)
             assert torch.equal(tbits(pts), tbits(want_pts)), (N, counts, first)
@@ -160,7 +180,7 @@ def test_motion_input_tabled_equals_motion_input_on_the_reference_indices(dev, N
                 assert torch.equal(tbits(bc), tbits(want_bc)), (N, counts, first)
             else:
                 assert untouched(bc)                                                   # NULL: nothing written
-    PU.motion_input_tabled(tp, tc, up(np.array([5, 7], np.int32), dev), table, tw, True, pts)      # used may be NULL
+    PU.motion_input_drawn(tp, tc, up(np.array([5, 7], np.int32), dev), table, tw, True, pts)      # used may be NULL
 
 
 @pytest.mark.parametrize("L", [1, 3])
@@ -182,15 +202,15 @@ def test_resample_tabled_lanes_equals_the_single_entry_lane_by_lane(dev, L):
                 d, g = guarded((L, S, 3), dev)
                 u, ug = guarded((L, S), dev, ISENT, torch.int32)
                 dst.append(d), dguard.append(g), used.append(u), uguard.append(ug)
-            PU.resample_tabled_lanes([(srcs[0], n0.view(-1)[1:], 2, tables[0], dst[0], used[0] if with_used else None),
-                                      (srcs[1], n1, 2, tables[1], dst[1], used[1] if with_used else None)])
+            PU.resample_drawn_lanes([(srcs[0], n0.view(-1)[1:], 2, tables[0], dst[0], used[0] if with_used else None),
+                                     (srcs[1], n1, 2, tables[1], dst[1], used[1] if with_used else None)])
             for c, (cap, S) in enumerate(TABLES):
                 assert untouched(dguard[c]) and untouched(uguard[c], ISENT)
                 if not with_used:
                     assert untouched(used[c], ISENT)                                   # NULL: nothing written
                 for l in range(L):
                     job, _, _ = tabled_alone(srcs[c][l], int(counts[c][l]), tables[c], S, dev)
-                    PU.resample_tabled([job])
+                    PU.resample_drawn([job])
                     assert torch.equal(tbits(dst[c][l]), tbits(job[3])), (L, launch, c, l)
                     assert not with_used or torch.equal(used[c][l], job[4]), (L, launch, c, l)
 
@@ -216,17 +236,17 @@ def test_motion_input_tabled_lanes_equals_the_single_entry_lane_by_lane(dev, L, 
         pts, pguard = guarded((L, 2 * N, 5), dev)
         bc, bguard = guarded((L, 2 * N, 9), dev)
         used, uguard = guarded((L, 2 * N), dev, ISENT, torch.int32)
-        PU.motion_input_tabled_lanes(tp, tc, tn, table, tw, tl, pts, bc if with_bc else False, used)
+        PU.motion_input_drawn_lanes(tp, tc, tn, table, tw, tl, pts, bc if with_bc else False, used)
         assert untouched(pguard) and untouched(bguard) and untouched(uguard, ISENT)
         if not with_bc:
             assert untouched(bc)
         for l in range(L):
             p1, b1 = torch.full((2 * N, 5), SENT, device=dev), torch.full((2 * N, 9), SENT, device=dev)
             u1 = torch.full((2 * N,), ISENT, dtype=torch.int32, device=dev)
-            PU.motion_input_tabled(tp[l], tc[l], tn[l], table, tw[l], bool(first[l]), p1, b1 if with_bc else False, u1)
+            PU.motion_input_drawn(tp[l], tc[l], tn[l], table, tw[l], bool(first[l]), p1, b1 if with_bc else False, u1)
             assert torch.equal(tbits(pts[l]), tbits(p1)) and torch.equal(used[l], u1), (L, N, l)
             assert not with_bc or torch.equal(tbits(bc[l]), tbits(b1)), (L, N, l)
-    PU.motion_input_tabled_lanes(tp, tc, tn, table, tw, tl, pts)                        # used may be NULL
+    PU.motion_input_drawn_lanes(tp, tc, tn, table, tw, tl, pts)                        # used may be NULL
 
 
 # ---- the single loops against sampling="reference" -------------------------------------------------------------------------------
