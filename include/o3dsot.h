@@ -1065,10 +1065,24 @@ int o3d_track_score(const float* a, const float* b, const int32_t* valid, int n,
  * the float32 input and rounded once.  row_floats = 3 | 4: raw row r is floats [r*row_floats, r*row_floats + 3) of raw, which
  * is 4-byte aligned, 16-byte when row_floats is 4.  Tables, planning (o3d_preload_scratch), compares, counting and limits are
  * the pair's above.  O3D_EINVAL, before any HIP call: everything that pair refuses, row_floats outside {3,4}, poses NULL with
- * F > 0, poses not 8-byte aligned.  F = 0 and B = 0 succeed without a launch. */
+ * F > 0, poses not 8-byte aligned.  F = 0 and B = 0 succeed without a launch.
+ *
+ * o3d_preload_steps_count / o3d_preload_steps_scatter: the same launches with a CHAIN OF ROUNDED RIGID STEPS per frame record
+ * -- what NuScenesDataset._get_frame_from_anno_data does, whose sweeps go sensor -> ego -> global by rotate / translate pairs on
+ * a float32 array.  steps (F,n_steps,12) float64 on the DEVICE, 8-byte aligned: step s of record f is a row-major 3x4 [R | t];
+ * n_steps in 1..O3D_PRELOAD_MAX_STEPS; two records over the same raw rows carry the same steps twice.  A step, on the float32
+ * input (x, y, z): r_i = float((M_i0*x + M_i1*y) + M_i2*z), fp64 in this order, rounded; then translate32 = 0: p_i =
+ * float(double(r_i) + M_i3) (numpy >= 2 adds an np.float64 scalar to a float32 array in fp64 and rounds on assignment), or
+ * translate32 = 1: p_i = r_i + float(M_i3), an fp32 add (numpy < 2 demotes the scalar).  p is the next step's input; the last p
+ * is tested and written: two steps round a point four times.  row_floats = 3 | 4 | 5: raw row r is floats [r*row_floats,
+ * r*row_floats + 3) of raw -- the .pcd.bin rows x y z intensity ring of 20 bytes are uploaded as they lie -- which is 4-byte
+ * aligned, 16-byte when row_floats is 4.  Tables, planning, compares, counting and limits are the first pair's.  O3D_EINVAL,
+ * before any HIP call: everything that pair refuses, row_floats outside 3..5, n_steps outside 1..O3D_PRELOAD_MAX_STEPS,
+ * translate32 outside {0,1}, steps NULL with F > 0, steps not 8-byte aligned.  F = 0 and B = 0 succeed without a launch. */
 #define O3D_PRELOAD_MAX_FRAMES 4096
 #define O3D_PRELOAD_MAX_BOXES 1024
 #define O3D_PRELOAD_MAX_ROWS 536870911
+#define O3D_PRELOAD_MAX_STEPS 4
 long o3d_preload_scratch(int32_t* frames, int F, long raw_rows, int* grid);
 int o3d_preload_count(const float* raw, long raw_rows, const int32_t* frames, const int32_t* frames_dev, int F,
                       const float* bounds, int B, const double* transform, int32_t* scratch, long scratch_len, int32_t* counts,
@@ -1082,6 +1096,13 @@ int o3d_preload_posed_count(const float* raw, long raw_rows, int row_floats, con
 int o3d_preload_posed_scatter(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
                               int F, const float* bounds, int B, const double* poses, int32_t* scratch, long scratch_len,
                               const long* out_row, float* pool, long pool_rows, void* stream);
+int o3d_preload_steps_count(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
+                            int F, const float* bounds, int B, const double* steps, int n_steps, int translate32,
+                            int32_t* scratch, long scratch_len, int32_t* counts, void* stream);
+int o3d_preload_steps_scatter(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
+                              int F, const float* bounds, int B, const double* steps, int n_steps, int translate32,
+                              int32_t* scratch, long scratch_len, const long* out_row, float* pool, long pool_rows,
+                              void* stream);
 
 #ifdef __cplusplus
 }

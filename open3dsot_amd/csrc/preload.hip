@@ -9,6 +9,9 @@
 //   o3d_preload_posed_count / o3d_preload_posed_scatter   the same launches with ONE TRANSFORM PER FRAME RECORD, read from the
 //                         device, over raw rows of 3 or 4 floats: the reference's WaymoDataset (datasets/waymo_data.py:118-167
 //                         _get_frame_from_anno), whose frames carry a vehicle-to-global pose each
+//   o3d_preload_steps_count / o3d_preload_steps_scatter   the same launches with A CHAIN OF ROUNDED RIGID STEPS per frame record
+//                         over raw rows of 3, 4 or 5 floats: the reference's NuScenesDataset (datasets/nuscenes_data.py:154-173
+//                         _get_frame_from_anno_data), whose sweeps go sensor -> ego -> global by rotate / translate pairs
 // The host reads `counts` between the two calls (the only synchronisation of a chunk), sizes the pool and uploads the first
 // pool row of every box.
 //
@@ -43,6 +46,18 @@
 // (n,3) rows, which are three 4-byte loads; rows of four floats stay one aligned 16-byte load.  The record, and with it the
 // pose, is uniform over a workgroup: the twelve doubles are scalar loads.
 //
+// ---- a chain of steps per record --------------------------------------------------------------------------------------------------------
+// steps (F,n_steps,12) fp64 on the device: step s of record f is a row-major 3x4 [R | t], n_steps in 1..O3D_PRELOAD_MAX_STEPS.
+// NuScenesDataset does pc.rotate(R); pc.translate(t) twice on a float32 array (datasets/data_classes.py:79-94): every rotate and
+// every translate stores back into float32, so a point is rounded FOUR times, and with ego translations of hundreds of metres
+// every rounding decides bits.  preload_step is the one statement of a step, on the float32 input (x, y, z):
+//   r_i = float((M_i0*x + M_i1*y) + M_i2*z)                 fp64, this order, rounded to float32 (np.dot(R, points[:3]) stored back)
+//   translate32 == 0:  p_i = float(double(r_i) + M_i3)      points[i] + np.float64 under numpy >= 2: an fp64 sum, rounded on assignment
+//   translate32 == 1:  p_i = r_i + float(M_i3)              the same line under numpy < 2: the scalar is demoted, an fp32 add
+// p is the next step's input; the last p is tested and written.  Raw row r is floats [r*row_floats, r*row_floats + 3): the
+// .pcd.bin rows of NuScenes are x y z intensity ring, 20 bytes, uploaded as they lie; the device reads 12 of every 20 bytes.
+// The record, and with it the chain, is uniform over a workgroup.
+//
 // ---- three launches, no workgroup ever waits for another ----------------------------------------------------------------------------------
 // The host knows every n and plans the table, as o3d_track_crop_groups_scratch does: record f owns workgroups [wg_start, wg_start
 // + W) of the count and scatter launches (W = ceil(n / 256), 1 for an empty frame, 0 for a record without boxes) and its boxes'
@@ -69,6 +84,11 @@ struct preload_xf {                                          // one transform fo
 struct preload_poses {                                       // one transform per frame record, on the device
     const double* poses;
     int row_floats;
+};
+
+struct preload_steps {                                       // a chain of rounded rigid steps per frame record, on the device
+    const double* steps;
+    int row_floats, n_steps, translate32;
 };
 
 // the record of workgroup (COL 4) or box (COL 2) `x`: the last f with frames[f][COL] <= x.  Records that own nothing share
@@ -115,6 +135,34 @@ __device__ __forceinline__ void preload_point(const float* __restrict__ raw, con
         x = r[0]; y = r[1]; z = r[2];
     }
     preload_apply(P.poses + 12 * (long)f, x, y, z, px, py, pz);
+}
+
+// the one statement of a rounded rigid step: rotate in fp64 in this order and round, then translate in fp64 and round
+// (translate32 == 0) or in fp32 (translate32 == 1).  In place: p is the next step's input
+__device__ __forceinline__ void preload_step(const double* __restrict__ m, int translate32, float& px, float& py, float& pz) {
+    const double x = px, y = py, z = pz;
+    const float rx = (float)((m[0] * x + m[1] * y) + m[2] * z);
+    const float ry = (float)((m[4] * x + m[5] * y) + m[6] * z);
+    const float rz = (float)((m[8] * x + m[9] * y) + m[10] * z);
+    if (translate32) {
+        px = rx + (float)m[3]; py = ry + (float)m[7]; pz = rz + (float)m[11];
+    } else {
+        px = (float)((double)rx + m[3]); py = (float)((double)ry + m[7]); pz = (float)((double)rz + m[11]);
+    }
+}
+
+// preload_steps: the chain of record f from the device table, rows of 3, 4 or 5 floats
+__device__ __forceinline__ void preload_point(const float* __restrict__ raw, const preload_steps C, int f, long row, float& px,
+                                              float& py, float& pz) {
+    if (C.row_floats == 4) {
+        const float4 v = reinterpret_cast<const float4*>(raw)[row];
+        px = v.x; py = v.y; pz = v.z;
+    } else {
+        const float* r = raw + C.row_floats * row;
+        px = r[0]; py = r[1]; pz = r[2];
+    }
+    const double* m = C.steps + 12 * ((long)C.n_steps * f);
+    for (int s = 0; s < C.n_steps; ++s) preload_step(m + 12 * s, C.translate32, px, py, pz);
 }
 
 template <bool SCATTER, class XF>
@@ -227,6 +275,13 @@ static bool preload_posed_ok(int row_floats, int F, const double* poses) {
     return F <= 0 || (poses && !(reinterpret_cast<uintptr_t>(poses) & 7u));
 }
 
+// what the steps pair refuses beyond preload_args_ok
+static bool preload_steps_ok(int row_floats, int F, const double* steps, int n_steps, int translate32) {
+    if (row_floats < 3 || row_floats > 5 || n_steps < 1 || n_steps > O3D_PRELOAD_MAX_STEPS || (translate32 != 0 && translate32 != 1))
+        return false;
+    return F <= 0 || (steps && !(reinterpret_cast<uintptr_t>(steps) & 7u));
+}
+
 }  // namespace
 
 // Host only (no HIP call).  frames (F,6): the caller sets columns 0 (first raw row), 1 (n) and 3 (number of boxes); this fills
@@ -294,5 +349,37 @@ extern "C" int o3d_preload_posed_scatter(const float* raw, long raw_rows, int ro
     if (B == 0 || pool_rows == 0) return O3D_OK;
     hipLaunchKernelGGL((preload_kernel<true, preload_poses>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F,
                        bounds, preload_poses{poses, row_floats}, scratch, out_row, pool, pool_rows);
+    return o3d_launch_status();
+}
+
+// The same launches with a chain of n_steps rounded rigid steps per frame record (steps (F,n_steps,12) fp64 on the device) over
+// raw rows of row_floats = 3 | 4 | 5 floats
+extern "C" int o3d_preload_steps_count(const float* raw, long raw_rows, int row_floats, const int32_t* frames, const int32_t* frames_dev,
+                                       int F, const float* bounds, int B, const double* steps, int n_steps, int translate32,
+                                       int32_t* scratch, long scratch_len, int32_t* counts, void* stream) {
+    long wgs;
+    if (!preload_steps_ok(row_floats, F, steps, n_steps, translate32) ||
+        !preload_args_ok(raw, raw_rows, frames, frames_dev, F, bounds, B, scratch, scratch_len, wgs, row_floats == 4 ? 16u : 4u) ||
+        (B > 0 && !counts))
+        return O3D_EINVAL;
+    if (B == 0) return O3D_OK;
+    hipLaunchKernelGGL((preload_kernel<false, preload_steps>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F,
+                       bounds, preload_steps{steps, row_floats, n_steps, translate32}, scratch, (const long*)nullptr, (float*)nullptr, 0L);
+    hipLaunchKernelGGL(preload_scan_kernel, dim3(B), dim3(CROP_WG), 0, o3d_stream(stream), frames_dev, F, scratch, counts);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_preload_steps_scatter(const float* raw, long raw_rows, int row_floats, const int32_t* frames,
+                                         const int32_t* frames_dev, int F, const float* bounds, int B, const double* steps, int n_steps,
+                                         int translate32, int32_t* scratch, long scratch_len, const long* out_row, float* pool,
+                                         long pool_rows, void* stream) {
+    long wgs;
+    if (!preload_steps_ok(row_floats, F, steps, n_steps, translate32) ||
+        !preload_args_ok(raw, raw_rows, frames, frames_dev, F, bounds, B, scratch, scratch_len, wgs, row_floats == 4 ? 16u : 4u) ||
+        pool_rows < 0 || (B > 0 && !out_row) || (pool_rows > 0 && !pool))
+        return O3D_EINVAL;
+    if (B == 0 || pool_rows == 0) return O3D_OK;
+    hipLaunchKernelGGL((preload_kernel<true, preload_steps>), dim3((int)wgs), dim3(CROP_WG), 0, o3d_stream(stream), raw, frames_dev, F,
+                       bounds, preload_steps{steps, row_floats, n_steps, translate32}, scratch, out_row, pool, pool_rows);
     return o3d_launch_status();
 }

@@ -1,4 +1,5 @@
-"""Dataset readers that leave the frames in HBM: the KITTI tracking set and the Waymo SOT set as sampler.DeviceTracklets.
+"""Dataset readers that leave the frames in HBM: the KITTI tracking set, the Waymo SOT set and nuScenes as
+sampler.DeviceTracklets.
 
 KittiTracklets mirrors the reference's kittiDataset (datasets/kitti.py) with coordinate_mode `velodyne` / `camera` and
 preload_offset: the same scene list per split string, the same tracklet list (order of first appearance of track_id in the
@@ -32,8 +33,25 @@ through a quaternion and back; length and width of the box are swapped; with pre
 points are still transformed.  Two stated deviations: points_xyz must be float32 (ValueError otherwise; the reference would
 keep a float64 array unrounded); and with preload_offset <= 0 the bounds are -inf / +inf under the same strict compares, so a
 point whose transformed coordinate is NaN or infinite is dropped where the reference, which does not compare at all, keeps it.  Non-preloading access (which swaps length and width back on a second read) is not restated.
+
+NuScenesTracklets mirrors the reference's NuScenesDataset with preloading (datasets/nuscenes_data.py) without the devkit:
+nuscenes_annotations reads the nine JSON tables the reference touches, restates the one piece of the devkit's reverse indexing
+it relies on (sample['data']['LIDAR_TOP']: the sample's key-frame sample_data record on that channel, the last in table order),
+filters the instances (scene of the first annotation in the split, its num_lidar_pts >= min_points, category among the general
+classes of the tracking class) and follows `next`; boxes are centre = translation, wlh = size, rotation = the matrix of the
+normalised quaternion, in fp64.  The .pcd.bin sweeps (x y z intensity ring, 20 bytes a row) go into the pinned buffer as they
+lie; the device takes every point sensor -> ego -> global by two rounded rigid steps (o3d_preload_steps_count /
+o3d_preload_steps_scatter): the reference's rotate / translate pairs store into a float32 array, four roundings a point.
+translate="float64" is the rule of numpy >= 2 (an np.float64 scalar added to a float32 array: an fp64 sum rounded on
+assignment), translate="float32" the rule of numpy < 2 (the scalar demoted: an fp32 add).  The split lists live in the devkit:
+pass scenes= where it is absent.  Quirks kept: a sweep whose length is no multiple of 20 bytes raises ValueError, a missing
+one FileNotFoundError, an empty one gives a (0,3) frame; key_frame_only cannot drop a frame of a well-formed set (the index
+above only holds key frames) but the flag and the reference's `continue` are kept; the same -inf / +inf bounds and the same NaN
+deviation as the Waymo reader with preload_offset <= 0.  Not restated: non-preloading access, and the devkit's loading and
+checking of the tables the reference never reads (attribute, visibility, log, map).
 """
 import ast
+import json
 import os
 import pickle
 
@@ -231,10 +249,11 @@ def copy_rows(host, rows, n):
 
 
 def _read_rows(host, path, n):
-    """the default row loader: a velodyne .bin, n rows of four floats, straight into the pinned buffer"""
+    """the default row loader: a velodyne .bin (n rows of four floats) or a NuScenes .pcd.bin (n rows of five), straight into
+    the pinned buffer"""
     with open(path, "rb") as f:
         got = f.readinto(host)
-    if got != 16 * n:
+    if got != host.nbytes:
         raise OSError("%s changed while it was read" % path)
 
 
@@ -243,12 +262,17 @@ class PreloadChunk:
     boxes_per_file: for each file a (k,6) float32 array of bounds (k >= 0).  A raw row is row_floats = 3 | 4 floats;
     loader(host rows (n,row_floats), source, n) fills the pinned buffer's rows of one file (default: source is the path of a
     velodyne .bin; with poses, source is the (n,row_floats) float32 array itself: copy_rows).  transform: one (3,4) fp64 for the chunk | None; poses: one (3,4) fp64 PER FILE instead (then transform is
-    None and the launches are o3d_preload_posed_*).  The steps are separate methods so that tools/preload_bench.py can time
+    None and the launches are o3d_preload_posed_*); steps: one (n_steps,12) fp64 block PER FILE instead, a chain of rounded
+    rigid steps with translate32 = 0 | 1 (then transform and poses are None, a raw row is 3 | 4 | 5 floats and the launches are
+    o3d_preload_steps_*).  The stages are separate methods so that tools/preload_bench.py can time
     them; run() is the sequence the readers use."""
 
-    def __init__(self, files, bounds_per_file, transform, device, pinned=None, row_floats=4, loader=None, poses=None):
+    def __init__(self, files, bounds_per_file, transform, device, pinned=None, row_floats=4, loader=None, poses=None, steps=None,
+                 translate32=0):
         assert poses is None or (transform is None and len(poses) == len(files))
-        assert row_floats == 4 or poses is not None
+        assert steps is None or (transform is None and poses is None and len(steps) == len(files))
+        assert row_floats == 4 or poses is not None or steps is not None
+        self.translate32 = int(translate32)
         self.device, self.transform = device, transform
         self.loader = loader if loader is not None else copy_rows if poses is not None else _read_rows
         recs, rec_pose, row = [], [], 0
@@ -264,6 +288,10 @@ class PreloadChunk:
         assert self.bounds.shape[0] == self.B
         self.poses = None if poses is None else \
             np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12)[np.array(rec_pose, np.int64)])
+        self.steps = None
+        if steps is not None:                                       # (files, n_steps, 12) -> (records, n_steps, 12)
+            steps = np.asarray(steps, np.float64).reshape(len(files), -1, 12) if len(files) else np.zeros((0, 1, 12))
+            self.steps = np.ascontiguousarray(steps[np.array(rec_pose, np.int64)])
         if pinned is None or pinned.shape[0] < row or pinned.shape[1] != row_floats:
             pinned = torch.empty((max(row, 1), row_floats), dtype=torch.float32).pin_memory()
         self.pinned = pinned
@@ -281,15 +309,21 @@ class PreloadChunk:
         tables = [self.frames.reshape(-1).view(np.uint8), self.bounds.reshape(-1).view(np.uint8)]
         if self.poses is not None:                # frames and bounds are 24 bytes a row: the doubles behind them are aligned
             tables.append(self.poses.reshape(-1).view(np.uint8))
+        if self.steps is not None:
+            tables.append(self.steps.reshape(-1).view(np.uint8))
         t = torch.from_numpy(np.concatenate(tables)).to(dev)
         nf, nb = self.frames.size * 4, self.bounds.size * 4
         self.dev_frames, self.dev_bounds = t[:nf].view(torch.int32), t[nf:nf + nb].view(torch.float32)
         self.dev_poses = None if self.poses is None else t[nf + nb:].view(torch.float64)
+        self.dev_steps = None if self.steps is None else t[nf + nb:].view(torch.float64).view(self.steps.shape)
         self.scratch = torch.empty((self.need,), dtype=torch.int32, device=dev)
         self.counts = torch.empty((self.B,), dtype=torch.int32, device=dev)
 
     def count(self):
-        if self.dev_poses is None:
+        if self.dev_steps is not None:
+            PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.counts,
+                             steps=self.dev_steps, translate32=self.translate32)
+        elif self.dev_poses is None:
             PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.counts)
         else:
             PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.counts,
@@ -304,7 +338,10 @@ class PreloadChunk:
         return counts
 
     def scatter(self):
-        if self.dev_poses is None:
+        if self.dev_steps is not None:
+            PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.out_row, self.pool,
+                               steps=self.dev_steps, translate32=self.translate32)
+        elif self.dev_poses is None:
             PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.out_row,
                                self.pool)
         else:
@@ -626,6 +663,209 @@ class WaymoTracklets(_PoolTracklets):
             cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
             self.split, self.category_name = (str(s) for s in z["info"][:2])
             self.preload_offset, self.tiny, self.path = ast.literal_eval(str(z["info"][2])), str(z["info"][3]) == "True", None
+            meta = [(str(k), [str(f) for f in fs]) for k, fs in zip(z["keys"], cut(z["files"]))]
+            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
+        return self
+
+
+# ---- NuScenes -----------------------------------------------------------------------------------------------------------------
+_NUSC_TABLES = ("category", "instance", "sample_annotation", "sample", "sample_data", "scene", "sensor", "calibrated_sensor", "ego_pose")
+_NUSC_LIDAR = "LIDAR_TOP"
+_NUSC_ROW_BYTES = 20                              # a .pcd.bin row: x y z intensity ring, float32 each
+
+
+def _general(prefix, *leaves):
+    return tuple(prefix + "." + leaf for leaf in leaves) if leaves else (prefix,)
+
+
+# the nuScenes tracking class -> the general (annotation) classes it covers, from the taxonomy of the tracking task
+NUSCENES_TRACKING_CLASSES = {
+    "void / ignore": _general("animal") + _general("human.pedestrian", "personal_mobility", "stroller", "wheelchair") +
+    _general("movable_object", "barrier", "debris", "pushable_pullable", "trafficcone") + _general("static_object.bicycle_rack") +
+    _general("vehicle.emergency", "ambulance", "police") + _general("vehicle.construction"),
+    "bicycle": _general("vehicle.bicycle"),
+    "bus": _general("vehicle.bus", "bendy", "rigid"),
+    "car": _general("vehicle.car"),
+    "motorcycle": _general("vehicle.motorcycle"),
+    "pedestrian": _general("human.pedestrian", "adult", "child", "construction_worker", "police_officer"),
+    "trailer": _general("vehicle.trailer"),
+    "truck": _general("vehicle.truck"),
+}
+
+
+def _read_json(file):
+    with open(file) as f:
+        return json.load(f)
+
+
+def nuscenes_split_scenes(scenes, split):
+    """the scene names of `split`.  scenes: a dict split -> names | the path of a JSON file holding such a dict | an iterable of
+    names (taken as the split's) | None: the devkit's create_splits_scenes(), imported here"""
+    if scenes is None:
+        try:
+            from nuscenes.utils.splits import create_splits_scenes
+        except ImportError:
+            raise ValueError("the nuScenes devkit (nuscenes.utils.splits) is not installed: pass scenes=, a dict split -> scene "
+                             "names, the path of a JSON file holding one, or the scene names of the split") from None
+        scenes = create_splits_scenes()
+    if isinstance(scenes, (str, os.PathLike)):
+        scenes = _read_json(scenes)
+    if isinstance(scenes, dict):
+        if split not in scenes:
+            raise ValueError("split %r is not among %s" % (split, sorted(scenes)))
+        scenes = scenes[split]
+    return set(scenes)
+
+
+def nuscenes_annotations(path, split, category_name="Car", version="v1.0-trainval", key_frame_only=False, min_points=False, scenes=None):
+    """The host half of the NuScenes reader (no device, no devkit): -> (tracklets, files, steps).  tracklets: a list of dicts
+    with key (the instance token), files (the sweep's `filename` of every frame, relative to path), frames (T,) int64 (indices
+    into `files`) and boxes (T,15) float64, instances in table order; files: the distinct sweeps in order of first use; steps
+    (len(files),2,12) float64: per sweep [R | t] of its calibrated sensor, then of its ego pose.  What
+    NuScenesDataset.filter_instance and _build_tracklet_anno do over the devkit's tables; every JSON table is read once."""
+    general = NUSCENES_TRACKING_CLASSES.get(category_name.lower())
+    if general is None:
+        raise ValueError("category_name %r is no nuScenes tracking class: %s" % (category_name, ", ".join(sorted(NUSCENES_TRACKING_CLASSES))))
+    in_split = nuscenes_split_scenes(scenes, split)
+    tables = {name: _read_json(os.path.join(path, version, name + ".json")) for name in _NUSC_TABLES}
+    by_token = {name: {r["token"]: r for r in rows} for name, rows in tables.items()}
+    # the devkit's reverse index, as far as the reference relies on it: sample['data'][channel] is the key-frame sample_data
+    # record of the sample on that channel, the last one in table order
+    lidar_of = {}
+    for sd in tables["sample_data"]:
+        if sd["is_key_frame"]:
+            sensor = by_token["sensor"][by_token["calibrated_sensor"][sd["calibrated_sensor_token"]]["sensor_token"]]
+            if sensor["channel"] == _NUSC_LIDAR:
+                lidar_of[sd["sample_token"]] = sd
+    index, files, steps, tracklets = {}, [], [], []
+    for instance in tables["instance"]:
+        first = by_token["sample_annotation"][instance["first_annotation_token"]]
+        scene = by_token["scene"][by_token["sample"][first["sample_token"]]["scene_token"]]
+        if not (scene["name"] in in_split and first["num_lidar_pts"] >= min_points and
+                by_token["category"][instance["category_token"]]["name"] in general):
+            continue
+        names, frames, boxes, token = [], [], [], instance["first_annotation_token"]
+        while token != "":
+            anno = by_token["sample_annotation"][token]
+            token = anno["next"]
+            if anno["sample_token"] not in lidar_of:
+                raise ValueError("sample %s has no key-frame %s record" % (anno["sample_token"], _NUSC_LIDAR))
+            sd = lidar_of[anno["sample_token"]]
+            if key_frame_only and not sd["is_key_frame"]:
+                continue
+            file = sd["filename"]
+            if file not in index:
+                index[file] = len(files)
+                files.append(file)
+                cs, ego = by_token["calibrated_sensor"][sd["calibrated_sensor_token"]], by_token["ego_pose"][sd["ego_pose_token"]]
+                steps.append([np.hstack([_quat_matrix(np.array(r["rotation"], np.float64)),
+                                         np.array(r["translation"], np.float64).reshape(3, 1)]).reshape(12) for r in (cs, ego)])
+            names.append(file)
+            frames.append(index[file])
+            boxes.append(np.concatenate([np.array(anno["translation"], np.float64), np.array(anno["size"], np.float64),
+                                         _quat_matrix(np.array(anno["rotation"], np.float64)).reshape(-1)]))
+        tracklets.append({"key": instance["token"], "files": names, "frames": np.array(frames, np.int64),
+                          "boxes": np.array(boxes, np.float64).reshape(-1, 15)})
+    return tracklets, files, np.array(steps, np.float64).reshape(-1, 2, 12)
+
+
+def nuscenes_rows(file):
+    """the rows of a .pcd.bin sweep as the reference reads it (np.fromfile(float32).reshape(-1, 5)): a missing file raises
+    FileNotFoundError, a length that is no multiple of 20 bytes ValueError"""
+    size = os.path.getsize(file)
+    if size % _NUSC_ROW_BYTES:
+        raise ValueError("%s: %d bytes are no rows of five float32 (x y z intensity ring)" % (file, size))
+    return size // _NUSC_ROW_BYTES
+
+
+class NuScenesTracklets(_PoolTracklets):
+    """NuScenesTracklets(path, split, ...): the tracklets of the nuScenes set under `path` (<version>/*.json, the sweeps where
+    sample_data names them), taken sensor -> ego -> global and cropped as the reference's NuScenesDataset preloads them,
+    resident in HBM.  A sampler.DeviceTracklets.  meta[k] = (instance token, the sweep files of its frames); pool / rows as in
+    KittiTracklets.  With preload_offset <= 0 nothing is cropped: the transformed sweep is written once and its tracklets
+    share the slice.  translate = "float64" (numpy >= 2: the translation is added in fp64 and rounded) | "float32" (numpy < 2:
+    an fp32 add).  scenes: see nuscenes_split_scenes."""
+
+    def __init__(self, path, split, category_name="Car", version="v1.0-trainval", key_frame_only=False, min_points=False,
+                 preload_offset=-1, scenes=None, translate="float64", device=None, chunk_frames=64):
+        super().__init__()
+        dev = _device(device, "NuScenesTracklets")
+        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
+            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        if translate not in ("float64", "float32"):
+            raise ValueError("translate must be 'float64' or 'float32'")
+        self.path, self.split, self.category_name, self.version = path, split, category_name, version
+        self.key_frame_only, self.min_points, self.preload_offset, self.translate = key_frame_only, min_points, preload_offset, translate
+        annos, files, steps = nuscenes_annotations(path, split, category_name, version, key_frame_only, min_points, scenes)
+        users = [[] for _ in files]               # per distinct sweep the tracklet frames that crop it
+        for k, a in enumerate(annos):
+            for t, f in enumerate(a["frames"]):
+                users[f].append((k, t))
+        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
+        shared = preload_offset <= 0
+        todo = []                                 # (path, n, bounds (k,6), [[(tracklet, frame index)] per box])
+        for file, who in zip(files, users):
+            full = os.path.join(path, file)
+            if shared:
+                todo.append((full, nuscenes_rows(full), preload_bounds(np.zeros((1, 15)), preload_offset), [who]))
+            else:
+                todo.append((full, nuscenes_rows(full), preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in who]), preload_offset),
+                             [[u] for u in who]))
+        segments, base, pinned, i = [], 0, None, 0
+        with torch.cuda.device(dev):
+            while i < len(todo):
+                # a chunk: at most chunk_frames sweeps, PRELOAD_MAX_FRAMES records and PRELOAD_MAX_ROWS raw rows
+                j, nrows, nrec = i, 0, 0
+                while j < len(todo) and j - i < chunk_frames:
+                    rec = max(1, -(-len(todo[j][2]) // PU.PRELOAD_MAX_BOXES))
+                    if j > i and (nrows + todo[j][1] > PU.PRELOAD_MAX_ROWS or nrec + rec > PU.PRELOAD_MAX_FRAMES):
+                        break
+                    nrows, nrec, j = nrows + todo[j][1], nrec + rec, j + 1
+                chunk = PreloadChunk([(t[0], t[1]) for t in todo[i:j]], [t[2] for t in todo[i:j]], None, dev, pinned, row_floats=5,
+                                     steps=steps[i:j], translate32=int(translate == "float32"))
+                counts = chunk.run()
+                pinned, b = chunk.pinned, 0
+                for t in todo[i:j]:
+                    for who in t[3]:
+                        for k, f in who:
+                            rows[k][f] = (base + chunk.first[b], counts[b])
+                        b += 1
+                segments.append(chunk.pool)
+                base += int(chunk.first[-1])
+                i = j
+            segments.append(torch.zeros((0, 3), dtype=torch.float32, device=dev))
+            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
+        self._assemble(pool, rows, [a["boxes"] for a in annos], [(a["key"], a["files"]) for a in annos])
+
+    def get_frames(self, seq_id, frame_ids):
+        t, (key, files) = self[seq_id], self.meta[seq_id]
+        return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (key, files[f])} for f in frame_ids]
+
+    # ---- the cache ----------------------------------------------------------------------------------------------------------
+    def save(self, file):
+        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
+        lengths = np.array([len(t) for t in self], np.int64)
+        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
+        arrays = dict(pool=self.pool.cpu().numpy(), lengths=lengths, rows=cat(self.rows, (0, 2), np.int64),
+                      boxes=cat(self.boxes64, (0, 15), np.float64), keys=np.array([m[0] for m in self.meta], dtype=np.str_),
+                      files=np.array([f for m in self.meta for f in m[1]], dtype=np.str_),
+                      info=np.array([self.split, self.category_name, self.version, self.translate, repr(self.preload_offset),
+                                     repr(self.key_frame_only), repr(self.min_points)]))
+        with open(file, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, file, device=None):
+        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
+        dev = _device(device, "NuScenesTracklets")
+        self = cls.__new__(cls)
+        DeviceTracklets.__init__(self)
+        with np.load(file) as z:
+            ends = np.cumsum(z["lengths"])
+            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
+            self.split, self.category_name, self.version, self.translate = (str(s) for s in z["info"][:4])
+            self.preload_offset, self.key_frame_only, self.min_points = (ast.literal_eval(str(s)) for s in z["info"][4:7])
+            self.path = None
             meta = [(str(k), [str(f) for f in fs]) for k, fs in zip(z["keys"], cut(z["files"]))]
             self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
         return self

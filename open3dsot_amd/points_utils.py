@@ -763,6 +763,7 @@ def crop_groups_table(groups, device):
 PRELOAD_MAX_FRAMES = capi.CONSTANTS["O3D_PRELOAD_MAX_FRAMES"]
 PRELOAD_MAX_BOXES = capi.CONSTANTS["O3D_PRELOAD_MAX_BOXES"]
 PRELOAD_MAX_ROWS = capi.CONSTANTS["O3D_PRELOAD_MAX_ROWS"]
+PRELOAD_MAX_STEPS = capi.CONSTANTS["O3D_PRELOAD_MAX_STEPS"]
 PRELOAD_COLS = 6      # a frame record: first raw row, n, first box, number of boxes, workgroup start, scratch base
 
 
@@ -779,9 +780,10 @@ def preload_plan(frames, raw_rows):
     return need, grid[0], grid[1]
 
 
-def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses=None):
+def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses=None, steps=None, translate32=0):
     _need_gpu(raw, "preload")
-    assert raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2 and raw.shape[1] in ((4,) if poses is None else (3, 4))
+    widths = (3, 4, 5) if steps is not None else (3, 4) if poses is not None else (4,)
+    assert raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2 and raw.shape[1] in widths
     assert frames.dtype == np.int32 and frames.ndim == 2 and frames.shape[1] == PRELOAD_COLS and frames.flags.c_contiguous
     for t, dt in ((dev_frames, torch.int32), (bounds, torch.float32), (scratch, torch.int32)):
         _need_gpu(t, "preload")
@@ -791,25 +793,38 @@ def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses
         _need_gpu(poses, "preload")
         assert transform is None and poses.dtype == torch.float64 and poses.is_contiguous() and poses.device == raw.device
         assert poses.numel() == 12 * frames.shape[0]
+    if steps is not None:
+        _need_gpu(steps, "preload")
+        assert transform is None and poses is None and translate32 in (0, 1)
+        assert steps.dtype == torch.float64 and steps.is_contiguous() and steps.device == raw.device
+        assert steps.dim() == 3 and steps.shape[0] == frames.shape[0] and 1 <= steps.shape[1] <= PRELOAD_MAX_STEPS and steps.shape[2] == 12
     if transform is not None:
         transform = np.ascontiguousarray(transform, np.float64)
         assert transform.shape == (3, 4)
     return transform
 
 
-def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts, poses=None):
+def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts, poses=None, steps=None, translate32=0):
     """One o3d_preload_count call (two launches, no sync): raw (rows,4) float32 GPU, frames = the planned (F,6) int32 table on
     the host and dev_frames its GPU copy, bounds (B,6) float32 GPU, transform = (3,4) float64 on the host | None, scratch =
     an int32 GPU tensor of at least preload_plan's length -> counts (B,) int32 GPU, written in place.
     poses = (F,12) float64 GPU, one transform per frame record: o3d_preload_posed_count instead, raw (rows, 3 | 4), transform
-    None"""
-    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses)
+    None.  steps = (F,n_steps,12) float64 GPU, a chain of rounded rigid steps per frame record, translate32 = 0 (the translation
+    is added in fp64 and rounded) | 1 (added in fp32): o3d_preload_steps_count instead, raw (rows, 3 | 4 | 5), transform and
+    poses None"""
+    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses, steps, translate32)
     _need_gpu(counts, "preload_count")
     B = bounds.numel() // 6
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= B
     dev = raw.device
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if steps is not None:
+            capi.check(capi.load().o3d_preload_steps_count(
+                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
+                B, steps.data_ptr(), steps.shape[1], int(translate32), scratch.data_ptr(), scratch.numel(), counts.data_ptr(), stream),
+                "o3d_preload_steps_count")
+            return
         if poses is not None:
             capi.check(capi.load().o3d_preload_posed_count(
                 raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
@@ -821,11 +836,12 @@ def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts, p
             stream), "o3d_preload_count")
 
 
-def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row, pool, pool_rows=None, poses=None):
+def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row, pool, pool_rows=None, poses=None, steps=None,
+                    translate32=0):
     """One o3d_preload_scatter launch after preload_count on the same operands: out_row (B,) int64 GPU = the first pool row of
     every box, pool (rows,3) float32 GPU, written in place; no row at or beyond pool_rows (default: all of pool) is written.
-    poses: as for preload_count (o3d_preload_posed_scatter)"""
-    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses)
+    poses: as for preload_count (o3d_preload_posed_scatter); steps, translate32: as for preload_count (o3d_preload_steps_scatter)"""
+    transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses, steps, translate32)
     _need_gpu(out_row, "preload_scatter")
     _need_gpu(pool, "preload_scatter")
     B = bounds.numel() // 6
@@ -836,6 +852,12 @@ def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row
     dev = raw.device
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if steps is not None:
+            capi.check(capi.load().o3d_preload_steps_scatter(
+                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
+                B, steps.data_ptr(), steps.shape[1], int(translate32), scratch.data_ptr(), scratch.numel(), out_row.data_ptr(),
+                pool.data_ptr(), pool_rows, stream), "o3d_preload_steps_scatter")
+            return
         if poses is not None:
             capi.check(capi.load().o3d_preload_posed_scatter(
                 raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),

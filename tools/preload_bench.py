@@ -1,7 +1,7 @@
-"""What reading a KITTI or a Waymo tree into HBM costs with the device-side preload crop (open3dsot_amd/datasets.py, csrc/preload.hip),
+"""What reading a KITTI, a Waymo or a nuScenes tree into HBM costs with the device-side preload crop (open3dsot_amd/datasets.py, csrc/preload.hip),
 against the host preload restated in numpy.  Not bench.py: that measures the training step on resident batches.
 
-  python tools/preload_bench.py [--dataset kitti|waymo] [--scenes 2] [--frames 50] [--points 120000] [--tracklets 8]
+  python tools/preload_bench.py [--dataset kitti|waymo|nuscenes] [--scenes 2] [--frames 50] [--points 120000] [--tracklets 8]
                                 [--offset 10] [--runs 7] [--chunk-frames 64] [--mode velodyne|camera] [--host-only]
 
 Setup: a synthetic tree in a temporary directory -- `--scenes` scenes (0019, 0020: the split `test`) of `--frames`
@@ -24,6 +24,15 @@ launches are the posed pair (a pose per frame record, rows of three floats), and
 into the pinned buffer (the bounds and the plan are outside it, as for KITTI).  The yardstick transforms with numpy's `dot`, as the reference does; the bit-for-bit comparison is
 against the same restatement with the ordered fp64 sum (BLAS may sum in another order, which reaches a float32 coordinate only
 at a rounding boundary), and `dot_clouds_differing` counts the clouds where the two restatements differ.
+
+--dataset nuscenes: the tree is the nine JSON tables and `--scenes` scenes of `--frames` key-frame .pcd.bin sweeps ((n,5)
+float32 rows: x y z intensity ring; an ego pose of hundreds of metres per sweep), `--tracklets` vehicle.car instances per scene
+annotated in every sample; the reader is NuScenesTracklets (translate="float64"), the launches are the steps pair (two rounded
+rigid steps per frame record, rows of five floats uploaded as they lie), and read_s is the readinto of the files.  raw_bytes
+is what is uploaded (20 bytes a row); launch_bytes counts the 12 bytes a row that the launches ask for, twice, plus the pool
+rows -- the memory system fetches whole lines, so the 8 bytes between are moved as well.  The yardstick does what the reference
+does with numpy (`dot` for rotate, `points[i] + np.float64` for translate, under the installed numpy >= 2); the bit-for-bit
+comparison is against the same restatement with the ordered fp64 sums, and `dot_clouds_differing` counts as for waymo.
 """
 import argparse
 import json
@@ -234,6 +243,171 @@ def main_waymo(args, torch, D):
         print(json.dumps(res))
 
 
+def write_nuscenes_tree(root, scenes, frames, points, tracklets, version, seed=0):
+    """the nine tables with the fields the reader looks at, and the sweeps -> the split table"""
+    rng = np.random.default_rng(seed)
+    os.makedirs(os.path.join(root, version), exist_ok=True)
+    os.makedirs(os.path.join(root, "samples", "LIDAR_TOP"), exist_ok=True)
+
+    def quat(yaw, pitch):
+        cz, sz, cy, sy = np.cos(yaw / 2), np.sin(yaw / 2), np.cos(pitch / 2), np.sin(pitch / 2)
+        return [float(cz * cy), float(-sz * sy), float(cz * sy), float(sz * cy)]         # Rz(yaw) Ry(pitch)
+
+    def matrix(q):
+        w, x, y, z = q
+        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    tables = {n: [] for n in ("category", "instance", "sample_annotation", "sample", "sample_data", "scene", "sensor", "calibrated_sensor",
+                              "ego_pose")}
+    tables["category"].append({"token": "cat_car", "name": "vehicle.car"})
+    tables["sensor"].append({"token": "lidar", "channel": "LIDAR_TOP", "modality": "lidar"})
+    cs = {"token": "cs", "sensor_token": "lidar", "rotation": quat(-1.57, 0.01), "translation": [0.94, 0.0, 1.84]}
+    tables["calibrated_sensor"].append(cs)
+    for s in range(scenes):
+        tables["scene"].append({"token": "scene%d" % s, "name": "scene-%04d" % s})
+        start = rng.uniform([-25.0, -25.0, -1.0], [25.0, 25.0, -0.6], size=(tracklets, 3))
+        speed = rng.uniform(-0.3, 0.3, size=(tracklets, 3)) * [1.0, 1.0, 0.0]
+        for k in range(tracklets):
+            tables["instance"].append({"token": "inst%d_%d" % (s, k), "category_token": "cat_car", "first_annotation_token": "a%d_%d_0" % (s, k)})
+        for frame in range(frames):
+            ego = {"token": "ego%d_%d" % (s, frame), "rotation": quat(0.5 + s + 0.01 * frame, 0.02),
+                   "translation": [411.3 + 600.0 * s + 1.5 * frame, 1180.9 - 0.8 * frame, 1.84]}
+            file = "samples/LIDAR_TOP/s%d_%d.pcd.bin" % (s, frame)
+            tables["ego_pose"].append(ego)
+            tables["sample"].append({"token": "smp%d_%d" % (s, frame), "scene_token": "scene%d" % s})
+            tables["sample_data"].append({"token": "sd%d_%d" % (s, frame), "sample_token": "smp%d_%d" % (s, frame), "ego_pose_token": ego["token"],
+                                          "calibrated_sensor_token": "cs", "is_key_frame": True, "filename": file})
+            for k in range(tracklets):
+                local = start[k] + frame * speed[k]
+                centre = matrix(ego["rotation"]) @ (matrix(cs["rotation"]) @ local + cs["translation"]) + ego["translation"]
+                yaw = 0.2 * k + 0.01 * frame
+                tables["sample_annotation"].append(
+                    {"token": "a%d_%d_%d" % (s, k, frame), "sample_token": "smp%d_%d" % (s, frame), "instance_token": "inst%d_%d" % (s, k),
+                     "translation": [float(v) for v in centre], "size": [1.6, 3.9, 1.5], "rotation": [float(np.cos(yaw / 2)), 0.0, 0.0, float(np.sin(yaw / 2))],
+                     "next": "a%d_%d_%d" % (s, k, frame + 1) if frame + 1 < frames else "", "num_lidar_pts": 40})
+            pts = np.empty((points, 5), np.float32)
+            pts[:, :3] = rng.uniform([-40.0, -40.0, -2.5], [40.0, 40.0, 1.5], size=(points, 3))
+            pts[:, 3] = rng.uniform(0, 255, size=points)
+            pts[:, 4] = rng.integers(0, 32, size=points)
+            pts.tofile(os.path.join(root, file))
+    for name, rows in tables.items():
+        with open(os.path.join(root, version, name + ".json"), "w") as f:
+            json.dump(rows, f)
+    return {"train": [sc["name"] for sc in tables["scene"]]}
+
+
+def host_preload_nuscenes(D, root, version, splits, offset, ordered=False):
+    """the host preload of NuScenesDataset in numpy: -> a list (per tracklet) of lists of (3,n) float32"""
+    annos, files, steps = D.nuscenes_annotations(root, "train", "Car", version, scenes=splits)
+    cache, out = {}, []
+    signs = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
+    for a in annos:
+        clouds = []
+        for f, box in zip(a["frames"], a["boxes"]):
+            if f not in cache:
+                pc = np.fromfile(os.path.join(root, files[f]), np.float32).reshape(-1, 5)[:, :4].T[:3]
+                for M in steps[f].reshape(-1, 3, 4):
+                    if ordered:
+                        x, y, z = (pc[i].astype(np.float64) for i in range(3))
+                        for i in range(3):
+                            pc[i] = (M[i, 0] * x + M[i, 1] * y) + M[i, 2] * z
+                    else:
+                        pc[:3] = np.dot(M[:, :3], pc[:3])
+                    for i in range(3):
+                        pc[i] = pc[i] + M[i, 3]                               # an np.float64 scalar: fp64 under numpy >= 2
+                cache[f] = pc
+            pc = cache[f]
+            if offset > 0:
+                w, l, h = box[3:6]
+                corners = box[6:15].reshape(3, 3) @ (signs * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
+                hi, lo = corners.max(1) + offset, corners.min(1) - offset
+                keep = (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])
+                pc = pc[:, keep]
+            clouds.append(pc)
+        out.append(clouds)
+    return out
+
+
+def main_nuscenes(args, torch, D):
+    version = "v1.0-trainval"
+    assert int(np.__version__.split(".")[0]) >= 2, "the yardstick's translate is numpy's: the reader's default mode is that of numpy >= 2"
+    with tempfile.TemporaryDirectory() as root:
+        splits = write_nuscenes_tree(root, args.scenes, args.frames, args.points, args.tracklets, version)
+        host = host_preload_nuscenes(D, root, version, splits, args.offset, ordered=True)      # reads every file once: the page cache is warm
+        by_dot = host_preload_nuscenes(D, root, version, splits, args.offset)
+        differing = sum(a.tobytes() != b.tobytes() for x, y in zip(host, by_dot) for a, b in zip(x, y))
+        del by_dot
+        host_s = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            host_preload_nuscenes(D, root, version, splits, args.offset)
+            host_s.append(time.perf_counter() - t0)
+        res = {"tool": "preload_bench", "dataset": "nuscenes", "scenes": args.scenes, "frames": args.frames, "points": args.points,
+               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, "crops": sum(len(c) for c in host),
+               "dot_clouds_differing": differing, "host_numpy_s": stat(host_s)}
+        if args.host_only:
+            print(json.dumps(res))
+            return
+        dev = torch.device("cuda", 0)
+        kw = dict(category_name="Car", version=version, preload_offset=args.offset, scenes=splits, device=dev, chunk_frames=args.chunk_frames)
+        trk = D.NuScenesTracklets(root, "train", **kw)                      # warm-up: code objects, the allocator, pinned memory
+        torch.cuda.synchronize(dev)
+        for t, h in zip(trk, host):                                         # faster and different is not faster
+            for g, c in zip(t.frames, h):
+                c = np.ascontiguousarray(c.T, np.float32)
+                assert tuple(g.shape) == c.shape and np.array_equal(g.cpu().numpy().view(np.int32), c.view(np.int32))
+        reader_s = []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            trk = D.NuScenesTracklets(root, "train", **kw)
+            torch.cuda.synchronize(dev)
+            reader_s.append(time.perf_counter() - t0)
+        # the split: the same chunks, step by step
+        annos, files, steps = D.nuscenes_annotations(root, "train", "Car", version, scenes=splits)
+        per_file = [[] for _ in files]
+        for a in annos:
+            for f, box in zip(a["frames"], a["boxes"]):
+                per_file[f].append(box)
+        chunks = [range(i, min(i + args.chunk_frames, len(files))) for i in range(0, len(files), args.chunk_frames)]
+        read_s, upload_ms, count_ms, scatter_ms, raw_bytes, read_bytes, pool_bytes = [], [], [], [], 0, 0, 0
+        ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
+        for run in range(args.runs + 1):                                    # run 0 warms up
+            tot = {"read": 0.0, "upload": 0.0, "count": 0.0, "scatter": 0.0}
+            raw_bytes = read_bytes = pool_bytes = 0
+            pinned = None
+            for ck in chunks:
+                bounds = [D.preload_bounds(np.stack(per_file[f]), args.offset) for f in ck]
+                paths = [os.path.join(root, files[f]) for f in ck]
+                c = D.PreloadChunk([(p, D.nuscenes_rows(p)) for p in paths], bounds, None, dev, pinned, row_floats=5, steps=steps[ck.start:ck.stop])
+                pinned = c.pinned
+                t0 = time.perf_counter()
+                c.read()
+                tot["read"] += time.perf_counter() - t0
+                e = [ev() for _ in range(5)]
+                with torch.cuda.device(dev):
+                    e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
+                    c.read_back()
+                    e[3].record(); c.scatter(); e[4].record()
+                torch.cuda.synchronize(dev)
+                tot["upload"] += e[0].elapsed_time(e[1])
+                tot["count"] += e[1].elapsed_time(e[2])
+                tot["scatter"] += e[3].elapsed_time(e[4])
+                raw_bytes += 20 * c.raw_rows
+                read_bytes += 12 * c.raw_rows
+                pool_bytes += 12 * c.pool.shape[0]
+            if run:
+                read_s.append(tot["read"]); upload_ms.append(tot["upload"]); count_ms.append(tot["count"]); scatter_ms.append(tot["scatter"])
+        launch_ms = [a + b for a, b in zip(count_ms, scatter_ms)]
+        moved = 2 * read_bytes + pool_bytes
+        res.update(reader_s=stat(reader_s), read_s=stat(read_s), upload_ms=stat(upload_ms), count_ms=stat(count_ms),
+                   scatter_ms=stat(scatter_ms), raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
+                   launch_GBps=stat([moved / (ms * 1e-3) / 1e9 for ms in launch_ms]),
+                   upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in upload_ms]), chunks=len(chunks),
+                   host_over_reader=statistics.median(host_s) / statistics.median(reader_s))
+        print(json.dumps(res))
+
+
 def stat(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": len(xs)}
 
@@ -245,7 +419,7 @@ def main():
     ap.add_argument("--offset", type=float, default=10.0)
     ap.add_argument("--scenes", type=int, choices=(1, 2), default=2)
     ap.add_argument("--mode", choices=("velodyne", "camera"), default="velodyne")
-    ap.add_argument("--dataset", choices=("kitti", "waymo"), default="kitti")
+    ap.add_argument("--dataset", choices=("kitti", "waymo", "nuscenes"), default="kitti")
     ap.add_argument("--host-only", action="store_true", help="write the tree and time the numpy restatement only (no device)")
     args = ap.parse_args()
     assert args.runs >= 7 or args.host_only, "a median of at least 7 runs"
@@ -255,6 +429,8 @@ def main():
         raise SystemExit("preload_bench needs a GPU: the reader cannot be measured on the host")
     if args.dataset == "waymo":
         return main_waymo(args, torch, D)
+    if args.dataset == "nuscenes":
+        return main_nuscenes(args, torch, D)
     with tempfile.TemporaryDirectory() as root:
         split = write_tree(root, args.scenes, args.frames, args.points, args.tracklets)
         host = host_preload(D, root, split, args.mode, args.offset)          # reads every file once: the page cache is warm
