@@ -553,7 +553,8 @@ int o3d_xcorr_reduce(const float* dN, const float* Y0, const float* A1, const fl
  * out (B, C2, np) from Z (C0, ldz) = W0 . [xyz ; feats] per point (o3d_pack_points + o3d_mlp_conv_fwd),
  * idx (B, np, ns), centers (B*np, 3) or NULL, v_l (4, C_l) = o3d_bn_eval_consts of layer l.
  * C0 % 8 == 0, C1 % 32 == 0, C2 % 32 == 0, ns a power of two <= 32, (B*np*ns) % 32 == 0; ld = point columns per
- * cloud in Z, pt_base = first column of this set of clouds. */
+ * cloud in Z, pt_base = first column of this set of clouds.  v1, v2 are read as float4: 16-byte aligned, else O3D_EINVAL
+ * (W1, W2 may sit on any 4-byte boundary: views of a flat parameter buffer). */
 int o3d_sa_eval_fused(const float* Z, long ldz, const int32_t* idx, const float* centers, const float* W0, int ldw,
                       const float* v0, const float* W1, const float* v1, const float* W2, const float* v2, int C0, int C1,
                       int C2, int B, int np, int ns, int ld, long pt_base, float* out, void* stream);

@@ -80,16 +80,22 @@ __device__ __forceinline__ void rows_times_slice(const float* __restrict__ A, in
     __syncthreads();
 }
 
-// sum over the rows of a per-thread partial: the row groups of a feature meet in LDS, fixed order
+// sum over the rows of a per-thread partial: the row groups of a feature meet in LDS, fixed order.  The 32 partials are
+// added in fp64 and rounded once: an fp32 chain puts up to R roundings into the batch variance, which the running variance
+// (m * var * R / (R - 1) next to a running value of order 1) then carries -- beyond 8 * 2^-24 of its terms at R = 64
+// (tests/test_rows_kernels_gpu.py).  Four chains of 8 instead of one of 32: the fp64 adds cost no more than the fp32 chain did
 __device__ __forceinline__ float rows_sum(float v, float* red) {
     const int tid = threadIdx.x, fl = tid % RM_FT, rg = tid / RM_FT;
     red[rg * RM_FT + fl] = v;
     __syncthreads();
-    float s = 0.f;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int g = 0; g < RM_RG; ++g) s += red[g * RM_FT + fl];
+    for (int g = 0; g < RM_RG; g += 4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s[u] += (double)red[(g + u) * RM_FT + fl];
+    }
     __syncthreads();
-    return s;
+    return (float)((s[0] + s[1]) + (s[2] + s[3]));
 }
 
 __device__ __forceinline__ void row_fwd_body(const RowFwd& a, float* Ws, float* red) {

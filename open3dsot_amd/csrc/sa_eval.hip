@@ -133,7 +133,10 @@ __global__ __launch_bounds__(256) void sa_eval_kernel(SaEvalArgs a) {
 // out (B, C2, np) = max over nsample of relu(bn2(W2 . relu(bn1(W1 . relu(bn0(Y0)))))),
 //   Y0[c, (b,j,k)] = Z[c, pt_base + b*ld + idx[b,j,k]] - W0[c*ldw + 0..2] . centers[b*np + j]      (centers may be NULL)
 // BatchNorm on running statistics: v_l (4, C_l) = {mean, invstd, scale, shift} (o3d_bn_eval_consts).
-// C0 % 8 == 0, C1 % 32 == 0, C2 % 32 == 0, ns a power of two <= 32, (B*np*ns) % 32 == 0.
+// C0 % 8 == 0, C1 % 32 == 0, C2 % 32 == 0, ns a power of two <= 32, (B*np*ns) % 32 == 0; v1, v2 16-byte aligned.
+// W1 / W2 are NOT required to be: their rows are read as float4 from global memory, and the trackers hand in views of the
+// optimizer's flat parameter buffer (optim.FlatAdam), which sit on any 4-byte boundary -- refusing those would refuse
+// every eval between training steps (tests/test_model_gpu.py, train -> eval -> train -> eval).
 extern "C" int o3d_sa_eval_fused(const float* Z, long ldz, const int32_t* idx, const float* centers, const float* W0,
                                  int ldw, const float* v0, const float* W1, const float* v1, const float* W2,
                                  const float* v2, int C0, int C1, int C2, int B, int np, int ns, int ld, long pt_base,
