@@ -343,6 +343,31 @@ int o3d_group_reduce_gather(const float* dN, const float* Y0, long ldp, const fl
                             const int32_t* ball_cnt, int B, int nseg, int npoint0, int ld0, int npoint1, int ld1, int C0,
                             int spanmax, int32_t* perm, int32_t* poff, float* S, float* T, void* stream);
 
+/* o3d_group_reduce_gather in a FIXED order (deterministic mode): same arguments, same poff, no float atomic; S and T are
+ * one fp32 expression of (gp, ball_off, ball_cnt, sizes; dN, Y0, cw, A1..A3) -- independent of timing, of C0 and the
+ * channel slabs, and of whether T is NULL.  o3d_group_reduce_gather_ordered_scratch: ints of poff, -1 = the shape does
+ * not fit the ordered kernels' LDS budget (3 KiB / 8 KiB tighter than the default pair's; there is no ordered fallback).
+ *
+ * The order, per cloud (b of segment s; its point columns start at pbase, its balls at bbase):
+ *   q0 = ball_off[bbase], q1 = ball_off[last ball] + ball_cnt[last ball], q0a = q0 & ~3, CH = 2048.
+ *   Chunk k = the columns q of [q0, q1) with (q - q0a) / CH == k, i.e. [max(q0, q0a + k*CH), min(q1, q0a + (k+1)*CH)).
+ *   dY[c, q] = fmaf(A1[c], dN[c, q], cw[q] * fmaf(A2[c], Y0[c, q], A3[c]))   (segment 1: A at +C0)
+ *   perm: per chunk, the entries (n << 16) | (q - q0a - k*CH), n = gp[q] - pbase, sorted by ascending entry value (by point,
+ *   then column); chunk k's entries are perm[q0 + poff[k*ld] .. q0 + poff[(k+1)*ld]), poff[k*ld + n] = start of point
+ *   n's list, relative to q0, the cloud's total at poff[nchunk*ld].
+ *   S[c, pbase + n] = acc, where acc = 0 and, for k = 0, 1, .. ascending with a non-empty list of n in chunk k:
+ *       cnt = entries of chunk k, per = ceil(cnt / 256); the list occupies positions [a, b) of the chunk's entries;
+ *       it is cut into pieces at the multiples of per inside (a, b); piece = (((0 + dY[e0]) + dY[e1]) + ..) over its
+ *       entries in position order; total = ((piece0 + piece1) + piece2) ..; acc = acc + total.
+ *   T[c, bbase + j] = acc, where acc = 0 and, for k ascending where ball j has columns in chunk k:
+ *       t = (((0 + dY[s0]) + dY[s0+1]) + ..) over the ball's columns inside the chunk, ascending; acc = acc + t.
+ * All additions are fp32 round-to-nearest, nothing is fused.  tests/ordered_reduce_oracle.py restates this in numpy. */
+long o3d_group_reduce_gather_ordered_scratch(int B, int nseg, int npoint0, int ld0, int npoint1, int ld1, int spanmax);
+int o3d_group_reduce_gather_ordered(const float* dN, const float* Y0, long ldp, const float* A1, const float* A2,
+                                    const float* A3, const int32_t* gp, const float* cw, const int32_t* ball_off,
+                                    const int32_t* ball_cnt, int B, int nseg, int npoint0, int ld0, int npoint1, int ld1,
+                                    int C0, int spanmax, int32_t* perm, int32_t* poff, float* S, float* T, void* stream);
+
 /* Per-point operand of layer 0 (QueryAndGroup's inputs before the gather, pointnet2_utils.py:318-333):
  * X0 (rows, ldz), ldz = B*(ld0 + ld1): rows [0,nxyz) = xyz^T * inv_radius, rows [nxyz, nxyz+C) = feats, further
  * rows zero; cloud b of segment s occupies columns [base_s + b*ld_s, +N_s), padded to ld_s by zeros.

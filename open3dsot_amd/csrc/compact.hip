@@ -962,6 +962,248 @@ __global__ __launch_bounds__(256) void reduce_gather_kernel(const float* __restr
         }
 }
 
+// ---------------------------------------------------------------------------------------
+// The ORDERED twins of the pair above (deterministic mode, fused.set_deterministic): no float atomic, and no order handed
+// out by an atomic survives into the result -- S and T are one fixed fp32 expression of (index, dN, Y0, constants).
+//   csr_build_ordered_kernel      csr_build_kernel's counting sort, then every (chunk, point) list put into ascending
+//                                 column order: chunk by chunk the <= RG_CH entries are staged in LDS and every entry is
+//                                 written back at (list start + number of smaller entries of its list).
+//   reduce_gather_ordered_kernel  reduce_gather_kernel with the same balanced split (thread t: entries [t*per, (t+1)*per)
+//                                 of the chunk, per = ceil(cnt/256)); a share's pieces are summed left to right from 0; a
+//                                 run inside one share is a plain LDS add; of a run cut by share boundaries, the pieces
+//                                 that CONTINUE it go to one LDS slot per thread and, behind a barrier, the thread that
+//                                 holds the first piece adds them in thread order and adds the total to the point's sum.
+// The written order is in include/o3dsot.h (o3d_group_reduce_gather_ordered); tests/ordered_reduce_oracle.py restates it.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void csr_build_ordered_kernel(const int32_t* __restrict__ gp,
+                                                                 const int32_t* __restrict__ ball_off,
+                                                                 const int32_t* __restrict__ ball_cnt, int B, SegParams sp0,
+                                                                 SegParams sp1, int nchunk, int poff_stride,
+                                                                 int32_t* __restrict__ perm, int32_t* __restrict__ poff) {
+    extern __shared__ int csr_sh[];         // cnt[nchunk*ld + 1], scan scratch [1024], one chunk's entries [RG_CH]
+    const int cloud = blockIdx.x;
+    const int seg = cloud >= B ? 1 : 0, b = cloud - seg * B;
+    const SegParams sp = seg ? sp1 : sp0;
+    const int npoint = sp.npoint, ld = sp.ld;
+    const int pbase = sp.pt_base + b * ld, bbase = sp.ball_base + b * npoint;
+    const int q0 = ball_off[bbase], q1 = ball_off[bbase + npoint - 1] + ball_cnt[bbase + npoint - 1];
+    const int q0a = q0 & ~3;
+    const int nbin = nchunk * ld;
+    int* cnt = csr_sh;
+    int* part = csr_sh + nbin + 1;
+    int* stg = part + 1024;
+    for (int i = threadIdx.x; i <= nbin; i += 1024) cnt[i] = 0;
+    __syncthreads();
+    for (int q = q0 + threadIdx.x; q < q1; q += 1024) atomicAdd(&cnt[((q - q0a) / RG_CH) * ld + (gp[q] - pbase)], 1);
+    __syncthreads();
+    const int per = (nbin + 1023) / 1024, i0 = threadIdx.x * per;       // exclusive scan of the bin counts
+    int local = 0;
+    for (int i = i0; i < i0 + per && i < nbin; ++i) local += cnt[i];
+    part[threadIdx.x] = local;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - local;
+    for (int i = i0; i < i0 + per && i < nbin; ++i) {
+        const int c = cnt[i];
+        cnt[i] = run;
+        run += c;
+    }
+    if (threadIdx.x == 1023) cnt[nbin] = part[1023];
+    __syncthreads();
+    int32_t* po = poff + (long)cloud * poff_stride;
+    for (int i = threadIdx.x; i <= nbin; i += 1024) po[i] = cnt[i];
+    __syncthreads();
+    // unordered fill, as csr_build_kernel: afterwards cnt[bin] = END of the bin's list = start of the next bin's
+    for (int q = q0 + threadIdx.x; q < q1; q += 1024) {
+        const int ch = (q - q0a) / RG_CH, n = gp[q] - pbase;
+        const int k = atomicAdd(&cnt[ch * ld + n], 1);
+        perm[q0 + k] = (n << 16) | (q - q0a - ch * RG_CH);
+    }
+    __syncthreads();                        // (the workgroup's own stores to perm are visible to it behind the barrier)
+    // order: a chunk's entries (<= RG_CH: one per column) staged in LDS; the entries of one list share the point bits and
+    // differ in the column, so an entry's place in its sorted list is the number of smaller entries of that list
+    for (int k = 0; k < nchunk; ++k) {
+        const int l0 = k * ld > 0 ? cnt[k * ld - 1] : 0, l1 = cnt[(k + 1) * ld - 1];
+        const int n = l1 - l0;
+        for (int i = threadIdx.x; i < n; i += 1024) stg[i] = perm[q0 + l0 + i];
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += 1024) {
+            const int e = stg[i];
+            const int bin = k * ld + (e >> 16);
+            const int s = (bin > 0 ? cnt[bin - 1] : 0) - l0, t = cnt[bin] - l0;
+            int r = 0;
+            for (int a = s; a < t; ++a) r += stg[a] < e ? 1 : 0;
+            perm[q0 + l0 + s + r] = e;
+        }
+        __syncthreads();
+    }
+}
+
+template <int CS>
+__global__ __launch_bounds__(256) void reduce_gather_ordered_kernel(
+    const float* __restrict__ dN, const float* __restrict__ Y0, long ldp, const float* __restrict__ A1,
+    const float* __restrict__ A2, const float* __restrict__ A3, const float* __restrict__ cw,
+    const int32_t* __restrict__ ball_off, const int32_t* __restrict__ ball_cnt, const int32_t* __restrict__ perm,
+    const int32_t* __restrict__ poff, int poff_stride, int B, SegParams sp0, SegParams sp1, int C0, long lds_row,
+    float* __restrict__ S, float* __restrict__ T, int nballs) {
+    extern __shared__ float rg_sm[];        // dy[CS][CH], sacc[CS][ld], tacc[CS][npoint], list[CH], hd[CS][256], hpt[256]
+    constexpr int CH = RG_CH;
+    const int slabs = (C0 + CS - 1) / CS;
+    const int cloud = blockIdx.x / slabs, c0 = (blockIdx.x - cloud * slabs) * CS;
+    const int seg = cloud >= B ? 1 : 0, b = cloud - seg * B;
+    const SegParams sp = seg ? sp1 : sp0;
+    const int npoint = sp.npoint, ld = sp.ld;
+    const int pbase = sp.pt_base + b * ld, bbase = sp.ball_base + b * npoint;
+    float* dy = rg_sm;
+    float* sacc = dy + CS * CH;
+    float* tacc = sacc + CS * ld;
+    int* lst = reinterpret_cast<int*>(tacc + CS * npoint);
+    float* hd = reinterpret_cast<float*>(lst + CH);
+    int* hpt = reinterpret_cast<int*>(hd + CS * 256);
+    const int q0 = ball_off[bbase], q1 = ball_off[bbase + npoint - 1] + ball_cnt[bbase + npoint - 1];
+    const int q0a = q0 & ~3;
+    const int32_t* po = poff + (long)cloud * poff_stride;
+    for (int i = threadIdx.x; i < CS * (ld + npoint); i += 256) sacc[i] = 0.f;
+    float a1[CS], a2[CS], a3[CS];
+    int crow[CS];                            // channel rows (clamped: an odd C0 repeats its last row, never stored)
+#pragma unroll
+    for (int c = 0; c < CS; ++c) {
+        crow[c] = c0 + c < C0 ? c0 + c : C0 - 1;
+        const int cc = seg * C0 + crow[c];
+        a1[c] = A1[cc]; a2[c] = A2[cc]; a3[c] = A3[cc];
+    }
+    for (int k = 0, lo = q0a; lo < q1; ++k, lo += CH) {
+        const int hi = lo + CH < q1 ? lo + CH : q1;
+        // phase A as reduce_gather_kernel: all global loads of the chunk in flight, then dY and the index into LDS
+        const int l0 = po[k * ld], l1 = po[(k + 1) * ld];
+        const int cnt = l1 - l0;
+        int ent[CH / 256];
+#pragma unroll
+        for (int u = 0; u < CH / 256; ++u) {
+            const int i = threadIdx.x + 256 * u;
+            ent[u] = perm[cnt > 0 ? q0 + l0 + (i < cnt ? i : cnt - 1) : 0];
+        }
+        float4 d[CH / 1024][CS], y[CH / 1024][CS], w4[CH / 1024];
+#pragma unroll
+        for (int it = 0; it < CH / 1024; ++it) {
+            const int q = lo + 4 * threadIdx.x + 1024 * it;
+            const int qc = q < hi ? q : lo;
+            w4[it] = *reinterpret_cast<const float4*>(&cw[qc]);
+#pragma unroll
+            for (int c = 0; c < CS; ++c) {
+                d[it][c] = *reinterpret_cast<const float4*>(&dN[(long)crow[c] * ldp + qc]);
+                y[it][c] = *reinterpret_cast<const float4*>(&Y0[(long)crow[c] * ldp + qc]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();                    // previous chunk fully consumed, its fold included (first pass: the zero fill)
+#pragma unroll
+        for (int it = 0; it < CH / 1024; ++it) {
+            const int i = 4 * threadIdx.x + 1024 * it;
+#pragma unroll
+            for (int c = 0; c < CS; ++c) {
+                float4 o;
+                o.x = fmaf(a1[c], d[it][c].x, w4[it].x * fmaf(a2[c], y[it][c].x, a3[c]));
+                o.y = fmaf(a1[c], d[it][c].y, w4[it].y * fmaf(a2[c], y[it][c].y, a3[c]));
+                o.z = fmaf(a1[c], d[it][c].z, w4[it].z * fmaf(a2[c], y[it][c].z, a3[c]));
+                o.w = fmaf(a1[c], d[it][c].w, w4[it].w * fmaf(a2[c], y[it][c].w, a3[c]));
+                *reinterpret_cast<float4*>(&dy[c * CH + i]) = o;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CH / 256; ++u) lst[threadIdx.x + 256 * u] = ent[u];
+        __syncthreads();
+        // phase B, balanced and ordered.  A point has ONE run per chunk (the list is sorted by point), so: a run that
+        // lies inside this share is touched by no other thread (plain add); the share's first run, when it continues
+        // the previous thread's last entry, is a HEAD piece (LDS slot of this thread); the share's last run, when the
+        // next thread's first entry continues it and it is no head piece, is the run's FIRST piece (kept in registers).
+        int tailpt = -1;
+        float sr[CS];
+        {
+            const int per = (cnt + 255) / 256;
+            const int e0 = threadIdx.x * per, e1 = e0 + per < cnt ? e0 + per : cnt;
+            const bool cut_l = e0 < e1 && e0 > 0 && (lst[e0 - 1] >> 16) == (lst[e0] >> 16);
+            int cur = -1, headpt = -1;
+            bool first = true;
+#pragma unroll
+            for (int c = 0; c < CS; ++c) sr[c] = 0.f;
+            for (int a = e0; a < e1; ++a) {
+                const int e = lst[a];
+                const int n = e >> 16, i = e & 0xffff;
+                if (n != cur) {
+                    if (cur >= 0) {         // a run that ends inside the share: the head piece or a whole run
+                        if (first && cut_l) {
+                            headpt = cur;
+#pragma unroll
+                            for (int c = 0; c < CS; ++c) hd[c * 256 + threadIdx.x] = sr[c];
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < CS; ++c) sacc[c * ld + cur] += sr[c];
+                        }
+                        first = false;
+                    }
+                    cur = n;
+#pragma unroll
+                    for (int c = 0; c < CS; ++c) sr[c] = 0.f;
+                }
+#pragma unroll
+                for (int c = 0; c < CS; ++c) sr[c] += dy[c * CH + i];
+            }
+            if (cur >= 0) {                 // the share's last run
+                if (first && cut_l) {       // (the whole share continues a run; it may go on into the next thread's)
+                    headpt = cur;
+#pragma unroll
+                    for (int c = 0; c < CS; ++c) hd[c * 256 + threadIdx.x] = sr[c];
+                } else if (e1 < cnt && (lst[e1] >> 16) == cur) {
+                    tailpt = cur;
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CS; ++c) sacc[c * ld + cur] += sr[c];
+                }
+            }
+            hpt[threadIdx.x] = headpt;
+        }
+        __syncthreads();
+        if (tailpt >= 0) {                  // fold: first piece + the head pieces of the following threads, in thread order
+            for (int u = threadIdx.x + 1; u < 256 && hpt[u] == tailpt; ++u) {
+#pragma unroll
+                for (int c = 0; c < CS; ++c) sr[c] += hd[c * 256 + u];
+            }
+#pragma unroll
+            for (int c = 0; c < CS; ++c) sacc[c * ld + tailpt] += sr[c];
+        }
+        if (T)
+            for (int j = threadIdx.x; j < npoint; j += 256) {     // thread j: its ball's part of the chunk, left to right
+                const int b0 = ball_off[bbase + j], b1 = b0 + ball_cnt[bbase + j];
+                const int s0 = b0 > lo ? b0 : lo, s1 = b1 < hi ? b1 : hi;
+                if (s0 >= s1) continue;
+                float t[CS];
+#pragma unroll
+                for (int c = 0; c < CS; ++c) t[c] = 0.f;
+                for (int q = s0; q < s1; ++q)
+#pragma unroll
+                    for (int c = 0; c < CS; ++c) t[c] += dy[c * CH + (q - lo)];
+#pragma unroll
+                for (int c = 0; c < CS; ++c) tacc[c * npoint + j] += t[c];
+            }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CS * ld; i += 256) {
+        const int c = i / ld, n = i - c * ld;
+        if (c0 + c < C0) S[(long)(c0 + c) * lds_row + pbase + n] = sacc[i];
+    }
+    if (T)
+        for (int i = threadIdx.x; i < CS * npoint; i += 256) {
+            const int c = i / npoint, j = i - c * npoint;
+            if (c0 + c < C0) T[(long)(c0 + c) * nballs + bbase + j] = tacc[i];
+        }
+}
+
 // dW[c, 0..2] -= sum over balls of T[c, ball] * centers[ball, :]: the centre term of
 // grouped_xyz = xyz[idx] - new_xyz (pointnet2_utils.py:322-324) in the layer-0 weight gradient.
 // One 1024-thread workgroup per channel, fixed summation order.
@@ -1455,5 +1697,59 @@ extern "C" int o3d_group_reduce_gather(const float* dN, const float* Y0, long ld
     const int slabs = (C0 + cs - 1) / cs;
     hipLaunchKernelGGL(reduce_gather_kernel<2>, dim3(B * nseg * slabs), dim3(256), lds_red, s, dN, Y0, ldp, A1, A2, A3, cw,
                            ball_off, ball_cnt, perm, poff, stride, B, sp0, sp1, C0, lds_row, S, T, nballs);
+    return o3d_launch_status();
+}
+
+// ---- the ORDERED pair (deterministic mode; csr_build_ordered_kernel / reduce_gather_ordered_kernel) ----------
+// LDS of the two ordered kernels: the build stages one chunk's entries, the reduce keeps one head piece per thread
+static size_t rgo_lds_csr(long nbin) { return ((size_t)nbin + 1 + 1024 + RG_CH) * 4; }
+static size_t rgo_lds_red(int cs, int ldm, int npm) {
+    return ((size_t)cs * RG_CH + (size_t)cs * (ldm + npm)) * 4 + (size_t)RG_CH * 4 + ((size_t)cs * 256 + 256) * 4 + 8;
+}
+
+// int32 elements of `poff` scratch for o3d_group_reduce_gather_ordered, or -1 when the shape does not fit the LDS budget
+// of the ordered kernels (the same ceilings as the default pair's, which they reach 8 KiB / 3 KiB sooner)
+extern "C" long o3d_group_reduce_gather_ordered_scratch(int B, int nseg, int npoint0, int ld0, int npoint1, int ld1,
+                                                        int spanmax) {
+    if (B <= 0 || (nseg != 1 && nseg != 2) || npoint0 <= 0 || ld0 <= 0 || spanmax <= 0 ||
+        (nseg == 2 && (npoint1 <= 0 || ld1 <= 0)))
+        return -1;
+    const int ldm = nseg == 2 && ld1 > ld0 ? ld1 : ld0, npm = nseg == 2 && npoint1 > npoint0 ? npoint1 : npoint0;
+    const long nbin = (long)rg_nchunk(spanmax) * ldm;
+    if (rgo_lds_csr(nbin) > 128 * 1024 || rgo_lds_red(rg_cs(), ldm, npm) > 80 * 1024) return -1;
+    return (long)B * nseg * (nbin + 1);
+}
+
+extern "C" int o3d_group_reduce_gather_ordered(const float* dN, const float* Y0, long ldp, const float* A1, const float* A2,
+                                               const float* A3, const int32_t* gp, const float* cw, const int32_t* ball_off,
+                                               const int32_t* ball_cnt, int B, int nseg, int npoint0, int ld0, int npoint1,
+                                               int ld1, int C0, int spanmax, int32_t* perm, int32_t* poff, float* S, float* T,
+                                               void* stream) {
+    if (!dN || !Y0 || !A1 || !A2 || !A3 || !gp || !cw || !ball_off || !ball_cnt || !perm || !poff || !S || C0 <= 0 ||
+        ldp <= 0 || ldp % 4 != 0 || o3d_group_reduce_gather_ordered_scratch(B, nseg, npoint0, ld0, npoint1, ld1, spanmax) < 0)
+        return O3D_EINVAL;
+    hipStream_t s = o3d_stream(stream);
+    const SegParams sp0 = {npoint0, ld0, 0, 0};
+    const SegParams sp1 = nseg == 2 ? SegParams{npoint1, ld1, B * ld0, B * npoint0} : sp0;
+    const long lds_row = (long)B * ld0 + (nseg == 2 ? (long)B * ld1 : 0);
+    const int nballs = B * npoint0 + (nseg == 2 ? B * npoint1 : 0);
+    const int ldm = nseg == 2 && ld1 > ld0 ? ld1 : ld0, npm = nseg == 2 && npoint1 > npoint0 ? npoint1 : npoint0;
+    const int nchunk = rg_nchunk(spanmax);
+    const int stride = nchunk * ldm + 1;
+    const size_t lds_csr = rgo_lds_csr((long)nchunk * ldm);
+    const size_t lds_red = rgo_lds_red(2, ldm, npm);
+    if (lds_csr > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(csr_build_ordered_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds_csr) != hipSuccess)
+        return O3D_ELAUNCH;
+    const void* rgk = reinterpret_cast<const void*>(reduce_gather_ordered_kernel<2>);
+    if (lds_red > 48 * 1024 &&
+        hipFuncSetAttribute(rgk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_red) != hipSuccess)
+        return O3D_ELAUNCH;
+    hipLaunchKernelGGL(csr_build_ordered_kernel, dim3(B * nseg), dim3(1024), lds_csr, s, gp, ball_off, ball_cnt, B, sp0, sp1,
+                       nchunk, stride, perm, poff);
+    const int slabs = (C0 + 1) / 2;
+    hipLaunchKernelGGL(reduce_gather_ordered_kernel<2>, dim3(B * nseg * slabs), dim3(256), lds_red, s, dN, Y0, ldp, A1, A2, A3,
+                       cw, ball_off, ball_cnt, perm, poff, stride, B, sp0, sp1, C0, lds_row, S, T, nballs);
     return o3d_launch_status();
 }

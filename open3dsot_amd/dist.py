@@ -187,6 +187,7 @@ class DataParallelStep:
         self._static = None
         self._static_loss = None
         self._static_grads = None      # the gradient tensors the captured backward writes (graph pool)
+        self._deterministic = None     # fused.deterministic_enabled() at the capture: the graph replays THOSE kernels
         self._eager_steps = 0
         self._buffers = [b for b in model.buffers()]
         # sampling prefetch (HISTORY.md section 7): the farthest-point-sampling indices of batch t+1 are computed on a second
@@ -266,6 +267,8 @@ class DataParallelStep:
         torch.cuda.synchronize()
         for b, v in zip(buffers, saved):
             b.copy_(v)
+        from . import fused
+        self._deterministic = fused.deterministic_enabled()
         g = torch.cuda.CUDAGraph()
         # thread_local: other threads of the process (the RCCL watchdog of torch.distributed polls events) may
         # keep calling the runtime while this thread captures
@@ -326,6 +329,12 @@ class DataParallelStep:
         """one training step on `batch`.  next_batch: the batch the NEXT call will be given (the very same dict object),
         when the caller knows it -- its input-only preprocessing (farthest-point sampling) then runs beside this step"""
         if self.graph is not None:
+            from . import fused
+            if fused.deterministic_enabled() != self._deterministic:
+                # (the captured graph would keep replaying the layer-0 list sums of the other mode)
+                raise RuntimeError("DataParallelStep: fused.set_deterministic(%s) since the step was captured with "
+                                   "deterministic mode %s; build a new trainer" % (
+                                       fused.deterministic_enabled(), "on" if self._deterministic else "off"))
             src = batch
             flat = isinstance(batch, FlatBatch) and batch.layout == self._static.layout
             if self._sampling is not None and self._static.extra_keys:

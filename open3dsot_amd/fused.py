@@ -547,11 +547,23 @@ class FusedGroupedMLPCompact(torch.autograd.Function):
                 S = torch.empty((Cout, ldz), device=dev, dtype=f32)
                 T = torch.empty((Cout, nballs), device=dev, dtype=f32) if nxyz else None
                 spanmax = max(npoints) * ns
-                npo = lib.o3d_group_reduce_gather_scratch(*cl.reduce_dims, spanmax) if _REDUCE_GATHER["on"] else -1
+                det = _DETERMINISTIC["on"]      # the ordered pair (no float atomic, a written order) or an error: see below
+                scratch = lib.o3d_group_reduce_gather_ordered_scratch if det else lib.o3d_group_reduce_gather_scratch
+                npo = scratch(*cl.reduce_dims, spanmax) if _REDUCE_GATHER["on"] else -1
+                if det and npo < 0:      # never an atomic kernel behind the caller's back
+                    raise RuntimeError(
+                        "open3dsot_amd: deterministic mode (fused.set_deterministic(True)) has no ordered layer-0 list sums "
+                        "for this set abstraction: (B, nseg, npoint0, ld0, npoint1, ld1) = %s, spanmax = %d %s; the kernels "
+                        "left for it use LDS float atomics" % (
+                            tuple(cl.reduce_dims), spanmax,
+                            "does not fit the LDS budget of o3d_group_reduce_gather_ordered" if _REDUCE_GATHER["on"]
+                            else "under set_reduce_gather(False)"))
                 if npo >= 0:     # the cloud's columns through a transposed index: one LDS atomic per run of equal points
+                    #              (deterministic mode: the index sorted, the pieces of a cut run folded in thread order)
                     perm = torch.empty((ldp,), device=dev, dtype=torch.int32)
                     poff = torch.empty((npo,), device=dev, dtype=torch.int32)
-                    _call("group_reduce", 0.0, lib.o3d_group_reduce_gather, dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1],
+                    _call("group_reduce", 0.0, lib.o3d_group_reduce_gather_ordered if det else lib.o3d_group_reduce_gather,
+                          dN.data_ptr(), act.Y.data_ptr(), ldp, A[0], A[1],
                           A[2], gp.data_ptr(), cw.data_ptr(), ball_off.data_ptr(), ball_cnt.data_ptr(), *cl.reduce_dims,
                           Cout, spanmax, perm.data_ptr(), poff.data_ptr(), S.data_ptr(), _ptr(T), st)
                 else:            # the index does not fit the LDS budget (o3d_group_reduce_gather_scratch < 0): one LDS atomic per column
@@ -638,6 +650,21 @@ def set_reduce_gather(enabled):
 
 def reduce_gather_enabled():
     return _REDUCE_GATHER["on"]
+
+
+# deterministic mode: the training step as a function of its inputs, bit for bit.  Everything else in the fused path sums in
+# a fixed order already; the layer-0 list sums then run through o3d_group_reduce_gather_ordered (csrc/compact.hip) or raise
+# where that does not fit, and the composed path's scatter backwards (ops.py) raise.  Off by default; a captured step keeps
+# the kernels it was captured with (dist.DataParallelStep refuses a switch flipped after its capture).
+_DETERMINISTIC = {"on": False}
+
+
+def set_deterministic(enabled):
+    _DETERMINISTIC["on"] = bool(enabled)
+
+
+def deterministic_enabled():
+    return _DETERMINISTIC["on"]
 
 
 # ---- tracking inference: one kernel per set abstraction (csrc/sa_eval.hip) --------------------------------------

@@ -14,6 +14,16 @@ from torch.autograd import Function
 from . import ext as _ext
 
 
+def _refuse_when_deterministic(name):
+    """deterministic mode (fused.set_deterministic): the backward of `name` scatters with float atomics (csrc/index_ops.hip),
+    so its sums depend on the order the atomics land in -- an error, as torch raises for its non-deterministic operators"""
+    from . import fused
+    if fused.deterministic_enabled():
+        raise RuntimeError("open3dsot_amd.ops.%s: the backward scatter uses float atomics and has no deterministic "
+                           "implementation, but fused.set_deterministic(True) is set (the fused set-abstraction path does not "
+                           "take this operator)" % name)
+
+
 class RandomDropout(nn.Module):
     """pointnet2_utils.py:24-32: feature dropout with a drop probability drawn from U(0, p) per call.  (The reference passes
     the bound method `self.train` as the training flag -- always true -- and calls a function its pytorch_utils.py lacks;
@@ -64,6 +74,7 @@ class GatherOperation(Function):
 
     @staticmethod
     def backward(ctx, grad_out):
+        _refuse_when_deterministic("GatherOperation")
         (idx,) = ctx.saved_tensors
         return _ext.gather_points_grad(grad_out.contiguous(), idx, ctx.n_src), None
 
@@ -108,6 +119,7 @@ class ThreeInterpolate(Function):
 
     @staticmethod
     def backward(ctx, grad_out):
+        _refuse_when_deterministic("ThreeInterpolate")
         idx, weight = ctx.saved_tensors
         g = _ext.three_interpolate_grad(grad_out.contiguous(), idx, weight, ctx.m_src)
         return g, None, None
@@ -127,6 +139,7 @@ class GroupingOperation(Function):
 
     @staticmethod
     def backward(ctx, grad_out):
+        _refuse_when_deterministic("GroupingOperation")
         (idx,) = ctx.saved_tensors
         return _ext.group_points_grad(grad_out.contiguous(), idx, ctx.n_src), None
 
