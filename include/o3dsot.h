@@ -517,6 +517,33 @@ int o3d_mlp_conv_wgrad2_group(const o3d_wgrad_job* jobs, int njobs, void* stream
 int o3d_adam_step(const long* jobs, int njobs, float* params, float* exp_avg, float* exp_avg_sq, double lr,
                   double beta1, double beta2, double eps, double weight_decay, double bc1, double bc2, void* stream);
 
+/* The rest of the flat-buffer optimizer family (csrc/optim.hip), on o3d_adam_step's job table; gradients may sit on any
+ * 4-byte boundary.
+ *
+ * o3d_grad_norm: the total 2-norm of all gradients of the table and torch.nn.utils.clip_grad_norm_'s coefficient
+ * (main.py:85 `gradient_clip_val`, norm clipping), in two plain launches: (njobs, O3D_NORM_SLICES) blocks store
+ * partials[job * O3D_NORM_SLICES + slice] = the sum of (double)g * (double)g over the slice (0 for an empty one; every
+ * entry is written, nothing needs clearing), one block adds them in a fixed order to S and writes
+ *   out[0] = (float)sqrt(S),   out[1] = (float)min(1, max_norm / (sqrt(S) + 1e-6))      (double, rounded once).
+ * partials: njobs * O3D_NORM_SLICES doubles, out: 2 floats, both DEVICE.  max_norm <= 0 (or NaN) is O3D_EINVAL: "no
+ * clipping" means not calling.  Non-finite gradients follow the arithmetic (out[0] shows them; a NaN stays a NaN).
+ *
+ * o3d_adam_step_scaled: o3d_adam_step with g * *grad_scale in place of g (before the weight decay); grad_scale is a
+ * DEVICE float, typically out + 1 above.  The same bits as o3d_adam_step on gradients scaled beforehand.
+ *
+ * o3d_sgd_step: torch.optim.SGD with momentum, dampening 0, no Nesterov (models/base_model.py:29-31), per element in
+ * this order, each line one float rounding:
+ *   g' = g * *grad_scale (grad_scale != NULL);  g' = fma(weight_decay, p, g') (weight_decay != 0);
+ *   buf = fma(momentum, buf, g');  p = fma(-lr, buf, p).
+ * A zero momentum buffer gives buf = g' exactly: torch's first-step rule without a flag. */
+#define O3D_NORM_SLICES 32
+int o3d_grad_norm(const long* jobs, int njobs, double max_norm, double* partials, float* out, void* stream);
+int o3d_adam_step_scaled(const long* jobs, int njobs, float* params, float* exp_avg, float* exp_avg_sq, double lr,
+                         double beta1, double beta2, double eps, double weight_decay, double bc1, double bc2,
+                         const float* grad_scale, void* stream);
+int o3d_sgd_step(const long* jobs, int njobs, float* params, float* momentum_buf, double lr, double momentum,
+                 double weight_decay, const float* grad_scale, void* stream);
+
 /* Best proposal of a tracked frame: replaces the host-side selection of MatchingBaseModel.evaluate_one_sample
  * (models/base_model.py:44-57: `estimation_box.cpu().numpy()`, `[:, 4].argmax()`, `[best, 0:4]`) -- SURVEY.md section
  * 8f-4 lists that device->host copy as part of the per-frame latency path.  boxes (B, P, 5) contiguous;

@@ -12,5 +12,7 @@ BAT / P2B feature-extraction hot path.
     open3dsot_amd.tracking       the frame loops on the device, and their evaluation (evaluate_sequence, evaluate)
     open3dsot_amd.metrics        IoU / centre distance of box pairs and Success / Precision as device counters
     open3dsot_amd.sampler        training batches built on the device (PointTrackingSampler + siamese_processing)
+    open3dsot_amd.optim          Adam / SGD on flat buffers, one launch per step, with gradient-norm clipping
+    open3dsot_amd.training       fit(): epochs, validation, checkpoints, resume (the reference's main.py)
 """
 __version__ = "0.1.0"

@@ -32,6 +32,7 @@ SOURCES = [
     ("train_batch.hip", ["-ffp-contract=off"]),      # calls track.hip's crop_test / gather_row (csrc/track_common.hpp): same contract
     ("metrics.hip", ["-ffp-contract=off"]),      # the scoring arithmetic's operation order is stated (tests/metrics_oracle.py)
     ("preload.hip", ["-ffp-contract=off"]),      # the camera transform's fp64 operation order is stated (tests/kitti_oracle.py)
+    ("optim.hip", ["-ffp-contract=off"]),      # the update rules' operation order is stated (tests/optim_oracle.py)
     ("capi_misc.hip", []),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",

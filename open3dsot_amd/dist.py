@@ -157,7 +157,7 @@ class DataParallelStep:
     outside the graph (eagerly enqueued while the graph runs)."""
 
     def __init__(self, model, optimizer=None, world=None, graph=False, graph_warmup=3, prefetch_sampling=True,
-                 require_graph=None, exchange=None):
+                 require_graph=None, exchange=None, grad_clip=None):
         self.model = model
         self.world = world if world is not None else (dist.get_world_size() if dist.is_initialized() else 1)
         # exchange: run the multi-rank path -- parameter broadcast, gradient pack inside the captured step, the one flat
@@ -176,6 +176,12 @@ class DataParallelStep:
             conf = model.configure_optimizers()
             optimizer, self.scheduler = conf["optimizer"], conf.get("lr_scheduler")   # StepLR of base_model.py:34-35
         self.optimizer = optimizer
+        # grad_clip (main.py:85 `gradient_clip_val`, norm clipping; None / 0: off): after reduce_gradients(), as under DDP.
+        # A flat optimizer clips inside its own step (two norm launches, the scale read on the device: optim._FlatClip);
+        # any other one -- the CPU mirror, the gloo tests -- goes through torch.nn.utils.clip_grad_norm_
+        self.grad_clip = grad_clip if grad_clip else None
+        if self.grad_clip and hasattr(optimizer, "last_grad_norm"):
+            optimizer.grad_clip = self.grad_clip
         self.graph_requested = bool(graph) and torch.cuda.is_available()
         # require_graph: a failed capture raises instead of falling back to the (several times slower) eager step;
         # default: the O3D_REQUIRE_GRAPH=1 environment switch (CI / benchmarking)
@@ -390,6 +396,8 @@ class DataParallelStep:
             loss = self._forward_backward(batch)
             self._eager_steps += 1
         self.reduce_gradients()
+        if self.grad_clip and not hasattr(self.optimizer, "last_grad_norm"):
+            torch.nn.utils.clip_grad_norm_(self.grads.params, self.grad_clip)
         self.optimizer.step()
         return loss
 

@@ -279,8 +279,12 @@ class M2TRACK(nn.Module):
 
     def configure_optimizers(self):
         c = self.config
-        # same update rule as the reference's torch.optim.Adam; on the GPU one launch on flat buffers
+        # same update rules as the reference's shared BaseModel (models/base_model.py:28-36); on the GPU one launch on flat
+        # buffers
         from . import optim
-        opt = optim.make_adam(self.parameters(), c.lr, c.wd)
+        if str(c.optimizer).lower() == "sgd":
+            opt = optim.make_sgd(self.parameters(), c.lr, c.wd)
+        else:
+            opt = optim.make_adam(self.parameters(), c.lr, c.wd)
         sched = torch.optim.lr_scheduler.StepLR(opt, step_size=c.lr_decay_step, gamma=c.lr_decay_rate)
         return {"optimizer": opt, "lr_scheduler": sched}

@@ -89,7 +89,7 @@ class MatchingBaseModel(nn.Module):
     def configure_optimizers(self):
         c = self.config
         if str(c.optimizer).lower() == "sgd":
-            opt = torch.optim.SGD(self.parameters(), lr=c.lr, momentum=0.9, weight_decay=c.wd)
+            opt = optim.make_sgd(self.parameters(), c.lr, c.wd)        # one launch as well (optim.FlatSGD)
         else:
             # same update rule as the reference's torch.optim.Adam; on the GPU one launch on flat buffers
             # (open3dsot_amd/optim.py::FlatAdam) instead of ~12 foreach launches per step
