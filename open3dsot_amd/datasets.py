@@ -49,8 +49,13 @@ one FileNotFoundError, an empty one gives a (0,3) frame; key_frame_only cannot d
 above only holds key frames) but the flag and the reference's `continue` are kept; the same -inf / +inf bounds and the same NaN
 deviation as the Waymo reader with preload_offset <= 0.  Not restated: non-preloading access, and the devkit's loading and
 checking of the tables the reference never reads (attribute, visibility, log, map).
+
+The three readers differ in how they parse and in what a raw frame is (kitti_items, waymo_items, nuscenes_items: one
+PreloadItem per distinct raw frame); the rest is stated once: preload_chunks cuts the items into chunks, PreloadChunk is the
+device half of a chunk, and _PoolTracklets runs the chunks, fills the row table, assembles the views and holds save / load.
 """
 import ast
+import collections
 import json
 import os
 import pickle
@@ -224,15 +229,6 @@ def preload_bounds(boxes, offset):
     return out
 
 
-def _device(device, who="KittiTracklets"):
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise RuntimeError("%s: CPU not supported (the frames live on a GPU)" % who)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def velodyne_rows(path):
     """rows of a velodyne .bin as the reference reads it (np.fromfile(float32).reshape(-1, 4)); -1: missing or unreadable as
     (n,4), which the reference turns into the single point (0,0,0)"""
@@ -257,41 +253,79 @@ def _read_rows(host, path, n):
         raise OSError("%s changed while it was read" % path)
 
 
+# a distinct raw frame as the planner and the chunk see it: the row loader's source, its raw rows, bounds (k,6) float32, per box
+# the (tracklet, frame index) pairs that take its rows, the key a chunk may not mix (KITTI: the scene, for a chunk has one
+# transform) and what the frame adds to the chunk's transform keyword (KITTI: the scene's transform, Waymo: the pose,
+# NuScenes: the steps)
+PreloadItem = collections.namedtuple("PreloadItem", "source n bounds users group extra", defaults=(None, None))
+
+
+def frame_boxes(annos, users, preload_offset):
+    """-> (bounds (k,6) float32, [[(tracklet, frame index)] per box]) of one raw frame.  preload_offset <= 0: no crop, one
+    box of -inf / +inf whose slice all users share, as they share one cloud in the reference; otherwise a box per user"""
+    if preload_offset <= 0:
+        return preload_bounds(np.zeros((1, 15)), preload_offset), [users]
+    return preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in users]), preload_offset), [[u] for u in users]
+
+
+def preload_chunks(items, chunk_frames, max_rows=PU.PRELOAD_MAX_ROWS, max_records=PU.PRELOAD_MAX_FRAMES, max_boxes=PU.PRELOAD_MAX_BOXES):
+    """The cut rule of every reader (pure host): yields the PreloadItems of `items` in order, as lists.  A chunk holds at most
+    chunk_frames items, one group, max_rows raw rows and max_records frame records (an item with k boxes takes
+    max(1, ceil(k / max_boxes))); its first item is always taken, and preload_plan refuses one that is too large alone.
+    `items` is pulled lazily: when a chunk is yielded, at most the one item that closed it has been pulled beyond it."""
+    chunk, nrows, nrec = [], 0, 0
+    for item in items:
+        rec = max(1, -(-len(item.bounds) // max_boxes))
+        if chunk and (item.group != chunk[0].group or nrows + item.n > max_rows or nrec + rec > max_records):
+            yield chunk
+            chunk, nrows, nrec = [], 0, 0
+        chunk.append(item)
+        nrows, nrec = nrows + item.n, nrec + rec
+        if len(chunk) == chunk_frames:
+            yield chunk
+            chunk, nrows, nrec = [], 0, 0
+    if chunk:
+        yield chunk
+
+
 class PreloadChunk:
-    """The device half for one chunk of raw frames: plan, upload, count, read back, scatter.  files: [(source, n rows)],
-    boxes_per_file: for each file a (k,6) float32 array of bounds (k >= 0).  A raw row is row_floats = 3 | 4 floats;
-    loader(host rows (n,row_floats), source, n) fills the pinned buffer's rows of one file (default: source is the path of a
-    velodyne .bin; with poses, source is the (n,row_floats) float32 array itself: copy_rows).  transform: one (3,4) fp64 for the chunk | None; poses: one (3,4) fp64 PER FILE instead (then transform is
-    None and the launches are o3d_preload_posed_*); steps: one (n_steps,12) fp64 block PER FILE instead, a chain of rounded
-    rigid steps with translate32 = 0 | 1 (then transform and poses are None, a raw row is 3 | 4 | 5 floats and the launches are
-    o3d_preload_steps_*).  The stages are separate methods so that tools/preload_bench.py can time
-    them; run() is the sequence the readers use."""
+    """The device half for one chunk of raw frames: plan, upload, count, read back, scatter.
+      files            [(source, n rows)]; a raw row is row_floats floats
+      bounds_per_file  for each file a (k,6) float32 array of bounds, k >= 0
+      loader           loader(host rows (n,row_floats), source, n) fills one file's rows of the pinned buffer.  Default:
+                       _read_rows (source is a path), with poses copy_rows (source is the (n,row_floats) array itself)
+    and one of three transforms, which picks the pair of launches:
+      transform        one (3,4) fp64 for the chunk | None; row_floats 4                              o3d_preload_*
+      poses            one (3,4) fp64 PER FILE; row_floats 3 | 4                                      o3d_preload_posed_*
+      steps            one (n_steps,12) fp64 block PER FILE, a chain of rounded rigid steps whose translation is added
+                       in fp64 and rounded (translate32 = 0) or in fp32 (1); row_floats 3 | 4 | 5     o3d_preload_steps_*
+    The stages are separate methods so that tools/preload_bench.py can time them; run() is the sequence the readers use."""
 
     def __init__(self, files, bounds_per_file, transform, device, pinned=None, row_floats=4, loader=None, poses=None, steps=None,
                  translate32=0):
         assert poses is None or (transform is None and len(poses) == len(files))
         assert steps is None or (transform is None and poses is None and len(steps) == len(files))
         assert row_floats == 4 or poses is not None or steps is not None
-        self.translate32 = int(translate32)
         self.device, self.transform = device, transform
         self.loader = loader if loader is not None else copy_rows if poses is not None else _read_rows
-        recs, rec_pose, row = [], [], 0
+        recs, rec_file, row = [], [], 0
         for i, ((_, n), b) in enumerate(zip(files, bounds_per_file)):
             for k0 in range(0, len(b), PU.PRELOAD_MAX_BOXES):       # a frame with more boxes than a record takes: more records
                 recs.append((row, n, 0, min(PU.PRELOAD_MAX_BOXES, len(b) - k0), 0, 0))
-                rec_pose.append(i)                                  # ... that carry the frame's pose each
+                rec_file.append(i)                                  # ... that carry the frame's pose or steps each
             row += n
         self.files, self.raw_rows = files, row
         self.frames = np.array(recs, np.int32).reshape(-1, PU.PRELOAD_COLS)
         self.need, self.wgs, self.B = PU.preload_plan(self.frames, row)
         self.bounds = np.concatenate([np.asarray(b, np.float32).reshape(-1, 6) for b in bounds_per_file] + [np.zeros((0, 6), np.float32)])
         assert self.bounds.shape[0] == self.B
-        self.poses = None if poses is None else \
-            np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12)[np.array(rec_pose, np.int64)])
-        self.steps = None
-        if steps is not None:                                       # (files, n_steps, 12) -> (records, n_steps, 12)
-            steps = np.asarray(steps, np.float64).reshape(len(files), -1, 12) if len(files) else np.zeros((0, 1, 12))
-            self.steps = np.ascontiguousarray(steps[np.array(rec_pose, np.int64)])
+        # what the launches take besides transform: nothing | poses (records,12) | steps (records,n_steps,12) and translate32
+        rec_file, self.per_record, self.how = np.array(rec_file, np.int64), {}, {}
+        if poses is not None:
+            self.per_record["poses"] = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12)[rec_file])
+        if steps is not None:
+            steps = np.asarray(steps, np.float64).reshape((len(files), -1, 12) if len(files) else (0, 1, 12))
+            self.per_record["steps"], self.how["translate32"] = np.ascontiguousarray(steps[rec_file]), int(translate32)
         if pinned is None or pinned.shape[0] < row or pinned.shape[1] != row_floats:
             pinned = torch.empty((max(row, 1), row_floats), dtype=torch.float32).pin_memory()
         self.pinned = pinned
@@ -306,28 +340,18 @@ class PreloadChunk:
     def upload(self):
         dev = self.device
         self.raw = self.pinned[:self.raw_rows].to(dev, non_blocking=True)
-        tables = [self.frames.reshape(-1).view(np.uint8), self.bounds.reshape(-1).view(np.uint8)]
-        if self.poses is not None:                # frames and bounds are 24 bytes a row: the doubles behind them are aligned
-            tables.append(self.poses.reshape(-1).view(np.uint8))
-        if self.steps is not None:
-            tables.append(self.steps.reshape(-1).view(np.uint8))
-        t = torch.from_numpy(np.concatenate(tables)).to(dev)
+        # one copy for the tables; frames and bounds are 24 bytes a row: the doubles behind them are aligned
+        tables = [self.frames, self.bounds] + list(self.per_record.values())
+        t = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8) for x in tables])).to(dev)
         nf, nb = self.frames.size * 4, self.bounds.size * 4
         self.dev_frames, self.dev_bounds = t[:nf].view(torch.int32), t[nf:nf + nb].view(torch.float32)
-        self.dev_poses = None if self.poses is None else t[nf + nb:].view(torch.float64)
-        self.dev_steps = None if self.steps is None else t[nf + nb:].view(torch.float64).view(self.steps.shape)
+        for name, x in self.per_record.items():
+            self.how[name] = t[nf + nb:].view(torch.float64).view(x.shape)
         self.scratch = torch.empty((self.need,), dtype=torch.int32, device=dev)
         self.counts = torch.empty((self.B,), dtype=torch.int32, device=dev)
 
     def count(self):
-        if self.dev_steps is not None:
-            PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.counts,
-                             steps=self.dev_steps, translate32=self.translate32)
-        elif self.dev_poses is None:
-            PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.counts)
-        else:
-            PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.counts,
-                             poses=self.dev_poses)
+        PU.preload_count(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.counts, **self.how)
 
     def read_back(self):
         """-> counts (B,) int64 on the host; allocates the chunk's pool segment and uploads every box's first row"""
@@ -338,15 +362,8 @@ class PreloadChunk:
         return counts
 
     def scatter(self):
-        if self.dev_steps is not None:
-            PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.out_row, self.pool,
-                               steps=self.dev_steps, translate32=self.translate32)
-        elif self.dev_poses is None:
-            PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.out_row,
-                               self.pool)
-        else:
-            PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, None, self.scratch, self.out_row, self.pool,
-                               poses=self.dev_poses)
+        PU.preload_scatter(self.raw, self.frames, self.dev_frames, self.dev_bounds, self.transform, self.scratch, self.out_row, self.pool,
+                           **self.how)
 
     def run(self):
         self.read()
@@ -357,8 +374,69 @@ class PreloadChunk:
         return counts
 
 
+def _frame_users(annos, key=lambda a, frame: int(frame)):
+    """{key of a distinct raw frame: [(tracklet, frame index)] that crop it}, in order of first use"""
+    users = {}
+    for k, a in enumerate(annos):
+        for t, frame in enumerate(a["frames"]):
+            users.setdefault(key(a, frame), []).append((k, t))
+    return users
+
+
+_STR = (str, str)                                 # an info field as written by save and parsed by load: a string as it stands,
+_LITERAL = (repr, ast.literal_eval)               # ... or a Python literal that comes back as it was given
+
+
 class _PoolTracklets(DeviceTracklets):
-    """what the readers share: every frame is a view of ONE pool tensor, and the reference's counting accessors"""
+    """what the readers share: the chunk loop, every frame a view of ONE pool tensor, the cache and the reference's counting
+    accessors.  A reader declares INFO, the attributes that save writes into `info` as (name, (write, parse)), and CHUNK, the
+    keywords of its PreloadChunks: kind, what the items' extras are (default "transform", one for the chunk | "poses" |
+    "steps", one per file), and row_floats.  meta[k] = (key, the files of the frames) unless it overrides _pack_meta /
+    _unpack_meta."""
+    INFO, CHUNK = (), {}
+
+    @classmethod
+    def _device(cls, device, chunk_frames=1):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("%s: CPU not supported (the frames live on a GPU)" % cls.__name__)
+        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
+            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    @classmethod
+    def preload_chunk(cls, items, device, pinned=None, **kw):
+        """the PreloadChunk of one list that preload_chunks yielded"""
+        kw = {**cls.CHUNK, **kw}
+        kind, extras = kw.pop("kind", "transform"), [item.extra for item in items]
+        if kind != "transform":
+            kw[kind] = extras
+        return PreloadChunk([(item.source, item.n) for item in items], [item.bounds for item in items],
+                            extras[0] if kind == "transform" else None, device, pinned, **kw)
+
+    def _preload(self, dev, annos, meta, items, chunk_frames, missing=(), **chunk_kw):
+        """runs the chunks of `items` (PreloadItems, pulled lazily) and assembles the tracklets over the pool: the chunks'
+        segments in order, then one origin point per (tracklet, frame index) of `missing`"""
+        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
+        segments, base, pinned = [], 0, None
+        with torch.cuda.device(dev):
+            for chunk_items in preload_chunks(items, chunk_frames):
+                chunk = self.preload_chunk(chunk_items, dev, pinned, **chunk_kw)
+                counts = chunk.run()
+                pinned, b = chunk.pinned, 0
+                for item in chunk_items:
+                    for who in item.users:
+                        for k, f in who:
+                            rows[k][f] = (base + chunk.first[b], counts[b])
+                        b += 1
+                segments.append(chunk.pool)
+                base += int(chunk.first[-1])
+            for k, f in missing:
+                rows[k][f] = (base, 1)
+                base += 1
+            segments.append(torch.zeros((len(missing), 3), dtype=torch.float32, device=dev))
+            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
+        self._assemble(pool, rows, [a["boxes"] for a in annos], meta)
 
     def _assemble(self, pool, rows, boxes64, meta):
         self.pool, self.rows, self.boxes64, self.meta = pool, rows, boxes64, meta
@@ -366,6 +444,7 @@ class _PoolTracklets(DeviceTracklets):
         for r, b in zip(rows, boxes64):
             self.append(DeviceTracklet([pool[int(s):int(s) + int(c)] for s, c in r], b.astype(np.float32).reshape(-1, 15)))
 
+    # ---- the reference's accessors ------------------------------------------------------------------------------------------
     def get_num_tracklets(self):
         return len(self)
 
@@ -375,71 +454,75 @@ class _PoolTracklets(DeviceTracklets):
     def get_num_frames_tracklet(self, tracklet_id):
         return len(self[tracklet_id])
 
+    def get_frames(self, seq_id, frame_ids):
+        t, (key, files) = self[seq_id], self.meta[seq_id]
+        return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (key, files[f])} for f in frame_ids]
+
+    # ---- the cache ----------------------------------------------------------------------------------------------------------
+    def _pack_meta(self):
+        return dict(keys=np.array([m[0] for m in self.meta], dtype=np.str_),
+                    files=np.array([f for m in self.meta for f in m[1]], dtype=np.str_))
+
+    def _unpack_meta(self, z, cut):
+        return [(str(k), [str(f) for f in fs]) for k, fs in zip(z["keys"], cut(z["files"]))]
+
+    def save(self, file):
+        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
+        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
+        arrays = dict(pool=self.pool.cpu().numpy(), lengths=np.array([len(t) for t in self], np.int64),
+                      rows=cat(self.rows, (0, 2), np.int64), boxes=cat(self.boxes64, (0, 15), np.float64), **self._pack_meta(),
+                      info=np.array([write(getattr(self, name)) for name, (write, _) in self.INFO]))
+        with open(file, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, file, device=None):
+        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
+        dev = cls._device(device)
+        self = cls.__new__(cls)
+        DeviceTracklets.__init__(self)
+        with np.load(file) as z:
+            ends = np.cumsum(z["lengths"])
+            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
+            self.path = None
+            for (name, (_, parse)), s in zip(cls.INFO, z["info"]):
+                setattr(self, name, parse(str(s)))
+            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), self._unpack_meta(z, cut))
+        return self
+
+
+def kitti_items(path, annos, calibs, coordinate_mode, preload_offset):
+    """-> (the PreloadItems of every distinct (scene, frame) in order of first use, the (tracklet, frame index) pairs whose
+    velodyne file is missing or unreadable as (n,4): the reference's `except` gives those one point at the origin)"""
+    items, missing = [], []
+    for (scene, frame), who in _frame_users(annos, lambda a, frame: (a["scene"], int(frame))).items():
+        file = os.path.join(path, "velodyne", scene, "%06d.bin" % frame)
+        n = velodyne_rows(file)
+        if n < 0:
+            missing += who
+        else:
+            transform = np.ascontiguousarray(calibs[scene][:3]) if coordinate_mode == "camera" else None
+            items.append(PreloadItem(file, n, *frame_boxes(annos, who, preload_offset), scene, transform))
+    return items, missing
+
 
 class KittiTracklets(_PoolTracklets):
     """KittiTracklets(path, split, ...): the tracklets of the KITTI tracking set under `path` (velodyne/, label_02/, calib/),
     cropped as the reference preloads them, resident in HBM.  A sampler.DeviceTracklets: goes unchanged into tracking.evaluate
     and DeviceBatchSampler.  meta[k] = (scene, track_id, frame numbers); pool = the one (rows,3) tensor all frames view;
     rows[k] = (T,2) int64 [first pool row, count] of tracklet k's frames."""
+    INFO = (("split", _STR), ("category_name", _STR), ("coordinate_mode", _STR), ("preload_offset", (repr, float)))
 
     def __init__(self, path, split, category_name="Car", coordinate_mode="velodyne", preload_offset=-1, device=None, chunk_frames=64):
         super().__init__()
-        dev = _device(device)
-        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
-            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        dev = self._device(device, chunk_frames)
         self.path, self.split, self.category_name = path, split, category_name
         self.coordinate_mode, self.preload_offset = coordinate_mode, preload_offset
         annos, calibs = kitti_annotations(path, split, category_name, coordinate_mode)
         self.scene_list = kitti_scene_list(split)
-        # every distinct (scene, frame) once, in order of first use, with the tracklet frames that crop it
-        users, missing = {}, []
-        for k, a in enumerate(annos):
-            for t, frame in enumerate(a["frames"]):
-                users.setdefault((a["scene"], int(frame)), []).append((k, t))
-        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
-        shared = preload_offset <= 0              # no crop: the tracklets of a frame share one slice, as they share one cloud
-        todo = []                                 # (file, n, bounds (k,6), [[(tracklet, frame index)] per box])
-        for (scene, frame), who in users.items():
-            file = os.path.join(path, "velodyne", scene, "%06d.bin" % frame)
-            n = velodyne_rows(file)
-            if n < 0:
-                missing += who
-            elif shared:
-                todo.append((scene, file, n, preload_bounds(np.zeros((1, 15)), preload_offset), [who]))
-            else:
-                todo.append((scene, file, n, preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in who]), preload_offset),
-                             [[u] for u in who]))
-        segments, base, pinned, i = [], 0, None, 0
-        with torch.cuda.device(dev):
-            while i < len(todo):
-                # a chunk: frames of one scene (one transform), at most chunk_frames of them and PRELOAD_MAX_ROWS raw rows
-                j, nrows, nrec = i, 0, 0
-                while j < len(todo) and j - i < chunk_frames and todo[j][0] == todo[i][0]:
-                    rec = max(1, -(-len(todo[j][3]) // PU.PRELOAD_MAX_BOXES))
-                    if j > i and (nrows + todo[j][2] > PU.PRELOAD_MAX_ROWS or nrec + rec > PU.PRELOAD_MAX_FRAMES):
-                        break
-                    nrows, nrec, j = nrows + todo[j][2], nrec + rec, j + 1
-                transform = np.ascontiguousarray(calibs[todo[i][0]][:3]) if coordinate_mode == "camera" else None
-                chunk = PreloadChunk([(t[1], t[2]) for t in todo[i:j]], [t[3] for t in todo[i:j]], transform, dev, pinned)
-                counts = chunk.run()
-                pinned, b = chunk.pinned, 0
-                for t in todo[i:j]:
-                    for who in t[4]:
-                        for k, f in who:
-                            rows[k][f] = (base + chunk.first[b], counts[b])
-                        b += 1
-                segments.append(chunk.pool)
-                base += int(chunk.first[-1])
-                i = j
-            for k, f in missing:                  # the reference's `except`: one point at the origin
-                rows[k][f] = (base, 1)
-                base += 1
-            segments.append(torch.zeros((len(missing), 3), dtype=torch.float32, device=dev))
-            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
-        meta = [(a["scene"], a["track_id"], a["frames"]) for a in annos]
-        self._assemble(pool, rows, [a["boxes"] for a in annos], meta)
+        items, missing = kitti_items(path, annos, calibs, coordinate_mode, preload_offset)
+        self._preload(dev, annos, [(a["scene"], a["track_id"], a["frames"]) for a in annos], items, chunk_frames, missing)
 
-    # ---- the reference's accessors ------------------------------------------------------------------------------------------
     def get_num_scenes(self):
         return len(self.scene_list)
 
@@ -448,34 +531,14 @@ class KittiTracklets(_PoolTracklets):
         return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (self.meta[seq_id][0], self.meta[seq_id][1], int(self.meta[seq_id][2][f]))}
                 for f in frame_ids]
 
-    # ---- the cache ----------------------------------------------------------------------------------------------------------
-    def save(self, file):
-        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
-        lengths = np.array([len(t) for t in self], np.int64)
-        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
-        arrays = dict(pool=self.pool.cpu().numpy(), lengths=lengths, rows=cat(self.rows, (0, 2), np.int64),
-                      boxes=cat(self.boxes64, (0, 15), np.float64), frames=cat((m[2] for m in self.meta), (0,), np.int64),
-                      scenes=np.array([m[0] for m in self.meta], dtype="U4"), track_ids=np.array([m[1] for m in self.meta], np.int64),
-                      info=np.array([self.split, self.category_name, self.coordinate_mode, repr(self.preload_offset)]),
-                      scene_list=np.array(self.scene_list, dtype="U4"))
-        with open(file, "wb") as f:
-            np.savez(f, **arrays)
+    def _pack_meta(self):
+        return dict(frames=np.concatenate([m[2] for m in self.meta] + [np.zeros((0,), np.int64)]),
+                    scenes=np.array([m[0] for m in self.meta], dtype="U4"), track_ids=np.array([m[1] for m in self.meta], np.int64),
+                    scene_list=np.array(self.scene_list, dtype="U4"))
 
-    @classmethod
-    def load(cls, file, device=None):
-        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
-        dev = _device(device)
-        self = cls.__new__(cls)
-        DeviceTracklets.__init__(self)
-        with np.load(file) as z:
-            ends = np.cumsum(z["lengths"])
-            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
-            self.split, self.category_name, self.coordinate_mode = (str(s) for s in z["info"][:3])
-            self.preload_offset = float(z["info"][3])
-            self.path, self.scene_list = None, [str(s) for s in z["scene_list"]]
-            meta = [(str(s), int(t), f) for s, t, f in zip(z["scenes"], z["track_ids"], cut(z["frames"]))]
-            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
-        return self
+    def _unpack_meta(self, z, cut):
+        self.scene_list = [str(s) for s in z["scene_list"]]
+        return [(str(s), int(t), f) for s, t, f in zip(z["scenes"], z["track_ids"], cut(z["frames"]))]
 
 
 # ---- Waymo --------------------------------------------------------------------------------------------------------------------
@@ -580,92 +643,36 @@ def waymo_points(file):
     return np.ascontiguousarray(pts)
 
 
+def waymo_items(annos, files, poses, preload_offset, root=None):
+    """-> an iterator over the PreloadItem of every distinct lidar file in order of first use.  The bounds are computed here;
+    a file's rows are known only once it is unpickled, so that happens when the planner pulls its item: once per file, and
+    the array goes when its chunk is done"""
+    users = _frame_users(annos)
+    boxes = [frame_boxes(annos, users[f], preload_offset) for f in range(len(files))]
+
+    def item(f):
+        pts = waymo_points(_waymo_open(files[f], root))
+        return PreloadItem(pts, pts.shape[0], *boxes[f], extra=poses[f])
+    return map(item, range(len(files)))
+
+
 class WaymoTracklets(_PoolTracklets):
     """WaymoTracklets(path, split, ...): the tracklets of <path>/sot_infos_<category>_<split>.pkl, transformed to the global
     frame and cropped as the reference's WaymoDataset preloads them, resident in HBM.  A sampler.DeviceTracklets.  meta[k] =
     (tracklet key, the 'PC' strings of its frames); pool / rows as in KittiTracklets.  With preload_offset <= 0 nothing is
     cropped: the transformed cloud of a frame is written once and its tracklets share the slice."""
 
+    INFO = (("split", _STR), ("category_name", _STR), ("preload_offset", _LITERAL), ("tiny", _LITERAL))
+    CHUNK = dict(kind="poses", row_floats=3)
+
     def __init__(self, path, split, category_name="VEHICLE", preload_offset=10, tiny=False, root=None, device=None, chunk_frames=64):
         super().__init__()
-        dev = _device(device, "WaymoTracklets")
-        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
-            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        dev = self._device(device, chunk_frames)
         self.path, self.preload_offset, self.tiny = path, preload_offset, bool(tiny)
         self.split, self.category_name = waymo_names(split, category_name)
         annos, files, poses = waymo_annotations(path, split, category_name, tiny, root)
-        users = [[] for _ in files]               # per distinct file the tracklet frames that crop it
-        for k, a in enumerate(annos):
-            for t, f in enumerate(a["frames"]):
-                users[f].append((k, t))
-        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
-        shared = preload_offset <= 0
-        segments, base, pinned, i, held = [], 0, None, 0, None
-        with torch.cuda.device(dev):
-            while i < len(files):
-                # a chunk: at most chunk_frames files, PRELOAD_MAX_FRAMES records and PRELOAD_MAX_ROWS raw rows; a file is
-                # unpickled when its chunk is formed (its n is not known before) and dropped when the chunk is done
-                chunk_files, bounds, who_of, nrows, nrec, j = [], [], [], 0, 0, i
-                while j < len(files) and j - i < chunk_frames:
-                    pts = held if held is not None else waymo_points(_waymo_open(files[j], root))
-                    held = None
-                    rec = 1 if shared else max(1, -(-len(users[j]) // PU.PRELOAD_MAX_BOXES))
-                    if j > i and (nrows + pts.shape[0] > PU.PRELOAD_MAX_ROWS or nrec + rec > PU.PRELOAD_MAX_FRAMES):
-                        held = pts                # the first file of the next chunk
-                        break
-                    chunk_files.append((pts, pts.shape[0]))
-                    if shared:
-                        bounds.append(preload_bounds(np.zeros((1, 15)), preload_offset))
-                        who_of.append([users[j]])
-                    else:
-                        bounds.append(preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in users[j]]), preload_offset))
-                        who_of.append([[u] for u in users[j]])
-                    nrows, nrec, j = nrows + pts.shape[0], nrec + rec, j + 1
-                chunk = PreloadChunk(chunk_files, bounds, None, dev, pinned, row_floats=3, poses=poses[i:j])
-                counts = chunk.run()
-                pinned, b = chunk.pinned, 0
-                for whos in who_of:
-                    for who in whos:
-                        for k, f in who:
-                            rows[k][f] = (base + chunk.first[b], counts[b])
-                        b += 1
-                segments.append(chunk.pool)
-                base += int(chunk.first[-1])
-                i = j
-            segments.append(torch.zeros((0, 3), dtype=torch.float32, device=dev))
-            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
-        self._assemble(pool, rows, [a["boxes"] for a in annos], [(a["key"], a["files"]) for a in annos])
-
-    def get_frames(self, seq_id, frame_ids):
-        t, (key, files) = self[seq_id], self.meta[seq_id]
-        return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (key, files[f])} for f in frame_ids]
-
-    # ---- the cache ----------------------------------------------------------------------------------------------------------
-    def save(self, file):
-        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
-        lengths = np.array([len(t) for t in self], np.int64)
-        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
-        arrays = dict(pool=self.pool.cpu().numpy(), lengths=lengths, rows=cat(self.rows, (0, 2), np.int64),
-                      boxes=cat(self.boxes64, (0, 15), np.float64), keys=np.array([m[0] for m in self.meta], dtype=np.str_),
-                      files=np.array([f for m in self.meta for f in m[1]], dtype=np.str_),
-                      info=np.array([self.split, self.category_name, repr(self.preload_offset), repr(self.tiny)]))
-        with open(file, "wb") as f:
-            np.savez(f, **arrays)
-
-    @classmethod
-    def load(cls, file, device=None):
-        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
-        dev = _device(device, "WaymoTracklets")
-        self = cls.__new__(cls)
-        DeviceTracklets.__init__(self)
-        with np.load(file) as z:
-            ends = np.cumsum(z["lengths"])
-            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
-            self.split, self.category_name = (str(s) for s in z["info"][:2])
-            self.preload_offset, self.tiny, self.path = ast.literal_eval(str(z["info"][2])), str(z["info"][3]) == "True", None
-            meta = [(str(k), [str(f) for f in fs]) for k, fs in zip(z["keys"], cut(z["files"]))]
-            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
-        return self
+        self._preload(dev, annos, [(a["key"], a["files"]) for a in annos], waymo_items(annos, files, poses, preload_offset, root),
+                      chunk_frames)
 
 
 # ---- NuScenes -----------------------------------------------------------------------------------------------------------------
@@ -778,6 +785,13 @@ def nuscenes_rows(file):
     return size // _NUSC_ROW_BYTES
 
 
+def nuscenes_items(path, annos, files, steps, preload_offset):
+    """-> the PreloadItems of every distinct sweep in order of first use"""
+    users = _frame_users(annos)
+    return [PreloadItem(full, nuscenes_rows(full), *frame_boxes(annos, users[f], preload_offset), extra=steps[f])
+            for f, full in enumerate(os.path.join(path, file) for file in files)]
+
+
 class NuScenesTracklets(_PoolTracklets):
     """NuScenesTracklets(path, split, ...): the tracklets of the nuScenes set under `path` (<version>/*.json, the sweeps where
     sample_data names them), taken sensor -> ego -> global and cropped as the reference's NuScenesDataset preloads them,
@@ -786,86 +800,18 @@ class NuScenesTracklets(_PoolTracklets):
     share the slice.  translate = "float64" (numpy >= 2: the translation is added in fp64 and rounded) | "float32" (numpy < 2:
     an fp32 add).  scenes: see nuscenes_split_scenes."""
 
+    INFO = (("split", _STR), ("category_name", _STR), ("version", _STR), ("translate", _STR), ("preload_offset", _LITERAL),
+            ("key_frame_only", _LITERAL), ("min_points", _LITERAL))
+    CHUNK = dict(kind="steps", row_floats=5)
+
     def __init__(self, path, split, category_name="Car", version="v1.0-trainval", key_frame_only=False, min_points=False,
                  preload_offset=-1, scenes=None, translate="float64", device=None, chunk_frames=64):
         super().__init__()
-        dev = _device(device, "NuScenesTracklets")
-        if not 1 <= int(chunk_frames) <= PU.PRELOAD_MAX_FRAMES:
-            raise ValueError("1 <= chunk_frames <= %d" % PU.PRELOAD_MAX_FRAMES)
+        dev = self._device(device, chunk_frames)
         if translate not in ("float64", "float32"):
             raise ValueError("translate must be 'float64' or 'float32'")
         self.path, self.split, self.category_name, self.version = path, split, category_name, version
         self.key_frame_only, self.min_points, self.preload_offset, self.translate = key_frame_only, min_points, preload_offset, translate
         annos, files, steps = nuscenes_annotations(path, split, category_name, version, key_frame_only, min_points, scenes)
-        users = [[] for _ in files]               # per distinct sweep the tracklet frames that crop it
-        for k, a in enumerate(annos):
-            for t, f in enumerate(a["frames"]):
-                users[f].append((k, t))
-        rows = [np.zeros((len(a["frames"]), 2), np.int64) for a in annos]
-        shared = preload_offset <= 0
-        todo = []                                 # (path, n, bounds (k,6), [[(tracklet, frame index)] per box])
-        for file, who in zip(files, users):
-            full = os.path.join(path, file)
-            if shared:
-                todo.append((full, nuscenes_rows(full), preload_bounds(np.zeros((1, 15)), preload_offset), [who]))
-            else:
-                todo.append((full, nuscenes_rows(full), preload_bounds(np.stack([annos[k]["boxes"][t] for k, t in who]), preload_offset),
-                             [[u] for u in who]))
-        segments, base, pinned, i = [], 0, None, 0
-        with torch.cuda.device(dev):
-            while i < len(todo):
-                # a chunk: at most chunk_frames sweeps, PRELOAD_MAX_FRAMES records and PRELOAD_MAX_ROWS raw rows
-                j, nrows, nrec = i, 0, 0
-                while j < len(todo) and j - i < chunk_frames:
-                    rec = max(1, -(-len(todo[j][2]) // PU.PRELOAD_MAX_BOXES))
-                    if j > i and (nrows + todo[j][1] > PU.PRELOAD_MAX_ROWS or nrec + rec > PU.PRELOAD_MAX_FRAMES):
-                        break
-                    nrows, nrec, j = nrows + todo[j][1], nrec + rec, j + 1
-                chunk = PreloadChunk([(t[0], t[1]) for t in todo[i:j]], [t[2] for t in todo[i:j]], None, dev, pinned, row_floats=5,
-                                     steps=steps[i:j], translate32=int(translate == "float32"))
-                counts = chunk.run()
-                pinned, b = chunk.pinned, 0
-                for t in todo[i:j]:
-                    for who in t[3]:
-                        for k, f in who:
-                            rows[k][f] = (base + chunk.first[b], counts[b])
-                        b += 1
-                segments.append(chunk.pool)
-                base += int(chunk.first[-1])
-                i = j
-            segments.append(torch.zeros((0, 3), dtype=torch.float32, device=dev))
-            pool = segments[0] if len(segments) == 1 else torch.cat(segments)
-        self._assemble(pool, rows, [a["boxes"] for a in annos], [(a["key"], a["files"]) for a in annos])
-
-    def get_frames(self, seq_id, frame_ids):
-        t, (key, files) = self[seq_id], self.meta[seq_id]
-        return [{"pc": t.frames[f], "3d_bbox": t.boxes[f], "meta": (key, files[f])} for f in frame_ids]
-
-    # ---- the cache ----------------------------------------------------------------------------------------------------------
-    def save(self, file):
-        """one file: the pool, the row offsets, the boxes (fp64) and the meta"""
-        lengths = np.array([len(t) for t in self], np.int64)
-        cat = lambda xs, shape, dt: np.concatenate(list(xs) + [np.zeros(shape, dt)])      # noqa: E731
-        arrays = dict(pool=self.pool.cpu().numpy(), lengths=lengths, rows=cat(self.rows, (0, 2), np.int64),
-                      boxes=cat(self.boxes64, (0, 15), np.float64), keys=np.array([m[0] for m in self.meta], dtype=np.str_),
-                      files=np.array([f for m in self.meta for f in m[1]], dtype=np.str_),
-                      info=np.array([self.split, self.category_name, self.version, self.translate, repr(self.preload_offset),
-                                     repr(self.key_frame_only), repr(self.min_points)]))
-        with open(file, "wb") as f:
-            np.savez(f, **arrays)
-
-    @classmethod
-    def load(cls, file, device=None):
-        """the tracklets that save(file) wrote: one upload, the frames are views of the pool again"""
-        dev = _device(device, "NuScenesTracklets")
-        self = cls.__new__(cls)
-        DeviceTracklets.__init__(self)
-        with np.load(file) as z:
-            ends = np.cumsum(z["lengths"])
-            cut = lambda a: np.split(a, ends[:-1]) if len(ends) else []      # noqa: E731
-            self.split, self.category_name, self.version, self.translate = (str(s) for s in z["info"][:4])
-            self.preload_offset, self.key_frame_only, self.min_points = (ast.literal_eval(str(s)) for s in z["info"][4:7])
-            self.path = None
-            meta = [(str(k), [str(f) for f in fs]) for k, fs in zip(z["keys"], cut(z["files"]))]
-            self._assemble(torch.from_numpy(z["pool"]).to(dev), cut(z["rows"]), cut(z["boxes"]), meta)
-        return self
+        self._preload(dev, annos, [(a["key"], a["files"]) for a in annos], nuscenes_items(path, annos, files, steps, preload_offset),
+                      chunk_frames, translate32=int(translate == "float32"))

@@ -768,7 +768,7 @@ PRELOAD_COLS = 6      # a frame record: first raw row, n, first box, number of b
 
 
 def preload_plan(frames, raw_rows):
-    """The host planner of o3d_preload_count / o3d_preload_scatter (no device call): frames (F,6) int32 with columns 0 (first
+    """The host planner of preload_count / preload_scatter (no device call): frames (F,6) int32 with columns 0 (first
     raw row), 1 (n) and 3 (number of boxes) set; fills columns 2, 4 and 5 in place -> (scratch length in int32, workgroups of
     the count / scatter launches, B).  Raises O3DError on a bad table."""
     assert frames.dtype == np.int32 and frames.ndim == 2 and frames.shape[1] == PRELOAD_COLS and frames.flags.c_contiguous
@@ -804,43 +804,47 @@ def _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses
     return transform
 
 
+_PRELOAD_ENTRIES = {"count": ("o3d_preload_count", "o3d_preload_posed_count", "o3d_preload_steps_count"),
+                    "scatter": ("o3d_preload_scatter", "o3d_preload_posed_scatter", "o3d_preload_steps_scatter")}
+
+
+def _preload_entry(which, raw, transform, poses, steps, translate32):
+    """what tells the three pairs of entry points apart -> (name, the arguments between raw's rows and the frame table, the
+    arguments between B and the scratch): the plain pair takes a host transform | NULL, the posed and the steps pair the
+    floats of a raw row and their per-record table"""
+    plain, posed, stepped = _PRELOAD_ENTRIES[which]
+    if steps is not None:
+        return stepped, (raw.shape[1],), (steps.data_ptr(), steps.shape[1], int(translate32))
+    if poses is not None:
+        return posed, (raw.shape[1],), (poses.data_ptr(),)
+    return plain, (), (None if transform is None else transform.ctypes.data,)
+
+
 def preload_count(raw, frames, dev_frames, bounds, transform, scratch, counts, poses=None, steps=None, translate32=0):
-    """One o3d_preload_count call (two launches, no sync): raw (rows,4) float32 GPU, frames = the planned (F,6) int32 table on
-    the host and dev_frames its GPU copy, bounds (B,6) float32 GPU, transform = (3,4) float64 on the host | None, scratch =
-    an int32 GPU tensor of at least preload_plan's length -> counts (B,) int32 GPU, written in place.
-    poses = (F,12) float64 GPU, one transform per frame record: o3d_preload_posed_count instead, raw (rows, 3 | 4), transform
+    """One count call (two launches, no sync): raw (rows,4) float32 GPU, frames = the planned (F,6) int32 table on the host and
+    dev_frames its GPU copy, bounds (B,6) float32 GPU, transform = (3,4) float64 on the host | None, scratch = an int32 GPU
+    tensor of at least preload_plan's length -> counts (B,) int32 GPU, written in place.
+    poses = (F,12) float64 GPU, one transform per frame record: the posed entry point instead, raw (rows, 3 | 4), transform
     None.  steps = (F,n_steps,12) float64 GPU, a chain of rounded rigid steps per frame record, translate32 = 0 (the translation
-    is added in fp64 and rounded) | 1 (added in fp32): o3d_preload_steps_count instead, raw (rows, 3 | 4 | 5), transform and
+    is added in fp64 and rounded) | 1 (added in fp32): the steps entry point instead, raw (rows, 3 | 4 | 5), transform and
     poses None"""
     transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses, steps, translate32)
     _need_gpu(counts, "preload_count")
     B = bounds.numel() // 6
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= B
+    name, width, how = _preload_entry("count", raw, transform, poses, steps, translate32)
     dev = raw.device
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if steps is not None:
-            capi.check(capi.load().o3d_preload_steps_count(
-                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
-                B, steps.data_ptr(), steps.shape[1], int(translate32), scratch.data_ptr(), scratch.numel(), counts.data_ptr(), stream),
-                "o3d_preload_steps_count")
-            return
-        if poses is not None:
-            capi.check(capi.load().o3d_preload_posed_count(
-                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
-                B, poses.data_ptr(), scratch.data_ptr(), scratch.numel(), counts.data_ptr(), stream), "o3d_preload_posed_count")
-            return
-        capi.check(capi.load().o3d_preload_count(
-            raw.data_ptr(), raw.shape[0], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
-            None if transform is None else transform.ctypes.data, scratch.data_ptr(), scratch.numel(), counts.data_ptr(),
-            stream), "o3d_preload_count")
+        capi.check(getattr(capi.load(), name)(
+            raw.data_ptr(), raw.shape[0], *width, frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
+            *how, scratch.data_ptr(), scratch.numel(), counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), name)
 
 
 def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row, pool, pool_rows=None, poses=None, steps=None,
                     translate32=0):
-    """One o3d_preload_scatter launch after preload_count on the same operands: out_row (B,) int64 GPU = the first pool row of
-    every box, pool (rows,3) float32 GPU, written in place; no row at or beyond pool_rows (default: all of pool) is written.
-    poses: as for preload_count (o3d_preload_posed_scatter); steps, translate32: as for preload_count (o3d_preload_steps_scatter)"""
+    """One scatter launch after preload_count on the same operands: out_row (B,) int64 GPU = the first pool row of every box,
+    pool (rows,3) float32 GPU, written in place; no row at or beyond pool_rows (default: all of pool) is written.
+    poses, steps, translate32: as for preload_count (the posed / the steps entry point)"""
     transform = _preload_operands(raw, frames, dev_frames, bounds, transform, scratch, poses, steps, translate32)
     _need_gpu(out_row, "preload_scatter")
     _need_gpu(pool, "preload_scatter")
@@ -849,25 +853,13 @@ def preload_scatter(raw, frames, dev_frames, bounds, transform, scratch, out_row
     assert pool.dtype == torch.float32 and pool.is_contiguous() and pool.dim() == 2 and pool.shape[1] == 3
     pool_rows = pool.shape[0] if pool_rows is None else int(pool_rows)
     assert 0 <= pool_rows <= pool.shape[0]
+    name, width, how = _preload_entry("scatter", raw, transform, poses, steps, translate32)
     dev = raw.device
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if steps is not None:
-            capi.check(capi.load().o3d_preload_steps_scatter(
-                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
-                B, steps.data_ptr(), steps.shape[1], int(translate32), scratch.data_ptr(), scratch.numel(), out_row.data_ptr(),
-                pool.data_ptr(), pool_rows, stream), "o3d_preload_steps_scatter")
-            return
-        if poses is not None:
-            capi.check(capi.load().o3d_preload_posed_scatter(
-                raw.data_ptr(), raw.shape[0], raw.shape[1], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(),
-                B, poses.data_ptr(), scratch.data_ptr(), scratch.numel(), out_row.data_ptr(), pool.data_ptr(), pool_rows, stream),
-                "o3d_preload_posed_scatter")
-            return
-        capi.check(capi.load().o3d_preload_scatter(
-            raw.data_ptr(), raw.shape[0], frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
-            None if transform is None else transform.ctypes.data, scratch.data_ptr(), scratch.numel(), out_row.data_ptr(),
-            pool.data_ptr(), pool_rows, stream), "o3d_preload_scatter")
+        capi.check(getattr(capi.load(), name)(
+            raw.data_ptr(), raw.shape[0], *width, frames.ctypes.data, dev_frames.data_ptr(), frames.shape[0], bounds.data_ptr(), B,
+            *how, scratch.data_ptr(), scratch.numel(), out_row.data_ptr(), pool.data_ptr(), pool_rows,
+            torch.cuda.current_stream(dev).cuda_stream), name)
 
 
 def train_select(counts, B, caps, sel, n_valid, overflow):

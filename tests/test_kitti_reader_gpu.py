@@ -165,6 +165,8 @@ def test_cache_round_trip(dev, ref, tree, tmp_path):
     file = str(tmp_path / "cache.dat")
     a.save(file)
     assert os.path.exists(file)                              # the name as given
+    with np.load(file) as z:
+        assert sorted(z.files) == ["boxes", "frames", "info", "lengths", "pool", "rows", "scene_list", "scenes", "track_ids"]
     b = D.KittiTracklets.load(file, device=dev)
     check_against_ref(b, ref, name)
     assert (b.split, b.category_name, b.coordinate_mode, b.preload_offset) == ("traintiny", "Other", "camera", 10)

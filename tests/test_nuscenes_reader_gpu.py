@@ -343,6 +343,8 @@ def test_cache_round_trip(dev, ref, tree, tmp_path):
     file = str(tmp_path / "cache.dat")
     a.save(file)
     assert os.path.exists(file)                              # the name as given
+    with np.load(file) as z:
+        assert sorted(z.files) == ["boxes", "files", "info", "keys", "lengths", "pool", "rows"]
     b = D.NuScenesTracklets.load(file, device=dev)
     check_against(b, ref_clouds(ref, name), ref, name)
     assert (b.split, b.category_name, b.version, b.translate) == ("train", "Pedestrian", V, "float64")

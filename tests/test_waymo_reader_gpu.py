@@ -294,6 +294,8 @@ def test_cache_round_trip(dev, ref, tree, tmp_path):
     file = str(tmp_path / "cache.dat")
     a.save(file)
     assert os.path.exists(file)                              # the name as given
+    with np.load(file) as z:
+        assert sorted(z.files) == ["boxes", "files", "info", "keys", "lengths", "pool", "rows"]
     b = D.WaymoTracklets.load(file, device=dev)
     check_against_ref(b, ref, name, tree)
     assert (b.split, b.category_name, b.preload_offset, b.tiny) == ("train", "pedestrian", 10, False)

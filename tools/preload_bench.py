@@ -10,6 +10,9 @@ frame.  Every file is read once before anything is timed, so all timings are fro
 of `--runs` runs with the smallest and the largest, one JSON line at the end:
   reader_s            KittiTracklets(...) end to end (host clock, ends in a device synchronise): parse, read, upload, crop
   read_s              the host's file reads into the pinned buffer (host clock), summed over the chunks
+  (read_s .. scatter_ms are the reader's own chunks run stage by stage: the reader's items -- datasets.kitti_items,
+   waymo_items, nuscenes_items -- cut by datasets.preload_chunks, the one cut rule, and made into PreloadChunks by the
+   reader class; `chunks` is their number)
   upload_ms           the raw frames and the tables, host to device (HIP events)
   count_ms, scatter_ms  the count + scan launches and the scatter launch (HIP events); launch_GBps = the bytes the three
                       launches must move (the raw rows twice, the pool rows once) over count_ms + scatter_ms
@@ -20,8 +23,8 @@ The clouds of the restatement and of the reader are compared bit for bit before 
 
 --dataset waymo: the tree is `--scenes` sequences of `--frames` lidar and annotation pickles ((n,3) float32 points, a pose of
 kilometres per frame), `--tracklets` VEHICLE objects per sequence annotated in every frame; the reader is WaymoTracklets, the
-launches are the posed pair (a pose per frame record, rows of three floats), and read_s is the unpickling plus the copy
-into the pinned buffer (the bounds and the plan are outside it, as for KITTI).  The yardstick transforms with numpy's `dot`, as the reference does; the bit-for-bit comparison is
+launches are the posed pair (a pose per frame record, rows of three floats), and read_s is the pull of the items, which
+unpickles, plus the copy into the pinned buffer (the bounds and the plan are outside it, as for KITTI).  The yardstick transforms with numpy's `dot`, as the reference does; the bit-for-bit comparison is
 against the same restatement with the ordered fp64 sum (BLAS may sum in another order, which reaches a float32 coordinate only
 at a rounding boundary), and `dot_clouds_differing` counts the clouds where the two restatements differ.
 
@@ -41,6 +44,7 @@ import statistics
 import sys
 import tempfile
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -77,11 +81,24 @@ def write_tree(root, scenes, frames, points, tracklets, seed=0):
     return "test" if scenes == 2 else "testtiny"
 
 
+SIGNS = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
+
+
+def crop(pc, box, offset):
+    """the reference's axis-aligned preload crop of a (3,n) float32 cloud: strictly inside the box's corners -+ offset, the
+    float32 coordinates against fp64 bounds; offset <= 0: the cloud itself"""
+    if offset <= 0:
+        return pc
+    w, l, h = box[3:6]
+    corners = box[6:15].reshape(3, 3) @ (SIGNS * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
+    hi, lo = corners.max(1) + offset, corners.min(1) - offset
+    return pc[:, (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])]
+
+
 def host_preload(D, root, split, mode, offset):
     """the host preload in numpy: -> a list (per tracklet) of lists of (n,3) float32"""
     annos, calibs = D.kitti_annotations(root, split, "Car", mode)
     cache, out = {}, []
-    signs = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
     for a in annos:
         clouds = []
         for frame, box in zip(a["frames"], a["boxes"]):
@@ -92,14 +109,7 @@ def host_preload(D, root, split, mode, offset):
                     pc = pc.copy()
                     pc[:3] = calibs[key[0]].dot(np.vstack((pc, np.ones(pc.shape[1]))))[:3]
                 cache[key] = pc
-            pc = cache[key]
-            if offset > 0:
-                w, l, h = box[3:6]
-                corners = box[6:15].reshape(3, 3) @ (signs * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
-                hi, lo = corners.max(1) + offset, corners.min(1) - offset
-                keep = (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])
-                pc = pc[:, keep]
-            clouds.append(pc)
+            clouds.append(crop(cache[key], box, offset))
         out.append(clouds)
     return out
 
@@ -139,7 +149,6 @@ def host_preload_waymo(D, root, split, offset, ordered=False):
     """the host preload of WaymoDataset in numpy: -> a list (per tracklet) of lists of (3,n) float32"""
     annos, files, poses = D.waymo_annotations(root, split, "VEHICLE")
     cache, out = {}, []
-    signs = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
     for a in annos:
         clouds = []
         for f, box in zip(a["frames"], a["boxes"]):
@@ -153,94 +162,9 @@ def host_preload_waymo(D, root, split, offset, ordered=False):
                 else:
                     pc[:3] = poses[f].dot(np.vstack((pc, np.ones(pc.shape[1]))))
                 cache[f] = pc
-            pc = cache[f]
-            if offset > 0:
-                w, l, h = box[3:6]
-                corners = box[6:15].reshape(3, 3) @ (signs * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
-                hi, lo = corners.max(1) + offset, corners.min(1) - offset
-                keep = (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])
-                pc = pc[:, keep]
-            clouds.append(pc)
+            clouds.append(crop(cache[f], box, offset))
         out.append(clouds)
     return out
-
-
-def main_waymo(args, torch, D):
-    with tempfile.TemporaryDirectory() as root:
-        split = write_waymo_tree(D, root, args.scenes, args.frames, args.points, args.tracklets)
-        host = host_preload_waymo(D, root, split, args.offset, ordered=True)       # reads every file once: the page cache is warm
-        by_dot = host_preload_waymo(D, root, split, args.offset)
-        differing = sum(a.tobytes() != b.tobytes() for x, y in zip(host, by_dot) for a, b in zip(x, y))
-        del by_dot
-        host_s = []
-        for _ in range(args.runs):
-            t0 = time.perf_counter()
-            host_preload_waymo(D, root, split, args.offset)
-            host_s.append(time.perf_counter() - t0)
-        res = {"tool": "preload_bench", "dataset": "waymo", "scenes": args.scenes, "frames": args.frames, "points": args.points,
-               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, "crops": sum(len(c) for c in host),
-               "dot_clouds_differing": differing, "host_numpy_s": stat(host_s)}
-        if args.host_only:
-            print(json.dumps(res))
-            return
-        dev = torch.device("cuda", 0)
-        kw = dict(category_name="VEHICLE", preload_offset=args.offset, device=dev, chunk_frames=args.chunk_frames)
-        trk = D.WaymoTracklets(root, split, **kw)                           # warm-up: code objects, the allocator, pinned memory
-        torch.cuda.synchronize(dev)
-        for t, h in zip(trk, host):                                         # faster and different is not faster
-            for g, c in zip(t.frames, h):
-                c = np.ascontiguousarray(c.T, np.float32)
-                assert tuple(g.shape) == c.shape and np.array_equal(g.cpu().numpy().view(np.int32), c.view(np.int32))
-        reader_s = []
-        for _ in range(args.runs):
-            t0 = time.perf_counter()
-            trk = D.WaymoTracklets(root, split, **kw)
-            torch.cuda.synchronize(dev)
-            reader_s.append(time.perf_counter() - t0)
-        # the split: the same chunks, step by step
-        annos, files, poses = D.waymo_annotations(root, split, "VEHICLE")
-        per_file = [[] for _ in files]
-        for a in annos:
-            for f, box in zip(a["frames"], a["boxes"]):
-                per_file[f].append(box)
-        chunks = [range(i, min(i + args.chunk_frames, len(files))) for i in range(0, len(files), args.chunk_frames)]
-        read_s, upload_ms, count_ms, scatter_ms, raw_bytes, pool_bytes = [], [], [], [], 0, 0
-        ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
-        for run in range(args.runs + 1):                                    # run 0 warms up
-            tot = {"read": 0.0, "upload": 0.0, "count": 0.0, "scatter": 0.0}
-            raw_bytes = pool_bytes = 0
-            pinned = None
-            for ck in chunks:
-                bounds = [D.preload_bounds(np.stack(per_file[f]), args.offset) for f in ck]
-                t0 = time.perf_counter()
-                rows = [D.waymo_points(files[f]) for f in ck]               # the file reads: unpickling ...
-                tot["read"] += time.perf_counter() - t0
-                c = D.PreloadChunk([(r, r.shape[0]) for r in rows], bounds, None, dev, pinned, row_floats=3, poses=poses[ck.start:ck.stop])
-                pinned = c.pinned
-                t0 = time.perf_counter()
-                c.read()                                                    # ... and the copy into the pinned buffer
-                tot["read"] += time.perf_counter() - t0
-                e = [ev() for _ in range(5)]
-                with torch.cuda.device(dev):
-                    e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
-                    c.read_back()
-                    e[3].record(); c.scatter(); e[4].record()
-                torch.cuda.synchronize(dev)
-                tot["upload"] += e[0].elapsed_time(e[1])
-                tot["count"] += e[1].elapsed_time(e[2])
-                tot["scatter"] += e[3].elapsed_time(e[4])
-                raw_bytes += 12 * c.raw_rows
-                pool_bytes += 12 * c.pool.shape[0]
-            if run:
-                read_s.append(tot["read"]); upload_ms.append(tot["upload"]); count_ms.append(tot["count"]); scatter_ms.append(tot["scatter"])
-        launch_ms = [a + b for a, b in zip(count_ms, scatter_ms)]
-        moved = 2 * raw_bytes + pool_bytes
-        res.update(reader_s=stat(reader_s), read_s=stat(read_s), upload_ms=stat(upload_ms), count_ms=stat(count_ms),
-                   scatter_ms=stat(scatter_ms), raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
-                   launch_GBps=stat([moved / (ms * 1e-3) / 1e9 for ms in launch_ms]),
-                   upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in upload_ms]), chunks=len(chunks),
-                   host_over_reader=statistics.median(host_s) / statistics.median(reader_s))
-        print(json.dumps(res))
 
 
 def write_nuscenes_tree(root, scenes, frames, points, tracklets, version, seed=0):
@@ -301,7 +225,6 @@ def host_preload_nuscenes(D, root, version, splits, offset, ordered=False):
     """the host preload of NuScenesDataset in numpy: -> a list (per tracklet) of lists of (3,n) float32"""
     annos, files, steps = D.nuscenes_annotations(root, "train", "Car", version, scenes=splits)
     cache, out = {}, []
-    signs = np.array([[1, 1, 1, 1, -1, -1, -1, -1], [1, -1, -1, 1, 1, -1, -1, 1], [1, 1, -1, -1, 1, 1, -1, -1]], np.float64)
     for a in annos:
         clouds = []
         for f, box in zip(a["frames"], a["boxes"]):
@@ -317,99 +240,97 @@ def host_preload_nuscenes(D, root, version, splits, offset, ordered=False):
                     for i in range(3):
                         pc[i] = pc[i] + M[i, 3]                               # an np.float64 scalar: fp64 under numpy >= 2
                 cache[f] = pc
-            pc = cache[f]
-            if offset > 0:
-                w, l, h = box[3:6]
-                corners = box[6:15].reshape(3, 3) @ (signs * np.array([[l / 2], [w / 2], [h / 2]])) + box[0:3, None]
-                hi, lo = corners.max(1) + offset, corners.min(1) - offset
-                keep = (pc[0] < hi[0]) & (pc[0] > lo[0]) & (pc[1] < hi[1]) & (pc[1] > lo[1]) & (pc[2] < hi[2]) & (pc[2] > lo[2])
-                pc = pc[:, keep]
-            clouds.append(pc)
+            clouds.append(crop(cache[f], box, offset))
         out.append(clouds)
     return out
 
 
-def main_nuscenes(args, torch, D):
-    version = "v1.0-trainval"
-    assert int(np.__version__.split(".")[0]) >= 2, "the yardstick's translate is numpy's: the reader's default mode is that of numpy >= 2"
-    with tempfile.TemporaryDirectory() as root:
-        splits = write_nuscenes_tree(root, args.scenes, args.frames, args.points, args.tracklets, version)
-        host = host_preload_nuscenes(D, root, version, splits, args.offset, ordered=True)      # reads every file once: the page cache is warm
-        by_dot = host_preload_nuscenes(D, root, version, splits, args.offset)
-        differing = sum(a.tobytes() != b.tobytes() for x, y in zip(host, by_dot) for a, b in zip(x, y))
-        del by_dot
-        host_s = []
-        for _ in range(args.runs):
-            t0 = time.perf_counter()
-            host_preload_nuscenes(D, root, version, splits, args.offset)
-            host_s.append(time.perf_counter() - t0)
-        res = {"tool": "preload_bench", "dataset": "nuscenes", "scenes": args.scenes, "frames": args.frames, "points": args.points,
-               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, "crops": sum(len(c) for c in host),
-               "dot_clouds_differing": differing, "host_numpy_s": stat(host_s)}
-        if args.host_only:
-            print(json.dumps(res))
-            return
-        dev = torch.device("cuda", 0)
-        kw = dict(category_name="Car", version=version, preload_offset=args.offset, scenes=splits, device=dev, chunk_frames=args.chunk_frames)
-        trk = D.NuScenesTracklets(root, "train", **kw)                      # warm-up: code objects, the allocator, pinned memory
-        torch.cuda.synchronize(dev)
-        for t, h in zip(trk, host):                                         # faster and different is not faster
-            for g, c in zip(t.frames, h):
-                c = np.ascontiguousarray(c.T, np.float32)
-                assert tuple(g.shape) == c.shape and np.array_equal(g.cpu().numpy().view(np.int32), c.view(np.int32))
-        reader_s = []
-        for _ in range(args.runs):
-            t0 = time.perf_counter()
-            trk = D.NuScenesTracklets(root, "train", **kw)
-            torch.cuda.synchronize(dev)
-            reader_s.append(time.perf_counter() - t0)
-        # the split: the same chunks, step by step
-        annos, files, steps = D.nuscenes_annotations(root, "train", "Car", version, scenes=splits)
-        per_file = [[] for _ in files]
-        for a in annos:
-            for f, box in zip(a["frames"], a["boxes"]):
-                per_file[f].append(box)
-        chunks = [range(i, min(i + args.chunk_frames, len(files))) for i in range(0, len(files), args.chunk_frames)]
-        read_s, upload_ms, count_ms, scatter_ms, raw_bytes, read_bytes, pool_bytes = [], [], [], [], 0, 0, 0
-        ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
-        for run in range(args.runs + 1):                                    # run 0 warms up
-            tot = {"read": 0.0, "upload": 0.0, "count": 0.0, "scatter": 0.0}
-            raw_bytes = read_bytes = pool_bytes = 0
-            pinned = None
-            for ck in chunks:
-                bounds = [D.preload_bounds(np.stack(per_file[f]), args.offset) for f in ck]
-                paths = [os.path.join(root, files[f]) for f in ck]
-                c = D.PreloadChunk([(p, D.nuscenes_rows(p)) for p in paths], bounds, None, dev, pinned, row_floats=5, steps=steps[ck.start:ck.stop])
-                pinned = c.pinned
-                t0 = time.perf_counter()
-                c.read()
-                tot["read"] += time.perf_counter() - t0
-                e = [ev() for _ in range(5)]
-                with torch.cuda.device(dev):
-                    e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
-                    c.read_back()
-                    e[3].record(); c.scatter(); e[4].record()
-                torch.cuda.synchronize(dev)
-                tot["upload"] += e[0].elapsed_time(e[1])
-                tot["count"] += e[1].elapsed_time(e[2])
-                tot["scatter"] += e[3].elapsed_time(e[4])
-                raw_bytes += 20 * c.raw_rows
-                read_bytes += 12 * c.raw_rows
-                pool_bytes += 12 * c.pool.shape[0]
-            if run:
-                read_s.append(tot["read"]); upload_ms.append(tot["upload"]); count_ms.append(tot["count"]); scatter_ms.append(tot["scatter"])
-        launch_ms = [a + b for a, b in zip(count_ms, scatter_ms)]
-        moved = 2 * read_bytes + pool_bytes
-        res.update(reader_s=stat(reader_s), read_s=stat(read_s), upload_ms=stat(upload_ms), count_ms=stat(count_ms),
-                   scatter_ms=stat(scatter_ms), raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
-                   launch_GBps=stat([moved / (ms * 1e-3) / 1e9 for ms in launch_ms]),
-                   upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in upload_ms]), chunks=len(chunks),
-                   host_over_reader=statistics.median(host_s) / statistics.median(reader_s))
-        print(json.dumps(res))
-
-
 def stat(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": len(xs)}
+
+
+def timed_pulls(items, tot):
+    """`items`, with the time of every pull added to tot["read"]: a Waymo item unpickles its lidar file when it is pulled"""
+    it = iter(items)
+    while True:
+        t0 = time.perf_counter()
+        item = next(it, None)
+        tot["read"] += time.perf_counter() - t0
+        if item is None:
+            return
+        yield item
+
+
+def staged(torch, D, reader, dev, items, args, raw_row_bytes, read_row_bytes):
+    """The reader's own chunks (D.preload_chunks over the reader's items, made into PreloadChunks by the reader class), stage by
+    stage -> the timing fields.  items() gives the items afresh for a run; a raw row is raw_row_bytes in the upload and
+    read_row_bytes of it are what a launch asks for"""
+    cols = {"read": [], "upload": [], "count": [], "scatter": []}
+    for run in range(args.runs + 1):                                        # run 0 warms up
+        tot = dict.fromkeys(cols, 0.0)
+        raw_rows = pool_rows = chunks = 0
+        pinned = None
+        for ck in D.preload_chunks(timed_pulls(items(), tot), args.chunk_frames):
+            c = reader.preload_chunk(ck, dev, pinned)
+            pinned = c.pinned
+            t0 = time.perf_counter()
+            c.read()
+            tot["read"] += time.perf_counter() - t0
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            with torch.cuda.device(dev):
+                e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
+                c.read_back()
+                e[3].record(); c.scatter(); e[4].record()
+            torch.cuda.synchronize(dev)
+            tot["upload"] += e[0].elapsed_time(e[1])
+            tot["count"] += e[1].elapsed_time(e[2])
+            tot["scatter"] += e[3].elapsed_time(e[4])
+            raw_rows, pool_rows, chunks = raw_rows + c.raw_rows, pool_rows + c.pool.shape[0], chunks + 1
+        if run:
+            for k in cols:
+                cols[k].append(tot[k])
+    raw_bytes, pool_bytes = raw_row_bytes * raw_rows, 12 * pool_rows
+    moved = 2 * read_row_bytes * raw_rows + pool_bytes
+    return dict(read_s=stat(cols["read"]), upload_ms=stat(cols["upload"]), count_ms=stat(cols["count"]), scatter_ms=stat(cols["scatter"]),
+                raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
+                launch_GBps=stat([moved / ((a + b) * 1e-3) / 1e9 for a, b in zip(cols["count"], cols["scatter"])]),
+                upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in cols["upload"]]), chunks=chunks)
+
+
+# per dataset: (args, D, root) -> what the JSON line says of the setup beyond the sizes (head, mid), host(ordered) the numpy
+# restatement (ordered=True: the fp64 sums in the device's order, what the clouds are compared against; by_dot: whether
+# ordered=False is another restatement), make(device) the reader, items() its PreloadItems, row_bytes = the bytes of a raw
+# row (uploaded, asked for by a launch)
+def setup_kitti(args, D, root):
+    split = write_tree(root, args.scenes, args.frames, args.points, args.tracklets)
+    kw = dict(category_name="Car", coordinate_mode=args.mode, preload_offset=args.offset, chunk_frames=args.chunk_frames)
+    annos, calibs = D.kitti_annotations(root, split, "Car", args.mode)
+    return SimpleNamespace(head={}, mid={"mode": args.mode}, by_dot=False, row_bytes=(16, 16),
+                           host=lambda ordered=False: host_preload(D, root, split, args.mode, args.offset),
+                           make=lambda dev: D.KittiTracklets(root, split, device=dev, **kw),
+                           items=lambda: D.kitti_items(root, annos, calibs, args.mode, args.offset)[0])
+
+
+def setup_waymo(args, D, root):
+    split = write_waymo_tree(D, root, args.scenes, args.frames, args.points, args.tracklets)
+    kw = dict(category_name="VEHICLE", preload_offset=args.offset, chunk_frames=args.chunk_frames)
+    annos, files, poses = D.waymo_annotations(root, split, "VEHICLE")
+    return SimpleNamespace(head={"dataset": "waymo"}, mid={}, by_dot=True, row_bytes=(12, 12),
+                           host=lambda ordered=False: host_preload_waymo(D, root, split, args.offset, ordered),
+                           make=lambda dev: D.WaymoTracklets(root, split, device=dev, **kw),
+                           items=lambda: D.waymo_items(annos, files, poses, args.offset))
+
+
+def setup_nuscenes(args, D, root):
+    version = "v1.0-trainval"
+    assert int(np.__version__.split(".")[0]) >= 2, "the yardstick's translate is numpy's: the reader's default mode is that of numpy >= 2"
+    splits = write_nuscenes_tree(root, args.scenes, args.frames, args.points, args.tracklets, version)
+    kw = dict(category_name="Car", version=version, preload_offset=args.offset, scenes=splits, chunk_frames=args.chunk_frames)
+    annos, files, steps = D.nuscenes_annotations(root, "train", "Car", version, scenes=splits)
+    return SimpleNamespace(head={"dataset": "nuscenes"}, mid={}, by_dot=True, row_bytes=(20, 12),
+                           host=lambda ordered=False: host_preload_nuscenes(D, root, version, splits, args.offset, ordered),
+                           make=lambda dev: D.NuScenesTracklets(root, "train", device=dev, **kw),
+                           items=lambda: D.nuscenes_items(root, annos, files, steps, args.offset))
 
 
 def main():
@@ -427,27 +348,25 @@ def main():
     from open3dsot_amd import datasets as D
     if not args.host_only and not torch.cuda.is_available():
         raise SystemExit("preload_bench needs a GPU: the reader cannot be measured on the host")
-    if args.dataset == "waymo":
-        return main_waymo(args, torch, D)
-    if args.dataset == "nuscenes":
-        return main_nuscenes(args, torch, D)
+    setup = {"kitti": setup_kitti, "waymo": setup_waymo, "nuscenes": setup_nuscenes}[args.dataset]
     with tempfile.TemporaryDirectory() as root:
-        split = write_tree(root, args.scenes, args.frames, args.points, args.tracklets)
-        host = host_preload(D, root, split, args.mode, args.offset)          # reads every file once: the page cache is warm
+        s = setup(args, D, root)
+        host = s.host(ordered=True)                                         # reads every file once: the page cache is warm
+        res = {"tool": "preload_bench", **s.head, "scenes": args.scenes, "frames": args.frames, "points": args.points,
+               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, **s.mid, "crops": sum(len(c) for c in host)}
+        if s.by_dot:
+            res["dot_clouds_differing"] = sum(a.tobytes() != b.tobytes() for x, y in zip(host, s.host()) for a, b in zip(x, y))
         host_s = []
         for _ in range(args.runs):
             t0 = time.perf_counter()
-            host_preload(D, root, split, args.mode, args.offset)
+            s.host()
             host_s.append(time.perf_counter() - t0)
-        res = {"tool": "preload_bench", "scenes": args.scenes, "frames": args.frames, "points": args.points,
-               "tracklets_per_scene": args.tracklets, "preload_offset": args.offset, "mode": args.mode,
-               "crops": sum(len(c) for c in host), "host_numpy_s": stat(host_s)}
+        res["host_numpy_s"] = stat(host_s)
         if args.host_only:
             print(json.dumps(res))
             return
         dev = torch.device("cuda", 0)
-        kw = dict(category_name="Car", coordinate_mode=args.mode, preload_offset=args.offset, device=dev, chunk_frames=args.chunk_frames)
-        trk = D.KittiTracklets(root, split, **kw)                           # warm-up: code objects, the allocator, pinned memory
+        trk = s.make(dev)                                                   # warm-up: code objects, the allocator, pinned memory
         torch.cuda.synchronize(dev)
         for t, h in zip(trk, host):                                         # faster and different is not faster
             for g, c in zip(t.frames, h):
@@ -456,59 +375,10 @@ def main():
         reader_s = []
         for _ in range(args.runs):
             t0 = time.perf_counter()
-            trk = D.KittiTracklets(root, split, **kw)
+            trk = s.make(dev)
             torch.cuda.synchronize(dev)
             reader_s.append(time.perf_counter() - t0)
-        # the split: the same chunks, step by step
-        annos, calibs = D.kitti_annotations(root, split, "Car", args.mode)
-        per_frame = {}
-        for a in annos:
-            for frame, box in zip(a["frames"], a["boxes"]):
-                per_frame.setdefault((a["scene"], int(frame)), []).append(box)
-        keys = list(per_frame)
-        chunks = []
-        i = 0
-        while i < len(keys):
-            j = i
-            while j < len(keys) and j - i < args.chunk_frames and keys[j][0] == keys[i][0]:
-                j += 1
-            chunks.append(keys[i:j])
-            i = j
-        read_s, upload_ms, count_ms, scatter_ms, raw_bytes, pool_bytes = [], [], [], [], 0, 0
-        ev = lambda: torch.cuda.Event(enable_timing=True)      # noqa: E731
-        for run in range(args.runs + 1):                                    # run 0 warms up
-            tot = {"read": 0.0, "upload": 0.0, "count": 0.0, "scatter": 0.0}
-            raw_bytes = pool_bytes = 0
-            pinned = None
-            for ck in chunks:
-                files = [(os.path.join(root, "velodyne", s, "%06d.bin" % f), D.velodyne_rows(os.path.join(root, "velodyne", s, "%06d.bin" % f)))
-                         for s, f in ck]
-                bounds = [D.preload_bounds(np.stack(per_frame[k]), args.offset) for k in ck]
-                T = np.ascontiguousarray(calibs[ck[0][0]][:3]) if args.mode == "camera" else None
-                c = D.PreloadChunk(files, bounds, T, dev, pinned)
-                pinned = c.pinned
-                t0 = time.perf_counter()
-                c.read()
-                tot["read"] += time.perf_counter() - t0
-                e = [ev() for _ in range(5)]
-                with torch.cuda.device(dev):
-                    e[0].record(); c.upload(); e[1].record(); c.count(); e[2].record()
-                    c.read_back()
-                    e[3].record(); c.scatter(); e[4].record()
-                torch.cuda.synchronize(dev)
-                tot["upload"] += e[0].elapsed_time(e[1])
-                tot["count"] += e[1].elapsed_time(e[2])
-                tot["scatter"] += e[3].elapsed_time(e[4])
-                raw_bytes += 16 * c.raw_rows
-                pool_bytes += 12 * c.pool.shape[0]
-            if run:
-                read_s.append(tot["read"]); upload_ms.append(tot["upload"]); count_ms.append(tot["count"]); scatter_ms.append(tot["scatter"])
-        launch_ms = [a + b for a, b in zip(count_ms, scatter_ms)]
-        moved = 2 * raw_bytes + pool_bytes
-        res.update(reader_s=stat(reader_s), read_s=stat(read_s), upload_ms=stat(upload_ms), count_ms=stat(count_ms),
-                   scatter_ms=stat(scatter_ms), raw_bytes=raw_bytes, pool_bytes=pool_bytes, launch_bytes=moved,
-                   launch_GBps=stat([moved / (ms * 1e-3) / 1e9 for ms in launch_ms]),
-                   upload_GBps=stat([raw_bytes / (ms * 1e-3) / 1e9 for ms in upload_ms]), chunks=len(chunks),
+        res.update(reader_s=stat(reader_s), **staged(torch, D, type(trk), dev, s.items, args, *s.row_bytes),
                    host_over_reader=statistics.median(host_s) / statistics.median(reader_s))
         print(json.dumps(res))
 
