@@ -46,6 +46,12 @@ loop L tracklets wide, each lane on its own tracklet's frames.  Which tracklet r
 every crop group and every lane table are host knowledge before the first frame: begin() plans them, uploads them in chunks,
 and step() only launches.
 
+K targets of one live scene (SceneTracker, MotionSceneTracker, track_scene, evaluate_scene): that
+free-running loop K targets wide on ONE stream of frames that arrive one at a time.  One o3d_track_crop_multi call per frame on
+a target table uploaded once, the lane kernels of the test epoch on a lane table that changes on events only, and enroll(): a
+slot takes a new object in mid-stream without a host stop.  MultiTargetTracker / MultiMotionTracker stay the K-target loops of
+sampling="reference".
+
 The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
 (`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
 """
@@ -192,7 +198,7 @@ class _DeviceTracker:
         self.counts_dev = torch.zeros((2 * (n_targets or 1),), dtype=torch.int32, device=self.dev)
         self.counts_host, self.counts_log = None, None
         if self.free_running:         # the counts stay on the device: row t of counts_log, written by a stream-ordered copy
-            self.counts_log = torch.full((int(max_frames), 2), -1, dtype=torch.int32, device=self.dev)
+            self.counts_log = torch.full((int(max_frames),) + lead + (2,), -1, dtype=torch.int32, device=self.dev)
             self.keys = None if self.tabled else draw_keys(self.seed)      # "table": the indices come from draw_table
         else:
             self.counts_host = torch.zeros(self.counts_dev.shape, dtype=torch.int32).pin_memory()
@@ -241,7 +247,7 @@ class _DeviceTracker:
             bigger[:T].copy_(self.boxes)
             self.boxes = bigger
             if self.free_running:                          # counts_log grows with boxes
-                log = torch.full((2 * T, 2), -1, dtype=torch.int32, device=self.dev)
+                log = torch.full((2 * T,) + self.counts_log.shape[1:], -1, dtype=torch.int32, device=self.dev)
                 log[:T].copy_(self.counts_log)
                 self.counts_log = log
 
@@ -533,6 +539,11 @@ class _MatchingTracker(_DeviceTracker):
                     bank[n:2 * n].copy_(bank[:n])
                 c.bank_total = 2 * nm
 
+    def _parity_states(self):
+        """the free-running loops with a leading axis (LaneTracker, SceneTracker), by frame parity p: (state_in, state_out, the
+        template counts = column 1 of state_out at stride 2) of bank_state (2,L,2)"""
+        return [(self.bank_state[1 - p], self.bank_state[p], self.bank_state[p].view(-1)[1:]) for p in (0, 1)]
+
     def _boxcloud(self):
         """the templates' BoxClouds against the canonical boxes (BAT only)"""
         if self.with_boxcloud:
@@ -686,7 +697,7 @@ class MultiTargetTracker(_KTargets, _MatchingTracker):
     shape_aggregation modes.  `update(points, ref_boxes=...)` (K,15): the reference's `reference_BB: previous_gt / current_gt`.
     `seed`: target k's limit_box draws use seed + k.  log, per frame: (search counts (K), model counts (K) | None, template
     counts (K)); crop_calls: the crop calls since init (one per frame, one more whenever a crop outgrew its buffer).
-    sampling: "reference" only ("device" and "table" raise ValueError: the K-target free-running loop is a follow-up)."""
+    sampling: "reference" only ("device" and "table" raise ValueError here: the K-target free-running loop is SceneTracker)."""
     _NAME, _REF_KW = "MultiTargetTracker", "ref_boxes"
 
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
@@ -903,7 +914,8 @@ class MultiMotionTracker(_KTargets, _DeviceTracker):
 
     log, per frame: (previous-frame counts (K), current-frame counts (K)); crop_calls: the crop calls since init (one per
     frame, one more whenever a crop outgrew the buffer: all 2K rows then grow to twice the largest count).
-    sampling: "reference" only ("device" and "table" raise ValueError: the K-target free-running loop is a follow-up)."""
+    sampling: "reference" only ("device" and "table" raise ValueError here: the K-target free-running loop is
+    MotionSceneTracker)."""
     _NAME = "MultiMotionTracker"
 
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference"):
@@ -1249,8 +1261,7 @@ class LaneTracker(_Lanes, _MatchingTracker):
         super().__init__(model, seed, use_graph, 1, search_capacity, model_capacity, L, sampling, record_indices, bank_capacity)
         self._lane_state(L, plan_steps, self.needs_ref_box, 1 if "PREVIOUS_GT" in str(self.reference_BB).upper() else 0,
                          self.aggregation != "first")
-        # by step parity: (state_in, state_out, the template counts = column 1 of state_out at stride 2); the model counts
-        self._states = [(self.bank_state[1 - p], self.bank_state[p], self.bank_state[p].view(-1)[1:]) for p in (0, 1)]
+        self._states = self._parity_states()               # by step parity
         self._model_counts = self.counts_dev[1:]
 
     def _clouds(self):
@@ -1295,9 +1306,14 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
         if int(capacity) < 1:
             raise ValueError("capacity must be positive")
         super().__init__(model, seed, use_graph, 1, _MOTION_DEFAULTS, L, sampling, record_indices)
+        self._motion_buffers(L, capacity)
+        self._lane_state(L, plan_steps)
+
+    def _motion_buffers(self, L, capacity):
+        """the buffers of the free-running motion loop with a leading axis (MotionLaneTracker, MotionSceneTracker)"""
         dev, N = self.dev, int(self.point_sample_size)
         f32 = dict(dtype=torch.float32, device=dev)
-        self.box_aware = bool(getattr(model, "box_aware", False))
+        self.box_aware = bool(getattr(self.model, "box_aware", False))
         self.inputs = {"points": torch.zeros((L, 2 * N, 5), **f32)}
         if self.box_aware:
             self.inputs["candidate_bc"] = torch.zeros((L, 2 * N, 9), **f32)
@@ -1307,7 +1323,6 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
         if self.tabled:
             self.table = draw_table(int(capacity), N, dev)
         self.draw_src = self.table if self.tabled else self.keys      # PU.motion_input_drawn_lanes' source
-        self._lane_state(L, plan_steps)
 
     def _clouds(self):
         c, cap = self, self.crop_buf.shape[2]
@@ -1325,6 +1340,270 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
         return int((log[:, 0] > cap).sum()), int((log[:, 1] > cap).sum()), 0
 
 
+# ---- K targets of one live scene, free-running -----------------------------------------------------------
+def _scene_sampling(name, who):
+    """the `sampling` keyword of a scene tracker, checked before anything else: the free-running modes only"""
+    if _sampling(name) not in FREE_RUNNING:
+        raise ValueError("%s: sampling=\"reference\" reads 2K counts back per frame, which is the loop of MultiTargetTracker / "
+                         "MultiMotionTracker; expected \"device\" or \"table\"" % who)
+    return name
+
+
+def scene_lane_rows(K, first=(), aggregation=None):
+    """The (K, LANE_COLS) int32 lane table of one frame of a scene tracker, a pure function: `active` is 1 for every slot (a
+    retired slot keeps running, only its box update is off, which o3d_track_offset_box_multi's own `active` decides), `first`
+    is 1 for the slots in `first` (every slot at t = 1, later the freshly enrolled ones), `has_crop` = first or aggregation !=
+    "first" (aggregation None, the motion tracker: both crops are made on every frame).  The columns of the epoch plan (t, row,
+    ref_row, rebase) are not read by the launches of a scene frame: 0, -1, -1, 0."""
+    rows = np.zeros((int(K), PU.LANE_COLS), np.int32)
+    is_first = np.zeros((int(K),), bool)
+    is_first[sorted(first)] = True
+    rows[:, PU.LANE["active"]] = 1
+    rows[:, PU.LANE["first"]] = is_first
+    rows[:, PU.LANE["has_crop"]] = is_first | (aggregation != "first")
+    rows[:, PU.LANE["row"]] = rows[:, PU.LANE["ref_row"]] = -1
+    return rows
+
+
+def scene_matching_overflow(log, starts, search_capacity, model_capacity, bank_capacity, aggregation):
+    """log (t,K,2): the counts of a SceneTracker; starts (K,): the frame after which slot k began to follow its object (0, or the
+    frame an enroll() followed) -> (K,3): _matching_overflow of every slot on its own rows, from its start frame on"""
+    return np.array([_matching_overflow(log[int(s):, k], search_capacity, model_capacity, bank_capacity, aggregation)
+                     for k, s in enumerate(starts)], np.int64).reshape(-1, 3)
+
+
+def scene_motion_overflow(log, starts, capacity):
+    """scene_matching_overflow for a MotionSceneTracker, by MotionLaneTracker.overflow's rule -> (K,3): (previous-frame cuts,
+    current-frame cuts, 0) of every slot from its start frame on"""
+    return np.array([[int((log[int(s) + 1:, k, 0] > capacity).sum()), int((log[int(s) + 1:, k, 1] > capacity).sum()), 0]
+                     for k, s in enumerate(starts)], np.int64).reshape(-1, 3)
+
+
+class _Scene(_KTargets):
+    """What SceneTracker and MotionSceneTracker put on top of _KTargets (the pack of K boxes, set_box, retire, the pinned target
+    table) and of their free-running bases' state with a leading K axis:
+
+      the fixed crop table    2K o3d_crop_target records whose pointers never change (boxes in fixed (K,15) buffers, outs in
+                              fixed buffers, counts in counts_dev laid out lane-major (K,2)): filled and uploaded ONCE, by the
+                              constructor
+      the lane table          (K, LANE_COLS) on the device, scene_lane_rows of the slots with a pending `first`; rewritten on
+                              events only (the first frame, the frame after a `first`, the frame after an enroll())
+      enroll                  a slot takes a NEW object from the most recent frame, with device writes only
+      the counts log          counts_log (T,K,2), row t written by stream-ordered device copies
+      overflow                per slot, from the slot's own start frame"""
+
+    def _scene_state(self, K, groups):
+        """groups: per crop group (boxes (K,15), scale, offset, mode, out (K,capacity,3)); group g counts into column g"""
+        self._k_state(K)
+        self.counts2 = self.counts_dev.view(K, 2)
+        kk = np.arange(K, dtype=np.uint64)
+        self._groups = []
+        for g, (boxes, scale, offset, mode, out) in enumerate(groups):
+            cap = out.shape[1]
+            self._groups.append(self._crop_group(g, boxes, scale, offset, mode, out.data_ptr() + 12 * cap * kk, cap))
+            self.crop_rec["count"][g * K:(g + 1) * K] = self.counts_dev.data_ptr() + 4 * (2 * kk + np.uint64(g))      # lane-major
+        self.crop_tab.copy_(self.crop_tab_host)                            # the one upload of the table
+        self.lanes = torch.zeros((K, PU.LANE_COLS), dtype=torch.int32, device=self.dev)
+        self.lane_uploads = 0
+        self._pending, self._on_device, self._has_crop = set(), None, np.zeros((K,), bool)
+        self._start = np.zeros((K,), np.int64)
+
+    def init(self, points0, boxes0):
+        boxes = super().init(points0, boxes0)
+        self._pending, self._on_device = set(range(self.K)), None          # t = 1 is every slot's first tracked frame
+        self._start[:] = 0
+        self.lane_uploads = 0                              # since init, as crop_calls
+        return boxes
+
+    def enroll(self, k, box):
+        """Slot k starts following a NEW object from the most recent frame (`prev_points`): slot k's init.  Its last box, yaw
+        state, canonical wlh and row t - 1 of the results are set from `box`, its template bank restarts empty, it is active
+        again, and its NEXT update() is its first tracked frame (the bank's `first` branch; the motion tracker's prior
+        targetness 1 / 0).  Device writes and, for a host box, one asynchronous copy from pinned memory: nothing is read back."""
+        if self.t < 1:
+            raise RuntimeError(self._NAME + ".enroll before init")
+        k = int(k) % self.K
+        with torch.cuda.device(self.dev):
+            if torch.is_tensor(box) and box.is_cuda:
+                b = PU.pack_box(box, self.dev)
+            else:
+                b = PU.pack_box(box, "cpu").pin_memory().to(self.dev, non_blocking=True)
+            self._restart(b, k)
+            self.canon_wlh[k].copy_(b[3:6])
+            if hasattr(self, "bank_state"):
+                self.bank_state[(self.t + 1) & 1, k].zero_()               # the slot the next frame reads as state_in
+            self.active[k] = 1
+        self.retired.discard(k)
+        self._pending.add(k)
+        self._start[k] = self.t - 1
+
+    def _lane_event(self):
+        """the lane table of this frame, uploaded only where it differs from the one on the device -> (lanes, has_crop (K,) on
+        the host)"""
+        first = frozenset(self._pending)
+        if first != self._on_device:
+            rows = scene_lane_rows(self.K, first, getattr(self, "aggregation", None))
+            self.lanes.copy_(torch.from_numpy(rows).pin_memory(), non_blocking=True)
+            self._on_device, self._has_crop = first, rows[:, PU.LANE["has_crop"]] != 0
+            self.lane_uploads += 1
+        return self.lanes, self._has_crop
+
+    def _crop_scene(self, clouds):
+        """the frame's one o3d_track_crop_multi call: clouds[g] | None = the points of group g of the fixed table"""
+        self.scratch = PU.crop_multi([(pts, self._groups[g]) for g, pts in enumerate(clouds) if pts is not None], self.scratch)
+        self.crop_calls += 1
+
+    def _log_scene_counts(self, made):
+        """row t of the counts log: column g of every slot where made[g] is True, of the slots made[g] lists otherwise"""
+        row = self.counts_log[self.t]
+        if all(m is True for m in made):
+            row.copy_(self.counts2)
+            return
+        for g, m in enumerate(made):
+            if m is True:
+                row[:, g].copy_(self.counts2[:, g])
+            else:
+                for k in m:
+                    row[k, g:g + 1].copy_(self.counts2[k, g:g + 1])
+
+    def _frame_done(self, pts):
+        self._pending.clear()
+        return self._done(pts, None)
+
+    def counts(self):
+        """(t,K,2) int32 on the host: row f the two crop counts of every slot at frame f, as the crop kernel counted them (before
+        the cut to the capacities), -1 where no crop was made.  One sync."""
+        return self.counts_log[:self.t].cpu().numpy()
+
+    def overflow(self, per_target=False):
+        """How often a fixed capacity cut something, on the host from counts() and the capacities (one sync): three sums over
+        the targets, as LaneTracker.overflow; per_target=True -> (K,3), row k worked out on slot k's rows from its own start
+        frame (0, or the frame its last enroll() followed)."""
+        per = self._overflow_rows(self.counts())
+        return per if per_target else tuple(int(v) for v in per.sum(0))
+
+
+class SceneTracker(_Scene, _MatchingTracker):
+    """K targets of one live scene, free-running (the matching trackers: trackers.BAT, trackers.P2B): MultiTargetTracker's
+    loop without its host stop.  Frames arrive one at a time, nothing is read back, nothing is uploaded per frame.
+
+        trk = SceneTracker(model, K)            # sampling="device" | "table"; model on the GPU, eval mode
+        trk.init(points0, boxes0)               # as MultiTargetTracker
+        boxes = trk.update(points)              # a (K,15) device VIEW of the new boxes: the frame is only ENQUEUED
+        trk.retire(1); trk.enroll(1, box)       # slot 1 stops, then follows a new object from the most recent frame
+        all_boxes = trk.results()               # (T,K,15) on the host, one sync
+
+    Per frame t >= 1, whatever K:
+
+      a device copy into ref (K,15)     the last boxes, or the caller's ref_boxes (a device tensor keeps the loop free of host
+                                        stops) with the retired rows replaced by their last boxes
+      o3d_track_crop_multi, one call    group 0: frame t against ref into search_buf (K,search_capacity,3); group 1 (only when
+                                        some slot takes a model crop): frame t-1 against the last boxes into staging
+                                        (K,model_capacity,3).  Its target table was uploaded once, by the constructor.
+      device copies of the counts       row t of counts_log (T,K,2)
+      o3d_track_bank_update_lanes       on the lane table of _Scene; bank_state (2,K,2) alternates by frame parity
+      o3d_track_resample_drawn_lanes    or its table twin: the index source is chosen once (draw_src)
+      o3d_boxcloud, forward + o3d_best_proposal at batch K    one replayed HIP graph (eager when the capture fails, unless
+                                        O3D_REQUIRE_GRAPH=1)
+      o3d_track_offset_box_multi        MultiTargetTracker's call: device frame counter, per-target active and rebase
+
+    Every lane kernel hands slot k's operands to the device function of the single-target form, so row k is a single
+    free-running SequenceTracker's row; with sampling="table" and nothing cut (overflow() == (0, 0, 0)) the inputs and boxes are
+    MultiTargetTracker's bit for bit.  The capacities are fixed, as for SequenceTracker(sampling="device").  `seed`: target k's
+    limit_box draws use seed + k; under "device" it also keys the index draws, the same two keys for every slot.
+    record_indices=True keeps the last frame's indices in used_t (K,template_size) / used_s (K,search_size)."""
+    _NAME, _REF_KW = "SceneTracker", "ref_boxes"
+
+    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
+                 bank_capacity=None, sampling="device", record_indices=False):
+        _scene_sampling(sampling, self._NAME)
+        if _is_motion(model):
+            raise TypeError("SceneTracker serves the matching trackers (BAT, P2B); the motion tracker follows the K targets of "
+                            "a live scene with MotionSceneTracker")
+        K = self._n_targets(n_targets)
+        super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity, K, sampling, record_indices,
+                         bank_capacity)
+        self.ref = torch.zeros((K, 15), dtype=torch.float32, device=self.dev)
+        self.rebase_all = torch.ones((K,), dtype=torch.int32, device=self.dev)
+        self._scene_state(K, [(self.ref, self.search_bb_scale, self.search_bb_offset, PU.CROP_SUBWINDOW, self.search_buf),
+                              (self.cur, self.model_bb_scale, self.model_bb_offset, PU.CROP_MODEL, self.staging)])
+        self._states = self._parity_states()
+        self._model_counts = self.counts_dev[1:]
+
+    def update(self, points, ref_boxes=None):
+        return self._run(points, ref_boxes)
+
+    def _update(self, pts, ref_boxes):
+        c = self
+        c._grow_boxes()
+        if ref_boxes is None:
+            c.ref.copy_(c.cur)
+        else:
+            c.ref.copy_(c._pack(ref_boxes))
+            for k in sorted(c.retired):                    # a retired target's reference is its own last box, not the caller's
+                c.ref[k].copy_(c.cur[k])
+        lanes, has_crop = c._lane_event()
+        cropped = np.flatnonzero(has_crop).tolist()
+        c._crop_scene([pts, c.prev_points if cropped else None])
+        c._log_scene_counts([True, True if len(cropped) == c.K else cropped])
+        state_in, state_out, totals = c._states[c.t & 1]
+        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
+        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
+                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
+        c._boxcloud()
+        best, _ = c._network()
+        PU.offset_box_multi(c.ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame,
+                            rebase=c.rebase_all if ref_boxes is not None else None, active=c.active, degrees=c.degrees,
+                            use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        return c._frame_done(pts)
+
+    def _overflow_rows(self, log):
+        return scene_matching_overflow(log, self._start, self.search_buf.shape[1], self.model_capacity, self.bank_capacity,
+                                       self.aggregation)
+
+
+class MotionSceneTracker(_Scene, _DeviceTracker):
+    """K targets of one live scene, free-running, for the motion tracker (m2track.M2TRACK): MultiMotionTracker's loop without
+    its host stop.  The surface is SceneTracker's (no ref_boxes: the motion tracker always starts from its last result).  Per
+    frame: o3d_track_crop_multi, one call on the fixed table (group 0: frame t-1, group 1: frame t, both against the last
+    boxes, into crop_buf (2,K,capacity,3), the counts lane-major (K,2)), a device copy of the counts into row t of counts_log,
+    o3d_track_motion_input_drawn_lanes or its table twin on the lane table (`first` per slot: the prior targetness of a slot's
+    first tracked frame is 1 / 0), the batch-K forward as one replayed HIP graph, o3d_track_offset_box_multi.
+    record_indices=True keeps the last frame's indices in used (K,2N)."""
+    _NAME = "MotionSceneTracker"
+
+    def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="device",
+                 record_indices=False):
+        _scene_sampling(sampling, self._NAME)
+        if not _is_motion(model):
+            raise TypeError("MotionSceneTracker serves the motion tracker (M2TRACK); the matching trackers (BAT, P2B) follow "
+                            "the K targets of a live scene with SceneTracker")
+        K = self._n_targets(n_targets)
+        if int(capacity) < 1:
+            raise ValueError("capacity must be positive")
+        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, K, sampling, record_indices)
+        MotionLaneTracker._motion_buffers(self, K, capacity)
+        self._scene_state(K, [(self.cur, self.bb_scale, self.bb_offset, PU.CROP_SUBWINDOW, self.crop_buf[h]) for h in (0, 1)])
+
+    def update(self, points):
+        return self._run(points)
+
+    def _update(self, pts):
+        c = self
+        c._grow_boxes()
+        lanes, _ = c._lane_event()
+        c._crop_scene([c.prev_points, pts])
+        c._log_scene_counts([True, True])
+        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.draw_src, c.canon_wlh, lanes, c.inputs["points"],
+                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        est = c._network()
+        PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
+                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        return c._frame_done(pts)
+
+    def _overflow_rows(self, log):
+        return scene_motion_overflow(log, self._start, self.crop_buf.shape[2])
+
 
 def tracker_for(model, **kw):
     """the tracker class of a model: MotionSequenceTracker for m2track.M2TRACK, SequenceTracker for the matching trackers"""
@@ -1334,6 +1613,11 @@ def tracker_for(model, **kw):
 def multi_tracker_for(model, n_targets, **kw):
     """tracker_for for K targets: MultiMotionTracker for m2track.M2TRACK, MultiTargetTracker for the matching trackers"""
     return (MultiMotionTracker if _is_motion(model) else MultiTargetTracker)(model, n_targets, **kw)
+
+
+def scene_tracker_for(model, n_targets, **kw):
+    """the scene tracker class of a model: MotionSceneTracker for m2track.M2TRACK, SceneTracker for the matching trackers"""
+    return (MotionSceneTracker if _is_motion(model) else SceneTracker)(model, n_targets, **kw)
 
 
 def lane_tracker_for(model, lanes, **kw):
@@ -1363,9 +1647,14 @@ def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None,
     """track_sequence for K targets in the same frames: boxes0 (K,15) the targets' boxes in frames[0]; ref_boxes[t] (K,15)
     (optional, matching trackers only) is handed to update() of frame t.  The tracker class follows the model's type.
     -> (T,K,15) result boxes on the host."""
+    return _track_k(multi_tracker_for, model, frames, boxes0, ref_boxes, seed=seed, use_graph=use_graph, sampling=sampling)
+
+
+def _track_k(make, model, frames, boxes0, ref_boxes, **kw):
+    """the loop of track_targets / track_scene on make(model, K, **kw)"""
     b0 = boxes0 if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray) else list(boxes0)
-    trk = multi_tracker_for(model, len(b0), seed=seed, use_graph=use_graph, sampling=sampling)
-    if isinstance(trk, MultiMotionTracker) and ref_boxes is not None:
+    trk = make(model, len(b0), **kw)
+    if isinstance(trk, (MultiMotionTracker, MotionSceneTracker)) and ref_boxes is not None:
         raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
     trk.init(frames[0], b0)
     for t in range(1, len(frames)):
@@ -1374,6 +1663,15 @@ def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None,
         else:
             trk.update(frames[t], ref_boxes[t])
     return trk.results()
+
+
+def track_scene(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None, sampling="device", **capacities):
+    """track_targets on a scene tracker (SceneTracker / MotionSceneTracker by the model's type): the K targets of one scene
+    free-running, sampling "device" | "table"; capacities: the tracker's fixed sizes (under "table" also the sizes of its draw
+    tables).  ref_boxes[t] as a device tensor keeps the loop free of host stops.  -> (T,K,15) result boxes on the host."""
+    _scene_sampling(sampling, "track_scene")
+    return _track_k(scene_tracker_for, model, frames, boxes0, ref_boxes, seed=seed, use_graph=use_graph, sampling=sampling,
+                    **capacities)
 
 
 def _track_with_gt(trk, frames, gt):
@@ -1411,9 +1709,24 @@ def evaluate_targets(model, frames, gt_boxes, valid=None, seed=0, use_graph=None
     the host: 0 where a target has no annotation; a target is retired at its first such frame (its later rows repeat its last
     box and are not scored, whatever `valid` says there).  -> (ious (T,K), distances (T,K), results (T,K,15)) device tensors."""
     _sampling(sampling, "evaluate_targets")
-    gt_host = gt_boxes.shape
-    trk = tracker if tracker is not None else multi_tracker_for(model, gt_host[1], seed=seed, use_graph=use_graph)
-    gt = PU._dev32(gt_boxes, trk.dev).reshape(gt_host[0], trk.K, 15)
+    trk = tracker if tracker is not None else multi_tracker_for(model, gt_boxes.shape[1], seed=seed, use_graph=use_graph)
+    return _evaluate_k(trk, frames, gt_boxes, valid, metrics)
+
+
+def evaluate_scene(model, frames, gt_boxes, valid=None, seed=0, use_graph=None, tracker=None, metrics=None, sampling="device",
+                   **capacities):
+    """evaluate_targets on a scene tracker (sampling "device" | "table"; capacities: its fixed sizes): the same contract and
+    the same return value, and no host stop per frame (the ground truth is uploaded once, retire() is a device write).
+    tracker: a SceneTracker / MotionSceneTracker to reuse."""
+    _scene_sampling(sampling, "evaluate_scene")
+    trk = tracker if tracker is not None else scene_tracker_for(model, gt_boxes.shape[1], seed=seed, use_graph=use_graph,
+                                                                sampling=sampling, **capacities)
+    return _evaluate_k(trk, frames, gt_boxes, valid, metrics)
+
+
+def _evaluate_k(trk, frames, gt_boxes, valid, metrics):
+    """the loop of evaluate_targets / evaluate_scene on a K-target tracker"""
+    gt = PU._dev32(gt_boxes, trk.dev).reshape(gt_boxes.shape[0], trk.K, 15)
     if len(frames) != gt.shape[0]:
         raise ValueError("%d frames, %d ground-truth boxes" % (len(frames), gt.shape[0]))
     live = None

@@ -35,6 +35,16 @@ build time and the bytes of the draw tables (built once, before the timed runs),
 reference loop's in bits.  A scratch tracker is created and warmed before the three (first_capture: the first tracker of a
 process is the slow one, whatever its mode).
 
+--targets K --sampling device | table [--model M2TRACK]: the K targets of one live scene free-running
+(tracking.scene_tracker_for(model, K, sampling=...): SceneTracker / MotionSceneTracker, no host stop per frame) against the
+K-target loop of sampling="reference" (MultiTargetTracker / MultiMotionTracker: 2K counts read back, 2K numpy draws and two
+uploads per frame) on the same synth.make_scene and the same model (fixture weights), both from frames resident in HBM, each
+timed from its first update() to the read-back of its boxes, --repeats times in turn; a scratch tracker is created and warmed
+before the two (first_capture).  Prints one JSON line: ms per frame of both (median, smallest and largest run), targets x
+frames per second, their ratio, overflow() of the scene tracker, whether each loop replays a graph, the host time per update()
+of both (the time until update() returns: the free-running loop only enqueues), and with "table" whether the two loops' boxes
+are equal in bits.
+
 --lanes L: the test epoch on L lanes (tracking.lane_tracker_for(model, L): --tracklets tracklets of --frames frames each, L at a
 time in one free-running loop) against the sequential epoch of evaluate(..., sampling="device") (one free-running tracker, one
 tracklet after the other) on the same tracklets, the same model (fixture weights) and the same SuccessPrecision scoring, both
@@ -251,6 +261,72 @@ def sampling_main(args, dev):
             np.linalg.norm(boxes["device"][:, :3] - boxes["reference"][:, :3], axis=1).max()), **tables}))
 
 
+def scene_main(args, dev):
+    """--targets K --sampling device | table: the free-running K-target loop against the reference-sampling K-target loop"""
+    K = args.targets
+    if args.model.upper() == "M2TRACK":
+        model, cfg = motion_model(dev)
+    else:
+        cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+        cfg.update(TO.TEST_KEYS)
+        model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+    frames, gt = synth.make_scene(args.seed, args.frames, max(args.points // K, 1024), K)
+    dframes = [torch.from_numpy(f).to(dev) for f in frames]
+    warm = min(20, args.frames)
+    scratch = first_capture(model, dframes, gt[0, 0])      # noqa: F841  (kept alive: the first tracker of a process is the slow one)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    trks = {"scene": tracking.scene_tracker_for(model, K, sampling=args.sampling)}      # "table": the draw tables are built here
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t0
+    trks["reference"] = tracking.multi_tracker_for(model, K)
+    for trk in trks.values():
+        trk.init(dframes[0], gt[0])
+        for t in range(1, warm):                                        # capture + warm-up
+            trk.update(dframes[t])
+    torch.cuda.synchronize()
+    times, host, boxes = {m: [] for m in trks}, {m: [] for m in trks}, {}
+    for _ in range(args.repeats):                                       # the two loops in turn: what disturbs one disturbs the other
+        for m, trk in trks.items():
+            trk.init(dframes[0], gt[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in range(1, args.frames):
+                trk.update(dframes[t])
+            t1 = time.perf_counter()                                    # every update() has returned
+            boxes[m] = trk.results()                                    # the one read-back of the boxes (a sync)
+            times[m].append(time.perf_counter() - t0)
+            host[m].append(t1 - t0)
+    n = args.frames - 1
+    ms = {m: sorted(1e3 * dt / n for dt in times[m]) for m in trks}
+    mid = {m: ms[m][len(ms[m]) // 2] for m in trks}
+    host_mid = {m: sorted(1e3 * dt / n for dt in host[m])[len(host[m]) // 2] for m in trks}
+    scn, ref = trks["scene"], trks["reference"]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(200):
+        scn._network()
+    torch.cuda.synchronize()
+    fwd_ms = (time.perf_counter() - t0) / 200 * 1e3
+    print(json.dumps({
+        "workload": "%s tracking %d targets through a %d-frame, %d-point synthetic scene (fixture weights, eval, fp32), median of %d "
+                    "runs, the two loops in turn" % (args.model.upper(), K, args.frames, int(frames[0].shape[0]), args.repeats),
+        "targets": K, "sampling": args.sampling,
+        "scene_ms_per_frame": round(mid["scene"], 4), "reference_ms_per_frame": round(mid["reference"], 4),
+        "scene_ms_per_frame_min_max": [round(ms["scene"][0], 4), round(ms["scene"][-1], 4)],
+        "reference_ms_per_frame_min_max": [round(ms["reference"][0], 4), round(ms["reference"][-1], 4)],
+        "scene_target_frames_per_s": round(K * 1e3 / mid["scene"], 1), "reference_target_frames_per_s": round(K * 1e3 / mid["reference"], 1),
+        "scene_over_reference": round(mid["reference"] / mid["scene"], 3),
+        "scene_host_ms_per_update": round(host_mid["scene"], 4), "reference_host_ms_per_update": round(host_mid["reference"], 4),
+        "batch_K_forward_replay_ms": round(fwd_ms, 4),
+        "hip_graph": [scn.graph is not None, ref.graph is not None], "scene_overflow": list(scn.overflow()),
+        "scene_overflow_targets": int(scn.overflow(per_target=True).any(1).sum()), "scene_lane_table_uploads_per_run": scn.lane_uploads,
+        "scene_tracker_build_s": round(build_s, 3),
+        "scene_boxes_equal_reference_boxes_in_bits": bool(np.array_equal(boxes["scene"].view(np.int32), boxes["reference"].view(np.int32))),
+        "largest_centre_distance_between_the_two_trajectories": float(
+            np.linalg.norm(boxes["scene"][..., :3] - boxes["reference"][..., :3], axis=-1).max())}))
+
+
 def lanes_main(args, dev):
     from open3dsot_amd import metrics as MT
     L = args.lanes
@@ -360,7 +436,9 @@ def main():
         return lanes_main(args, dev)
     if args.targets > 0:
         if args.sampling in tracking.FREE_RUNNING:
-            raise SystemExit("--sampling %s times the single-target loops; the K-target loops have no free-running mode yet" % args.sampling)
+            if args.frames < 2:
+                raise SystemExit("--targets K --sampling %s times a scene: at least 2 frames" % args.sampling)
+            return scene_main(args, dev)
         return multi_target_main(args, dev)
     if args.sampling in tracking.FREE_RUNNING:
         return sampling_main(args, dev)
