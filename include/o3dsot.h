@@ -135,7 +135,8 @@ int o3d_knn(const float* query, const float* ref, int B, int Q, int R, int D, in
 /* Y[b,co,p] = sum_ci W[co,ci] * f(X[b,ci,p]);  f = identity when in_scale == NULL, else
  * f(x) = max(x*in_scale[ci] + in_shift[ci], 0).  X (B,Cin,P), W (Cout,Cin), Y (B,Cout,P).
  * part != NULL: receives per-tile partial statistics [B*P/128][2][Cout] = {sum y,
- * sum (y - stat_c[co])^2} (stat_c == NULL means 0). */
+ * sum (y - stat_c[co])^2} (stat_c == NULL means 0).  in_scale and in_shift are both given or both NULL: exactly one of them
+ * NULL is refused with O3D_EINVAL. */
 int o3d_mlp_conv_fwd(const float* X, const float* W, const float* in_scale, const float* in_shift,
                      int B, int Cin, int Cout, int P, float* Y, float* part, const float* stat_c,
                      void* stream);
@@ -200,18 +201,30 @@ int o3d_mlp_conv_dgrad_wt(const float* dN, const float* dOut, const float* out, 
                           const float* mean_p, float* dNprev, float* part, void* stream);
 
 /* dX (B,Cin,P) = W^T (A1*dN + A2*Y + A3): gradient w.r.t. an operand that is not a BN+ReLU output
- * (the per-point operand [xyz;feats] of layer 0).  No mask, no statistics. */
+ * (the per-point operand [xyz;feats] of layer 0).  No mask, no statistics.  dN (dense, (B,Cout,P)), Y and A1..A3 are all
+ * required -- there is no pooled source and no "dY = dN" shortcut here: any of them NULL is refused with O3D_EINVAL, as is
+ * P % 128 != 0. */
 int o3d_mlp_conv_dgrad_plain(const float* dN, const float* Y, const float* A1, const float* A2,
                              const float* A3, const float* W, int B, int Cin, int Cout, int P,
                              float* dX, void* stream);
 
 /* Weight gradient dW (Cout,Cin) = sum_{b,p} dY[b,co,p] * X[b,ci,p]; X = f(X raw) as in
  * o3d_mlp_conv_fwd.  part: scratch of (nslices+16)*Cout*Cin floats (split over positions, reduced in a fixed
- * order).  X must not be NULL. */
+ * order).  X must not be NULL; in_scale and in_shift are both given or both NULL (exactly one of them NULL is refused with
+ * O3D_EINVAL).  P % 32 == 0.  A slice that receives no 32-position chunk (nslices above B*P/32) writes zeros. */
 int o3d_mlp_conv_wgrad(const float* dN, const float* dOut, const float* out, const int32_t* arg, int ns,
                        const float* Y, const float* A1, const float* A2, const float* A3,
                        const float* X, const float* in_scale, const float* in_shift, int B, int Cin, int Cout,
                        int P, int nslices, float* part, float* dW, void* stream);
+
+/* Which kernel a batched entry above launches for a shape, computed by the entries' own rules (no launch):
+ *   entry 0: o3d_mlp_conv_fwd, M = Cout, K = Cin, part = 1 when statistics partials are requested, else 0
+ *   entry 1: o3d_mlp_conv_dgrad_wt with Wt given, M = Cin, K = Cout (part ignored)
+ *   entry 2: o3d_mlp_conv_dgrad, o3d_mlp_conv_dgrad_plain, o3d_mlp_conv_dgrad_wt with Wt == NULL, M = Cin, K = Cout
+ * -> 64 / 128 / 256: the LDS-staged generic kernel with that many rows per workgroup; 1000 * class + tile: the direct kernel
+ * of csrc/mlp_direct.hip (class as o3d_direct_class, at this B; tile = columns per wave tile): 2064, 4064 or 3128;
+ * -1: a shape the entry refuses.  tests/test_batched_gemm_kernels_gpu.py asserts it for every case. */
+int o3d_mlp_conv_class(int entry, int B, int M, int K, int P, int part);
 
 /* ---- compact (distinct-neighbour) layout, csrc/compact.hip ------------------------------------------
  * ball_query pads a ball with copies of its first hit (pointnet2_utils.py:268); copies have identical

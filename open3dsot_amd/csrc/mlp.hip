@@ -39,6 +39,7 @@ int o3d_direct_dgrad(const float* dN, const float* pk, int ns,
                      int Cin, int Cout, int P, const float* Yprev, const float* scale_p, const float* shift_p,
                      const float* mean_p, float* dNprev, float* part, const float* w, const int32_t* meta,
                      long start1, int tile, hipStream_t st);
+int o3d_direct_class_b(int B, int M, int K, int P, int tile);
 
 namespace {
 
@@ -889,13 +890,17 @@ inline size_t dgrad_lds(int BM) {
     return stage > red ? stage : red;
 }
 
+// rows per workgroup tile of the generic forward (rows = Cout) and data-gradient (rows = Cin) kernels
+inline int generic_bm(int rows) { return rows > 128 ? 256 : rows > 64 ? 128 : 64; }
+
 template <bool XFORM>
 int launch_fwd(const FwdArgs& a, hipStream_t s) {
     const int tiles = a.B * (a.P / BN_POS);
-    if (a.Cout > 128) {
+    const int bm = generic_bm(a.Cout);
+    if (bm == 256) {
         return launch(conv_fwd_kernel<256, XFORM>, dim3(tiles, o3d_cdiv(a.Cout, 256)), dim3(512),
                       fwd_lds(256), s, a);
-    } else if (a.Cout > 64) {
+    } else if (bm == 128) {
         return launch(conv_fwd_kernel<128, XFORM>, dim3(tiles, 1), dim3(256), fwd_lds(128), s, a);
     }
     return launch(conv_fwd_kernel<64, XFORM>, dim3(tiles, 1), dim3(128), fwd_lds(64), s, a);
@@ -904,10 +909,11 @@ int launch_fwd(const FwdArgs& a, hipStream_t s) {
 template <bool POOLED, int EPI>
 int launch_dgrad(const DgradArgs& a, hipStream_t s) {
     const int tiles = a.B * (a.P / BN_POS);
-    if (a.M > 128) {
+    const int bm = generic_bm(a.M);
+    if (bm == 256) {
         return launch(conv_dgrad_kernel<256, POOLED, EPI>, dim3(tiles, o3d_cdiv(a.M, 256)), dim3(512),
                       dgrad_lds(256), s, a);
-    } else if (a.M > 64) {
+    } else if (bm == 128) {
         return launch(conv_dgrad_kernel<128, POOLED, EPI>, dim3(tiles, 1), dim3(256), dgrad_lds(128), s, a);
     }
     return launch(conv_dgrad_kernel<64, POOLED, EPI>, dim3(tiles, 1), dim3(128), dgrad_lds(64), s, a);
@@ -918,14 +924,33 @@ int launch_dgrad(const DgradArgs& a, hipStream_t s) {
 // --------------------------------------------------------------------------------------
 // C-ABI
 // --------------------------------------------------------------------------------------
+// (the statistics partials are one row per 128 columns by contract: narrower tiles only without them)
+static int fwd_direct_tile(int B, int Cout, int P, bool part) { return part ? 128 : o3d_direct_tile((long)B * P, Cout, 0); }
+
+// Which kernel a batched entry launches for a shape, by the rules the entries below apply themselves (no launch).
+//   entry 0: o3d_mlp_conv_fwd, M = Cout, K = Cin, part = whether statistics partials are requested
+//   entry 1: o3d_mlp_conv_dgrad_wt with Wt given, M = Cin, K = Cout (part ignored: always written)
+//   entry 2: o3d_mlp_conv_dgrad, o3d_mlp_conv_dgrad_plain and o3d_mlp_conv_dgrad_wt without Wt, M = Cin, K = Cout
+// -> 64 / 128 / 256: the LDS-staged generic kernel with that many rows per workgroup; 1000 * class + tile: the direct kernel
+// (class of o3d_direct_class at this B, tile = its columns per wave tile: 2064, 4064, 3128); -1: a shape the entry refuses.
+extern "C" int o3d_mlp_conv_class(int entry, int B, int M, int K, int P, int part) {
+    if (entry < 0 || entry > 2 || B <= 0 || M <= 0 || K <= 0 || P <= 0 || P % BN_POS != 0) return -1;
+    if (entry != 2 && o3d_direct_ok(M, K, P)) {
+        const int tile = entry == 0 ? fwd_direct_tile(B, M, P, part != 0) : 128;
+        return 1000 * o3d_direct_class_b(B, M, K, P, tile) + tile;
+    }
+    return generic_bm(M);
+}
+
 extern "C" int o3d_mlp_conv_fwd(const float* X, const float* W, const float* in_scale,
                                 const float* in_shift, int B, int Cin, int Cout, int P, float* Y,
                                 float* part, const float* stat_c, void* stream) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0 || P % BN_POS != 0 || !X || !W || !Y) return O3D_EINVAL;
-    if (o3d_direct_ok(Cout, Cin, P) && (in_scale == nullptr) == (in_shift == nullptr))
-        // (the statistics partials are one row per 128 columns by contract: narrower tiles only without them)
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0 || P % BN_POS != 0 || !X || !W || !Y ||
+        (in_scale == nullptr) != (in_shift == nullptr))
+        return O3D_EINVAL;
+    if (o3d_direct_ok(Cout, Cin, P))
         return o3d_direct_fwd(X, W, in_scale, in_shift, B, Cin, Cout, P, Y, part, stat_c, nullptr, nullptr, 0,
-                              part ? 128 : o3d_direct_tile((long)B * P, Cout, 0), o3d_stream(stream));
+                              fwd_direct_tile(B, Cout, P, part != nullptr), o3d_stream(stream));
     FwdArgs a = {};
     a.X = X; a.W = W; a.Y = Y; a.in_scale = in_scale; a.in_shift = in_shift; a.part = part; a.stat_c = stat_c;
     a.B = B; a.Cin = Cin; a.Cout = Cout; a.P = P;
@@ -1095,7 +1120,8 @@ extern "C" int o3d_mlp_conv_wgrad(const float* dN, const float* dOut, const floa
                                   const float* X, const float* in_scale, const float* in_shift,
                                   int B, int Cin, int Cout, int P, int nslices, float* part, float* dW,
                                   void* stream) {
-    if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0 || P % WBK != 0 || nslices <= 0 || !X || !part || !dW)
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || P <= 0 || P % WBK != 0 || nslices <= 0 || !X || !part || !dW ||
+        (in_scale == nullptr) != (in_shift == nullptr))
         return O3D_EINVAL;
     WgradArgs a = {};
     if (fill_dy(a.dy, dN, dOut, out, arg, Y, A1, A2, A3, ns) != O3D_OK) return O3D_EINVAL;

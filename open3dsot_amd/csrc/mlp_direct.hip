@@ -801,6 +801,13 @@ extern "C" int o3d_direct_class(long ldp, int M, int K, int tile) {
     return small_class(a, tile);      // launch_direct's rule: split-K when splitk_ok, else the tile's own class (no narrow tile)
 }
 
+// the class launch_direct picks for a batched (B, ., P) problem on `tile` columns: its own rule, no launch
+int o3d_direct_class_b(int B, int M, int K, int P, int tile) {
+    DirectArgs a = {};
+    a.M = M; a.K = K; a.P = P; a.B = B;
+    return small_class(a, tile);
+}
+
 // forward: Y = W . f(X), see o3d_mlp_conv_fwd
 int o3d_direct_fwd(const float* X, const float* W, const float* in_scale, const float* in_shift, int B, int Cin,
                    int Cout, int P, float* Y, float* part, const float* stat_c, const float* w, const int32_t* meta,

@@ -113,6 +113,7 @@ def test_signatures_and_return_types_hand_pinned():
             "o3d_bn_finalize": "pip",                                          # a struct pointer and a count
             "o3d_thin_bwd_scratch": "",                                        # (void)
             "o3d_track_crop_groups_aug": "pppiplp",                            # const T* const*
+            "o3d_mlp_conv_class": "iiiiii",                                    # a pure query: ints only
             "o3d_version": ""}
     for name, kinds in pins.items():
         assert "".join(KIND[a] for a in capi.SIGNATURES[name]) == kinds, name
@@ -148,6 +149,16 @@ def test_entry_points_reject_bad_arguments_before_touching_the_device():
     assert lib.o3d_center_term(None, None, 8, 8, 3, None, None) == EINVAL
     # the compact data gradient rebuilds dY from dN AND Y: every operand valid but Y
     assert lib.o3d_mlp_conv_dgrad_c(p, None, p, p, p, p, 64, 128, 2048, p, p, 1024, 64, p, p, p, p, p, p, None) == EINVAL
+    # the batched GEMM entries: exactly one of in_scale / in_shift NULL is refused (the transform would read the other)
+    for sc, sh in ((p, None), (None, p)):
+        assert lib.o3d_mlp_conv_fwd(p, p, sc, sh, 1, 3, 37, 128, p, None, None, None) == EINVAL
+        assert lib.o3d_mlp_conv_fwd(p, p, sc, sh, 1, 16, 64, 128, p, None, None, None) == EINVAL        # the aligned shape too
+        assert lib.o3d_mlp_conv_wgrad(p, None, None, None, 4, p, p, p, p, p, sc, sh, 1, 3, 37, 128, 1, p, p, None) == EINVAL
+    # o3d_mlp_conv_class: which kernel those entries launch, without a launch
+    c = lib.o3d_mlp_conv_class
+    assert [c(0, 2, 37, 3, 128, 1), c(0, 2, 100, 3, 128, 1), c(0, 2, 300, 3, 128, 1)] == [64, 128, 256]
+    assert [c(0, 2, 64, 16, 128, 1), c(0, 2, 64, 16, 128, 0), c(0, 2, 128, 64, 128, 0), c(1, 2, 64, 16, 128, 1)] == [3128, 2064, 4064, 3128]
+    assert c(2, 2, 64, 16, 128, 1) == 64 and c(0, 2, 64, 16, 100, 1) == -1 and c(5, 2, 64, 16, 128, 1) == -1
     for entry, mirror in ((lib.o3d_bn_finalize, fused._BnFinArgs), (lib.o3d_bn_bwd_finalize, fused._BnBwdFinArgs)):
         jobs = (mirror * 2)()                               # zeroed jobs: `part` is NULL
         assert entry(None, 1, None) == EINVAL
