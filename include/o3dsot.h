@@ -52,11 +52,12 @@ int o3d_furthest_point_sampling_pair(const float* xyz0, int N0, int npoint0, int
 
 /* ---- gather ---------------------------------------------------------------------------
  * replaces _ext.gather_points(features, idx)              pointnet2_utils.py:92
- * feats (B,C,N), idx (B,npoint) -> out (B,C,npoint) */
+ * feats (B,C,N), idx (B,npoint) -> out (B,C,npoint).  B <= 65535.  N == 0 with anything to gather (B, C, npoint > 0) is
+ * O3D_EINVAL: no index could be in range. */
 int o3d_gather_points(const float* feats, const int32_t* idx, int B, int C, int N, int npoint,
                       float* out, void* stream);
 /* replaces _ext.gather_points_grad(grad_out, idx, N)      pointnet2_utils.py:98
- * grad_out (B,C,npoint) -> grad_feats (B,C,N); grad_feats is zero-filled by the call. */
+ * grad_out (B,C,npoint) -> grad_feats (B,C,N); grad_feats is zero-filled by the call (a refused call writes nothing). */
 int o3d_gather_points_grad(const float* grad_out, const int32_t* idx, int B, int C, int N,
                            int npoint, float* grad_feats, void* stream);
 
@@ -89,11 +90,12 @@ int o3d_sample_query(const float* xyz0, const int32_t* sidx0, int N0, int npoint
 
 /* ---- grouping -------------------------------------------------------------------------
  * replaces _ext.group_points(features, idx)               pointnet2_utils.py:217
- * feats (B,C,N), idx (B,npoint,nsample) -> out (B,C,npoint,nsample) */
+ * feats (B,C,N), idx (B,npoint,nsample) -> out (B,C,npoint,nsample).  B <= 65535.  N == 0 with anything to group
+ * (B, C, npoint * nsample > 0) is O3D_EINVAL: no index could be in range. */
 int o3d_group_points(const float* feats, const int32_t* idx, int B, int C, int N, int npoint,
                      int nsample, float* out, void* stream);
 /* replaces _ext.group_points_grad(grad_out, idx, N)       pointnet2_utils.py:237
- * grad_out (B,C,npoint,nsample) -> grad_feats (B,C,N); zero-filled by the call. */
+ * grad_out (B,C,npoint,nsample) -> grad_feats (B,C,N); zero-filled by the call (a refused call writes nothing). */
 int o3d_group_points_grad(const float* grad_out, const int32_t* idx, int B, int C, int N,
                           int npoint, int nsample, float* grad_feats, void* stream);
 
@@ -103,11 +105,12 @@ int o3d_group_points_grad(const float* grad_out, const int32_t* idx, int B, int 
 int o3d_three_nn(const float* unknown, const float* known, int B, int n, int m, float* dist2,
                  int32_t* idx, void* stream);
 /* replaces _ext.three_interpolate(features, idx, weight)  pointnet2_utils.py:162
- * feats (B,c,m), idx (B,n,3), weight (B,n,3) -> out (B,c,n) */
+ * feats (B,c,m), idx (B,n,3), weight (B,n,3) -> out (B,c,n).  m == 0 with anything to interpolate (B, c, n > 0) is
+ * O3D_EINVAL: feats has no column to read (o3d_three_nn with m == 0 returns idx 0 and dist2 inf, which must not come here). */
 int o3d_three_interpolate(const float* feats, const int32_t* idx, const float* weight, int B,
                           int c, int m, int n, float* out, void* stream);
 /* replaces _ext.three_interpolate_grad(grad_out, idx, weight, m)  pointnet2_utils.py:184
- * grad_out (B,c,n) -> grad_feats (B,c,m); zero-filled by the call. */
+ * grad_out (B,c,n) -> grad_feats (B,c,m); zero-filled by the call (a refused call writes nothing). */
 int o3d_three_interpolate_grad(const float* grad_out, const int32_t* idx, const float* weight,
                                int B, int c, int n, int m, float* grad_feats, void* stream);
 
@@ -727,7 +730,7 @@ int o3d_m2track_loss(const float* seg_logits, const int64_t* seg_label, const fl
  * get_point_to_box_distance (datasets/points_utils.py:127-143) with Box.corners (datasets/data_classes.py:
  * 226-250): out (B,N,9) = distance of every point to the box centre (channel 0) and to the 8 corners
  * (channels 1..8, the corner order of Box.corners).  wlh = (width, length, height); rot (B,3,3) row-major
- * rotation matrix of the box orientation. */
+ * rotation matrix of the box orientation.  B <= 65535 (one grid row per box), else O3D_EINVAL. */
 int o3d_boxcloud(const float* points, const float* center, const float* wlh, const float* rot, float wlh_factor,
                  int B, int N, float* out, void* stream);
 

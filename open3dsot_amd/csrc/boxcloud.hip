@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void boxcloud_kernel(const float* __restrict__
 // the box orientation -> out (B,N,9): distance to the centre (channel 0) and to corner k (channel 1+k).
 extern "C" int o3d_boxcloud(const float* points, const float* center, const float* wlh, const float* rot,
                             float wlh_factor, int B, int N, float* out, void* stream) {
-    if (B < 0 || N < 0 || (B > 0 && N > 0 && (!points || !center || !wlh || !rot || !out))) return O3D_EINVAL;
+    if (B < 0 || N < 0 || B > 65535 || (B > 0 && N > 0 && (!points || !center || !wlh || !rot || !out))) return O3D_EINVAL;
     if (B == 0 || N == 0) return O3D_OK;
     hipLaunchKernelGGL(boxcloud_kernel, dim3(o3d_cdiv(N, 256), B), dim3(256), 0, o3d_stream(stream), points, center, wlh,
                        rot, wlh_factor, N, out);

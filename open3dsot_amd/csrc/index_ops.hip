@@ -309,7 +309,7 @@ extern "C" int o3d_group_points(const float* feats, const int32_t* idx, int B, i
     if (B < 0 || C < 0 || N < 0 || npoint < 0 || nsample < 0 || B > 65535) return O3D_EINVAL;
     const long Q = (long)npoint * nsample;
     if (B == 0 || C == 0 || Q == 0) return O3D_OK;
-    if (!feats || !idx || !out || Q > 0x7fffffffL) return O3D_EINVAL;
+    if (!feats || !idx || !out || Q > 0x7fffffffL || N == 0) return O3D_EINVAL;      // N == 0: every index would be out of range
     hipLaunchKernelGGL(group_points_kernel, dim3(o3d_cdiv(Q, 256), o3d_cdiv(C, GCT), B), dim3(256), 0,
                        o3d_stream(stream), feats, idx, C, N, (int)Q, out);
     return o3d_launch_status();
@@ -321,10 +321,9 @@ extern "C" int o3d_group_points_grad(const float* grad_out, const int32_t* idx, 
     const long Q = (long)npoint * nsample;
     const size_t bytes = sizeof(float) * (size_t)B * C * N;
     if (bytes == 0) return O3D_OK;
-    if (!grad_feats) return O3D_EINVAL;
+    if (!grad_feats || (Q > 0 && (!grad_out || !idx || Q > 0x7fffffffL))) return O3D_EINVAL;   // before the zero fill: a refusal writes nothing
     if (hipMemsetAsync(grad_feats, 0, bytes, o3d_stream(stream)) != hipSuccess) return O3D_ELAUNCH;
     if (Q == 0) return O3D_OK;
-    if (!grad_out || !idx || Q > 0x7fffffffL) return O3D_EINVAL;
     hipLaunchKernelGGL(group_points_grad_kernel, dim3(o3d_cdiv(Q, 256), o3d_cdiv(C, GCT), B),
                        dim3(256), 0, o3d_stream(stream), grad_out, idx, C, N, (int)Q, grad_feats);
     return o3d_launch_status();
@@ -408,7 +407,7 @@ extern "C" int o3d_three_interpolate(const float* feats, const int32_t* idx, con
                                      int B, int c, int m, int n, float* out, void* stream) {
     if (B < 0 || c < 0 || m < 0 || n < 0 || B > 65535) return O3D_EINVAL;
     if (B == 0 || c == 0 || n == 0) return O3D_OK;
-    if (!feats || !idx || !weight || !out) return O3D_EINVAL;
+    if (!feats || !idx || !weight || !out || m == 0) return O3D_EINVAL;               // m == 0: feats has no column to read
     hipLaunchKernelGGL(three_interpolate_kernel, dim3(o3d_cdiv(n, 256), o3d_cdiv(c, GCT), B),
                        dim3(256), 0, o3d_stream(stream), feats, idx, weight, c, m, n, out);
     return o3d_launch_status();
@@ -420,10 +419,9 @@ extern "C" int o3d_three_interpolate_grad(const float* grad_out, const int32_t* 
     if (B < 0 || c < 0 || m < 0 || n < 0 || B > 65535) return O3D_EINVAL;
     const size_t bytes = sizeof(float) * (size_t)B * c * m;
     if (bytes == 0) return O3D_OK;
-    if (!grad_feats) return O3D_EINVAL;
+    if (!grad_feats || (n > 0 && (!grad_out || !idx || !weight))) return O3D_EINVAL;            // before the zero fill: a refusal writes nothing
     if (hipMemsetAsync(grad_feats, 0, bytes, o3d_stream(stream)) != hipSuccess) return O3D_ELAUNCH;
     if (n == 0) return O3D_OK;
-    if (!grad_out || !idx || !weight) return O3D_EINVAL;
     hipLaunchKernelGGL(three_interpolate_grad_kernel, dim3(o3d_cdiv(n, 256), o3d_cdiv(c, GCT), B),
                        dim3(256), 0, o3d_stream(stream), grad_out, idx, weight, c, n, m, grad_feats);
     return o3d_launch_status();
