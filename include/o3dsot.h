@@ -1104,6 +1104,53 @@ int o3d_track_score(const float* a, const float* b, const int32_t* valid, int n,
                     float* distances, const float* thr_s, int ns, const float* thr_p, int np, int64_t* cnt_s, int64_t* cnt_p,
                     int64_t* total, void* stream);
 
+/* ---- the lifecycle of a scene tracker's K slots as device work (tracking.ManagedSceneTracker / ManagedMotionSceneTracker;
+ * DESIGN.md section 12j): per frame, associate a set of detections with the K tracks, retire the lost tracks, enroll the
+ * unmatched detections into free slots.  D is 0..O3D_SCENE_MAX_DETECTIONS, K 1..O3D_CROP_MULTI_MAX_TARGETS.
+ *
+ * o3d_scene_pair_scores (csrc/metrics.hip): tracks (K,15), active (K) int32, dets (D,15), n_det (1) int32 on the device, clamped
+ * to [0, D] -> overlaps, distances (K,D) float32.  For an active k and d < n_det the pair (a = tracks[k], b = dets[d]) is
+ * scored by the device function o3d_track_score calls, so the two numbers carry o3d_track_score's bits for that pair; rows of
+ * inactive slots and columns d >= n_det are written overlap -1, distance +inf.  One thread per pair.  D == 0: no launch.
+ *
+ * o3d_scene_manage (csrc/scene.hip), ONE launch of one workgroup, after frame t's o3d_track_offset_box_multi; t = frame[0] - 1
+ * is read on the device.  State: cur (K,15), yaw_state (K,10), canon_wlh (K,3), results (T,K,15), active (K) int32, slot
+ * (K, O3D_SCENE_SLOT_COLS) int32 = {id, misses, starved, start} with id -1 for a free slot (active == (id >= 0)), next_id (1)
+ * int32.  counts: the frame's crop counts, slot k's at counts[2 k + count_col] (count_col 0 | 1).  In this order:
+ *   admissible   active[k] && d < n_det && overlaps[k,d] >= min_iou && distances[k,d] <= max_dist, as fp32 compares (a NaN is
+ *                never admissible)
+ *   match        the admissible pairs ordered by (overlap descending, distance ascending, k ascending, d ascending) are walked
+ *                and a pair is taken when its track and its detection are both still unmatched -> match[k], det_match[d], an
+ *                index or -1: a pure function of the inputs (LDS keeps every free track's first free pair of its row and every
+ *                free detection's first free pair of its column; per round every pair that is both is taken, and only the rows
+ *                and columns whose kept partner was taken are scanned again; no atomics)
+ *   counters     of every slot active on entry: with has_dets != 0 a matched slot's misses = 0, an unmatched slot's += 1; with
+ *                min_points > 0, starved = (count < min_points) ? starved + 1 : 0 (on every frame, whatever has_dets)
+ *   retire       misses > max_misses || (min_points > 0 && starved > max_starved): active = 0, id = -1; the box stays
+ *   enroll       (enroll != 0) the unmatched detections d < n_det whose 15 numbers are finite, in ascending d, take the free
+ *                slots (those retired just now included) in ascending k: cur[k] = dets[d], yaw_state[k] = {R, 0}, canon_wlh[k]
+ *                = wlh, results[t][k] = dets[d] (0 <= t < T), bank_state_next[k] = {0, 0} (NULL: the motion tracker has no
+ *                bank), active[k] = 1, slot[k] = {next_id++, 0, 0, t}; those left over are counted: dropped
+ *   lanes        (K, O3D_LANE_COLS), the NEXT frame's lane table: row k = {1, first, has_crop, 0, -1, -1, 0} with first = slot k
+ *                was enrolled in this call and has_crop = first || rule != O3D_BANK_FIRST (rule -1, the motion tracker: 1)
+ *   logs         row t (0 <= t < T) of ids_log (T,K) = the new id of a slot enrolled in this call, else its id on entry;
+ *                match_log (T,K) = match; dropped_log (T) = dropped
+ * All stores are ordinary vector stores.  has_dets == 0 (the caller passed no detection set for this frame): n_det counts as 0
+ * and the misses stay as they are; the call is still made on every frame, because it is what clears `first`.
+ * Both entries return O3D_EINVAL before any HIP call for a NULL operand (bank_state_next excepted; overlaps, distances, dets
+ * and n_det may be NULL when D == 0), K or D outside the ranges above, dim not 2 | 3, up not 1 | 2, T < 1, count_col not 0 | 1,
+ * rule outside -1..3. */
+#define O3D_SCENE_MAX_DETECTIONS 1024
+#define O3D_SCENE_SLOT_COLS 4
+int o3d_scene_pair_scores(const float* tracks, const int32_t* active, int K, const float* dets, const int32_t* n_det, int D,
+                          int dim, int up, float* overlaps, float* distances, void* stream);
+int o3d_scene_manage(const float* overlaps, const float* distances, const float* dets, const int32_t* n_det, int K, int D,
+                     float* cur, float* yaw_state, float* canon_wlh, float* results, int T, const int32_t* frame,
+                     int32_t* active, int32_t* slot, int32_t* next_id, const int32_t* counts, int count_col,
+                     int32_t* bank_state_next, int32_t* lanes, int rule, int32_t* ids_log, int32_t* match_log,
+                     int32_t* dropped_log, float min_iou, float max_dist, int max_misses, int min_points, int max_starved,
+                     int enroll, int has_dets, void* stream);
+
 /* ---- the preload crop of a dataset reader (csrc/preload.hip; open3dsot_amd/datasets.py is the caller) ----------------------
  * What kittiDataset._get_frame_from_anno does per annotated object per frame -- PointCloud.transform in camera mode, then
  * crop_pc_axis_aligned(pc, box, offset=preload_offset) -- for a chunk of raw frames in HBM: three launches and one read-back.

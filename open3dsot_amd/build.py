@@ -31,6 +31,7 @@ SOURCES = [
     ("track.hip", ["-ffp-contract=off"]),      # the crop's operation order is part of its contract (tests/tracking_oracle.py)
     ("train_batch.hip", ["-ffp-contract=off"]),      # calls track.hip's crop_test / gather_row (csrc/track_common.hpp): same contract
     ("metrics.hip", ["-ffp-contract=off"]),      # the scoring arithmetic's operation order is stated (tests/metrics_oracle.py)
+    ("scene.hip", ["-ffp-contract=off"]),      # the lifecycle's order of decisions is stated (tests/scene_manage_oracle.py)
     ("preload.hip", ["-ffp-contract=off"]),      # the camera transform's fp64 operation order is stated (tests/kitti_oracle.py)
     ("optim.hip", ["-ffp-contract=off"]),      # the update rules' operation order is stated (tests/optim_oracle.py)
     ("capi_misc.hip", []),

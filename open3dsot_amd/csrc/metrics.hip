@@ -2,6 +2,8 @@
 // launch, with optional accumulation of the Success / Precision threshold counts (TorchSuccess / TorchPrecision, :75-125).
 //
 //   o3d_track_score       a (n,15) annotation boxes, b (n,15) result boxes -> overlaps (n), distances (n), counters
+//   o3d_scene_pair_scores tracks (K,15) x detections (D,15) -> overlaps (K,D), distances (K,D): the same score_pair for every
+//                         pair of a scene tracker's frame (csrc/scene.hip reads the two matrices)
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -199,7 +201,35 @@ __global__ __launch_bounds__(SCORE_WG) void score_kernel(ScoreArgs g) {
     }
 }
 
+// o3d_scene_pair_scores: score_pair for every (track k, detection d) of a scene tracker's frame, one thread per pair; the
+// pairs of an inactive slot or of a column at or beyond n_det[0] (clamped to [0, D]) are written -1 / +inf
+__global__ __launch_bounds__(SCORE_WG) void pair_score_kernel(const float* __restrict__ tracks, const int32_t* __restrict__ active, int K,
+                                                              const float* __restrict__ dets, const int32_t* __restrict__ n_det, int D,
+                                                              int dim, int up, float* __restrict__ overlaps,
+                                                              float* __restrict__ distances) {
+    const long i = (long)blockIdx.x * SCORE_WG + threadIdx.x;
+    if (i >= (long)K * D) return;
+    const int k = (int)(i / D), d = (int)(i % D);
+    const int n = min(max(n_det[0], 0), D);
+    float ov = -1.f, di = __int_as_float(0x7f800000);
+    if (active[k] != 0 && d < n) score_pair(tracks + 15 * (long)k, dets + 15 * (long)d, dim, up, ov, di);
+    overlaps[i] = ov;
+    distances[i] = di;
+}
+
 }  // namespace
+
+extern "C" int o3d_scene_pair_scores(const float* tracks, const int32_t* active, int K, const float* dets, const int32_t* n_det, int D,
+                                     int dim, int up, float* overlaps, float* distances, void* stream) {
+    if (K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || D < 0 || D > O3D_SCENE_MAX_DETECTIONS || (dim != 2 && dim != 3) ||
+        (up != 1 && up != 2) || !tracks || !active)
+        return O3D_EINVAL;
+    if (D == 0) return O3D_OK;
+    if (!dets || !n_det || !overlaps || !distances) return O3D_EINVAL;
+    hipLaunchKernelGGL(pair_score_kernel, dim3(o3d_cdiv((long)K * D, SCORE_WG)), dim3(SCORE_WG), 0, o3d_stream(stream), tracks, active,
+                       K, dets, n_det, D, dim, up, overlaps, distances);
+    return o3d_launch_status();
+}
 
 extern "C" int o3d_track_score(const float* a, const float* b, const int32_t* valid, int n, int dim, int up, float* overlaps,
                                float* distances, const float* thr_s, int ns, const float* thr_p, int np, int64_t* cnt_s,

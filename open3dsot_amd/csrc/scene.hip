@@ -1,0 +1,249 @@
+// The lifecycle of a scene tracker's K slots as device work (tracking.ManagedSceneTracker / ManagedMotionSceneTracker; DESIGN.md
+// section 12j): after frame t's o3d_track_offset_box_multi, ONE launch of ONE workgroup that
+//
+//   matches      the K tracks with the frame's detections, greedily, on the (K,D) overlap / distance matrices that
+//                o3d_scene_pair_scores (csrc/metrics.hip) wrote
+//   counts       each slot's missed frames and starved crops
+//   retires      the slots that are lost
+//   enrolls      the unmatched detections into the free slots, with the writes of tracking.SceneTracker.enroll
+//   writes       the next frame's lane table and row t of the three logs
+//
+// ---- the written order (tests/scene_manage_oracle.py restates it in numpy) ---------------------------------------------------------
+// t = frame[0] - 1;  n = has_dets ? min(max(n_det[0], 0), D) : 0.  Slot k is `active on entry` when active[k] != 0.
+//   admissible(k,d)   active on entry && d < n && overlaps[k,d] >= min_iou && distances[k,d] <= max_dist   (fp32 compares)
+//   order             pair p comes before pair q when, in this order of tests, p's overlap is larger, p's distance is smaller,
+//                     p's k is smaller, p's d is smaller
+//   match             walk the admissible pairs in that order; take a pair when match[k] and det_match[d] are both still -1
+//   counters          active on entry: has_dets ? (misses = match[k] >= 0 ? 0 : misses + 1);
+//                     min_points > 0 ? (starved = counts[2 k + count_col] < min_points ? starved + 1 : 0)
+//   retire            active on entry && (misses > max_misses || (min_points > 0 && starved > max_starved)): active = 0, id = -1
+//   enroll            (enroll != 0) the j-th (from 0) detection d < n with det_match[d] < 0 and 15 finite numbers, in ascending d,
+//                     takes the j-th free slot (active == 0 after retire) in ascending k; id = next_id + j; detections beyond
+//                     the free slots are `dropped`; next_id += the number enrolled
+//   lanes, logs       as include/o3dsot.h states them
+//
+// ---- the match without a sort --------------------------------------------------------------------------------------------------------
+// The order is strict and total, so the walk's result is unique.  Call a pair whose ends are both still free a mutual first when
+// it comes first among the free admissible pairs of its row AND first among the free admissible pairs of its column.  The walk
+// takes every mutual first: when it reaches the pair both ends are still free, because only a pair that shares an end with it
+// could have used one up, and all of those come later.  Taking the mutual firsts and repeating on what is left therefore gives
+// the walk's result; the first free pair of all is always a mutual first, so every round takes at least one pair until no free
+// admissible pair is left.
+//   kept state   per track k its row's first pair among the free detections (row_first[k] = its d), per detection d its column's
+//                first pair among the free tracks (col_first[d] = its k), in LDS.  A wave scans a row or a column of the two
+//                matrices in global memory, 64 entries at a time, and a wave64 butterfly picks the first.
+//   a round      (k, d) is taken when row_first[k] == d and col_first[d] == k; all such pairs at once.  A kept pair stays the
+//                first of its row (column) as long as its own detection (track) is free, so ONLY the rows whose kept detection
+//                and the columns whose kept track were just taken are scanned again.
+// Tracks that each have their own nearest detection are matched in one round; the worst case (every pair tied) is one take per
+// round, min(K, n) rounds.  The matrices are never rescanned as a whole.  No atomics anywhere: every LDS or global word has one
+// writer between two barriers, so the result is a function of the inputs.
+//
+// Thread i owns track i (i < K) and detection i (i < D); the workgroup always has 1024 threads, so that the first scan of the K rows
+// and n columns is spread over 16 waves.  A round costs three barriers (four with a scan); two of them also carry a vote: whether
+// any pair was taken (else the match is complete) and whether any row or column asked for a new scan.
+#include "o3d_common.hpp"
+
+namespace {
+
+constexpr int SCENE_MAX = 1024;
+static_assert(O3D_CROP_MULTI_MAX_TARGETS <= SCENE_MAX && O3D_SCENE_MAX_DETECTIONS <= SCENE_MAX, "one thread per track and per detection");
+static_assert(O3D_SCENE_SLOT_COLS == 4, "slot = {id, misses, starved, start}");
+
+struct ManageArgs {
+    const float* overlaps; const float* distances; const float* dets; const int32_t* n_det;
+    float* cur; float* yaw_state; float* canon_wlh; float* results; const int32_t* frame;
+    int32_t* active; int32_t* slot; int32_t* next_id; const int32_t* counts; int32_t* bank_state_next; int32_t* lanes;
+    int32_t* ids_log; int32_t* match_log; int32_t* dropped_log;
+    int K, D, T, count_col, rule, max_misses, min_points, max_starved, enroll, has_dets;
+    float min_iou, max_dist;
+};
+
+struct Cand { float ov, di; int k, d; };       // d < 0: none
+
+__device__ __forceinline__ bool before(const Cand& p, const Cand& q) {
+    if (p.d < 0) return false;
+    if (q.d < 0) return true;
+    if (p.ov != q.ov) return p.ov > q.ov;
+    if (p.di != q.di) return p.di < q.di;
+    if (p.k != q.k) return p.k < q.k;
+    return p.d < q.d;
+}
+
+// the first of the 64 lanes' candidates, in every lane
+__device__ __forceinline__ Cand wave_first(Cand c) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        Cand o{__shfl_xor(c.ov, m, 64), __shfl_xor(c.di, m, 64), __shfl_xor(c.k, m, 64), __shfl_xor(c.d, m, 64)};
+        if (before(o, c)) c = o;
+    }
+    return c;
+}
+
+// the number of threads below this one whose flag is set, and the number of all: ballots per wave, the wave sums through LDS
+__device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    if (lane == 0) s_cnt[w] = __popcll(b);
+    __syncthreads();
+    int base = 0, all = 0;
+    for (int i = 0; i < nw; ++i) {
+        base += i < w ? s_cnt[i] : 0;
+        all += s_cnt[i];
+    }
+    __syncthreads();                                   // s_cnt is free again
+    total = all;
+    return base + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
+    __shared__ int s_d[SCENE_MAX], s_need[SCENE_MAX];            // per track: row_first (-1: none); the row is to be scanned
+    __shared__ int s_k[SCENE_MAX], s_cneed[SCENE_MAX];           // per detection: col_first (-1: none); the column is to be scanned
+    __shared__ int s_match[SCENE_MAX], s_dmatch[SCENE_MAX];
+    __shared__ int s_act[SCENE_MAX];                             // per track: active on entry
+    __shared__ int s_free[SCENE_MAX], s_newid[SCENE_MAX];        // the free slots in ascending k; per slot: enrolled ? its id : -1
+    __shared__ int s_cnt[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    const int K = a.K, D = a.D;
+    const int t = a.frame[0] - 1;
+    const int n = (a.has_dets && D > 0) ? min(max(a.n_det[0], 0), D) : 0;
+    const int next0 = a.next_id[0];
+    const bool mine = tid < K;
+    const bool act_in = mine && a.active[tid] != 0;
+    s_match[tid] = -1;
+    s_dmatch[tid] = -1;
+    s_d[tid] = -1;
+    s_k[tid] = -1;
+    s_newid[tid] = -1;
+    s_act[tid] = act_in;
+    s_need[tid] = act_in && n > 0;
+    s_cneed[tid] = tid < n;
+    __syncthreads();
+
+    bool scan = n > 0;                                 // the same in every thread: some row or column is to be scanned
+    for (;;) {
+        if (scan) {
+            for (int i = w; i < K + n; i += nw) {      // the rows [0, K) and the columns [K, K + n) to scan, a wave each
+                const bool row = i < K;
+                const int r = row ? i : i - K;
+                if (!(row ? s_need[r] : s_cneed[r])) continue;      // the same word in all 64 lanes
+                Cand c{0.f, 0.f, -1, -1};
+                for (int j = lane; j < (row ? n : K); j += 64) {
+                    const int k = row ? r : j, d = row ? j : r;
+                    if (row ? s_dmatch[d] >= 0 : (!s_act[k] || s_match[k] >= 0)) continue;
+                    const Cand x{a.overlaps[(long)k * D + d], a.distances[(long)k * D + d], k, d};
+                    if (x.ov >= a.min_iou && x.di <= a.max_dist && before(x, c)) c = x;
+                }
+                c = wave_first(c);
+                if (lane == 0) {
+                    if (row) { s_d[r] = c.d; s_need[r] = 0; }
+                    else { s_k[r] = c.d >= 0 ? c.k : -1; s_cneed[r] = 0; }
+                }
+            }
+            __syncthreads();
+        }
+        const int d = mine ? s_d[tid] : -1;            // >= 0: active on entry, still unmatched, and its row has a free pair
+        const bool win = d >= 0 && s_k[d] == tid;      // a mutual first
+        if (!__syncthreads_or(win)) break;             // no free admissible pair is left (the first of all is always mutual)
+        if (win) { s_match[tid] = d; s_dmatch[d] = tid; s_d[tid] = -1; s_k[d] = -1; }
+        __syncthreads();
+        const bool row_again = d >= 0 && !win && s_dmatch[d] >= 0;         // its kept detection was taken by another track
+        const int k = tid < n ? s_k[tid] : -1;
+        const bool col_again = k >= 0 && s_match[k] >= 0;                  // its kept track took another detection
+        if (row_again) s_need[tid] = 1;
+        if (col_again) s_cneed[tid] = 1;
+        scan = __syncthreads_or(row_again || col_again) != 0;
+    }
+    __syncthreads();
+
+    // counters and retire, slot tid
+    int id = -1, misses = 0, starved = 0, start = 0;
+    bool act = act_in;
+    if (mine) {
+        const int32_t* s = a.slot + O3D_SCENE_SLOT_COLS * tid;
+        id = s[0]; misses = s[1]; starved = s[2]; start = s[3];
+    }
+    const int id_in = id;
+    if (act_in) {
+        if (a.has_dets) misses = s_match[tid] >= 0 ? 0 : misses + 1;
+        if (a.min_points > 0) starved = a.counts[2 * tid + a.count_col] < a.min_points ? starved + 1 : 0;
+        if (misses > a.max_misses || (a.min_points > 0 && starved > a.max_starved)) { act = false; id = -1; }
+    }
+
+    // enroll: the j-th unmatched finite detection takes the j-th free slot
+    bool wants = a.enroll && tid < n && s_dmatch[tid] < 0;
+    if (wants) {
+        const float* b = a.dets + 15 * (long)tid;
+        for (int i = 0; i < 15; ++i) wants = wants && isfinite(b[i]);
+    }
+    int n_free, n_want;
+    const int r_free = block_rank(mine && !act, s_cnt, n_free);
+    const int r_want = block_rank(wants, s_cnt, n_want);
+    if (mine && !act) s_free[r_free] = tid;
+    __syncthreads();
+    if (wants && r_want < n_free) {
+        const int k = s_free[r_want];
+        const float* b = a.dets + 15 * (long)tid;
+        for (int i = 0; i < 15; ++i) {
+            a.cur[15 * (long)k + i] = b[i];
+            if (t >= 0 && t < a.T) a.results[15 * ((long)t * K + k) + i] = b[i];
+        }
+        for (int i = 0; i < 9; ++i) a.yaw_state[10 * (long)k + i] = b[6 + i];
+        a.yaw_state[10 * (long)k + 9] = 0.f;
+        for (int i = 0; i < 3; ++i) a.canon_wlh[3 * (long)k + i] = b[3 + i];
+        if (a.bank_state_next) { a.bank_state_next[2 * k] = 0; a.bank_state_next[2 * k + 1] = 0; }
+        s_newid[k] = next0 + r_want;
+    }
+    __syncthreads();
+
+    // the slot row, the lane row and the logs, slot tid
+    if (mine) {
+        const int nid = s_newid[tid];
+        const bool first = nid >= 0;
+        int32_t* s = a.slot + O3D_SCENE_SLOT_COLS * tid;
+        s[0] = first ? nid : id;
+        s[1] = first ? 0 : misses;
+        s[2] = first ? 0 : starved;
+        s[3] = first ? t : start;
+        a.active[tid] = (first || act) ? 1 : 0;
+        int32_t* l = a.lanes + O3D_LANE_COLS * tid;
+        l[O3D_LANE_ACTIVE] = 1;
+        l[O3D_LANE_FIRST] = first ? 1 : 0;
+        l[O3D_LANE_HAS_CROP] = (first || a.rule != O3D_BANK_FIRST) ? 1 : 0;
+        l[O3D_LANE_T] = 0;
+        l[O3D_LANE_ROW] = -1;
+        l[O3D_LANE_REF_ROW] = -1;
+        l[O3D_LANE_REBASE] = 0;
+        if (t >= 0 && t < a.T) {
+            a.ids_log[(long)t * K + tid] = first ? nid : id_in;
+            a.match_log[(long)t * K + tid] = s_match[tid];
+        }
+    }
+    if (tid == 0) {
+        const int taken = min(n_want, n_free);
+        a.next_id[0] = next0 + taken;
+        if (t >= 0 && t < a.T) a.dropped_log[t] = n_want - taken;
+    }
+}
+
+}  // namespace
+
+extern "C" int o3d_scene_manage(const float* overlaps, const float* distances, const float* dets, const int32_t* n_det, int K, int D,
+                                float* cur, float* yaw_state, float* canon_wlh, float* results, int T, const int32_t* frame,
+                                int32_t* active, int32_t* slot, int32_t* next_id, const int32_t* counts, int count_col,
+                                int32_t* bank_state_next, int32_t* lanes, int rule, int32_t* ids_log, int32_t* match_log,
+                                int32_t* dropped_log, float min_iou, float max_dist, int max_misses, int min_points, int max_starved,
+                                int enroll, int has_dets, void* stream) {
+    if (K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || D < 0 || D > O3D_SCENE_MAX_DETECTIONS || T < 1 || (count_col != 0 && count_col != 1) ||
+        rule < -1 || rule > O3D_BANK_ALL)
+        return O3D_EINVAL;
+    if (D > 0 && (!overlaps || !distances || !dets || !n_det)) return O3D_EINVAL;
+    if (!cur || !yaw_state || !canon_wlh || !results || !frame || !active || !slot || !next_id || !counts || !lanes || !ids_log ||
+        !match_log || !dropped_log)
+        return O3D_EINVAL;
+    ManageArgs a{overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, results, frame, active, slot, next_id, counts,
+                 bank_state_next, lanes, ids_log, match_log, dropped_log, K, D, T, count_col, rule, max_misses, min_points,
+                 max_starved, enroll, has_dets, min_iou, max_dist};
+    hipLaunchKernelGGL(manage_kernel, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}

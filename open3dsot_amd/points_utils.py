@@ -686,6 +686,64 @@ def lane_start(gt, lanes, cur, yaw_state, wlh, state=None):
                                                     torch.cuda.current_stream(dev).cuda_stream), "o3d_track_lane_start")
 
 
+# ---- the lifecycle of a scene tracker's slots on the device (tracking.ManagedSceneTracker; csrc/metrics.hip, csrc/scene.hip) ------
+SCENE_MAX_DETECTIONS = capi.CONSTANTS["O3D_SCENE_MAX_DETECTIONS"]
+SCENE_SLOT_COLS = capi.CONSTANTS["O3D_SCENE_SLOT_COLS"]      # slot = {id, misses, starved, start}
+
+
+def scene_pair_scores(tracks, active, dets, n_det, dim=3, up=2, out=None):
+    """One o3d_scene_pair_scores launch (no sync): tracks (K,15), active (K,) int32, dets (D,15), n_det (1,) int32 on the device
+    -> (overlaps, distances) (K,D) float32, written into out = (overlaps, distances) when given.  Pair (k, d) holds what
+    metrics.score_boxes(tracks[k], dets[d]) gives, bit for bit; inactive rows and columns >= n_det hold -1 / +inf."""
+    what = "scene_pair_scores"
+    K, D = tracks.shape[0], dets.shape[0]
+    _f32(tracks, (K, 15), what)
+    _f32(dets, (D, 15), what)
+    _i32(active, K, what)
+    _i32(n_det, 1, what)
+    dev = tracks.device
+    if out is None:
+        out = (torch.empty((K, D), dtype=torch.float32, device=dev), torch.empty((K, D), dtype=torch.float32, device=dev))
+    for o in out:
+        _f32(o, (K, D), what)
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_scene_pair_scores(tracks.data_ptr(), active.data_ptr(), K, dets.data_ptr(), n_det.data_ptr(), D,
+                                                     int(dim), int(up), out[0].data_ptr(), out[1].data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream), what)
+    return out
+
+
+def scene_manage(overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, results, frame, active, slot, next_id, counts,
+                 count_col, bank_state_next, lanes, rule, ids_log, match_log, dropped_log, min_iou=0.0, max_dist=float("inf"),
+                 max_misses=2, min_points=0, max_starved=0, enroll=True, has_dets=True):
+    """One o3d_scene_manage launch (no sync) after the frame's offset_box_multi: the greedy match on overlaps / distances (K,D),
+    the miss and starvation counters, retire, enroll and the next frame's lane table, as include/o3dsot.h states them.  dets
+    (D,15), n_det (1,) int32, cur (K,15), yaw_state (K,10), canon_wlh (K,3), results (T,K,15), frame (1,) int32, active (K,) int32,
+    slot (K,SCENE_SLOT_COLS) int32, next_id (1,) int32, counts (K,2) int32 with count_col 0 | 1, bank_state_next (K,2) int32 |
+    None, lanes (K,LANE_COLS) int32, rule: a shape_aggregation name | None (the motion tracker), ids_log / match_log (T,K) and
+    dropped_log (T,) int32."""
+    what = "scene_manage"
+    K, D, T = cur.shape[0], dets.shape[0], results.shape[0]
+    for t, shape in ((overlaps, (K, D)), (distances, (K, D)), (dets, (D, 15)), (cur, (K, 15)), (yaw_state, (K, 10)),
+                     (canon_wlh, (K, 3)), (results, (T, K, 15))):
+        _f32(t, shape, what)
+    for t, numel in ((n_det, 1), (frame, 1), (active, K), (slot, K * SCENE_SLOT_COLS), (next_id, 1), (counts, 2 * K),
+                     (ids_log, T * K), (match_log, T * K), (dropped_log, T)):
+        _i32(t, numel, what)
+    assert _lane_table(lanes, what) == K
+    if bank_state_next is not None:
+        _i32(bank_state_next, 2 * K, what)
+    dev = cur.device
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_scene_manage(
+            overlaps.data_ptr(), distances.data_ptr(), dets.data_ptr(), n_det.data_ptr(), K, D, cur.data_ptr(), yaw_state.data_ptr(),
+            canon_wlh.data_ptr(), results.data_ptr(), T, frame.data_ptr(), active.data_ptr(), slot.data_ptr(), next_id.data_ptr(),
+            counts.data_ptr(), int(count_col), bank_state_next.data_ptr() if bank_state_next is not None else None, lanes.data_ptr(),
+            BANK_RULES[rule] if rule is not None else -1, ids_log.data_ptr(), match_log.data_ptr(), dropped_log.data_ptr(),
+            float(min_iou), float(max_dist), int(max_misses), int(min_points), int(max_starved), int(bool(enroll)),
+            int(bool(has_dets)), torch.cuda.current_stream(dev).cuda_stream), what)
+
+
 def _box_device(box, what):
     """the GPU a box lives on (a (15,) tensor or a (center, wlh, rot) triple of tensors); anything else is refused"""
     parts = (box,) if torch.is_tensor(box) else tuple(box)

@@ -52,6 +52,11 @@ a target table uploaded once, the lane kernels of the test epoch on a lane table
 slot takes a new object in mid-stream without a host stop.  MultiTargetTracker / MultiMotionTracker stay the K-target loops of
 sampling="reference".
 
+The slots' lifecycle on the device (ManagedSceneTracker, ManagedMotionSceneTracker, managed_scene_tracker_for; DESIGN.md section
+12j): a scene tracker whose update() also takes the frame's detections as a device tensor.  Two launches after the box update
+(o3d_scene_pair_scores, o3d_scene_manage) match detections and tracks, retire the lost slots, enroll the unmatched detections
+into free slots and write the next frame's lane table: objects enter and leave without a host stop.
+
 The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
 (`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
 """
@@ -1605,6 +1610,256 @@ class MotionSceneTracker(_Scene, _DeviceTracker):
         return scene_motion_overflow(log, self._start, self.crop_buf.shape[2])
 
 
+# ---- the slots' lifecycle on the device: associate detections, retire, enroll ------------------------------
+_MANAGE_DEFAULTS = dict(min_iou=0.0, max_dist=float("inf"), max_misses=2, min_points=0, max_starved=0, enroll=True, max_detections=256)
+
+
+def _unit_box():
+    """the box a free slot holds until a detection takes it: centre 0, wlh (1,1,1), identity"""
+    b = np.zeros((15,), np.float32)
+    b[3:6], b[[6, 10, 14]] = 1.0, 1.0
+    return b
+
+
+class _Managed:
+    """What ManagedSceneTracker and ManagedMotionSceneTracker put on top of a scene tracker: per frame, after the box update, two
+    launches (o3d_scene_pair_scores, o3d_scene_manage) that match the frame's detections with the K tracks, count missed frames
+    and starved crops, retire the lost slots, enroll the unmatched detections into the free slots with SceneTracker.enroll's
+    writes, and write the NEXT frame's lane table.  The lane table therefore belongs to the device (no _pending, no _lane_event
+    upload) and both crop groups are made on every frame, because the host no longer knows which slot is `first`.
+
+      slot (K,4) int32        {id, misses, starved, start} per slot, id -1 = free; `active` stays id >= 0
+      next_id (1,) int32      the next track id
+      ids_log, match_log (T,K), dropped_log (T,)    row t: who held slot k after frame t, the detection it matched, the
+                                                     detections that found no free slot; they grow with `boxes`
+
+    manage = dict(min_iou, max_dist, max_misses, min_points, max_starved, enroll, max_detections); the overlap and the distance
+    are metrics.score_boxes' with the model config's IoU_space / up_axis, as in score()."""
+
+    def _managed_state(self, manage):
+        from . import metrics as MT
+        p = dict(_MANAGE_DEFAULTS)
+        unknown = set(manage or {}) - set(p)
+        if unknown:
+            raise ValueError("%s: manage has no %s; expected %s" % (self._NAME, sorted(unknown), sorted(p)))
+        p.update(manage or {})
+        self.max_detections = int(p.pop("max_detections"))
+        if not 1 <= self.max_detections <= PU.SCENE_MAX_DETECTIONS:
+            raise ValueError("%s: max_detections must be 1..%d" % (self._NAME, PU.SCENE_MAX_DETECTIONS))
+        self.manage = dict(min_iou=float(p["min_iou"]), max_dist=float(p["max_dist"]), max_misses=int(p["max_misses"]),
+                           min_points=int(p["min_points"]), max_starved=int(p["max_starved"]), enroll=bool(p["enroll"]))
+        cfg = self.model.config
+        self.score_dim = int(getattr(cfg, "IoU_space", 3))
+        self.score_up = MT.up_index(tuple(getattr(cfg, "up_axis", (0, 0, 1))))
+        K, T, i32 = self.K, self.boxes.shape[0], dict(dtype=torch.int32, device=self.dev)
+        self.slot = torch.zeros((K, PU.SCENE_SLOT_COLS), **i32)
+        self.next_id = torch.zeros((1,), **i32)
+        self.n_det = torch.zeros((1,), **i32)
+        self.ids_log, self.match_log = torch.full((T, K), -1, **i32), torch.full((T, K), -1, **i32)
+        self.dropped_log = torch.zeros((T,), **i32)
+        self._pairs = torch.empty((2, K * self.max_detections), dtype=torch.float32, device=self.dev)
+        self._no_dets = torch.empty((0, 15), dtype=torch.float32, device=self.dev)
+
+    def init(self, points0, boxes0):
+        """n0 <= K boxes: slot k < n0 follows boxes0[k] with id k; the other slots are free and hold the unit box."""
+        if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray):
+            b = PU._dev32(boxes0, self.dev).reshape(-1, 15)
+        else:
+            b = torch.stack([PU.pack_box(x, self.dev) for x in boxes0]) if len(boxes0) else torch.zeros((0, 15), device=self.dev)
+        n0, K = b.shape[0], self.K
+        if n0 > K:
+            raise ValueError("%d boxes for %d slots" % (n0, K))
+        padded = torch.from_numpy(np.tile(_unit_box(), (K, 1))).to(self.dev)
+        padded[:n0].copy_(b)
+        boxes = super().init(points0, padded)
+        self._pending = set()                              # the parent's host copy of `first`: not kept here, the device owns it
+        occupied = np.arange(K) < n0
+        slot = np.zeros((K, PU.SCENE_SLOT_COLS), np.int32)
+        slot[:, 0] = np.where(occupied, np.arange(K), -1)
+        self.slot.copy_(torch.from_numpy(slot))
+        self.active.copy_(torch.from_numpy(occupied.astype(np.int32)))
+        self.next_id.fill_(n0)
+        self.ids_log.fill_(-1)
+        self.match_log.fill_(-1)
+        self.dropped_log.zero_()
+        self.ids_log[0].copy_(self.slot[:, 0])
+        self.lanes.copy_(torch.from_numpy(scene_lane_rows(K, np.flatnonzero(occupied).tolist(), getattr(self, "aggregation", None))))
+        return boxes
+
+    def _grow_boxes(self):
+        T = self.boxes.shape[0]
+        super()._grow_boxes()
+        if self.boxes.shape[0] != T:                       # the three logs grow with boxes
+            for name, fill in (("ids_log", -1), ("match_log", -1), ("dropped_log", 0)):
+                old = getattr(self, name)
+                log = torch.full((self.boxes.shape[0],) + old.shape[1:], fill, dtype=torch.int32, device=self.dev)
+                log[:T].copy_(old)
+                setattr(self, name, log)
+
+    def update(self, points, detections=None, n_detections=None, ref_boxes=None):
+        """One frame, only enqueued.  detections: (D,15) boxes, D <= max_detections, or None (no detection set for this frame:
+        nothing is matched, missed or enrolled; the starvation rule and the lane table still run).  A device float32 tensor
+        keeps the frame free of host stops; a host array or a list of boxes travels as one asynchronous copy from pinned
+        memory.  n_detections: None (= D), an int, or a device int32 (1,) tensor: the first n_detections rows count.
+        -> a (K,15) device VIEW of the boxes after the frame, the enrolled ones included."""
+        if ref_boxes is not None:
+            raise ValueError("%s.update takes no ref_boxes: a managed tracker starts every slot from its own last box" % self._NAME)
+        dets = self._detections(detections)
+        PU._need_gpu(points, self._NAME + ".update")
+        if self.t < 1:
+            raise RuntimeError(self._NAME + ".update before init")
+        with torch.cuda.device(self.dev):
+            if dets is not None and not dets.is_cuda:
+                dets = dets.pin_memory().to(self.dev, non_blocking=True)
+            n_det = self.n_det
+            if dets is not None and torch.is_tensor(n_detections):
+                PU._i32(n_detections, 1, self._NAME + ".update")
+                n_det = n_detections
+            elif dets is not None:
+                n_det.fill_(dets.shape[0] if n_detections is None else int(n_detections))
+            return self._update(points.contiguous().float(), dets, n_det)
+
+    def _detections(self, detections):
+        """the checks of update()'s detection set, before anything touches the device -> a (D,15) float32 tensor | None"""
+        if detections is None:
+            return None
+        if torch.is_tensor(detections):
+            d = detections.to(torch.float32).reshape(-1, 15).contiguous()
+        elif isinstance(detections, np.ndarray):
+            d = torch.from_numpy(np.ascontiguousarray(detections, dtype=np.float32).reshape(-1, 15))
+        else:
+            d = torch.stack([PU.pack_box(x, "cpu") for x in detections]) if len(detections) else torch.zeros((0, 15))
+        if d.shape[0] > self.max_detections:
+            raise ValueError("%s.update: %d detections for max_detections = %d" % (self._NAME, d.shape[0], self.max_detections))
+        return d
+
+    def _manage(self, dets, n_det, count_col, bank_state_next, rule):
+        """the two management launches of a frame, after its offset_box_multi"""
+        has = dets is not None
+        if not has:
+            dets = self._no_dets
+        K, D = self.K, dets.shape[0]
+        ov, di = (self._pairs[i, :K * D].view(K, D) for i in (0, 1))
+        if D:
+            PU.scene_pair_scores(self.cur, self.active, dets, n_det, self.score_dim, self.score_up, out=(ov, di))
+        PU.scene_manage(ov, di, dets, n_det, self.cur, self.yaw_state, self.canon_wlh, self.boxes, self.frame, self.active, self.slot,
+                        self.next_id, self.counts2, count_col, bank_state_next, self.lanes, rule, self.ids_log, self.match_log,
+                        self.dropped_log, has_dets=has, **self.manage)
+
+    # ---- manual events: the parent's device writes plus the slot row, the lane row and the id ---------------------------------------
+    def enroll(self, k, box):
+        """SceneTracker.enroll as device writes into the managed state: slot k takes the next id."""
+        super().enroll(k, box)
+        k = int(k) % self.K
+        self._pending.clear()                              # `first` is written into the device's lane row below
+        with torch.cuda.device(self.dev):
+            self.slot[k].zero_()
+            self.slot[k, 0:1].copy_(self.next_id)
+            self.slot[k, 3] = self.t - 1
+            self.next_id += 1
+            self.lanes[k, PU.LANE["first"]] = 1
+            self.lanes[k, PU.LANE["has_crop"]] = 1
+            self.ids_log[self.t - 1, k:k + 1].copy_(self.slot[k, 0:1])
+
+    def retire(self, k):
+        """SceneTracker.retire, and slot k is free: a later detection may take it."""
+        super().retire(k)
+        self.slot[int(k) % self.K, 0] = -1
+
+    # ---- read-backs, one sync each -----------------------------------------------------------------------------------------------------
+    def status(self):
+        """{active, ids, misses, starved, start}, each (K,) int32 on the host"""
+        s = torch.cat([self.active.view(-1, 1), self.slot], 1).cpu().numpy()
+        return dict(active=s[:, 0], ids=s[:, 1], misses=s[:, 2], starved=s[:, 3], start=s[:, 4])
+
+    def events(self):
+        """(ids_log (t,K), match_log (t,K), dropped_log (t,)) int32 on the host, rows [0:t]"""
+        t, K = self.t, self.K
+        e = torch.cat([self.ids_log[:t], self.match_log[:t], self.dropped_log[:t, None]], 1).cpu().numpy()
+        return e[:, :K], e[:, K:2 * K], e[:, 2 * K]
+
+    def tracks(self):
+        """{id: (first_frame, boxes (n,15))}: every object ever followed, its boxes from the frame it was enrolled on (or 0) to
+        the last frame its slot carried its id, from results() and ids_log"""
+        res, ids = self.results(), self.events()[0]
+        out = {}
+        for f, k in zip(*np.nonzero(ids >= 0)):
+            out.setdefault(int(ids[f, k]), (int(f), []))[1].append(res[f, k])
+        return {i: (f, np.stack(rows)) for i, (f, rows) in out.items()}
+
+    def overflow(self, per_target=False):
+        """the scene tracker's overflow(), with every slot's start frame taken from `slot`"""
+        self._start[:] = self.status()["start"]
+        return super().overflow(per_target)
+
+
+class ManagedSceneTracker(_Managed, SceneTracker):
+    """SceneTracker with the slots' lifecycle on the device:
+
+        trk = ManagedSceneTracker(model, K, manage=dict(max_misses=1, max_dist=3.0))
+        trk.init(points0, boxes0)                          # n0 <= K boxes; the other slots are free
+        boxes = trk.update(points, detections, n)          # detections (D,15) and n (1,) int32 on the device: no host stop
+        trk.status(); trk.events(); trk.tracks()           # one sync each
+
+    A frame is SceneTracker's with the model crop made for every slot, followed by the two management launches of _Managed.  A
+    free slot still runs through the crops and the batch-K forward (the batch keeps its shape)."""
+    _NAME = "ManagedSceneTracker"
+
+    def __init__(self, model, n_targets, manage=None, **kw):
+        super().__init__(model, n_targets, **kw)
+        if self.needs_ref_box:
+            raise ValueError("%s: reference_BB %r needs the caller's ref_boxes, which a managed tracker does not take"
+                             % (self._NAME, self.reference_BB))
+        self._managed_state(manage)
+
+    def _update(self, pts, dets, n_det):
+        c = self
+        c._grow_boxes()
+        c.ref.copy_(c.cur)
+        c._crop_scene([pts, c.prev_points])
+        c._log_scene_counts([True, True])
+        state_in, state_out, totals = c._states[c.t & 1]
+        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, c.lanes, state_in, state_out)
+        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
+                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
+        c._boxcloud()
+        best, _ = c._network()
+        PU.offset_box_multi(c.ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
+                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        c._manage(dets, n_det, 0, state_out, c.aggregation)        # state_out: what the next frame reads as state_in
+        return c._done(pts, None)
+
+    def _overflow_rows(self, log):
+        if self.aggregation == "first":        # the model crop is made on every frame, but banked on a slot's first frame only
+            log = log.copy()
+            for k, s in enumerate(self._start):
+                log[int(s) + 2:, k, 1] = -1
+        return super()._overflow_rows(log)
+
+
+class ManagedMotionSceneTracker(_Managed, MotionSceneTracker):
+    """MotionSceneTracker with the slots' lifecycle on the device: ManagedSceneTracker's surface for the motion tracker.  The
+    starvation rule reads the current-frame crop's count (column 1); there is no template bank to restart."""
+    _NAME = "ManagedMotionSceneTracker"
+
+    def __init__(self, model, n_targets, manage=None, **kw):
+        super().__init__(model, n_targets, **kw)
+        self._managed_state(manage)
+
+    def _update(self, pts, dets, n_det):
+        c = self
+        c._grow_boxes()
+        c._crop_scene([c.prev_points, pts])
+        c._log_scene_counts([True, True])
+        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.draw_src, c.canon_wlh, c.lanes, c.inputs["points"],
+                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        est = c._network()
+        PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
+                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        c._manage(dets, n_det, 1, None, None)
+        return c._done(pts, None)
+
+
 def tracker_for(model, **kw):
     """the tracker class of a model: MotionSequenceTracker for m2track.M2TRACK, SequenceTracker for the matching trackers"""
     return (MotionSequenceTracker if _is_motion(model) else SequenceTracker)(model, **kw)
@@ -1618,6 +1873,12 @@ def multi_tracker_for(model, n_targets, **kw):
 def scene_tracker_for(model, n_targets, **kw):
     """the scene tracker class of a model: MotionSceneTracker for m2track.M2TRACK, SceneTracker for the matching trackers"""
     return (MotionSceneTracker if _is_motion(model) else SceneTracker)(model, n_targets, **kw)
+
+
+def managed_scene_tracker_for(model, n_targets, **kw):
+    """scene_tracker_for with the slots' lifecycle on the device: ManagedMotionSceneTracker for m2track.M2TRACK,
+    ManagedSceneTracker for the matching trackers; kw: the scene tracker's keywords and manage=dict(...)"""
+    return (ManagedMotionSceneTracker if _is_motion(model) else ManagedSceneTracker)(model, n_targets, **kw)
 
 
 def lane_tracker_for(model, lanes, **kw):

@@ -53,6 +53,14 @@ the read-back of the metric, --repeats times in turn.  The tracklets are --disti
 rotation.  Prints one JSON line: tracklet-frames/s of both (median, smallest and largest run), their ratio, the schedule's
 steps and idle-lane share, overflow() and the batch-L forward replay.  With --sampling table a second lane tracker with
 sampling="table" joins the rotation: tracklet-frames/s of both lane epochs and their ratio.
+
+--targets K --manage D [--sampling device | table] [--model M2TRACK]: the managed scene tracker
+(tracking.managed_scene_tracker_for(model, K): the slots' lifecycle as two device launches per frame) with D
+device-resident detections per frame (the ground truth of the first min(D, K) targets, then boxes far away) against the plain
+scene tracker at the same K, on the same scene, model and sampling ("table" unless given), both timed as above, --repeats times
+in turn.  Prints one JSON line: ms per frame of both and their ratio, the device time of the two management launches (200 calls
+between two events: o3d_scene_pair_scores alone, then both) and of the frame's crop call with and without the model-crop group
+(the managed tracker always makes it), the managed tracker's final status and whether both replay a graph.
 """
 import argparse
 import json
@@ -327,6 +335,95 @@ def scene_main(args, dev):
             np.linalg.norm(boxes["scene"][..., :3] - boxes["reference"][..., :3], axis=-1).max())}))
 
 
+def device_ms(fn, n=200):
+    """ms per call of fn between two events on the current stream, after 10 calls of warm-up"""
+    for _ in range(10):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def manage_main(args, dev):
+    """--targets K --manage D: the managed scene tracker with D device detections per frame against the plain scene tracker"""
+    K, D = args.targets, args.manage
+    sampling = args.sampling if args.sampling in tracking.FREE_RUNNING else "table"
+    motion = args.model.upper() == "M2TRACK"
+    if motion:
+        model, cfg = motion_model(dev)
+    else:
+        cfg = dict(trackers.BAT_CAR if args.model.upper() == "BAT" else trackers.P2B_CAR)
+        cfg.update(TO.TEST_KEYS)
+        model = TO.init_weights(trackers.get_model(args.model)(trackers.make_config(cfg))).to(dev).eval()
+    frames, gt = synth.make_scene(args.seed, args.frames, max(args.points // K, 1024), K)
+    dframes = [torch.from_numpy(f).to(dev) for f in frames]
+    far = np.tile(gt[:, :1], (1, max(D - K, 0), 1))                    # detections that match nothing: 10 km away, 10 m apart
+    far[:, :, 0] += 1e4 + 10.0 * np.arange(far.shape[1])[None, :]
+    dets = [torch.from_numpy(np.ascontiguousarray(np.concatenate([gt[t, :min(D, K)], far[t]], 0))).to(dev) for t in range(args.frames)]
+    n_det = torch.tensor([D], dtype=torch.int32, device=dev)
+    warm = min(20, args.frames)
+    scratch = first_capture(model, dframes, gt[0, 0])      # noqa: F841  (kept alive: the first tracker of a process is the slow one)
+    trks = {"managed": tracking.managed_scene_tracker_for(model, K, sampling=sampling, manage=dict(max_detections=max(D, 1))),
+            "scene": tracking.scene_tracker_for(model, K, sampling=sampling)}
+
+    def run(m, n):
+        trk = trks[m]
+        trk.init(dframes[0], gt[0])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t in range(1, n):
+            if m == "managed":
+                trk.update(dframes[t], dets[t], n_det)
+            else:
+                trk.update(dframes[t])
+        t1 = time.perf_counter()
+        trk.results()                                                   # the one read-back of the boxes (a sync)
+        return time.perf_counter() - t0, t1 - t0
+    for m in trks:
+        run(m, warm)                                                    # capture + warm-up
+    times, host = {m: [] for m in trks}, {m: [] for m in trks}
+    for _ in range(args.repeats):                                       # the two loops in turn: what disturbs one disturbs the other
+        for m in trks:
+            dt, dh = run(m, args.frames)
+            times[m].append(dt)
+            host[m].append(dh)
+    n = args.frames - 1
+    ms = {m: sorted(1e3 * dt / n for dt in times[m]) for m in trks}
+    mid = {m: ms[m][len(ms[m]) // 2] for m in trks}
+    host_mid = {m: sorted(1e3 * dt / n for dt in host[m])[len(host[m]) // 2] for m in trks}
+    man, scn = trks["managed"], trks["scene"]
+    status, next_id, dropped = man.status(), int(man.next_id), int(man.events()[2][-1])      # before the timing calls below
+    last = dets[args.frames - 1]
+    ov, di = (man._pairs[i, :K * D].view(K, D) for i in (0, 1))
+    scores_ms = device_ms(lambda: PU.scene_pair_scores(man.cur, man.active, last, n_det, man.score_dim, man.score_up, out=(ov, di)))
+    bank_next = None if motion else man.bank_state[man.t & 1]
+    both_ms = device_ms(lambda: man._manage(last, n_det, 1 if motion else 0, bank_next, None if motion else man.aggregation))
+    pts, prev = dframes[-1], dframes[-2]
+    crop_both_ms = device_ms(lambda: man._crop_scene([prev, pts] if motion else [pts, prev]))
+    crop_one_ms = crop_both_ms if motion else device_ms(lambda: man._crop_scene([pts, None]))
+    print(json.dumps({
+        "workload": "%s tracking %d targets through a %d-frame, %d-point synthetic scene with %d device detections per frame (fixture "
+                    "weights, eval, fp32), median of %d runs, the two loops in turn" % (args.model.upper(), K, args.frames,
+                                                                                        int(frames[0].shape[0]), D, args.repeats),
+        "targets": K, "detections": D, "sampling": sampling,
+        "managed_ms_per_frame": round(mid["managed"], 4), "scene_ms_per_frame": round(mid["scene"], 4),
+        "managed_ms_per_frame_min_max": [round(ms["managed"][0], 4), round(ms["managed"][-1], 4)],
+        "scene_ms_per_frame_min_max": [round(ms["scene"][0], 4), round(ms["scene"][-1], 4)],
+        "managed_over_scene": round(mid["managed"] / mid["scene"], 4),
+        "managed_host_ms_per_update": round(host_mid["managed"], 4), "scene_host_ms_per_update": round(host_mid["scene"], 4),
+        "pair_scores_launch_device_ms": round(scores_ms, 5), "manage_launch_device_ms": round(both_ms - scores_ms, 5),
+        "management_device_ms_per_frame": round(both_ms, 5), "management_share_of_scene_frame": round(both_ms / mid["scene"], 4),
+        "crop_call_device_ms_both_groups": round(crop_both_ms, 5), "crop_call_device_ms_search_group_only": round(crop_one_ms, 5),
+        "hip_graph": [man.graph is not None, scn.graph is not None],
+        "managed_active_slots": int(status["active"].sum()), "managed_next_id": next_id,
+        "managed_dropped_detections_last_frame": dropped, "managed_overflow": list(man.overflow()),
+        "scene_overflow": list(scn.overflow())}))
+
+
 def lanes_main(args, dev):
     from open3dsot_amd import metrics as MT
     L = args.lanes
@@ -423,6 +520,8 @@ def main():
                          "free-running loop on the reference's indices as a third loop (with --lanes: a second lane epoch)")
     ap.add_argument("--repeats", type=int, default=15, help="--sampling device, --lanes: timed runs per loop (the median is reported)")
     ap.add_argument("--lanes", type=int, default=0, help="L > 0: the test epoch on L lanes against the sequential free-running epoch")
+    ap.add_argument("--manage", type=int, default=0, help="with --targets K: D > 0 device detections per frame, the managed scene "
+                                                          "tracker against the plain one")
     ap.add_argument("--tracklets", type=int, default=64, help="--lanes: tracklets of the epoch, --frames frames each")
     ap.add_argument("--distinct", type=int, default=8, help="--lanes: different synthetic sequences, used in rotation")
     args = ap.parse_args()
@@ -434,6 +533,10 @@ def main():
         if args.targets > 0 or args.frames < 2:
             raise SystemExit("--lanes times the test epoch: no --targets, at least 2 frames per tracklet")
         return lanes_main(args, dev)
+    if args.manage > 0:
+        if args.targets < 1 or args.frames < 3:
+            raise SystemExit("--manage D times the managed scene tracker: it needs --targets K and at least 3 frames")
+        return manage_main(args, dev)
     if args.targets > 0:
         if args.sampling in tracking.FREE_RUNNING:
             if args.frames < 2:
