@@ -1151,6 +1151,49 @@ int o3d_scene_manage(const float* overlaps, const float* distances, const float*
                      int32_t* dropped_log, float min_iou, float max_dist, int max_misses, int min_points, int max_starved,
                      int enroll, int has_dets, void* stream);
 
+/* ---- scoring a managed scene on the device: the CLEAR-MOT bookkeeping (metrics.ClearMOT) -------------
+ * Ground truth gt (F,G,15) with gt_valid (F,G) int32 (0: object g has no annotation in frame f) against the tracked run's
+ * hyp (F,K,15) boxes and hyp_ids (F,K) int32 (the track id slot k carried in frame f, < 0: none), all on the device.  G and K
+ * are 1..O3D_CROP_MULTI_MAX_TARGETS.
+ *
+ * o3d_scene_pair_scores_frames (csrc/metrics.hip) -> overlaps, distances (F,G,K) float32.  Pair (f,g,k) with gt_valid[f,g] != 0
+ * && hyp_ids[f,k] >= 0 is scored by the device function of o3d_track_score and o3d_scene_pair_scores (a = gt[f,g], b =
+ * hyp[f,k]) and carries their bits for that pair; every other pair is written overlap -1, distance +inf.  One thread per pair
+ * on a 64-bit index.  F >= 0; F == 0 returns 0 without a launch.
+ *
+ * o3d_scene_mot_walk (csrc/scene.hip): ONE launch of one workgroup of 1024 threads walks frames 0..F-1 in order (the loop over
+ * the frames is inside the kernel), F in 0..O3D_SCENE_MOT_MAX_FRAMES; F == 0 returns 0 without a launch.  State carried in
+ * device memory, read on entry and written on exit, so that a sequence may be walked in several calls: last_id (G) int32, the id
+ * g was last matched to (-1: none); tracked_prev (G) int32, whether g was matched at its most recent valid frame; ever (G)
+ * int32, whether g was ever matched.  Per frame f, in this order (ov, di = overlaps[f], distances[f]):
+ *   admissible   gt_valid[f,g] != 0 && hyp_ids[f,k] >= 0 && ov[g,k] >= min_iou && di[g,k] <= max_dist, as fp32 compares (a NaN
+ *                is never admissible)
+ *   carry        for g ascending, g valid and last_id[g] >= 0: k = the column with hyp_ids[f,k] == last_id[g].  PRECONDITION:
+ *                the non-negative ids of a frame are distinct; where they are not, the lowest such k counts.  When k exists,
+ *                (g,k) is admissible and no smaller g took column k: match[g] = k.  A kept identity wins over a better-scoring
+ *                new pairing; of two objects that remember the same id the lower g gets it.
+ *   rest         the walk of o3d_scene_manage, by the same device function, over the admissible pairs whose two ends are both
+ *                still free: ordered by (overlap descending, distance ascending, g ascending, k ascending), a pair is taken
+ *                when its object and its column are both still unmatched
+ *   count        per valid g, matched: tp += 1; idsw += 1 when last_id[g] >= 0 && last_id[g] != hyp_ids[f,match[g]]; frag += 1
+ *                when ever[g] && !tracked_prev[g]; then last_id[g] = that id, ever[g] = 1, tracked_prev[g] = 1.  Unmatched:
+ *                fn += 1, tracked_prev[g] = 0.  An invalid g leaves its state untouched.  fp = the columns with an id >= 0 left
+ *                unmatched.
+ *   rows         match_slot (F,G) int32 = k | -1; match_id (F,G) int32 = hyp_ids[f,k] | -1; match_ov, match_di (F,G) float32 =
+ *                ov[g,k], di[g,k] copied (-1 / +inf when g is invalid or unmatched); per_frame (F,8) int32 = {gt, hyp, tp, fp,
+ *                fn, idsw, frag, 0} with gt = the valid objects and hyp = the columns with an id
+ * The leftover assignment is this library's greedy rule, not the Hungarian optimum, and the identity memory is the last known
+ * match, kept through gaps.  No atomics and no flag that a thread waits on: barriers and the stream order are the only
+ * dependences, and all stores are ordinary vector stores, so the result is a function of the inputs.
+ * Both entries return O3D_EINVAL before any HIP call for a NULL operand, F, G or K outside the ranges above, dim not 2 | 3, up
+ * not 1 | 2, and (o3d_scene_pair_scores_frames) more than 2^31 - 1 workgroups of 256 pairs. */
+#define O3D_SCENE_MOT_MAX_FRAMES 4096
+int o3d_scene_pair_scores_frames(const float* gt, const int32_t* gt_valid, const float* hyp, const int32_t* hyp_ids, int F, int G,
+                                 int K, int dim, int up, float* overlaps, float* distances, void* stream);
+int o3d_scene_mot_walk(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids, int F, int G,
+                       int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev, int32_t* ever,
+                       int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di, int32_t* per_frame, void* stream);
+
 /* ---- the preload crop of a dataset reader (csrc/preload.hip; open3dsot_amd/datasets.py is the caller) ----------------------
  * What kittiDataset._get_frame_from_anno does per annotated object per frame -- PointCloud.transform in camera mode, then
  * crop_pc_axis_aligned(pc, box, offset=preload_offset) -- for a chunk of raw frames in HBM: three launches and one read-back.

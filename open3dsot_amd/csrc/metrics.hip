@@ -4,6 +4,8 @@
 //   o3d_track_score       a (n,15) annotation boxes, b (n,15) result boxes -> overlaps (n), distances (n), counters
 //   o3d_scene_pair_scores tracks (K,15) x detections (D,15) -> overlaps (K,D), distances (K,D): the same score_pair for every
 //                         pair of a scene tracker's frame (csrc/scene.hip reads the two matrices)
+//   o3d_scene_pair_scores_frames  gt (F,G,15) x hyp (F,K,15) -> overlaps (F,G,K), distances (F,G,K): the same score_pair for
+//                         every pair of every frame of a tracked run (o3d_scene_mot_walk reads them)
 //
 // A box is 15 floats: centre c (3), wlh = width, length, height (3), row-major rotation R (9).
 //
@@ -217,7 +219,37 @@ __global__ __launch_bounds__(SCORE_WG) void pair_score_kernel(const float* __res
     distances[i] = di;
 }
 
+// o3d_scene_pair_scores_frames: score_pair for every (frame f, ground-truth object g, hypothesis k) of a tracked run, one thread
+// per pair on a 64-bit index; the pairs of an object without annotation (gt_valid == 0) or of an empty column (hyp_ids < 0) are
+// written -1 / +inf
+__global__ __launch_bounds__(SCORE_WG) void pair_score_frames_kernel(const float* __restrict__ gt, const int32_t* __restrict__ gt_valid,
+                                                                     const float* __restrict__ hyp, const int32_t* __restrict__ hyp_ids,
+                                                                     long pairs, int G, int K, int dim, int up,
+                                                                     float* __restrict__ overlaps, float* __restrict__ distances) {
+    const long i = (long)blockIdx.x * SCORE_WG + threadIdx.x;
+    if (i >= pairs) return;
+    const long fg = i / K, f = fg / G;
+    const long fk = f * K + (i - fg * K);
+    float ov = -1.f, di = __int_as_float(0x7f800000);
+    if (gt_valid[fg] != 0 && hyp_ids[fk] >= 0) score_pair(gt + 15 * fg, hyp + 15 * fk, dim, up, ov, di);
+    overlaps[i] = ov;
+    distances[i] = di;
+}
+
 }  // namespace
+
+extern "C" int o3d_scene_pair_scores_frames(const float* gt, const int32_t* gt_valid, const float* hyp, const int32_t* hyp_ids, int F,
+                                            int G, int K, int dim, int up, float* overlaps, float* distances, void* stream) {
+    if (F < 0 || G < 1 || G > O3D_CROP_MULTI_MAX_TARGETS || K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || (dim != 2 && dim != 3) ||
+        (up != 1 && up != 2) || !gt || !gt_valid || !hyp || !hyp_ids || !overlaps || !distances)
+        return O3D_EINVAL;
+    const long pairs = (long)F * G * K;
+    if ((pairs + SCORE_WG - 1) / SCORE_WG > 0x7fffffffL) return O3D_EINVAL;       // more workgroups than one launch takes
+    if (F == 0) return O3D_OK;
+    hipLaunchKernelGGL(pair_score_frames_kernel, dim3(o3d_cdiv(pairs, SCORE_WG)), dim3(SCORE_WG), 0, o3d_stream(stream), gt, gt_valid,
+                       hyp, hyp_ids, pairs, G, K, dim, up, overlaps, distances);
+    return o3d_launch_status();
+}
 
 extern "C" int o3d_scene_pair_scores(const float* tracks, const int32_t* active, int K, const float* dets, const int32_t* n_det, int D,
                                      int dim, int up, float* overlaps, float* distances, void* stream) {

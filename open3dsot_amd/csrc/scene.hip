@@ -42,6 +42,9 @@
 // Thread i owns track i (i < K) and detection i (i < D); the workgroup always has 1024 threads, so that the first scan of the K rows
 // and n columns is spread over 16 waves.  A round costs three barriers (four with a scan); two of them also carry a vote: whether
 // any pair was taken (else the match is complete) and whether any row or column asked for a new scan.
+//
+// The same file holds o3d_scene_mot_walk, which scores such a run afterwards: it calls the same match,
+// greedy_match below, once per frame; its own written order stands above its kernel.
 #include "o3d_common.hpp"
 
 namespace {
@@ -96,6 +99,53 @@ __device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int& total) {
     return base + __popcll(b & ((1ull << lane) - 1ull));
 }
 
+// The match without a sort (above), for both kernels of this file: rows k < K against columns d < n of two matrices of row
+// stride D.  On entry, behind a barrier: s_match[k] / s_dmatch[d] = -1 for a free row / column (>= 0: taken before the call, or
+// not in play), s_act[k] != 0 for a row in play, s_d = s_k = -1, s_need[k] = row k is in play and free (and n > 0), s_cneed[d] =
+// column d < n is free.  On return, behind a barrier: s_match / s_dmatch hold the walk's result on the free rows and columns.
+// Called by all 1024 threads.
+__device__ __forceinline__ void greedy_match(const float* overlaps, const float* distances, int K, int D, int n, float min_iou,
+                                             float max_dist, int* s_d, int* s_need, int* s_k, int* s_cneed, int* s_match,
+                                             int* s_dmatch, const int* s_act) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    const bool mine = tid < K;
+    bool scan = n > 0;                                 // the same in every thread: some row or column is to be scanned
+    for (;;) {
+        if (scan) {
+            for (int i = w; i < K + n; i += nw) {      // the rows [0, K) and the columns [K, K + n) to scan, a wave each
+                const bool row = i < K;
+                const int r = row ? i : i - K;
+                if (!(row ? s_need[r] : s_cneed[r])) continue;      // the same word in all 64 lanes
+                Cand c{0.f, 0.f, -1, -1};
+                for (int j = lane; j < (row ? n : K); j += 64) {
+                    const int k = row ? r : j, d = row ? j : r;
+                    if (row ? s_dmatch[d] >= 0 : (!s_act[k] || s_match[k] >= 0)) continue;
+                    const Cand x{overlaps[(long)k * D + d], distances[(long)k * D + d], k, d};
+                    if (x.ov >= min_iou && x.di <= max_dist && before(x, c)) c = x;
+                }
+                c = wave_first(c);
+                if (lane == 0) {
+                    if (row) { s_d[r] = c.d; s_need[r] = 0; }
+                    else { s_k[r] = c.d >= 0 ? c.k : -1; s_cneed[r] = 0; }
+                }
+            }
+            __syncthreads();
+        }
+        const int d = mine ? s_d[tid] : -1;            // >= 0: in play, still unmatched, and its row has a free pair
+        const bool win = d >= 0 && s_k[d] == tid;      // a mutual first
+        if (!__syncthreads_or(win)) break;             // no free admissible pair is left (the first of all is always mutual)
+        if (win) { s_match[tid] = d; s_dmatch[d] = tid; s_d[tid] = -1; s_k[d] = -1; }
+        __syncthreads();
+        const bool row_again = d >= 0 && !win && s_dmatch[d] >= 0;         // its kept detection was taken by another track
+        const int k = tid < n ? s_k[tid] : -1;
+        const bool col_again = k >= 0 && s_match[k] >= 0;                  // its kept track took another detection
+        if (row_again) s_need[tid] = 1;
+        if (col_again) s_cneed[tid] = 1;
+        scan = __syncthreads_or(row_again || col_again) != 0;
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
     __shared__ int s_d[SCENE_MAX], s_need[SCENE_MAX];            // per track: row_first (-1: none); the row is to be scanned
     __shared__ int s_k[SCENE_MAX], s_cneed[SCENE_MAX];           // per detection: col_first (-1: none); the column is to be scanned
@@ -103,7 +153,7 @@ __global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
     __shared__ int s_act[SCENE_MAX];                             // per track: active on entry
     __shared__ int s_free[SCENE_MAX], s_newid[SCENE_MAX];        // the free slots in ascending k; per slot: enrolled ? its id : -1
     __shared__ int s_cnt[16];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    const int tid = threadIdx.x;
     const int K = a.K, D = a.D;
     const int t = a.frame[0] - 1;
     const int n = (a.has_dets && D > 0) ? min(max(a.n_det[0], 0), D) : 0;
@@ -120,41 +170,7 @@ __global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
     s_cneed[tid] = tid < n;
     __syncthreads();
 
-    bool scan = n > 0;                                 // the same in every thread: some row or column is to be scanned
-    for (;;) {
-        if (scan) {
-            for (int i = w; i < K + n; i += nw) {      // the rows [0, K) and the columns [K, K + n) to scan, a wave each
-                const bool row = i < K;
-                const int r = row ? i : i - K;
-                if (!(row ? s_need[r] : s_cneed[r])) continue;      // the same word in all 64 lanes
-                Cand c{0.f, 0.f, -1, -1};
-                for (int j = lane; j < (row ? n : K); j += 64) {
-                    const int k = row ? r : j, d = row ? j : r;
-                    if (row ? s_dmatch[d] >= 0 : (!s_act[k] || s_match[k] >= 0)) continue;
-                    const Cand x{a.overlaps[(long)k * D + d], a.distances[(long)k * D + d], k, d};
-                    if (x.ov >= a.min_iou && x.di <= a.max_dist && before(x, c)) c = x;
-                }
-                c = wave_first(c);
-                if (lane == 0) {
-                    if (row) { s_d[r] = c.d; s_need[r] = 0; }
-                    else { s_k[r] = c.d >= 0 ? c.k : -1; s_cneed[r] = 0; }
-                }
-            }
-            __syncthreads();
-        }
-        const int d = mine ? s_d[tid] : -1;            // >= 0: active on entry, still unmatched, and its row has a free pair
-        const bool win = d >= 0 && s_k[d] == tid;      // a mutual first
-        if (!__syncthreads_or(win)) break;             // no free admissible pair is left (the first of all is always mutual)
-        if (win) { s_match[tid] = d; s_dmatch[d] = tid; s_d[tid] = -1; s_k[d] = -1; }
-        __syncthreads();
-        const bool row_again = d >= 0 && !win && s_dmatch[d] >= 0;         // its kept detection was taken by another track
-        const int k = tid < n ? s_k[tid] : -1;
-        const bool col_again = k >= 0 && s_match[k] >= 0;                  // its kept track took another detection
-        if (row_again) s_need[tid] = 1;
-        if (col_again) s_cneed[tid] = 1;
-        scan = __syncthreads_or(row_again || col_again) != 0;
-    }
-    __syncthreads();
+    greedy_match(a.overlaps, a.distances, K, D, n, a.min_iou, a.max_dist, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
 
     // counters and retire, slot tid
     int id = -1, misses = 0, starved = 0, start = 0;
@@ -226,7 +242,141 @@ __global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
     }
 }
 
+// ---- o3d_scene_mot_walk: the CLEAR-MOT bookkeeping of a tracked run (metrics.ClearMOT) -----------------------
+// One workgroup walks frames 0..F-1 of a chunk in order, the loop over the frames inside the kernel; what a frame hands to the
+// next -- per ground-truth object g the id it was last matched to, whether it was matched at its most recent valid frame, whether
+// it was ever matched -- lives in the registers of thread g and is read from / written back to device memory at the two ends, so
+// a sequence may be walked in several calls.  Thread i owns object i (i < G) and column i (i < K).
+//
+// The written order per frame f (tests/mot_oracle.py restates it in numpy); ov, di = the frame's (G,K) matrices:
+//   admissible(g,k)   gt_valid[f,g] != 0 && hyp_ids[f,k] >= 0 && ov[g,k] >= min_iou && di[g,k] <= max_dist   (fp32 compares; a
+//                     NaN is never admissible)
+//   carry             for g ascending, g valid and last_id[g] >= 0: k = the LOWEST column with hyp_ids[f,k] == last_id[g] (the
+//                     non-negative ids of a frame are meant to be distinct); when k exists, (g,k) is admissible and no smaller g
+//                     took column k: match[g] = k.  A kept identity wins over a better-scoring new pairing; of two objects that
+//                     remember one id the lower g gets it.
+//                     Here: thread g finds its k and tests the pair; thread k then takes the lowest g that asked for it.
+//   rest              greedy_match (above, o3d_scene_manage's own walk: overlap descending, distance ascending, g ascending, k
+//                     ascending) over the admissible pairs whose two ends are both still free
+//   count             per valid g, matched: tp++; idsw++ when last_id[g] >= 0 && last_id[g] != hyp_ids[f,match[g]]; frag++ when
+//                     ever[g] && !tracked_prev[g]; then last_id[g] = that id, ever[g] = 1, tracked_prev[g] = 1.  Unmatched: fn++,
+//                     tracked_prev[g] = 0.  An invalid g leaves its state untouched.  fp = the columns with an id left unmatched.
+//   rows              match_slot[f,g] = k | -1, match_id[f,g] = hyp_ids[f,k] | -1, match_ov / match_di[f,g] = ov / di[g,k] copied,
+//                     -1 / +inf when g is invalid or unmatched; per_frame[f] = {gt, hyp, tp, fp, fn, idsw, frag, 0}
+// No atomics, no flag a thread waits on: between two barriers every LDS or global word has one writer.  A column without an id is
+// handed to greedy_match as taken (s_dmatch = G, no object's index).  The sums of a frame: a ballot per wave and counter, the 16
+// wave counts through LDS, thread 0 adds them.
+constexpr int WALK_SUMS = 6;                           // valid objects, columns with an id, tp, fp, idsw, frag
+
+struct WalkArgs {
+    const float* overlaps; const float* distances; const int32_t* gt_valid; const int32_t* hyp_ids;
+    int32_t* last_id; int32_t* tracked_prev; int32_t* ever;
+    int32_t* match_slot; int32_t* match_id; float* match_ov; float* match_di; int32_t* per_frame;
+    int F, G, K;
+    float min_iou, max_dist;
+};
+
+__global__ __launch_bounds__(SCENE_MAX) void mot_walk_kernel(WalkArgs a) {
+    __shared__ int s_d[SCENE_MAX], s_need[SCENE_MAX];            // greedy_match's, rows = objects
+    __shared__ int s_k[SCENE_MAX], s_cneed[SCENE_MAX];           // and columns = the K slots
+    __shared__ int s_match[SCENE_MAX], s_dmatch[SCENE_MAX];
+    __shared__ int s_act[SCENE_MAX];                             // per object: valid in this frame
+    __shared__ int s_ids[SCENE_MAX], s_carry[SCENE_MAX];         // per column: its id; per object: the column it asks to keep
+    __shared__ int s_cnt[16 * WALK_SUMS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    const int G = a.G, K = a.K;
+    const bool mine = tid < G, col = tid < K;
+    int last = -1;
+    bool prev = false, ever = false;
+    if (mine) { last = a.last_id[tid]; prev = a.tracked_prev[tid] != 0; ever = a.ever[tid] != 0; }
+    for (int f = 0; f < a.F; ++f) {
+        const float* ov = a.overlaps + (long)f * G * K;
+        const float* di = a.distances + (long)f * G * K;
+        const int id = col ? a.hyp_ids[(long)f * K + tid] : -1;
+        const bool valid = mine && a.gt_valid[(long)f * G + tid] != 0;
+        s_ids[tid] = id;
+        s_act[tid] = valid;
+        s_match[tid] = -1;
+        s_dmatch[tid] = id >= 0 ? -1 : G;
+        s_d[tid] = -1;
+        s_k[tid] = -1;
+        __syncthreads();
+
+        // carry: object tid asks for the lowest column that holds the id it remembers
+        int c = -1;
+        if (valid && last >= 0) {
+            for (int k = 0; k < K; ++k)
+                if (s_ids[k] == last) { c = k; break; }
+            if (c >= 0 && !(ov[(long)tid * K + c] >= a.min_iou && di[(long)tid * K + c] <= a.max_dist)) c = -1;
+        }
+        s_carry[tid] = c;
+        __syncthreads();
+        if (id >= 0) {                                 // column tid goes to the lowest object that asked for it
+            for (int g = 0; g < G; ++g)
+                if (s_carry[g] == tid) { s_match[g] = tid; s_dmatch[tid] = g; break; }
+        }
+        __syncthreads();
+        s_need[tid] = valid && s_match[tid] < 0;
+        s_cneed[tid] = col && s_dmatch[tid] < 0;
+        __syncthreads();
+
+        greedy_match(ov, di, G, K, K, a.min_iou, a.max_dist, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
+
+        // count, object tid and column tid
+        const int m = valid ? s_match[tid] : -1;
+        const bool matched = m >= 0;
+        const int mid = matched ? s_ids[m] : -1;
+        const bool flags[WALK_SUMS] = {valid, id >= 0, matched, id >= 0 && s_dmatch[tid] < 0, matched && last >= 0 && last != mid,
+                                       matched && ever && !prev};
+        if (valid) {
+            if (matched) { last = mid; ever = true; }
+            prev = matched;
+        }
+        if (mine) {
+            const long o = (long)f * G + tid;
+            a.match_slot[o] = m;
+            a.match_id[o] = mid;
+            a.match_ov[o] = matched ? ov[(long)tid * K + m] : -1.f;
+            a.match_di[o] = matched ? di[(long)tid * K + m] : __int_as_float(0x7f800000);
+        }
+#pragma unroll
+        for (int i = 0; i < WALK_SUMS; ++i) {
+            const unsigned long long b = __ballot(flags[i]);
+            if (lane == 0) s_cnt[w * WALK_SUMS + i] = __popcll(b);
+        }
+        __syncthreads();                               // the frame's LDS has been read by everyone: the next frame may write it
+        if (tid == 0) {
+            int sum[WALK_SUMS];
+#pragma unroll
+            for (int i = 0; i < WALK_SUMS; ++i) {
+                sum[i] = 0;
+                for (int j = 0; j < nw; ++j) sum[i] += s_cnt[j * WALK_SUMS + i];
+            }
+            int32_t* row = a.per_frame + 8 * (long)f;
+            row[0] = sum[0]; row[1] = sum[1]; row[2] = sum[2]; row[3] = sum[3];
+            row[4] = sum[0] - sum[2]; row[5] = sum[4]; row[6] = sum[5]; row[7] = 0;
+        }
+    }
+    if (mine) { a.last_id[tid] = last; a.tracked_prev[tid] = prev ? 1 : 0; a.ever[tid] = ever ? 1 : 0; }
+}
+
 }  // namespace
+
+extern "C" int o3d_scene_mot_walk(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids, int F,
+                                  int G, int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev, int32_t* ever,
+                                  int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di, int32_t* per_frame,
+                                  void* stream) {
+    if (F < 0 || F > O3D_SCENE_MOT_MAX_FRAMES || G < 1 || G > O3D_CROP_MULTI_MAX_TARGETS || K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS)
+        return O3D_EINVAL;
+    if (!overlaps || !distances || !gt_valid || !hyp_ids || !last_id || !tracked_prev || !ever || !match_slot || !match_id ||
+        !match_ov || !match_di || !per_frame)
+        return O3D_EINVAL;
+    if (F == 0) return O3D_OK;
+    WalkArgs a{overlaps, distances, gt_valid, hyp_ids, last_id, tracked_prev, ever, match_slot, match_id, match_ov, match_di, per_frame,
+               F, G, K, min_iou, max_dist};
+    hipLaunchKernelGGL(mot_walk_kernel, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
 
 extern "C" int o3d_scene_manage(const float* overlaps, const float* distances, const float* dets, const int32_t* n_det, int K, int D,
                                 float* cur, float* yaw_state, float* canon_wlh, float* results, int T, const int32_t* frame,

@@ -127,3 +127,134 @@ class SuccessPrecision:
         total = int(c[2 * n])
         return {"success": curve_area(c[:n], total, self.xaxis[0], self.max_overlap),
                 "precision": curve_area(c[n:2 * n], total, self.xaxis[1], self.max_accuracy), "frames": total}
+
+
+# ---- scoring a managed scene: the CLEAR-MOT bookkeeping (Bernardin & Stiefelhagen 2008) on the device; DESIGN.md section 12k ---
+MOT_CHUNK_BYTES = 64 << 20             # the two (chunk,G,K) float32 score matrices of one update() chunk stay under this
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else 0.0
+
+
+class ClearMOT:
+    """The multi-object counterpart of SuccessPrecision: G ground-truth objects against the K slots of a managed scene tracker
+    whose slots change hands (tracking.ManagedSceneTracker: boxes (T,K,15) and ids_log (T,K)), scored where they are.  Per chunk
+    of frames two launches, o3d_scene_pair_scores_frames (every pair's overlap and distance, metrics.score_boxes' bits) and
+    o3d_scene_mot_walk (one workgroup walks the frames in order: an object keeps the track id it was last matched to while that
+    pair passes the gates, the rest is matched greedily by overlap descending, distance ascending), as include/o3dsot.h states
+    them.  A pair can match when overlap >= min_iou and distance <= max_dist (2 m: the centre distance commonly used for a true
+    positive in 3D tracking).  State on the device: the walk's last_id / tracked_prev / ever (G,), totals (8,) int64 = the sums
+    of per_frame, sums (2,) float64 = the matched pairs' distances and overlaps, seen / hit (G,) int64 = every object's valid and
+    matched frames.  The integer totals of several ranks add up.
+
+        m = ClearMOT(G, device=dev)
+        m.update(gt, valid, trk.boxes[:t], trk.ids_log[:t])       # or trk.score_mot(gt, valid, metrics=m); no sync
+        m.compute()                                                # {"mota": ..., "idsw": ..., ...}, one read-back
+
+    keep_logs=True keeps every chunk's match rows for logs().  sot: a SuccessPrecision that takes the matched pairs' overlaps
+    and distances through its update()."""
+
+    def __init__(self, G, device=None, min_iou=0.0, max_dist=2.0, dim=3, up_axis=(0, 0, 1), keep_logs=False, sot=None):
+        from . import points_utils as PU
+        G = int(G)
+        if not 1 <= G <= PU.CROP_MULTI_MAX_TARGETS:
+            raise ValueError("G must be 1..%d" % PU.CROP_MULTI_MAX_TARGETS)
+        if dim not in (2, 3):
+            raise ValueError("dim %r: 2 or 3" % (dim,))
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError("ClearMOT: CPU not supported (the state lives on a GPU)")
+        capi.load()
+        self.G, self.dev, self.dim, self.up = G, dev, int(dim), up_index(up_axis)
+        self.min_iou, self.max_dist, self.keep_logs, self.sot = float(min_iou), float(max_dist), bool(keep_logs), sot
+        self.state = torch.zeros((3, G), dtype=torch.int32, device=dev)          # last_id, tracked_prev, ever
+        self.counts = torch.zeros((8 + 2 * G,), dtype=torch.int64, device=dev)   # totals (8), seen (G), hit (G)
+        self.sums = torch.zeros((2,), dtype=torch.float64, device=dev)           # matched distances, matched overlaps
+        self.reset()
+
+    def reset(self):
+        self.state.zero_()
+        self.state[0].fill_(-1)
+        self.counts.zero_()
+        self.sums.zero_()
+        self.frames, self._logs = 0, []
+
+    def chunk_frames(self, K):
+        """the frames of one chunk of update() for K columns: the two score matrices within MOT_CHUNK_BYTES, the walk's cap"""
+        from . import points_utils as PU
+        return max(1, min(PU.SCENE_MOT_MAX_FRAMES, MOT_CHUNK_BYTES // (8 * self.G * int(K))))
+
+    def update(self, gt, valid, boxes, ids):
+        """F further frames, in order: gt (F,G,15) float32, valid (F,G) | None (every object annotated in every frame), boxes
+        (F,K,15) float32, ids (F,K) int32 (< 0: the slot holds no track), device tensors.  Two launches per chunk and a few
+        reductions in torch; no sync."""
+        from . import points_utils as PU
+        what = "ClearMOT.update"
+        for t in (gt, boxes, ids) + (() if valid is None else (valid,)):
+            _need_gpu(t, what)
+        F, G = gt.shape[0], self.G
+        if tuple(gt.shape) != (F, G, 15) or boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 15:
+            raise ValueError("%s: gt %s and boxes %s for G = %d" % (what, tuple(gt.shape), tuple(boxes.shape), G))
+        K = boxes.shape[1]
+        if tuple(ids.shape) != (F, K) or (valid is not None and tuple(valid.shape) != (F, G)):
+            raise ValueError("%s: ids %s, valid %s for (F,G,K) = %s" % (what, tuple(ids.shape), None if valid is None else
+                                                                      tuple(valid.shape), (F, G, K)))
+        gt, boxes, ids = gt.float().contiguous(), boxes.float().contiguous(), ids.to(torch.int32).contiguous()
+        valid = torch.ones((F, G), dtype=torch.int32, device=self.dev) if valid is None else (valid != 0).to(torch.int32).contiguous()
+        step = self.chunk_frames(K)
+        with torch.cuda.device(self.dev):
+            for lo in range(0, F, step):
+                hi = min(lo + step, F)
+                v, h = valid[lo:hi], ids[lo:hi]
+                ov, di = PU.scene_pair_scores_frames(gt[lo:hi], v, boxes[lo:hi], h, self.dim, self.up)
+                rows = PU.scene_mot_walk(ov, di, v, h, self.state[0], self.state[1], self.state[2], self.min_iou, self.max_dist)
+                slot, _, mov, mdi, per_frame = rows
+                hit = slot >= 0
+                self.counts[:8] += per_frame.sum(0)
+                self.counts[8:8 + G] += v.sum(0)
+                self.counts[8 + G:] += hit.sum(0)
+                zero = torch.zeros((), dtype=torch.float64, device=self.dev)
+                self.sums[0] += torch.where(hit, mdi.double(), zero).sum()
+                self.sums[1] += torch.where(hit, mov.double(), zero).sum()
+                if self.sot is not None:                   # an unmatched row (-1, +inf) passes no threshold: only `total` is set right
+                    self.sot.update(mov, mdi)
+                    self.sot.counts[2 * self.sot.n] -= (~hit).sum()
+                if self.keep_logs:
+                    self._logs.append(rows[:4])
+        self.frames += F
+
+    def logs(self):
+        """keep_logs=True: {match_slot, match_id (T,G) int32, match_ov, match_di (T,G) float32} device tensors over every frame
+        since reset(); no sync"""
+        if not self.keep_logs:
+            raise RuntimeError("ClearMOT.logs: created with keep_logs=False")
+        names = ("match_slot", "match_id", "match_ov", "match_di")
+        kinds = (torch.int32, torch.int32, torch.float32, torch.float32)
+        return {n: torch.cat([c[i] for c in self._logs]) if self._logs else torch.zeros((0, self.G), dtype=k, device=self.dev)
+                for i, (n, k) in enumerate(zip(names, kinds))}
+
+    def _read(self):
+        """the one read-back: the integer counters and the bits of the two float64 sums"""
+        return torch.cat([self.counts, self.sums.view(torch.int64)]).cpu()
+
+    def compute(self):
+        """{frames, gt, hyp, tp, fp, fn, idsw, frag, mota, motp_dist, motp_iou, recall, precision, objects, mostly_tracked,
+        mostly_lost}: mota = 1 - (fn + fp + idsw) / gt; motp_* the means over the true positives; mostly_tracked / mostly_lost
+        the share of the `objects` (those with a valid frame) matched in >= 80 % / <= 20 % of their valid frames.  Every rate is
+        0.0 when its denominator is 0."""
+        from .points_utils import MOT_FRAME_COLS
+        c, G = self._read(), self.G
+        tot = dict(zip(MOT_FRAME_COLS, c[:7].tolist()))
+        seen, hit = c[8:8 + G], c[8 + G:8 + 2 * G]
+        s_di, s_ov = c[8 + 2 * G:].view(torch.float64).tolist()
+        live = seen > 0
+        objects = int(live.sum())
+        res = dict(frames=self.frames, **tot)
+        res["mota"] = 1.0 - _ratio(tot["fn"] + tot["fp"] + tot["idsw"], tot["gt"]) if tot["gt"] else 0.0
+        res["motp_dist"], res["motp_iou"] = _ratio(s_di, tot["tp"]), _ratio(s_ov, tot["tp"])
+        res["recall"], res["precision"] = _ratio(tot["tp"], tot["gt"]), _ratio(tot["tp"], tot["hyp"])
+        res["objects"] = objects
+        res["mostly_tracked"] = _ratio(int((live & (5 * hit >= 4 * seen)).sum()), objects)
+        res["mostly_lost"] = _ratio(int((live & (5 * hit <= seen)).sum()), objects)
+        return res

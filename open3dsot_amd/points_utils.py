@@ -744,6 +744,70 @@ def scene_manage(overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, re
             int(bool(has_dets)), torch.cuda.current_stream(dev).cuda_stream), what)
 
 
+# ---- scoring a managed scene on the device (metrics.ClearMOT; csrc/metrics.hip, csrc/scene.hip) -----------
+SCENE_MOT_MAX_FRAMES = capi.CONSTANTS["O3D_SCENE_MOT_MAX_FRAMES"]
+MOT_FRAME_COLS = ("gt", "hyp", "tp", "fp", "fn", "idsw", "frag")       # per_frame's columns 0..6; column 7 is 0
+
+
+def scene_pair_scores_frames(gt, gt_valid, hyp, hyp_ids, dim=3, up=2, out=None):
+    """One o3d_scene_pair_scores_frames launch (no sync): gt (F,G,15), gt_valid (F,G) int32, hyp (F,K,15), hyp_ids (F,K) int32 on
+    the device -> (overlaps, distances) (F,G,K) float32, written into out = (overlaps, distances) when given.  Pair (f,g,k) holds
+    what metrics.score_boxes(gt[f,g], hyp[f,k]) gives, bit for bit; the pairs of an invalid g or of a column without an id hold
+    -1 / +inf."""
+    what = "scene_pair_scores_frames"
+    F, G, K = gt.shape[0], gt.shape[1], hyp.shape[1]
+    _f32(gt, (F, G, 15), what)
+    _f32(hyp, (F, K, 15), what)
+    _i32(gt_valid, F * G, what)
+    _i32(hyp_ids, F * K, what)
+    dev = gt.device
+    if out is None:
+        out = (torch.empty((F, G, K), dtype=torch.float32, device=dev), torch.empty((F, G, K), dtype=torch.float32, device=dev))
+    for o in out:
+        _f32(o, (F, G, K), what)
+    if F == 0:                                             # empty tensors have no address to pass
+        return out
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_scene_pair_scores_frames(gt.data_ptr(), gt_valid.data_ptr(), hyp.data_ptr(), hyp_ids.data_ptr(), F, G,
+                                                            K, int(dim), int(up), out[0].data_ptr(), out[1].data_ptr(),
+                                                            torch.cuda.current_stream(dev).cuda_stream), what)
+    return out
+
+
+def scene_mot_walk(overlaps, distances, gt_valid, hyp_ids, last_id, tracked_prev, ever, min_iou=0.0, max_dist=float("inf"), out=None):
+    """One o3d_scene_mot_walk launch (no sync): the CLEAR-MOT walk over the F frames of overlaps / distances (F,G,K) in order, as
+    include/o3dsot.h states it.  gt_valid (F,G), hyp_ids (F,K) int32; last_id, tracked_prev, ever (G,) int32: the carried state,
+    updated in place.  -> (match_slot (F,G) int32, match_id (F,G) int32, match_ov (F,G), match_di (F,G) float32, per_frame (F,8)
+    int32 = MOT_FRAME_COLS and a 0), written into `out` when given."""
+    what = "scene_mot_walk"
+    F, G, K = overlaps.shape
+    _f32(overlaps, (F, G, K), what)
+    _f32(distances, (F, G, K), what)
+    _i32(gt_valid, F * G, what)
+    _i32(hyp_ids, F * K, what)
+    for t in (last_id, tracked_prev, ever):
+        _i32(t, G, what)
+    dev = overlaps.device
+    if out is None:
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = (torch.empty((F, G), **i32), torch.empty((F, G), **i32), torch.empty((F, G), dtype=torch.float32, device=dev),
+               torch.empty((F, G), dtype=torch.float32, device=dev), torch.empty((F, 8), **i32))
+    slot, ids, mov, mdi, per_frame = out
+    _i32(slot, F * G, what)
+    _i32(ids, F * G, what)
+    _f32(mov, (F, G), what)
+    _f32(mdi, (F, G), what)
+    _i32(per_frame, F * 8, what)
+    if F == 0:
+        return out
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_scene_mot_walk(
+            overlaps.data_ptr(), distances.data_ptr(), gt_valid.data_ptr(), hyp_ids.data_ptr(), F, G, K, float(min_iou), float(max_dist),
+            last_id.data_ptr(), tracked_prev.data_ptr(), ever.data_ptr(), slot.data_ptr(), ids.data_ptr(), mov.data_ptr(), mdi.data_ptr(),
+            per_frame.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), what)
+    return out
+
+
 def _box_device(box, what):
     """the GPU a box lives on (a (15,) tensor or a (center, wlh, rot) triple of tensors); anything else is refused"""
     parts = (box,) if torch.is_tensor(box) else tuple(box)

@@ -55,7 +55,8 @@ sampling="reference".
 The slots' lifecycle on the device (ManagedSceneTracker, ManagedMotionSceneTracker, managed_scene_tracker_for; DESIGN.md section
 12j): a scene tracker whose update() also takes the frame's detections as a device tensor.  Two launches after the box update
 (o3d_scene_pair_scores, o3d_scene_manage) match detections and tracks, retire the lost slots, enroll the unmatched detections
-into free slots and write the next frame's lane table: objects enter and leave without a host stop.
+into free slots and write the next frame's lane table: objects enter and leave without a host stop.  score_mot() /
+evaluate_managed_scene() score such a run as multi-object tracking (metrics.ClearMOT).
 
 The template bank: each frame's crop by its own result box is computed once and kept on the device; `shape_aggregation`
 (`first`, `previous`, `firstandprevious`, `all`; models/base_model.py:166-195) decides which crops form the template cloud.
@@ -1787,6 +1788,29 @@ class _Managed:
             out.setdefault(int(ids[f, k]), (int(f), []))[1].append(res[f, k])
         return {i: (f, np.stack(rows)) for i, (f, rows) in out.items()}
 
+    def score_mot(self, gt_boxes, valid=None, metrics=None, **gates):
+        """Score rows [0:t] of the run against gt_boxes (t,G,15), where they are: boxes[:t] and ids_log[:t] go to a
+        metrics.ClearMOT, whose overlap and distance are the model config's, as in score().  A slot
+        follows no fixed object here, so G need not be K.  valid (t,G) | None: 0 where an object has no annotation.  metrics:
+        a ClearMOT to add to | None: a new one with **gates (min_iou, max_dist, keep_logs, sot).  Device tensors travel as they
+        are: no host stop and no upload.  -> the ClearMOT; compute() is its one read-back."""
+        from . import metrics as MT
+        gt = PU._dev32(gt_boxes, self.dev)
+        if gt.dim() != 3 or gt.shape[0] != self.t or gt.shape[2] != 15:
+            raise ValueError("%s.score_mot: gt_boxes %s for %d frames" % (self._NAME, tuple(gt.shape), self.t))
+        if valid is not None:
+            valid = torch.as_tensor(valid).to(self.dev)
+        if metrics is None:
+            cfg = self.model.config
+            metrics = MT.ClearMOT(gt.shape[1], self.dev, dim=self.score_dim, up_axis=tuple(getattr(cfg, "up_axis", (0, 0, 1))), **gates)
+        elif gates:
+            raise ValueError("%s.score_mot: the gates %s belong to the ClearMOT that is passed" % (self._NAME, sorted(gates)))
+        elif (metrics.dim, metrics.up) != (self.score_dim, self.score_up):
+            raise ValueError("%s.score_mot: the ClearMOT scores dim %d, up %d; the model config says %d, %d"
+                             % (self._NAME, metrics.dim, metrics.up, self.score_dim, self.score_up))
+        metrics.update(gt, valid, self.boxes[:self.t], self.ids_log[:self.t])
+        return metrics
+
     def overflow(self, per_target=False):
         """the scene tracker's overflow(), with every slot's start frame taken from `slot`"""
         self._start[:] = self.status()["start"]
@@ -1983,6 +2007,49 @@ def evaluate_scene(model, frames, gt_boxes, valid=None, seed=0, use_graph=None, 
     trk = tracker if tracker is not None else scene_tracker_for(model, gt_boxes.shape[1], seed=seed, use_graph=use_graph,
                                                                 sampling=sampling, **capacities)
     return _evaluate_k(trk, frames, gt_boxes, valid, metrics)
+
+
+def evaluate_managed_scene(model, frames, gt_boxes, valid=None, detections=None, n_detections=None, n_targets=None, manage=None,
+                           mot=None, sampling="table", **capacities):
+    """A managed scene tracker over `frames` with a detection set per frame, scored as multi-object tracking (DESIGN.md section
+    12k).  gt_boxes (T,G,15), valid (T,G) | None on the host: 0 where an object has no annotation.  The tracker
+    (managed_scene_tracker_for(model, n_targets or G, manage=manage, sampling=sampling, **capacities; seed, use_graph among
+    them) starts from frame 0's valid boxes and runs one update(frames[t], detections[t], n_detections[t:t+1]) per frame.
+    detections (T,D,15) with n_detections (T,) | None (= D each); detections=None: every frame's valid ground-truth boxes,
+    moved to the front on the host once and uploaded once.  mot: a metrics.ClearMOT to add to | a dict of its gates | None.
+    No host stop per frame.  -> (the ClearMOT's compute() dict, the tracker)."""
+    _scene_sampling(sampling, "evaluate_managed_scene")
+    gt_host = np.ascontiguousarray(gt_boxes.detach().cpu().numpy() if torch.is_tensor(gt_boxes) else gt_boxes, dtype=np.float32)
+    if gt_host.ndim != 3 or gt_host.shape[2] != 15 or gt_host.shape[0] != len(frames):
+        raise ValueError("gt_boxes %s for %d frames" % (gt_host.shape, len(frames)))
+    T, G = gt_host.shape[:2]
+    live = np.ones((T, G), bool) if valid is None else np.asarray(valid.detach().cpu().numpy() if torch.is_tensor(valid) else valid) != 0
+    if live.shape != (T, G):
+        raise ValueError("valid must be (T,G) = %s" % ((T, G),))
+    if detections is None:
+        order = np.argsort(~live, axis=1, kind="stable")                     # the valid objects first, in ascending g
+        detections = np.take_along_axis(gt_host, order[:, :, None], axis=1)
+        n_detections = live.sum(1)
+    manage = dict(manage or {})
+    manage.setdefault("max_detections", max(int(detections.shape[1]), 1))
+    trk = managed_scene_tracker_for(model, int(n_targets) if n_targets is not None else G, manage=manage, sampling=sampling,
+                                    **capacities)
+    dev = trk.dev
+    dets = PU._dev32(detections, dev).reshape(T, -1, 15)
+    if n_detections is None:
+        n_det = torch.full((T,), dets.shape[1], dtype=torch.int32, device=dev)
+    else:
+        n_det = torch.as_tensor(np.asarray(n_detections.detach().cpu().numpy() if torch.is_tensor(n_detections) else n_detections,
+                                           dtype=np.int32)).to(dev)
+    gt, live_dev = torch.from_numpy(gt_host).to(dev), torch.from_numpy(live.astype(np.int32)).to(dev)
+    trk.init(frames[0], gt_host[0][live[0]])
+    for t in range(1, T):
+        trk.update(frames[t], dets[t], n_det[t:t + 1])
+    if isinstance(mot, dict) or mot is None:
+        m = trk.score_mot(gt, live_dev, **(mot or {}))
+    else:
+        m = trk.score_mot(gt, live_dev, metrics=mot)
+    return m.compute(), trk
 
 
 def _evaluate_k(trk, frames, gt_boxes, valid, metrics):

@@ -60,7 +60,10 @@ device-resident detections per frame (the ground truth of the first min(D, K) ta
 scene tracker at the same K, on the same scene, model and sampling ("table" unless given), both timed as above, --repeats times
 in turn.  Prints one JSON line: ms per frame of both and their ratio, the device time of the two management launches (200 calls
 between two events: o3d_scene_pair_scores alone, then both) and of the frame's crop call with and without the model-crop group
-(the managed tracker always makes it), the managed tracker's final status and whether both replay a graph.
+(the managed tracker always makes it), the managed tracker's final status and whether both replay a graph.  With --mot the
+tracked run is then scored as multi-object tracking against the K ground-truth objects (tracker.score_mot, DESIGN.md section
+12k): the device time of score_mot over all frames and of o3d_scene_pair_scores_frames and o3d_scene_mot_walk alone, each run
+between two events (median, smallest, largest of 15), and the CLEAR-MOT numbers of the run.
 """
 import argparse
 import json
@@ -405,6 +408,7 @@ def manage_main(args, dev):
     pts, prev = dframes[-1], dframes[-2]
     crop_both_ms = device_ms(lambda: man._crop_scene([prev, pts] if motion else [pts, prev]))
     crop_one_ms = crop_both_ms if motion else device_ms(lambda: man._crop_scene([pts, None]))
+    mot = mot_timing(man, gt, dev) if args.mot else {}
     print(json.dumps({
         "workload": "%s tracking %d targets through a %d-frame, %d-point synthetic scene with %d device detections per frame (fixture "
                     "weights, eval, fp32), median of %d runs, the two loops in turn" % (args.model.upper(), K, args.frames,
@@ -421,7 +425,44 @@ def manage_main(args, dev):
         "hip_graph": [man.graph is not None, scn.graph is not None],
         "managed_active_slots": int(status["active"].sum()), "managed_next_id": next_id,
         "managed_dropped_detections_last_frame": dropped, "managed_overflow": list(man.overflow()),
-        "scene_overflow": list(scn.overflow())}))
+        "scene_overflow": list(scn.overflow()), **mot}))
+
+
+def mot_timing(man, gt, dev, runs=15):
+    """--mot: score the managed run that was just tracked as multi-object tracking, G = K ground-truth
+    objects over all its frames: the device time of score_mot (both launches and the torch reductions of ClearMOT.update) and of
+    each launch alone, every run between two events of its own, median and range of `runs` runs after 3 of warm-up"""
+    from open3dsot_amd import metrics as MT
+    T, K = man.t, man.K
+    g_dev = torch.from_numpy(np.ascontiguousarray(gt[:T], dtype=np.float32)).to(dev)
+    v_dev = torch.ones((T, K), dtype=torch.int32, device=dev)
+    boxes, ids = man.boxes[:T], man.ids_log[:T]
+    m = MT.ClearMOT(K, dev, dim=man.score_dim, up_axis=(0, 0, 1) if man.score_up == 2 else (0, -1, 0))
+    assert m.chunk_frames(K) >= T, "the separate launches below time one chunk"
+    ov, di = PU.scene_pair_scores_frames(g_dev, v_dev, boxes, ids, m.dim, m.up)
+    rows = PU.scene_mot_walk(ov, di, v_dev, ids, m.state[0], m.state[1], m.state[2], m.min_iou, m.max_dist)
+
+    def timed(fn):
+        ms = []
+        for i in range(runs + 3):
+            m.reset()                                                   # every run walks from the empty state
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= 3:
+                ms.append(a.elapsed_time(b))
+        ms.sort()
+        return [round(ms[len(ms) // 2], 4), round(ms[0], 4), round(ms[-1], 4)]
+    whole = timed(lambda: man.score_mot(g_dev, v_dev, metrics=m))
+    res = m.compute()
+    scores = timed(lambda: PU.scene_pair_scores_frames(g_dev, v_dev, boxes, ids, m.dim, m.up, out=(ov, di)))
+    walk = timed(lambda: PU.scene_mot_walk(ov, di, v_dev, ids, m.state[0], m.state[1], m.state[2], m.min_iou, m.max_dist, out=rows))
+    return {"mot_frames": T, "mot_objects": K, "mot_gates": [m.min_iou, m.max_dist], "mot_runs": runs,
+            "score_mot_device_ms_median_min_max": whole, "pair_scores_frames_device_ms_median_min_max": scores,
+            "mot_walk_device_ms_median_min_max": walk, "mot_walk_ms_per_frame": round(walk[0] / T, 5),
+            "mot": {k: (round(v, 6) if isinstance(v, float) else v) for k, v in res.items()}}
 
 
 def lanes_main(args, dev):
@@ -522,6 +563,8 @@ def main():
     ap.add_argument("--lanes", type=int, default=0, help="L > 0: the test epoch on L lanes against the sequential free-running epoch")
     ap.add_argument("--manage", type=int, default=0, help="with --targets K: D > 0 device detections per frame, the managed scene "
                                                           "tracker against the plain one")
+    ap.add_argument("--mot", action="store_true", help="with --manage: time score_mot (ClearMOT) on the tracked run, and its two "
+                                                       "launches alone, each between two events, 15 runs")
     ap.add_argument("--tracklets", type=int, default=64, help="--lanes: tracklets of the epoch, --frames frames each")
     ap.add_argument("--distinct", type=int, default=8, help="--lanes: different synthetic sequences, used in rotation")
     args = ap.parse_args()
