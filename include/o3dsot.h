@@ -1182,8 +1182,8 @@ int o3d_scene_manage(const float* overlaps, const float* distances, const float*
  *   rows         match_slot (F,G) int32 = k | -1; match_id (F,G) int32 = hyp_ids[f,k] | -1; match_ov, match_di (F,G) float32 =
  *                ov[g,k], di[g,k] copied (-1 / +inf when g is invalid or unmatched); per_frame (F,8) int32 = {gt, hyp, tp, fp,
  *                fn, idsw, frag, 0} with gt = the valid objects and hyp = the columns with an id
- * The leftover assignment is this library's greedy rule, not the Hungarian optimum, and the identity memory is the last known
- * match, kept through gaps.  No atomics and no flag that a thread waits on: barriers and the stream order are the only
+ * The leftover assignment of this entry is the library's greedy rule (o3d_scene_mot_walk_assign below takes the optimal one),
+ * and the identity memory is the last known match, kept through gaps.  No atomics and no flag that a thread waits on: barriers and the stream order are the only
  * dependences, and all stores are ordinary vector stores, so the result is a function of the inputs.
  * Both entries return O3D_EINVAL before any HIP call for a NULL operand, F, G or K outside the ranges above, dim not 2 | 3, up
  * not 1 | 2, and (o3d_scene_pair_scores_frames) more than 2^31 - 1 workgroups of 256 pairs. */
@@ -1193,6 +1193,51 @@ int o3d_scene_pair_scores_frames(const float* gt, const int32_t* gt_valid, const
 int o3d_scene_mot_walk(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids, int F, int G,
                        int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev, int32_t* ever,
                        int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di, int32_t* per_frame, void* stream);
+
+/* ---- optimal assignment for the scene trackers and CLEAR-MOT (csrc/scene.hip) ------------------------
+ * `assignment` selects who belongs to whom on the admissible pairs of an (rows, cols) overlap / distance matrix pair:
+ *   O3D_ASSIGN_GREEDY    the walk of o3d_scene_manage above (overlap descending, distance ascending, row, column ascending)
+ *   O3D_ASSIGN_OPTIMAL   of the one-to-one sets of admissible pairs on the free rows and columns: the MOST pairs, and among
+ *                        those the smallest sum of the integer cost q (maximum-cardinality, minimum-cost; the Hungarian optimum)
+ * `cost` is q of an admissible pair, int32 in [0, 2^20], each product one rounded fp32 multiply:
+ *   O3D_COST_DISTANCE    (int) rintf(fminf(fmaxf(distance, 0), 1024) * 1024)           unit 1/1024 m; >= 1024 m ties at 2^20
+ *   O3D_COST_OVERLAP     (int) rintf((1 - fminf(fmaxf(overlap, 0), 1)) * 1048576)
+ * admissible(r,c) is the entry's own test (fp32 compares, a NaN is never admissible).  The optimum is the minimum-sum assignment
+ * of the matrix with q on the admissible pairs, one private "stay unmatched" column per row at 2^32 and the inadmissible pairs
+ * excluded, in int64: nothing is rounded and at 1024 rows nothing overflows.  WHICH optimum of several: the free rows in play
+ * are inserted in ascending order, each by one shortest augmenting path on the reduced costs; the next column of a path is the
+ * unused one of smallest tentative length, of equal lengths the lowest column index, real columns before the rows' private
+ * ones; a tentative length is replaced only by a strictly smaller one (csrc/scene.hip states the order in full,
+ * tests/assign_oracle.py restates it).  One workgroup, no atomics, every loop bounded by the sizes: a pure function of the
+ * inputs.  `cost` is ignored by the greedy walk itself.
+ *
+ * o3d_scene_assign: ONE launch of one workgroup, the match alone.  overlaps, distances (K,D) float32; row_active (K) int32 |
+ * NULL: every row is in play; n_col (1) int32 on the device, clamped to [0, D] | NULL: D; K 1..O3D_CROP_MULTI_MAX_TARGETS, D
+ * 1..O3D_SCENE_MAX_DETECTIONS.  admissible(r,c) = row r in play && c < n_col && overlaps[r,c] >= min_iou && distances[r,c] <=
+ * max_dist.  -> match (K) int32 = c | -1, col_match (D) int32 = r | -1, summary (2) int64 = {pairs, the sum of q over the pairs}
+ * (with O3D_ASSIGN_GREEDY too: the greedy pairs summed under `cost`).
+ * o3d_scene_manage_assign / o3d_scene_mot_walk_assign: o3d_scene_manage / o3d_scene_mot_walk with the match (the walk's `rest`
+ * step; its carry is unchanged) made by `assignment` under `cost`; everything else, and with O3D_ASSIGN_GREEDY every bit, is
+ * theirs -- the two older entries forward here.
+ * All three return O3D_EINVAL before any HIP call for an unknown assignment or cost, and for what their namesakes refuse
+ * (o3d_scene_assign: overlaps, distances, match, col_match or summary NULL, K or D outside the ranges above). */
+#define O3D_ASSIGN_GREEDY 0
+#define O3D_ASSIGN_OPTIMAL 1
+#define O3D_COST_DISTANCE 0
+#define O3D_COST_OVERLAP 1
+int o3d_scene_assign(const float* overlaps, const float* distances, const int32_t* row_active, const int32_t* n_col, int K, int D,
+                     float min_iou, float max_dist, int assignment, int cost, int32_t* match, int32_t* col_match,
+                     int64_t* summary, void* stream);
+int o3d_scene_manage_assign(const float* overlaps, const float* distances, const float* dets, const int32_t* n_det, int K, int D,
+                            float* cur, float* yaw_state, float* canon_wlh, float* results, int T, const int32_t* frame,
+                            int32_t* active, int32_t* slot, int32_t* next_id, const int32_t* counts, int count_col,
+                            int32_t* bank_state_next, int32_t* lanes, int rule, int32_t* ids_log, int32_t* match_log,
+                            int32_t* dropped_log, float min_iou, float max_dist, int max_misses, int min_points, int max_starved,
+                            int enroll, int has_dets, int assignment, int cost, void* stream);
+int o3d_scene_mot_walk_assign(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids, int F,
+                              int G, int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev, int32_t* ever,
+                              int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di, int32_t* per_frame,
+                              int assignment, int cost, void* stream);
 
 /* ---- the preload crop of a dataset reader (csrc/preload.hip; open3dsot_amd/datasets.py is the caller) ----------------------
  * What kittiDataset._get_frame_from_anno does per annotated object per frame -- PointCloud.transform in camera mode, then

@@ -60,6 +60,7 @@ struct ManageArgs {
     int32_t* ids_log; int32_t* match_log; int32_t* dropped_log;
     int K, D, T, count_col, rule, max_misses, min_points, max_starved, enroll, has_dets;
     float min_iou, max_dist;
+    int cost;
 };
 
 struct Cand { float ov, di; int k, d; };       // d < 0: none
@@ -146,6 +147,159 @@ __device__ __forceinline__ void greedy_match(const float* overlaps, const float*
     __syncthreads();
 }
 
+// ---- optimal_match: maximum-cardinality, minimum-cost assignment ---------------------------------------------
+// The rule (tests/assign_oracle.py restates it in Python ints), on what greedy_match takes:
+//   admissible(r,c)   greedy_match's test on a free row in play and a free column c < n: overlaps[r,c] >= min_iou &&
+//                     distances[r,c] <= max_dist, fp32 compares, a NaN is never admissible
+//   q(r,c)            the int32 cost of an admissible pair, in [0, 2^20]; each product is one rounded fp32 multiply
+//                       O3D_COST_DISTANCE  (int) rintf(fminf(fmaxf(di, 0.f), 1024.f) * 1024.f)          unit 1/1024 m, >= 1024 m ties
+//                       O3D_COST_OVERLAP   (int) rintf((1.f - fminf(fmaxf(ov, 0.f), 1.f)) * 1048576.f)
+//   objective         of the one-to-one sets of admissible pairs: the most pairs, and among those the smallest sum of q.  That is
+//                     the minimum-sum assignment of the matrix with q on the admissible pairs, one private `stay unmatched`
+//                     column per row at BIG = 2^32, and the inadmissible pairs excluded.  Columns are numbered real c = c, dummy of
+//                     row r = SCENE_MAX + r.  Potentials, lengths and sums are int64: at 1024 rows a sum stays under 2^42.
+//   which optimum     u[r] = 0, v[c] = 0.  The free rows in play are inserted in ascending r, each by ONE shortest augmenting path
+//                     on the reduced costs q(r,c) - u[r] - v[c] (BIG - u[r] for the dummy, whose v stays 0: see below):
+//                       start     no column has a length or is used; the current row is i at length 0, reached from no column
+//                       a step    every unused real column c admissible to the current row r0 (reached from column j0 at length
+//                                 L) gets the tentative length L + q(r0,c) - u[r0] - v[c] when that is STRICTLY smaller than the
+//                                 one it has, and then remembers j0 as its predecessor; the dummy of r0 gets L + BIG - u[r0].  The
+//                                 next column is the unused one with a length of the smallest length; of equal lengths the lowest
+//                                 column number (so a real column before a dummy one).  A dummy column or a real column that no
+//                                 row holds ends the path, at length Dend.  Otherwise the column is used, its row is the next
+//                                 current row, reached from this column at its length.
+//                       potentials   a used column c of length d: v[c] += d - Dend and u[its row] += Dend - d; u[i] += Dend
+//                       augment   from the end column backwards along the predecessors every column takes the row its predecessor
+//                                 held, the first column of the path takes i.  A path that ends in the dummy of row t leaves t
+//                                 unmatched for good.
+// The dummy of row t is only ever reached from t, so it can only end a path, never lie inside one: it is never `used`, its v
+// stays 0, a row that went to its dummy is never visited again and the matched rows only grow.  Lengths are kept absolute (the
+// per-step subtraction of the textbook form shifts every unused column alike and changes no comparison).
+//
+// Thread c owns real column c and the dummy of row c: v, the two lengths, `used` and the row held when it became used live in
+// its registers.  LDS: u as two int32 halves (in greedy_match's s_d / s_k), the predecessor of every real column (in its s_cneed,
+// read into a register first), column -> row in s_dmatch and row -> column in s_match (the result arrays themselves), the rows to
+// insert in s_need as handed in.  A step is one coalesced read of row r0's two entries per thread, a wave64 butterfly on (length,
+// column, the row that holds it) and ONE barrier: the 16 wave results go through a double-buffered LDS table that every thread
+// reads.  Thread 0 walks the augmentation while the others update the potentials (disjoint words) or are still reading the last
+// step's table: nothing the augmentation writes is read between the last step's barrier and the one that ends the insertion.  Every loop has a
+// bound that the data cannot move: K insertions, K + 1 steps (a step uses up a matched row, or ends), K + 1 links.  No atomics.
+// Contract on entry and return: greedy_match's (s_d and s_k need not be -1).  Called by all 1024 threads.
+constexpr long long ASSIGN_BIG = 1ll << 32, ASSIGN_INF = 1ll << 62;
+constexpr int ASSIGN_NONE = 2 * SCENE_MAX;             // no column: after every real (c) and dummy (SCENE_MAX + r) number
+
+__device__ __forceinline__ int assign_cost(float ov, float di, int cost) {
+    return cost == O3D_COST_OVERLAP ? (int)rintf((1.f - fminf(fmaxf(ov, 0.f), 1.f)) * 1048576.f)
+                                    : (int)rintf(fminf(fmaxf(di, 0.f), 1024.f) * 1024.f);
+}
+
+struct PathEnd { long long len; int col, row; };       // row: the row that holds the column (-1: none, or a dummy column)
+
+__device__ __forceinline__ bool shorter(const PathEnd& p, const PathEnd& q) { return p.len < q.len || (p.len == q.len && p.col < q.col); }
+
+__device__ __forceinline__ long long u_read(const int* s_ulo, const int* s_uhi, int r) {
+    return (long long)(((unsigned long long)(unsigned)s_uhi[r] << 32) | (unsigned)s_ulo[r]);
+}
+
+__device__ __forceinline__ void optimal_match(const float* overlaps, const float* distances, int K, int D, int n, float min_iou,
+                                              float max_dist, int cost, int* s_ulo, const int* s_need, int* s_uhi, int* s_way,
+                                              int* s_match, int* s_dmatch) {
+    __shared__ long long s_len[2][SCENE_MAX / 64];     // the 16 waves' shortest, double-buffered over the steps
+    __shared__ int s_col[2][SCENE_MAX / 64], s_row[2][SCENE_MAX / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const bool col_ok = tid < n && s_way[tid] != 0;    // s_way arrives as s_cneed: column tid < n is free
+    long long v = 0;
+    s_ulo[tid] = 0;
+    s_uhi[tid] = 0;
+    __syncthreads();
+    int buf = 0;
+    for (int i = 0; i < K; ++i) {
+        if (!s_need[i]) continue;                      // the same word in every thread
+        long long dist = ASSIGN_INF, ddist = ASSIGN_INF, l0 = 0, dend = 0;
+        bool used = false;
+        int urow = -1, r0 = i, j0 = -1, jend = ASSIGN_NONE;
+        // the row that holds column tid, read HERE, behind the barrier that ended the last augmentation: thread 0 rewrites
+        // s_dmatch while slower threads are still deciding whether the path has ended, so that decision must not read it
+        const int hold = col_ok ? s_dmatch[tid] : -1;
+        for (int step = 0; step <= K; ++step) {
+            const long long base = l0 - u_read(s_ulo, s_uhi, r0);
+            if (col_ok && !used) {
+                const float ov = overlaps[(long)r0 * D + tid], di = distances[(long)r0 * D + tid];
+                if (ov >= min_iou && di <= max_dist) {
+                    const long long cand = base + assign_cost(ov, di, cost) - v;
+                    if (cand < dist) { dist = cand; s_way[tid] = j0; }
+                }
+            }
+            if (tid == r0) ddist = base + ASSIGN_BIG;
+            PathEnd p{ASSIGN_INF, ASSIGN_NONE, -1};
+            if (!used && dist < ASSIGN_INF) p = PathEnd{dist, tid, hold};
+            if (ddist < ASSIGN_INF && shorter(PathEnd{ddist, SCENE_MAX + tid, -1}, p)) p = PathEnd{ddist, SCENE_MAX + tid, -1};
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) {
+                const PathEnd o{__shfl_xor(p.len, m, 64), __shfl_xor(p.col, m, 64), __shfl_xor(p.row, m, 64)};
+                if (shorter(o, p)) p = o;
+            }
+            if (lane == 0) { s_len[buf][w] = p.len; s_col[buf][w] = p.col; s_row[buf][w] = p.row; }
+            __syncthreads();
+            p = PathEnd{s_len[buf][0], s_col[buf][0], s_row[buf][0]};
+#pragma unroll
+            for (int x = 1; x < SCENE_MAX / 64; ++x) {
+                const PathEnd o{s_len[buf][x], s_col[buf][x], s_row[buf][x]};
+                if (shorter(o, p)) p = o;
+            }
+            buf ^= 1;
+            if (p.col >= ASSIGN_NONE) break;           // no column has a length: cannot happen, i's own dummy always has one
+            const int r = p.row;
+            if (r < 0) { jend = p.col; dend = p.len; break; }
+            if (tid == p.col) { used = true; urow = r; }
+            r0 = r;
+            j0 = p.col;
+            l0 = p.len;
+        }
+        if (jend < ASSIGN_NONE) {                      // the same in every thread
+            if (used) {                                // one writer per row: a row is held by one column
+                v += dist - dend;
+                const long long u = u_read(s_ulo, s_uhi, urow) + (dend - dist);
+                s_ulo[urow] = (int)(unsigned)(unsigned long long)u;
+                s_uhi[urow] = (int)(unsigned)((unsigned long long)u >> 32);
+            }
+            if (tid == i) {
+                const long long u = u_read(s_ulo, s_uhi, i) + dend;
+                s_ulo[i] = (int)(unsigned)(unsigned long long)u;
+                s_uhi[i] = (int)(unsigned)((unsigned long long)u >> 32);
+            }
+            if (tid == 0) {
+                int c = jend;
+                if (c >= SCENE_MAX) {                  // the dummy of row t: t stays, or becomes, unmatched
+                    const int t = c - SCENE_MAX;
+                    c = t == i ? -1 : s_match[t];
+                    s_match[t] = -1;
+                }
+                for (int link = 0; link <= K && c >= 0; ++link) {
+                    const int pc = s_way[c];
+                    const int r = pc < 0 ? i : s_dmatch[pc];
+                    s_dmatch[c] = r;
+                    s_match[r] = c;
+                    c = pc;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the match of both kernels of this file, by the rule the launch names
+template <int RULE>
+__device__ __forceinline__ void scene_match(const float* overlaps, const float* distances, int K, int D, int n, float min_iou,
+                                            float max_dist, int cost, int* s_d, int* s_need, int* s_k, int* s_cneed, int* s_match,
+                                            int* s_dmatch, const int* s_act) {
+    if constexpr (RULE == O3D_ASSIGN_GREEDY)
+        greedy_match(overlaps, distances, K, D, n, min_iou, max_dist, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
+    else
+        optimal_match(overlaps, distances, K, D, n, min_iou, max_dist, cost, s_d, s_need, s_k, s_cneed, s_match, s_dmatch);
+}
+
+template <int RULE>
 __global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
     __shared__ int s_d[SCENE_MAX], s_need[SCENE_MAX];            // per track: row_first (-1: none); the row is to be scanned
     __shared__ int s_k[SCENE_MAX], s_cneed[SCENE_MAX];           // per detection: col_first (-1: none); the column is to be scanned
@@ -170,7 +324,8 @@ __global__ __launch_bounds__(SCENE_MAX) void manage_kernel(ManageArgs a) {
     s_cneed[tid] = tid < n;
     __syncthreads();
 
-    greedy_match(a.overlaps, a.distances, K, D, n, a.min_iou, a.max_dist, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
+    scene_match<RULE>(a.overlaps, a.distances, K, D, n, a.min_iou, a.max_dist, a.cost, s_d, s_need, s_k, s_cneed, s_match, s_dmatch,
+                      s_act);
 
     // counters and retire, slot tid
     int id = -1, misses = 0, starved = 0, start = 0;
@@ -274,8 +429,10 @@ struct WalkArgs {
     int32_t* match_slot; int32_t* match_id; float* match_ov; float* match_di; int32_t* per_frame;
     int F, G, K;
     float min_iou, max_dist;
+    int cost;
 };
 
+template <int RULE>
 __global__ __launch_bounds__(SCENE_MAX) void mot_walk_kernel(WalkArgs a) {
     __shared__ int s_d[SCENE_MAX], s_need[SCENE_MAX];            // greedy_match's, rows = objects
     __shared__ int s_k[SCENE_MAX], s_cneed[SCENE_MAX];           // and columns = the K slots
@@ -320,7 +477,7 @@ __global__ __launch_bounds__(SCENE_MAX) void mot_walk_kernel(WalkArgs a) {
         s_cneed[tid] = col && s_dmatch[tid] < 0;
         __syncthreads();
 
-        greedy_match(ov, di, G, K, K, a.min_iou, a.max_dist, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
+        scene_match<RULE>(ov, di, G, K, K, a.min_iou, a.max_dist, a.cost, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
 
         // count, object tid and column tid
         const int m = valid ? s_match[tid] : -1;
@@ -360,21 +517,124 @@ __global__ __launch_bounds__(SCENE_MAX) void mot_walk_kernel(WalkArgs a) {
     if (mine) { a.last_id[tid] = last; a.tracked_prev[tid] = prev ? 1 : 0; a.ever[tid] = ever ? 1 : 0; }
 }
 
+// ---- o3d_scene_assign: the match alone, as an operator and as the per-call pin of the two rules ---------------
+// One workgroup: sets up greedy_match's entry contract from row_active / n_col, calls the rule's device function and writes
+// match, col_match and summary = {pairs, the sum of q over the pairs under `cost`} (ballots would not do for an int64 sum: a
+// wave64 butterfly, the 16 wave sums through LDS, thread 0 adds them in wave order).
+struct AssignArgs {
+    const float* overlaps; const float* distances; const int32_t* row_active; const int32_t* n_col;
+    int32_t* match; int32_t* col_match; long long* summary;
+    int K, D, cost;
+    float min_iou, max_dist;
+};
+
+template <int RULE>
+__global__ __launch_bounds__(SCENE_MAX) void assign_kernel(AssignArgs a) {
+    __shared__ int s_d[SCENE_MAX], s_need[SCENE_MAX], s_k[SCENE_MAX], s_cneed[SCENE_MAX];
+    __shared__ int s_match[SCENE_MAX], s_dmatch[SCENE_MAX], s_act[SCENE_MAX];
+    __shared__ long long s_sum[SCENE_MAX / 64];
+    __shared__ int s_cnt[SCENE_MAX / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int K = a.K, D = a.D;
+    const int n = a.n_col ? min(max(a.n_col[0], 0), D) : D;
+    const bool act = tid < K && (!a.row_active || a.row_active[tid] != 0);
+    s_match[tid] = -1;
+    s_dmatch[tid] = -1;
+    s_d[tid] = -1;
+    s_k[tid] = -1;
+    s_act[tid] = act;
+    s_need[tid] = act && n > 0;
+    s_cneed[tid] = tid < n;
+    __syncthreads();
+
+    scene_match<RULE>(a.overlaps, a.distances, K, D, n, a.min_iou, a.max_dist, a.cost, s_d, s_need, s_k, s_cneed, s_match, s_dmatch, s_act);
+
+    const int m = tid < K ? s_match[tid] : -1;
+    if (tid < K) a.match[tid] = m;
+    if (tid < D) a.col_match[tid] = s_dmatch[tid];
+    long long q = m >= 0 ? assign_cost(a.overlaps[(long)tid * D + m], a.distances[(long)tid * D + m], a.cost) : 0;
+#pragma unroll
+    for (int x = 1; x < 64; x <<= 1) q += __shfl_xor(q, x, 64);
+    const unsigned long long b = __ballot(m >= 0);
+    if (lane == 0) { s_sum[w] = q; s_cnt[w] = __popcll(b); }
+    __syncthreads();
+    if (tid == 0) {
+        long long pairs = 0, sum = 0;
+        for (int x = 0; x < SCENE_MAX / 64; ++x) { pairs += s_cnt[x]; sum += s_sum[x]; }
+        a.summary[0] = pairs;
+        a.summary[1] = sum;
+    }
+}
+
+bool assign_known(int assignment, int cost) {
+    return (assignment == O3D_ASSIGN_GREEDY || assignment == O3D_ASSIGN_OPTIMAL) && (cost == O3D_COST_DISTANCE || cost == O3D_COST_OVERLAP);
+}
+
 }  // namespace
 
-extern "C" int o3d_scene_mot_walk(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids, int F,
-                                  int G, int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev, int32_t* ever,
-                                  int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di, int32_t* per_frame,
-                                  void* stream) {
-    if (F < 0 || F > O3D_SCENE_MOT_MAX_FRAMES || G < 1 || G > O3D_CROP_MULTI_MAX_TARGETS || K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS)
+extern "C" int o3d_scene_assign(const float* overlaps, const float* distances, const int32_t* row_active, const int32_t* n_col, int K,
+                                int D, float min_iou, float max_dist, int assignment, int cost, int32_t* match, int32_t* col_match,
+                                int64_t* summary, void* stream) {
+    if (K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || D < 1 || D > O3D_SCENE_MAX_DETECTIONS || !assign_known(assignment, cost))
+        return O3D_EINVAL;
+    if (!overlaps || !distances || !match || !col_match || !summary) return O3D_EINVAL;
+    AssignArgs a{overlaps, distances, row_active, n_col, match, col_match, (long long*)summary, K, D, cost, min_iou, max_dist};
+    if (assignment == O3D_ASSIGN_OPTIMAL)
+        hipLaunchKernelGGL(assign_kernel<O3D_ASSIGN_OPTIMAL>, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    else
+        hipLaunchKernelGGL(assign_kernel<O3D_ASSIGN_GREEDY>, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_scene_mot_walk_assign(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids,
+                                         int F, int G, int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev,
+                                         int32_t* ever, int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di,
+                                         int32_t* per_frame, int assignment, int cost, void* stream) {
+    if (F < 0 || F > O3D_SCENE_MOT_MAX_FRAMES || G < 1 || G > O3D_CROP_MULTI_MAX_TARGETS || K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS ||
+        !assign_known(assignment, cost))
         return O3D_EINVAL;
     if (!overlaps || !distances || !gt_valid || !hyp_ids || !last_id || !tracked_prev || !ever || !match_slot || !match_id ||
         !match_ov || !match_di || !per_frame)
         return O3D_EINVAL;
     if (F == 0) return O3D_OK;
     WalkArgs a{overlaps, distances, gt_valid, hyp_ids, last_id, tracked_prev, ever, match_slot, match_id, match_ov, match_di, per_frame,
-               F, G, K, min_iou, max_dist};
-    hipLaunchKernelGGL(mot_walk_kernel, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+               F, G, K, min_iou, max_dist, cost};
+    if (assignment == O3D_ASSIGN_OPTIMAL)
+        hipLaunchKernelGGL(mot_walk_kernel<O3D_ASSIGN_OPTIMAL>, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    else
+        hipLaunchKernelGGL(mot_walk_kernel<O3D_ASSIGN_GREEDY>, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    return o3d_launch_status();
+}
+
+extern "C" int o3d_scene_mot_walk(const float* overlaps, const float* distances, const int32_t* gt_valid, const int32_t* hyp_ids, int F,
+                                  int G, int K, float min_iou, float max_dist, int32_t* last_id, int32_t* tracked_prev, int32_t* ever,
+                                  int32_t* match_slot, int32_t* match_id, float* match_ov, float* match_di, int32_t* per_frame,
+                                  void* stream) {
+    return o3d_scene_mot_walk_assign(overlaps, distances, gt_valid, hyp_ids, F, G, K, min_iou, max_dist, last_id, tracked_prev, ever,
+                                     match_slot, match_id, match_ov, match_di, per_frame, O3D_ASSIGN_GREEDY, O3D_COST_DISTANCE, stream);
+}
+
+extern "C" int o3d_scene_manage_assign(const float* overlaps, const float* distances, const float* dets, const int32_t* n_det, int K,
+                                       int D, float* cur, float* yaw_state, float* canon_wlh, float* results, int T,
+                                       const int32_t* frame, int32_t* active, int32_t* slot, int32_t* next_id, const int32_t* counts,
+                                       int count_col, int32_t* bank_state_next, int32_t* lanes, int rule, int32_t* ids_log,
+                                       int32_t* match_log, int32_t* dropped_log, float min_iou, float max_dist, int max_misses,
+                                       int min_points, int max_starved, int enroll, int has_dets, int assignment, int cost,
+                                       void* stream) {
+    if (K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || D < 0 || D > O3D_SCENE_MAX_DETECTIONS || T < 1 || (count_col != 0 && count_col != 1) ||
+        rule < -1 || rule > O3D_BANK_ALL || !assign_known(assignment, cost))
+        return O3D_EINVAL;
+    if (D > 0 && (!overlaps || !distances || !dets || !n_det)) return O3D_EINVAL;
+    if (!cur || !yaw_state || !canon_wlh || !results || !frame || !active || !slot || !next_id || !counts || !lanes || !ids_log ||
+        !match_log || !dropped_log)
+        return O3D_EINVAL;
+    ManageArgs a{overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, results, frame, active, slot, next_id, counts,
+                 bank_state_next, lanes, ids_log, match_log, dropped_log, K, D, T, count_col, rule, max_misses, min_points,
+                 max_starved, enroll, has_dets, min_iou, max_dist, cost};
+    if (assignment == O3D_ASSIGN_OPTIMAL)
+        hipLaunchKernelGGL(manage_kernel<O3D_ASSIGN_OPTIMAL>, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
+    else
+        hipLaunchKernelGGL(manage_kernel<O3D_ASSIGN_GREEDY>, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
     return o3d_launch_status();
 }
 
@@ -384,16 +644,8 @@ extern "C" int o3d_scene_manage(const float* overlaps, const float* distances, c
                                 int32_t* bank_state_next, int32_t* lanes, int rule, int32_t* ids_log, int32_t* match_log,
                                 int32_t* dropped_log, float min_iou, float max_dist, int max_misses, int min_points, int max_starved,
                                 int enroll, int has_dets, void* stream) {
-    if (K < 1 || K > O3D_CROP_MULTI_MAX_TARGETS || D < 0 || D > O3D_SCENE_MAX_DETECTIONS || T < 1 || (count_col != 0 && count_col != 1) ||
-        rule < -1 || rule > O3D_BANK_ALL)
-        return O3D_EINVAL;
-    if (D > 0 && (!overlaps || !distances || !dets || !n_det)) return O3D_EINVAL;
-    if (!cur || !yaw_state || !canon_wlh || !results || !frame || !active || !slot || !next_id || !counts || !lanes || !ids_log ||
-        !match_log || !dropped_log)
-        return O3D_EINVAL;
-    ManageArgs a{overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, results, frame, active, slot, next_id, counts,
-                 bank_state_next, lanes, ids_log, match_log, dropped_log, K, D, T, count_col, rule, max_misses, min_points,
-                 max_starved, enroll, has_dets, min_iou, max_dist};
-    hipLaunchKernelGGL(manage_kernel, dim3(1), dim3(SCENE_MAX), 0, o3d_stream(stream), a);
-    return o3d_launch_status();
+    return o3d_scene_manage_assign(overlaps, distances, dets, n_det, K, D, cur, yaw_state, canon_wlh, results, T, frame, active, slot,
+                                   next_id, counts, count_col, bank_state_next, lanes, rule, ids_log, match_log, dropped_log, min_iou,
+                                   max_dist, max_misses, min_points, max_starved, enroll, has_dets, O3D_ASSIGN_GREEDY,
+                                   O3D_COST_DISTANCE, stream);
 }

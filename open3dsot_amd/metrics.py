@@ -142,8 +142,9 @@ class ClearMOT:
     whose slots change hands (tracking.ManagedSceneTracker: boxes (T,K,15) and ids_log (T,K)), scored where they are.  Per chunk
     of frames two launches, o3d_scene_pair_scores_frames (every pair's overlap and distance, metrics.score_boxes' bits) and
     o3d_scene_mot_walk (one workgroup walks the frames in order: an object keeps the track id it was last matched to while that
-    pair passes the gates, the rest is matched greedily by overlap descending, distance ascending), as include/o3dsot.h states
-    them.  A pair can match when overlap >= min_iou and distance <= max_dist (2 m: the centre distance commonly used for a true
+    pair passes the gates, the rest is matched greedily by overlap descending, distance ascending -- or, with
+    assignment="optimal", by the maximum-cardinality, minimum-cost assignment under cost = "distance" | "overlap", CLEAR-MOT as
+    published, through o3d_scene_mot_walk_assign), as include/o3dsot.h states them.  A pair can match when overlap >= min_iou and distance <= max_dist (2 m: the centre distance commonly used for a true
     positive in 3D tracking).  State on the device: the walk's last_id / tracked_prev / ever (G,), totals (8,) int64 = the sums
     of per_frame, sums (2,) float64 = the matched pairs' distances and overlaps, seen / hit (G,) int64 = every object's valid and
     matched frames.  The integer totals of several ranks add up.
@@ -155,8 +156,11 @@ class ClearMOT:
     keep_logs=True keeps every chunk's match rows for logs().  sot: a SuccessPrecision that takes the matched pairs' overlaps
     and distances through its update()."""
 
-    def __init__(self, G, device=None, min_iou=0.0, max_dist=2.0, dim=3, up_axis=(0, 0, 1), keep_logs=False, sot=None):
+    def __init__(self, G, device=None, min_iou=0.0, max_dist=2.0, dim=3, up_axis=(0, 0, 1), keep_logs=False, sot=None,
+                 assignment="greedy", cost="distance"):
         from . import points_utils as PU
+        PU._assign_args(assignment, cost, "ClearMOT")
+        self.assignment, self.cost = assignment, cost
         G = int(G)
         if not 1 <= G <= PU.CROP_MULTI_MAX_TARGETS:
             raise ValueError("G must be 1..%d" % PU.CROP_MULTI_MAX_TARGETS)
@@ -208,7 +212,8 @@ class ClearMOT:
                 hi = min(lo + step, F)
                 v, h = valid[lo:hi], ids[lo:hi]
                 ov, di = PU.scene_pair_scores_frames(gt[lo:hi], v, boxes[lo:hi], h, self.dim, self.up)
-                rows = PU.scene_mot_walk(ov, di, v, h, self.state[0], self.state[1], self.state[2], self.min_iou, self.max_dist)
+                rows = PU.scene_mot_walk(ov, di, v, h, self.state[0], self.state[1], self.state[2], self.min_iou, self.max_dist,
+                                         assignment=self.assignment, cost=self.cost)
                 slot, _, mov, mdi, per_frame = rows
                 hit = slot >= 0
                 self.counts[:8] += per_frame.sum(0)

@@ -713,10 +713,59 @@ def scene_pair_scores(tracks, active, dets, n_det, dim=3, up=2, out=None):
     return out
 
 
+ASSIGNMENTS = {"greedy": capi.CONSTANTS["O3D_ASSIGN_GREEDY"], "optimal": capi.CONSTANTS["O3D_ASSIGN_OPTIMAL"]}
+ASSIGN_COSTS = {"distance": capi.CONSTANTS["O3D_COST_DISTANCE"], "overlap": capi.CONSTANTS["O3D_COST_OVERLAP"]}
+
+
+def _assign_args(assignment, cost, what):
+    """(assignment, cost) as the header numbers them; an unknown name is refused here, by name"""
+    if assignment not in ASSIGNMENTS:
+        raise ValueError("%s: assignment must be one of %s, got %r" % (what, sorted(ASSIGNMENTS), assignment))
+    if cost not in ASSIGN_COSTS:
+        raise ValueError("%s: cost must be one of %s, got %r" % (what, sorted(ASSIGN_COSTS), cost))
+    return ASSIGNMENTS[assignment], ASSIGN_COSTS[cost]
+
+
+def scene_assign(overlaps, distances, row_active=None, n_col=None, min_iou=0.0, max_dist=float("inf"), assignment="optimal",
+                 cost="distance", out=None):
+    """One o3d_scene_assign launch (no sync): who belongs to whom on overlaps / distances (K,D) float32 on the device.  A pair is
+    admissible when its row is in play (row_active (K,) int32 | None: all), its column is below n_col ((1,) int32 on the device |
+    None: D), overlap >= min_iou and distance <= max_dist.  assignment="optimal": the most admissible pairs and among those the
+    smallest sum of the integer cost (cost="distance": 1/1024 m units, "overlap": (1 - overlap) * 2^20), as include/o3dsot.h
+    states it; "greedy": the walk of o3d_scene_manage.  -> (match (K,) int32 = column | -1, col_match (D,) int32 = row | -1,
+    summary (2,) int64 = {pairs, sum of the cost}), written into `out` when given."""
+    what = "scene_assign"
+    K, D = overlaps.shape
+    _f32(overlaps, (K, D), what)
+    _f32(distances, (K, D), what)
+    if row_active is not None:
+        _i32(row_active, K, what)
+    if n_col is not None:
+        _i32(n_col, 1, what)
+    rule_args = _assign_args(assignment, cost, what)
+    dev = overlaps.device
+    if out is None:
+        out = (torch.empty((K,), dtype=torch.int32, device=dev), torch.empty((D,), dtype=torch.int32, device=dev),
+               torch.empty((2,), dtype=torch.int64, device=dev))
+    match, col_match, summary = out
+    _i32(match, K, what)
+    _i32(col_match, D, what)
+    _need_gpu(summary, what)
+    assert summary.dtype == torch.int64 and summary.numel() == 2 and summary.is_contiguous(), what
+    with torch.cuda.device(dev):
+        capi.check(capi.load().o3d_scene_assign(
+            overlaps.data_ptr(), distances.data_ptr(), row_active.data_ptr() if row_active is not None else None,
+            n_col.data_ptr() if n_col is not None else None, K, D, float(min_iou), float(max_dist), *rule_args, match.data_ptr(),
+            col_match.data_ptr(), summary.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), what)
+    return out
+
+
 def scene_manage(overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, results, frame, active, slot, next_id, counts,
                  count_col, bank_state_next, lanes, rule, ids_log, match_log, dropped_log, min_iou=0.0, max_dist=float("inf"),
-                 max_misses=2, min_points=0, max_starved=0, enroll=True, has_dets=True):
-    """One o3d_scene_manage launch (no sync) after the frame's offset_box_multi: the greedy match on overlaps / distances (K,D),
+                 max_misses=2, min_points=0, max_starved=0, enroll=True, has_dets=True, *, assignment="greedy", cost="distance"):
+    """One o3d_scene_manage launch (no sync) after the frame's offset_box_multi: the match on overlaps / distances (K,D) -- the
+    greedy walk, or with assignment="optimal" the maximum-cardinality, minimum-cost assignment under `cost` ("distance" |
+    "overlap") through o3d_scene_manage_assign --,
     the miss and starvation counters, retire, enroll and the next frame's lane table, as include/o3dsot.h states them.  dets
     (D,15), n_det (1,) int32, cur (K,15), yaw_state (K,10), canon_wlh (K,3), results (T,K,15), frame (1,) int32, active (K,) int32,
     slot (K,SCENE_SLOT_COLS) int32, next_id (1,) int32, counts (K,2) int32 with count_col 0 | 1, bank_state_next (K,2) int32 |
@@ -733,15 +782,21 @@ def scene_manage(overlaps, distances, dets, n_det, cur, yaw_state, canon_wlh, re
     assert _lane_table(lanes, what) == K
     if bank_state_next is not None:
         _i32(bank_state_next, 2 * K, what)
+    rule_args = _assign_args(assignment, cost, what)
     dev = cur.device
     with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_scene_manage(
-            overlaps.data_ptr(), distances.data_ptr(), dets.data_ptr(), n_det.data_ptr(), K, D, cur.data_ptr(), yaw_state.data_ptr(),
-            canon_wlh.data_ptr(), results.data_ptr(), T, frame.data_ptr(), active.data_ptr(), slot.data_ptr(), next_id.data_ptr(),
-            counts.data_ptr(), int(count_col), bank_state_next.data_ptr() if bank_state_next is not None else None, lanes.data_ptr(),
-            BANK_RULES[rule] if rule is not None else -1, ids_log.data_ptr(), match_log.data_ptr(), dropped_log.data_ptr(),
-            float(min_iou), float(max_dist), int(max_misses), int(min_points), int(max_starved), int(bool(enroll)),
-            int(bool(has_dets)), torch.cuda.current_stream(dev).cuda_stream), what)
+        lib = capi.load()
+        args = (overlaps.data_ptr(), distances.data_ptr(), dets.data_ptr(), n_det.data_ptr(), K, D, cur.data_ptr(), yaw_state.data_ptr(),
+                canon_wlh.data_ptr(), results.data_ptr(), T, frame.data_ptr(), active.data_ptr(), slot.data_ptr(), next_id.data_ptr(),
+                counts.data_ptr(), int(count_col), bank_state_next.data_ptr() if bank_state_next is not None else None, lanes.data_ptr(),
+                BANK_RULES[rule] if rule is not None else -1, ids_log.data_ptr(), match_log.data_ptr(), dropped_log.data_ptr(),
+                float(min_iou), float(max_dist), int(max_misses), int(min_points), int(max_starved), int(bool(enroll)),
+                int(bool(has_dets)))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if assignment == "greedy":                         # the entry it always went through
+            capi.check(lib.o3d_scene_manage(*args, stream), what)
+        else:
+            capi.check(lib.o3d_scene_manage_assign(*args, *rule_args, stream), what + "_assign")
 
 
 # ---- scoring a managed scene on the device (metrics.ClearMOT; csrc/metrics.hip, csrc/scene.hip) -----------
@@ -774,9 +829,11 @@ def scene_pair_scores_frames(gt, gt_valid, hyp, hyp_ids, dim=3, up=2, out=None):
     return out
 
 
-def scene_mot_walk(overlaps, distances, gt_valid, hyp_ids, last_id, tracked_prev, ever, min_iou=0.0, max_dist=float("inf"), out=None):
+def scene_mot_walk(overlaps, distances, gt_valid, hyp_ids, last_id, tracked_prev, ever, min_iou=0.0, max_dist=float("inf"), out=None,
+                   *, assignment="greedy", cost="distance"):
     """One o3d_scene_mot_walk launch (no sync): the CLEAR-MOT walk over the F frames of overlaps / distances (F,G,K) in order, as
-    include/o3dsot.h states it.  gt_valid (F,G), hyp_ids (F,K) int32; last_id, tracked_prev, ever (G,) int32: the carried state,
+    include/o3dsot.h states it; with assignment="optimal" the leftover match of every frame is the maximum-cardinality,
+    minimum-cost assignment under `cost` ("distance" | "overlap"), through o3d_scene_mot_walk_assign.  gt_valid (F,G), hyp_ids (F,K) int32; last_id, tracked_prev, ever (G,) int32: the carried state,
     updated in place.  -> (match_slot (F,G) int32, match_id (F,G) int32, match_ov (F,G), match_di (F,G) float32, per_frame (F,8)
     int32 = MOT_FRAME_COLS and a 0), written into `out` when given."""
     what = "scene_mot_walk"
@@ -798,13 +855,19 @@ def scene_mot_walk(overlaps, distances, gt_valid, hyp_ids, last_id, tracked_prev
     _f32(mov, (F, G), what)
     _f32(mdi, (F, G), what)
     _i32(per_frame, F * 8, what)
+    rule_args = _assign_args(assignment, cost, what)
     if F == 0:
         return out
     with torch.cuda.device(dev):
-        capi.check(capi.load().o3d_scene_mot_walk(
-            overlaps.data_ptr(), distances.data_ptr(), gt_valid.data_ptr(), hyp_ids.data_ptr(), F, G, K, float(min_iou), float(max_dist),
-            last_id.data_ptr(), tracked_prev.data_ptr(), ever.data_ptr(), slot.data_ptr(), ids.data_ptr(), mov.data_ptr(), mdi.data_ptr(),
-            per_frame.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), what)
+        lib = capi.load()
+        args = (overlaps.data_ptr(), distances.data_ptr(), gt_valid.data_ptr(), hyp_ids.data_ptr(), F, G, K, float(min_iou),
+                float(max_dist), last_id.data_ptr(), tracked_prev.data_ptr(), ever.data_ptr(), slot.data_ptr(), ids.data_ptr(),
+                mov.data_ptr(), mdi.data_ptr(), per_frame.data_ptr())
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if assignment == "greedy":                         # the entry it always went through
+            capi.check(lib.o3d_scene_mot_walk(*args, stream), what)
+        else:
+            capi.check(lib.o3d_scene_mot_walk_assign(*args, *rule_args, stream), what + "_assign")
     return out
 
 

@@ -1612,7 +1612,8 @@ class MotionSceneTracker(_Scene, _DeviceTracker):
 
 
 # ---- the slots' lifecycle on the device: associate detections, retire, enroll ------------------------------
-_MANAGE_DEFAULTS = dict(min_iou=0.0, max_dist=float("inf"), max_misses=2, min_points=0, max_starved=0, enroll=True, max_detections=256)
+_MANAGE_DEFAULTS = dict(min_iou=0.0, max_dist=float("inf"), max_misses=2, min_points=0, max_starved=0, enroll=True, max_detections=256,
+                        assignment="greedy", cost="distance")
 
 
 def _unit_box():
@@ -1634,8 +1635,10 @@ class _Managed:
       ids_log, match_log (T,K), dropped_log (T,)    row t: who held slot k after frame t, the detection it matched, the
                                                      detections that found no free slot; they grow with `boxes`
 
-    manage = dict(min_iou, max_dist, max_misses, min_points, max_starved, enroll, max_detections); the overlap and the distance
-    are metrics.score_boxes' with the model config's IoU_space / up_axis, as in score()."""
+    manage = dict(min_iou, max_dist, max_misses, min_points, max_starved, enroll, max_detections, assignment, cost); the overlap
+    and the distance are metrics.score_boxes' with the model config's IoU_space / up_axis, as in score().  assignment="optimal"
+    matches by the maximum-cardinality, minimum-cost assignment under cost = "distance" | "overlap" 
+    instead of the greedy walk: still two launches per frame, no host stop, no upload."""
 
     def _managed_state(self, manage):
         from . import metrics as MT
@@ -1647,8 +1650,10 @@ class _Managed:
         self.max_detections = int(p.pop("max_detections"))
         if not 1 <= self.max_detections <= PU.SCENE_MAX_DETECTIONS:
             raise ValueError("%s: max_detections must be 1..%d" % (self._NAME, PU.SCENE_MAX_DETECTIONS))
+        PU._assign_args(p["assignment"], p["cost"], self._NAME)
         self.manage = dict(min_iou=float(p["min_iou"]), max_dist=float(p["max_dist"]), max_misses=int(p["max_misses"]),
-                           min_points=int(p["min_points"]), max_starved=int(p["max_starved"]), enroll=bool(p["enroll"]))
+                           min_points=int(p["min_points"]), max_starved=int(p["max_starved"]), enroll=bool(p["enroll"]),
+                           assignment=p["assignment"], cost=p["cost"])
         cfg = self.model.config
         self.score_dim = int(getattr(cfg, "IoU_space", 3))
         self.score_up = MT.up_index(tuple(getattr(cfg, "up_axis", (0, 0, 1))))
@@ -1792,7 +1797,7 @@ class _Managed:
         """Score rows [0:t] of the run against gt_boxes (t,G,15), where they are: boxes[:t] and ids_log[:t] go to a
         metrics.ClearMOT, whose overlap and distance are the model config's, as in score().  A slot
         follows no fixed object here, so G need not be K.  valid (t,G) | None: 0 where an object has no annotation.  metrics:
-        a ClearMOT to add to | None: a new one with **gates (min_iou, max_dist, keep_logs, sot).  Device tensors travel as they
+        a ClearMOT to add to | None: a new one with **gates (min_iou, max_dist, keep_logs, sot, assignment, cost).  Device tensors travel as they
         are: no host stop and no upload.  -> the ClearMOT; compute() is its one read-back."""
         from . import metrics as MT
         gt = PU._dev32(gt_boxes, self.dev)
@@ -2017,6 +2022,8 @@ def evaluate_managed_scene(model, frames, gt_boxes, valid=None, detections=None,
     them) starts from frame 0's valid boxes and runs one update(frames[t], detections[t], n_detections[t:t+1]) per frame.
     detections (T,D,15) with n_detections (T,) | None (= D each); detections=None: every frame's valid ground-truth boxes,
     moved to the front on the host once and uploaded once.  mot: a metrics.ClearMOT to add to | a dict of its gates | None.
+    assignment / cost ("optimal", "distance" | "overlap": DESIGN.md section 12l) go into `manage` for the tracker and into the
+    gates of `mot` for the metric; the two are chosen independently.
     No host stop per frame.  -> (the ClearMOT's compute() dict, the tracker)."""
     _scene_sampling(sampling, "evaluate_managed_scene")
     gt_host = np.ascontiguousarray(gt_boxes.detach().cpu().numpy() if torch.is_tensor(gt_boxes) else gt_boxes, dtype=np.float32)

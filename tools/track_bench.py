@@ -63,7 +63,11 @@ between two events: o3d_scene_pair_scores alone, then both) and of the frame's c
 (the managed tracker always makes it), the managed tracker's final status and whether both replay a graph.  With --mot the
 tracked run is then scored as multi-object tracking against the K ground-truth objects (tracker.score_mot, DESIGN.md section
 12k): the device time of score_mot over all frames and of o3d_scene_pair_scores_frames and o3d_scene_mot_walk alone, each run
-between two events (median, smallest, largest of 15), and the CLEAR-MOT numbers of the run.
+between two events (median, smallest, largest of 15), and the CLEAR-MOT numbers of the run.  --assignment optimal [--cost overlap]
+ adds, in the same process beside the greedy run: a second managed tracker that matches by the optimal
+assignment, timed in turn with the other two, its o3d_scene_manage_assign launch, with --mot the walk and score_mot under the
+optimal rule, the path steps the Python restatement (tests/assign_oracle.py) counts on the read-back matrices, and one
+o3d_scene_assign call at K = D = 64 with every pair tied, timed once after one warm-up call.
 """
 import argparse
 import json
@@ -78,6 +82,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))      # det_init, for motion_oracle.init_weights
+import assign_oracle as AO  # noqa: E402
 import motion_oracle as MO  # noqa: E402
 import tracking_oracle as TO  # noqa: E402
 from open3dsot_amd import m2track, points_utils as PU, synth, trackers, tracking  # noqa: E402
@@ -372,6 +377,10 @@ def manage_main(args, dev):
     scratch = first_capture(model, dframes, gt[0, 0])      # noqa: F841  (kept alive: the first tracker of a process is the slow one)
     trks = {"managed": tracking.managed_scene_tracker_for(model, K, sampling=sampling, manage=dict(max_detections=max(D, 1))),
             "scene": tracking.scene_tracker_for(model, K, sampling=sampling)}
+    optimal = args.assignment == "optimal"
+    if optimal:
+        rule = dict(assignment="optimal", cost=args.cost)
+        trks["managed_optimal"] = tracking.managed_scene_tracker_for(model, K, sampling=sampling, manage=dict(max_detections=max(D, 1), **rule))
 
     def run(m, n):
         trk = trks[m]
@@ -379,7 +388,7 @@ def manage_main(args, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for t in range(1, n):
-            if m == "managed":
+            if m != "scene":
                 trk.update(dframes[t], dets[t], n_det)
             else:
                 trk.update(dframes[t])
@@ -409,6 +418,8 @@ def manage_main(args, dev):
     crop_both_ms = device_ms(lambda: man._crop_scene([prev, pts] if motion else [pts, prev]))
     crop_one_ms = crop_both_ms if motion else device_ms(lambda: man._crop_scene([pts, None]))
     mot = mot_timing(man, gt, dev) if args.mot else {}
+    if optimal:
+        mot.update(optimal_timing(trks["managed_optimal"], last, n_det, motion, gt, dev, rule, scores_ms, mid, ms, args.mot))
     print(json.dumps({
         "workload": "%s tracking %d targets through a %d-frame, %d-point synthetic scene with %d device detections per frame (fixture "
                     "weights, eval, fp32), median of %d runs, the two loops in turn" % (args.model.upper(), K, args.frames,
@@ -428,7 +439,40 @@ def manage_main(args, dev):
         "scene_overflow": list(scn.overflow()), **mot}))
 
 
-def mot_timing(man, gt, dev, runs=15):
+def optimal_timing(man, last, n_det, motion, gt, dev, rule, scores_ms, mid, ms, with_mot):
+    """--assignment optimal: the second managed tracker's figures, keys prefixed optimal_; the path steps of the last frame's
+    match and (--mot) of every frame of the walk, counted by tests/assign_oracle.py on the read-back matrices; the tied call"""
+    K, D = man.K, last.shape[0]
+    ov, di = (man._pairs[i, :K * D].view(K, D) for i in (0, 1))
+    bank_next = None if motion else man.bank_state[man.t & 1]
+    active = man.active.cpu().numpy()                                   # before the timing calls below
+    PU.scene_pair_scores(man.cur, man.active, last, n_det, man.score_dim, man.score_up, out=(ov, di))
+    stats = {}
+    AO.assign(ov.cpu().numpy(), di.cpu().numpy(), active, int(n_det), man.manage["min_iou"], man.manage["max_dist"], stats=stats, **rule)
+    both_ms = device_ms(lambda: man._manage(last, n_det, 1 if motion else 0, bank_next, None if motion else man.aggregation))
+    out = {"optimal_rule": rule, "optimal_managed_ms_per_frame": round(mid["managed_optimal"], 4),
+           "optimal_managed_ms_per_frame_min_max": [round(ms["managed_optimal"][0], 4), round(ms["managed_optimal"][-1], 4)],
+           "optimal_manage_launch_device_ms": round(both_ms - scores_ms, 5),
+           "optimal_management_share_of_scene_frame": round(both_ms / mid["scene"], 4),
+           "optimal_manage_path_steps_last_frame": stats["steps"], "optimal_hip_graph": man.graph is not None}
+    if with_mot:
+        res = mot_timing(man, gt, dev, rule=rule)
+        out.update({"optimal_" + k: v for k, v in res.items()})
+    n = 64                                                              # every pair tied: row r takes r + 1 steps
+    tied = (torch.zeros((n, n), device=dev), torch.ones((n, n), device=dev))
+    PU.scene_assign(*tied, **rule)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    res = PU.scene_assign(*tied, **rule)
+    b.record()
+    b.synchronize()
+    steps = n * (n + 1) // 2
+    out.update({"assign_tied_64_device_ms_once": round(a.elapsed_time(b), 5), "assign_tied_64_path_steps": steps,
+                "assign_tied_64_us_per_step": round(1e3 * a.elapsed_time(b) / steps, 4), "assign_tied_64_summary": res[2].tolist()})
+    return out
+
+
+def mot_timing(man, gt, dev, runs=15, rule=None):
     """--mot: score the managed run that was just tracked as multi-object tracking, G = K ground-truth
     objects over all its frames: the device time of score_mot (both launches and the torch reductions of ClearMOT.update) and of
     each launch alone, every run between two events of its own, median and range of `runs` runs after 3 of warm-up"""
@@ -437,10 +481,16 @@ def mot_timing(man, gt, dev, runs=15):
     g_dev = torch.from_numpy(np.ascontiguousarray(gt[:T], dtype=np.float32)).to(dev)
     v_dev = torch.ones((T, K), dtype=torch.int32, device=dev)
     boxes, ids = man.boxes[:T], man.ids_log[:T]
-    m = MT.ClearMOT(K, dev, dim=man.score_dim, up_axis=(0, 0, 1) if man.score_up == 2 else (0, -1, 0))
+    rule = dict(rule or {})                                             # {}: the greedy walk
+    m = MT.ClearMOT(K, dev, dim=man.score_dim, up_axis=(0, 0, 1) if man.score_up == 2 else (0, -1, 0), **rule)
     assert m.chunk_frames(K) >= T, "the separate launches below time one chunk"
     ov, di = PU.scene_pair_scores_frames(g_dev, v_dev, boxes, ids, m.dim, m.up)
-    rows = PU.scene_mot_walk(ov, di, v_dev, ids, m.state[0], m.state[1], m.state[2], m.min_iou, m.max_dist)
+    rows = PU.scene_mot_walk(ov, di, v_dev, ids, m.state[0], m.state[1], m.state[2], m.min_iou, m.max_dist, **rule)
+    steps = {}
+    if rule:                                                            # the path steps of the walk, counted by the restatement
+        stats = {}
+        AO.mot_walk(ov.cpu().numpy(), di.cpu().numpy(), v_dev.cpu().numpy(), ids.cpu().numpy(), None, m.min_iou, m.max_dist, stats=stats, **rule)
+        steps = {"mot_walk_path_steps_per_frame": round(stats["steps"] / T, 2)}
 
     def timed(fn):
         ms = []
@@ -458,11 +508,11 @@ def mot_timing(man, gt, dev, runs=15):
     whole = timed(lambda: man.score_mot(g_dev, v_dev, metrics=m))
     res = m.compute()
     scores = timed(lambda: PU.scene_pair_scores_frames(g_dev, v_dev, boxes, ids, m.dim, m.up, out=(ov, di)))
-    walk = timed(lambda: PU.scene_mot_walk(ov, di, v_dev, ids, m.state[0], m.state[1], m.state[2], m.min_iou, m.max_dist, out=rows))
+    walk = timed(lambda: PU.scene_mot_walk(ov, di, v_dev, ids, m.state[0], m.state[1], m.state[2], m.min_iou, m.max_dist, out=rows, **rule))
     return {"mot_frames": T, "mot_objects": K, "mot_gates": [m.min_iou, m.max_dist], "mot_runs": runs,
             "score_mot_device_ms_median_min_max": whole, "pair_scores_frames_device_ms_median_min_max": scores,
             "mot_walk_device_ms_median_min_max": walk, "mot_walk_ms_per_frame": round(walk[0] / T, 5),
-            "mot": {k: (round(v, 6) if isinstance(v, float) else v) for k, v in res.items()}}
+            "mot": {k: (round(v, 6) if isinstance(v, float) else v) for k, v in res.items()}, **steps}
 
 
 def lanes_main(args, dev):
@@ -565,6 +615,9 @@ def main():
                                                           "tracker against the plain one")
     ap.add_argument("--mot", action="store_true", help="with --manage: time score_mot (ClearMOT) on the tracked run, and its two "
                                                        "launches alone, each between two events, 15 runs")
+    ap.add_argument("--assignment", default="greedy", choices=sorted(PU.ASSIGNMENTS),
+                    help="with --manage: optimal adds a managed tracker, its launches and (--mot) its walk under the optimal assignment")
+    ap.add_argument("--cost", default="distance", choices=sorted(PU.ASSIGN_COSTS), help="--assignment optimal: the integer cost")
     ap.add_argument("--tracklets", type=int, default=64, help="--lanes: tracklets of the epoch, --frames frames each")
     ap.add_argument("--distinct", type=int, default=8, help="--lanes: different synthetic sequences, used in rotation")
     args = ap.parse_args()
