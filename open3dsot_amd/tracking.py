@@ -178,13 +178,64 @@ class DrawCache:
         return len(self._held)
 
 
+def _is_motion(model):
+    from .m2track import M2TRACK
+    return isinstance(model, M2TRACK)
+
+
+_OTHER_FAMILY = {      # class -> where the models of the other family go
+    "MultiTargetTracker": "the motion tracker follows one target per MotionSequenceTracker, K targets per MultiMotionTracker",
+    "MultiMotionTracker": "the matching trackers (BAT, P2B) follow K targets with MultiTargetTracker",
+    "LaneTracker": "the motion tracker runs on MotionLaneTracker", "MotionLaneTracker": "the matching trackers run on LaneTracker",
+    "SceneTracker": "the motion tracker follows the K targets of a live scene with MotionSceneTracker",
+    "MotionSceneTracker": "the matching trackers (BAT, P2B) follow the K targets of a live scene with SceneTracker"}
+
+
+def _require_family(model, motion, name):
+    """class `name` serves one model family: the motion tracker (m2track.M2TRACK) or the matching trackers"""
+    if _is_motion(model) != motion:
+        family = "motion tracker (M2TRACK)" if motion else "matching trackers (BAT, P2B)"
+        raise TypeError("%s serves the %s; %s" % (name, family, _OTHER_FAMILY[name]))
+
+
+def _reference_rule(reference_BB):
+    """the config's reference_BB -> (by_gt, back): under previous_result a frame starts from the tracker's last box; under
+    previous_gt / current_gt (by_gt) from the ground-truth box of frame t - back, back = 1 / 0"""
+    u = str(reference_BB).upper()
+    if not any(k in u for k in ("PREVIOUS_RESULT", "CURRENT_GT", "PREVIOUS_GT")):
+        raise ValueError("reference_BB %r" % (reference_BB,))
+    by_gt = "PREVIOUS_RESULT" not in u
+    return by_gt, 1 if by_gt and "PREVIOUS_GT" in u else 0
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else x
+
+
+def _score_space(cfg):
+    """(dim, up_axis) of estimateOverlap / estimateAccuracy: the config's IoU_space and up_axis, 3 and (0,0,1) when absent"""
+    return int(getattr(cfg, "IoU_space", 3)), tuple(getattr(cfg, "up_axis", (0, 0, 1)))
+
+
+def _boxes15(boxes, device, keep=False):
+    """a tensor, an ndarray or a list of boxes as pack_box takes them (an empty one included) -> (n,15) float32, contiguous,
+    on `device`; keep: a tensor stays on the device it is on"""
+    if torch.is_tensor(boxes) and keep:
+        b = boxes.to(torch.float32)
+    elif torch.is_tensor(boxes) or isinstance(boxes, np.ndarray):
+        b = PU._dev32(boxes, device)
+    else:
+        b = torch.stack([PU.pack_box(x, device) for x in boxes]) if len(boxes) else torch.zeros((0, 15), device=device)
+    return b.reshape(-1, 15).contiguous()
+
+
 class _DeviceTracker:
     """What the tracking loops share: the box state on the device (the last result box, R0 + accumulated yaw, the canonical
     box's wlh), the (T,15) results buffer with its device-side frame counter, the crop call with the frame's one count
-    read-back (and buffer growth when a crop exceeds its capacity), the index staging and the network as a HIP graph captured
-    once per tracker (eager when the capture fails, unless O3D_REQUIRE_GRAPH=1).  With n_targets = K the per-target state has
-    a leading K axis (`lead`): cur (K,15), yaw_state (K,10), boxes (T,K,15), counts_dev (2K,).  Subclasses provide `_update()`
-    and `_forward()` on their static inputs."""
+    read-back (and buffer growth when a crop exceeds its capacity), the index staging, the network as a HIP graph captured
+    once per tracker (eager when the capture fails, unless O3D_REQUIRE_GRAPH=1) and the one box update (_offset_box).  With
+    n_targets = K the per-target state has a leading K axis (`lead`): cur (K,15), yaw_state (K,10), boxes (T,K,15), counts_dev
+    (2K,).  Subclasses provide `_update()` and `_forward()` on their static inputs."""
     _NAME = "tracker"
 
     def __init__(self, model, seed, use_graph, max_frames, defaults, n_targets=None, sampling="reference", record_indices=False):
@@ -222,12 +273,14 @@ class _DeviceTracker:
     def _pack(self, box0):
         return PU.pack_box(box0, self.dev)
 
-    def _restart(self, b, k=Ellipsis):
-        """the last result box (of target k) := b, its yaw state restarted from b's rotation"""
+    def _restart(self, b, k=Ellipsis, row=True):
+        """the last result box (of target k) := b, its yaw state restarted from b's rotation; row: b is also the result of the
+        most recent frame"""
         self.cur[k].copy_(b)
         self.yaw_state[k][..., :9].copy_(b[..., 6:15])
         self.yaw_state[k][..., 9] = 0.0
-        self.boxes[self.t - 1][k].copy_(b)
+        if row:
+            self.boxes[self.t - 1][k].copy_(b)
 
     def init(self, points0, box0):
         PU._need_gpu(points0, self._NAME + ".init")
@@ -332,6 +385,17 @@ class _DeviceTracker:
         with torch.no_grad():
             return self.model.evaluate_one_sample(self.inputs)
 
+    def _offset_box(self, ref, offset, rebase=None):
+        """The frame's one box update, getOffsetBB with the config's keywords: `ref` moved by `offset` into cur and into row
+        `frame` of the results.  rebase (the caller gave ref): a flag, or (K,) int32 | None where `lead` and `active` exist."""
+        c = self
+        if c.lead:
+            PU.offset_box_multi(ref, offset, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, rebase=rebase,
+                                active=c.active, degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        else:
+            PU.offset_box(ref, offset.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=rebase, degrees=c.degrees,
+                          use_z=c.use_z, limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+
     # ---- one frame ---------------------------------------------------------------------------------------------------------
     def _run(self, points, *args):
         """update(): the checks, then the subclass's _update on the tracker's device"""
@@ -381,9 +445,7 @@ class _DeviceTracker:
             raise ValueError("%s.score: gt_boxes %s for results %s" % (self._NAME, tuple(gt.shape), (self.t,) + self.lead + (15,)))
         if valid is not None:
             valid = torch.as_tensor(valid).to(self.dev)
-        cfg = self.model.config
-        return MT.score_boxes(gt, self.boxes[:self.t], int(getattr(cfg, "IoU_space", 3)), tuple(getattr(cfg, "up_axis", (0, 0, 1))),
-                              valid=valid, accumulate=metrics)
+        return MT.score_boxes(gt, self.boxes[:self.t], *_score_space(self.model.config), valid=valid, accumulate=metrics)
 
 
 class _KTargets:
@@ -408,14 +470,21 @@ class _KTargets:
         self.draws = DrawCache()
         self.crop_calls = 0
 
+    def _k_stage(self, record_dtype, n_records, idx_cols):
+        """the one upload per frame of a sampling="reference" K-loop, a pinned buffer and its device copy: n_records job
+        records (job_rec), then the K targets' indices (idx_rec (K, idx_cols) int32, on the device at idx_ptr)"""
+        jb = n_records * record_dtype.itemsize
+        self.stage_host = torch.zeros((jb + 4 * self.K * idx_cols,), dtype=torch.uint8).pin_memory()
+        self.stage = torch.zeros((jb + 4 * self.K * idx_cols,), dtype=torch.uint8, device=self.dev)
+        self.job_rec = self.stage_host.numpy()[:jb].view(record_dtype)
+        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(self.K, idx_cols)
+        self.idx_ptr = self.stage.data_ptr() + jb
+
     def _pack(self, boxes):
-        if torch.is_tensor(boxes) or isinstance(boxes, np.ndarray):
-            b = PU._dev32(boxes, self.dev).reshape(-1, 15)
-        else:
-            b = torch.stack([PU.pack_box(x, self.dev) for x in boxes])
+        b = _boxes15(boxes, self.dev)
         if b.shape[0] != self.K:
             raise ValueError("%d boxes for %d targets" % (b.shape[0], self.K))
-        return b.contiguous()
+        return b
 
     def init(self, points0, boxes0):
         boxes = super().init(points0, boxes0)
@@ -458,7 +527,8 @@ class _MatchingTracker(_DeviceTracker):
     """What SequenceTracker (one target, K = 1, no leading axis) and MultiTargetTracker (K targets) share: the config rules
     (reference_BB, shape_aggregation), the batch-K static inputs of the network, the canonical boxes of the BoxCloud, the
     search buffer and the template bank (one per target) with its slot rules.  bank_fixed / bank_total / slots / counts are
-    ints for the single tracker and (K,) int64 arrays for K targets; the same expressions serve both."""
+    ints for the single tracker and (K,) int64 arrays for K targets; the same expressions serve both.  For the free-running
+    loops with a leading axis it also holds the family's one _feed and its two crop groups."""
     _REF_KW = "ref_box"
 
     def __init__(self, model, seed, use_graph, max_frames, search_capacity, model_capacity, n_targets=None, sampling="reference",
@@ -466,9 +536,7 @@ class _MatchingTracker(_DeviceTracker):
         super().__init__(model, seed, use_graph, max_frames, _DEFAULTS, n_targets, sampling, record_indices)
         self.K = K = n_targets or 1
         self.aggregation = _aggregation(self.shape_aggregation)
-        if not any(k in str(self.reference_BB).upper() for k in ("PREVIOUS_RESULT", "PREVIOUS_GT", "CURRENT_GT")):
-            raise ValueError("reference_BB %r" % (self.reference_BB,))
-        self.needs_ref_box = "PREVIOUS_RESULT" not in str(self.reference_BB).upper()
+        self.needs_ref_box = _reference_rule(self.reference_BB)[0]
         self.with_boxcloud = hasattr(model, "mlp_bc")
         M, N = int(self.template_size), int(self.search_size)
         f32 = dict(dtype=torch.float32, device=self.dev)
@@ -494,6 +562,9 @@ class _MatchingTracker(_DeviceTracker):
                 self.table_t = draw_table(self.bank_capacity, M, self.dev)
                 self.table_s = draw_table(int(search_capacity), N, self.dev)
             self.draw_src = (self.table_t, self.table_s) if self.tabled else self.keys      # PU.resample_drawn's sources: (template, search)
+            if lead:                  # _feed's views, by frame parity p: (state_in, state_out, the template counts = its column 1)
+                self._states = [(self.bank_state[1 - p], self.bank_state[p], self.bank_state[p].view(-1)[1:]) for p in (0, 1)]
+                self._model_counts = self.counts_dev[1:]
         else:
             self.bank = torch.empty(self.lead + (2 * self.model_capacity, 3), **f32)
         # log, per frame: (search count, model count of the crop made this frame | None, template points)
@@ -545,16 +616,34 @@ class _MatchingTracker(_DeviceTracker):
                     bank[n:2 * n].copy_(bank[:n])
                 c.bank_total = 2 * nm
 
-    def _parity_states(self):
-        """the free-running loops with a leading axis (LaneTracker, SceneTracker), by frame parity p: (state_in, state_out, the
-        template counts = column 1 of state_out at stride 2) of bank_state (2,L,2)"""
-        return [(self.bank_state[1 - p], self.bank_state[p], self.bank_state[p].view(-1)[1:]) for p in (0, 1)]
-
     def _boxcloud(self):
         """the templates' BoxClouds against the canonical boxes (BAT only)"""
         if self.with_boxcloud:
             PU.boxcloud_into(self.inputs["points2cc_dist_t"], self.inputs["template_points"], self.canon_centre, self.canon_wlh,
                              self.canon_rot)
+
+    # ---- the free-running loops with a leading axis (LaneTracker, SceneTracker, ManagedSceneTracker) ---------------------------
+    def _feed(self, lanes, parity):
+        """Everything between the crops and the box update, on the lane table `lanes`: the staged model crops into the banks, both
+        draws and gathers, the BoxClouds, the network -> (the offsets (L,4), state_out: what the next frame reads as state_in)"""
+        c = self
+        state_in, state_out, totals = c._states[parity]
+        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
+        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
+                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
+        c._boxcloud()
+        return c._network()[0], state_out
+
+    # the two crop groups of a scene frame; group g counts into column g of the counts (K,2)
+    _FRAME_GROUP = 0          # group 0 (the search windows) crops the frame, group 1 (the model crops) the one before; a managed
+    #                           slot starves on column 0, and its bank restarts in _feed's state_out under `aggregation`
+    _GATED = 1                # the model crop is made only for the slots whose bank takes one (scene_lane_rows' has_crop)
+
+    def _crop_groups(self, ref):
+        """per group (boxes (K,15), scale, offset, mode, out (K,capacity,3)): the search windows by `ref`, the model crops by cur"""
+        c = self
+        return [(ref, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf),
+                (c.cur, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, c.staging)]
 
 
 def _matching_overflow(counts, search_capacity, model_capacity, bank_capacity, aggregation):
@@ -646,8 +735,7 @@ class SequenceTracker(_MatchingTracker):
                            (c.search_buf, c.counts_dev[0:1], c.draw_src[1], c.inputs["search_points"], c.used_s)])
         c._boxcloud()
         best, _ = c._network()
-        PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
-                      use_z=c.use_z, limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        c._offset_box(ref, best, ref_box is not None)
         return c._done(pts, None)
 
     def overflow(self):
@@ -671,8 +759,7 @@ class SequenceTracker(_MatchingTracker):
                           (None if zero_s else c.search_buf, c.idx[M:], c.inputs["search_points"])])
         c._boxcloud()
         best, _ = c._network()
-        PU.offset_box(ref, best.reshape(-1), out=c.cur, yaw_state=c.yaw_state, rebase=ref_box is not None, degrees=c.degrees,
-                      use_z=c.use_z, limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        c._offset_box(ref, best, ref_box is not None)
         return c._done(pts, (ns, nm, nt))
 
 
@@ -709,22 +796,13 @@ class MultiTargetTracker(_KTargets, _MatchingTracker):
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
                  sampling="reference"):
         _sampling(sampling, self._NAME)
-        from .m2track import M2TRACK
-        if isinstance(model, M2TRACK):
-            raise TypeError("MultiTargetTracker serves the matching trackers (BAT, P2B); the motion tracker follows one "
-                            "target per MotionSequenceTracker, K targets per MultiMotionTracker")
+        _require_family(model, False, "MultiTargetTracker")
         K = self._n_targets(n_targets)
         super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity, K)
         self._k_state(K)
-        dev, MN = self.dev, int(self.template_size) + int(self.search_size)
-        self.rebase_all = torch.ones((K,), dtype=torch.int32, device=dev)
+        self.rebase_all = torch.ones((K,), dtype=torch.int32, device=self.dev)
         # the frame's one upload: 2K resample jobs [template 0..K-1, search 0..K-1], then the K * (M + N) indices
-        jb = 2 * K * PU.RESAMPLE_JOB.itemsize
-        self.stage_host = torch.zeros((jb + 4 * K * MN,), dtype=torch.uint8).pin_memory()
-        self.stage = torch.zeros((jb + 4 * K * MN,), dtype=torch.uint8, device=dev)
-        self.job_rec = self.stage_host.numpy()[:jb].view(PU.RESAMPLE_JOB)
-        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, MN)
-        self.idx_ptr = self.stage.data_ptr() + jb
+        self._k_stage(PU.RESAMPLE_JOB, 2 * K, int(self.template_size) + int(self.search_size))
 
     def _crops(self, pts, ref, slots):
         """the frame's one crop call + the count read-back -> (search counts (K), model counts (K) | None)"""
@@ -788,9 +866,7 @@ class MultiTargetTracker(_KTargets, _MatchingTracker):
         PU.resample_multi(c.stage, 2 * K)
         c._boxcloud()
         best, _ = c._network()
-        PU.offset_box_multi(ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame,
-                            rebase=c.rebase_all if ref_boxes is not None else None, active=c.active, degrees=c.degrees,
-                            use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        c._offset_box(ref, best, c.rebase_all if ref_boxes is not None else None)
         return c._done(pts, (ns, nm, nt))
 
 
@@ -798,7 +874,50 @@ class MultiTargetTracker(_KTargets, _MatchingTracker):
 _MOTION_DEFAULTS = dict(bb_scale=1.25, bb_offset=2, point_sample_size=1024, degrees=False, use_z=True, limit_box=False)
 
 
-class MotionSequenceTracker(_DeviceTracker):
+class _MotionTracker(_DeviceTracker):
+    """What the loops of the motion tracker (m2track.M2TRACK) share: the batch-K static inputs of the network and the two crop
+    buffers, with `lead` = () for one target, (K,) / (L,) for K targets or L lanes, and, free-running, the record of the
+    indices, the index source and the feed of the loops with a leading axis."""
+
+    def __init__(self, model, seed, use_graph, max_frames, capacity, n_targets=None, sampling="reference", record_indices=False):
+        if sampling in FREE_RUNNING and int(capacity) < 1:         # a fixed size: nothing can grow a buffer without reading a count
+            raise ValueError("capacity must be positive")
+        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, n_targets, sampling, record_indices)
+        dev, lead, N = self.dev, self.lead, int(self.point_sample_size)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.box_aware = bool(getattr(model, "box_aware", False))
+        self.inputs = {"points": torch.zeros((n_targets or 1, 2 * N, 5), **f32)}
+        if self.box_aware:
+            self.inputs["candidate_bc"] = torch.zeros((n_targets or 1, 2 * N, 9), **f32)
+        self.crop_buf = torch.empty((2,) + lead + (int(capacity), 3), **f32)      # [0] the previous frame's crops, [1] the current one's
+        if self.free_running:
+            self._halves = (self.crop_buf[0], self.crop_buf[1])            # views made once: nothing grows crop_buf here
+            self.used = torch.full(lead + (2 * N,), -1, dtype=torch.int32, device=dev) if self.record_indices else None
+            self.used_prev, self.used_this = (self.used[..., :N], self.used[..., N:]) if self.record_indices else (None, None)
+            if self.tabled:           # one table for both halves: the reference draws both with seed=1
+                self.table = draw_table(int(capacity), N, dev)
+            self.draw_src = self.table if self.tabled else self.keys      # the source of PU.motion_input_drawn and its lane form
+
+    # ---- the free-running loops with a leading axis (MotionLaneTracker, MotionSceneTracker, ManagedMotionSceneTracker) ----------
+    def _feed(self, lanes, parity):
+        """Everything between the crops and the box update, on the lane table `lanes`: gather, time stamp, prior-targetness
+        mask and candidate BoxCloud into the static inputs, the network.  -> (the offsets (L,4), None: there is no bank)"""
+        c = self
+        PU.motion_input_drawn_lanes(c._halves[0], c._halves[1], c.counts2, c.draw_src, c.canon_wlh, lanes, c.inputs["points"],
+                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
+        return c._network(), None
+
+    # the two crop groups of a scene frame; group g counts into column g of the counts (K,2)
+    _FRAME_GROUP = 1          # group 0 crops the frame before, group 1 the frame; a managed slot starves on column 1
+    _GATED = None             # both are made on every frame, whatever the lane rows say
+    aggregation = None        # no template bank: scene_lane_rows and o3d_scene_manage take no rule
+
+    def _crop_groups(self, ref):
+        """per group (boxes (K,15), scale, offset, mode, out (K,capacity,3)): both by the last boxes"""
+        return [(self.cur, self.bb_scale, self.bb_offset, PU.CROP_SUBWINDOW, self.crop_buf[h]) for h in (0, 1)]
+
+
+class MotionSequenceTracker(_MotionTracker):
     """Device-resident tracking loop for the motion tracker (m2track.M2TRACK): the frame loop of evaluate_one_sequence over
     MotionBaseModel.build_input_dict (models/base_model.py:255-304).  Same surface as SequenceTracker (init, update, set_box,
     results, log, out).  Per frame t >= 1:
@@ -826,24 +945,9 @@ class MotionSequenceTracker(_DeviceTracker):
     _NAME = "MotionSequenceTracker"
 
     def __init__(self, model, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference", record_indices=False):
-        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, None, sampling, record_indices)
-        dev, N = self.dev, int(self.point_sample_size)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.box_aware = bool(getattr(model, "box_aware", False))
-        self.inputs = {"points": torch.zeros((1, 2 * N, 5), **f32)}
-        if self.box_aware:
-            self.inputs["candidate_bc"] = torch.zeros((1, 2 * N, 9), **f32)
-        self.crop_buf = torch.empty((2, int(capacity), 3), **f32)          # [0] the previous frame's crop, [1] the current one's
-        if self.free_running:
-            if int(capacity) < 1:
-                raise ValueError("capacity must be positive")
-            self.used = torch.full((2 * N,), -1, dtype=torch.int32, device=dev) if self.record_indices else None
-            self.used_prev, self.used_this = (self.used[:N], self.used[N:]) if self.record_indices else (None, None)
-            if self.tabled:           # one table for both halves: the reference draws both with seed=1
-                self.table = draw_table(int(capacity), N, dev)
-            self.draw_src = self.table if self.tabled else self.keys      # PU.motion_input_drawn's source
-        else:
-            self._index_buffers(2 * N)
+        super().__init__(model, seed, use_graph, max_frames, capacity, None, sampling, record_indices)
+        if not self.free_running:
+            self._index_buffers(2 * int(self.point_sample_size))
 
     def _crops(self, pts):
         c = self
@@ -869,8 +973,7 @@ class MotionSequenceTracker(_DeviceTracker):
         PU.motion_input_drawn(c.crop_buf[0], c.crop_buf[1], c.counts_dev, c.draw_src, c.canon_wlh, c.t == 1, c.inputs["points"],
                               c.inputs["candidate_bc"] if c.box_aware else False, c.used)
         est = c._network()
-        PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
-                      limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        c._offset_box(c.cur, est)
         return c._done(pts, None)
 
     def overflow(self):
@@ -890,12 +993,11 @@ class MotionSequenceTracker(_DeviceTracker):
         PU.motion_input(c.crop_buf[0, :n_prev], c.crop_buf[1, :n_this], c.idx, c.canon_wlh, c.t == 1, zero=zero,
                         out_points=c.inputs["points"], out_bc=c.inputs["candidate_bc"] if c.box_aware else False)
         est = c._network()
-        PU.offset_box(c.cur, est.reshape(-1), out=c.cur, yaw_state=c.yaw_state, degrees=c.degrees, use_z=c.use_z,
-                      limit_box=c.limit_box, seed=c.seed, results=c.boxes, frame=c.frame)
+        c._offset_box(c.cur, est)
         return c._done(pts, (n_prev, n_this))
 
 
-class MultiMotionTracker(_KTargets, _DeviceTracker):
+class MultiMotionTracker(_KTargets, _MotionTracker):
     """Device-resident tracking loop of the motion tracker (m2track.M2TRACK) for K targets in the same frames: what
     MotionSequenceTracker does per target happens here once per frame for all of them.  The surface is MultiTargetTracker's:
 
@@ -926,27 +1028,12 @@ class MultiMotionTracker(_KTargets, _DeviceTracker):
 
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="reference"):
         _sampling(sampling, self._NAME)
-        from .m2track import M2TRACK
-        if not isinstance(model, M2TRACK):
-            raise TypeError("MultiMotionTracker serves the motion tracker (M2TRACK); the matching trackers (BAT, P2B) follow "
-                            "K targets with MultiTargetTracker")
+        _require_family(model, True, "MultiMotionTracker")
         K = self._n_targets(n_targets)
-        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, K)
+        super().__init__(model, seed, use_graph, max_frames, capacity, K)
         self._k_state(K)
-        dev, N = self.dev, int(self.point_sample_size)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.box_aware = bool(getattr(model, "box_aware", False))
-        self.inputs = {"points": torch.zeros((K, 2 * N, 5), **f32)}
-        if self.box_aware:
-            self.inputs["candidate_bc"] = torch.zeros((K, 2 * N, 9), **f32)
-        self.crop_buf = torch.empty((2, K, int(capacity), 3), **f32)       # [0] the previous frame's crops, [1] the current one's
         # the frame's one upload: K motion jobs, then the K * 2N indices
-        jb = K * PU.MOTION_JOB.itemsize
-        self.stage_host = torch.zeros((jb + 8 * K * N,), dtype=torch.uint8).pin_memory()
-        self.stage = torch.zeros((jb + 8 * K * N,), dtype=torch.uint8, device=dev)
-        self.job_rec = self.stage_host.numpy()[:jb].view(PU.MOTION_JOB)
-        self.idx_rec = self.stage_host.numpy()[jb:].view(np.int32).reshape(K, 2 * N)
-        self.idx_ptr = self.stage.data_ptr() + jb
+        self._k_stage(PU.MOTION_JOB, K, 2 * int(self.point_sample_size))
 
     def _crops(self, pts):
         """the frame's one crop call + the count read-back -> (previous-frame counts (K), current-frame counts (K))"""
@@ -991,8 +1078,7 @@ class MultiMotionTracker(_KTargets, _DeviceTracker):
         PU.motion_input_multi(c.stage, K, N, c.canon_wlh, c.t == 1, c.inputs["points"],
                               c.inputs["candidate_bc"] if c.box_aware else False)
         est = c._network()
-        PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
-                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
+        c._offset_box(c.cur, est)
         return c._done(pts, (n_prev, n_this))
 
 
@@ -1002,11 +1088,6 @@ def _lane_sampling(name, who):
         raise ValueError("%s: sampling=%r draws its indices on the host, from counts that a lane tracker never reads back; "
                          "expected \"device\" or \"table\"" % (who, name))
     return name
-
-
-def _is_motion(model):
-    from .m2track import M2TRACK
-    return isinstance(model, M2TRACK)
 
 
 # ---- the test epoch on L lanes --------------------------------------------------------------------------
@@ -1093,8 +1174,9 @@ class _Lanes:
     (tracklet j owns rows [row0_j, row0_j + T_j)), runs lane_schedule, and from then on everything a step needs is host
     knowledge: per step the lane table (L, LANE_COLS) and one o3d_crop_plan group with one o3d_crop_target per (lane, cloud).
     They are built for plan_steps steps at a time in one host buffer (plan_lane_steps) and uploaded with ONE copy before the
-    chunk's first step; step() only launches.  A subclass provides _clouds() (its two crops per lane) and _launch() (the step
-    behind the crops), and tells _lane_state its reference rule: by_gt, back and crop_all of plan_lane_steps."""
+    chunk's first step; step() only launches: the step's crop groups, the family's _feed on the step's lane table, the box
+    update (_offset).  A subclass provides _clouds() (its two crops per lane) and tells _lane_state its reference rule: by_gt,
+    back and crop_all of plan_lane_steps."""
 
     def _lane_state(self, L, plan_steps, by_gt=False, back=0, crop_all=True):
         self.L, self.plan_steps, self._rule = L, int(plan_steps), (bool(by_gt), int(back), bool(crop_all))
@@ -1192,7 +1274,8 @@ class _Lanes:
         k = s % self.plan_steps
         with torch.cuda.device(self.dev):
             PU.crop_groups(self._plan_h[k, :self._groups[k]], self._tables.dev("plan", k), self.scratch)
-            self._launch(s, self._lane_rows[k])
+            lanes = self._lane_rows[k]
+            self._offset(lanes, self._feed(lanes, s & 1)[0])
             self.s = s + 1
             self._enter(self.s)
         return self.s < self.steps
@@ -1213,10 +1296,7 @@ class _Lanes:
     def set_box(self, lane, box):
         """Overwrite lane `lane`'s current box (teacher forcing in the tests): a device copy; its yaw state restarts from the
         box's rotation.  No result row changes."""
-        b = PU.pack_box(box, self.dev)
-        self.cur[lane].copy_(b)
-        self.yaw_state[lane, :9].copy_(b[6:15])
-        self.yaw_state[lane, 9] = 0.0
+        self._restart(PU.pack_box(box, self.dev), lane, row=False)
 
     def _rows(self, j):
         return slice(int(self.row0[j]), int(self.row0[j + 1]))
@@ -1234,9 +1314,7 @@ class _Lanes:
         its first box against itself, as the reference does); metrics: a SuccessPrecision that the same launch adds to.
         -> (overlaps (R), distances (R)) device tensors; no sync."""
         from . import metrics as MT
-        cfg = self.model.config
-        return MT.score_boxes(self.gt, self.boxes, int(getattr(cfg, "IoU_space", 3)), tuple(getattr(cfg, "up_axis", (0, 0, 1))),
-                              accumulate=metrics)
+        return MT.score_boxes(self.gt, self.boxes, *_score_space(self.model.config), accumulate=metrics)
 
 
 class LaneTracker(_Lanes, _MatchingTracker):
@@ -1261,30 +1339,16 @@ class LaneTracker(_Lanes, _MatchingTracker):
     def __init__(self, model, lanes, seed=0, use_graph=None, search_capacity=32768, model_capacity=8192, bank_capacity=None,
                  record_indices=False, plan_steps=256, sampling="device"):
         _lane_sampling(sampling, self._NAME)
-        if _is_motion(model):
-            raise TypeError("LaneTracker serves the matching trackers (BAT, P2B); the motion tracker runs on MotionLaneTracker")
+        _require_family(model, False, "LaneTracker")
         L = _KTargets._n_targets(lanes)
         super().__init__(model, seed, use_graph, 1, search_capacity, model_capacity, L, sampling, record_indices, bank_capacity)
-        self._lane_state(L, plan_steps, self.needs_ref_box, 1 if "PREVIOUS_GT" in str(self.reference_BB).upper() else 0,
-                         self.aggregation != "first")
-        self._states = self._parity_states()               # by step parity
-        self._model_counts = self.counts_dev[1:]
+        self._lane_state(L, plan_steps, *_reference_rule(self.reference_BB), self.aggregation != "first")
 
     def _clouds(self):
         """the clouds of plan_lane_steps: the search window of frame t, the model crop of frame t - 1 where the bank takes one"""
         c = self
         return ((0, True, c.search_bb_scale, c.search_bb_offset, PU.CROP_SUBWINDOW, c.search_buf.data_ptr(), c.search_buf.shape[1], False),
                 (1, False, c.model_bb_scale, c.model_bb_offset, PU.CROP_MODEL, c.staging.data_ptr(), c.model_capacity, True))
-
-    def _launch(self, s, lanes):
-        c = self
-        state_in, state_out, totals = c._states[s & 1]
-        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
-        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
-                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
-        c._boxcloud()
-        best, _ = c._network()
-        c._offset(lanes, best)
 
     def overflow(self):
         """-> (truncated search crops, truncated model crops, frames on which a bank was full) over all tracklets, on the host
@@ -1295,7 +1359,7 @@ class LaneTracker(_Lanes, _MatchingTracker):
         return tuple(int(sum(p[i] for p in per)) for i in range(3))
 
 
-class MotionLaneTracker(_Lanes, _DeviceTracker):
+class MotionLaneTracker(_Lanes, _MotionTracker):
     """The test epoch of the motion tracker (m2track.M2TRACK) on L lanes: MotionSequenceTracker's free-running loop, L
     tracklets wide.  The surface is LaneTracker's.  Per step: o3d_track_crop_groups (3 launches: the previous and the current
     frame of every busy lane by its last result box), o3d_track_motion_input_drawn_lanes, the batch-L network as one replayed
@@ -1306,39 +1370,14 @@ class MotionLaneTracker(_Lanes, _DeviceTracker):
 
     def __init__(self, model, lanes, seed=0, use_graph=None, capacity=32768, record_indices=False, plan_steps=256, sampling="device"):
         _lane_sampling(sampling, self._NAME)
-        if not _is_motion(model):
-            raise TypeError("MotionLaneTracker serves the motion tracker (M2TRACK); the matching trackers run on LaneTracker")
+        _require_family(model, True, "MotionLaneTracker")
         L = _KTargets._n_targets(lanes)
-        if int(capacity) < 1:
-            raise ValueError("capacity must be positive")
-        super().__init__(model, seed, use_graph, 1, _MOTION_DEFAULTS, L, sampling, record_indices)
-        self._motion_buffers(L, capacity)
+        super().__init__(model, seed, use_graph, 1, capacity, L, sampling, record_indices)
         self._lane_state(L, plan_steps)
-
-    def _motion_buffers(self, L, capacity):
-        """the buffers of the free-running motion loop with a leading axis (MotionLaneTracker, MotionSceneTracker)"""
-        dev, N = self.dev, int(self.point_sample_size)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.box_aware = bool(getattr(self.model, "box_aware", False))
-        self.inputs = {"points": torch.zeros((L, 2 * N, 5), **f32)}
-        if self.box_aware:
-            self.inputs["candidate_bc"] = torch.zeros((L, 2 * N, 9), **f32)
-        self.crop_buf = torch.empty((2, L, int(capacity), 3), **f32)       # [0] the previous frame's crops, [1] the current one's
-        self._crops = (self.crop_buf[0], self.crop_buf[1])
-        self.used = torch.full((L, 2 * N), -1, dtype=torch.int32, device=dev) if self.record_indices else None
-        if self.tabled:
-            self.table = draw_table(int(capacity), N, dev)
-        self.draw_src = self.table if self.tabled else self.keys      # PU.motion_input_drawn_lanes' source
 
     def _clouds(self):
         c, cap = self, self.crop_buf.shape[2]
         return tuple((1 - h, True, c.bb_scale, c.bb_offset, PU.CROP_SUBWINDOW, c.crop_buf[h].data_ptr(), cap, False) for h in (0, 1))
-
-    def _launch(self, s, lanes):
-        c = self
-        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.draw_src, c.canon_wlh, lanes, c.inputs["points"],
-                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
-        c._offset(lanes, c._network())
 
     def overflow(self):
         """-> (truncated previous-frame crops, truncated current-frame crops, 0) over all tracklets (one sync)"""
@@ -1396,10 +1435,12 @@ class _Scene(_KTargets):
                               events only (the first frame, the frame after a `first`, the frame after an enroll())
       enroll                  a slot takes a NEW object from the most recent frame, with device writes only
       the counts log          counts_log (T,K,2), row t written by stream-ordered device copies
+      the frame               _update, written once for both families: what differs is the family's (_MatchingTracker /
+                              _MotionTracker: _crop_groups, _FRAME_GROUP, _GATED, _feed) and SceneTracker's _reference
       overflow                per slot, from the slot's own start frame"""
 
     def _scene_state(self, K, groups):
-        """groups: per crop group (boxes (K,15), scale, offset, mode, out (K,capacity,3)); group g counts into column g"""
+        """groups: the family's _crop_groups; group g counts into column g"""
         self._k_state(K)
         self.counts2 = self.counts_dev.view(K, 2)
         kk = np.arange(K, dtype=np.uint64)
@@ -1411,7 +1452,7 @@ class _Scene(_KTargets):
         self.crop_tab.copy_(self.crop_tab_host)                            # the one upload of the table
         self.lanes = torch.zeros((K, PU.LANE_COLS), dtype=torch.int32, device=self.dev)
         self.lane_uploads = 0
-        self._pending, self._on_device, self._has_crop = set(), None, np.zeros((K,), bool)
+        self._pending, self._on_device, self._cropped = set(), None, True
         self._start = np.zeros((K,), np.int64)
 
     def init(self, points0, boxes0):
@@ -1444,25 +1485,50 @@ class _Scene(_KTargets):
         self._start[k] = self.t - 1
 
     def _lane_event(self):
-        """the lane table of this frame, uploaded only where it differs from the one on the device -> (lanes, has_crop (K,) on
-        the host)"""
+        """the lane table of this frame, uploaded only where it differs from the one on the device -> (lanes, the slots with
+        has_crop, on the host: True = every slot, else their list)"""
         first = frozenset(self._pending)
         if first != self._on_device:
-            rows = scene_lane_rows(self.K, first, getattr(self, "aggregation", None))
+            rows = scene_lane_rows(self.K, first, self.aggregation)
             self.lanes.copy_(torch.from_numpy(rows).pin_memory(), non_blocking=True)
-            self._on_device, self._has_crop = first, rows[:, PU.LANE["has_crop"]] != 0
+            cropped = np.flatnonzero(rows[:, PU.LANE["has_crop"]]).tolist()
+            self._on_device, self._cropped = first, True if len(cropped) == self.K else cropped
             self.lane_uploads += 1
-        return self.lanes, self._has_crop
+        return self.lanes, self._cropped
 
     def _crop_scene(self, clouds):
         """the frame's one o3d_track_crop_multi call: clouds[g] | None = the points of group g of the fixed table"""
         self.scratch = PU.crop_multi([(pts, self._groups[g]) for g, pts in enumerate(clouds) if pts is not None], self.scratch)
         self.crop_calls += 1
 
+    # ---- one frame ---------------------------------------------------------------------------------------------------------
+    ref = None                # SceneTracker: its own (K,15) buffer, which the fixed table points at and _reference fills
+    _ALL_MADE = (True, True)  # _log_scene_counts' `made` of a frame that makes both groups for every slot
+
+    def _update(self, pts, ref_boxes=None):
+        """The frame of a live scene, whichever family: the reference boxes (the last ones where the class keeps no `ref`), the
+        lane table (uploaded on an event only), the one crop call, the counts log, the family's _feed, the one box update."""
+        c = self
+        c._grow_boxes()
+        ref = c.cur if c.ref is None else c._reference(ref_boxes)
+        lanes, cropped = c._lane_event()
+        clouds, made, g = [c.prev_points, c.prev_points], c._ALL_MADE, c._GATED
+        clouds[c._FRAME_GROUP] = pts
+        if cropped is not True and g is not None:          # the family's gated group: made for the slots in `cropped` only
+            made = [True, True]
+            made[g] = cropped
+            if not cropped:
+                clouds[g] = None
+        c._crop_scene(clouds)
+        c._log_scene_counts(made)
+        offsets, state_out = c._feed(lanes, c.t & 1)
+        c._offset_box(ref, offsets, c.rebase_all if ref_boxes is not None else None)
+        return c._frame_done(pts, state_out)
+
     def _log_scene_counts(self, made):
         """row t of the counts log: column g of every slot where made[g] is True, of the slots made[g] lists otherwise"""
         row = self.counts_log[self.t]
-        if all(m is True for m in made):
+        if made is self._ALL_MADE or all(m is True for m in made):
             row.copy_(self.counts2)
             return
         for g, m in enumerate(made):
@@ -1472,7 +1538,7 @@ class _Scene(_KTargets):
                 for k in m:
                     row[k, g:g + 1].copy_(self.counts2[k, g:g + 1])
 
-    def _frame_done(self, pts):
+    def _frame_done(self, pts, state_out):
         self._pending.clear()
         return self._done(pts, None)
 
@@ -1523,52 +1589,32 @@ class SceneTracker(_Scene, _MatchingTracker):
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, search_capacity=32768, model_capacity=8192,
                  bank_capacity=None, sampling="device", record_indices=False):
         _scene_sampling(sampling, self._NAME)
-        if _is_motion(model):
-            raise TypeError("SceneTracker serves the matching trackers (BAT, P2B); the motion tracker follows the K targets of "
-                            "a live scene with MotionSceneTracker")
+        _require_family(model, False, "SceneTracker")
         K = self._n_targets(n_targets)
         super().__init__(model, seed, use_graph, max_frames, search_capacity, model_capacity, K, sampling, record_indices,
                          bank_capacity)
         self.ref = torch.zeros((K, 15), dtype=torch.float32, device=self.dev)
         self.rebase_all = torch.ones((K,), dtype=torch.int32, device=self.dev)
-        self._scene_state(K, [(self.ref, self.search_bb_scale, self.search_bb_offset, PU.CROP_SUBWINDOW, self.search_buf),
-                              (self.cur, self.model_bb_scale, self.model_bb_offset, PU.CROP_MODEL, self.staging)])
-        self._states = self._parity_states()
-        self._model_counts = self.counts_dev[1:]
+        self._scene_state(K, self._crop_groups(self.ref))
 
     def update(self, points, ref_boxes=None):
         return self._run(points, ref_boxes)
 
-    def _update(self, pts, ref_boxes):
+    def _reference(self, ref_boxes):
+        """a device copy into ref (K,15), which the fixed table points at: the last boxes, or the caller's"""
         c = self
-        c._grow_boxes()
-        if ref_boxes is None:
-            c.ref.copy_(c.cur)
-        else:
-            c.ref.copy_(c._pack(ref_boxes))
+        c.ref.copy_(c.cur if ref_boxes is None else c._pack(ref_boxes))
+        if ref_boxes is not None:
             for k in sorted(c.retired):                    # a retired target's reference is its own last box, not the caller's
                 c.ref[k].copy_(c.cur[k])
-        lanes, has_crop = c._lane_event()
-        cropped = np.flatnonzero(has_crop).tolist()
-        c._crop_scene([pts, c.prev_points if cropped else None])
-        c._log_scene_counts([True, True if len(cropped) == c.K else cropped])
-        state_in, state_out, totals = c._states[c.t & 1]
-        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, lanes, state_in, state_out)
-        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
-                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
-        c._boxcloud()
-        best, _ = c._network()
-        PU.offset_box_multi(c.ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame,
-                            rebase=c.rebase_all if ref_boxes is not None else None, active=c.active, degrees=c.degrees,
-                            use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
-        return c._frame_done(pts)
+        return c.ref
 
     def _overflow_rows(self, log):
         return scene_matching_overflow(log, self._start, self.search_buf.shape[1], self.model_capacity, self.bank_capacity,
                                        self.aggregation)
 
 
-class MotionSceneTracker(_Scene, _DeviceTracker):
+class MotionSceneTracker(_Scene, _MotionTracker):
     """K targets of one live scene, free-running, for the motion tracker (m2track.M2TRACK): MultiMotionTracker's loop without
     its host stop.  The surface is SceneTracker's (no ref_boxes: the motion tracker always starts from its last result).  Per
     frame: o3d_track_crop_multi, one call on the fixed table (group 0: frame t-1, group 1: frame t, both against the last
@@ -1581,31 +1627,13 @@ class MotionSceneTracker(_Scene, _DeviceTracker):
     def __init__(self, model, n_targets, seed=0, use_graph=None, max_frames=1024, capacity=32768, sampling="device",
                  record_indices=False):
         _scene_sampling(sampling, self._NAME)
-        if not _is_motion(model):
-            raise TypeError("MotionSceneTracker serves the motion tracker (M2TRACK); the matching trackers (BAT, P2B) follow "
-                            "the K targets of a live scene with SceneTracker")
+        _require_family(model, True, "MotionSceneTracker")
         K = self._n_targets(n_targets)
-        if int(capacity) < 1:
-            raise ValueError("capacity must be positive")
-        super().__init__(model, seed, use_graph, max_frames, _MOTION_DEFAULTS, K, sampling, record_indices)
-        MotionLaneTracker._motion_buffers(self, K, capacity)
-        self._scene_state(K, [(self.cur, self.bb_scale, self.bb_offset, PU.CROP_SUBWINDOW, self.crop_buf[h]) for h in (0, 1)])
+        super().__init__(model, seed, use_graph, max_frames, capacity, K, sampling, record_indices)
+        self._scene_state(K, self._crop_groups(self.cur))
 
     def update(self, points):
         return self._run(points)
-
-    def _update(self, pts):
-        c = self
-        c._grow_boxes()
-        lanes, _ = c._lane_event()
-        c._crop_scene([c.prev_points, pts])
-        c._log_scene_counts([True, True])
-        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.draw_src, c.canon_wlh, lanes, c.inputs["points"],
-                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
-        est = c._network()
-        PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
-                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
-        return c._frame_done(pts)
 
     def _overflow_rows(self, log):
         return scene_motion_overflow(log, self._start, self.crop_buf.shape[2])
@@ -1627,8 +1655,9 @@ class _Managed:
     """What ManagedSceneTracker and ManagedMotionSceneTracker put on top of a scene tracker: per frame, after the box update, two
     launches (o3d_scene_pair_scores, o3d_scene_manage) that match the frame's detections with the K tracks, count missed frames
     and starved crops, retire the lost slots, enroll the unmatched detections into the free slots with SceneTracker.enroll's
-    writes, and write the NEXT frame's lane table.  The lane table therefore belongs to the device (no _pending, no _lane_event
-    upload) and both crop groups are made on every frame, because the host no longer knows which slot is `first`.
+    writes, and write the NEXT frame's lane table.  The frame is _Scene._update with three differences, each one override here:
+    the lane table belongs to the device (_lane_event uploads nothing, no _pending), both crop groups are made on every frame,
+    because the host no longer knows which slot is `first`, and _frame_done runs _manage by the family's _FRAME_GROUP / aggregation.
 
       slot (K,4) int32        {id, misses, starved, start} per slot, id -1 = free; `active` stays id >= 0
       next_id (1,) int32      the next track id
@@ -1654,9 +1683,8 @@ class _Managed:
         self.manage = dict(min_iou=float(p["min_iou"]), max_dist=float(p["max_dist"]), max_misses=int(p["max_misses"]),
                            min_points=int(p["min_points"]), max_starved=int(p["max_starved"]), enroll=bool(p["enroll"]),
                            assignment=p["assignment"], cost=p["cost"])
-        cfg = self.model.config
-        self.score_dim = int(getattr(cfg, "IoU_space", 3))
-        self.score_up = MT.up_index(tuple(getattr(cfg, "up_axis", (0, 0, 1))))
+        self.score_dim, self._up_axis = _score_space(self.model.config)
+        self.score_up = MT.up_index(self._up_axis)
         K, T, i32 = self.K, self.boxes.shape[0], dict(dtype=torch.int32, device=self.dev)
         self.slot = torch.zeros((K, PU.SCENE_SLOT_COLS), **i32)
         self.next_id = torch.zeros((1,), **i32)
@@ -1668,10 +1696,7 @@ class _Managed:
 
     def init(self, points0, boxes0):
         """n0 <= K boxes: slot k < n0 follows boxes0[k] with id k; the other slots are free and hold the unit box."""
-        if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray):
-            b = PU._dev32(boxes0, self.dev).reshape(-1, 15)
-        else:
-            b = torch.stack([PU.pack_box(x, self.dev) for x in boxes0]) if len(boxes0) else torch.zeros((0, 15), device=self.dev)
+        b = _boxes15(boxes0, self.dev)
         n0, K = b.shape[0], self.K
         if n0 > K:
             raise ValueError("%d boxes for %d slots" % (n0, K))
@@ -1689,7 +1714,7 @@ class _Managed:
         self.match_log.fill_(-1)
         self.dropped_log.zero_()
         self.ids_log[0].copy_(self.slot[:, 0])
-        self.lanes.copy_(torch.from_numpy(scene_lane_rows(K, np.flatnonzero(occupied).tolist(), getattr(self, "aggregation", None))))
+        self.lanes.copy_(torch.from_numpy(scene_lane_rows(K, np.flatnonzero(occupied).tolist(), self.aggregation)))
         return boxes
 
     def _grow_boxes(self):
@@ -1708,39 +1733,46 @@ class _Managed:
         keeps the frame free of host stops; a host array or a list of boxes travels as one asynchronous copy from pinned
         memory.  n_detections: None (= D), an int, or a device int32 (1,) tensor: the first n_detections rows count.
         -> a (K,15) device VIEW of the boxes after the frame, the enrolled ones included."""
-        if ref_boxes is not None:
+        if ref_boxes is not None:                          # in front of the detections' checks, and those in front of _run's
             raise ValueError("%s.update takes no ref_boxes: a managed tracker starts every slot from its own last box" % self._NAME)
-        dets = self._detections(detections)
-        PU._need_gpu(points, self._NAME + ".update")
-        if self.t < 1:
-            raise RuntimeError(self._NAME + ".update before init")
-        with torch.cuda.device(self.dev):
-            if dets is not None and not dets.is_cuda:
-                dets = dets.pin_memory().to(self.dev, non_blocking=True)
-            n_det = self.n_det
-            if dets is not None and torch.is_tensor(n_detections):
-                PU._i32(n_detections, 1, self._NAME + ".update")
-                n_det = n_detections
-            elif dets is not None:
-                n_det.fill_(dets.shape[0] if n_detections is None else int(n_detections))
-            return self._update(points.contiguous().float(), dets, n_det)
+        return self._run(points, self._detections(detections), n_detections)
+
+    def _check(self, dets, n_detections):
+        """nothing is left for _run to check: update() has refused ref_boxes, which the parent's _check would ask for"""
 
     def _detections(self, detections):
         """the checks of update()'s detection set, before anything touches the device -> a (D,15) float32 tensor | None"""
         if detections is None:
             return None
-        if torch.is_tensor(detections):
-            d = detections.to(torch.float32).reshape(-1, 15).contiguous()
-        elif isinstance(detections, np.ndarray):
-            d = torch.from_numpy(np.ascontiguousarray(detections, dtype=np.float32).reshape(-1, 15))
-        else:
-            d = torch.stack([PU.pack_box(x, "cpu") for x in detections]) if len(detections) else torch.zeros((0, 15))
+        d = _boxes15(detections, "cpu", keep=True)
         if d.shape[0] > self.max_detections:
             raise ValueError("%s.update: %d detections for max_detections = %d" % (self._NAME, d.shape[0], self.max_detections))
         return d
 
+    def _update(self, pts, dets, n_detections):
+        """the detections onto the device (_dets: what _frame_done hands to _manage), then the scene tracker's frame"""
+        if dets is not None and not dets.is_cuda:
+            dets = dets.pin_memory().to(self.dev, non_blocking=True)
+        n_det = self.n_det
+        if dets is not None and torch.is_tensor(n_detections):
+            PU._i32(n_detections, 1, self._NAME + ".update")
+            n_det = n_detections
+        elif dets is not None:
+            n_det.fill_(dets.shape[0] if n_detections is None else int(n_detections))
+        self._dets = (dets, n_det)
+        return super()._update(pts)
+
+    def _lane_event(self):
+        """the lane table is the device's (o3d_scene_manage writes the next frame's): no upload, every group for every slot"""
+        return self.lanes, True
+
+    def _frame_done(self, pts, state_out):
+        """the family's rule: a slot starves on the count of its crop of the frame; its bank restarts in state_out (None: no bank)"""
+        self._manage(*self._dets, self._FRAME_GROUP, state_out, self.aggregation)
+        return self._done(pts, None)
+
     def _manage(self, dets, n_det, count_col, bank_state_next, rule):
-        """the two management launches of a frame, after its offset_box_multi"""
+        """the two management launches of a frame, after its box update"""
         has = dets is not None
         if not has:
             dets = self._no_dets
@@ -1806,8 +1838,7 @@ class _Managed:
         if valid is not None:
             valid = torch.as_tensor(valid).to(self.dev)
         if metrics is None:
-            cfg = self.model.config
-            metrics = MT.ClearMOT(gt.shape[1], self.dev, dim=self.score_dim, up_axis=tuple(getattr(cfg, "up_axis", (0, 0, 1))), **gates)
+            metrics = MT.ClearMOT(gt.shape[1], self.dev, dim=self.score_dim, up_axis=self._up_axis, **gates)
         elif gates:
             raise ValueError("%s.score_mot: the gates %s belong to the ClearMOT that is passed" % (self._NAME, sorted(gates)))
         elif (metrics.dim, metrics.up) != (self.score_dim, self.score_up):
@@ -1841,23 +1872,6 @@ class ManagedSceneTracker(_Managed, SceneTracker):
                              % (self._NAME, self.reference_BB))
         self._managed_state(manage)
 
-    def _update(self, pts, dets, n_det):
-        c = self
-        c._grow_boxes()
-        c.ref.copy_(c.cur)
-        c._crop_scene([pts, c.prev_points])
-        c._log_scene_counts([True, True])
-        state_in, state_out, totals = c._states[c.t & 1]
-        PU.bank_update_lanes(c.staging, c._model_counts, 2, c.bank, c.aggregation, c.lanes, state_in, state_out)
-        PU.resample_drawn_lanes([(c.bank, totals, 2, c.draw_src[0], c.inputs["template_points"], c.used_t),
-                                 (c.search_buf, c.counts_dev, 2, c.draw_src[1], c.inputs["search_points"], c.used_s)])
-        c._boxcloud()
-        best, _ = c._network()
-        PU.offset_box_multi(c.ref, best, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
-                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
-        c._manage(dets, n_det, 0, state_out, c.aggregation)        # state_out: what the next frame reads as state_in
-        return c._done(pts, None)
-
     def _overflow_rows(self, log):
         if self.aggregation == "first":        # the model crop is made on every frame, but banked on a slot's first frame only
             log = log.copy()
@@ -1874,19 +1888,6 @@ class ManagedMotionSceneTracker(_Managed, MotionSceneTracker):
     def __init__(self, model, n_targets, manage=None, **kw):
         super().__init__(model, n_targets, **kw)
         self._managed_state(manage)
-
-    def _update(self, pts, dets, n_det):
-        c = self
-        c._grow_boxes()
-        c._crop_scene([c.prev_points, pts])
-        c._log_scene_counts([True, True])
-        PU.motion_input_drawn_lanes(c._crops[0], c._crops[1], c.counts2, c.draw_src, c.canon_wlh, c.lanes, c.inputs["points"],
-                                    c.inputs["candidate_bc"] if c.box_aware else False, c.used)
-        est = c._network()
-        PU.offset_box_multi(c.cur, est, yaw_state=c.yaw_state, out=c.cur, results=c.boxes, frame=c.frame, active=c.active,
-                            degrees=c.degrees, use_z=c.use_z, limit_box=c.limit_box, seed=c.seed)
-        c._manage(dets, n_det, 1, None, None)
-        return c._done(pts, None)
 
 
 def tracker_for(model, **kw):
@@ -1922,15 +1923,30 @@ def track_sequence(model, frames, box0, ref_boxes=None, seed=0, use_graph=None, 
     "table" (the free-running loop on the reference's draw, read from a device table).
     -> (T,15) result boxes on the host."""
     trk = tracker_for(model, seed=seed, use_graph=use_graph, sampling=sampling)
-    if isinstance(trk, MotionSequenceTracker) and ref_boxes is not None:
+    _drive(trk, frames, box0, ref_boxes)
+    return trk.results()
+
+
+def _drive(trk, frames, box0, refs=None, retire=None, by_rule=False):
+    """The frame loop of every convenience function: trk.init(frames[0], box0), then one update() per frame, with refs[t] where
+    refs is given.  by_rule: refs is the ground truth and the tracker's reference_BB decides (generate_search_area,
+    models/base_model.py:208-214): nothing under previous_result (and for a motion tracker), refs[t - 1] under previous_gt,
+    refs[t] under current_gt.  retire (T,K) bool on the host | None: a target is retired in front of its first False frame."""
+    back = 0
+    if by_rule:
+        by_gt, back = _reference_rule(trk.reference_BB) if hasattr(trk, "reference_BB") else (False, 0)
+        refs = refs if by_gt else None
+    elif refs is not None and isinstance(trk, _MotionTracker):
         raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
     trk.init(frames[0], box0)
     for t in range(1, len(frames)):
-        if ref_boxes is None:
+        if retire is not None:
+            for k in np.flatnonzero(retire[t - 1] & ~retire[t]):
+                trk.retire(int(k))
+        if refs is None:
             trk.update(frames[t])
         else:
-            trk.update(frames[t], ref_boxes[t])
-    return trk.results()
+            trk.update(frames[t], refs[t - back])
 
 
 def track_targets(model, frames, boxes0, ref_boxes=None, seed=0, use_graph=None, sampling="reference"):
@@ -1944,14 +1960,7 @@ def _track_k(make, model, frames, boxes0, ref_boxes, **kw):
     """the loop of track_targets / track_scene on make(model, K, **kw)"""
     b0 = boxes0 if torch.is_tensor(boxes0) or isinstance(boxes0, np.ndarray) else list(boxes0)
     trk = make(model, len(b0), **kw)
-    if isinstance(trk, (MultiMotionTracker, MotionSceneTracker)) and ref_boxes is not None:
-        raise ValueError("the motion tracker always starts from its previous result: ref_boxes is not supported")
-    trk.init(frames[0], b0)
-    for t in range(1, len(frames)):
-        if ref_boxes is None:
-            trk.update(frames[t])
-        else:
-            trk.update(frames[t], ref_boxes[t])
+    _drive(trk, frames, b0, ref_boxes)
     return trk.results()
 
 
@@ -1970,14 +1979,7 @@ def _track_with_gt(trk, frames, gt):
     tracker's device."""
     if len(frames) != gt.shape[0]:
         raise ValueError("%d frames, %d ground-truth boxes" % (len(frames), gt.shape[0]))
-    trk.init(frames[0], gt[0])
-    by_gt = getattr(trk, "needs_ref_box", False)
-    back = 1 if by_gt and "PREVIOUS_GT" in str(trk.reference_BB).upper() else 0
-    for t in range(1, len(frames)):
-        if by_gt:
-            trk.update(frames[t], gt[t - back])
-        else:
-            trk.update(frames[t])
+    _drive(trk, frames, gt[0], gt, by_rule=True)
 
 
 def evaluate_sequence(model, frames, gt_boxes, seed=0, use_graph=None, tracker=None, metrics=None, sampling="reference"):
@@ -2026,11 +2028,11 @@ def evaluate_managed_scene(model, frames, gt_boxes, valid=None, detections=None,
     gates of `mot` for the metric; the two are chosen independently.
     No host stop per frame.  -> (the ClearMOT's compute() dict, the tracker)."""
     _scene_sampling(sampling, "evaluate_managed_scene")
-    gt_host = np.ascontiguousarray(gt_boxes.detach().cpu().numpy() if torch.is_tensor(gt_boxes) else gt_boxes, dtype=np.float32)
+    gt_host = np.ascontiguousarray(_host(gt_boxes), dtype=np.float32)
     if gt_host.ndim != 3 or gt_host.shape[2] != 15 or gt_host.shape[0] != len(frames):
         raise ValueError("gt_boxes %s for %d frames" % (gt_host.shape, len(frames)))
     T, G = gt_host.shape[:2]
-    live = np.ones((T, G), bool) if valid is None else np.asarray(valid.detach().cpu().numpy() if torch.is_tensor(valid) else valid) != 0
+    live = np.ones((T, G), bool) if valid is None else np.asarray(_host(valid)) != 0
     if live.shape != (T, G):
         raise ValueError("valid must be (T,G) = %s" % ((T, G),))
     if detections is None:
@@ -2046,8 +2048,7 @@ def evaluate_managed_scene(model, frames, gt_boxes, valid=None, detections=None,
     if n_detections is None:
         n_det = torch.full((T,), dets.shape[1], dtype=torch.int32, device=dev)
     else:
-        n_det = torch.as_tensor(np.asarray(n_detections.detach().cpu().numpy() if torch.is_tensor(n_detections) else n_detections,
-                                           dtype=np.int32)).to(dev)
+        n_det = torch.as_tensor(np.asarray(_host(n_detections), dtype=np.int32)).to(dev)
     gt, live_dev = torch.from_numpy(gt_host).to(dev), torch.from_numpy(live.astype(np.int32)).to(dev)
     trk.init(frames[0], gt_host[0][live[0]])
     for t in range(1, T):
@@ -2066,21 +2067,11 @@ def _evaluate_k(trk, frames, gt_boxes, valid, metrics):
         raise ValueError("%d frames, %d ground-truth boxes" % (len(frames), gt.shape[0]))
     live = None
     if valid is not None:
-        live = np.asarray(valid.detach().cpu().numpy() if torch.is_tensor(valid) else valid) != 0
+        live = np.asarray(_host(valid)) != 0
         if live.shape != (gt.shape[0], trk.K) or not live[0].all():
             raise ValueError("valid must be (T,K) with every target annotated in frame 0")
         live = np.logical_and.accumulate(live, axis=0)
-    trk.init(frames[0], gt[0])
-    by_gt = getattr(trk, "needs_ref_box", False)
-    back = 1 if by_gt and "PREVIOUS_GT" in str(trk.reference_BB).upper() else 0
-    for t in range(1, len(frames)):
-        if live is not None:
-            for k in np.flatnonzero(live[t - 1] & ~live[t]):
-                trk.retire(int(k))
-        if by_gt:
-            trk.update(frames[t], gt[t - back])
-        else:
-            trk.update(frames[t])
+    _drive(trk, frames, gt[0], gt, retire=live, by_rule=True)
     ious, distances = trk.score(gt, valid=live, metrics=metrics)
     return ious, distances, trk.boxes[:trk.t]
 
